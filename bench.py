@@ -20,8 +20,6 @@ import time
 
 import numpy as np
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # the library's default (csrc/capi.hip ctx_init); torch initialises HIP first in this process
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 T_PROCESS_START = time.time()
 if ROOT not in sys.path:
@@ -35,6 +33,7 @@ MSM_BYTES_PER_POINT = 96       # 64 B base + 32 B scalar, each
 NTT_BYTES_PER_ELEM = 64        # read once + write once
 CLOCK_WARMUP_MSM = 150         # untimed steps before the contract's --warmup steps (an idle MI355X sits at ~600 MHz): reported as clock_warmup_steps
 CLOCK_WARMUP_NTT = 200
+NTT_DUMP_SAMPLE = 1 << 18      # --dump-outputs: rows of the 2^22-element NTT output kept (16 MB as float64 words; the whole column would be 256 MB)
 
 
 def rand_fr(rng, n):
@@ -72,6 +71,9 @@ def main():
     ap.add_argument("--with-batch", action="store_true", help="also time the pipelined 4-column batch commit (extra.msm_batch4_*)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for 1-GPU plumbing tests)")
     ap.add_argument("--share-device", action="store_true", help="testing only: every rank uses GPU 0")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="rank 0 writes what the last timed step of each region returned to DIR/<name>.npy "
+                    "(float64; every 254-bit value as its eight 32-bit little-endian words, exact): msm_result (2, 8) = the affine point x, y; "
+                    "ntt_sample (%d, 8) = a fixed, seeded sample of the transformed column, rows in ascending index order" % NTT_DUMP_SAMPLE)
     args = ap.parse_args()
 
     import torch
@@ -237,6 +239,10 @@ def main():
     barrier_sync()
     t_ntt = time.perf_counter() - t0
     os.environ.pop("EZKL_HIP_TIMING", None)
+    if args.dump_outputs and rank == 0:                 # before the steps below transform the column again
+        idx = np.sort(np.random.default_rng(SEED + 1).choice(n_ntt, NTT_DUMP_SAMPLE, replace=False))
+        dump_outputs(args.dump_outputs, {"msm_result": _words(result).reshape(2, 8),
+                                         "ntt_sample": _words(col.to_numpy(shape=(n_ntt, 4))[idx])})
     for _ in range(max(5, args.steps // 2)):            # the same transforms with their event pair (HIP events around the three passes)
         ntt_step()
     barrier_sync()
@@ -578,6 +584,25 @@ def emit(full):
         os.write(_LINE_FD, (line + "\n").encode())
     else:
         print(line, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _words(limbs):
+    """u64 limbs -> their 32-bit little-endian words as float64 (exact: every word is below 2^53); the last axis doubles"""
+    a = np.ascontiguousarray(limbs, np.uint64)
+    return a.view("<u4").reshape(a.shape[:-1] + (2 * a.shape[-1],)).astype(np.float64)
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: DIR/<name>.npy per array, so that two builds can be compared output for output on the same seeded inputs"""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def strong_scaling(world, rank, dist, dev, B, D, torch, args, barrier_sync):

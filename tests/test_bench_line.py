@@ -92,3 +92,17 @@ def test_multi_rank_line_carries_the_three_sharded_proofs():
     full["prove"]["transformer_k22"] = {"error": "z" * 3000}
     line = json.loads(bench.compact_line(full))
     assert len(line["prove_multi"]["transformer_k22"]["error"]) == 200 and len(bench.compact_line(full)) < bench.LINE_LIMIT
+
+
+def test_dump_outputs_words_are_exact_and_bounded(tmp_path):
+    """--dump-outputs: every 254-bit value leaves as its 32-bit words in float64, bit-exact; a dump over the size limit is refused"""
+    import numpy as np
+    rng = np.random.default_rng(1)
+    limbs = rng.integers(0, 1 << 63, size=(5, 4), dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    bench.dump_outputs(str(tmp_path / "out"), {"a": bench._words(limbs)})
+    back = np.load(tmp_path / "out" / "a.npy")
+    assert back.dtype == np.float64 and back.shape == (5, 8)
+    assert (np.ascontiguousarray(back.astype(np.uint64).astype(np.uint32)).view(np.uint64).reshape(5, 4) == limbs).all()
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"b": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
+    assert not (tmp_path / "big").exists()

@@ -5,9 +5,6 @@ import pytest
 from conftest import GOLDEN, fe_from_int
 from ezkl_amd import codecs
 
-REF_ASSETS = "/root/reference/tests/assets"
-
-
 def test_srs_roundtrip_and_fields():
     buf = open(os.path.join(GOLDEN, "kzg_k6.srs"), "rb").read()
     srs = codecs.read_srs(buf)
@@ -46,17 +43,17 @@ def test_pk_roundtrip_synthetic():
         codecs.read_pk(buf, npm, ns + 1)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_ASSETS, "pk.key")), reason="reference assets only exist in the build container")
 def test_reference_pk_and_proof_files():
-    """the real artefacts of the reference parse to exactly EOF and agree with the golden subset"""
-    buf = open(os.path.join(REF_ASSETS, "pk.key"), "rb").read()
+    """the real artefacts of the reference (its pk.key and proof.json, stored under tests/golden) parse to exactly EOF and agree with the
+    golden subset"""
+    buf = open(os.path.join(GOLDEN, "pk_k6.key"), "rb").read()
     pk = codecs.read_pk(buf, n_perm=32, n_selectors=80)
     assert len(pk["fixed_values"]) == 38 and pk["l0"].shape == (512, 4) and len(pk["perm_cosets"]) == 32
     assert codecs.write_pk(pk) == buf
     g = np.load(os.path.join(GOLDEN, "pk_k6_subset.npz"))
     for j, idx in enumerate(g["fixed_idx"]):
         assert pk["fixed_cosets"][idx].tobytes() == g["fixed_cosets"][j].tobytes()
-    pr = codecs.read_proof_json(open(os.path.join(REF_ASSETS, "proof.json")).read())
+    pr = codecs.read_proof_json(open(os.path.join(GOLDEN, "proof_k6.json")).read())
     assert len(pr["proof"]) == 14816 and pr["transcript_type"] == "EVM"
     pts, ev, tail = codecs.split_evm_proof(pr["proof"], 114, 231)
     q = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47

@@ -4,7 +4,7 @@
 # tools/ab.sh <experiment> -- the A/B experiments of round 4 behind NOTEBOOK.md §4.1.3 / §4.3 (one script, one `run` helper; each line of
 # output is one setting: best proof times of REPS proofs, the stage times of the best one, the proof hash -- identical everywhere).
 #   bash tools/run.sh <tag> ab:<experiment>     on the GPU box; the log lands in gpurun_out/<tag>_ab_<experiment>.log
-# experiments: group (fused-group sizes, k = 20 MLP) | circuits (general-scalar groups across the bench circuits) | hwq (hardware queues)
+# experiments: group (fused-group sizes, k = 20 MLP) | circuits (general-scalar groups across the bench circuits)
 #   | prio (stream priorities) | evalh (sweep code generation) | merged (z committed under the lookup sums) | early (random polynomial
 #   committed under the witness upload x priorities) | matrix (early x groups, k = 20 / 22) | slots (batch slots x groups) | taper (upload
 #   phases in tapered groups) | benchvar (bench.py twice with 4 and 6 slots: box-to-box and run-to-run variation) | msmdebug (the batches
@@ -31,9 +31,6 @@ case "$1" in
       run "mlp17 BIG=$BIG" EZKL_MSM_GROUP_BIG=$BIG CIRCUIT=mlp K=17 REPS=6; run "conv17 BIG=$BIG" EZKL_MSM_GROUP_BIG=$BIG CIRCUIT=conv K=17 REPS=6
       run "mlp22 BIG=$BIG" EZKL_MSM_GROUP_BIG=$BIG CIRCUIT=mlp K=22 MLP_BLOCKS=5 MLP_FILL=25 REPS=3
     done ;;
-  hwq)
-    for Q in 4 8 12 16 24; do run "HWQ=$Q" $M GPU_MAX_HW_QUEUES=$Q; done
-    for Q in 12 16; do run "HWQ=$Q GROUP_BIG=1" $M GPU_MAX_HW_QUEUES=$Q EZKL_MSM_GROUP_BIG=1; done ;;
   prio)
     run "defaults" $M; run "LIB high" $M EZKL_HIP_PRIO_LIB=-1; run "AUX low" $M EZKL_HIP_PRIO_AUX=1
     run "LIB high AUX low" $M EZKL_HIP_PRIO_LIB=-1 EZKL_HIP_PRIO_AUX=1; run "LIB high MSM high AUX low" $M EZKL_HIP_PRIO_LIB=-1 EZKL_HIP_PRIO_MSM=-1 EZKL_HIP_PRIO_AUX=1

@@ -6,7 +6,6 @@
 Prints the group's proof time next to the one-context prover's, checks that the bytes are equal and that the product's verifier accepts."""
 import hashlib, json, os, sys, time
 import numpy as np
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 os.environ.pop("LOCAL_RANK", None)

@@ -11,7 +11,6 @@ all_gathered, evaluations travel as scalars and SHPLONK as two 64-byte folds.  E
 CIRCUIT: fixture (the reference's k = 6 circuit, tests/fixture_k6.py), mlp, einsum, conv (tools/bench_circuits.py)."""
 import hashlib, json, os, sys, time
 import numpy as np
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ezkl_amd

@@ -20,7 +20,7 @@
 #   multi2       two owner-mode ranks (gloo) sharing the device, k = 20 MLP          -> <tag>_multi2.json
 #   k22          K=22 MLP_BLOCKS=5 MLP_FILL=25 proof + HBM high-water (opt-in size)  -> <tag>_mlp_k22.log
 #   k22cold      the same with the cold one-shot (writes 68 GB of artefacts to /tmp) -> <tag>_mlp_k22_cold.log
-#   ab:<name>    an A/B experiment of tools/ab.sh (group, circuits, hwq, prio, evalh, ...)  -> <tag>_ab_<name>.log
+#   ab:<name>    an A/B experiment of tools/ab.sh (group, circuits, prio, evalh, ...)  -> <tag>_ab_<name>.log
 #   sh:<file>    bash tools/<file>                                                    -> <tag>_<file>.log
 #   tests:<a,b>  pytest -m gpu on the listed files                                  -> <tag>_pytest_subset.log
 #   py:<file>    python <file> (a probe under tools/)                                -> <tag>_<file>.log
