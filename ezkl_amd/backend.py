@@ -725,24 +725,41 @@ class GraphProgram:
             sub.code.append([op, target, *remap(t0, i0, r0), *remap(t1, i1, r1)])
         return sub, queries
 
-    def check_compiles(self, n_columns):
-        """host-only: lower the program to HIP source and compile it for gfx950 with hiprtc (no GPU needed)"""
+    def _host_program(self, n_columns, challenges):
+        """the program with null column pointers, for the host-only entry points.  Every entry point validates the whole program (operand
+        indices included): without `challenges`, as many zero challenges as the code reads are declared"""
         code, consts, rots = self.arrays()
         cols = (C.c_void_p * max(1, n_columns))()
-        ch = np.zeros((1, 4), np.uint64)
+        if challenges is None:
+            n_chal = 1 + max([int(ins[3 + 3 * q]) for ins in code.tolist() for q in (0, 1) if ins[2 + 3 * q] == CHALLENGE] + [0])
+            challenges = np.zeros((n_chal, 4), np.uint64)
+        ch = _fe(np.asarray(challenges, np.uint64).reshape(-1, 4))
         pr = _Prog(_p(code), code.shape[0], self.n_intermediates, _p(consts), consts.shape[0], _p(rots), rots.shape[0],
-                   C.cast(cols, _vp), n_columns, _p(ch), 1, self.k, self.ext_k)
+                   C.cast(cols, _vp), n_columns, _p(ch), ch.shape[0], self.k, self.ext_k)
+        return pr, (code, consts, rots, cols, ch)
+
+    def check_compiles(self, n_columns, challenges=None):
+        """host-only: lower the program to HIP source and compile it for gfx950 with hiprtc (no GPU needed).  With EZKL_HIP_JIT_DUMP=<file>
+        set, the library writes the source it compiles there (tools/evalh29_model.py reads it)"""
+        pr, keep = self._host_program(n_columns, challenges)
         _l.check(_l.load().ezkl_hip_eval_h_check(C.byref(pr)), "ezkl_hip_eval_h_check")
 
-    def scheduled_code(self, n_columns):
+    def generated_source(self, n_columns, challenges=None):
+        """host-only: the HIP source the sweep JIT generates for this program (the generator EZKL_EVALH_R29 selects), not compiled
+        (ezkl_hip_eval_h_source; tools/evalh29_model.py reads it)"""
+        pr, keep = self._host_program(n_columns, challenges)
+        n = C.c_size_t(0)
+        rc = _l.load().ezkl_hip_eval_h_source(C.byref(pr), None, C.c_size_t(0), C.byref(n))
+        if n.value == 0:                              # the program itself was refused (a valid one has a non-empty source)
+            _l.check(rc, "ezkl_hip_eval_h_source")
+        buf = C.create_string_buffer(n.value + 1)
+        _l.check(_l.load().ezkl_hip_eval_h_source(C.byref(pr), buf, C.c_size_t(n.value + 1), C.byref(n)), "ezkl_hip_eval_h_source")
+        return buf.value.decode()
+
+    def scheduled_code(self, n_columns, challenges=None):
         """host-only: the instruction order the library executes this program in (ezkl_hip_eval_h_schedule)"""
-        code, consts, rots = self.arrays()
-        cols = (C.c_void_p * max(1, n_columns))()
-        # every entry point validates the whole program (operand indices included): declare as many challenges as the code reads
-        n_chal = 1 + max([int(ins[3 + 3 * q]) for ins in code.tolist() for q in (0, 1) if ins[2 + 3 * q] == CHALLENGE] + [0])
-        ch = np.zeros((n_chal, 4), np.uint64)
-        pr = _Prog(_p(code), code.shape[0], self.n_intermediates, _p(consts), consts.shape[0], _p(rots), rots.shape[0],
-                   C.cast(cols, _vp), n_columns, _p(ch), n_chal, self.k, self.ext_k)
+        pr, keep = self._host_program(n_columns, challenges)
+        code = keep[0]
         out = np.zeros_like(code)
         _l.check(_l.load().ezkl_hip_eval_h_schedule(C.byref(pr), out.ctypes.data_as(C.c_void_p)), "ezkl_hip_eval_h_schedule")
         return out

@@ -1120,6 +1120,11 @@ int ezkl_hip_eval_h_check(const ezkl_program_t* prog) {
     return eval_jit_compile_only(prog);        // host-only: hiprtc cross-compiles for gfx950 without a GPU
 }
 
+int ezkl_hip_eval_h_source(const ezkl_program_t* prog, char* out, size_t cap, size_t* len) {
+    if (!prog || !prog->code || !len || prog->n_instr == 0) return EZKL_ERR_INVALID;
+    return eval_jit_source_only(prog, out, cap, len);        // host-only: no compile, no device
+}
+
 int ezkl_hip_eval_h_schedule(const ezkl_program_t* prog, uint32_t* out_code) {
     if (!prog || !prog->code || !out_code || prog->n_instr == 0) return EZKL_ERR_INVALID;
     return eval_schedule_only(prog, out_code);       // host-only: no device needed

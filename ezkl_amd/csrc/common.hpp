@@ -162,6 +162,7 @@ int msm_call_start(Ctx* c, std::unique_lock<std::recursive_mutex>& lk, const Bas
 int msm_call_finish(Ctx* c, std::unique_lock<std::recursive_mutex>& lk, int slot, void* out_host);
 int eval_program(Ctx* c, hipStream_t st, const ezkl_program_t* p, fe_t* out, bool ordered);
 int eval_jit_compile_only(const ezkl_program_t* p);
+int eval_jit_source_only(const ezkl_program_t* p, char* out, size_t cap, size_t* len);
 int eval_prepare(Ctx* c, const ezkl_program_t* p);
 int eval_schedule_only(const ezkl_program_t* p, uint32_t* out_code);
 void eval_jit_stats(uint64_t* compiled, uint64_t* from_disk, uint64_t* hits);

@@ -168,7 +168,14 @@ static uint32_t allocate_slots(const ezkl_program_t* p, std::vector<uint32_t>& c
     std::vector<int64_t> cur_ver(ni, -1), last_use(n, -1);
     std::vector<int64_t> src_ver(2 * (size_t)n, -1), tgt_ver(n, -1);
     for (uint32_t i = 0; i < n; i++) {
-        const uint32_t* I = &code[8 * (size_t)i];
+        uint32_t* I = &code[8 * (size_t)i];
+        // a Horner step on a target no instruction has written is 0 * factor + term: a STORE of the term.  Its target gets a fresh slot,
+        // which may still hold a dead value of this row, so the kernel must not read it (the JIT generators emit the term alone as well).
+        // The factor is still an operand of the program: a read of a never-written intermediate there is refused like any other
+        if (I[0] == EZKL_OP_HORNER_STEP && cur_ver[I[1]] < 0) {
+            if (I[5] == EZKL_SRC_INTERMEDIATE && cur_ver[I[6]] < 0) return 0xffffffffu;
+            I[0] = EZKL_OP_STORE;
+        }
         for (int q = 0; q < n_src(I[0]); q++)
             if (I[2 + 3 * q] == EZKL_SRC_INTERMEDIATE) {
                 int64_t v = cur_ver[I[3 + 3 * q]];
@@ -636,11 +643,26 @@ static int jit_get(Ctx* c, const ezkl_program_t* p, const std::vector<uint32_t>&
     if (from_disk) g_jit_from_disk++; else g_jit_compiled++;
     return EZKL_OK;
 }
-// every entry point validates the WHOLE program -- opcodes, targets and every source operand -- before anything indexes with it
-// (schedule_program / allocate_slots index by operand, the generators index constants and columns)
+// a host word is canonical (< p): the sweep kernels load constants and challenges as values below p (ld29 bounds them by 32 p), so a
+// word in [p, 2^256) -- up to ~169 p after the 5-bit shift -- would leave a non-canonical, wrong result (tests/test_gpu_evalh_bounds.py)
+static bool words_canonical(const void* words, uint32_t n) {
+    static constexpr uint32_t MOD[8] = BN32_FR_MOD_INIT;
+    const uint32_t* w = (const uint32_t*)words;
+    for (uint32_t i = 0; i < n; i++, w += 8) {
+        int j = 7;
+        while (j > 0 && w[j] == MOD[j]) j--;
+        if (w[j] >= MOD[j]) return false;
+    }
+    return true;
+}
+// every entry point validates the WHOLE program -- opcodes, targets, every source operand, and that its constants and challenges are
+// canonical -- before anything indexes with it (schedule_program / allocate_slots index by operand, the generators index constants and
+// columns).  O(n) over host arrays; device columns are not checked (include/ezkl_hip.h: every producing kernel writes canonical words)
 static int validate_program(const ezkl_program_t* p) {
     if (p->ext_k > 28 || p->k > p->ext_k) return EZKL_ERR_INVALID;
     if (p->n_instr && !p->code) return EZKL_ERR_INVALID;
+    if ((p->n_constants && !p->constants) || (p->n_challenges && !p->challenges)) return EZKL_ERR_INVALID;
+    if (!words_canonical(p->constants, p->n_constants) || !words_canonical(p->challenges, p->n_challenges)) return EZKL_ERR_INVALID;
     for (uint32_t i = 0; i < p->n_instr; i++) {
         const uint32_t* I = p->code + 8 * (size_t)i;
         if (I[0] > EZKL_OP_HORNER_STEP || I[1] >= p->n_intermediates) return EZKL_ERR_INVALID;
@@ -656,8 +678,9 @@ static int validate_program(const ezkl_program_t* p) {
     }
     return EZKL_OK;
 }
-// offline self-check used by build(): does the JIT source for a program compile for gfx950? (no GPU needed)
-int eval_jit_compile_only(const ezkl_program_t* p0) {
+// the source the JIT generator emits for a program, after the same validation, scheduling and slot check as a sweep; rotation offsets
+// are left at 0 (they depend on ext_k only through the launch, and no GPU is needed)
+static int jit_source_offline(const ezkl_program_t* p0, std::string& src) {
     if (int rc = validate_program(p0)) return rc;
     ezkl_program_t scheduled = *p0;
     const std::vector<uint32_t> sched_code = getenv("EZKL_EVALH_NO_SCHEDULE") ? std::vector<uint32_t>(p0->code, p0->code + 8 * (size_t)p0->n_instr) : schedule_program(p0);
@@ -668,7 +691,13 @@ int eval_jit_compile_only(const ezkl_program_t* p0) {
         if (allocate_slots(p, tmp) == 0xffffffffu) return EZKL_ERR_INVALID;
     }
     std::vector<uint32_t> rot(p->n_rotations ? p->n_rotations : 1, 0);
-    std::string src = jit_knob("EZKL_EVALH_R29", 2) ? jit_source_r29(p, rot) : jit_source(p, rot);
+    src = jit_knob("EZKL_EVALH_R29", 2) ? jit_source_r29(p, rot) : jit_source(p, rot);
+    return EZKL_OK;
+}
+// offline self-check used by build(): does the JIT source for a program compile for gfx950? (no GPU needed)
+int eval_jit_compile_only(const ezkl_program_t* p0) {
+    std::string src;
+    if (int rc = jit_source_offline(p0, src)) return rc;
     if (const char* dump = getenv("EZKL_HIP_JIT_DUMP")) {     // developer aid: the generated source, to look at its register use offline
         if (FILE* f = fopen(dump, "w")) { fwrite(src.data(), 1, src.size(), f); fclose(f); }
     }
@@ -680,6 +709,17 @@ int eval_jit_compile_only(const ezkl_program_t* p0) {
     hiprtcResult r = hiprtcCompileProgram(prog, 3, opts);
     hiprtcDestroyProgram(&prog);
     return r == HIPRTC_SUCCESS ? EZKL_OK : EZKL_ERR_HIP;
+}
+
+// host-only: the generated source itself (tools/evalh29_model.py checks it), without the hiprtc compile.  *len = its length; it is
+// copied with a terminating NUL when cap > *len, otherwise EZKL_ERR_INVALID tells the caller to retry with a larger buffer
+int eval_jit_source_only(const ezkl_program_t* p0, char* out, size_t cap, size_t* len) {
+    std::string src;
+    if (int rc = jit_source_offline(p0, src)) return rc;
+    *len = src.size();
+    if (!out || cap <= src.size()) return EZKL_ERR_INVALID;
+    memcpy(out, src.c_str(), src.size() + 1);
+    return EZKL_OK;
 }
 
 // host-only: the order the library will execute a program in (schedule_program), for callers and tests that want to look at it

@@ -356,6 +356,9 @@ typedef struct {
     const void* challenges;     uint32_t n_challenges;    /* n x 32 B Fr, host */
     uint32_t k, ext_k;
 } ezkl_program_t;
+/* Every word must be canonical (< r, Montgomery form): constants and challenges are checked (EZKL_ERR_INVALID otherwise); the column words
+ * and out_dev are NOT -- every kernel of this library that produces a column writes canonical words, and a check of device columns would
+ * cost a pass over them per call.  A non-canonical column word gives an undefined (possibly non-canonical) result for its rows. */
 /* out_dev[r] = program(row r) with ValueSource::PreviousValue = old out_dev[r]; 2^ext_k rows.  The host arrays of `prog` are borrowed
  * for the call only (packed into pinned staging the library owns); on a caller stream, or on the library stream in asynchronous mode
  * (ezkl_hip_set_async), the call returns once the launch is queued -- the columns and out_dev must stay valid until it has run. */
@@ -363,6 +366,9 @@ int ezkl_hip_eval_h_dev(const ezkl_program_t* prog, void* out_dev, void* stream)
 /* the sweep is JIT-compiled (hiprtc) into straight-line gfx950 code, once per program; this host-only call
  * checks that a program lowers and compiles (column pointers are not dereferenced; no GPU needed) */
 int ezkl_hip_eval_h_check(const ezkl_program_t* prog);
+/* host-only: the source ezkl_hip_eval_h_check would compile (the generator selected by EZKL_EVALH_R29; rotation offsets written as 0).
+ * *len receives its length in bytes; it is copied NUL-terminated into out when cap > *len, else EZKL_ERR_INVALID (query with out = NULL) */
+int ezkl_hip_eval_h_source(const ezkl_program_t* prog, char* out, size_t cap, size_t* len);
 /* host-only: the instruction order the sweep will execute (the library re-orders a program for short live ranges: every term is
  * computed right before the Horner step that consumes it; dependencies per intermediate are kept, so the value is the program's);
  * out_code receives n_instr x 8 words in the layout of prog->code */

@@ -463,6 +463,9 @@ void oracle_eval_program(const oracle_program *p, fe *out) {
         for (size_t r = 0; r < ne; r++) {
             fe prev = out[r];
             uint32_t last = 0;
+            /* every row starts from zero intermediates: a HORNER_STEP on a target no instruction has written yet is 0 * s1 + s0, never
+             * the value the previous row left there */
+            memset(im, 0, (p->n_intermediates ? p->n_intermediates : 1) * sizeof(fe));
             for (uint32_t ii = 0; ii < p->n_instr; ii++) {
                 const uint32_t *I = p->code + 8 * (size_t)ii;
                 fe s[2];

@@ -121,3 +121,17 @@ def test_eval_h_check_refuses_malformed_programs():
     bad.n_intermediates = 1
     with pytest.raises(L.EzklHipError):
         bad.check_compiles(1)
+    # a Horner step on a target no instruction has written is 0 * factor + term, but its factor is still read: a never-written
+    # intermediate there is refused as well (the generators index their tables by the factor's version)
+    def horner_on_fresh(factor):
+        h = B.GraphProgram(4, 6)
+        h.calc("add", h.column(0), h.column(0))                                   # t0
+        h.n_intermediates = 3
+        h.code.append([B.OPS["horner_step"], 1, B.INTERMEDIATE, 0, 0, B.INTERMEDIATE, factor, 0])
+        h.code.append([B.OPS["add"], 2, B.INTERMEDIATE, 1, 0, B.INTERMEDIATE, 0, 0])
+        return h
+    for call in (horner_on_fresh(2).check_compiles, horner_on_fresh(2).generated_source):
+        with pytest.raises(L.EzklHipError) as e:
+            call(1)
+        assert e.value.code == -3                                                 # EZKL_ERR_INVALID
+    horner_on_fresh(0).check_compiles(1)                                          # a written factor: accepted

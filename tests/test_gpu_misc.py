@@ -64,9 +64,10 @@ def _gate_program(B, k, ek):
 
 @pytest.mark.parametrize("mode", ["jit", "interp"])
 @pytest.mark.parametrize("k,ek", [(3, 5), (8, 10), (12, 15)])
-def test_eval_h_program(hip, k, ek, mode, monkeypatch):
+def test_eval_h_program(hip, k, ek, mode, monkeypatch, tmp_path):
     from ezkl_amd import backend as B
     monkeypatch.setenv("EZKL_EVALH_MODE", mode)
+    monkeypatch.setenv("EZKL_HIP_CACHE_DIR", str(tmp_path))
     rng = np.random.default_rng(k)
     ne = 1 << ek
     cols = [rand_fr(rng, ne) for _ in range(4)]
@@ -77,7 +78,9 @@ def test_eval_h_program(hip, k, ek, mode, monkeypatch):
     want = ob.eval_program(code, prog.n_intermediates, consts, rots, cols, chal, k, ek, previous=prev)
     dcols = [B.DeviceBuffer.from_numpy(c) for c in cols]
     dout = B.DeviceBuffer.from_numpy(prev)
+    before = sum(B.jit_stats())
     prog.evaluate_h([d.ptr for d in dcols], chal, dout.ptr)
+    assert sum(B.jit_stats()) - before == (1 if mode == "jit" else 0)        # jit mode ran a compiled kernel, not the interpreter
     assert (dout.to_numpy(shape=(ne, 4)) == want).all()
 
 
@@ -107,9 +110,10 @@ def _random_program(B, rng, k, ek, ncols, ninstr):
 
 @pytest.mark.parametrize("mode", ["jit", "interp"])
 @pytest.mark.parametrize("seed", [1, 2, 3])
-def test_eval_h_random_dag(hip, seed, mode, monkeypatch):
+def test_eval_h_random_dag(hip, seed, mode, monkeypatch, tmp_path):
     from ezkl_amd import backend as B
     monkeypatch.setenv("EZKL_EVALH_MODE", mode)
+    monkeypatch.setenv("EZKL_HIP_CACHE_DIR", str(tmp_path))
     rng = np.random.default_rng(seed)
     k, ek, ncols = 9, 11, 12
     ne = 1 << ek
@@ -121,7 +125,9 @@ def test_eval_h_random_dag(hip, seed, mode, monkeypatch):
     want = ob.eval_program(code, prog.n_intermediates, consts, rots, cols, chal, k, ek, previous=prev)
     dcols = [B.DeviceBuffer.from_numpy(c) for c in cols]
     dout = B.DeviceBuffer.from_numpy(prev)
+    before = sum(B.jit_stats())
     prog.evaluate_h([d.ptr for d in dcols], chal, dout.ptr)
+    assert sum(B.jit_stats()) - before == (1 if mode == "jit" else 0)        # jit mode ran a compiled kernel, not the interpreter
     assert (dout.to_numpy(shape=(ne, 4)) == want).all()
 
 

@@ -65,7 +65,7 @@ def subc(K):
     return c
 
 
-SUBC = {K: subc(K) for K in (2, 4, 8, 16, 32)}
+SUBC = {K: subc(K) for K in (2, 4, 8, 16, 32, 64, 128)}          # K = 2 << KI, KI = 0..6 (field29.hpp sub / neg)
 SKIP_UNIT2 = True          # stage 2 of a plain transform: the twiddle of every other butterfly is w_4^0 = 1 -- no product (ntt.hip, round 5)
 
 
