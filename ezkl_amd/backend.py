@@ -508,6 +508,39 @@ def lookup_multiplicity_batch(inputs_per_lookup, table_ptrs, n_rows, usable_rows
     return outs, int(miss.to_numpy(np.uint32, (1,))[0])
 
 
+def _records(rec, counters, cap):
+    """(records as (kind, index, sub, row) tuples -- at most cap of them, in the order the kernel appended them --, counters)"""
+    cnt = counters.to_numpy(np.uint64)
+    m = int(min(cnt[0], cap))
+    r = rec.to_numpy(np.uint32)[:4 * m].reshape(m, 4) if m else np.zeros((0, 4), np.uint32)
+    return [tuple(int(x) for x in row) for row in r], [int(x) for x in cnt]
+
+
+def lookup_missing_rows(inputs_per_lookup, table_ptrs, n_rows, usable_rows, cap=1024, stream=None):
+    """the mock prover's lookup check (ezkl_hip_lookup_missing_rows_dev): every usable input row absent from its table.  Returns
+    (records (2, lookup, input, row), [total, misses of argument 0, ...])"""
+    L = len(table_ptrs)
+    flat = [p for ins in inputs_per_lookup for p in ins]
+    which = [l for l, ins in enumerate(inputs_per_lookup) for _ in ins]
+    rec, cnt = DeviceBuffer(max(1, cap) * 16), DeviceBuffer.from_numpy(np.zeros(1 + L, np.uint64))
+    a_in = (C.c_void_p * max(1, len(flat)))(*flat)
+    a_which = (C.c_uint32 * max(1, len(which)))(*which)
+    a_tab = (C.c_void_p * L)(*table_ptrs)
+    _l.check(_l.load().ezkl_hip_lookup_missing_rows_dev(a_in, a_which, C.c_uint32(len(flat)), a_tab, C.c_uint32(L), C.c_uint32(n_rows), C.c_uint32(usable_rows),
+                                                         _vp(rec.ptr), C.c_uint32(cap), _vp(cnt.ptr), _stream_ptr(stream)), "ezkl_hip_lookup_missing_rows_dev")
+    return _records(rec, cnt, cap)
+
+
+def copy_check(col_ptrs, next_ptr, log_n, cap=1024, stream=None):
+    """the mock prover's copy check (ezkl_hip_copy_check_dev): every cell that differs from its cycle successor.  Returns
+    (records (3, column, 0, row), [total])"""
+    rec, cnt = DeviceBuffer(max(1, cap) * 16), DeviceBuffer.from_numpy(np.zeros(1, np.uint64))
+    a = (C.c_void_p * max(1, len(col_ptrs)))(*col_ptrs)
+    _l.check(_l.load().ezkl_hip_copy_check_dev(a, C.c_uint32(len(col_ptrs)), _vp(next_ptr), C.c_uint32(log_n), _vp(rec.ptr), C.c_uint32(cap), _vp(cnt.ptr),
+                                                _stream_ptr(stream)), "ezkl_hip_copy_check_dev")
+    return _records(rec, cnt, cap)
+
+
 def eval_polynomial(coeffs_ptr, n, x, stream=None):
     """halo2 eval_polynomial on a resident coefficient vector"""
     out = np.zeros(4, np.uint64)
@@ -772,6 +805,34 @@ class GraphProgram:
         pr = _Prog(_p(code), code.shape[0], self.n_intermediates, _p(consts), consts.shape[0], _p(rots), rots.shape[0],
                    C.cast(cols, _vp), len(column_ptrs), _p(ch), ch.shape[0], self.k, self.ext_k)
         _l.check(_l.load().ezkl_hip_eval_h_dev(C.byref(pr), _vp(out_ptr), _stream_ptr(stream)), "ezkl_hip_eval_h_dev")
+
+
+    def check_source(self, n_columns, slots, challenges=None):
+        """host-only: the source of the mock prover's check kernel for the intermediates `slots` (ezkl_hip_eval_check_source; k == ext_k)"""
+        pr, keep = self._host_program(n_columns, challenges)
+        sl = (C.c_uint32 * max(1, len(slots)))(*slots)
+        n = C.c_size_t(0)
+        rc = _l.load().ezkl_hip_eval_check_source(C.byref(pr), sl, C.c_uint32(len(slots)), None, C.c_size_t(0), C.byref(n))
+        if n.value == 0:
+            _l.check(rc, "ezkl_hip_eval_check_source")
+        buf = C.create_string_buffer(n.value + 1)
+        _l.check(_l.load().ezkl_hip_eval_check_source(C.byref(pr), sl, C.c_uint32(len(slots)), buf, C.c_size_t(n.value + 1), C.byref(n)),
+                 "ezkl_hip_eval_check_source")
+        return buf.value.decode()
+
+    def check_rows(self, column_ptrs, challenges, slots, row_lo, row_hi, cap=1024, stream=None):
+        """the mock prover's gate check on device columns of 2^k rows (ezkl_hip_eval_check_dev): every row in [row_lo, row_hi) where a
+        listed intermediate is not zero.  Returns (records (1, slot, 0, row), [total])"""
+        code, consts, rots = self.arrays()
+        ch = _fe(np.asarray(challenges, np.uint64).reshape(-1, 4))
+        cols = (C.c_void_p * max(1, len(column_ptrs)))(*column_ptrs)
+        pr = _Prog(_p(code), code.shape[0], self.n_intermediates, _p(consts), consts.shape[0], _p(rots), rots.shape[0],
+                   C.cast(cols, _vp), len(column_ptrs), _p(ch), ch.shape[0], self.k, self.ext_k)
+        sl = (C.c_uint32 * max(1, len(slots)))(*slots)
+        rec, cnt = DeviceBuffer(max(1, cap) * 16), DeviceBuffer.from_numpy(np.zeros(1, np.uint64))
+        _l.check(_l.load().ezkl_hip_eval_check_dev(C.byref(pr), sl, C.c_uint32(len(slots)), C.c_uint32(row_lo), C.c_uint32(row_hi), _vp(rec.ptr),
+                                                    C.c_uint32(cap), _vp(cnt.ptr), _stream_ptr(stream)), "ezkl_hip_eval_check_dev")
+        return _records(rec, cnt, cap)
 
 
 def jit_stats():

@@ -1125,6 +1125,38 @@ int ezkl_hip_eval_h_source(const ezkl_program_t* prog, char* out, size_t cap, si
     return eval_jit_source_only(prog, out, cap, len);        // host-only: no compile, no device
 }
 
+int ezkl_hip_eval_check_dev(const ezkl_program_t* prog, const uint32_t* check_slots, uint32_t n_checks, uint32_t row_lo, uint32_t row_hi, void* records_dev,
+                            uint32_t cap, void* counters_dev, void* stream) {
+    if (!prog || !prog->code || !check_slots || n_checks == 0 || !counters_dev || (cap && !records_dev)) return EZKL_ERR_INVALID;
+    EZ_CTX(c);
+    return eval_check(c, pick_stream(c, stream), prog, check_slots, n_checks, row_lo, row_hi, records_dev, cap, counters_dev);
+}
+int ezkl_hip_eval_check_source(const ezkl_program_t* prog, const uint32_t* check_slots, uint32_t n_checks, char* out, size_t cap, size_t* len) {
+    if (!prog || !prog->code || !check_slots || n_checks == 0 || !len) return EZKL_ERR_INVALID;
+    return eval_check_source_only(prog, check_slots, n_checks, out, cap, len);        // host-only: no compile, no device
+}
+int ezkl_hip_lookup_missing_rows_dev(const void* const* inputs_dev, const uint32_t* input_lookup, uint32_t n_inputs, const void* const* tables_dev,
+                                     uint32_t n_lookups, uint32_t n_rows, uint32_t usable_rows, void* records_dev, uint32_t cap, void* counters_dev,
+                                     void* stream) {
+    if (!tables_dev || !counters_dev || n_lookups == 0 || (cap && !records_dev) || (n_inputs && (!inputs_dev || !input_lookup))) return EZKL_ERR_INVALID;
+    for (uint32_t j = 0; j < n_inputs; j++)
+        if (!inputs_dev[j]) return EZKL_ERR_INVALID;
+    for (uint32_t l = 0; l < n_lookups; l++)
+        if (!tables_dev[l]) return EZKL_ERR_INVALID;
+    EZ_CTX(c);
+    return lookup_missing_rows(c, pick_stream(c, stream), (const fe_t* const*)inputs_dev, input_lookup, n_inputs, (const fe_t* const*)tables_dev, n_lookups,
+                               n_rows, usable_rows, records_dev, cap, counters_dev);
+}
+int ezkl_hip_copy_check_dev(const void* const* cols_dev, uint32_t m, const void* next_dev, uint32_t log_n, void* records_dev, uint32_t cap, void* counters_dev,
+                            void* stream) {
+    if ((m && (!cols_dev || !next_dev)) || !counters_dev || (cap && !records_dev) || log_n > 28) return EZKL_ERR_INVALID;
+    if (((uint64_t)m << log_n) > ((uint64_t)1 << 32)) return EZKL_ERR_INVALID;         // cells are numbered in 32 bits
+    for (uint32_t j = 0; j < m; j++)
+        if (!cols_dev[j]) return EZKL_ERR_INVALID;
+    EZ_CTX(c);
+    return copy_check(c, pick_stream(c, stream), (const fe_t* const*)cols_dev, m, (const uint32_t*)next_dev, log_n, records_dev, cap, counters_dev);
+}
+
 int ezkl_hip_eval_h_schedule(const ezkl_program_t* prog, uint32_t* out_code) {
     if (!prog || !prog->code || !out_code || prog->n_instr == 0) return EZKL_ERR_INVALID;
     return eval_schedule_only(prog, out_code);       // host-only: no device needed

@@ -163,6 +163,12 @@ int msm_call_finish(Ctx* c, std::unique_lock<std::recursive_mutex>& lk, int slot
 int eval_program(Ctx* c, hipStream_t st, const ezkl_program_t* p, fe_t* out, bool ordered);
 int eval_jit_compile_only(const ezkl_program_t* p);
 int eval_jit_source_only(const ezkl_program_t* p, char* out, size_t cap, size_t* len);
+int eval_check_source_only(const ezkl_program_t* p, const uint32_t* slots, uint32_t n_checks, char* out, size_t cap, size_t* len);
+int eval_check(Ctx* c, hipStream_t st, const ezkl_program_t* p, const uint32_t* slots, uint32_t n_checks, uint32_t row_lo, uint32_t row_hi, void* rec,
+               uint32_t cap, void* count);
+int lookup_missing_rows(Ctx* c, hipStream_t st, const fe_t* const* inputs, const uint32_t* which, uint32_t n_items, const fe_t* const* tables,
+                        uint32_t n_lookups, uint32_t n_rows, uint32_t usable, void* rec, uint32_t cap, void* count);
+int copy_check(Ctx* c, hipStream_t st, const fe_t* const* cols, uint32_t m, const uint32_t* next, uint32_t log_n, void* rec, uint32_t cap, void* count);
 int eval_prepare(Ctx* c, const ezkl_program_t* p);
 int eval_schedule_only(const ezkl_program_t* p, uint32_t* out_code);
 void eval_jit_stats(uint64_t* compiled, uint64_t* from_disk, uint64_t* hits);

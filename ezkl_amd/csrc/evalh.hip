@@ -340,7 +340,11 @@ struct V29 {
     int alpha = 32, L = 1;
     long long var = -1;    // version id when `expr` is a variable (its state lives in the table), -1 for a load
 };
-static std::string jit_source_r29(const ezkl_program_t* p, const std::vector<uint32_t>& rot) {
+// checks != nullptr: the CHECK kernel of the mock prover (ezkl_hip_eval_check_dev) instead of the sweep.  The program runs with ext_k == k
+// on rows [row_lo, row_hi); right after the last write of every listed intermediate its value is reduced as the sweep's result is and tested
+// for zero, and a failing lane appends {1, slot, 0, row} through one ballot + one atomic per wave (ezkl_report).  Nothing else is stored.
+// checks == nullptr emits exactly the sweep source it always did.
+static std::string jit_source_r29(const ezkl_program_t* p, const std::vector<uint32_t>& rot, const std::vector<uint32_t>* checks = nullptr) {
     std::string s;
     s.reserve(1024 + (size_t)p->n_instr * 160);
     const int waves = jit_knob("EZKL_EVALH_WAVES", 4), barrier = jit_knob("EZKL_EVALH_BARRIER", 1);
@@ -358,14 +362,38 @@ static std::string jit_source_r29(const ezkl_program_t* p, const std::vector<uin
          "    const uint32_t lo = w.v[word], hi = word + 1 < 8 ? w.v[word + 1] : 0u;\n"
          "    r.v[i] = (sh ? __builtin_amdgcn_alignbit(hi, lo, sh) : lo) & M29;\n  }\n"
          "  r.v[8] = w.v[7] >> 3;\n  return r;\n}\n";
+    if (checks)      // the lanes of a wave that fail append together: slot = count before the add + rank among the failing lanes; slots >= cap are counted only
+        s += "__device__ __forceinline__ void ezkl_report(bool fail, uint32_t slot, uint32_t r, uint4* __restrict__ rec, uint32_t cap,\n"
+             "    unsigned long long* __restrict__ count) {\n"
+             "  const unsigned long long m = __ballot(fail);\n  if (!m) return;\n"
+             "  const uint32_t lane = threadIdx.x & 63, leader = __ffsll(m) - 1;\n"
+             "  unsigned long long base = 0;\n"
+             "  if (lane == leader) base = atomicAdd(count, (unsigned long long)__popcll(m));\n"
+             "  base = ((unsigned long long)__shfl((uint32_t)(base >> 32), leader) << 32) | __shfl((uint32_t)base, leader);\n"
+             "  const unsigned long long at = base + __popcll(m & ((1ull << lane) - 1));\n"
+             "  if (fail && at < cap) rec[at] = make_uint4(1u, slot, 0u, r);\n}\n";
     s += "extern \"C\" __global__ __launch_bounds__(256) ";
     if (waves > 0) s += "__attribute__((amdgpu_waves_per_eu(" + std::to_string(waves) + "," + std::to_string(waves) + "))) ";
-    s += "void evalh_jit(const fe_t* const* __restrict__ cols, const fe_t* __restrict__ consts,\n"
-         "    const fe_t* __restrict__ chal, fe_t* __restrict__ out, uint32_t ne_mask, uint32_t T) {\n"
-         "  const uint32_t tid = (XCD_MAP && gridDim.x % 8 == 0 ? (blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : blockIdx.x) * blockDim.x + threadIdx.x;\n"
+    if (checks)
+        s += "void evalh_check(const fe_t* const* __restrict__ cols, const fe_t* __restrict__ consts,\n"
+             "    const fe_t* __restrict__ chal, uint32_t ne_mask, uint32_t row_lo, uint32_t row_hi, uint32_t T, uint4* __restrict__ rec, uint32_t cap,\n"
+             "    unsigned long long* __restrict__ count) {\n";
+    else
+        s += "void evalh_jit(const fe_t* const* __restrict__ cols, const fe_t* __restrict__ consts,\n"
+             "    const fe_t* __restrict__ chal, fe_t* __restrict__ out, uint32_t ne_mask, uint32_t T) {\n";
+    s += "  const uint32_t tid = (XCD_MAP && gridDim.x % 8 == 0 ? (blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : blockIdx.x) * blockDim.x + threadIdx.x;\n"
          "  const f29_t c_one = Fr29::one();\n"
-         "  const f29_t c_r256 = Fr29::unpack(Fr::one());\n"        // 2^256 mod p, normalized: R' -> R
-         "  for (uint32_t r = tid; r <= ne_mask; r += T) {\n";
+         "  const f29_t c_r256 = Fr29::unpack(Fr::one());\n";       // 2^256 mod p, normalized: R' -> R
+    s += checks ? "  for (uint32_t r = row_lo + tid; r < row_hi; r += T) {\n" : "  for (uint32_t r = tid; r <= ne_mask; r += T) {\n";
+    // check mode: the instruction after which each listed intermediate holds its final value
+    std::vector<int64_t> check_at(p->n_instr, -1);
+    if (checks)
+        for (uint32_t j : *checks) {
+            int64_t last_w = -1;
+            for (uint32_t i = 0; i < p->n_instr; i++)
+                if (p->code[8 * (size_t)i + 1] == j) last_w = i;
+            check_at[last_w] = j;          // the caller (eval_check_prepare) has verified that every listed slot is written
+        }
     auto n_src = [](uint32_t op) { return (op == EZKL_OP_SQUARE || op == EZKL_OP_DOUBLE || op == EZKL_OP_NEGATE || op == EZKL_OP_STORE) ? 1 : 2; };
     std::vector<int64_t> cur_ver(p->n_intermediates, -1);
     std::vector<int> A(p->n_instr, 0), Ls(p->n_instr, 0);                 // state of version i (defined by instruction i)
@@ -424,6 +452,17 @@ static std::string jit_source_r29(const ezkl_program_t* p, const std::vector<uin
         while (a.alpha + K > 160 && a.var >= 0 && a.alpha > 3) reduce(a);
         return K;
     };
+    // check mode: the value is brought to the form the sweep's store takes (canonical after R' -> R) and compared with zero
+    auto emit_check = [&](uint32_t i) {
+        if (!checks || check_at[i] < 0) return;
+        const long long ver = cur_ver[check_at[i]];
+        V29 v;
+        v.expr = "v" + std::to_string(ver);
+        v.var = ver; v.alpha = A[ver]; v.L = Ls[ver];
+        while (v.L > 6) normalize(v);
+        while (v.alpha > 169) reduce(v);
+        s += "    ezkl_report(!Fr::is_zero(Fr29::pack(Fr29::cond_sub<0>(" + MUL + v.expr + ", c_r256)))), " + std::to_string(check_at[i]) + "u, r, rec, cap, count);\n";
+    };
     long long last = -1;
     for (uint32_t i = 0; i < p->n_instr; i++) {
         const uint32_t* I = p->code + 8 * (size_t)i;
@@ -445,6 +484,7 @@ static std::string jit_source_r29(const ezkl_program_t* p, const std::vector<uin
             A[tv] = (int)(am + a.alpha);
             Ls[tv] = 1 + a.L;
             last = tv;
+            emit_check(i);
             continue;
         }
         cur_ver[I[1]] = i;
@@ -500,6 +540,11 @@ static std::string jit_source_r29(const ezkl_program_t* p, const std::vector<uin
             A[i] = a.alpha; Ls[i] = a.L;
             break;
         }
+        emit_check(i);
+    }
+    if (checks) {
+        s += "  }\n}\n";
+        return s;
     }
     // R' -> R and canonical form: v * 2^256 / 2^261 < (alpha / 169 + 1) p <= 2 p, one conditional subtraction, pack
     {
@@ -553,9 +598,15 @@ static uint64_t jit_build_digest() {
     }();
     return d;
 }
-static int jit_get(Ctx* c, const ezkl_program_t* p, const std::vector<uint32_t>& rot, hipFunction_t* fn) {
+// checks != nullptr: the check kernel of those slots (jit_source_r29); its identity holds a tag and the slots besides, so a sweep and a check
+// kernel of the same program never share a cache entry, and the key of every sweep is the one it always was
+static int jit_get(Ctx* c, const ezkl_program_t* p, const std::vector<uint32_t>& rot, hipFunction_t* fn, const std::vector<uint32_t>* checks = nullptr) {
     std::string key((const char*)p->code, (size_t)p->n_instr * 32);
     key.append((const char*)rot.data(), rot.size() * 4);
+    if (checks) {
+        key.append("check", 5);
+        key.append((const char*)checks->data(), checks->size() * 4);
+    }
     const uint64_t build = jit_build_digest();
     key.append((const char*)&build, sizeof build);
     const int knobs[5] = {jit_knob("EZKL_EVALH_WAVES", 4), jit_knob("EZKL_EVALH_BARRIER", 1), jit_knob("EZKL_EVALH_R29", 2), jit_knob("EZKL_EVALH_XCD", 0),
@@ -576,7 +627,7 @@ static int jit_get(Ctx* c, const ezkl_program_t* p, const std::vector<uint32_t>&
     const std::string arch = jit_arch(c), dir = jit_cache_dir();
     char name[160];
     // second, independent hash in the file name + the key length: a stale or colliding file is caught by the embedded key check below
-    snprintf(name, sizeof name, "/evalh_%s_%016llx_%016llx_%zu.co", arch.c_str(), (unsigned long long)h,
+    snprintf(name, sizeof name, checks ? "/evalhchk_%s_%016llx_%016llx_%zu.co" : "/evalh_%s_%016llx_%016llx_%zu.co", arch.c_str(), (unsigned long long)h,
              (unsigned long long)fnv1a(key.data(), key.size(), 0x9e3779b97f4a7c15ull ^ build), key.size());
     std::vector<char> bin;
     bool from_disk = false;
@@ -596,7 +647,7 @@ static int jit_get(Ctx* c, const ezkl_program_t* p, const std::vector<uint32_t>&
         }
     }
     if (!from_disk) {
-        std::string src = jit_knob("EZKL_EVALH_R29", 2) ? jit_source_r29(p, rot) : jit_source(p, rot);
+        std::string src = checks ? jit_source_r29(p, rot, checks) : jit_knob("EZKL_EVALH_R29", 2) ? jit_source_r29(p, rot) : jit_source(p, rot);
         const char* hn[5] = {"field.hpp", "bn254_constants.h", "montmul_gen.hpp", "field29.hpp", "montmul29_gen.hpp"};
         const char* hs[5] = {k_src_field, k_src_constants, k_src_montmul, k_src_field29, k_src_montmul29};
         hiprtcProgram prog;
@@ -631,7 +682,7 @@ static int jit_get(Ctx* c, const ezkl_program_t* p, const std::vector<uint32_t>&
             }
         }
     }
-    if (hipModuleLoadData(&k.mod, bin.data()) != hipSuccess || hipModuleGetFunction(&k.fn, k.mod, "evalh_jit") != hipSuccess) {
+    if (hipModuleLoadData(&k.mod, bin.data()) != hipSuccess || hipModuleGetFunction(&k.fn, k.mod, checks ? "evalh_check" : "evalh_jit") != hipSuccess) {
         (void)hipGetLastError();
         if (from_disk) (void)remove((dir + name).c_str());     // a damaged cache entry: drop it, the next call compiles
         k.failed = !from_disk;
@@ -843,6 +894,91 @@ int eval_program(Ctx* c, hipStream_t st, const ezkl_program_t* p, fe_t* out, boo
     EZ_HIP(hipEventRecord(e1, st));
     if ((rc = arena_done(scratch_arena(c, st), st))) return rc;
     if (!ordered) EZ_HIP(hipStreamSynchronize(st));
+    return EZKL_OK;
+}
+
+// ---- check mode: the gate check of the mock prover (ezkl_hip_eval_check_dev) ----
+// The program runs on the 2^k Lagrange rows themselves (ext_k == k: a rotation is a row offset, indices wrap mod 2^k).  It is scheduled and
+// slot-checked as a sweep is; every listed intermediate must be written by the program, and may be listed once.  Only the radix-2^29
+// generators have a check form (EZKL_EVALH_R29=0 -> EZKL_ERR_INVALID).
+static int check_prepare(const ezkl_program_t* p0, const uint32_t* slots, uint32_t n_checks, std::vector<uint32_t>& sched, std::vector<uint32_t>& checks) {
+    if (int rc = validate_program(p0)) return rc;
+    if (p0->k != p0->ext_k || p0->n_instr == 0 || n_checks == 0 || !slots) return EZKL_ERR_INVALID;
+    if (jit_knob("EZKL_EVALH_R29", 2) == 0) return EZKL_ERR_INVALID;
+    std::vector<uint8_t> written(p0->n_intermediates, 0), listed(p0->n_intermediates, 0);
+    for (uint32_t i = 0; i < p0->n_instr; i++) written[p0->code[8 * (size_t)i + 1]] = 1;
+    for (uint32_t q = 0; q < n_checks; q++) {
+        const uint32_t j = slots[q];
+        if (j >= p0->n_intermediates || !written[j] || listed[j]) return EZKL_ERR_INVALID;
+        listed[j] = 1;
+    }
+    sched = getenv("EZKL_EVALH_NO_SCHEDULE") ? std::vector<uint32_t>(p0->code, p0->code + 8 * (size_t)p0->n_instr) : schedule_program(p0);
+    ezkl_program_t sp = *p0;
+    sp.code = sched.data();
+    std::vector<uint32_t> tmp;
+    if (allocate_slots(&sp, tmp) == 0xffffffffu) return EZKL_ERR_INVALID;
+    checks.assign(slots, slots + n_checks);
+    return EZKL_OK;
+}
+
+// host-only: the check kernel's source (rotation offsets written as 0), with the contract of eval_jit_source_only
+int eval_check_source_only(const ezkl_program_t* p0, const uint32_t* slots, uint32_t n_checks, char* out, size_t cap, size_t* len) {
+    std::vector<uint32_t> sched, checks;
+    if (int rc = check_prepare(p0, slots, n_checks, sched, checks)) return rc;
+    ezkl_program_t sp = *p0;
+    sp.code = sched.data();
+    const std::vector<uint32_t> rot(p0->n_rotations ? p0->n_rotations : 1, 0);
+    const std::string src = jit_source_r29(&sp, rot, &checks);
+    *len = src.size();
+    if (!out || cap <= src.size()) return EZKL_ERR_INVALID;
+    memcpy(out, src.c_str(), src.size() + 1);
+    return EZKL_OK;
+}
+
+// rows [row_lo, row_hi); rec: cap records of 16 B (device), count: one u64 (device) the failures are ADDED to -- record i of this call goes
+// to rec[count_before + i] when that is below cap.  The host arrays of the program are borrowed: the call returns after the kernel has run.
+int eval_check(Ctx* c, hipStream_t st, const ezkl_program_t* p0, const uint32_t* slots, uint32_t n_checks, uint32_t row_lo, uint32_t row_hi, void* rec,
+               uint32_t cap, void* count) {
+    std::vector<uint32_t> sched, checks;
+    if (int rc = check_prepare(p0, slots, n_checks, sched, checks)) return rc;
+    const size_t n = (size_t)1 << p0->k;
+    if (row_lo > row_hi || row_hi > n) return EZKL_ERR_INVALID;
+    if (row_lo == row_hi) return EZKL_OK;
+    ezkl_program_t sp = *p0;
+    sp.code = sched.data();
+    std::vector<uint32_t> rot(p0->n_rotations ? p0->n_rotations : 1, 0);
+    for (uint32_t i = 0; i < p0->n_rotations; i++) {
+        int64_t v = (int64_t)p0->rotations[i] % (int64_t)n;
+        if (v < 0) v += (int64_t)n;
+        rot[i] = (uint32_t)v;
+    }
+    hipFunction_t fn = nullptr;
+    if (int rc = jit_get(c, &sp, rot, &fn, &checks)) return rc;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_cols = al((size_t)(p0->n_constants ? p0->n_constants : 1) * 32);
+    const size_t o_chal = o_cols + al((size_t)(p0->n_columns ? p0->n_columns : 1) * 8);
+    const size_t total = o_chal + al((size_t)(p0->n_challenges ? p0->n_challenges : 1) * 32);
+    uint8_t* S = nullptr;
+    int rc = arena_reserve(scratch_arena(c, st), total, st, (void**)&S);
+    if (rc) return rc;
+    if (p0->n_constants) EZ_HIP(hipMemcpyAsync(S, p0->constants, (size_t)p0->n_constants * 32, hipMemcpyHostToDevice, st));
+    if (p0->n_columns) EZ_HIP(hipMemcpyAsync(S + o_cols, p0->columns, (size_t)p0->n_columns * 8, hipMemcpyHostToDevice, st));
+    if (p0->n_challenges) EZ_HIP(hipMemcpyAsync(S + o_chal, p0->challenges, (size_t)p0->n_challenges * 32, hipMemcpyHostToDevice, st));
+    // whole waves only (the report is a ballot over the wave): T is a multiple of 256, every lane's first row is row_lo + tid
+    size_t T = (size_t)c->num_cus * 256 * (size_t)jit_knob("EZKL_EVALH_TMUL", 16);
+    if (T > row_hi - row_lo) T = row_hi - row_lo;
+    T = (T + 255) & ~(size_t)255;
+    const fe_t* const* d_cols = (const fe_t* const*)(S + o_cols);
+    const fe_t* d_consts = (const fe_t*)S;
+    const fe_t* d_chal = (const fe_t*)(S + o_chal);
+    uint32_t ne_mask = (uint32_t)(n - 1), lo = row_lo, hi = row_hi, Tj = (uint32_t)T, capj = cap;
+    void* d_rec = rec;
+    void* d_count = count;
+    void* args[] = {&d_cols, &d_consts, &d_chal, &ne_mask, &lo, &hi, &Tj, &d_rec, &capj, &d_count};
+    EZ_HIP(hipModuleLaunchKernel(fn, (unsigned)(T / 256), 1, 1, 256, 1, 1, 0, st, args, nullptr));
+    EZ_HIP(hipGetLastError());
+    if ((rc = arena_done(scratch_arena(c, st), st))) return rc;
+    EZ_HIP(hipStreamSynchronize(st));
     return EZKL_OK;
 }
 

@@ -1042,6 +1042,30 @@ static bool check_key_fits(const ConstraintSystem& cs, uint32_t coset_count, con
     }
     throw Error(EZKL_ERR_NOMEM, msg);
 }
+// permutation: cycle structure over (colpos, row) cells numbered c * n + r; returns the cycle successor of every cell (halo2
+// permutation::keygen::Assembly::copy: `root` a cycle label, `size` the cycle length).  keygen turns it into the sigma columns, the mock
+// prover compares every cell with its successor.
+static std::vector<uint32_t> copy_cycles(const ConstraintSystem& cs, const uint32_t* copies, size_t n_copies) {
+    const size_t n = cs.n, m = cs.perm.size(), cells = m * n;
+    std::vector<uint32_t> nxt(cells), root(cells), size(cells, 1);
+    for (size_t i = 0; i < cells; i++) nxt[i] = root[i] = (uint32_t)i;
+    for (size_t i = 0; i < n_copies; i++) {
+        const uint32_t* cp = copies + 4 * i;
+        invalid(cp[0] >= m || cp[2] >= m || cp[1] >= n || cp[3] >= n, "copy constraint out of range");
+        uint32_t a = cp[0] * n + cp[1], b = cp[2] * n + cp[3];
+        if (root[a] == root[b]) continue;
+        if (size[root[a]] < size[root[b]]) std::swap(a, b);
+        const uint32_t ra = root[a], rb = root[b];
+        size[ra] += size[rb];
+        uint32_t cur = b;
+        do {                                     // relabel the smaller cycle
+            root[cur] = ra;
+            cur = nxt[cur];
+        } while (cur != b);
+        std::swap(nxt[a], nxt[b]);
+    }
+    return nxt;
+}
 static std::unique_ptr<ProvingKey> keygen(ConstraintSystem& cs, ezkl_bases_t g, const void* const* fixed_values, const uint32_t* copies, size_t n_copies) {
     const uint32_t n = cs.n, k = cs.k;
     Backend be(k, n, g, nullptr, cs.shard);
@@ -1069,26 +1093,8 @@ static std::unique_ptr<ProvingKey> keygen(ConstraintSystem& cs, ezkl_bases_t g, 
         pk->fixed_cosets.push_back(pk->stream ? Col() : be.key_cosets(pk->fixed_polys.back(), cs.ext_k));
     }
     lap("fixed columns");
-    // permutation: cycle structure over (colpos, row) cells numbered c * n + r; `nxt` is the cycle successor, `root` a
-    // cycle label, `size` the cycle length (halo2 permutation::keygen::Assembly::copy)
-    const size_t m = cs.perm.size(), cells = m * n;
-    std::vector<uint32_t> nxt(cells), root(cells), size(cells, 1);
-    for (size_t i = 0; i < cells; i++) nxt[i] = root[i] = (uint32_t)i;
-    for (size_t i = 0; i < n_copies; i++) {
-        const uint32_t* cp = copies + 4 * i;
-        invalid(cp[0] >= m || cp[2] >= m || cp[1] >= n || cp[3] >= n, "copy constraint out of range");
-        uint32_t a = cp[0] * n + cp[1], b = cp[2] * n + cp[3];
-        if (root[a] == root[b]) continue;
-        if (size[root[a]] < size[root[b]]) std::swap(a, b);
-        const uint32_t ra = root[a], rb = root[b];
-        size[ra] += size[rb];
-        uint32_t cur = b;
-        do {                                     // relabel the smaller cycle
-            root[cur] = ra;
-            cur = nxt[cur];
-        } while (cur != b);
-        std::swap(nxt[a], nxt[b]);
-    }
+    const size_t m = cs.perm.size();
+    const std::vector<uint32_t> nxt = copy_cycles(cs, copies, n_copies);
     lap("copy cycles (host)");
     // sigma[c][r] = delta^c' * omega^r' for (c', r') = nxt[(c, r)]: gathered on the device (ezkl_hip_permutation_sigma_dev) from the
     // resident omega^r column and the m powers of delta; only the successor map travels (4 B per cell)
@@ -1940,6 +1946,207 @@ static Col compress_column(const ConstraintSystem& cs, const Backend& be, const 
     chal.insert(chal.end(), user_chal.begin(), user_chal.end());
     prog.run(cols, chal, out->ptr());
     return out;
+}
+
+// ------------------------------------------------------------------ mock prover (halo2 MockProver::run + verify, /root/reference/src/execute.rs:1280-1305)
+// The assignment in Lagrange form, as given (no blinding rows): every gate on the usable rows, every lookup input row against the usable
+// table rows, every copy-constrained cell against its cycle successor.  No SRS, no key, no MSM or NTT.  The gates are ONE check program (each
+// gate polynomial stored to a slot of its own), the lookups are theta-compressed with a random theta as the prover does (compress_column),
+// the copies use the successor map keygen builds (copy_cycles).  Challenges and theta come from `seed` (Rng: ChaCha20; 0 = OS entropy).
+static void mock(ConstraintSystem& cs, const void* const* fixed_values, const uint32_t* copies, size_t n_copies, const void* const* advice,
+                 ezkl_advice_fn advice_fn, void* advice_user, const void* const* instances, const uint32_t* instance_lens, uint64_t seed,
+                 ezkl_check_record_t* out, size_t cap, uint64_t totals[3], size_t* n_out) {
+    const uint32_t n = cs.n, k = cs.k, u = cs.usable;
+    const size_t nl = cs.lookups.size(), m = cs.perm.size();
+    // host-side checks first: a malformed call is EZKL_ERR_INVALID with or without a device
+    for (uint32_t i = 0; i < cs.n_instance; i++) invalid(instance_lens[i] > n, "too many instance values");
+    const std::vector<uint32_t> nxt = copy_cycles(cs, copies, n_copies);
+    // Every column is resident at once: advice, fixed, instance, one compressed column per lookup input and table, the successor map, the
+    // lookup hash tables and the record buffers.  Checked up front (as check_key_fits does for a key), not inside a hipMalloc.
+    const uint32_t dcap = (uint32_t)std::min<size_t>(cap, (size_t)1 << 16);      // records kept per kind on the first pass
+    {
+        size_t free_b = 0, total_b = 0, pool[4] = {0, 0, 0, 0};
+        check(ezkl_hip_mem_info(&free_b, &total_b), "ezkl_hip_mem_info");       // no device: EZKL_ERR_NO_DEVICE
+        (void)ezkl_hip_pool_stats(pool);
+        uint64_t n_lookup_cols = 0;
+        for (auto& l : cs.lookups) n_lookup_cols += l.inputs.size() + 1;
+        const uint64_t cols = (uint64_t)cs.n_advice + cs.n_fixed + cs.n_instance + n_lookup_cols;
+        const uint64_t need = cols * n * 32 + (uint64_t)m * n * 4 + (uint64_t)nl * 4 * n * 4 + 3ull * dcap * 16;
+        const uint64_t avail = (uint64_t)free_b + pool[2];
+        if (need > avail) {
+            char msg[300];
+            snprintf(msg, sizeof msg, "mock: the %llu columns of this circuit (2^%u rows) need %.2f GiB on the device, %.2f GiB are available",
+                     (unsigned long long)cols, k, need / 1073741824.0, avail / 1073741824.0);
+            throw Error(EZKL_ERR_NOMEM, msg);
+        }
+    }
+    Backend be(k, n, nullptr, nullptr);
+    Rng rng(nullptr, nullptr, seed);
+    // 1. fixed and instance columns (the instance column is zero past its values)
+    std::vector<Col> fixed_cols, inst_cols, adv_cols(cs.n_advice);
+    for (uint32_t c = 0; c < cs.n_fixed; c++) fixed_cols.push_back(be.upload(fixed_values[c], n));
+    for (uint32_t i = 0; i < cs.n_instance; i++) {
+        std::vector<U256> vals(instance_lens[i]);
+        for (uint32_t j = 0; j < instance_lens[i]; j++) {
+            std::memcpy(vals[j].data(), (const uint8_t*)instances[i] + 32 * j, 32);
+            invalid(cmp(vals[j], FR.p) >= 0, "non-canonical instance value");
+        }
+        Col col = be.zeros(n);
+        if (!vals.empty()) be.set_rows(col, 0, vals);
+        inst_cols.push_back(col);
+    }
+    // 2. advice, phase by phase; the challenges of the second phase are drawn from the seed
+    std::vector<Fe> user_chal;
+    for (uint32_t phase = 0; phase < 2; phase++) {
+        std::vector<uint32_t> idxs;
+        for (uint32_t c = 0; c < cs.n_advice; c++)
+            if (cs.advice_phase[c] == phase) idxs.push_back(c);
+        if (phase == 1)
+            for (const U256& w : rng.vec(cs.n_challenges)) user_chal.push_back(Fe{w});
+        if (idxs.empty()) continue;
+        std::vector<std::vector<U256>> host;
+        std::vector<const void*> src(cs.n_advice, nullptr);
+        if (advice_fn) {
+            std::vector<void*> dst(cs.n_advice, nullptr);
+            if (!cs.advice_by_pointer) {
+                host.resize(cs.n_advice);
+                for (uint32_t c : idxs) {
+                    host[c].assign(n, U256{0, 0, 0, 0});
+                    dst[c] = host[c].data();
+                }
+            }
+            std::vector<U256> ch;
+            for (auto& f : user_chal) ch.push_back(f.v);
+            invalid(advice_fn(advice_user, phase, ch.data(), (uint32_t)ch.size(), dst.data()) != 0, "advice callback failed");
+            for (uint32_t c : idxs) src[c] = dst[c];
+        } else {
+            for (uint32_t c : idxs) src[c] = advice[c];
+        }
+        for (uint32_t c : idxs) {
+            invalid(src[c] == nullptr, "missing advice column");
+            adv_cols[c] = be.upload(src[c], n);
+        }
+    }
+    auto col_handle = [&](uint32_t kind, uint32_t c) -> Col { return kind == N_ADV ? adv_cols[c] : kind == N_INST ? inst_cols[c] : fixed_cols[c]; };
+    // every kind runs into a record buffer of its own; a kind with more failures than the first buffer held runs once more with room for
+    // min(cap, its count), so that `out` is complete whenever the total is at most cap
+    struct KindOut {
+        std::vector<uint64_t> counters;
+        std::vector<ezkl_check_record_t> recs;
+    };
+    auto collect = [&](size_t n_counters, const std::function<void(void*, uint32_t, void*)>& run) {
+        uint32_t c0 = dcap;
+        for (int pass = 0;; pass++) {
+            Col rec = be.alloc(std::max<size_t>(1, ((size_t)c0 * 16 + 31) / 32));
+            Col cnt = be.zeros((n_counters * 8 + 31) / 32);
+            run(rec->ptr(), c0, cnt->ptr());
+            KindOut o;
+            o.counters.resize(n_counters);
+            check(ezkl_hip_memcpy_d2h(o.counters.data(), cnt->ptr(), n_counters * 8), "ezkl_hip_memcpy_d2h");
+            if (pass == 0 && o.counters[0] > c0 && cap > c0) {
+                c0 = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(cap, o.counters[0]), UINT32_MAX);
+                continue;
+            }
+            o.recs.resize((size_t)std::min<uint64_t>(o.counters[0], c0));
+            if (!o.recs.empty()) check(ezkl_hip_memcpy_d2h(o.recs.data(), rec->ptr(), o.recs.size() * 16), "ezkl_hip_memcpy_d2h");
+            return o;
+        }
+    };
+    std::vector<ezkl_check_record_t> all;
+    for (int i = 0; i < 3; i++) totals[i] = 0;
+    // 3. gates: one program, gate g stored to slot slots[g], checked on rows [0, usable)
+    if (!cs.gates.empty()) {
+        Program prog(k, k);
+        std::vector<Col> cols;
+        std::map<std::pair<uint32_t, uint32_t>, uint32_t> index;
+        Lowering low{cs, prog,
+                     [&](uint32_t kind, uint32_t c) {
+                         auto key = std::make_pair(kind, c);
+                         auto it = index.find(key);
+                         if (it != index.end()) return it->second;
+                         index[key] = (uint32_t)cols.size();
+                         cols.push_back(col_handle(kind, c));
+                         return (uint32_t)cols.size() - 1;
+                     },
+                     [&](uint32_t idx) { return prog.challenge(idx); },
+                     {}};
+        std::vector<uint32_t> slots;
+        std::map<uint32_t, uint32_t> gate_of;
+        for (size_t g = 0; g < cs.gates.size(); g++) {
+            const Src t = prog.calc(EZKL_OP_STORE, low.lower(cs.gates[g]));
+            slots.push_back(t.idx);
+            gate_of[t.idx] = (uint32_t)g;
+        }
+        std::vector<const void*> ptrs;
+        for (auto& c : cols) ptrs.push_back(c->ptr());
+        const uint32_t n_cols = (uint32_t)ptrs.size();
+        if (ptrs.empty()) ptrs.push_back(nullptr);
+        std::vector<Fe> chal = user_chal;
+        if (chal.empty()) chal.push_back(Fe::zero());
+        ezkl_program_t p{};
+        p.code = prog.code.data();
+        p.n_instr = (uint32_t)(prog.code.size() / 8);
+        p.n_intermediates = prog.n_int;
+        p.constants = prog.constants.data();
+        p.n_constants = (uint32_t)prog.constants.size();
+        p.rotations = prog.rotations.data();
+        p.n_rotations = (uint32_t)prog.rotations.size();
+        p.columns = ptrs.data();
+        p.n_columns = n_cols;
+        p.challenges = chal.data();
+        p.n_challenges = (uint32_t)user_chal.size();
+        p.k = k;
+        p.ext_k = k;
+        KindOut o = collect(1, [&](void* rec, uint32_t c0, void* cnt) {
+            check(ezkl_hip_eval_check_dev(&p, slots.data(), (uint32_t)slots.size(), 0, u, rec, c0, cnt, nullptr), "ezkl_hip_eval_check_dev");
+        });
+        totals[0] = o.counters[0];
+        for (auto& r : o.recs) {
+            r.index = gate_of.at(r.index);
+            all.push_back(r);
+        }
+    }
+    // 4. lookups: every input and table compressed with a random theta, each input row probed in its table
+    if (nl) {
+        const Fe theta{rng.vec(1)[0]};
+        std::vector<Col> keep;
+        std::vector<const void*> in_ptrs, tab_ptrs;
+        std::vector<uint32_t> which;
+        for (size_t l = 0; l < nl; l++) {
+            for (auto& t : cs.lookups[l].inputs) {
+                keep.push_back(compress_column(cs, be, t, theta, col_handle, user_chal));
+                in_ptrs.push_back(keep.back()->ptr());
+                which.push_back((uint32_t)l);
+            }
+            keep.push_back(compress_column(cs, be, cs.lookups[l].table, theta, col_handle, user_chal));
+            tab_ptrs.push_back(keep.back()->ptr());
+        }
+        KindOut o = collect(1 + nl, [&](void* rec, uint32_t c0, void* cnt) {
+            check(ezkl_hip_lookup_missing_rows_dev(in_ptrs.data(), which.data(), (uint32_t)in_ptrs.size(), tab_ptrs.data(), (uint32_t)nl, n, u, rec, c0, cnt,
+                                                   nullptr),
+                  "ezkl_hip_lookup_missing_rows_dev");
+        });
+        totals[1] = o.counters[0];
+        all.insert(all.end(), o.recs.begin(), o.recs.end());
+    }
+    // 5. copies: every cell against its cycle successor
+    if (m) {
+        Col next = be.alloc(((size_t)m * n * 4 + 31) / 32);
+        check(ezkl_hip_memcpy_h2d(next->ptr(), nxt.data(), (size_t)m * n * 4), "ezkl_hip_memcpy_h2d");
+        std::vector<const void*> ptrs;
+        for (auto& pc : cs.perm) ptrs.push_back(col_handle(pc.first, pc.second)->ptr());
+        KindOut o = collect(1, [&](void* rec, uint32_t c0, void* cnt) {
+            check(ezkl_hip_copy_check_dev(ptrs.data(), (uint32_t)m, next->ptr(), k, rec, c0, cnt, nullptr), "ezkl_hip_copy_check_dev");
+        });
+        totals[2] = o.counters[0];
+        all.insert(all.end(), o.recs.begin(), o.recs.end());
+    }
+    std::sort(all.begin(), all.end(), [](const ezkl_check_record_t& a, const ezkl_check_record_t& b) {
+        return std::tie(a.kind, a.index, a.sub, a.row) < std::tie(b.kind, b.index, b.sub, b.row);
+    });
+    if (all.size() > cap) all.resize(cap);
+    if (!all.empty()) std::memcpy(out, all.data(), all.size() * sizeof(ezkl_check_record_t));
+    *n_out = all.size();
 }
 
 // ------------------------------------------------------------------ create_proof
@@ -3046,6 +3253,22 @@ int ezkl_prover_pk_set_transcript_repr(ezkl_pk_t h, const void* repr) {
     if (cmp(v, FR.p) >= 0) return EZKL_ERR_INVALID;              // a canonical scalar, as halo2 transcript_repr is
     h->pk->digest = Fe::from_canonical(v);
     return EZKL_OK;
+}
+int ezkl_prover_mock(ezkl_cs_t h, const void* const* fixed_values, const uint32_t* copies, size_t n_copies, const void* const* advice, ezkl_advice_fn advice_fn,
+                     void* advice_user, const void* const* instances, const uint32_t* instance_lens, uint64_t seed, ezkl_check_record_t* out, size_t cap,
+                     uint64_t totals[3], size_t* n_out) {
+    if (!h || !totals || !n_out || (cap && !out)) return EZKL_ERR_INVALID;
+    const ConstraintSystem& cs = *h->cs;
+    if ((cs.n_fixed && !fixed_values) || (n_copies && !copies) || (cs.n_instance && (!instances || !instance_lens))) return EZKL_ERR_INVALID;
+    if (cs.n_advice && !advice && !advice_fn) return EZKL_ERR_INVALID;
+    for (uint32_t c = 0; c < cs.n_fixed; c++)
+        if (!fixed_values[c]) return EZKL_ERR_INVALID;
+    for (uint32_t c = 0; c < cs.n_advice && !advice_fn; c++)
+        if (!advice[c]) return EZKL_ERR_INVALID;
+    for (uint32_t i = 0; i < cs.n_instance; i++)
+        if (instance_lens[i] && !instances[i]) return EZKL_ERR_INVALID;
+    *n_out = 0;
+    return guarded([&] { mock(*h->cs, fixed_values, copies, n_copies, advice, advice_fn, advice_user, instances, instance_lens, seed, out, cap, totals, n_out); });
 }
 int ezkl_prover_create_proof(ezkl_pk_t pk, ezkl_bases_t g, ezkl_bases_t g_lagrange, const void* const* advice, ezkl_advice_fn advice_fn, void* advice_user,
                              const void* const* instances, const uint32_t* instance_lens, ezkl_rng_fn rng, void* rng_user, uint64_t seed, void* proof_out,

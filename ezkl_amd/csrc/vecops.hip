@@ -486,6 +486,116 @@ int lookup_multiplicity(Ctx* c, hipStream_t st, const fe_t* const* inputs, uint3
     return lookup_multiplicity_batch(c, st, inputs, which.data(), n_inputs, &table, 1, n_rows, usable, &m_out, missing_host, missing_dev);
 }
 
+// ---- the mock prover's reports (ezkl_hip_lookup_missing_rows_dev, ezkl_hip_copy_check_dev) ----
+// A failing lane appends one 16-byte record; the failing lanes of a wave take consecutive slots with ONE atomic on the shared cursor
+// (count[0]), and slots at or past cap are counted but never written.  per (may be NULL): a second counter the wave's failures are added to.
+EZ_D void report_append(bool fail, uint4 r, uint4* rec, uint32_t cap, unsigned long long* count, unsigned long long* per) {
+    const unsigned long long m = __ballot(fail);
+    if (!m) return;
+    const uint32_t lane = threadIdx.x & 63, leader = __ffsll(m) - 1;
+    unsigned long long base = 0;
+    if (lane == leader) {
+        base = atomicAdd(count, (unsigned long long)__popcll(m));
+        if (per) atomicAdd(per, (unsigned long long)__popcll(m));
+    }
+    base = ((unsigned long long)__shfl((uint32_t)(base >> 32), (int)leader) << 32) | __shfl((uint32_t)base, (int)leader);
+    const unsigned long long at = base + __popcll(m & ((1ull << lane) - 1));
+    if (fail && at < cap) rec[at] = r;
+}
+// ht_count_kernel's probe, reporting instead of counting: input item y (argument which[y], its sub[y]-th input) on row i is absent from
+// the hash table of its argument's table -> {2, which[y], sub[y], i}; count[1 + which[y]] is that argument's total
+__global__ __launch_bounds__(256) void ht_miss_kernel(const fe_t* const* inputs, const uint32_t* which, const uint32_t* sub, uint32_t rows,
+                                                      const fe_t* const* tables, const uint32_t* slots, uint32_t hcap, uint4* rec, uint32_t cap,
+                                                      unsigned long long* count) {
+    const uint32_t l = which[blockIdx.y], mask = hcap - 1;
+    const fe_t* input = inputs[blockIdx.y];
+    const fe_t* table = tables[l];
+    slots += (size_t)l * hcap;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool absent = false;
+    if (i < rows) {
+        const fe_t key = ld_fe(input + i);
+        uint32_t h = ht_hash(key, mask);
+        for (;;) {
+            const uint32_t cur = slots[h];
+            if (cur == HT_EMPTY) { absent = true; break; }
+            if (Fr::eq(ld_fe(table + cur), key)) break;
+            h = (h + 1) & mask;
+        }
+    }
+    report_append(absent, make_uint4(2u, l, sub[blockIdx.y], i), rec, cap, count, count + 1 + l);
+}
+int lookup_missing_rows(Ctx* c, hipStream_t st, const fe_t* const* inputs, const uint32_t* which, uint32_t n_items, const fe_t* const* tables,
+                        uint32_t n_lookups, uint32_t n_rows, uint32_t usable, void* rec, uint32_t cap, void* count) {
+    if (usable > n_rows || n_lookups == 0 || n_lookups > 65535 || n_items > 65535) return EZKL_ERR_INVALID;
+    std::vector<uint32_t> sub(n_items ? n_items : 1, 0), seen(n_lookups, 0);
+    for (uint32_t y = 0; y < n_items; y++) {
+        if (which[y] >= n_lookups) return EZKL_ERR_INVALID;
+        sub[y] = seen[which[y]]++;                    // the position of the input among its argument's inputs
+    }
+    if (usable == 0 || n_items == 0) return EZKL_OK;
+    uint32_t hcap = 16;                               // the table size of lookup_multiplicity_batch
+    while (hcap < 2 * usable) hcap <<= 1;
+    const size_t n_ptr = (size_t)n_items + n_lookups;
+    const size_t words = 2 * (size_t)n_items + (size_t)n_lookups * hcap;
+    uint8_t* d = nullptr;
+    int rc = arena_reserve(c->aux, n_ptr * 8 + words * 4, st, (void**)&d);
+    if (rc) return rc;
+    std::vector<uint8_t> head(n_ptr * 8 + 2 * (size_t)n_items * 4);
+    memcpy(head.data(), inputs, (size_t)n_items * 8);
+    memcpy(head.data() + (size_t)n_items * 8, tables, (size_t)n_lookups * 8);
+    memcpy(head.data() + n_ptr * 8, which, (size_t)n_items * 4);
+    memcpy(head.data() + n_ptr * 8 + (size_t)n_items * 4, sub.data(), (size_t)n_items * 4);
+    const fe_t** d_inputs = reinterpret_cast<const fe_t**>(d);
+    const fe_t** d_tables = d_inputs + n_items;
+    uint32_t* d_which = reinterpret_cast<uint32_t*>(d + n_ptr * 8);
+    uint32_t *d_sub = d_which + n_items, *slots = d_sub + n_items;
+    EZ_HIP(hipMemcpyAsync(d, head.data(), head.size(), hipMemcpyHostToDevice, st));
+    EZ_HIP(hipMemsetAsync(slots, 0xff, (size_t)n_lookups * hcap * 4, st));
+    hipLaunchKernelGGL(ht_build_kernel, dim3(cdiv(usable, 256), n_lookups), dim3(256), 0, st, d_tables, usable, slots, hcap);
+    hipLaunchKernelGGL(ht_miss_kernel, dim3(cdiv(usable, 256), n_items), dim3(256), 0, st, d_inputs, (const uint32_t*)d_which, (const uint32_t*)d_sub,
+                       usable, d_tables, (const uint32_t*)slots, hcap, (uint4*)rec, cap, (unsigned long long*)count);
+    EZ_HIP(hipGetLastError());
+    if ((rc = arena_done(c->aux, st))) return rc;
+    EZ_HIP(hipStreamSynchronize(st));                 // `head` is pageable host memory
+    return EZKL_OK;
+}
+// cell t = c n + r of the m columns against its cycle successor next[t]: 4 B of map and two 32-B reads per cell; a mismatch (or a successor
+// outside the m columns, which no cycle map has) -> {3, c, 0, r}
+__global__ __launch_bounds__(256) void copy_check_kernel(const fe_t* const* cols, const uint32_t* next, uint32_t log_n, uint32_t m, uint4* rec,
+                                                         uint32_t cap, unsigned long long* count) {
+    const size_t cells = (size_t)m << log_n, n = (size_t)1 << log_n;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    // the loop runs whole waves to its end (the report is a ballot over the wave): lanes past the last cell take part without a cell
+    for (size_t base = (size_t)blockIdx.x * blockDim.x; base < cells; base += stride) {
+        const size_t t = base + threadIdx.x;
+        bool bad = false;
+        uint32_t c = 0, r = 0;
+        if (t < cells) {
+            const uint32_t s = next[t];
+            c = (uint32_t)(t >> log_n);
+            r = (uint32_t)(t & (n - 1));
+            const uint32_t sc = s >> log_n;
+            bad = sc >= m || !Fr::eq(ld_fe(cols[c] + r), ld_fe(cols[sc] + (s & (uint32_t)(n - 1))));
+        }
+        report_append(bad, make_uint4(3u, c, 0u, r), rec, cap, count, nullptr);
+    }
+}
+int copy_check(Ctx* c, hipStream_t st, const fe_t* const* cols, uint32_t m, const uint32_t* next, uint32_t log_n, void* rec, uint32_t cap, void* count) {
+    if (m == 0) return EZKL_OK;
+    const fe_t** d = nullptr;
+    int rc = arena_reserve(c->aux, (size_t)m * 8, st, (void**)&d);
+    if (rc) return rc;
+    EZ_HIP(hipMemcpyAsync(d, cols, (size_t)m * 8, hipMemcpyHostToDevice, st));
+    const size_t cells = (size_t)m << log_n;
+    hipLaunchKernelGGL(copy_check_kernel, dim3(stream_grid(c, cells)), dim3(256), 0, st, (const fe_t* const*)d, next, log_n, m, (uint4*)rec, cap,
+                       (unsigned long long*)count);
+    EZ_HIP(hipGetLastError());
+    if ((rc = arena_done(c->aux, st))) return rc;
+    EZ_HIP(hipStreamSynchronize(st));                 // `cols` is the caller's host array
+    return EZKL_OK;
+}
+
 // ---- polynomial evaluation at a point (halo2 eval_polynomial: hundreds of O(n) Horner reductions per proof,
 //      create_proof step 10 in SURVEY.md §3.1; A14) ----
 // lane t evaluates its 32-coefficient segment by Horner, scales it by x^(32 t) (square-and-multiply on the lane

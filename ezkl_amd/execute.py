@@ -5,6 +5,7 @@
     setup(compiled_circuit, srs_path, vk_path, pk_path)                         execute.rs:1543-1572 -> pfsys::create_keys (mod.rs:376-400)
     gen_witness(compiled_circuit, data, output, vk_path, srs_path)               execute.rs:577-660 -> GraphCircuit::forward (graph/mod.rs:1734-1849)
     prove(witness, compiled_circuit, pk_path, proof_path, srs_path, check_mode)  execute.rs:1575-1627 -> create_proof_circuit (mod.rs:404-489)
+    mock(witness, compiled_circuit)                                              execute.rs:1280-1305 -> MockProver::run(..).verify()
     verify(proof_path, compiled_circuit, pk_path, srs_path)                      execute.rs:1651-1722 -> verify_proof_circuit (mod.rs:557-590)
 
 File formats are the reference's: kzg*.srs / pk.key / vk.key in halo2 raw bytes, witness.json (GraphWitness), proof.json (Snark) and
@@ -361,7 +362,73 @@ def verify(proof_path, compiled_circuit, vk_path=None, srs_path=None, recommit=F
 def _plonk_cs(circuit):
     """the constraint system as keygen saw it: re-running `configure` + selector compression (halo2 does the same on load_pk,
     src/pfsys/mod.rs:627) -- a fresh synthesis pass without witness values gives the selector activations"""
+    return _fresh_keygen_inputs(circuit)[0]
+
+
+def _fresh_keygen_inputs(circuit):
+    """(cs, fixed, copies, region) of a fresh synthesis pass without witness values: what keygen saw"""
     fresh = EL.MlpCircuit(circuit.k, circuit.w, circuit.weights, circuit.biases, circuit.base, circuit.legs,
                           total_assignments=circuit.settings.total_assignments, relu_last=circuit.relu_last, n_inputs=circuit.n_inputs,
                           relu_first=circuit.relu_first)
-    return fresh.keygen_inputs([0] * circuit.n_inputs)[0]
+    return fresh.keygen_inputs([0] * circuit.n_inputs)
+
+
+class MockError(ValueError):
+    """`mock` found unsatisfied constraints: .records = [(kind, index, sub, row)] (kind 1 gate, 2 lookup, 3 copy; at most the first
+    MOCK_CAP, sorted), .totals = exact failure counts (gates, lookups, copies)"""
+
+    def __init__(self, msg, records, totals):
+        super().__init__(msg)
+        self.records, self.totals = records, totals
+
+
+MOCK_CAP = 1024
+_KIND_NAMES = {"adv": "advice", "fix": "fixed", "inst": "instance"}
+
+
+def mock(witness_path, compiled_circuit):
+    """`ezkl mock` (/root/reference/src/execute.rs:1280-1305: MockProver::run(logrows, &circuit, public_inputs).verify()) on the GPU: the
+    witness is laid out by the synthesis `prove` uses and every gate, lookup and copy constraint is checked row by row
+    (native.mock -> ezkl_prover_mock).  No SRS, no keys.  The public inputs are the witness file's outputs (prepare_public_inputs), so a
+    wrong output is a failing copy into the instance column.  Returns "" when every constraint holds; raises MockError otherwise, its message
+    naming the first failures (gate / row, lookup / input / row, the two cells of a copy)."""
+    w = codecs.read_witness_json(open(witness_path).read())
+    circuit, j = _load_circuit(compiled_circuit)
+    if len(w["inputs"]) != 1 or len(w["inputs"][0]) != circuit.n_inputs:
+        raise ValueError("witness does not match the circuit's input shape")
+    signed = lambda v: v if v < EL.R // 2 else v - EL.R
+    adv, inst = circuit.witness([signed(v) for v in w["inputs"][0]])            # GraphCircuit::synthesize
+    public = [list(c) for c in w["outputs"]] if w["outputs"] else inst
+    cs, fixed, copies, _ = _fresh_keygen_inputs(circuit)
+    records, totals = NV.mock(cs, EL.cols_to_mont(fixed, B), copies, EL.cols_to_mont(adv, B), instances=public, seed=1, cap=MOCK_CAP)
+    if not any(totals):
+        return ""
+    cols = {"adv": adv, "fix": fixed, "inst": [list(c) + [0] * (cs.n - len(c)) for c in public]}
+    value = lambda cell: int(cols[cs.perm[cell[0]][0]][cs.perm[cell[0]][1]][cell[1]]) % EL.R
+    name = lambda cell: "%s %d, row %d" % (_KIND_NAMES[cs.perm[cell[0]][0]], cs.perm[cell[0]][1], cell[1])
+    cycles = None
+    lines = []
+    for kind, index, sub, row in records[:10]:
+        if kind == 1:
+            lines.append("gate %d not satisfied on row %d" % (index, row))
+        elif kind == 2:
+            lines.append("lookup %d input %d row %d: not in table" % (index, sub, row))
+        else:
+            if cycles is None:                                                  # the copy cycles, for naming the cell a failing one differs from
+                parent = {}
+                def find(x):
+                    while parent.setdefault(x, x) != x:
+                        parent[x] = parent[parent[x]]
+                        x = parent[x]
+                    return x
+                for a, b in copies:
+                    parent[find(tuple(a))] = find(tuple(b))
+                cycles = {}
+                for x in list(parent):
+                    cycles.setdefault(find(x), []).append(x)
+                cycles = {x: members for members in cycles.values() for x in members}
+            cell = (index, row)
+            other = next((o for o in sorted(cycles.get(cell, [])) if value(o) != value(cell)), None)
+            lines.append("copy (%s) != (%s)" % (name(cell), name(other)) if other else "copy (%s) differs from its copy cycle" % name(cell))
+    msg = "mock: %d gate, %d lookup and %d copy constraint failures: %s" % (totals[0], totals[1], totals[2], "; ".join(lines))
+    raise MockError(msg, records, totals)

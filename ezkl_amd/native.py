@@ -16,7 +16,7 @@ _lib = None
 SYMBOLS = ["ezkl_prover_cs_parse", "ezkl_prover_cs_free", "ezkl_prover_cs_info", "ezkl_prover_cs_set_shard", "ezkl_prover_cs_set_shard_comm", "ezkl_prover_cs_set_shard_full_bases", "ezkl_prover_cs_set_advice_by_pointer", "ezkl_prover_cs_set_sweep_gather",
            "ezkl_prover_cs_sharded_sweeps", "ezkl_prover_cs_set_shard_exchange", "ezkl_prover_cs_shard_stats", "ezkl_prover_group_create", "ezkl_prover_group_size", "ezkl_prover_group_free",
            "ezkl_prover_group_load_srs", "ezkl_prover_group_keygen", "ezkl_prover_group_pk", "ezkl_prover_group_pk_read_file", "ezkl_prover_pk_residency", "ezkl_prover_group_create_proof", "ezkl_prover_keygen", "ezkl_prover_pk_free", "ezkl_prover_pk_sweep_stats", "ezkl_prover_pk_write", "ezkl_prover_pk_read", "ezkl_prover_pk_read_file", "ezkl_prover_pk_recommit", "ezkl_prover_pk_set_selectors", "ezkl_prover_pk_set_transcript_repr", "ezkl_prover_vk",
-           "ezkl_prover_create_proof", "ezkl_prover_create_proof_fmt", "ezkl_prover_verify_proof", "ezkl_prover_verify_proof_vk", "ezkl_prover_g2_mul_generator", "ezkl_prover_keccak256", "ezkl_prover_last_error"]
+           "ezkl_prover_create_proof", "ezkl_prover_create_proof_fmt", "ezkl_prover_mock", "ezkl_prover_verify_proof", "ezkl_prover_verify_proof_vk", "ezkl_prover_g2_mul_generator", "ezkl_prover_keccak256", "ezkl_prover_last_error"]
 ADVICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p))
 RNG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_size_t)
 FOLD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32)
@@ -447,3 +447,64 @@ def create_proof(pk, g, g_lagrange, advice_values, rng=None, seed=0, instances=(
         if not verify_proof(pk, g2, s_g2, proof, instances):
             raise RuntimeError("SAFE check failed: the proof just made does not verify")
     return proof
+
+
+class CheckRecord(C.Structure):
+    """ezkl_check_record_t (include/ezkl_hip.h): kind 1 gate, 2 lookup, 3 copy"""
+    _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("sub", C.c_uint32), ("row", C.c_uint32)]
+
+
+def mock(cs, fixed, copies, advice, instances=(), seed=1, cap=1024):
+    """halo2's MockProver::run(k, circuit, instances).verify() on the GPU (ezkl_prover_mock): no SRS, no keys.  cs: plonk.ConstraintSystem;
+    fixed: Montgomery (n, 4) uint64 columns; copies: as for NativeProvingKey; advice: list of Montgomery columns, or a callable
+    advice(phase, challenges) -> {column: array} (second-phase advice: the challenges are drawn from `seed`); instances: lists of ints.
+    Returns (records, totals): records = up to `cap` tuples (kind, index, sub, row) sorted, kind 1 = gate `index` on `row`, 2 = input `sub`
+    of lookup `index` on `row`, 3 = cell (permutation column position `index`, `row`) differs from its copy-cycle successor; totals = exact
+    failure counts (gates, lookups, copies).  The records are complete whenever sum(totals) <= cap."""
+    n = cs.n
+    circuit = NativeCircuit(cs)
+    try:
+        fx = [np.ascontiguousarray(v, np.uint64).reshape(n, 4) for v in fixed]
+        cp = _copies_array(copies)
+        keep = []
+        adv_arr, adv_cb = None, C.cast(None, ADVICE_FN)
+        if callable(advice):
+            _check(load().ezkl_prover_cs_set_advice_by_pointer(circuit.h, 1), "ezkl_prover_cs_set_advice_by_pointer")
+            def _cb(_user, phase, chal_ptr, n_chal, cols_ptr):
+                try:
+                    ch = np.ctypeslib.as_array(C.cast(chal_ptr, C.POINTER(C.c_uint64)), shape=(n_chal, 4)) if n_chal else np.zeros((0, 4), np.uint64)
+                    vals = advice(int(phase), [_pl.from_mont(c) for c in ch])
+                    for c, a in vals.items():
+                        if cs.advice_phase[c] != phase:
+                            continue
+                        a = np.ascontiguousarray(a, np.uint64)
+                        assert a.size == 4 * n
+                        keep.append(a)                # by pointer: the array must outlive the call
+                        cols_ptr[c] = a.ctypes.data
+                    return 0
+                except Exception:                     # never unwind through the C frames
+                    import traceback
+                    traceback.print_exc()
+                    return 1
+            adv_cb = ADVICE_FN(_cb)
+        else:
+            for i, a in enumerate(advice):
+                a = np.ascontiguousarray(a, np.uint64)
+                if a.size != 4 * n:
+                    raise ValueError("advice column %d: expected (n, 4) uint64 Montgomery words with n = %d; got %s" % (i, n, a.shape))
+                keep.append(a.reshape(n, 4))
+            if len(keep) != cs.n_advice:
+                raise ValueError("%d advice columns given, the circuit has %d" % (len(keep), cs.n_advice))
+            adv_arr = _ptr_array(keep)
+        inst = [np.stack([_pl.to_mont(v) for v in vals]) if len(vals) else np.zeros((0, 4), np.uint64) for vals in instances]
+        if len(inst) != cs.n_instance:
+            raise ValueError("%d instance columns given, the circuit has %d" % (len(inst), cs.n_instance))
+        lens = (C.c_uint32 * max(1, len(inst)))(*[a.shape[0] for a in inst])
+        out = (CheckRecord * max(1, cap))()
+        totals = (C.c_uint64 * 3)()
+        n_out = C.c_size_t(0)
+        _check(load().ezkl_prover_mock(circuit.h, _ptr_array(fx), cp.ctypes.data_as(C.c_void_p), C.c_size_t(cp.shape[0]), adv_arr, adv_cb, None,
+                                       _ptr_array(inst), lens, C.c_uint64(seed), out, C.c_size_t(cap), totals, C.byref(n_out)), "ezkl_prover_mock")
+        return [(r.kind, r.index, r.sub, r.row) for r in out[:n_out.value]], tuple(int(t) for t in totals)
+    finally:
+        circuit.free()

@@ -380,6 +380,33 @@ int ezkl_hip_eval_h_prepare(const ezkl_program_t* prog);
 /* how this process obtained its sweep kernels so far: compiled by hiprtc, loaded from the on-disk cache, found in memory */
 int ezkl_hip_eval_h_jit_stats(uint64_t* compiled, uint64_t* from_disk, uint64_t* memory_hits);
 
+/* ---- mock prover: report the failing constraints instead of folding them into a quotient or a count (halo2 MockProver::verify) ----
+ * Every call appends 16-byte records {kind, index, sub, row} to records_dev through a cursor: counters_dev[0] (device u64, zeroed by the
+ * caller for a fresh list) is ADDED the number of failures found, and failure i of the call goes to records_dev[cursor_before + i] when that
+ * is below cap -- failures past cap are counted, never written (records_dev may be NULL when cap = 0).  The order of the records is
+ * unspecified.  The calls return after their kernels have run. */
+typedef struct { uint32_t kind, index, sub, row; } ezkl_check_record_t;   /* kind 1 gate, 2 lookup, 3 copy */
+/* Gate check: the program runs with ext_k == k on the Lagrange rows themselves (a rotation is a row offset, indices wrap mod 2^k).  For
+ * every row in [row_lo, row_hi) and every listed intermediate j (written by the program, listed once) whose final value is not zero:
+ * {1, j, 0, row}.  JIT-compiled like the sweep (same validation, scheduling and on-disk cache, a cache identity of its own); radix-2^29
+ * generators only: EZKL_EVALH_R29=0 gives EZKL_ERR_INVALID. */
+int ezkl_hip_eval_check_dev(const ezkl_program_t* prog, const uint32_t* check_slots, uint32_t n_checks, uint32_t row_lo, uint32_t row_hi, void* records_dev,
+                            uint32_t cap, void* counters_dev, void* stream);
+/* host-only: the source of that check kernel, with the contract of ezkl_hip_eval_h_source */
+int ezkl_hip_eval_check_source(const ezkl_program_t* prog, const uint32_t* check_slots, uint32_t n_checks, char* out, size_t cap, size_t* len);
+/* Lookup miss rows: the inputs and tables of ezkl_hip_lookup_multiplicity_batch_dev (theta-compressed columns; input j belongs to argument
+ * input_lookup[j]).  For every usable row r of an input absent from the usable rows of its table: {2, lookup, input, r}, `input` counting
+ * the argument's own inputs from 0.  counters_dev holds 1 + n_lookups u64: the cursor, then per argument the number of its misses (the
+ * `missing` of lookup_multiplicity_batch_dev on the same columns). */
+int ezkl_hip_lookup_missing_rows_dev(const void* const* inputs_dev, const uint32_t* input_lookup, uint32_t n_inputs, const void* const* tables_dev,
+                                     uint32_t n_lookups, uint32_t n_rows, uint32_t usable_rows, void* records_dev, uint32_t cap, void* counters_dev,
+                                     void* stream);
+/* Copy check: m columns of 2^log_n rows (cols_dev: m device pointers in host memory), cells numbered c 2^log_n + r as in
+ * ezkl_hip_permutation_sigma_dev; next_dev (device u32, m 2^log_n entries) = the cycle successor of every cell.  Every cell whose value
+ * differs from its successor's (or whose successor lies outside the m columns): {3, c, 0, r}. */
+int ezkl_hip_copy_check_dev(const void* const* cols_dev, uint32_t m, const void* next_dev, uint32_t log_n, void* records_dev, uint32_t cap, void* counters_dev,
+                            void* stream);
+
 /* ---- multi-GPU: the collectives of the sharded prove path, RCCL over xGMI on the library's device pointers (csrc/comm.hip) ----
  * One process per GPU (ezkl_hip_init picks the device).  The reference has no multi-GPU path (icicle is single-GPU), so
  * these replace nothing: a launcher creates the id on rank 0 (ezkl_hip_comm_unique_id), hands the 128 bytes to every rank by whatever

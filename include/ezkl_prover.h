@@ -203,6 +203,19 @@ int ezkl_prover_create_proof_fmt(ezkl_pk_t pk, ezkl_bases_t g, ezkl_bases_t g_la
                                  ezkl_advice_fn advice_fn, void* advice_user, const void* const* instances, const uint32_t* instance_lens, ezkl_rng_fn rng,
                                  void* rng_user, uint64_t seed, void* proof_out, size_t cap, size_t* proof_len, double* timings);
 
+/* ---- mock: halo2's MockProver::run(k, circuit, instances).verify() (/root/reference/src/execute.rs:1280-1305) on the GPU ----
+ * The assignment is checked in Lagrange form, as given: no SRS, no key, no blinding.  fixed_values / copies as for ezkl_prover_keygen,
+ * advice / advice_fn / advice_user and instances / instance_lens as for ezkl_prover_create_proof (the second phase's challenges, and the
+ * theta that compresses the lookups, are drawn from `seed` with the library's generator; 0 = OS entropy).  Checked: every gate on rows
+ * [0, usable) (kind 1, index = gate), every usable input row of every lookup against the usable rows of its table (kind 2, index = lookup,
+ * sub = its input), every copy-constrained cell against its cycle successor (kind 3, index = permutation column position, row).
+ * totals = the exact number of failures per kind; out receives min(cap, total) records sorted by (kind, index, sub, row), *n_out of them
+ * -- the complete set whenever the total is at most cap.  Every column must fit on the device at once: EZKL_ERR_NOMEM up front otherwise.
+ * EZKL_ERR_NO_DEVICE without a GPU. */
+int ezkl_prover_mock(ezkl_cs_t cs, const void* const* fixed_values, const uint32_t* copies, size_t n_copies, const void* const* advice, ezkl_advice_fn advice_fn,
+                     void* advice_user, const void* const* instances, const uint32_t* instance_lens, uint64_t seed, ezkl_check_record_t* out, size_t cap,
+                     uint64_t totals[3], size_t* n_out);
+
 /* ---- verify_proof: the verifier of these proofs, on the host (pairing in csrc/prover/pairing.hpp) ----
  * /root/reference/src/pfsys/mod.rs:557-590 verify_proof_circuit, and the CheckMode::SAFE self-check of create_proof_circuit (:470-480:
  * every proof is verified before it is returned).  pk supplies the constraint system and the verifying key (commitments + digest);

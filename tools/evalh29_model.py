@@ -63,6 +63,8 @@ LINE_SHAPES = [
     ("reduce", re.compile(r"v(\d+) = %s\(v(\d+), c_one\);$" % _MUL)),
     ("horner", re.compile(r"v(\d+) = Fr29::add\(%s\(v(\d+), %s\), %s\);$" % (_MUL, _OPND, _OPND))),
     ("store", re.compile(r"st_fe\(out \+ r, Fr29::pack\(Fr29::cond_sub<0>\(%s\(v(\d+), c_r256\)\)\)\);$" % _MUL)),
+    # the check kernel of the mock prover (ezkl_hip_eval_check_dev): slot's value reduced as the store's is, then compared with zero
+    ("check", re.compile(r"ezkl_report\(!Fr::is_zero\(Fr29::pack\(Fr29::cond_sub<0>\(%s\(v(\d+), c_r256\)\)\)\), (\d+)u, r, rec, cap, count\);$" % _MUL)),
     ("barrier", re.compile(r"(?:asm volatile\(\"\" ::: \"memory\"\)|__builtin_amdgcn_sched_barrier\(0\));$")),
 ]
 # what the model's ld29 / constants assume about the preamble of the generated file
@@ -70,6 +72,7 @@ _PREAMBLE = ["r.v[0] = (w.v[0] << 5) & M29;", "const int bit = 29 * i - 5, word 
              "r.v[i] = (sh ? __builtin_amdgcn_alignbit(hi, lo, sh) : lo) & M29;", "r.v[8] = w.v[7] >> 3;",
              "const f29_t c_one = Fr29::one();", "const f29_t c_r256 = Fr29::unpack(Fr::one());"]
 _LOOP = "for (uint32_t r = tid; r <= ne_mask; r += T) {"
+_LOOP_CHECK = "for (uint32_t r = row_lo + tid; r < row_hi; r += T) {"
 
 
 def body(src):
@@ -77,7 +80,7 @@ def body(src):
     lines = src.splitlines()
     for s in _PREAMBLE:
         assert s in src, "generated preamble changed: %r not found" % s
-    start = [i for i, l in enumerate(lines) if l.strip() == _LOOP]
+    start = [i for i, l in enumerate(lines) if l.strip() in (_LOOP, _LOOP_CHECK)]
     assert len(start) == 1, "row loop not found"
     out = []
     for i in range(start[0] + 1, len(lines)):
@@ -102,7 +105,13 @@ def parse(src):
                 break
         else:
             raise AssertionError("line %d: not a shape the model knows: %s" % (ln, t))
-    assert prog and prog[-1][0] == "store" and sum(k == "store" for k, _, _ in prog) == 1, "the body must end in its one store"
+    n_store, n_check = sum(k == "store" for k, _, _ in prog), sum(k == "check" for k, _, _ in prog)
+    if n_check:                                        # a check kernel: no store, every listed slot tested once
+        assert n_store == 0, "a check kernel stores nothing"
+        slots = [int(g[1]) for k, g, _ in prog if k == "check"]
+        assert len(set(slots)) == len(slots), "a slot is checked twice"
+    else:
+        assert prog and prog[-1][0] == "store" and n_store == 1, "the body must end in its one store"
     return prog
 
 
@@ -231,6 +240,7 @@ def run(src, dom):
         if isinstance(dom, Bound):
             peak[0] = max(peak[0], val[1])
 
+    checks = []
     for kind, g, ln in prog:
         try:
             if kind == "add":
@@ -250,10 +260,14 @@ def run(src, dom):
             elif kind == "horner":
                 t = "v" + g[0]
                 define(t, dom.add(dom.mul(opnd(t), opnd(g[2])), opnd(g[3])), False)
+            elif kind == "check":
+                checks.append((int(g[1]), dom.final(opnd("v" + g[0]))))
             else:
                 return dom.final(opnd("v" + g[0])), (peak[0] if isinstance(dom, Bound) else None)
         except AssertionError as e:
             raise AssertionError("line %d (%s): %s" % (ln, kind, e)) from None
+    if checks:
+        return checks, (peak[0] if isinstance(dom, Bound) else None)
     raise AssertionError("unreachable")
 
 
@@ -267,6 +281,11 @@ def concrete(src, cols, consts, chal, prev):
     """concrete mode: one row.  cols[i] is the word every rotation of column i reads in this row (the dumped source is generated with
     every rotation offset at 0); words are the Montgomery forms x 2^256 mod p as integers.  Returns the 256-bit word the kernel stores."""
     return run(src, Concrete(cols, consts, chal, prev))[0]
+
+
+def concrete_checks(src, cols, consts, chal):
+    """concrete mode of a check kernel: one row -> {slot: the 256-bit word its value reduces to} (the kernel reports the slot if non-zero)"""
+    return dict(run(src, Concrete(cols, consts, chal, 0))[0])
 
 
 # ---- the plain big-int evaluation of a program ------------------------------------------------------------------------------------
