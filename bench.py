@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json configs[1]: 2^20-point BN254 G1 MSM + 2^22 Fr NTT microbench per MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of synthetic input already resident in HBM:
@@ -11,6 +11,12 @@ reported under "extra" (elems/s).  Multi-GPU (weak scaling): e
 2^20-point slice; each step ends with an RCCL all_gather of the 64-byte partial points and a host fold,
 the only exchange the path has.  NTT columns are independent per rank (no collective).
 Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline needs: set-up, warm-up, the two timed regions, --dump-outputs,
+the line.  --full adds everything else the benchmark measures or checks: per-kernel device times and the
+product / copy micro-benchmarks, the side legs (two MSMs in flight, witness-like scalars, inverse and coset
+NTTs), the CPU baselines and the end-to-end prove legs, and with N ranks the strong-scaling MSMs and the
+sharded proofs.
 """
 import argparse
 import json
@@ -65,9 +71,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side-legs", action="store_true", help="only the two timed regions of the contract (uniform 2^20 MSM, 2^22 NTT): no two-in-flight, "
-                    "witness-like, inverse / coset legs -- what tools/profile_bench.sh profiles, so that rocprofv3's per-kernel averages are those of the headline")
+    ap.add_argument("--full", action="store_true", help="also every figure and check beyond the headline (see the module docstring); a plain run "
+                    "is set-up, warm-up, the two timed regions and the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines and no prove legs")
+    ap.add_argument("--no-side-legs", action="store_true", help="with --full: no two-in-flight, witness-like, inverse / coset legs")
     ap.add_argument("--with-batch", action="store_true", help="also time the pipelined 4-column batch commit (extra.msm_batch4_*)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for 1-GPU plumbing tests)")
     ap.add_argument("--share-device", action="store_true", help="testing only: every rank uses GPU 0")
@@ -160,18 +167,20 @@ def main():
     errors = []
     if acc_cnt != args.steps or B.kernel_ms_stats("msm")[1] != 0:      # bookkeeping, never worth the headline line
         errors.append("msm_accumulate event pairs harvested: %d for %d timed steps" % (acc_cnt, args.steps))
-    for _ in range(max(5, args.steps // 2)):            # whole-chain device time (both event pairs recorded): outside the timed region
-        msm_step()
-    barrier_sync()
-    msm_sum, msm_cnt = B.kernel_ms_stats("msm")
-    msm_ms = [msm_sum / max(1, msm_cnt)]
+    if args.full:
+        for _ in range(max(5, args.steps // 2)):        # whole-chain device time (both event pairs recorded): outside the timed region
+            msm_step()
+        barrier_sync()
+        msm_sum, msm_cnt = B.kernel_ms_stats("msm")
+        msm_ms = [msm_sum / max(1, msm_cnt)]
 
     # ... and the same K steps with TWO MSMs in flight (ezkl_hip_msm_g1_start_dev / _finish: step i + 1 is queued before step i is waited for,
     # so the latency-bound sort / reduce kernels and the host tail of one step run under the accumulation of the other -- what a prover's
     # commit phases do with their batches).  Reported beside the headline (roofline.msm_two_in_flight), never as `value`: the headline stays
     # the synchronous step of rounds 1-4.  Single rank only (with N ranks every step ends in the fold's collective).
     t_msm2 = None
-    if world == 1 and not args.no_side_legs:
+    side_legs = args.full and not args.no_side_legs
+    if world == 1 and side_legs:
         try:
             tok = B.msm_g1_start_dev(bases, scalars.ptr, n_msm)
             for _ in range(3):
@@ -198,7 +207,7 @@ def main():
     # columns a prover commits look like.  The same K synchronous steps over the same bases; reported beside the headline
     # (roofline.msm_witness_like), checked against the oracle in the cpu_baseline leg.  Single rank only, like the leg above.
     w_leg = None
-    if world == 1 and not args.no_side_legs:
+    if world == 1 and side_legs:
         try:
             scalars_w = B.DeviceBuffer.from_numpy(witness_like_fr(np.random.default_rng(SEED + 17), n_msm))
             for _ in range(max(3, args.warmup)):
@@ -243,20 +252,22 @@ def main():
         idx = np.sort(np.random.default_rng(SEED + 1).choice(n_ntt, NTT_DUMP_SAMPLE, replace=False))
         dump_outputs(args.dump_outputs, {"msm_result": _words(result).reshape(2, 8),
                                          "ntt_sample": _words(col.to_numpy(shape=(n_ntt, 4))[idx])})
-    for _ in range(max(5, args.steps // 2)):            # the same transforms with their event pair (HIP events around the three passes)
-        ntt_step()
-    barrier_sync()
+    if args.full:
+        for _ in range(max(5, args.steps // 2)):        # the same transforms with their event pair (HIP events around the three passes)
+            ntt_step()
+        barrier_sync()
     B.set_async(was_async)
-    ntt_sum, ntt_cnt = B.kernel_ms_stats("ntt")
-    ntt_ms = [ntt_sum / max(1, ntt_cnt)]
-    if ntt_cnt != max(5, args.steps // 2):
-        errors.append("ntt event pairs harvested: %d for %d steps" % (ntt_cnt, max(5, args.steps // 2)))
+    if args.full:
+        ntt_sum, ntt_cnt = B.kernel_ms_stats("ntt")
+        ntt_ms = [ntt_sum / max(1, ntt_cnt)]
+        if ntt_cnt != max(5, args.steps // 2):
+            errors.append("ntt event pairs harvested: %d for %d steps" % (ntt_cnt, max(5, args.steps // 2)))
 
     # the other two forms BASELINE.md §3 names, on the GPU as on the CPU (cpu_baseline.ntt): the inverse transform (lagrange_to_coeff: omega^-1 and
     # the 1/n scale) and the prover's coset form (coeff_to_extended: 2^20 coefficients, zeta twist, zero-extended to 2^22), queued the same way
     ntt_forms, was_async = {}, None
     try:
-        if args.no_side_legs:
+        if not side_legs:
             raise StopIteration
         was_async = B.set_async(True)
         os.environ["EZKL_HIP_TIMING"] = "none"
@@ -307,7 +318,7 @@ def main():
     # N > 1: STRONG scaling of one MSM (BASELINE configs[3]: "MSM sharded across 8"): ONE 2^20-point and ONE 2^22-point MSM whose points
     # are split over the ranks, partials folded after an all_gather of 64 bytes per rank -- next to the weak-scaling headline above.
     strong = None
-    if world > 1:
+    if world > 1 and args.full:
         try:
             strong = strong_scaling(world, rank, dist, dev, B, D, torch, args, barrier_sync)
         except Exception as e:                      # never lose the headline line to this leg
@@ -317,15 +328,47 @@ def main():
     # CHILD (tools/prove_bench.py) and the children form their own process group on the next port, so a failure or a hang in
     # this leg can only cost its timeout: the headline line below is printed regardless.
     prove_multi = None
-    if world > 1 and not args.no_cpu_baseline:
+    if world > 1 and args.full and not args.no_cpu_baseline:
         prove_multi = prove_leg_multi(world, rank, local_rank, args)
 
     if rank == 0:
+        acc_avg_ms = float(np.mean(acc_ms))
+        achieved = MSM_BYTES_PER_POINT * n_msm / (acc_avg_ms * 1e-3) / 1e9
+        out = {
+            "metric": "BN254 G1 MSM pts/s (2^20 points per GPU; NTT 2^22 elems/s in extra)",
+            "value": world * n_msm * args.steps / t_msm,
+            "unit": "pts/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "clock_warmup_steps": {"msm": CLOCK_WARMUP_MSM, "ntt": CLOCK_WARMUP_NTT,
+                                   "note": "untimed steps of the same workload BEFORE the `warmup` steps, so that the K timed steps run at the clocks a prover runs at"},
+            "ms_per_step": t_msm / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u32x8 (254-bit modular integer, Montgomery)",
+            "data": "synthetic",
+            "config": {"workload": "configs[1]: standalone 2^20-point BN254 G1 MSM (uniform scalars, try-and-increment bases) "
+                                   "+ 2^22 scalar-field NTT per GPU", "msm_points_per_gpu": n_msm, "ntt_elems_per_gpu": n_ntt,
+                       "parallelism": "points sharded across %d rank(s); all_gather of 64-B partials + host fold" % world},
+            # the accumulate kernel's figures come from the event pairs of the timed region itself, so a plain run keeps them
+            "roofline": {"bound": "hbm", "kernel": "msm_accumulate_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "avg_launch_ms": acc_avg_ms,
+                         # the other half of BASELINE.json's metric: the 2^22-point NTT of the second timed region
+                         "ntt": {"metric": "BN254 Fr NTT elems/s (2^22 points per GPU)", "elems_per_s": world * n_ntt * args.steps / t_ntt,
+                                 "ms_per_step": t_ntt / args.steps * 1e3,
+                                 "steps_queued": "stream-ordered (ezkl_hip_set_async), one synchronise after the K steps; no event records inside the timed region"}},
+            "extra": {"ntt_elems_per_s": world * n_ntt * args.steps / t_ntt, "ntt_ms_per_step": t_ntt / args.steps * 1e3,
+                      "result_x_limb0": int(result[0])},
+        }
+        if t_batch is not None:
+            out["extra"].update({"msm_batch4_ms_per_msm": t_batch * 1e3, "msm_batch4_pts_per_s_per_gpu": n_msm / t_batch,
+                                 "batch_matches_single": bool((bres[0] == B.msm_g1_dev(bases, scalars.ptr, n_msm)).all())})
+    if rank == 0 and args.full:
         modmul = B.ubench("modmul")
         modmul29 = B.ubench("modmul29")           # the carry-free radix-2^29 product the MSM kernels use
         copy_bps = B.ubench("copy")
-        acc_avg_ms = float(np.mean(acc_ms))
-        achieved = MSM_BYTES_PER_POINT * n_msm / (acc_avg_ms * 1e-3) / 1e9
         # HBM traffic per launch of the dominant kernel: PMC counters need their own rocprofv3 passes (the guide: never together with the
         # kernel trace), so bench.py cannot measure them itself; it reports the tracked reduction of those passes WITH its source label
         traffic, traffic_source, ntt_traffic = None, None, None
@@ -346,53 +389,25 @@ def main():
                     ntt_traffic = tj.get("ntt_2p22_bytes_per_transform")
             except Exception:
                 traffic = None
-        out = {
-            "metric": "BN254 G1 MSM pts/s (2^20 points per GPU; NTT 2^22 elems/s in extra)",
-            "value": world * n_msm * args.steps / t_msm,
-            "unit": "pts/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "clock_warmup_steps": {"msm": CLOCK_WARMUP_MSM, "ntt": CLOCK_WARMUP_NTT,
-                                   "note": "untimed steps of the same workload BEFORE the `warmup` steps, so that the K timed steps run at the clocks a prover runs at"},
-            "ms_per_step": t_msm / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32x8 (254-bit modular integer, Montgomery)",
-            "data": "synthetic",
-            "config": {"workload": "configs[1]: standalone 2^20-point BN254 G1 MSM (uniform scalars, try-and-increment bases) "
-                                   "+ 2^22 scalar-field NTT per GPU", "msm_points_per_gpu": n_msm, "ntt_elems_per_gpu": n_ntt,
-                       "parallelism": "points sharded across %d rank(s); all_gather of 64-B partials + host fold" % world},
-            "roofline": {"bound": "hbm", "kernel": "msm_accumulate_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "avg_launch_ms": acc_avg_ms,
-                         "note": "integer-VALU bound, not HBM bound: see roofline.product_peak (NOTEBOOK.md §roofline)",
-                         # the other half of BASELINE.json's metric, where the driver's record keeps it: the 2^22-point NTT of the second timed region
-                         "ntt": {"metric": "BN254 Fr NTT elems/s (2^22 points per GPU)", "elems_per_s": world * n_ntt * args.steps / t_ntt,
-                                 "ms_per_step": t_ntt / args.steps * 1e3, "device_ms_per_transform": float(np.mean(ntt_ms)), "launches_per_transform": 3,
-                                 "bound": "hbm", "achieved": NTT_BYTES_PER_ELEM * n_ntt / (float(np.mean(ntt_ms)) * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                 "frac": NTT_BYTES_PER_ELEM * n_ntt / (float(np.mean(ntt_ms)) * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": ntt_traffic,
-                                 "inverse_elems_per_s": ntt_forms.get("inverse_elems_per_s"), "coset_2p20_to_2p22_elems_per_s": ntt_forms.get("coset_2p20_to_2p22_elems_per_s"),
-                                 "steps_queued": "stream-ordered (ezkl_hip_set_async), one synchronise after the K steps; no event records inside the timed region, device_ms_per_transform from steps right after it"},
-                         # what the kernels are actually bound by, measured in this run (ezkl_hip_ubench): 254-bit Montgomery products per second with
-                         # every lane issuing the radix-2^29 product and nothing else; and the copy bandwidth this box reaches
-                         "product_peak": {"modmul29_per_s": modmul29, "modmul32_per_s": modmul, "hbm_copy_GBs": copy_bps / 1e9},
-                         "msm_device_ms": float(np.mean(msm_ms)),
-                         "timing_events": "timed region: one HIP event pair per step, around msm_accumulate_kernel (EZKL_HIP_TIMING=kernel); msm_device_ms from steps after the region with both pairs",
-                         "msm_witness_like": w_leg,
-                         "msm_two_in_flight": ({"pts_per_s": n_msm * args.steps / t_msm2, "ms_per_step": t_msm2 / args.steps * 1e3,
-                                                "note": "the same K steps with step i + 1 queued before step i is waited for (ezkl_hip_msm_g1_start_dev / _finish); not the headline"}
-                                               if t_msm2 else None)},
-            "extra": {"msm_device_ms": float(np.mean(msm_ms)), "ntt_elems_per_s": world * n_ntt * args.steps / t_ntt,
-                      "ntt_ms_per_step": t_ntt / args.steps * 1e3, "ntt_device_ms": float(np.mean(ntt_ms)),
-                      "ntt_achieved_GBs": NTT_BYTES_PER_ELEM * n_ntt / (float(np.mean(ntt_ms)) * 1e-3) / 1e9,
-                      "modmul_per_s": modmul, "modmul29_per_s": modmul29, "hbm_copy_GBs": copy_bps / 1e9,
-                      "result_x_limb0": int(result[0])},
-        }
-        if t_batch is not None:
-            out["extra"].update({"msm_batch4_ms_per_msm": t_batch * 1e3, "msm_batch4_pts_per_s_per_gpu": n_msm / t_batch,
-                                 "batch_matches_single": bool((bres[0] == B.msm_g1_dev(bases, scalars.ptr, n_msm)).all())})
+        ntt_gbs = NTT_BYTES_PER_ELEM * n_ntt / (float(np.mean(ntt_ms)) * 1e-3) / 1e9
+        rf = out["roofline"]
+        rf.update({"traffic": traffic, "traffic_source": traffic_source,
+                   "note": "integer-VALU bound, not HBM bound: see roofline.product_peak (NOTEBOOK.md §roofline)",
+                   # what the kernels are actually bound by, measured in this run (ezkl_hip_ubench): 254-bit Montgomery products per second with
+                   # every lane issuing the radix-2^29 product and nothing else; and the copy bandwidth this device reaches
+                   "product_peak": {"modmul29_per_s": modmul29, "modmul32_per_s": modmul, "hbm_copy_GBs": copy_bps / 1e9},
+                   "msm_device_ms": float(np.mean(msm_ms)),
+                   "timing_events": "timed region: one HIP event pair per step, around msm_accumulate_kernel (EZKL_HIP_TIMING=kernel); msm_device_ms from steps after the region with both pairs",
+                   "msm_witness_like": w_leg,
+                   "msm_two_in_flight": ({"pts_per_s": n_msm * args.steps / t_msm2, "ms_per_step": t_msm2 / args.steps * 1e3,
+                                          "note": "the same K steps with step i + 1 queued before step i is waited for (ezkl_hip_msm_g1_start_dev / _finish); not the headline"}
+                                         if t_msm2 else None)})
+        rf["ntt"].update({"device_ms_per_transform": float(np.mean(ntt_ms)), "launches_per_transform": 3, "bound": "hbm", "achieved": ntt_gbs,
+                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ntt_gbs / HBM_PEAK_GBS, "traffic": ntt_traffic,
+                          "inverse_elems_per_s": ntt_forms.get("inverse_elems_per_s"), "coset_2p20_to_2p22_elems_per_s": ntt_forms.get("coset_2p20_to_2p22_elems_per_s")})
+        rf["ntt"]["steps_queued"] += ", device_ms_per_transform from steps right after it"
+        out["extra"].update({"msm_device_ms": float(np.mean(msm_ms)), "ntt_device_ms": float(np.mean(ntt_ms)), "ntt_achieved_GBs": ntt_gbs,
+                             "modmul_per_s": modmul, "modmul29_per_s": modmul29, "hbm_copy_GBs": copy_bps / 1e9})
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(bases, scalars, n_msm, result)
             if w_leg is not None:                        # the (W) result against the oracle on the same input
@@ -468,6 +483,7 @@ def main():
         rks.append(rk("msm_accumulate_kernel", "2^20-point MSM of the timed region (96 B per point)", MSM_BYTES_PER_POINT * n_msm, acc_avg_ms, traffic,
                       {"products_per_launch": 13 * n_msm * 10}))
         out["roofline_kernels"] = rks
+    if rank == 0:
         if prove_multi is not None:
             out["prove"] = prove_multi
         if strong is not None:
@@ -507,16 +523,19 @@ def compact_line(full):
     line["clock_warmup_steps"] = g(full.get("clock_warmup_steps"), "msm", "ntt")
     line["config"] = g(full.get("config"), "workload", "parallelism")
     r = g(rf, "bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_ms", "msm_device_ms")
-    r["traffic_source"] = (rf.get("traffic_source") or "")[:100] or None
+    if "traffic_source" in rf:                       # the figures from here on are those of a --full run
+        r["traffic_source"] = (rf.get("traffic_source") or "")[:100] or None
     r["ntt"] = g(rf.get("ntt"), "elems_per_s", "ms_per_step", "device_ms_per_transform", "launches_per_transform", "achieved", "frac", "traffic",
                  "inverse_elems_per_s", "coset_2p20_to_2p22_elems_per_s")
     for k in ("msm_witness_like", "msm_two_in_flight"):
         if rf.get(k):
             r[k] = g(rf[k], "pts_per_s", "ms_per_step", "accumulate_ms", "device_ms")
-    r["product_peak"] = rf.get("product_peak")
+    if "product_peak" in rf:
+        r["product_peak"] = rf["product_peak"]
     # the kernels of the metric's own workload, one short row each (the long form: bench_full.json roofline_kernels)
-    r["kernels"] = [dict(g(k_, "kernel", "avg_launch_ms", "achieved", "frac", "traffic"), valu_frac=(k_.get("valu") or {}).get("frac"))
-                    for k_ in (full.get("roofline_kernels") or [])]
+    if "roofline_kernels" in full:
+        r["kernels"] = [dict(g(k_, "kernel", "avg_launch_ms", "achieved", "frac", "traffic"), valu_frac=(k_.get("valu") or {}).get("frac"))
+                        for k_ in full["roofline_kernels"]]
     line["roofline"] = r
     p20 = g(full.get("prove_seconds_k20_mlp"), "gpu", "gpu_first_of_process", "cold", "cpu", "cpu_threads", "identical", "verifier_accepts", "error")
     if cb is not None:
@@ -636,7 +655,7 @@ def prove_leg():
     averages rocprofv3 reports for this process stay those of the timed MSM / NTT regions.  Part of the checker leg: each child
     verifies its proof with the oracle's pairing verifier.  The legs run in the order of their weight for BASELINE.json's metric and
     each one only if the run's time budget (EZKL_BENCH_BUDGET_S, default 150 s from process start) still covers its estimated cost, so
-    that the default `python bench.py` ends within minutes on a fresh box; what was skipped is listed under "skipped":
+    that `python bench.py --full` ends within minutes; what was skipped is listed under "skipped":
       * `mlp_k20`: the metric's own configuration, "ezkl prove wall-seconds (k = 20 MLP)" -- 9 x (Gemm 665 x 665 + bias + ReLU) over the ezkl
         gate set, laid out once and shipped as bench_cache/mlp_k20_s1.npz; warm prove on the GPU, then the same create_proof on the host
         cores (Python host + C oracle kernels, OpenMP) with identical proof bytes;

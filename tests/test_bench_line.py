@@ -72,6 +72,22 @@ def test_emit_prints_one_line_and_keeps_the_full_record(tmp_path, capsys, monkey
     assert json.load(open(tmp_path / "bench_full.json"))["prove"]["mlp_k20"]["prove_seconds_gpu"] == full["prove"]["mlp_k20"]["prove_seconds_gpu"]
 
 
+def test_plain_run_line_has_no_placeholders_for_full_figures():
+    """a plain run's record holds the headline and the figures of the two timed regions only: its line keeps the contract's keys and
+    carries no empty entries for what --full measures"""
+    full = _record("r05av_bench.log")
+    plain = {k: full[k] for k in CONTRACT_KEYS + ["clock_warmup_steps", "extra"]}
+    plain["roofline"] = {k: full["roofline"][k] for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "avg_launch_ms")}
+    plain["roofline"]["ntt"] = {k: full["roofline"]["ntt"][k] for k in ("metric", "elems_per_s", "ms_per_step")}
+    line = json.loads(bench.compact_line(plain))
+    for k in CONTRACT_KEYS:
+        assert k in line, k
+    assert line["value"] == pytest.approx(full["value"], rel=1e-4) and line["ms_per_step"] == pytest.approx(full["ms_per_step"], rel=1e-4)
+    assert set(line["roofline"]) == {"bound", "kernel", "achieved", "peak", "unit", "frac", "avg_launch_ms", "ntt"}
+    assert set(line["roofline"]["ntt"]) == {"elems_per_s", "ms_per_step"}
+    assert not {"cpu_baseline", "prove_seconds_k20_mlp", "prove_other_circuits", "prove_multi", "errors"} & set(line)
+
+
 def test_multi_rank_line_carries_the_three_sharded_proofs():
     """N > 1: configs[3] (einsum, MLP k = 20) and configs[4] (the transformer surrogate at k = 22) each with what a SCALE run is checked by --
     seconds, same proof on every rank, verifier, rccl_ranks_seen -- and still a short line"""

@@ -389,6 +389,40 @@ def test_column_sharded_ntt_prover_two_ranks_same_proof(hip):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_only(hip, tmp_path):
+    """`bench.py --gpus 1` without --full: ONE line with the contract's keys and the figures of the two timed regions, the dumped MSM
+    result equal to the oracle's on the same seeded input, and nothing of what --full adds (side legs, per-kernel rows, CPU baselines,
+    prove legs)"""
+    import json, os, subprocess, sys
+    from conftest import ROOT
+    import bench
+    from oracle import binding as ob
+    env = dict(os.environ, EZKL_BENCH_FULL=str(tmp_path / "full.json"))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "dump")], env=env, capture_output=True, text=True, timeout=300)
+    objs = json_lines(r.stdout)
+    assert r.returncode == 0 and len(objs) == 1, r.stderr[-2000:]
+    j = objs[0]
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+                "config", "roofline"):
+        assert key in j
+    assert j["n_gpus"] == 1 and j["steps"] == 3 and j["warmup"] == 1 and j["unit"] == "pts/s" and j["higher_is_better"] is True
+    assert abs(j["value"] - (1 << 20) * 3 / (j["ms_per_step"] * 3e-3)) < 1e-3 * j["value"]
+    assert j["roofline"]["avg_launch_ms"] > 0 and j["roofline"]["ntt"]["elems_per_s"] > 0 and "errors" not in j
+    full = json.load(open(tmp_path / "full.json"))
+    for key in ("cpu_baseline", "prove", "prove_seconds_k20_mlp", "roofline_kernels"):
+        assert key not in full, key
+    for key in ("product_peak", "msm_device_ms", "msm_witness_like", "msm_two_in_flight", "traffic"):
+        assert key not in full["roofline"], key
+    assert "device_ms_per_transform" not in full["roofline"]["ntt"] and "inverse_elems_per_s" not in full["roofline"]["ntt"]
+    n = 1 << 20
+    want = ob.msm(bench.rand_fr(np.random.default_rng(bench.SEED), n), ob.gen_bases(bench.SEED, n))
+    assert (np.load(tmp_path / "dump" / "msm_result.npy") == bench._words(want).reshape(2, 8)).all()
+    assert np.load(tmp_path / "dump" / "ntt_sample.npy").shape == (bench.NTT_DUMP_SAMPLE, 8)
+    assert full["extra"]["result_x_limb0"] == int(want[0])
+
+
+@pytest.mark.gpu
 def test_bench_contract_two_ranks(hip, tmp_path):
     """`bench.py --gpus 2` the way the driver launches it (torchrun), on one GPU with gloo: ONE JSON line from rank 0 with the
     contract's keys -- short enough for the driver's record -- the whole-job value, and the sharded end-to-end prove leg accepted by the
@@ -398,7 +432,7 @@ def test_bench_contract_two_ranks(hip, tmp_path):
     env = dict(os.environ, EZKL_BENCH_PROVE_TIMEOUT="200", EZKL_BENCH_MULTI_MLP20="0", EZKL_BENCH_MULTI_K22="11", EZKL_BENCH_FULL=str(tmp_path / "full.json"))
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29561", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--backend", "gloo", "--share-device"], env=env, capture_output=True, text=True, timeout=900)
+                        "--backend", "gloo", "--share-device", "--full"], env=env, capture_output=True, text=True, timeout=900)
     objs = json_lines(r.stdout)
     assert len(objs) == 1, r.stderr[-2000:]
     j = objs[0]
@@ -434,7 +468,7 @@ def test_bench_contract_four_and_three_ranks_on_one_device(hip, world, tmp_path)
     env = dict(os.environ, EZKL_BENCH_FULL=str(tmp_path / "full.json"))
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
                         "--master-port", str(29570 + world), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-                        "--backend", "gloo", "--share-device", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--backend", "gloo", "--share-device", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     objs = json_lines(r.stdout)
     assert len(objs) == 1, r.stderr[-2000:]
     j = objs[0]

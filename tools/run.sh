@@ -4,7 +4,7 @@
 #   /usr/local/graft/bin/gpurun --timeout 1500 -- 'bash tools/run.sh r04a suite bench'
 # jobs:
 #   suite        pytest -m gpu with --durations=40 and the memory report           -> <tag>_pytest_gpu.log
-#   bench        python bench.py (the driver's default command), wall time logged   -> <tag>_bench.log
+#   bench        python bench.py --full (every leg), wall time logged               -> <tag>_bench.log
 #   bench2       the bench contract at world 2 on ONE device (gloo plumbing test)   -> <tag>_bench2.log
 #   profile      rocprofv3 --kernel-trace --stats of `bench.py --no-cpu-baseline`   -> <tag>_kernel_stats.txt, <tag>_bench_profiled.log
 #   pmc          FETCH_SIZE / WRITE_SIZE passes over the 2^20 MSM + 2^22 NTT        -> <tag>_pmc_traffic.json
@@ -35,7 +35,7 @@ for JOB in "$@"; do
       echo "pytest rc=$?" >> "$O/${TAG}_pytest_gpu.log"; tail -60 "$O/${TAG}_pytest_gpu.log" ;;
     bench)
       TB=$(date +%s)
-      (cd "$R" && timeout ${BENCH_TIMEOUT:-600} python bench.py ${BENCH_ARGS:-}) > "$O/${TAG}_bench.log" 2> "$O/${TAG}_bench.err"
+      (cd "$R" && timeout ${BENCH_TIMEOUT:-600} python bench.py --full ${BENCH_ARGS:-}) > "$O/${TAG}_bench.log" 2> "$O/${TAG}_bench.err"
       echo "bench.py rc=$? wall $(( $(date +%s) - TB )) s" >> "$O/${TAG}_bench.log"
       grep '^{"metric' "$O/${TAG}_bench.log" | python -c "
 import sys, json
