@@ -856,6 +856,67 @@ def kernel_ms_stats(which, reset=False):
     return float(s.value), int(n.value)
 
 
+class WitnessError(ValueError):
+    """a synthesis on the device met a value outside its decomposition range (the layout's own assertion on the host path)"""
+
+
+class WitnessPlan:
+    """a witness plan (witness_plan.WitnessPlan bytes) resident on the device: `run` synthesizes the advice columns of one proof
+    into DeviceBuffers (ezkl_hip_witness_run_dev) -- the columns native.create_proof takes as they are"""
+
+    def __init__(self, blob):
+        blob = bytes(blob)
+        self.h = _vp()
+        L = _l.load()
+        rc = L.ezkl_hip_witness_plan_upload(blob, C.c_size_t(len(blob)), C.byref(self.h))
+        if rc == -3:
+            raise ValueError(L.ezkl_hip_witness_last_error().decode() or "witness plan refused")
+        _l.check(rc, "ezkl_hip_witness_plan_upload")
+        info = (C.c_uint32 * 8)()
+        _l.check(L.ezkl_hip_witness_plan_info(self.h, info), "ezkl_hip_witness_plan_info")
+        self.k, self.n_advice, self.n_inputs, self.n_outputs, self.n_records, self.n_cells, self.n_ops, self.n_params = [int(v) for v in info]
+        self.last = None                             # counters of the last run
+
+    def alloc_columns(self):
+        return [DeviceBuffer(32 << self.k) for _ in range(self.n_advice)]
+
+    def run(self, inputs, columns=None, stream=None):
+        """inputs: the model inputs as (signed) integers -> (columns: n_advice DeviceBuffers of 2^k Montgomery words, outputs as ints).
+        self.last = dict(cells_written, launches, device_ms).  Raises WitnessError, naming the op, when a value does not fit its
+        decomposition; the process goes on and the plan can run again."""
+        x = np.ascontiguousarray(np.asarray([int(v) for v in inputs], dtype=np.int64))
+        if len(x) != self.n_inputs:
+            raise ValueError("the plan takes %d inputs, got %d" % (self.n_inputs, len(x)))
+        cols = columns if columns is not None else self.alloc_columns()
+        if len(cols) != self.n_advice or any(c.nbytes < (32 << self.k) for c in cols):
+            raise ValueError("the plan writes %d columns of %d bytes" % (self.n_advice, 32 << self.k))
+        ptrs = (_vp * self.n_advice)(*[c.ptr for c in cols])
+        outs = np.zeros((max(1, self.n_outputs), 4), np.uint64)
+        status = (C.c_uint64 * 4)()
+        L = _l.load()
+        rc = L.ezkl_hip_witness_run_dev(self.h, _p(x), C.c_size_t(len(x)), ptrs, _p(outs), status, _stream_ptr(stream))
+        self.last = dict(failed=int(status[0]), first=(int(status[1]) >> 32, int(status[1]) & 0xffffffff), cells_written=int(status[2]), launches=int(status[3]))
+        if rc == -3 and status[0]:
+            if columns is None:
+                for c in cols:
+                    c.free()
+            raise WitnessError(L.ezkl_hip_witness_last_error().decode())
+        _l.check(rc, "ezkl_hip_witness_run_dev")
+        self.last["device_ms"] = last_kernel_ms("witness")
+        return cols, [_from_mont_int(outs[i]) for i in range(self.n_outputs)]
+
+    def free(self):
+        if self.h:
+            _l.load().ezkl_hip_witness_plan_free(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def ubench(which):
     out = C.c_double(0)
     _l.check(_l.load().ezkl_hip_ubench(which.encode(), C.byref(out)), "ezkl_hip_ubench")

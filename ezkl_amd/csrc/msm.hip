@@ -1456,7 +1456,8 @@ int msm_upload_end(MsmUpload* u) {
 // is integer_rep_to_felt of an i128 -- the quantised tensor values -- before it becomes 32 bytes of Montgomery form).  PCIe is the
 // scarce link of the advice phase (12 columns x 32 MB at ~53 GB/s = 7 ms of a 67 ms proof), so a column may cross it as 8 or 16 bytes
 // per cell and is expanded HERE: x >= 0 -> x, x < 0 -> r - |x| (integer_rep_to_felt), then x * 2^256 mod r (one product per cell).
-// format: 0 = 32-byte Montgomery words (halo2's Vec<Fp>), 1 = int64, 2 = int128 (little-endian two's complement).
+// format: 0 = 32-byte Montgomery words (halo2's Vec<Fp>), 1 = int64, 2 = int128 (little-endian two's complement), 3 = a DEVICE column of
+// Montgomery words (EZKL_COLUMN_DEVICE_FP: a witness synthesized on the device, witness.hip) -- copied on the device, never across PCIe.
 __global__ __launch_bounds__(256) void msm_expand_integer_rep_kernel(const uint64_t* src, uint32_t words, fe_t* dst, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -1494,8 +1495,8 @@ int msm_upload_begin(Ctx* c, const fe_t* const* host_cols, fe_t* const* dev_cols
     g_open_upload = u;
     size_t stage_words = 0, stage_off = 0;
     for (size_t j = 0; formats && j < batch; j++) {
-        if (formats[j] > 2) { g_open_upload = nullptr; delete u; return EZKL_ERR_INVALID; }
-        stage_words += n * formats[j];
+        if (formats[j] > EZKL_COLUMN_DEVICE_FP) { g_open_upload = nullptr; delete u; return EZKL_ERR_INVALID; }
+        if (formats[j] != EZKL_COLUMN_DEVICE_FP) stage_words += n * formats[j];
     }
     if (stage_words) {
         // from the column pool (ezkl_hip_malloc: a block of this size is parked after the first proof; hipMalloc / hipFree would synchronise the device)
@@ -1504,8 +1505,11 @@ int msm_upload_begin(Ctx* c, const fe_t* const* host_cols, fe_t* const* dev_cols
     }
     for (size_t j = 0; j < batch; j++) {
         hipError_t e = hipEventCreateWithFlags(&u->ev[j], hipEventDisableTiming);
-        const uint32_t words = formats ? formats[j] : 0;                 // 64-bit words per cell of an integer column (0: 32-byte field elements)
-        if (e == hipSuccess && words) {
+        const bool resident = formats && formats[j] == EZKL_COLUMN_DEVICE_FP;    // the source is a device column already: no PCIe, the caller's stays as it is
+        const uint32_t words = formats && !resident ? formats[j] : 0;    // 64-bit words per cell of an integer column (0: 32-byte field elements)
+        if (e == hipSuccess && resident) {
+            if (host_cols[j] != dev_cols[j]) e = hipMemcpyAsync(dev_cols[j], host_cols[j], n * sizeof(fe_t), hipMemcpyDeviceToDevice, g_copy_st);
+        } else if (e == hipSuccess && words) {
             // a staging block per integer column (expanding inside the destination column would race its own reads)
             uint64_t* stage = u->stage + stage_off;
             stage_off += n * words;

@@ -25,6 +25,7 @@
 #include "hostfield.hpp"
 #include "transcript.hpp"
 #include "pairing.hpp"
+#include "../witness_plan.hpp"
 
 namespace ezkl_prover {
 using ezkl_hip::check;
@@ -2318,7 +2319,8 @@ static std::vector<uint8_t> create_proof(ProvingKey& pk, ezkl_bases_t g, ezkl_ba
             for (size_t j = 0; j < idxs.size(); j++) {
                 if (up_of[j] == SIZE_MAX) continue;
                 const uint8_t f = advice_formats[idxs[j]];
-                invalid(f > EZKL_COLUMN_INT128, "unknown advice column format");
+                invalid(f > EZKL_COLUMN_DEVICE_FP, "unknown advice column format");
+                invalid(f == EZKL_COLUMN_DEVICE_FP && (cs.shard.on() || owners), "device-resident advice columns are for the single-context prover (not sharded, not a group)");
                 invalid(f != EZKL_COLUMN_FP && advice_fn && !cs.advice_by_pointer, "integer advice columns need caller-owned buffers (direct pointers, or a by-pointer callback)");
                 fmts.push_back(f);
             }
@@ -3386,6 +3388,16 @@ int ezkl_prover_keccak256(const void* data, size_t len, void* out32) {
     return EZKL_OK;
 }
 const char* ezkl_prover_last_error(void) { return g_last_error.c_str(); }
+int ezkl_prover_witness_plan_check(const void* blob, size_t len) {
+    ezkl::wplan::Plan plan;
+    std::string why;
+    if (ezkl::wplan::parse(blob, len, plan, why)) {
+        g_last_error.clear();
+        return EZKL_OK;
+    }
+    g_last_error = why;
+    return EZKL_ERR_INVALID;
+}
 }
 
 

@@ -1,0 +1,349 @@
+// witness.hip -- witness synthesis on the device from a recorded plan (ezkl_amd/witness_plan.py; blob layout: witness_plan.hpp).
+//
+// halo2 fills the advice columns in GraphCircuit::synthesize (/root/reference/src/graph/mod.rs:2010-2200) by running the model's layout
+// (src/circuit/ops/layouts.rs) cell by cell on the host.  For the MLP op family which cell holds what is a function of the circuit
+// alone, so the layout is recorded once as a list of RECORDS and replayed here for every proof: one launch per record into resident,
+// zero-filled columns of 2^k Montgomery words.  ezkl_amd/witness_plan.py `run_plan_host` is the executable specification: a lane
+// here does to one element what one iteration of its loops does.
+//
+//  * element-wise records (copy, const, input, param, add / sub / mult, decompose hints, range-check index, inverse-or-zero): one lane
+//    per destination cell; the index arrays are read coalesced, and where they hold contiguous runs (they mostly do: the layout
+//    advances a linear coordinate) so are the 32-byte cells;
+//  * dot records (the running sum of w products per row, layouts.rs:532-610, with the duplicated row at the top of a new column as
+//    a step without products): all dots of a record run in parallel, 16 lanes to a dot -- a chunked scan over its rows, see
+//    wit_dot_kernel.  The index arrays are step-major (step s of every dot, then step s + 1): a wave holds 4 dots x 16 row chunks, so
+//    one index read of a wave is 16 runs of 4 consecutive words, one run per chunk.
+//
+// A value that does not fit its decomposition (|x| >= base^legs: the layout's "value exceeds the decomposition range") writes nothing
+// wrong silently: the lane counts itself in status[0] and keeps the SMALLEST (record, element) in status[1] -- vector atomics in plain
+// C++, as the mock prover's kernels in vecops.hip -- and the host call returns EZKL_ERR_INVALID naming the op.  Nothing traps.
+// The only device memory written is the destination columns, the plan's own scratch (inputs, outputs) and the status words; the plan's
+// index pool, parameters and constants are read-only after upload.
+#include "common.hpp"
+#include "witness_plan.hpp"
+
+namespace ezkl {
+namespace {
+using namespace wplan;
+
+struct WitCols {
+    fe_t* p[MAX_ADVICE];
+};
+// status words on the device: [0] failing lanes, [1] ~(record << 32 | element) of the first one (atomicMax over the complement: zero = none),
+// [2] cells written
+EZ_D fe_t* wit_cell(const WitCols& cols, uint32_t k, uint32_t idx) { return cols.p[idx >> k] + (idx & ((1u << k) - 1)); }
+
+// integer_rep_to_felt (/root/reference/src/fieldutils.rs:9-17) as msm_expand_integer_rep_kernel does it for EZKL_COLUMN_INT64: x >= 0 -> x,
+// x < 0 -> r - |x|, then the Montgomery form
+EZ_D fe_t wit_from_i64(int64_t x) {
+    const bool neg = x < 0;
+    const uint64_t m = neg ? ~(uint64_t)x + 1 : (uint64_t)x;
+    fe_t v = Fr::zero();
+    v.v[0] = (uint32_t)m; v.v[1] = (uint32_t)(m >> 32);
+    if (neg) {
+        uint32_t br = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) v.v[i] = subb32(FrP::MOD[i], v.v[i], br);
+    }
+    return Fr::to_mont(v);
+}
+EZ_HD constexpr uint32_t wit_half(int i) { return (FrP::MOD[i] >> 1) | (i < 7 ? (FrP::MOD[i + 1] << 31) : 0u); }   // limb i of (r - 1) / 2
+// the signed value of a Montgomery word as the layout reads it (`v if v < r // 2 else v - r`): sign and magnitude.  fits: |x| < 2^62.
+EZ_D void wit_signed(const fe_t& mont, bool& neg, uint64_t& mag, bool& fits) {
+    const fe_t c = Fr::from_mont(mont);
+    uint32_t br = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) (void)subb32(c.v[i], wit_half(i), br);
+    neg = br == 0;                                        // c >= (r - 1) / 2
+    fe_t m = c;
+    if (neg) {
+        br = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) m.v[i] = subb32(FrP::MOD[i], c.v[i], br);
+    }
+    uint32_t hi = m.v[1] >> 30;
+#pragma unroll
+    for (int i = 2; i < 8; i++) hi |= m.v[i];
+    fits = hi == 0;
+    mag = (uint64_t)m.v[0] | ((uint64_t)m.v[1] << 32);
+}
+EZ_D void wit_report(bool fail, uint32_t rec, uint32_t elem, unsigned long long* status) {
+    const unsigned long long m = __ballot(fail);
+    if (!m) return;
+    if ((threadIdx.x & 63) == (uint32_t)__ffsll(m) - 1) atomicAdd(&status[0], (unsigned long long)__popcll(m));
+    if (fail) atomicMax(&status[1], ~(((unsigned long long)rec << 32) | elem));
+}
+EZ_D void wit_count(uint32_t wrote, unsigned long long* status) {          // one atomic per wave
+#pragma unroll
+    for (int off = 32; off; off >>= 1) wrote += __shfl_down(wrote, off);
+    if ((threadIdx.x & 63) == 0 && wrote) atomicAdd(&status[2], (unsigned long long)wrote);
+}
+
+template <uint32_t KIND>
+__global__ __launch_bounds__(256) void wit_elem_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* __restrict__ a,
+                                                       const uint32_t* __restrict__ b, uint32_t count, uint32_t p0, uint32_t p1,
+                                                       const int64_t* __restrict__ ints, const fe_t* __restrict__ consts, uint32_t rec,
+                                                       unsigned long long* status) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < count;
+    bool fail = false;
+    if (live) {
+        const uint32_t ia = a[i];
+        fe_t v;
+        if (KIND == COPY) v = ld_fe(wit_cell(cols, k, ia));
+        else if (KIND == CONST) v = ld_fe(consts + ia);
+        else if (KIND == INPUT || KIND == PARAM) v = wit_from_i64(ints[ia]);
+        else if (KIND == ADD) v = Fr::add(ld_fe(wit_cell(cols, k, ia)), ld_fe(wit_cell(cols, k, b[i])));
+        else if (KIND == SUB) v = Fr::sub(ld_fe(wit_cell(cols, k, ia)), ld_fe(wit_cell(cols, k, b[i])));
+        else if (KIND == MUL) v = Fr::mul(ld_fe(wit_cell(cols, k, ia)), ld_fe(wit_cell(cols, k, b[i])));
+        else if (KIND == INVZ) v = Fr::inv(ld_fe(wit_cell(cols, k, ia)));                    // a^(r-2): inv(0) = 0
+        else {
+            bool neg, fits;
+            uint64_t mag;
+            wit_signed(ld_fe(wit_cell(cols, k, ia)), neg, mag, fits);
+            if (KIND == HINT) {
+                uint64_t bound = 1;
+                for (uint32_t t = 0; t < p1; t++) bound *= p0;                                // < 2^62: checked on upload
+                fail = !fits || mag >= bound;
+                const uint32_t e = b[i];
+                if (e == NONE) v = mag == 0 ? Fr::zero() : neg ? Fr::neg(Fr::one()) : Fr::one();
+                else {
+                    uint64_t d = 1;
+                    for (uint32_t t = 0; t < e; t++) d *= p0;
+                    v = Fr::from_u64((mag / d) % p0);
+                }
+            } else {                                                                          // RCIDX: |x - lo| // col_size
+                fail = !fits;                                                                 // |x| >= 2^62: as run_plan_host refuses it
+                const int64_t s = neg ? -(int64_t)mag : (int64_t)mag, diff = s - (int64_t)(int32_t)p0;
+                v = Fr::from_u64((uint64_t)(diff < 0 ? -diff : diff) / p1);
+            }
+        }
+        if (!fail) st_fe(wit_cell(cols, k, dst[i]), v);
+    }
+    wit_report(fail, rec, i, status);
+    wit_count(live && !fail ? 1u : 0u, status);
+}
+
+// DOT_LANES consecutive lanes share one dot product; step s of dot d: dst[s * n_dots + d], products (a, b)[(s * w + j) * n_dots + d], j < w.
+// The rows of a dot are cut into DOT_LANES contiguous chunks.  Pass 1: every lane sums the products of its chunk.  A scan over the
+// group's lanes (wave shuffles, no LDS) gives each lane the running sum at the start of its chunk.  Pass 2: the lane walks its chunk
+// again and writes the running sum of every row.  Field addition is exact, so the sums are those of the row-by-row walk bit for bit.
+constexpr uint32_t DOT_LANES = 16;
+EZ_D fe_t wit_shfl_up(const fe_t& v, uint32_t delta) {
+    fe_t r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.v[i] = __shfl_up(v.v[i], delta, DOT_LANES);
+    return r;
+}
+EZ_D fe_t wit_dot_row(const WitCols& cols, uint32_t k, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t n_dots, uint32_t w, uint32_t s,
+                      uint32_t d, fe_t acc) {
+    for (uint32_t j = 0; j < w; j++) {
+        const size_t at = ((size_t)s * w + j) * n_dots + d;
+        const uint32_t ia = a[at];
+        if (ia != NONE) acc = Fr::add(acc, Fr::mul(ld_fe(wit_cell(cols, k, ia)), ld_fe(wit_cell(cols, k, b[at]))));
+    }
+    return acc;
+}
+__global__ __launch_bounds__(64) void wit_dot_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* __restrict__ a,
+                                                     const uint32_t* __restrict__ b, uint32_t n_dots, uint32_t w, uint32_t n_steps,
+                                                     unsigned long long* status) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t g = (uint32_t)(t % DOT_LANES), chunk = (n_steps + DOT_LANES - 1) / DOT_LANES;
+    const bool live = t / DOT_LANES < n_dots;                    // the same for every lane of a group
+    const uint32_t d = live ? (uint32_t)(t / DOT_LANES) : 0;
+    const uint32_t s0 = g * chunk < n_steps ? g * chunk : n_steps, s1 = s0 + chunk < n_steps ? s0 + chunk : n_steps;
+    fe_t sum = Fr::zero();
+    if (live)
+        for (uint32_t s = s0; s < s1; s++)
+            if (dst[(size_t)s * n_dots + d] != NONE) sum = wit_dot_row(cols, k, a, b, n_dots, w, s, d, sum);
+    for (uint32_t off = 1; off < DOT_LANES; off <<= 1) {           // inclusive scan of the chunk sums over the group
+        const fe_t o = wit_shfl_up(sum, off);
+        if (g >= off) sum = Fr::add(sum, o);
+    }
+    fe_t acc = wit_shfl_up(sum, 1);                               // exclusive: the running sum before this lane's first row
+    if (g == 0) acc = Fr::zero();
+    uint32_t wrote = 0;
+    if (live)
+        for (uint32_t s = s0; s < s1; s++) {
+            const uint32_t cell = dst[(size_t)s * n_dots + d];
+            if (cell == NONE) continue;
+            acc = wit_dot_row(cols, k, a, b, n_dots, w, s, d, acc);
+            st_fe(wit_cell(cols, k, cell), acc);
+            wrote++;
+        }
+    wit_count(wrote, status);
+}
+
+__global__ __launch_bounds__(64) void wit_gather_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ cells, uint32_t n, fe_t* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) st_fe(out + i, ld_fe(wit_cell(cols, k, cells[i])));
+}
+
+struct DevPlan {
+    Plan host;                      // the validated blob: records, outputs and counts drive the launches; pool / params / consts are
+                                    // released once they are on the device (n_params is kept for ezkl_hip_witness_plan_info)
+    uint32_t n_params = 0;
+    uint32_t* pool = nullptr;       // device copies, read-only after upload
+    uint32_t* outputs = nullptr;
+    int64_t* params = nullptr;
+    fe_t* consts = nullptr;         // Montgomery form
+    // per-run scratch, owned by the plan (from the column pool: nothing is allocated per run)
+    int64_t* inputs = nullptr;
+    fe_t* outs = nullptr;
+    unsigned long long* status = nullptr;
+    Ctx* ctx = nullptr;
+};
+thread_local std::string t_wit_error;
+
+void plan_release(DevPlan* p) {
+    for (void* q : {(void*)p->pool, (void*)p->outputs, (void*)p->params, (void*)p->consts, (void*)p->inputs, (void*)p->outs, (void*)p->status})
+        if (q) (void)ezkl_hip_free(q);
+    delete p;
+}
+template <uint32_t KIND>
+void launch_elem(hipStream_t st, const WitCols& cols, uint32_t k, const DevPlan* p, const Rec& r, uint32_t ri) {
+    const int64_t* ints = KIND == INPUT ? p->inputs : p->params;
+    hipLaunchKernelGGL(wit_elem_kernel<KIND>, dim3(cdiv(r.count, 256)), dim3(256), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, p->pool + r.b, r.count, r.p0, r.p1,
+                       ints, (const fe_t*)p->consts, ri, p->status);
+}
+}  // namespace
+}  // namespace ezkl
+
+using namespace ezkl;
+
+extern "C" {
+
+const char* ezkl_hip_witness_last_error(void) { return t_wit_error.c_str(); }
+
+int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out) {
+    if (!out) return EZKL_ERR_INVALID;
+    *out = nullptr;
+    DevPlan* p = new DevPlan();
+    if (!wplan::parse(blob, len, p->host, t_wit_error)) {          // host-only: a bad blob is refused before a device is asked for
+        delete p;
+        return EZKL_ERR_INVALID;
+    }
+    t_wit_error.clear();
+    Ctx* c = ctx();
+    if (!c) { delete p; return EZKL_ERR_NO_DEVICE; }
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    p->ctx = c;
+    const Plan& h = p->host;
+    std::vector<fe_t> consts(h.consts.size() / 32);
+    for (size_t i = 0; i < consts.size(); i++) {
+        fe_t v;
+        memcpy(v.v, h.consts.data() + 32 * i, 32);
+        consts[i] = Fr::to_mont(v);
+    }
+    struct Up { void** dev; const void* src; size_t bytes; };
+    const Up ups[] = {{(void**)&p->pool, h.pool.data(), h.pool.size() * 4},       {(void**)&p->outputs, h.outputs.data(), h.outputs.size() * 4},
+                      {(void**)&p->params, h.params.data(), h.params.size() * 8}, {(void**)&p->consts, consts.data(), consts.size() * 32},
+                      {(void**)&p->inputs, nullptr, (size_t)h.n_inputs * 8},      {(void**)&p->outs, nullptr, h.outputs.size() * 32},
+                      {(void**)&p->status, nullptr, 32}};
+    int rc = EZKL_OK;
+    for (const Up& u : ups) {
+        if ((rc = ezkl_hip_malloc(u.dev, u.bytes ? u.bytes : 1))) break;
+        if (u.src && u.bytes && (rc = ezkl_hip_memcpy_h2d(*u.dev, u.src, u.bytes))) break;
+    }
+    if (!rc) rc = ezkl_hip_synchronize();
+    if (rc) { plan_release(p); return rc; }
+    p->n_params = (uint32_t)h.params.size();
+    std::vector<uint32_t>().swap(p->host.pool);                   // 138 MB at k = 20: the device copy is the one that is read from here on
+    std::vector<int64_t>().swap(p->host.params);
+    std::vector<uint8_t>().swap(p->host.consts);
+    *out = reinterpret_cast<ezkl_wplan_t>(p);
+    return EZKL_OK;
+}
+
+int ezkl_hip_witness_plan_free(ezkl_wplan_t plan) {
+    if (!plan) return EZKL_OK;
+    DevPlan* p = reinterpret_cast<DevPlan*>(plan);
+    EZ_CTX(c);
+    if (c != p->ctx) return EZKL_ERR_INVALID;
+    EZ_HIP(hipStreamSynchronize(c->stream));
+    plan_release(p);
+    return EZKL_OK;
+}
+
+int ezkl_hip_witness_plan_info(ezkl_wplan_t plan, uint32_t out[8]) {
+    if (!plan || !out) return EZKL_ERR_INVALID;
+    const Plan& h = reinterpret_cast<DevPlan*>(plan)->host;
+    const uint32_t v[8] = {h.k, h.n_advice, h.n_inputs, (uint32_t)h.outputs.size(), (uint32_t)h.recs.size(), h.n_cells, h.n_ops, reinterpret_cast<DevPlan*>(plan)->n_params};
+    memcpy(out, v, sizeof v);
+    return EZKL_OK;
+}
+
+int ezkl_hip_witness_run_dev(ezkl_wplan_t plan, const int64_t* inputs_host, size_t n_inputs, void* const* advice_cols_dev, void* outputs_host,
+                             uint64_t status[4], void* stream) {
+    if (!plan || !advice_cols_dev || !status || (n_inputs && !inputs_host)) return EZKL_ERR_INVALID;
+    DevPlan* p = reinterpret_cast<DevPlan*>(plan);
+    const Plan& h = p->host;
+    if (n_inputs != h.n_inputs || (!h.outputs.empty() && !outputs_host)) return EZKL_ERR_INVALID;
+    WitCols cols;
+    for (uint32_t j = 0; j < MAX_ADVICE; j++) cols.p[j] = nullptr;
+    for (uint32_t j = 0; j < h.n_advice; j++) {
+        if (!advice_cols_dev[j]) return EZKL_ERR_INVALID;
+        for (uint32_t i = 0; i < j; i++)
+            if (advice_cols_dev[i] == advice_cols_dev[j]) return EZKL_ERR_INVALID;
+        cols.p[j] = static_cast<fe_t*>(advice_cols_dev[j]);
+    }
+    memset(status, 0, 4 * sizeof(uint64_t));
+    EZ_CTX(c);
+    if (c != p->ctx) return EZKL_ERR_INVALID;
+    hipStream_t st = pick_stream(c, stream);
+    const uint32_t k = h.k;
+    const size_t n = (size_t)1 << k;
+    uint64_t launches = 0;
+    hipEvent_t e0, e1;
+    int rc = ev_pair(c, "witness", &e0, &e1);
+    if (rc) return rc;
+    EZ_HIP(hipEventRecord(e0, st));
+    for (uint32_t j = 0; j < h.n_advice; j++, launches++) EZ_HIP(hipMemsetAsync(cols.p[j], 0, n * sizeof(fe_t), st));
+    EZ_HIP(hipMemsetAsync(p->status, 0, 32, st));
+    launches++;
+    if (n_inputs) EZ_HIP(hipMemcpyAsync(p->inputs, inputs_host, n_inputs * 8, hipMemcpyHostToDevice, st));
+    for (size_t ri = 0; ri < h.recs.size(); ri++, launches++) {
+        const Rec& r = h.recs[ri];
+        switch (r.kind) {
+        case COPY: launch_elem<COPY>(st, cols, k, p, r, (uint32_t)ri); break;
+        case CONST: launch_elem<CONST>(st, cols, k, p, r, (uint32_t)ri); break;
+        case INPUT: launch_elem<INPUT>(st, cols, k, p, r, (uint32_t)ri); break;
+        case PARAM: launch_elem<PARAM>(st, cols, k, p, r, (uint32_t)ri); break;
+        case ADD: launch_elem<ADD>(st, cols, k, p, r, (uint32_t)ri); break;
+        case SUB: launch_elem<SUB>(st, cols, k, p, r, (uint32_t)ri); break;
+        case MUL: launch_elem<MUL>(st, cols, k, p, r, (uint32_t)ri); break;
+        case HINT: launch_elem<HINT>(st, cols, k, p, r, (uint32_t)ri); break;
+        case RCIDX: launch_elem<RCIDX>(st, cols, k, p, r, (uint32_t)ri); break;
+        case INVZ: launch_elem<INVZ>(st, cols, k, p, r, (uint32_t)ri); break;
+        default:
+            hipLaunchKernelGGL(wit_dot_kernel, dim3(cdiv((size_t)r.count * DOT_LANES, 64)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, p->pool + r.b, r.count, r.p0, r.p1,
+                               p->status);
+        }
+        EZ_HIP(hipGetLastError());
+    }
+    if (!h.outputs.empty()) {
+        hipLaunchKernelGGL(wit_gather_kernel, dim3(cdiv(h.outputs.size(), 64)), dim3(64), 0, st, cols, k, p->outputs, (uint32_t)h.outputs.size(), p->outs);
+        EZ_HIP(hipGetLastError());
+        launches++;
+    }
+    EZ_HIP(hipEventRecord(e1, st));
+    unsigned long long dev_status[4] = {0, 0, 0, 0};
+    if (!h.outputs.empty()) EZ_HIP(hipMemcpyAsync(outputs_host, p->outs, h.outputs.size() * 32, hipMemcpyDeviceToHost, st));
+    EZ_HIP(hipMemcpyAsync(dev_status, p->status, 32, hipMemcpyDeviceToHost, st));
+    EZ_HIP(hipStreamSynchronize(st));
+    status[0] = dev_status[0];
+    status[1] = dev_status[0] ? ~dev_status[1] : 0;
+    status[2] = dev_status[2];
+    status[3] = launches;
+    if (dev_status[0]) {
+        const uint32_t ri = (uint32_t)(status[1] >> 32), el = (uint32_t)status[1];
+        const uint32_t kind = ri < h.recs.size() ? h.recs[ri].kind : (uint32_t)N_KINDS;
+        t_wit_error = std::string("witness: value exceeds the decomposition range (") + (kind < N_KINDS ? KIND_NAMES[kind] : "?") + " record " + std::to_string(ri) +
+                      ", element " + std::to_string(el) + "; " + std::to_string(dev_status[0]) + " cells in all)";
+        return EZKL_ERR_INVALID;
+    }
+    t_wit_error.clear();
+    return EZKL_OK;
+}
+
+}  // extern "C"

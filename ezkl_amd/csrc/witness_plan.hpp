@@ -1,0 +1,175 @@
+// witness_plan.hpp -- the witness-plan blob (ezkl_amd/witness_plan.py writes it) parsed and validated on the host.  Plain C++, no device
+// code: libezkl_hip.so runs it before a plan reaches the device (ezkl_hip_witness_plan_upload), libezkl_prover.so exposes it as
+// ezkl_prover_witness_plan_check so that the sanitizer build (tools/asan_run.sh) covers it.  witness_plan.validate is its Python mirror.
+//
+// Layout (little-endian): 20 x u32 header -- magic "EZWP", version, k, n_advice, n_records, n_inputs, n_params, n_consts, n_outputs,
+// n_cells, n_words, n_ops, 8 reserved -- and the 32-byte parameter hash; then n_params x int64, n_consts x 32 bytes (canonical Fr),
+// n_records x {kind, count, p0, p1, dst, a, b, 0}, n_outputs x u32 cells, n_words x u32 pool.  Cells are numbered column * 2^k + row.
+#pragma once
+#include <stdint.h>
+#include <algorithm>
+#include <string.h>
+#include <string>
+#include <vector>
+
+namespace ezkl {
+namespace wplan {
+
+constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64;
+enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, N_KINDS };
+static const char* const KIND_NAMES[N_KINDS] = {"copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot"};
+struct Rec {
+    uint32_t kind, count, p0, p1, dst, a, b, pad;
+};
+struct Plan {
+    uint32_t k = 0, n_advice = 0, n_inputs = 0, n_cells = 0, n_ops = 0;
+    uint8_t param_hash[32] = {0};
+    std::vector<int64_t> params;
+    std::vector<uint8_t> consts;       // 32 bytes each, canonical
+    std::vector<Rec> recs;
+    std::vector<uint32_t> outputs, pool;
+};
+// BN254 Fr modulus, little-endian bytes (a constant must be canonical)
+static const uint8_t FR_MOD_LE[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
+                                      0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
+
+// the set of cells written so far.  Its memory is bounded by the BLOB, not by the geometry two header words claim: one bit per cell
+// when that is no more than the pool itself (a laid-out circuit: most cells are written), otherwise one bit per distinct pool word
+// (every cell a record can name is a pool word), found by binary search.
+class Written {
+    std::vector<uint64_t> w;
+    std::vector<uint32_t> keys;        // sparse form: the distinct pool words, sorted
+    bool dense;
+    uint64_t at(uint32_t cell) const { return dense ? cell : (uint64_t)(std::lower_bound(keys.begin(), keys.end(), cell) - keys.begin()); }
+public:
+    Written(uint64_t cells, const std::vector<uint32_t>& pool) : dense(cells <= 32 * (uint64_t)pool.size() + ((uint64_t)1 << 19)) {
+        if (!dense) {
+            keys = pool;
+            std::sort(keys.begin(), keys.end());
+            keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+        }
+        w.assign(((dense ? cells : keys.size()) + 63) / 64, 0);
+    }
+    bool get(uint32_t cell) const {
+        const uint64_t i = at(cell);
+        if (!dense && (i >= keys.size() || keys[i] != cell)) return false;     // not a pool word (an output cell can be anything)
+        return (w[i >> 6] >> (i & 63)) & 1;
+    }
+    void set(uint32_t cell) { const uint64_t i = at(cell); w[i >> 6] |= (uint64_t)1 << (i & 63); }
+};
+
+// parse + validate; false with `why` set when the blob is refused.  Everything the kernels index with is checked here: every cell
+// index < n_advice * 2^k, every table index in range, every pool span inside the pool, each cell written at most once and read only
+// after an EARLIER record has written it.
+inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
+    auto fail = [&](const std::string& s) { why = "witness plan: " + s; return false; };
+    auto at_rec = [&](size_t ri, uint32_t kind, const char* s) { return fail("record " + std::to_string(ri) + " (" + (kind < N_KINDS ? KIND_NAMES[kind] : "?") + "): " + s); };
+    const uint8_t* p = static_cast<const uint8_t*>(blob);
+    uint32_t h[20];
+    if (!blob || len < sizeof h + 32) return fail("shorter than its header");
+    memcpy(h, p, sizeof h);
+    if (h[0] != MAGIC) return fail("bad magic");
+    if (h[1] != VERSION) return fail("version " + std::to_string(h[1]) + ", this build reads " + std::to_string(VERSION));
+    const uint32_t k = h[2], n_adv = h[3], n_rec = h[4], n_in = h[5], n_par = h[6], n_con = h[7], n_out = h[8], n_cells = h[9], n_words = h[10];
+    if (k < 1 || k > 28 || n_adv == 0 || n_adv > MAX_ADVICE || ((uint64_t)n_adv << k) > ((uint64_t)1 << 32)) return fail("bad geometry");
+    const uint64_t want = (uint64_t)sizeof h + 32 + 8ull * n_par + 32ull * n_con + 32ull * n_rec + 4ull * n_out + 4ull * n_words;
+    if (want != len) return fail(std::to_string(len) + " bytes, its header says " + std::to_string(want));
+    out.k = k; out.n_advice = n_adv; out.n_inputs = n_in; out.n_cells = n_cells; out.n_ops = h[11];
+    p += sizeof h;
+    memcpy(out.param_hash, p, 32); p += 32;
+    out.params.resize(n_par);   if (n_par) memcpy(out.params.data(), p, 8ull * n_par);   p += 8ull * n_par;
+    out.consts.resize(32ull * n_con); if (n_con) memcpy(out.consts.data(), p, 32ull * n_con); p += 32ull * n_con;
+    out.recs.resize(n_rec);     if (n_rec) memcpy(out.recs.data(), p, 32ull * n_rec);    p += 32ull * n_rec;
+    out.outputs.resize(n_out);  if (n_out) memcpy(out.outputs.data(), p, 4ull * n_out);  p += 4ull * n_out;
+    out.pool.resize(n_words);   if (n_words) memcpy(out.pool.data(), p, 4ull * n_words);
+    for (uint32_t i = 0; i < n_con; i++) {               // canonical: below the modulus, compared from the top byte down
+        const uint8_t* c = out.consts.data() + 32ull * i;
+        int j = 31;
+        while (j >= 0 && c[j] == FR_MOD_LE[j]) j--;
+        if (j < 0 || c[j] > FR_MOD_LE[j]) return fail("a constant is not a canonical field element");
+    }
+    const uint64_t cells = (uint64_t)n_adv << k;
+    if (n_cells > n_words) return fail("more cells than index words");
+    Written written(cells, out.pool);
+    uint64_t total = 0;
+    const std::vector<uint32_t>& P = out.pool;
+    auto span_ok = [&](uint32_t off, uint64_t n) { return off <= P.size() && n <= P.size() - off; };
+    for (size_t ri = 0; ri < out.recs.size(); ri++) {
+        const Rec& r = out.recs[ri];
+        if (r.kind >= N_KINDS) return at_rec(ri, r.kind, "unknown kind");
+        if (r.count == 0) return at_rec(ri, r.kind, "empty");
+        uint64_t n_dst = r.count, n_a = r.count, n_b = 0;
+        bool a_cells = false, b_cells = false;
+        uint32_t a_lim = 0;
+        switch (r.kind) {
+        case COPY: case INVZ: a_cells = true; break;
+        case ADD: case SUB: case MUL: a_cells = b_cells = true; n_b = r.count; break;
+        case CONST: a_lim = n_con; break;
+        case INPUT: a_lim = n_in; break;
+        case PARAM: a_lim = n_par; break;
+        case HINT: {
+            a_cells = true; n_b = r.count;
+            uint64_t bound = 1;
+            if (r.p0 < 2 || r.p1 == 0) return at_rec(ri, r.kind, "bad decomposition");
+            for (uint32_t t = 0; t < r.p1; t++) {
+                if (bound > (((uint64_t)1 << 62) - 1) / r.p0) return at_rec(ri, r.kind, "bad decomposition");     // base^legs < 2^62, without overflow
+                bound *= r.p0;
+            }
+            break;
+        }
+        case RCIDX: a_cells = true; if (r.p1 == 0) return at_rec(ri, r.kind, "zero table column size"); break;
+        case DOT:
+            if (r.p0 == 0 || r.p1 == 0 || (uint64_t)r.count * r.p1 > P.size() || (uint64_t)r.count * r.p1 * r.p0 > P.size()) return at_rec(ri, r.kind, "bad dot shape");
+            n_dst = (uint64_t)r.count * r.p1; n_a = n_b = n_dst * r.p0; a_cells = b_cells = true;
+            break;
+        }
+        if (!span_ok(r.dst, n_dst) || !span_ok(r.a, n_a) || !span_ok(r.b, n_b)) return at_rec(ri, r.kind, "an index array runs past the pool");
+        const bool sparse = r.kind == DOT;               // 0xffffffff = no entry
+        for (uint64_t i = 0; i < n_a; i++) {
+            const uint32_t x = P[r.a + i];
+            if (sparse && x == NONE) {
+                if (P[r.b + i] != NONE) return at_rec(ri, r.kind, "a product with one operand");
+                continue;
+            }
+            if (a_cells) {
+                if (x >= cells) return at_rec(ri, r.kind, "cell index out of range");
+                if (!written.get(x)) return at_rec(ri, r.kind, "a cell is read before an earlier record has written it");
+            } else if (x >= a_lim) return at_rec(ri, r.kind, "table index out of range");
+        }
+        for (uint64_t i = 0; i < n_b; i++) {
+            const uint32_t x = P[r.b + i];
+            if (r.kind == HINT) {
+                if (x != NONE && x >= r.p1) return at_rec(ri, r.kind, "bad decomposition");
+                continue;
+            }
+            if (sparse && x == NONE) {
+                if (P[r.a + i] != NONE) return at_rec(ri, r.kind, "a product with one operand");
+                continue;
+            }
+            if (b_cells) {
+                if (x >= cells) return at_rec(ri, r.kind, "cell index out of range");
+                if (!written.get(x)) return at_rec(ri, r.kind, "a cell is read before an earlier record has written it");
+            }
+        }
+        // destinations after every source of the record: a record never reads what it writes
+        for (uint64_t i = 0; i < n_dst; i++) {
+            const uint32_t x = P[r.dst + i];
+            if (sparse && x == NONE) continue;
+            if (x >= cells) return at_rec(ri, r.kind, "cell index out of range");
+        }
+        for (uint64_t i = 0; i < n_dst; i++) {
+            const uint32_t x = P[r.dst + i];
+            if (sparse && x == NONE) continue;
+            if (written.get(x)) return at_rec(ri, r.kind, "a cell is written twice");
+            written.set(x);
+            total++;
+        }
+    }
+    if (total != n_cells) return fail(std::to_string(total) + " cells written, its header says " + std::to_string(n_cells));
+    for (uint32_t c : out.outputs)
+        if (c >= cells || !written.get(c)) return fail("an output cell is never written");
+    return true;
+}
+
+}  // namespace wplan
+}  // namespace ezkl

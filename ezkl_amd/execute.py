@@ -23,6 +23,7 @@ import numpy as np
 
 from . import backend as B
 from . import codecs, ezkl_layout as EL, native as NV
+from . import witness_plan as WP
 
 
 class CheckMode:
@@ -169,6 +170,16 @@ def setup(compiled_circuit, srs_path, vk_path, pk_path, sample_input=None):
     open(pk_path, "wb").write(data)
     vk_len = 7 + 64 * (cs.n_fixed + len(cs.perm)) + cs.n_selectors * ((cs.n + 7) // 8)
     open(vk_path, "wb").write(data[:vk_len])                   # vk.key is the prefix of pk.key
+    # the witness plan `prove` replays on the device: an OPTIONAL artefact, written after the keys.  A circuit the recorder refuses
+    # (WP.PlanError: e.g. a decomposition range beyond 62 bits, a parameter beyond int64) has none and proves on the host path.
+    try:
+        plan = WP.record_plan(circuit).to_bytes()
+    except WP.PlanError:
+        plan = None
+        if os.path.exists(pk_path + ".wplan"):                 # never leave another key's plan next to this one
+            os.remove(pk_path + ".wplan")
+    if plan is not None:
+        open(pk_path + ".wplan", "wb").write(plan)
     return dict(n_advice=cs.n_advice, n_fixed=cs.n_fixed, n_lookups=len(cs.lookups), degree=cs.degree, pk_bytes=len(data))
 
 
@@ -303,28 +314,94 @@ def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None
     return json.loads(text)
 
 
-def prove(witness_path, compiled_circuit, pk_path, proof_path, srs_path, check_mode=CheckMode.UNSAFE, seed=0, recommit=False):
+def _plan_for(circuit, pk_path):
+    """the witness plan setup wrote next to the key, if it is THIS circuit's (geometry and parameter hash); otherwise a fresh recording"""
+    try:
+        blob = open(pk_path + ".wplan", "rb").read()
+        h = WP.peek(blob)
+        if (h["k"], h["n_advice"], h["n_inputs"], h["param_hash"]) == (circuit.k, len(circuit.gc.cs.advice), circuit.n_inputs, WP.params_hash(circuit)):
+            return blob                                   # the upload validates the rest
+    except (OSError, WP.PlanError):
+        pass
+    return WP.record_plan(circuit).to_bytes()
+
+
+def _device_witness(circuit, pk_path, x, mode):
+    """synthesis on the device (backend.WitnessPlan): -> (resident advice columns, instance column, the run's counters), or None when
+    mode is "auto" and the device path is not to be taken: the gate is closed (ezkl_amd.enabled), there is no device, or the inputs do
+    not fit int64, or the recorder refuses the circuit (WP.PlanError).  mode "device" raises instead."""
+    import ezkl_amd
+    forced = mode == "device"
+    if not forced and not ezkl_amd.enabled(circuit.k):
+        return None
+    if any(not -(1 << 63) <= v < 1 << 63 for v in x) or len(circuit.gc.cs.advice) > 64:
+        if forced:
+            raise ValueError("synthesis=\"device\": an input does not fit int64, or the circuit has more than 64 advice columns")
+        return None
+    try:
+        blob = _plan_for(circuit, pk_path)
+    except WP.PlanError:                                 # a circuit the host engine lays out and the recorder does not: the host path
+        if forced:
+            raise
+        return None
+    try:
+        dev = B.WitnessPlan(blob)
+    except ezkl_amd.EzklHipError as e:
+        if forced or e.code != -1:                       # EZKL_ERR_NO_DEVICE: the host path, as before
+            raise
+        return None
+    try:
+        cols, outs = dev.run(x)
+        return cols, [outs], dev.last
+    finally:
+        dev.free()
+
+
+def prove(witness_path, compiled_circuit, pk_path, proof_path, srs_path, check_mode=CheckMode.UNSAFE, seed=0, recommit=False, synthesis="auto",
+          report=None):
     """GraphWitness + compiled circuit + pk + SRS files -> proof.json (Snark).  seed = 0: OS entropy (OsRng); otherwise the
-    reference's det-prove.  CheckMode.SAFE verifies the proof before returning it, as create_proof_circuit does."""
+    reference's det-prove.  CheckMode.SAFE verifies the proof before returning it, as create_proof_circuit does.
+    synthesis: where the advice columns are made -- "host": the layout engine, cell by cell (circuit.witness), uploaded by create_proof;
+    "device": the witness plan replayed by HIP kernels into resident columns that create_proof takes as they are (raises if that cannot
+    be done); "auto": the device when the GPU gate is open (ezkl_amd.enabled(k)) and a device is there, else the host.  The proof bytes
+    are the same either way.  report (a dict, may be None) receives how the witness was made: {"path": "host"} or {"path": "device",
+    "cells_written", "launches", "device_ms", ...} -- the counters of backend.WitnessPlan.run."""
+    if synthesis not in ("auto", "host", "device"):
+        raise ValueError("synthesis must be \"auto\", \"host\" or \"device\"")
     w = codecs.read_witness_json(open(witness_path).read())
     circuit, j = _load_circuit(compiled_circuit)
     if len(w["inputs"]) != 1 or len(w["inputs"][0]) != circuit.n_inputs:
         raise ValueError("witness does not match the circuit's input shape")
     signed = lambda v: v if v < EL.R // 2 else v - EL.R
     cs = circuit.gc.cs
-    adv, inst = circuit.witness([signed(v) for v in w["inputs"][0]])            # GraphCircuit::synthesize
-    if w["outputs"] and inst != w["outputs"]:
-        raise ValueError("the witness file's outputs do not match the circuit's outputs")
-    ncs = _plonk_cs(circuit)
-    srs = load_params_prover(srs_path, circuit.k)                               # downsizes an SRS file larger than the circuit
-    bg, bgl = B.Bases(srs["g"]), B.Bases(srs["g_lagrange"])
+    x = [signed(v) for v in w["inputs"][0]]
+    made = _device_witness(circuit, pk_path, x, synthesis) if synthesis != "host" else None
+    if made is None:
+        adv, inst = circuit.witness(x)                                          # GraphCircuit::synthesize
+        how = dict(path="host")
+    else:
+        adv, inst, counters = made                                              # the same columns, already on the device
+        how = dict(counters, path="device")
+    if report is not None:
+        report.clear()
+        report.update(how)
+    resident = adv if made is not None else []                                  # DeviceBuffers to give back, whatever happens below
     try:
-        # recommit: the key file's commitments were made under ANOTHER SRS (the reference's fixture key: the public powers of tau)
-        pk = NV.NativeProvingKey.from_bytes(NV.NativeCircuit(ncs), open(pk_path, "rb").read(), recommit=bg if recommit else None)
-        proof = NV.create_proof(pk, bg, bgl, EL.cols_to_mont(adv, B), seed=seed, instances=inst, check_mode=check_mode,
-                                g2=srs["g2"], s_g2=srs["s_g2"])
+        if w["outputs"] and inst != w["outputs"]:
+            raise ValueError("the witness file's outputs do not match the circuit's outputs")
+        ncs = _plonk_cs(circuit)
+        srs = load_params_prover(srs_path, circuit.k)                           # downsizes an SRS file larger than the circuit
+        bg, bgl = B.Bases(srs["g"]), B.Bases(srs["g_lagrange"])
+        try:
+            # recommit: the key file's commitments were made under ANOTHER SRS (the reference's fixture key: the public powers of tau)
+            pk = NV.NativeProvingKey.from_bytes(NV.NativeCircuit(ncs), open(pk_path, "rb").read(), recommit=bg if recommit else None)
+            proof = NV.create_proof(pk, bg, bgl, adv if made is not None else EL.cols_to_mont(adv, B), seed=seed, instances=inst,
+                                    check_mode=check_mode, g2=srs["g2"], s_g2=srs["s_g2"])
+        finally:
+            bg.free(); bgl.free()
     finally:
-        bg.free(); bgl.free()
+        for c in resident:
+            c.free()
     open(proof_path, "w").write(codecs.write_proof_json(proof, inst))
     return proof
 

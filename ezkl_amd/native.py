@@ -16,7 +16,7 @@ _lib = None
 SYMBOLS = ["ezkl_prover_cs_parse", "ezkl_prover_cs_free", "ezkl_prover_cs_info", "ezkl_prover_cs_set_shard", "ezkl_prover_cs_set_shard_comm", "ezkl_prover_cs_set_shard_full_bases", "ezkl_prover_cs_set_advice_by_pointer", "ezkl_prover_cs_set_sweep_gather",
            "ezkl_prover_cs_sharded_sweeps", "ezkl_prover_cs_set_shard_exchange", "ezkl_prover_cs_shard_stats", "ezkl_prover_group_create", "ezkl_prover_group_size", "ezkl_prover_group_free",
            "ezkl_prover_group_load_srs", "ezkl_prover_group_keygen", "ezkl_prover_group_pk", "ezkl_prover_group_pk_read_file", "ezkl_prover_pk_residency", "ezkl_prover_group_create_proof", "ezkl_prover_keygen", "ezkl_prover_pk_free", "ezkl_prover_pk_sweep_stats", "ezkl_prover_pk_write", "ezkl_prover_pk_read", "ezkl_prover_pk_read_file", "ezkl_prover_pk_recommit", "ezkl_prover_pk_set_selectors", "ezkl_prover_pk_set_transcript_repr", "ezkl_prover_vk",
-           "ezkl_prover_create_proof", "ezkl_prover_create_proof_fmt", "ezkl_prover_mock", "ezkl_prover_verify_proof", "ezkl_prover_verify_proof_vk", "ezkl_prover_g2_mul_generator", "ezkl_prover_keccak256", "ezkl_prover_last_error"]
+           "ezkl_prover_create_proof", "ezkl_prover_create_proof_fmt", "ezkl_prover_mock", "ezkl_prover_verify_proof", "ezkl_prover_verify_proof_vk", "ezkl_prover_g2_mul_generator", "ezkl_prover_keccak256", "ezkl_prover_last_error", "ezkl_prover_witness_plan_check"]
 ADVICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p))
 RNG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_size_t)
 FOLD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32)
@@ -378,7 +378,9 @@ def create_proof(pk, g, g_lagrange, advice_values, rng=None, seed=0, instances=(
     """advice_values: list of columns, or a callable advice_values(phase, challenges) -> {column: array} (second-phase advice).  A column
     is an (n, 4) uint64 array of Montgomery words (halo2's Fp), or the INTEGERS its cells were made from (ezkl's IntegerRep,
     src/fieldutils.rs:6-17): an (n,) int64 array, or an (n, 2) uint64 array of little-endian two's-complement 128-bit values -- 8 / 16
-    bytes per cell across PCIe instead of 32, expanded on the device (ezkl_prover_create_proof_fmt); the proof bytes are the same.  rng: object with .vec(m) -> (m,4) u64 Montgomery residues (None = the library's own
+    bytes per cell across PCIe instead of 32, expanded on the device (ezkl_prover_create_proof_fmt); or a backend.DeviceBuffer of 2^k
+    Montgomery words already on the device (a witness synthesized there, backend.WitnessPlan.run): it is not copied to the host and is
+    left as it is; the proof bytes are the same in every case, and the kinds mix freely.  rng: object with .vec(m) -> (m,4) u64 Montgomery residues (None = the library's own
     generator, seeded with `seed`, 0 = OS entropy); instances: list of lists of ints.  Returns the proof bytes."""
     cs = pk.circuit.cs
     n = cs.n
@@ -406,6 +408,12 @@ def create_proof(pk, g, g_lagrange, advice_values, rng=None, seed=0, instances=(
     else:
         fmts = []
         for a in advice_values:
+            if hasattr(a, "ptr") and hasattr(a, "nbytes"):             # backend.DeviceBuffer: a resident column (EZKL_COLUMN_DEVICE_FP), taken without a host round trip
+                if not a.ptr or a.nbytes < 32 * n:
+                    raise ValueError("advice column %d: a device column needs %d bytes" % (len(fmts), 32 * n))
+                fmts.append(3)
+                keep.append(a)
+                continue
             a = np.asarray(a)
             # the format follows from dtype AND shape; anything else is refused rather than reinterpreted (a mis-shaped Montgomery
             # column taken for integers would prove a different witness)
@@ -421,7 +429,7 @@ def create_proof(pk, g, g_lagrange, advice_values, rng=None, seed=0, instances=(
             if a.shape[0] != n:
                 raise ValueError("advice column %d has %d rows, the circuit has %d" % (len(fmts), a.shape[0], n))
             keep.append(a)
-        adv_arr = _ptr_array(keep)
+        adv_arr = (C.c_void_p * max(1, len(keep)))(*[a.ptr if f == 3 else a.ctypes.data for a, f in zip(keep, fmts)])
         if any(fmts):
             adv_fmt = (C.c_uint8 * len(fmts))(*fmts)
     rng_cb = C.cast(None, RNG_FN)

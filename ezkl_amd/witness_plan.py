@@ -1,0 +1,622 @@
+"""Witness plans: the layout of an MlpCircuit recorded ONCE, replayed for every proof.
+
+Which advice cell holds which value depends only on the circuit (BaseRegion places cells from the linear coordinate, the duplicated rows
+of `dot` from the block geometry; constants, weights and biases are the same for every input), so `record_plan` runs one witness-free
+layout pass over a BaseRegion subclass whose VALUES are symbols: the placement code that runs is BaseRegion's own (cell_of, flush,
+_dup_inputs, the duplicate row at the top of a new column, every layouts.rs op as BaseRegion lays it out), and every `put` records how
+the cell it wrote is produced from earlier cells, a model input, a circuit parameter or a constant.  The cell writes are grouped into
+RECORDS -- one kernel launch each on the device (csrc/witness.hip) -- by data dependence: a write joins the latest record of its kind
+when everything it reads was written by an earlier record, so the 650 dot products of a layer are one record, not 650.
+
+The plan is a flat little-endian blob (`WitnessPlan.to_bytes`):
+
+    header   20 x u32: magic "EZWP", version, k, n_advice, n_records, n_inputs, n_params, n_consts, n_outputs, n_cells, n_words, n_ops,
+             then the 32-byte parameter hash
+    params   n_params  x int64        weights then biases (fixed at record time)
+    consts   n_consts  x 32 bytes     canonical field elements
+    records  n_records x 8 u32        kind, count, p0, p1, dst, a, b, 0   (dst / a / b: word offsets into the pool)
+    outputs  n_outputs x u32          the cells that hold the circuit's outputs
+    pool     n_words   x u32          cell indices (column * 2^k + row), table indices, per-element arguments
+
+A record of an element-wise kind has `count` destination cells pool[dst + i], produced from pool[a + i] (and pool[b + i]):
+
+    COPY a = source cell | CONST a = constant index | INPUT a = input index | PARAM a = parameter index | ADD, SUB, MUL a, b = source cells
+    HINT   a = source cell, b = 0xffffffff: the sign of the signed value; else the digit (|x| // p0^b) % p0; p0 = base, p1 = legs, and
+           |x| >= p0^p1 is the decomposition-range failure
+    RCIDX  a = source cell: |x - p0| // p1 (p0 = the range's lower end as int32, p1 = the table column size); |x| >= 2^62 -- more than a lane
+           holds in 64 bits, never a sign or a digit -- is reported like a decomposition-range failure, here and on the device
+    INVZ   a = source cell: 1 / x, or 0 for x = 0
+    DOT    count dot products of p1 steps of p0 products each, step-major: step s of dot d writes the running sum to pool[dst + s * count + d]
+           (0xffffffff: no such step) after adding the products of pool[a + (s * p0 + j) * count + d] and pool[b + ...] (0xffffffff: none --
+           the duplicated running sum at the top of a new column is a step without products)
+
+COUPLING WITH ezkl_layout.py.  The recorder reuses BaseRegion's value expressions too, by operator overloading on the symbols below, and
+recognises them AS THEY ARE SPELT there.  Whoever rewrites one of these lines of BaseRegion must extend the symbol classes with it (the
+equality tests of tests/test_witness_plan_cpu.py fail loudly -- an assert or a PlanError during recording -- until then):
+    decompose / range_check   `s = v if v < R // 2 else v - R`   (a comparison with exactly R // 2 answers True: the symbol IS the signed value)
+    decompose                 `(s > 0) - (s < 0)`, `abs(s)`, `(mag // base ** e) % base`, `assert mag < base ** legs` (recorded as the run-time check)
+    range_check               `abs(s - lo) // col_size`
+    pairwise                  `x + y`, `x - y`, `x * y` on two assigned cells
+    dot                       `acc = (acc + sum(x.v * y.v for ...)) % R` with acc and sum() starting from the integer 0
+    equals_zero               `pow(v, -1, R) if v else 0`   (the truth value of a cell symbol is True: INVZ covers both branches)
+    Val.__init__ and the ops  `... % R` on any symbol is the symbol
+
+Every cell is written at most once and only reads cells of earlier records; `validate` checks that (the C library runs the same check
+on upload).  `run_plan_host` interprets the blob with Python integers: the executable specification of the device kernels."""
+import hashlib
+import struct
+
+import numpy as np
+
+from . import ezkl_circuit as EC
+from . import ezkl_layout as EL
+
+R = EL.R
+MAGIC, VERSION = 0x50575A45, 1                  # "EZWP"
+NONE = 0xFFFFFFFF
+COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT = range(11)
+KIND_NAMES = ["copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot"]
+_HEADER = struct.Struct("<20I32s")
+RANGE_ERROR = "value exceeds the decomposition range"
+
+
+class PlanError(ValueError):
+    pass
+
+
+# ---- symbolic values: what a Val's .v holds during the recording pass -------------------------------------------------------------------
+class _Sym:
+    """a value the layout does arithmetic on; only the forms BaseRegion's ops use exist, anything else is refused by name"""
+    __hash__ = object.__hash__
+
+    def __mod__(self, m):                          # Val.__init__ and the ops reduce mod r
+        assert m == R
+        return self
+
+    def _no(self, *a, **kw):
+        raise PlanError("the witness plan recorder does not cover this use of a %s value" % type(self).__name__)
+    __add__ = __radd__ = __sub__ = __rsub__ = __mul__ = __rmul__ = __floordiv__ = __lt__ = __gt__ = __le__ = __ge__ = __abs__ = __pow__ = _no
+    __bool__ = __int__ = __index__ = _no
+
+
+class _Cell(_Sym):
+    """the value of an advice cell written earlier"""
+
+    def __init__(self, idx): self.idx = idx
+    def __add__(self, o): return _Bin(ADD, self, o)
+    def __sub__(self, o): return _Bin(SUB, self, o) if isinstance(o, _Cell) else _Shift(self, o)
+    def __mul__(self, o): return _Bin(MUL, self, o)
+    def __lt__(self, o): return True if o == R // 2 else _Cmp(self, "<", o)     # `v if v < R // 2 else v - R`: the signed value is the symbol itself
+    def __gt__(self, o): return _Cmp(self, ">", o)
+    def __abs__(self): return _Mag(self)
+    def __bool__(self): return True                                             # `pow(v, -1, R) if v else 0` is INVZ either way
+    def __pow__(self, e, m=None):
+        assert e == -1 and m == R
+        return _Un(INVZ, self)
+
+
+class _Input(_Sym):
+    def __init__(self, idx): self.idx = idx
+
+
+class _Param(_Sym):
+    def __init__(self, idx): self.idx = idx
+
+
+class _Bin(_Sym):
+    def __init__(self, kind, a, b):
+        if not (isinstance(a, _Cell) and isinstance(b, _Cell)):
+            self._no()
+        self.kind, self.a, self.b = kind, a.idx, b.idx
+
+    def __radd__(self, o):                         # sum(products) starts from 0
+        assert self.kind == MUL and o == 0
+        return _Products([(self.a, self.b)])
+
+
+class _Products(_Sym):
+    """the w products of one dot step"""
+
+    def __init__(self, pairs): self.pairs = pairs
+    def __add__(self, o):
+        assert isinstance(o, _Bin) and o.kind == MUL
+        return _Products(self.pairs + [(o.a, o.b)])
+    def __radd__(self, o):                         # acc + products, acc = 0 on the first step
+        assert o == 0
+        return _Acc(None, self.pairs)
+
+
+class _Acc(_Sym):
+    """a running dot sum: the previous running sum (None on the first step) plus this step's products; `cell` once it has been put"""
+
+    def __init__(self, prev, pairs): self.prev, self.pairs, self.cell = prev, pairs, None
+    def __add__(self, o):
+        assert isinstance(o, _Products)
+        return _Acc(self, o.pairs)
+
+
+class _Un(_Sym):
+    def __init__(self, kind, a): self.kind, self.a = kind, a.idx
+
+
+class _Cmp(_Sym):
+    def __init__(self, a, op, c):
+        assert c == 0
+        self.a, self.op = a, op
+    def __sub__(self, o):                          # (s > 0) - (s < 0)
+        assert isinstance(o, _Cmp) and self.op == ">" and o.op == "<" and o.a is self.a
+        return _Sign(self.a)
+
+
+class _Sign(_Sym):
+    def __init__(self, a): self.a = a.idx
+
+
+class _Mag(_Sym):
+    """|signed value|; `mag < base ** legs` is the layout's range assertion: it is recorded, and checked at run time"""
+
+    def __init__(self, a): self.a, self.bound = a.idx, None
+    def __floordiv__(self, d): return _MagDiv(self, d)
+    def __lt__(self, bound):
+        self.bound = bound
+        return True
+
+
+class _MagDiv(_Sym):
+    """|x| // base^e, then `% base`: a digit"""
+
+    def __init__(self, mag, div, base=None): self.mag, self.div, self.base = mag, div, base
+    def __mod__(self, m):
+        if self.base is None:
+            return _MagDiv(self.mag, self.div, m)
+        assert m == R
+        return self
+
+
+class _Shift(_Sym):
+    """signed value - lo, |.| // col_size: the table-column index of a range check"""
+
+    def __init__(self, a, lo): self.a, self.lo, self.absd, self.col_size = a.idx, lo, False, None
+    def __abs__(self):
+        self.absd = True
+        return self
+    def __floordiv__(self, c):
+        assert self.absd
+        self.col_size = c
+        return self
+
+
+def _ilog(x, base):
+    e = 0
+    while x > 1 and x % base == 0:
+        x //= base
+        e += 1
+    if x != 1:
+        raise PlanError("a digit divisor that is not a power of the base")
+    return e
+
+
+# ---- the recording region ----------------------------------------------------------------------------------------------------------------
+class _Records:
+    """cell writes grouped by kind and data dependence"""
+
+    def __init__(self):
+        self.recs = []                             # dict(kind, p0, p1, dst, a, b) / for DOT: dict(kind, p0, dots)
+        self.latest = {}                           # (kind, p0, p1) -> record index
+        self.rec_of = {}                           # cell -> record that writes it
+
+    def _slot(self, key, sources):
+        need = 1 + max((self.rec_of[s] for s in sources), default=-1)
+        ri = self.latest.get(key)
+        if ri is None or ri < need:
+            ri = self.latest[key] = len(self.recs)
+            self.recs.append(dict(kind=key[0], p0=key[1], p1=key[2], dst=[], a=[], b=[], dots=[]))
+        return ri
+
+    def _claim(self, dst, ri):
+        if dst in self.rec_of:
+            raise PlanError("advice cell %d is written twice: not a write-once layout" % dst)
+        self.rec_of[dst] = ri
+
+    def emit(self, kind, dst, a, b=None, p0=0, p1=0, reads=()):
+        for s in reads:
+            if s not in self.rec_of:
+                raise PlanError("advice cell %d is read before it is written" % s)
+        ri = self._slot((kind, p0, p1), reads)
+        rec = self.recs[ri]
+        rec["dst"].append(dst); rec["a"].append(a)
+        if b is not None:
+            rec["b"].append(b)
+        self._claim(dst, ri)
+
+    def emit_dot(self, w, steps):
+        """steps: [(dst, [(a, b), ...])]"""
+        reads = [c for _, pairs in steps for ab in pairs for c in ab]
+        for s in reads:
+            if s not in self.rec_of:
+                raise PlanError("advice cell %d is read before it is written" % s)
+        ri = self._slot((DOT, w, 0), reads)
+        self.recs[ri]["dots"].append(steps)
+        for dst, _ in steps:
+            self._claim(dst, ri)
+
+
+class RecordingRegion(EL.BaseRegion):
+    """BaseRegion with symbolic values: every placement decision is the parent's; `put` records how the cell is produced"""
+
+    def __init__(self, gc):
+        super().__init__(gc, witness=False)
+        self.n_adv = len(gc.cs.advice)
+        self.out = _Records()
+        self.consts, self.const_idx = [], {}
+        self.n_ops = 0
+        self._dot = None
+
+    def copy(self, a, b):                          # copy constraints belong to keygen, not to the witness
+        pass
+
+    def _const(self, v):
+        v %= R
+        if v not in self.const_idx:
+            self.const_idx[v] = len(self.consts)
+            self.consts.append(v)
+        return self.const_idx[v]
+
+    def put(self, var, linear, val):
+        placed = super().put(var, linear, val)     # cell_of / cartesian_coord: the parent's placement
+        _, col, row = placed.cell
+        dst = (col << self.k) + row
+        v, out = val.v, self.out
+        if isinstance(v, int):
+            out.emit(CONST, dst, self._const(v))
+        elif isinstance(v, _Cell):
+            if self._dot is not None and self._dot and v.idx == self._dot[-1][0]:
+                self._dot.append((dst, []))        # the running sum duplicated at the top of a new column: a step without products
+            else:
+                out.emit(COPY, dst, v.idx, reads=(v.idx,))
+        elif isinstance(v, _Input):
+            out.emit(INPUT, dst, v.idx)
+        elif isinstance(v, _Param):
+            out.emit(PARAM, dst, v.idx)
+        elif isinstance(v, _Bin):
+            out.emit(v.kind, dst, v.a, v.b, reads=(v.a, v.b))
+        elif isinstance(v, _Un):
+            out.emit(v.kind, dst, v.a, reads=(v.a,))
+        elif isinstance(v, _Sign):
+            base, legs = self._decomp
+            out.emit(HINT, dst, v.a, NONE, p0=base, p1=legs, reads=(v.a,))
+        elif isinstance(v, _MagDiv) and v.base is not None:
+            base, legs = self._decomp
+            if v.base != base or v.mag.bound != base ** legs:
+                raise PlanError("a digit hint without the layout's range assertion")
+            out.emit(HINT, dst, v.mag.a, _ilog(v.div, base), p0=base, p1=legs, reads=(v.mag.a,))
+        elif isinstance(v, _Shift) and v.col_size is not None:
+            if not -(1 << 31) <= v.lo < 1 << 31 or not 0 < v.col_size < 1 << 32:
+                raise PlanError("range check bounds beyond 32 bits")
+            out.emit(RCIDX, dst, v.a, p0=v.lo & NONE, p1=v.col_size, reads=(v.a,))
+        elif isinstance(v, _Acc):
+            summed = [cell for cell, pairs in self._dot or [] if pairs]    # the steps so far, without the duplicated rows
+            if self._dot is None or v.cell is not None or (v.prev is None) != (not summed) or (summed and v.prev.cell != summed[-1]):
+                raise PlanError("a running sum outside the dot it belongs to")
+            v.cell = dst
+            self._dot.append((dst, v.pairs))
+        else:
+            raise PlanError("the witness plan recorder does not cover a %s value" % type(v).__name__)
+        return EL.Val(_Cell(dst), placed.cell)
+
+    # ---- the ops: BaseRegion's own, counted; the out-of-scope ones refused by name -------------------------------------------------------
+    def _counted(name):
+        def op(self, *a, **kw):
+            self.n_ops += 1
+            return getattr(EL.BaseRegion, name)(self, *a, **kw)
+        op.__name__ = name
+        return op
+    pairwise, enforce_equality, range_check = _counted("pairwise"), _counted("enforce_equality"), _counted("range_check")
+
+    def decompose(self, vals, base, legs):
+        self.n_ops += 1
+        self._decomp = (base, legs)
+        if base ** legs >= 1 << 62:
+            raise PlanError("decomposition range beyond 62 bits")
+        return super().decompose(vals, base, legs)
+
+    def dot(self, a, b):
+        self.n_ops += 1
+        self._dot = []
+        try:
+            last = super().dot(a, b)
+            steps = self._dot
+        finally:
+            self._dot = None
+        self.out.emit_dot(self.w, steps)
+        return last
+
+    def _refused(name):
+        def op(self, *a, **kw):
+            raise PlanError("witness plans do not cover `%s` (the MLP op family only: decompose, range_check, dot, pairwise, "
+                            "enforce_equality, equals_zero, relu, output_equals_instance)" % name)
+        return op
+    nonlinearity, sum, prod, _accumulate = _refused("nonlinearity"), _refused("sum"), _refused("prod"), _refused("sum / prod")
+    dynamic_lookup, shuffle, _lookup_any = _refused("dynamic_lookup"), _refused("shuffle"), _refused("lookup_any")
+    del _counted, _refused
+
+
+def params_hash(circuit):
+    """what a plan depends on besides the layout code: the circuit's shape options and its parameters"""
+    h = hashlib.sha256()
+    h.update(struct.pack("<8q", circuit.k, circuit.w, circuit.base, circuit.legs, int(circuit.relu_last), int(circuit.relu_first), circuit.n_inputs,
+                         len(circuit.weights)))
+    for W, b in zip(circuit.weights, circuit.biases):
+        h.update(struct.pack("<3q", len(W), len(W[0]), len(b)))
+        h.update(np.asarray(W, np.int64).tobytes())
+        h.update(np.asarray(b, np.int64).tobytes())
+    return h.digest()
+
+
+def record_plan(circuit):
+    """one witness-free layout pass of an MlpCircuit -> WitnessPlan.  The op sequence is MlpCircuit.synthesize's, with the input vector and
+    the parameters as symbols; every other circuit class is refused by name."""
+    if type(circuit) is not EL.MlpCircuit:
+        raise PlanError("witness plans cover MlpCircuit only, not %s (conv, einsum and the surrogate circuits keep the host path)" % type(circuit).__name__)
+    if any(c.phase != 0 for c in circuit.gc.cs.advice):
+        raise PlanError("witness plans do not cover second-phase advice")
+    reg = RecordingRegion(circuit.gc)
+    if (len(circuit.gc.cs.advice) << circuit.k) > 1 << 32:
+        raise PlanError("cells are numbered in 32 bits")
+    Val = EL.Val
+    params = []
+    def param(v):
+        if not -(1 << 63) <= v < 1 << 63:
+            raise PlanError("a parameter beyond int64")
+        params.append(int(v))
+        return Val(_Param(len(params) - 1))
+    vals = [Val(_Input(i)) for i in range(circuit.n_inputs)]
+    _, vals = reg.decompose(vals, circuit.base, circuit.legs)
+    if circuit.relu_first:
+        vals = reg.relu(vals, circuit.base, circuit.legs)
+    for i, (W, b) in enumerate(zip(circuit.weights, circuit.biases)):
+        outs = [reg.dot(vals, [param(wv) for wv in row]) for row in W]
+        vals = reg.pairwise(outs, [param(bv) for bv in b], EC.ADD)
+        if i + 1 < len(circuit.weights) or circuit.relu_last:
+            vals = reg.relu(vals, circuit.base, circuit.legs)
+    outputs = [v.v.idx for v in vals]                          # MlpCircuit.outputs: the values the final equality is made on
+    reg.output_equals_instance(vals, circuit.gc.instance, 0, circuit.base, circuit.legs)
+    # (reg.finish writes the fixed constant column: keygen's, not the witness's)
+    return WitnessPlan._from_recorder(circuit, reg, params, outputs)
+
+
+class WitnessPlan:
+    def __init__(self, k, n_advice, n_inputs, params, consts, records, outputs, pool, n_cells, n_ops, param_hash):
+        self.k, self.n_advice, self.n_inputs = k, n_advice, n_inputs
+        self.params = np.ascontiguousarray(params, np.int64)
+        self.consts = [int(c) for c in consts]
+        self.records = np.ascontiguousarray(records, np.uint32).reshape(-1, 8)
+        self.outputs = np.ascontiguousarray(outputs, np.uint32)
+        self.pool = np.ascontiguousarray(pool, np.uint32)
+        self.n_cells, self.n_ops, self.param_hash = n_cells, n_ops, bytes(param_hash)
+
+    @classmethod
+    def _from_recorder(cls, circuit, reg, params, outputs):
+        pool, records, n_cells = [], [], 0
+        off = 0
+        def push(a):
+            nonlocal off
+            a = np.asarray(a, np.uint32).reshape(-1)
+            pool.append(a)
+            off += len(a)
+            return off - len(a)
+        for rec in reg.out.recs:
+            if rec["kind"] == DOT:
+                w, dots = rec["p0"], rec["dots"]
+                nd, ns = len(dots), max(len(d) for d in dots)
+                dst = np.full((ns, nd), NONE, np.uint32)
+                a = np.full((ns, w, nd), NONE, np.uint32)
+                b = np.full((ns, w, nd), NONE, np.uint32)
+                for d, steps in enumerate(dots):
+                    for s, (cell, pairs) in enumerate(steps):
+                        dst[s, d] = cell
+                        for j, (x, y) in enumerate(pairs):
+                            a[s, j, d], b[s, j, d] = x, y
+                    n_cells += len(steps)
+                records.append([DOT, nd, w, ns, push(dst), push(a), push(b), 0])
+            else:
+                n = len(rec["dst"])
+                n_cells += n
+                records.append([rec["kind"], n, rec["p0"], rec["p1"], push(rec["dst"]), push(rec["a"]), push(rec["b"]) if rec["b"] else 0, 0])
+        return cls(circuit.k, reg.n_adv, circuit.n_inputs, params, reg.consts, records, outputs,
+                   np.concatenate(pool) if pool else np.zeros(0, np.uint32), n_cells, reg.n_ops, params_hash(circuit))
+
+    # ---- the blob ------------------------------------------------------------------------------------------------------------------------
+    def to_bytes(self):
+        head = _HEADER.pack(MAGIC, VERSION, self.k, self.n_advice, len(self.records), self.n_inputs, len(self.params), len(self.consts),
+                            len(self.outputs), self.n_cells, len(self.pool), self.n_ops, 0, 0, 0, 0, 0, 0, 0, 0, self.param_hash)
+        return b"".join([head, self.params.astype("<i8").tobytes(), b"".join(c.to_bytes(32, "little") for c in self.consts),
+                         self.records.astype("<u4").tobytes(), self.outputs.astype("<u4").tobytes(), self.pool.astype("<u4").tobytes()])
+
+    @classmethod
+    def from_bytes(cls, blob):
+        blob = bytes(blob)
+        if len(blob) < _HEADER.size:
+            raise PlanError("witness plan: shorter than its header")
+        f = _HEADER.unpack_from(blob)
+        if f[0] != MAGIC:
+            raise PlanError("witness plan: bad magic")
+        if f[1] != VERSION:
+            raise PlanError("witness plan: version %d, this build reads %d" % (f[1], VERSION))
+        _, _, k, n_adv, n_rec, n_in, n_par, n_con, n_out, n_cells, n_words, n_ops = f[:12]
+        sizes = [8 * n_par, 32 * n_con, 32 * n_rec, 4 * n_out, 4 * n_words]
+        if len(blob) != _HEADER.size + sum(sizes):
+            raise PlanError("witness plan: %d bytes, its header says %d" % (len(blob), _HEADER.size + sum(sizes)))
+        o = [_HEADER.size]
+        for s in sizes:
+            o.append(o[-1] + s)
+        params = np.frombuffer(blob, "<i8", n_par, o[0])
+        consts = [int.from_bytes(blob[o[1] + 32 * i:o[1] + 32 * i + 32], "little") for i in range(n_con)]
+        records = np.frombuffer(blob, "<u4", 8 * n_rec, o[2])
+        outputs = np.frombuffer(blob, "<u4", n_out, o[3])
+        pool = np.frombuffer(blob, "<u4", n_words, o[4])
+        return cls(k, n_adv, n_in, params, consts, records, outputs, pool, n_cells, n_ops, f[20])
+
+    def __eq__(self, other):
+        return isinstance(other, WitnessPlan) and self.to_bytes() == other.to_bytes()
+
+    @property
+    def n_records(self):
+        return len(self.records)
+
+    def validate(self):
+        validate(self)
+        return self
+
+
+def peek(blob):
+    """the header of a plan blob: what `prove` compares with the compiled circuit before it uploads the blob"""
+    if len(blob) < _HEADER.size:
+        raise PlanError("witness plan: shorter than its header")
+    f = _HEADER.unpack_from(blob)
+    if f[0] != MAGIC or f[1] != VERSION:
+        raise PlanError("witness plan: bad magic or version")
+    names = ["k", "n_advice", "n_records", "n_inputs", "n_params", "n_consts", "n_outputs", "n_cells", "n_words", "n_ops"]
+    return dict(zip(names, f[2:12]), param_hash=f[20])
+
+
+def _span(plan, off, n, what, ri):
+    if off > len(plan.pool) or n > len(plan.pool) - off:
+        raise PlanError("witness plan: record %d: %s runs past the pool" % (ri, what))
+    return plan.pool[off:off + n]
+
+
+class _Written:
+    """the set of cells written so far, as csrc/witness_plan.hpp keeps it: memory bounded by the blob, not by the geometry its header claims
+    -- one flag per cell when that is no more than the pool itself, otherwise one per distinct pool word (binary search)"""
+
+    def __init__(self, cells, pool):
+        self.keys = None if cells <= 32 * len(pool) + (1 << 19) else np.unique(pool)
+        self.flags = np.zeros(cells if self.keys is None else len(self.keys), bool)
+
+    def _at(self, x):
+        if self.keys is None:
+            return x, np.ones(len(x), bool)
+        i = np.minimum(np.searchsorted(self.keys, x), max(len(self.keys) - 1, 0))
+        return i, (self.keys[i] == x if len(self.keys) else np.zeros(len(x), bool))
+
+    def get(self, x):
+        i, known = self._at(x)
+        return self.flags[i] & known if len(self.flags) else known
+
+    def set(self, x):
+        self.flags[self._at(x)[0]] = True
+
+
+def validate(plan):
+    """the check ezkl_hip_witness_plan_upload makes before anything reaches the device, mirrored line by line: geometry, every cell index below
+    n_advice * 2^k, every table index in range, every cell written at most once and read only after an EARLIER record wrote it"""
+    if not 1 <= plan.k <= 28 or not 0 < plan.n_advice <= 64 or (plan.n_advice << plan.k) > 1 << 32:
+        raise PlanError("witness plan: bad geometry")
+    cells = plan.n_advice << plan.k
+    if any(c >= R for c in plan.consts):
+        raise PlanError("witness plan: a constant is not a canonical field element")
+    if plan.n_cells > len(plan.pool):
+        raise PlanError("witness plan: more cells than index words")
+    written = _Written(cells, plan.pool)
+    total = 0
+    for ri, (kind, count, p0, p1, dst, a, b, _) in enumerate(plan.records.tolist()):
+        if kind > DOT:
+            raise PlanError("witness plan: record %d: unknown kind %d" % (ri, kind))
+        if count == 0:
+            raise PlanError("witness plan: record %d is empty" % ri)
+        if kind == DOT:
+            w, ns = p0, p1
+            if w == 0 or ns == 0 or count * ns * w > len(plan.pool):
+                raise PlanError("witness plan: record %d: bad dot shape" % ri)
+            d = _span(plan, dst, count * ns, "dst", ri)
+            xa, xb = _span(plan, a, count * ns * w, "a", ri), _span(plan, b, count * ns * w, "b", ri)
+            if ((xa == NONE) != (xb == NONE)).any():
+                raise PlanError("witness plan: record %d (dot): a product with one operand" % ri)
+            srcs = np.concatenate([xa, xb])
+            srcs = srcs[srcs != NONE]
+            d = d[d != NONE]
+        else:
+            d = _span(plan, dst, count, "dst", ri)
+            x = _span(plan, a, count, "a", ri)
+            srcs = np.zeros(0, np.uint32)
+            if kind in (COPY, ADD, SUB, MUL, HINT, RCIDX, INVZ):
+                srcs = x
+            else:
+                lim = {CONST: len(plan.consts), INPUT: plan.n_inputs, PARAM: len(plan.params)}[kind]
+                if (x >= lim).any():
+                    raise PlanError("witness plan: record %d (%s): table index out of range" % (ri, KIND_NAMES[kind]))
+            if kind in (ADD, SUB, MUL):
+                srcs = np.concatenate([srcs, _span(plan, b, count, "b", ri)])
+            if kind == HINT:
+                e = _span(plan, b, count, "b", ri)
+                if p0 < 2 or p1 == 0 or p0 ** p1 >= 1 << 62 or ((e != NONE) & (e >= p1)).any():
+                    raise PlanError("witness plan: record %d: bad decomposition" % ri)
+            if kind == RCIDX and p1 == 0:
+                raise PlanError("witness plan: record %d: zero table column size" % ri)
+        if (d >= cells).any() or (srcs >= cells).any():
+            raise PlanError("witness plan: record %d (%s): cell index out of range" % (ri, KIND_NAMES[kind]))
+        if not written.get(srcs).all():
+            raise PlanError("witness plan: record %d (%s): a cell is read before an earlier record has written it" % (ri, KIND_NAMES[kind]))
+        if written.get(d).any() or len(np.unique(d)) != len(d):
+            raise PlanError("witness plan: record %d (%s): a cell is written twice" % (ri, KIND_NAMES[kind]))
+        written.set(d)
+        total += len(d)
+    if total != plan.n_cells:
+        raise PlanError("witness plan: %d cells written, its header says %d" % (total, plan.n_cells))
+    if (plan.outputs >= cells).any() or not written.get(plan.outputs).all():
+        raise PlanError("witness plan: an output cell is never written")
+
+
+def _signed(v):
+    return v if v < R // 2 else v - R
+
+
+def run_plan_host(plan, x):
+    """interpret the plan with Python integers -> (advice columns as lists of canonical ints, outputs).  Record by record, element by
+    element, what one lane of the device kernels does."""
+    validate(plan)
+    if len(x) != plan.n_inputs:
+        raise ValueError("the plan takes %d inputs, got %d" % (plan.n_inputs, len(x)))
+    n = 1 << plan.k
+    cells = [0] * (plan.n_advice * n)
+    P, params, consts = plan.pool.tolist(), plan.params.tolist(), plan.consts
+    xs = [int(v) for v in x]
+    for ri, (kind, count, p0, p1, dst, a, b, _) in enumerate(plan.records.tolist()):
+        if kind == DOT:
+            w, ns = p0, p1
+            for d in range(count):
+                acc = 0
+                for s in range(ns):
+                    cell = P[dst + s * count + d]
+                    if cell == NONE:
+                        continue
+                    for j in range(w):
+                        ia = P[a + (s * w + j) * count + d]
+                        if ia != NONE:
+                            acc = (acc + cells[ia] * cells[P[b + (s * w + j) * count + d]]) % R
+                    cells[cell] = acc
+            continue
+        lo = p0 - (1 << 32) if p0 >> 31 else p0
+        for i in range(count):
+            ia = P[a + i]
+            if kind == COPY: v = cells[ia]
+            elif kind == CONST: v = consts[ia]
+            elif kind == INPUT: v = xs[ia] % R
+            elif kind == PARAM: v = params[ia] % R
+            elif kind == ADD: v = (cells[ia] + cells[P[b + i]]) % R
+            elif kind == SUB: v = (cells[ia] - cells[P[b + i]]) % R
+            elif kind == MUL: v = cells[ia] * cells[P[b + i]] % R
+            elif kind == INVZ: v = pow(cells[ia], -1, R) if cells[ia] else 0
+            elif kind == RCIDX:
+                s = _signed(cells[ia])
+                if abs(s) >= 1 << 62:                 # what a lane holds in 64 bits; the layout only range-checks signs and digits
+                    raise AssertionError("%s (%s record %d, element %d)" % (RANGE_ERROR, KIND_NAMES[kind], ri, i))
+                v = abs(s - lo) // p1
+            else:
+                s, e = _signed(cells[ia]), P[b + i]
+                if abs(s) >= p0 ** p1:
+                    raise AssertionError("%s (%s record %d, element %d)" % (RANGE_ERROR, KIND_NAMES[kind], ri, i))
+                v = ((s > 0) - (s < 0)) % R if e == NONE else (abs(s) // p0 ** e) % p0
+            cells[P[dst + i]] = v
+    return [cells[c * n:(c + 1) * n] for c in range(plan.n_advice)], [cells[c] for c in plan.outputs.tolist()]

@@ -233,11 +233,41 @@ int ezkl_hip_upload_begin(const void* const* host_cols, void* const* dev_cols, s
 #define EZKL_COLUMN_FP 0        /* 32-byte Montgomery words, halo2curves' in-memory Fr */
 #define EZKL_COLUMN_INT64 1     /* int64_t per cell */
 #define EZKL_COLUMN_INT128 2    /* little-endian two's-complement 128-bit integer per cell (Rust's i128 = ezkl's IntegerRep) */
+/* the "host" pointer is a DEVICE column of 2^k 32-byte Montgomery words (ezkl_hip_malloc; e.g. filled by ezkl_hip_witness_run_dev): it is
+ * copied into the destination column on the device -- no host round trip -- and left unmodified (the blinding rows go into the copy).
+ * Everything queued on the library stream has run before the copy starts; a column written on another stream must be complete. */
+#define EZKL_COLUMN_DEVICE_FP 3
 int ezkl_hip_upload_begin_fmt(const void* const* host_cols, const uint8_t* formats, void* const* dev_cols, size_t batch, size_t n,
                               const void* const* tail_rows, size_t tail_start, size_t tail_count, ezkl_upload_t* out_upload);
 int ezkl_hip_upload_wait(ezkl_upload_t upload, size_t column, void* stream);
 int ezkl_hip_upload_commit(ezkl_upload_t upload, ezkl_bases_t h, size_t commit_first, size_t commit_count, void* out_affine);
 int ezkl_hip_upload_end(ezkl_upload_t upload);
+/* ---- witness synthesis on the device from a recorded plan: replaces the per-cell host pass of GraphCircuit::synthesize
+ *      (/root/reference/src/graph/mod.rs:2010-2200) for the op family whose cell positions do not depend on the input -- the MLP ops of
+ *      /root/reference/src/circuit/ops/layouts.rs: dot :532-610, pairwise :2917-2990, equals_zero :3549-3580, enforce_equality :4959-4981,
+ *      range_check :5024-5105, decompose :6321-6423, leaky_relu at slope 0 :6457-6474, output :6740-6779 ----
+ * A PLAN is the layout recorded once per circuit (ezkl_amd/witness_plan.py; byte layout: csrc/witness_plan.hpp): a list of records, each a
+ * batch of cell writes of one kind (copy, const, input, param, add / sub / mult, decompose hint, range-check index, inverse-or-zero, dot)
+ * with u32 cell indices column * 2^k + row, a table of int64 parameters and a table of constants.
+ * upload: the blob is validated on the HOST first -- version, every cell index < n_advice * 2^k, every table index in range, every cell
+ *   written once and read only after an earlier record wrote it -- and refused with EZKL_ERR_INVALID otherwise (also without a device;
+ *   ezkl_hip_witness_last_error says why); then its tables go to the device, where they are read-only.  n_advice <= 64.
+ * run: zero-fills the n_advice columns (device, 2^k x 32 bytes each, distinct, e.g. from ezkl_hip_malloc), uploads the n_inputs int64
+ *   model inputs (they enter the field as EZKL_COLUMN_INT64 cells do) and replays the plan, ONE launch per record, on `stream` (NULL: the
+ *   library stream); returns after the stream has drained with outputs_host = the circuit's outputs (32-byte Montgomery words) and
+ *   status = {cells that failed, (record << 32 | element) of the first, cells written, launches (fills included)}.  A value that does
+ *   not fit its decomposition (|x| >= base^legs, the layout's "value exceeds the decomposition range") is counted by the kernel -- nothing
+ *   traps, the process goes on -- and the call returns EZKL_ERR_INVALID with ezkl_hip_witness_last_error naming the op, record and
+ *   element; the columns are then not a witness.  Scratch belongs to the plan (column pool): nothing is allocated per run, and a plan
+ *   runs one synthesis at a time.  HIP events around the run: ezkl_hip_last_kernel_ms("witness").
+ * info: out = {k, n_advice, n_inputs, n_outputs, n_records, n_cells, n_ops (layout-op calls recorded), n_params}. */
+typedef struct ezkl_wplan_s* ezkl_wplan_t;
+int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out_plan);
+int ezkl_hip_witness_plan_free(ezkl_wplan_t plan);
+int ezkl_hip_witness_plan_info(ezkl_wplan_t plan, uint32_t out[8]);
+int ezkl_hip_witness_run_dev(ezkl_wplan_t plan, const int64_t* inputs_host, size_t n_inputs, void* const* advice_cols_dev, void* outputs_host,
+                             uint64_t status[4], void* stream);
+const char* ezkl_hip_witness_last_error(void);   /* the calling thread's last refusal (upload) or range failure (run); "" after a success */
 /* A commit batch fed as its columns become final: begin; push (one column / several: fused into groups as the one-call batch does) any
  * number of times; finish returns the points in push order and closes the batch (also after an error).  A push returns once the MSMs
  * are QUEUED: they start behind everything queued on the library stream so far (an event, no host synchronisation), on the MSM slot

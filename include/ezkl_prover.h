@@ -194,11 +194,15 @@ typedef void (*ezkl_rng_fn)(void* user, void* out, size_t n_elems);
 int ezkl_prover_create_proof(ezkl_pk_t pk, ezkl_bases_t g, ezkl_bases_t g_lagrange, const void* const* advice, ezkl_advice_fn advice_fn,
                              void* advice_user, const void* const* instances, const uint32_t* instance_lens, ezkl_rng_fn rng, void* rng_user,
                              uint64_t seed, void* proof_out, size_t cap, size_t* proof_len, double* timings);
-/* The same with a FORMAT per advice column (EZKL_COLUMN_FP / _INT64 / _INT128 of ezkl_hip.h; advice_formats[c] for column c, NULL = all
+/* The same with a FORMAT per advice column (EZKL_COLUMN_FP / _INT64 / _INT128 / _DEVICE_FP of ezkl_hip.h; advice_formats[c] for column c, NULL = all
  * 32-byte Fp): every cell of an ezkl advice column is integer_rep_to_felt of an IntegerRep (/root/reference/src/fieldutils.rs:6-17), and a
  * caller that hands the integers over moves 8 or 16 bytes per cell across PCIe instead of 32 -- the columns are expanded on the device as
  * their copies land.  The proof is byte for byte the one made from the 32-byte columns.  Integer columns need caller-owned buffers: direct
- * `advice` pointers, or a callback of a constraint system set to by-pointer advice. */
+ * `advice` pointers, or a callback of a constraint system set to by-pointer advice.
+ * EZKL_COLUMN_DEVICE_FP: advice[c] is a DEVICE column of 2^k x 32 bytes (ezkl_hip_malloc), e.g. a witness synthesized on the device
+ * (ezkl_hip_witness_run_dev): it is taken without a host round trip and left unmodified -- the blinding rows go into the prover's own
+ * copy, as for host columns.  Host and device columns mix freely in one call; the proof is byte for byte that of the host columns.
+ * Single-context proving only: EZKL_ERR_INVALID on a sharded constraint system. */
 int ezkl_prover_create_proof_fmt(ezkl_pk_t pk, ezkl_bases_t g, ezkl_bases_t g_lagrange, const void* const* advice, const uint8_t* advice_formats,
                                  ezkl_advice_fn advice_fn, void* advice_user, const void* const* instances, const uint32_t* instance_lens, ezkl_rng_fn rng,
                                  void* rng_user, uint64_t seed, void* proof_out, size_t cap, size_t* proof_len, double* timings);
@@ -233,6 +237,9 @@ int ezkl_prover_verify_proof_vk(ezkl_cs_t cs, const void* vk_buf, size_t vk_len,
 int ezkl_prover_g2_mul_generator(const void* scalar, void* out128);
 /* keccak256 of a byte string (exposed so the transcript can be tested against the Python restatement without a GPU) */
 int ezkl_prover_keccak256(const void* data, size_t len, void* out32);
+/* the host-side validation ezkl_hip_witness_plan_upload runs on a witness-plan blob (ezkl_hip.h; csrc/witness_plan.hpp), without a device
+ * and without uploading anything: EZKL_OK, or EZKL_ERR_INVALID with the reason in ezkl_prover_last_error */
+int ezkl_prover_witness_plan_check(const void* blob, size_t len);
 /* last error text of the calling thread ("" if none) */
 const char* ezkl_prover_last_error(void);
 

@@ -1,0 +1,105 @@
+"""Witness synthesis of the bench MLP (tools/bench_circuits.py kind="mlp"): the host path against the device path, per circuit size.
+
+    host_s          circuit.witness(x) + cols_to_mont -- what `execute.prove(synthesis="host")` does before create_proof: the yardstick
+    record_plan_s   witness_plan.record_plan -- a SETUP cost (once per circuit, `execute.setup` writes the plan next to the key)
+    device_ms       one synthesis on the device, HIP events around the run (fills, input upload, one launch per record, output gather):
+                    the first run after the upload apart, then the minimum and median of --repeat runs
+    plan_bytes, records, launches, cells
+
+One process per size, every GPU step under its own time limit:
+
+    timeout -k 10 600 python tools/synth_bench.py --k 14 --tag <tag> && timeout -k 10 900 python tools/synth_bench.py --k 17 --tag <tag>
+
+Each run merges its entry into profiles/<tag>_synth.json.  --skip-host leaves the host pass out (k = 20: over a minute of Python);
+--plan-dir keeps recorded plans between runs (a plan depends only on the circuit)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--k", type=int, required=True)
+    ap.add_argument("--tag", default="synth")
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--base", type=int, default=None, help="decomposition base (default: the bench's 16384)")
+    ap.add_argument("--repeat", type=int, default=10)
+    ap.add_argument("--skip-host", action="store_true")
+    ap.add_argument("--plan-dir", default=None)
+    a = ap.parse_args()
+    import bench_circuits as BC
+    import ezkl_amd
+    from ezkl_amd import backend as B, ezkl_layout as EL, witness_plan as WP
+    ezkl_amd.init()
+    circuit, x = BC.mlp_circuit(a.k, np.random.default_rng(a.seed), base=a.base)
+    out = dict(k=a.k, circuit="MLP %d x (Gemm %dx%d + bias + ReLU), base %d" % (len(circuit.weights), len(circuit.weights[0]), len(circuit.weights[0]), circuit.base),
+               advice_columns=len(circuit.gc.cs.advice))
+    host = None
+    if not a.skip_host:
+        t = time.perf_counter()
+        adv, inst = circuit.witness(x)
+        t1 = time.perf_counter()
+        host = EL.cols_to_mont(adv, B)
+        B.synchronize()
+        t2 = time.perf_counter()
+        out.update(host_witness_s=round(t1 - t, 3), host_cols_to_mont_s=round(t2 - t1, 3), host_s=round(t2 - t, 3))
+        print("k=%d host: circuit.witness %.3f s + cols_to_mont %.3f s" % (a.k, t1 - t, t2 - t1), flush=True)
+    blob, path = None, a.plan_dir and os.path.join(a.plan_dir, "mlp_k%d_s%d_b%d.wplan" % (a.k, a.seed, circuit.base))
+    if path and os.path.exists(path):
+        blob = open(path, "rb").read()
+        if WP.peek(blob)["param_hash"] != WP.params_hash(circuit):
+            blob = None
+    if blob is None:
+        t = time.perf_counter()
+        plan = WP.record_plan(circuit)
+        out["record_plan_s"] = round(time.perf_counter() - t, 3)
+        print("k=%d plan recording (setup, once per circuit): %.3f s" % (a.k, out["record_plan_s"]), flush=True)
+        blob = plan.to_bytes()
+        if path:
+            os.makedirs(a.plan_dir, exist_ok=True)
+            open(path, "wb").write(blob)
+    h = WP.peek(blob)
+    t = time.perf_counter()
+    dev = B.WitnessPlan(blob)
+    out.update(plan_bytes=len(blob), records=h["n_records"], layout_ops=h["n_ops"], cells=h["n_cells"], plan_upload_s=round(time.perf_counter() - t, 3))
+    cols = dev.alloc_columns()
+    _, outs = dev.run(x, columns=cols)
+    out.update(launches=dev.last["launches"], cells_written=dev.last["cells_written"], device_first_ms=round(dev.last["device_ms"], 4))
+    assert dev.last["cells_written"] == h["n_cells"]
+    if host is not None:                             # the run that is timed computes what the host computes
+        n = 1 << a.k
+        assert [outs] == inst
+        for c, r in zip(cols, host):
+            assert c.to_numpy(shape=(n, 4)).tobytes() == np.ascontiguousarray(r).tobytes()
+        out["columns_equal_host"] = True
+    ms, wall = [], []
+    for _ in range(a.repeat):
+        t = time.perf_counter()
+        dev.run(x, columns=cols)
+        wall.append((time.perf_counter() - t) * 1e3)
+        ms.append(dev.last["device_ms"])
+    out.update(device_ms_min=round(min(ms), 4), device_ms_median=round(float(np.median(ms)), 4), device_call_wall_ms_median=round(float(np.median(wall)), 4),
+               repeat=a.repeat)
+    print("k=%d device: %.3f ms min, %.3f ms median of %d (first %.3f ms); %d launches for %d records / %d layout ops; plan %d bytes, %d cells"
+          % (a.k, min(ms), float(np.median(ms)), a.repeat, out["device_first_ms"], out["launches"], out["records"], out["layout_ops"], len(blob), h["n_cells"]), flush=True)
+    for c in cols:
+        c.free()
+    dev.free()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    dst = os.path.join(ROOT, "profiles", "%s_synth.json" % a.tag)
+    doc = json.load(open(dst)) if os.path.exists(dst) else {}
+    doc["k%d" % a.k] = out
+    json.dump(doc, open(dst, "w"), indent=1, sort_keys=True)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
