@@ -857,7 +857,8 @@ def kernel_ms_stats(which, reset=False):
 
 
 class WitnessError(ValueError):
-    """a synthesis on the device met a value outside its decomposition range (the layout's own assertion on the host path)"""
+    """a synthesis on the device met a value outside its decomposition range, or a lookup input outside its table (the layout's own
+    assertions on the host path)"""
 
 
 class WitnessPlan:
@@ -883,7 +884,7 @@ class WitnessPlan:
     def run(self, inputs, columns=None, stream=None):
         """inputs: the model inputs as (signed) integers -> (columns: n_advice DeviceBuffers of 2^k Montgomery words, outputs as ints).
         self.last = dict(cells_written, launches, device_ms).  Raises WitnessError, naming the op, when a value does not fit its
-        decomposition; the process goes on and the plan can run again."""
+        decomposition or its lookup table; the process goes on and the plan can run again."""
         x = np.ascontiguousarray(np.asarray([int(v) for v in inputs], dtype=np.int64))
         if len(x) != self.n_inputs:
             raise ValueError("the plan takes %d inputs, got %d" % (self.n_inputs, len(x)))

@@ -6,19 +6,21 @@
 // zero-filled columns of 2^k Montgomery words.  ezkl_amd/witness_plan.py `run_plan_host` is the executable specification: a lane
 // here does to one element what one iteration of its loops does.
 //
-//  * element-wise records (copy, const, input, param, add / sub / mult, decompose hints, range-check index, inverse-or-zero): one lane
-//    per destination cell; the index arrays are read coalesced, and where they hold contiguous runs (they mostly do: the layout
-//    advances a linear coordinate) so are the 32-byte cells;
+//  * element-wise records (copy, const, input, param, add / sub / mult, decompose hints, range-check index, inverse-or-zero, static
+//    lookup output and its table-column index): one lane per destination cell; the index arrays are read coalesced, and where they
+//    hold contiguous runs (they mostly do: the layout advances a linear coordinate) so are the 32-byte cells;
 //  * dot records (the running sum of w products per row, layouts.rs:532-610, with the duplicated row at the top of a new column as
 //    a step without products): all dots of a record run in parallel, 16 lanes to a dot -- a chunked scan over its rows, see
 //    wit_dot_kernel.  The index arrays are step-major (step s of every dot, then step s + 1): a wave holds 4 dots x 16 row chunks, so
 //    one index read of a wave is 16 runs of 4 consecutive words, one run per chunk.
 //
 // A value that does not fit its decomposition (|x| >= base^legs: the layout's "value exceeds the decomposition range") writes nothing
-// wrong silently: the lane counts itself in status[0] and keeps the SMALLEST (record, element) in status[1] -- vector atomics in plain
-// C++, as the mock prover's kernels in vecops.hip -- and the host call returns EZKL_ERR_INVALID naming the op.  Nothing traps.
+// wrong silently, and neither does a lookup input outside its table (layouts.rs:5143-5222 `nonlinearity`; the layout's "lookup input
+// outside the table range"): the lane counts itself in status[0] and keeps the SMALLEST (record, element) in status[1] -- vector
+// atomics in plain C++, as the mock prover's kernels in vecops.hip -- and the host call returns EZKL_ERR_INVALID naming the op.
+// Nothing traps.
 // The only device memory written is the destination columns, the plan's own scratch (inputs, outputs) and the status words; the plan's
-// index pool, parameters and constants are read-only after upload.
+// index pool, parameters, constants and lookup-table values are read-only after upload.
 #include "common.hpp"
 #include "witness_plan.hpp"
 
@@ -81,9 +83,10 @@ EZ_D void wit_count(uint32_t wrote, unsigned long long* status) {          // on
 
 template <uint32_t KIND>
 __global__ __launch_bounds__(256) void wit_elem_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* __restrict__ a,
-                                                       const uint32_t* __restrict__ b, uint32_t count, uint32_t p0, uint32_t p1,
+                                                       const uint32_t* __restrict__ b, uint32_t count, uint32_t p0, uint32_t p1, uint32_t p2,
                                                        const int64_t* __restrict__ ints, const fe_t* __restrict__ consts, uint32_t rec,
                                                        unsigned long long* status) {
+    // TABLE / TBLIDX: the launcher has resolved the table directory -- ints = the table's values, p0 = lo (int32), p1 = n, p2 = col_size
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < count;
     bool fail = false;
@@ -112,10 +115,17 @@ __global__ __launch_bounds__(256) void wit_elem_kernel(WitCols cols, uint32_t k,
                     for (uint32_t t = 0; t < e; t++) d *= p0;
                     v = Fr::from_u64((mag / d) % p0);
                 }
-            } else {                                                                          // RCIDX: |x - lo| // col_size
+            } else if (KIND == RCIDX) {                                                       // |x - lo| // col_size
                 fail = !fits;                                                                 // |x| >= 2^62: as run_plan_host refuses it
                 const int64_t s = neg ? -(int64_t)mag : (int64_t)mag, diff = s - (int64_t)(int32_t)p0;
                 v = Fr::from_u64((uint64_t)(diff < 0 ? -diff : diff) / p1);
+            } else {                                                                          // TABLE: values[s - lo]; TBLIDX: (s - lo) // col_size
+                fail = !fits;                                                                 // |s| >= 2^62: outside every table
+                if (fits) {
+                    const int64_t s = neg ? -(int64_t)mag : (int64_t)mag, diff = s - (int64_t)(int32_t)p0;
+                    fail = diff < 0 || diff >= (int64_t)p1;                                   // outside [lo, lo + n - 1]: nothing is read
+                    if (!fail) v = KIND == TABLE ? wit_from_i64(ints[diff]) : Fr::from_u64((uint64_t)diff / p2);
+                }
             }
         }
         if (!fail) st_fe(wit_cell(cols, k, dst[i]), v);
@@ -187,6 +197,7 @@ struct DevPlan {
     uint32_t* outputs = nullptr;
     int64_t* params = nullptr;
     fe_t* consts = nullptr;         // Montgomery form
+    int64_t* table_values = nullptr;   // the static lookup tables' values (directory: host.tables)
     // per-run scratch, owned by the plan (from the column pool: nothing is allocated per run)
     int64_t* inputs = nullptr;
     fe_t* outs = nullptr;
@@ -196,14 +207,20 @@ struct DevPlan {
 thread_local std::string t_wit_error;
 
 void plan_release(DevPlan* p) {
-    for (void* q : {(void*)p->pool, (void*)p->outputs, (void*)p->params, (void*)p->consts, (void*)p->inputs, (void*)p->outs, (void*)p->status})
+    for (void* q : {(void*)p->pool, (void*)p->outputs, (void*)p->params, (void*)p->consts, (void*)p->table_values, (void*)p->inputs, (void*)p->outs, (void*)p->status})
         if (q) (void)ezkl_hip_free(q);
     delete p;
 }
 template <uint32_t KIND>
 void launch_elem(hipStream_t st, const WitCols& cols, uint32_t k, const DevPlan* p, const Rec& r, uint32_t ri) {
     const int64_t* ints = KIND == INPUT ? p->inputs : p->params;
-    hipLaunchKernelGGL(wit_elem_kernel<KIND>, dim3(cdiv(r.count, 256)), dim3(256), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, p->pool + r.b, r.count, r.p0, r.p1,
+    uint32_t p0 = r.p0, p1 = r.p1, p2 = 0;
+    if (KIND == TABLE || KIND == TBLIDX) {                            // the directory entry, resolved here: r.p0 < tables.size() was checked on upload
+        const Table& t = p->host.tables[r.p0];
+        ints = p->table_values + t.off;
+        p0 = (uint32_t)t.lo; p1 = t.n; p2 = t.col_size;
+    }
+    hipLaunchKernelGGL(wit_elem_kernel<KIND>, dim3(cdiv(r.count, 256)), dim3(256), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, p->pool + r.b, r.count, p0, p1, p2,
                        ints, (const fe_t*)p->consts, ri, p->status);
 }
 }  // namespace
@@ -239,7 +256,7 @@ int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out
     const Up ups[] = {{(void**)&p->pool, h.pool.data(), h.pool.size() * 4},       {(void**)&p->outputs, h.outputs.data(), h.outputs.size() * 4},
                       {(void**)&p->params, h.params.data(), h.params.size() * 8}, {(void**)&p->consts, consts.data(), consts.size() * 32},
                       {(void**)&p->inputs, nullptr, (size_t)h.n_inputs * 8},      {(void**)&p->outs, nullptr, h.outputs.size() * 32},
-                      {(void**)&p->status, nullptr, 32}};
+                      {(void**)&p->status, nullptr, 32},                          {(void**)&p->table_values, h.table_values.data(), h.table_values.size() * 8}};
     int rc = EZKL_OK;
     for (const Up& u : ups) {
         if ((rc = ezkl_hip_malloc(u.dev, u.bytes ? u.bytes : 1))) break;
@@ -251,6 +268,7 @@ int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out
     std::vector<uint32_t>().swap(p->host.pool);                   // 138 MB at k = 20: the device copy is the one that is read from here on
     std::vector<int64_t>().swap(p->host.params);
     std::vector<uint8_t>().swap(p->host.consts);
+    std::vector<int64_t>().swap(p->host.table_values);            // (the directory stays: the launcher resolves it)
     *out = reinterpret_cast<ezkl_wplan_t>(p);
     return EZKL_OK;
 }
@@ -315,6 +333,8 @@ int ezkl_hip_witness_run_dev(ezkl_wplan_t plan, const int64_t* inputs_host, size
         case HINT: launch_elem<HINT>(st, cols, k, p, r, (uint32_t)ri); break;
         case RCIDX: launch_elem<RCIDX>(st, cols, k, p, r, (uint32_t)ri); break;
         case INVZ: launch_elem<INVZ>(st, cols, k, p, r, (uint32_t)ri); break;
+        case TABLE: launch_elem<TABLE>(st, cols, k, p, r, (uint32_t)ri); break;
+        case TBLIDX: launch_elem<TBLIDX>(st, cols, k, p, r, (uint32_t)ri); break;
         default:
             hipLaunchKernelGGL(wit_dot_kernel, dim3(cdiv((size_t)r.count * DOT_LANES, 64)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, p->pool + r.b, r.count, r.p0, r.p1,
                                p->status);
@@ -338,7 +358,8 @@ int ezkl_hip_witness_run_dev(ezkl_wplan_t plan, const int64_t* inputs_host, size
     if (dev_status[0]) {
         const uint32_t ri = (uint32_t)(status[1] >> 32), el = (uint32_t)status[1];
         const uint32_t kind = ri < h.recs.size() ? h.recs[ri].kind : (uint32_t)N_KINDS;
-        t_wit_error = std::string("witness: value exceeds the decomposition range (") + (kind < N_KINDS ? KIND_NAMES[kind] : "?") + " record " + std::to_string(ri) +
+        const char* what = kind == TABLE || kind == TBLIDX ? "witness: lookup input outside the table range (" : "witness: value exceeds the decomposition range (";
+        t_wit_error = std::string(what) + (kind < N_KINDS ? KIND_NAMES[kind] : "?") + " record " + std::to_string(ri) +
                       ", element " + std::to_string(el) + "; " + std::to_string(dev_status[0]) + " cells in all)";
         return EZKL_ERR_INVALID;
     }

@@ -3,8 +3,12 @@
 // ezkl_prover_witness_plan_check so that the sanitizer build (tools/asan_run.sh) covers it.  witness_plan.validate is its Python mirror.
 //
 // Layout (little-endian): 20 x u32 header -- magic "EZWP", version, k, n_advice, n_records, n_inputs, n_params, n_consts, n_outputs,
-// n_cells, n_words, n_ops, 8 reserved -- and the 32-byte parameter hash; then n_params x int64, n_consts x 32 bytes (canonical Fr),
-// n_records x {kind, count, p0, p1, dst, a, b, 0}, n_outputs x u32 cells, n_words x u32 pool.  Cells are numbered column * 2^k + row.
+// n_cells, n_words, n_ops, n_tables, n_table_values, 6 reserved -- and the 32-byte parameter hash; then n_params x int64, n_consts x
+// 32 bytes (canonical Fr), n_records x {kind, count, p0, p1, dst, a, b, 0}, n_outputs x u32 cells, n_words x u32 pool, n_tables x
+// {lo (int32), n, col_size, offset} and n_table_values x int64: the static lookup tables, f(lo + i) as signed integers (both sections
+// are empty in a plan without lookups: the two header words were reserved zeros).  Cells are numbered column * 2^k + row.
+// A TABLE / TBLIDX record: a = source cell, p0 = table index; with s the signed value of the cell, values[offset + (s - lo)] as a field
+// element / (s - lo) // col_size.  s outside [lo, lo + n - 1] is a run-time failure of the lane, as a value beyond its decomposition is.
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -16,10 +20,15 @@ namespace ezkl {
 namespace wplan {
 
 constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64;
-enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, N_KINDS };
-static const char* const KIND_NAMES[N_KINDS] = {"copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot"};
+enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, N_KINDS };
+static const char* const KIND_NAMES[N_KINDS] = {"copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot",
+                                                "nonlinearity", "nonlinearity_index"};
 struct Rec {
     uint32_t kind, count, p0, p1, dst, a, b, pad;
+};
+struct Table {
+    int32_t lo;
+    uint32_t n, col_size, off;
 };
 struct Plan {
     uint32_t k = 0, n_advice = 0, n_inputs = 0, n_cells = 0, n_ops = 0;
@@ -28,6 +37,8 @@ struct Plan {
     std::vector<uint8_t> consts;       // 32 bytes each, canonical
     std::vector<Rec> recs;
     std::vector<uint32_t> outputs, pool;
+    std::vector<Table> tables;
+    std::vector<int64_t> table_values;
 };
 // BN254 Fr modulus, little-endian bytes (a constant must be canonical)
 static const uint8_t FR_MOD_LE[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
@@ -70,9 +81,9 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
     memcpy(h, p, sizeof h);
     if (h[0] != MAGIC) return fail("bad magic");
     if (h[1] != VERSION) return fail("version " + std::to_string(h[1]) + ", this build reads " + std::to_string(VERSION));
-    const uint32_t k = h[2], n_adv = h[3], n_rec = h[4], n_in = h[5], n_par = h[6], n_con = h[7], n_out = h[8], n_cells = h[9], n_words = h[10];
+    const uint32_t k = h[2], n_adv = h[3], n_rec = h[4], n_in = h[5], n_par = h[6], n_con = h[7], n_out = h[8], n_cells = h[9], n_words = h[10], n_tab = h[12], n_val = h[13];
     if (k < 1 || k > 28 || n_adv == 0 || n_adv > MAX_ADVICE || ((uint64_t)n_adv << k) > ((uint64_t)1 << 32)) return fail("bad geometry");
-    const uint64_t want = (uint64_t)sizeof h + 32 + 8ull * n_par + 32ull * n_con + 32ull * n_rec + 4ull * n_out + 4ull * n_words;
+    const uint64_t want = (uint64_t)sizeof h + 32 + 8ull * n_par + 32ull * n_con + 32ull * n_rec + 4ull * n_out + 4ull * n_words + 16ull * n_tab + 8ull * n_val;
     if (want != len) return fail(std::to_string(len) + " bytes, its header says " + std::to_string(want));
     out.k = k; out.n_advice = n_adv; out.n_inputs = n_in; out.n_cells = n_cells; out.n_ops = h[11];
     p += sizeof h;
@@ -81,12 +92,19 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
     out.consts.resize(32ull * n_con); if (n_con) memcpy(out.consts.data(), p, 32ull * n_con); p += 32ull * n_con;
     out.recs.resize(n_rec);     if (n_rec) memcpy(out.recs.data(), p, 32ull * n_rec);    p += 32ull * n_rec;
     out.outputs.resize(n_out);  if (n_out) memcpy(out.outputs.data(), p, 4ull * n_out);  p += 4ull * n_out;
-    out.pool.resize(n_words);   if (n_words) memcpy(out.pool.data(), p, 4ull * n_words);
+    out.pool.resize(n_words);   if (n_words) memcpy(out.pool.data(), p, 4ull * n_words);  p += 4ull * n_words;
+    out.tables.resize(n_tab);   if (n_tab) memcpy(out.tables.data(), p, 16ull * n_tab);   p += 16ull * n_tab;
+    out.table_values.resize(n_val); if (n_val) memcpy(out.table_values.data(), p, 8ull * n_val);
     for (uint32_t i = 0; i < n_con; i++) {               // canonical: below the modulus, compared from the top byte down
         const uint8_t* c = out.consts.data() + 32ull * i;
         int j = 31;
         while (j >= 0 && c[j] == FR_MOD_LE[j]) j--;
         if (j < 0 || c[j] > FR_MOD_LE[j]) return fail("a constant is not a canonical field element");
+    }
+    for (size_t ti = 0; ti < out.tables.size(); ti++) {
+        const Table& t = out.tables[ti];
+        if (t.n < 1 || t.col_size < 1 || (int64_t)t.lo + t.n - 1 > 0x7fffffffll) return fail("table " + std::to_string(ti) + ": bad lookup table shape");
+        if (t.off > n_val || t.n > n_val - t.off) return fail("table " + std::to_string(ti) + ": runs past the table values");
     }
     const uint64_t cells = (uint64_t)n_adv << k;
     if (n_cells > n_words) return fail("more cells than index words");
@@ -118,6 +136,7 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
             break;
         }
         case RCIDX: a_cells = true; if (r.p1 == 0) return at_rec(ri, r.kind, "zero table column size"); break;
+        case TABLE: case TBLIDX: a_cells = true; if (r.p0 >= n_tab) return at_rec(ri, r.kind, "lookup table index out of range"); break;
         case DOT:
             if (r.p0 == 0 || r.p1 == 0 || (uint64_t)r.count * r.p1 > P.size() || (uint64_t)r.count * r.p1 * r.p0 > P.size()) return at_rec(ri, r.kind, "bad dot shape");
             n_dst = (uint64_t)r.count * r.p1; n_a = n_b = n_dst * r.p0; a_cells = b_cells = true;

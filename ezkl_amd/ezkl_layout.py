@@ -696,6 +696,7 @@ class ConvMnistCircuit(LayoutCircuit):
         self.k, self.w = logrows, num_inner_cols
         self.image, self.kernel, self.oc, self.stride, self.classes = image, kernel, out_channels, stride, classes
         self.slides = (image - kernel) // stride + 1
+        self.n_inputs = image * image
         self.length = out_channels * self.slides * self.slides
         self.base, self.legs, self.denom = decomp_base, decomp_legs, denom
         rng = np.random.default_rng(seed)
@@ -714,13 +715,14 @@ class ConvMnistCircuit(LayoutCircuit):
         act = np.array([self.gc.div(max(int(v), 0)) for v in conv])
         return [int(v) for v in self.fc_w @ act + self.fc_b]
 
-    def synthesize(self, img, witness=True):
-        reg = BaseRegion(self.gc, witness)
-        img = np.asarray(img, np.int64).reshape(self.image, self.image)
+    def layout(self, reg, inputs, param):
+        """the op sequence, stated once: `synthesize` runs it on a BaseRegion with the image's values, witness_plan.record_plan on a
+        recording region with symbols.  inputs: the image, row-major, as Vals; param(v) -> the Val of a circuit parameter (they are
+        asked for in a fixed order: kernels, then per output its conv bias, the linear layer's rows, its biases)"""
         s, K, st = self.slides, self.kernel, self.stride
         # conv: kernel and image are assigned once, side by side; every patch / filter slice below is a copy of those cells
-        ker = reg.assign(reg.inputs[0], [Val(int(v) % R) for v in self.kernels.reshape(-1)])
-        im = reg.assign(reg.inputs[1], [Val(int(v) % R) for v in img.reshape(-1)])
+        ker = reg.assign(reg.inputs[0], [param(v) for v in self.kernels.reshape(-1)])
+        im = reg.assign(reg.inputs[1], inputs)
         reg.increment(max(len(ker), len(im)))
         ker = [ker[o * K * K:(o + 1) * K * K] for o in range(self.oc)]
         vals = []
@@ -729,14 +731,26 @@ class ConvMnistCircuit(LayoutCircuit):
                 for j in range(s):
                     patch = [im[(i * st + a) * self.image + j * st + b] for a in range(K) for b in range(K)]
                     res = reg.dot(patch, ker[o])
-                    res = reg.pairwise([res], [Val(int(self.conv_bias[o]) % R)], EC.ADD)
+                    res = reg.pairwise([res], [param(self.conv_bias[o])], EC.ADD)
                     reg.flush()
                     vals.append(res[0])
         vals = reg.relu(vals, self.base, self.legs)
         vals = reg.nonlinearity(vals, "div_%d" % self.denom)
-        outs = [reg.dot([Val(int(v) % R) for v in row], vals) for row in self.fc_w]
-        outs = reg.pairwise(outs, [Val(int(v) % R) for v in self.fc_b], EC.ADD)
+        outs = [reg.dot([param(v) for v in row], vals) for row in self.fc_w]
+        outs = reg.pairwise(outs, [param(v) for v in self.fc_b], EC.ADD)
         reg.constrain_instance(outs, self.gc.instance)
+        return outs
+
+    def plan_identity(self):
+        """what a witness plan of this circuit depends on besides the layout code and the lookup tables (witness_plan.params_hash)"""
+        shape = [self.k, self.w, self.image, self.kernel, self.oc, self.stride, self.classes, self.base, self.legs, self.denom,
+                 self.gc.advices[0].num_blocks()]
+        return b"".join(np.asarray(a, np.int64).tobytes() for a in (shape, self.kernels, self.conv_bias, self.fc_w, self.fc_b))
+
+    def synthesize(self, img, witness=True):
+        reg = BaseRegion(self.gc, witness)
+        img = np.asarray(img, np.int64).reshape(self.image, self.image)
+        outs = self.layout(reg, [Val(int(v) % R) for v in img.reshape(-1)], lambda v: Val(int(v) % R))
         reg.finish(self.gc.const_cols)
         self.outputs = [v.v for v in outs]
         return reg

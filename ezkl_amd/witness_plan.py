@@ -1,4 +1,4 @@
-"""Witness plans: the layout of an MlpCircuit recorded ONCE, replayed for every proof.
+"""Witness plans: the layout of an MlpCircuit or a ConvMnistCircuit recorded ONCE, replayed for every proof.
 
 Which advice cell holds which value depends only on the circuit (BaseRegion places cells from the linear coordinate, the duplicated rows
 of `dot` from the block geometry; constants, weights and biases are the same for every input), so `record_plan` runs one witness-free
@@ -6,17 +6,24 @@ layout pass over a BaseRegion subclass whose VALUES are symbols: the placement c
 _dup_inputs, the duplicate row at the top of a new column, every layouts.rs op as BaseRegion lays it out), and every `put` records how
 the cell it wrote is produced from earlier cells, a model input, a circuit parameter or a constant.  The cell writes are grouped into
 RECORDS -- one kernel launch each on the device (csrc/witness.hip) -- by data dependence: a write joins the latest record of its kind
-when everything it reads was written by an earlier record, so the 650 dot products of a layer are one record, not 650.
+when everything it reads was written by an earlier record, so the 650 dot products of a layer are one record, not 650.  (A circuit that
+states its op sequence itself -- `layout`, see record_plan -- is grouped by dependence LEVEL: a write joins the EARLIEST record of its kind
+that comes after every record it reads from.  A cell is written once and read only by writes later in program order, so no element
+of an existing record can depend on the cell that joins it.  The conv loop alternates dot and add and copies its patches from early
+cells: under the latest-fit rule every patch copy lands behind the previous dot and forces a new dot record, 1751 records for the conv +
+ReLU part at k = 17; by levels it is 25.  The MLP path keeps the latest-fit rule: its blobs stay what they were.)
 
 The plan is a flat little-endian blob (`WitnessPlan.to_bytes`):
 
     header   20 x u32: magic "EZWP", version, k, n_advice, n_records, n_inputs, n_params, n_consts, n_outputs, n_cells, n_words, n_ops,
-             then the 32-byte parameter hash
+             n_tables, n_table_values, 6 reserved (zero); then the 32-byte parameter hash
     params   n_params  x int64        weights then biases (fixed at record time)
     consts   n_consts  x 32 bytes     canonical field elements
     records  n_records x 8 u32        kind, count, p0, p1, dst, a, b, 0   (dst / a / b: word offsets into the pool)
     outputs  n_outputs x u32          the cells that hold the circuit's outputs
     pool     n_words   x u32          cell indices (column * 2^k + row), table indices, per-element arguments
+    tables   n_tables  x 4 u32        lo (int32), n (entries), col_size, offset into the values      } both sections are empty in a plan
+    values   n_table_values x int64   f(lo + i) of a static lookup table, as a signed integer        } without lookups: the MLP blobs
 
 A record of an element-wise kind has `count` destination cells pool[dst + i], produced from pool[a + i] (and pool[b + i]):
 
@@ -29,6 +36,11 @@ A record of an element-wise kind has `count` destination cells pool[dst + i], pr
     DOT    count dot products of p1 steps of p0 products each, step-major: step s of dot d writes the running sum to pool[dst + s * count + d]
            (0xffffffff: no such step) after adding the products of pool[a + (s * p0 + j) * count + d] and pool[b + ...] (0xffffffff: none --
            the duplicated running sum at the top of a new column is a step without products)
+    TABLE  a = source cell, p0 = table index: with s the signed value of the cell, values[offset + (s - lo)] as a field element (a negative
+           value as integer_rep_to_felt maps it)
+    TBLIDX a = source cell, p0 = table index: (s - lo) // col_size, the table column that holds s
+           both: s < lo, s > lo + n - 1 or |s| >= 2^62 is the lookup-range failure ("lookup input outside the table range"), reported like the
+           decomposition-range failure
 
 COUPLING WITH ezkl_layout.py.  The recorder reuses BaseRegion's value expressions too, by operator overloading on the symbols below, and
 recognises them AS THEY ARE SPELT there.  Whoever rewrites one of these lines of BaseRegion must extend the symbol classes with it (the
@@ -39,10 +51,13 @@ equality tests of tests/test_witness_plan_cpu.py fail loudly -- an assert or a P
     pairwise                  `x + y`, `x - y`, `x * y` on two assigned cells
     dot                       `acc = (acc + sum(x.v * y.v for ...)) % R` with acc and sum() starting from the integer 0
     equals_zero               `pow(v, -1, R) if v else 0`   (the truth value of a cell symbol is True: INVZ covers both branches)
+    nonlinearity              `assert table.range[0] <= signed(v) <= table.range[1]` (recorded as the run-time check), `table.f(signed(v)) % R`,
+                              `(signed(v) - table.range[0]) // table.col_size` -- LookupRecordingRegion only; `table` is its stand-in there
     Val.__init__ and the ops  `... % R` on any symbol is the symbol
 
 Every cell is written at most once and only reads cells of earlier records; `validate` checks that (the C library runs the same check
 on upload).  `run_plan_host` interprets the blob with Python integers: the executable specification of the device kernels."""
+import bisect
 import hashlib
 import struct
 
@@ -54,10 +69,11 @@ from . import ezkl_layout as EL
 R = EL.R
 MAGIC, VERSION = 0x50575A45, 1                  # "EZWP"
 NONE = 0xFFFFFFFF
-COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT = range(11)
-KIND_NAMES = ["copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot"]
+COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX = range(13)
+KIND_NAMES = ["copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot", "nonlinearity", "nonlinearity_index"]
 _HEADER = struct.Struct("<20I32s")
 RANGE_ERROR = "value exceeds the decomposition range"
+LOOKUP_ERROR = "lookup input outside the table range"
 
 
 class PlanError(ValueError):
@@ -88,6 +104,12 @@ class _Cell(_Sym):
     def __mul__(self, o): return _Bin(MUL, self, o)
     def __lt__(self, o): return True if o == R // 2 else _Cmp(self, "<", o)     # `v if v < R // 2 else v - R`: the signed value is the symbol itself
     def __gt__(self, o): return _Cmp(self, ">", o)
+    def __ge__(self, o):                           # `lo <= s <= hi`, the lookup's range assertion: recorded, checked by `put` and at run time
+        self.lo = o
+        return True
+    def __le__(self, o):
+        self.hi = o
+        return True
     def __abs__(self): return _Mag(self)
     def __bool__(self): return True                                             # `pow(v, -1, R) if v else 0` is INVZ either way
     def __pow__(self, e, m=None):
@@ -174,16 +196,21 @@ class _MagDiv(_Sym):
 
 
 class _Shift(_Sym):
-    """signed value - lo, |.| // col_size: the table-column index of a range check"""
+    """signed value - lo, |.| // col_size: the table-column index of a range check; without the |.|: that of a static lookup"""
 
     def __init__(self, a, lo): self.a, self.lo, self.absd, self.col_size = a.idx, lo, False, None
     def __abs__(self):
         self.absd = True
         return self
     def __floordiv__(self, c):
-        assert self.absd
         self.col_size = c
         return self
+
+
+class _Looked(_Sym):
+    """table.f(signed value): the output of a static lookup"""
+
+    def __init__(self, cell, table): self.cell, self.table = cell, table
 
 
 def _ilog(x, base):
@@ -200,13 +227,22 @@ def _ilog(x, base):
 class _Records:
     """cell writes grouped by kind and data dependence"""
 
-    def __init__(self):
+    def __init__(self, earliest=False):
         self.recs = []                             # dict(kind, p0, p1, dst, a, b) / for DOT: dict(kind, p0, dots)
         self.latest = {}                           # (kind, p0, p1) -> record index
+        self.of_key = {} if earliest else None     # earliest fit: (kind, p0, p1) -> its record indices, ascending
         self.rec_of = {}                           # cell -> record that writes it
 
     def _slot(self, key, sources):
         need = 1 + max((self.rec_of[s] for s in sources), default=-1)
+        if self.of_key is not None:                # the earliest record of the kind above every record the write reads from
+            mine = self.of_key.setdefault(key, [])
+            at = bisect.bisect_left(mine, need)
+            if at < len(mine):
+                return mine[at]
+            mine.append(len(self.recs))
+            self.recs.append(dict(kind=key[0], p0=key[1], p1=key[2], dst=[], a=[], b=[], dots=[]))
+            return mine[-1]
         ri = self.latest.get(key)
         if ri is None or ri < need:
             ri = self.latest[key] = len(self.recs)
@@ -244,10 +280,10 @@ class _Records:
 class RecordingRegion(EL.BaseRegion):
     """BaseRegion with symbolic values: every placement decision is the parent's; `put` records how the cell is produced"""
 
-    def __init__(self, gc):
+    def __init__(self, gc, earliest=False):
         super().__init__(gc, witness=False)
         self.n_adv = len(gc.cs.advice)
-        self.out = _Records()
+        self.out = _Records(earliest)
         self.consts, self.const_idx = [], {}
         self.n_ops = 0
         self._dot = None
@@ -266,7 +302,11 @@ class RecordingRegion(EL.BaseRegion):
         placed = super().put(var, linear, val)     # cell_of / cartesian_coord: the parent's placement
         _, col, row = placed.cell
         dst = (col << self.k) + row
-        v, out = val.v, self.out
+        self._emit(val.v, dst)
+        return EL.Val(_Cell(dst), placed.cell)
+
+    def _emit(self, v, dst):
+        out = self.out
         if isinstance(v, int):
             out.emit(CONST, dst, self._const(v))
         elif isinstance(v, _Cell):
@@ -290,7 +330,7 @@ class RecordingRegion(EL.BaseRegion):
             if v.base != base or v.mag.bound != base ** legs:
                 raise PlanError("a digit hint without the layout's range assertion")
             out.emit(HINT, dst, v.mag.a, _ilog(v.div, base), p0=base, p1=legs, reads=(v.mag.a,))
-        elif isinstance(v, _Shift) and v.col_size is not None:
+        elif isinstance(v, _Shift) and v.col_size is not None and v.absd:
             if not -(1 << 31) <= v.lo < 1 << 31 or not 0 < v.col_size < 1 << 32:
                 raise PlanError("range check bounds beyond 32 bits")
             out.emit(RCIDX, dst, v.a, p0=v.lo & NONE, p1=v.col_size, reads=(v.a,))
@@ -302,7 +342,6 @@ class RecordingRegion(EL.BaseRegion):
             self._dot.append((dst, v.pairs))
         else:
             raise PlanError("the witness plan recorder does not cover a %s value" % type(v).__name__)
-        return EL.Val(_Cell(dst), placed.cell)
 
     # ---- the ops: BaseRegion's own, counted; the out-of-scope ones refused by name -------------------------------------------------------
     def _counted(name):
@@ -341,9 +380,92 @@ class RecordingRegion(EL.BaseRegion):
     del _counted, _refused
 
 
+def _table_values(table):
+    """f over the table's range [lo, hi] as int64"""
+    lo, hi = table.range
+    if not (-(1 << 31) <= lo <= hi < 1 << 31) or not 0 < table.col_size < 1 << 32:
+        raise PlanError("lookup table bounds beyond 32 bits")
+    vals = [int(table.f(x)) for x in range(lo, hi + 1)]
+    if any(not -(1 << 63) <= v < 1 << 63 for v in vals):
+        raise PlanError("a lookup table value beyond int64")
+    return np.array(vals, np.int64)
+
+
+class _SymTable:
+    """what BaseRegion.nonlinearity reads of a Table, with `f` answering a symbol"""
+
+    def __init__(self, table, index):
+        self.range, self.col_size, self.index = tuple(table.range), table.col_size, index
+
+    def f(self, x):
+        if not isinstance(x, _Cell):
+            raise PlanError("a lookup on a %s value" % type(x).__name__)
+        return _Looked(x, self)
+
+
+class _SymBase:
+    """the region's BaseConfig with the static tables replaced by their stand-ins (made on first use); everything else is the config's own"""
+
+    def __init__(self, base, region):
+        self._base, self.static_tables = base, _SymTables(base, region)
+
+    def __getattr__(self, name):
+        return getattr(self._base, name)
+
+
+class _SymTables(dict):
+    def __init__(self, base, region): self.base, self.region = base, region
+    def __missing__(self, name):
+        table = self.base.static_tables[name]
+        self[name] = sym = _SymTable(table, len(self.region.tables))
+        self.region.tables.append((table.range[0], table.col_size, _table_values(table)))
+        return sym
+
+
+class LookupRecordingRegion(RecordingRegion):
+    """RecordingRegion + `nonlinearity` (a static lookup: TABLE for f(x), TBLIDX for the table column beside it), with records grouped by
+    dependence level.  tables: [(lo, col_size, values as int64)] in order of first use."""
+
+    def __init__(self, gc):
+        super().__init__(gc, earliest=True)
+        self.tables = []
+        self.base = _SymBase(gc.base, self)
+        self._lookup_src = {}                      # source cell -> (its symbol, table) of the lookups recorded so far
+
+    def nonlinearity(self, vals, name):
+        self.n_ops += 1
+        return EL.BaseRegion.nonlinearity(self, vals, name)
+
+    def _asserted(self, cell, table):
+        if (getattr(cell, "lo", None), getattr(cell, "hi", None)) != table.range:
+            raise PlanError("a lookup without the layout's range assertion")
+
+    def _emit(self, v, dst):
+        if isinstance(v, _Looked):
+            self._asserted(v.cell, v.table)
+            self._lookup_src[v.cell.idx] = (v.cell, v.table)
+            self.out.emit(TABLE, dst, v.cell.idx, p0=v.table.index, reads=(v.cell.idx,))
+        elif isinstance(v, _Shift) and v.col_size is not None and not v.absd:
+            src = self._lookup_src.get(v.a)
+            if src is None or v.lo != src[1].range[0] or v.col_size != src[1].col_size:
+                raise PlanError("a table-column index without its lookup")
+            self._asserted(*src)
+            self.out.emit(TBLIDX, dst, v.a, p0=src[1].index, reads=(v.a,))
+        else:
+            super()._emit(v, dst)
+
+
 def params_hash(circuit):
-    """what a plan depends on besides the layout code: the circuit's shape options and its parameters"""
+    """what a plan depends on besides the layout code: the circuit's shape options and its parameters (for a circuit with `layout`: its
+    `plan_identity()` bytes and its static lookup tables)"""
     h = hashlib.sha256()
+    if type(circuit) is not EL.MlpCircuit:
+        h.update(("layout:%s:" % type(circuit).__name__).encode())
+        h.update(circuit.plan_identity())
+        for name, table in sorted(circuit.gc.base.static_tables.items()):
+            h.update(name.encode() + struct.pack("<3q", table.range[0], table.range[1], table.col_size))
+            h.update(_table_values(table).tobytes())
+        return h.digest()
     h.update(struct.pack("<8q", circuit.k, circuit.w, circuit.base, circuit.legs, int(circuit.relu_last), int(circuit.relu_first), circuit.n_inputs,
                          len(circuit.weights)))
     for W, b in zip(circuit.weights, circuit.biases):
@@ -354,23 +476,31 @@ def params_hash(circuit):
 
 
 def record_plan(circuit):
-    """one witness-free layout pass of an MlpCircuit -> WitnessPlan.  The op sequence is MlpCircuit.synthesize's, with the input vector and
-    the parameters as symbols; every other circuit class is refused by name."""
-    if type(circuit) is not EL.MlpCircuit:
-        raise PlanError("witness plans cover MlpCircuit only, not %s (conv, einsum and the surrogate circuits keep the host path)" % type(circuit).__name__)
+    """one witness-free layout pass -> WitnessPlan, with the input vector and the parameters as symbols.  An MlpCircuit: the op sequence is
+    MlpCircuit.synthesize's, restated here.  A circuit that states its op sequence itself -- `layout(reg, inputs, param) -> outputs`, which its
+    own `synthesize` runs too, with `n_inputs` and `plan_identity()` (ConvMnistCircuit) -- is recorded from that, on a
+    LookupRecordingRegion.  Every other circuit class is refused by name."""
+    mlp = type(circuit) is EL.MlpCircuit
+    if not mlp and not (callable(getattr(circuit, "layout", None)) and callable(getattr(circuit, "plan_identity", None))):
+        raise PlanError("witness plans cover MlpCircuit and circuits that state their `layout`, not %s (einsum, sum / prod and the surrogate "
+                        "circuits keep the host path)" % type(circuit).__name__)
     if any(c.phase != 0 for c in circuit.gc.cs.advice):
         raise PlanError("witness plans do not cover second-phase advice")
-    reg = RecordingRegion(circuit.gc)
+    reg = RecordingRegion(circuit.gc) if mlp else LookupRecordingRegion(circuit.gc)
     if (len(circuit.gc.cs.advice) << circuit.k) > 1 << 32:
         raise PlanError("cells are numbered in 32 bits")
     Val = EL.Val
     params = []
     def param(v):
+        v = int(v)
         if not -(1 << 63) <= v < 1 << 63:
             raise PlanError("a parameter beyond int64")
-        params.append(int(v))
+        params.append(v)
         return Val(_Param(len(params) - 1))
     vals = [Val(_Input(i)) for i in range(circuit.n_inputs)]
+    if not mlp:
+        outs = circuit.layout(reg, vals, param)
+        return WitnessPlan._from_recorder(circuit, reg, params, [v.v.idx for v in outs])
     _, vals = reg.decompose(vals, circuit.base, circuit.legs)
     if circuit.relu_first:
         vals = reg.relu(vals, circuit.base, circuit.legs)
@@ -386,8 +516,11 @@ def record_plan(circuit):
 
 
 class WitnessPlan:
-    def __init__(self, k, n_advice, n_inputs, params, consts, records, outputs, pool, n_cells, n_ops, param_hash):
+    def __init__(self, k, n_advice, n_inputs, params, consts, records, outputs, pool, n_cells, n_ops, param_hash, tables=(), table_values=()):
+        """tables: (lo, n, col_size, offset into table_values) per static lookup table"""
         self.k, self.n_advice, self.n_inputs = k, n_advice, n_inputs
+        self.tables = [tuple(int(v) for v in t) for t in tables]
+        self.table_values = np.ascontiguousarray(table_values, np.int64).reshape(-1)
         self.params = np.ascontiguousarray(params, np.int64)
         self.consts = [int(c) for c in consts]
         self.records = np.ascontiguousarray(records, np.uint32).reshape(-1, 8)
@@ -423,15 +556,23 @@ class WitnessPlan:
                 n = len(rec["dst"])
                 n_cells += n
                 records.append([rec["kind"], n, rec["p0"], rec["p1"], push(rec["dst"]), push(rec["a"]), push(rec["b"]) if rec["b"] else 0, 0])
+        tables, values = [], []
+        for lo, col_size, vals in getattr(reg, "tables", ()):
+            tables.append((lo, len(vals), col_size, sum(len(v) for v in values)))
+            values.append(vals)
         return cls(circuit.k, reg.n_adv, circuit.n_inputs, params, reg.consts, records, outputs,
-                   np.concatenate(pool) if pool else np.zeros(0, np.uint32), n_cells, reg.n_ops, params_hash(circuit))
+                   np.concatenate(pool) if pool else np.zeros(0, np.uint32), n_cells, reg.n_ops, params_hash(circuit),
+                   tables, np.concatenate(values) if values else ())
 
     # ---- the blob ------------------------------------------------------------------------------------------------------------------------
     def to_bytes(self):
         head = _HEADER.pack(MAGIC, VERSION, self.k, self.n_advice, len(self.records), self.n_inputs, len(self.params), len(self.consts),
-                            len(self.outputs), self.n_cells, len(self.pool), self.n_ops, 0, 0, 0, 0, 0, 0, 0, 0, self.param_hash)
+                            len(self.outputs), self.n_cells, len(self.pool), self.n_ops, len(self.tables), len(self.table_values), 0, 0, 0, 0, 0, 0,
+                            self.param_hash)
+        directory = b"".join(struct.pack("<iIII", *t) for t in self.tables)
         return b"".join([head, self.params.astype("<i8").tobytes(), b"".join(c.to_bytes(32, "little") for c in self.consts),
-                         self.records.astype("<u4").tobytes(), self.outputs.astype("<u4").tobytes(), self.pool.astype("<u4").tobytes()])
+                         self.records.astype("<u4").tobytes(), self.outputs.astype("<u4").tobytes(), self.pool.astype("<u4").tobytes(),
+                         directory, self.table_values.astype("<i8").tobytes()])
 
     @classmethod
     def from_bytes(cls, blob):
@@ -443,8 +584,8 @@ class WitnessPlan:
             raise PlanError("witness plan: bad magic")
         if f[1] != VERSION:
             raise PlanError("witness plan: version %d, this build reads %d" % (f[1], VERSION))
-        _, _, k, n_adv, n_rec, n_in, n_par, n_con, n_out, n_cells, n_words, n_ops = f[:12]
-        sizes = [8 * n_par, 32 * n_con, 32 * n_rec, 4 * n_out, 4 * n_words]
+        _, _, k, n_adv, n_rec, n_in, n_par, n_con, n_out, n_cells, n_words, n_ops, n_tab, n_val = f[:14]
+        sizes = [8 * n_par, 32 * n_con, 32 * n_rec, 4 * n_out, 4 * n_words, 16 * n_tab, 8 * n_val]
         if len(blob) != _HEADER.size + sum(sizes):
             raise PlanError("witness plan: %d bytes, its header says %d" % (len(blob), _HEADER.size + sum(sizes)))
         o = [_HEADER.size]
@@ -455,7 +596,9 @@ class WitnessPlan:
         records = np.frombuffer(blob, "<u4", 8 * n_rec, o[2])
         outputs = np.frombuffer(blob, "<u4", n_out, o[3])
         pool = np.frombuffer(blob, "<u4", n_words, o[4])
-        return cls(k, n_adv, n_in, params, consts, records, outputs, pool, n_cells, n_ops, f[20])
+        tables = [struct.unpack_from("<iIII", blob, o[5] + 16 * i) for i in range(n_tab)]
+        values = np.frombuffer(blob[o[6]:o[7]], "<i8")
+        return cls(k, n_adv, n_in, params, consts, records, outputs, pool, n_cells, n_ops, f[20], tables, values)
 
     def __eq__(self, other):
         return isinstance(other, WitnessPlan) and self.to_bytes() == other.to_bytes()
@@ -476,8 +619,8 @@ def peek(blob):
     f = _HEADER.unpack_from(blob)
     if f[0] != MAGIC or f[1] != VERSION:
         raise PlanError("witness plan: bad magic or version")
-    names = ["k", "n_advice", "n_records", "n_inputs", "n_params", "n_consts", "n_outputs", "n_cells", "n_words", "n_ops"]
-    return dict(zip(names, f[2:12]), param_hash=f[20])
+    names = ["k", "n_advice", "n_records", "n_inputs", "n_params", "n_consts", "n_outputs", "n_cells", "n_words", "n_ops", "n_tables", "n_table_values"]
+    return dict(zip(names, f[2:14]), param_hash=f[20])
 
 
 def _span(plan, off, n, what, ri):
@@ -510,7 +653,8 @@ class _Written:
 
 def validate(plan):
     """the check ezkl_hip_witness_plan_upload makes before anything reaches the device, mirrored line by line: geometry, every cell index below
-    n_advice * 2^k, every table index in range, every cell written at most once and read only after an EARLIER record wrote it"""
+    n_advice * 2^k, every table index in range, every lookup table inside the table values, every cell written at most once and read only
+    after an EARLIER record wrote it"""
     if not 1 <= plan.k <= 28 or not 0 < plan.n_advice <= 64 or (plan.n_advice << plan.k) > 1 << 32:
         raise PlanError("witness plan: bad geometry")
     cells = plan.n_advice << plan.k
@@ -518,10 +662,15 @@ def validate(plan):
         raise PlanError("witness plan: a constant is not a canonical field element")
     if plan.n_cells > len(plan.pool):
         raise PlanError("witness plan: more cells than index words")
+    for ti, (lo, n, col_size, off) in enumerate(plan.tables):
+        if n < 1 or col_size < 1 or lo + n - 1 > (1 << 31) - 1:
+            raise PlanError("witness plan: table %d: bad lookup table shape" % ti)
+        if off > len(plan.table_values) or n > len(plan.table_values) - off:
+            raise PlanError("witness plan: table %d: runs past the table values" % ti)
     written = _Written(cells, plan.pool)
     total = 0
     for ri, (kind, count, p0, p1, dst, a, b, _) in enumerate(plan.records.tolist()):
-        if kind > DOT:
+        if kind > TBLIDX:
             raise PlanError("witness plan: record %d: unknown kind %d" % (ri, kind))
         if count == 0:
             raise PlanError("witness plan: record %d is empty" % ri)
@@ -540,7 +689,7 @@ def validate(plan):
             d = _span(plan, dst, count, "dst", ri)
             x = _span(plan, a, count, "a", ri)
             srcs = np.zeros(0, np.uint32)
-            if kind in (COPY, ADD, SUB, MUL, HINT, RCIDX, INVZ):
+            if kind in (COPY, ADD, SUB, MUL, HINT, RCIDX, INVZ, TABLE, TBLIDX):
                 srcs = x
             else:
                 lim = {CONST: len(plan.consts), INPUT: plan.n_inputs, PARAM: len(plan.params)}[kind]
@@ -554,6 +703,8 @@ def validate(plan):
                     raise PlanError("witness plan: record %d: bad decomposition" % ri)
             if kind == RCIDX and p1 == 0:
                 raise PlanError("witness plan: record %d: zero table column size" % ri)
+            if kind in (TABLE, TBLIDX) and p0 >= len(plan.tables):
+                raise PlanError("witness plan: record %d (%s): lookup table index out of range" % (ri, KIND_NAMES[kind]))
         if (d >= cells).any() or (srcs >= cells).any():
             raise PlanError("witness plan: record %d (%s): cell index out of range" % (ri, KIND_NAMES[kind]))
         if not written.get(srcs).all():
@@ -608,6 +759,12 @@ def run_plan_host(plan, x):
             elif kind == SUB: v = (cells[ia] - cells[P[b + i]]) % R
             elif kind == MUL: v = cells[ia] * cells[P[b + i]] % R
             elif kind == INVZ: v = pow(cells[ia], -1, R) if cells[ia] else 0
+            elif kind in (TABLE, TBLIDX):
+                t_lo, t_n, t_col, t_off = plan.tables[p0]
+                s = _signed(cells[ia])
+                if s < t_lo or s > t_lo + t_n - 1 or abs(s) >= 1 << 62:
+                    raise AssertionError("%s (%s record %d, element %d)" % (LOOKUP_ERROR, KIND_NAMES[kind], ri, i))
+                v = int(plan.table_values[t_off + s - t_lo]) % R if kind == TABLE else (s - t_lo) // t_col
             elif kind == RCIDX:
                 s = _signed(cells[ia])
                 if abs(s) >= 1 << 62:                 # what a lane holds in 64 bits; the layout only range-checks signs and digits

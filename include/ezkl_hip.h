@@ -245,12 +245,18 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
 /* ---- witness synthesis on the device from a recorded plan: replaces the per-cell host pass of GraphCircuit::synthesize
  *      (/root/reference/src/graph/mod.rs:2010-2200) for the op family whose cell positions do not depend on the input -- the MLP ops of
  *      /root/reference/src/circuit/ops/layouts.rs: dot :532-610, pairwise :2917-2990, equals_zero :3549-3580, enforce_equality :4959-4981,
- *      range_check :5024-5105, decompose :6321-6423, leaky_relu at slope 0 :6457-6474, output :6740-6779 ----
+ *      range_check :5024-5105, decompose :6321-6423, leaky_relu at slope 0 :6457-6474, output :6740-6779 -- and static lookups
+ *      (nonlinearity :5143-5222), which with those ops is the conv2d_mnist example's layout ----
  * A PLAN is the layout recorded once per circuit (ezkl_amd/witness_plan.py; byte layout: csrc/witness_plan.hpp): a list of records, each a
- * batch of cell writes of one kind (copy, const, input, param, add / sub / mult, decompose hint, range-check index, inverse-or-zero, dot)
- * with u32 cell indices column * 2^k + row, a table of int64 parameters and a table of constants.
- * upload: the blob is validated on the HOST first -- version, every cell index < n_advice * 2^k, every table index in range, every cell
- *   written once and read only after an earlier record wrote it -- and refused with EZKL_ERR_INVALID otherwise (also without a device;
+ * batch of cell writes of one kind (copy, const, input, param, add / sub / mult, decompose hint, range-check index, inverse-or-zero, dot,
+ * static-lookup output, static-lookup table-column index) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
+ * of constants and -- header words 12 / 13 (n_tables, n_table_values; zero, as reserved words were, in a plan without lookups), after the
+ * pool -- a directory of {lo (int32), n, col_size, offset} per static lookup table and the tables' values f(lo + i) as int64.  The version
+ * word stays 1.  A lookup record names its source cells and a table: with s the signed value of the cell, the output kind writes
+ * values[offset + (s - lo)] as a field element (negative: r - |v|), the index kind (s - lo) // col_size.
+ * upload: the blob is validated on the HOST first -- version, every cell index < n_advice * 2^k, every table index in range, every lookup
+ *   table inside the values with n >= 1, col_size >= 1 and lo + n - 1 <= 2^31 - 1, every cell written once and read only after an earlier
+ *   record wrote it -- and refused with EZKL_ERR_INVALID otherwise (also without a device;
  *   ezkl_hip_witness_last_error says why); then its tables go to the device, where they are read-only.  n_advice <= 64.
  * run: zero-fills the n_advice columns (device, 2^k x 32 bytes each, distinct, e.g. from ezkl_hip_malloc), uploads the n_inputs int64
  *   model inputs (they enter the field as EZKL_COLUMN_INT64 cells do) and replays the plan, ONE launch per record, on `stream` (NULL: the
@@ -258,7 +264,8 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *   status = {cells that failed, (record << 32 | element) of the first, cells written, launches (fills included)}.  A value that does
  *   not fit its decomposition (|x| >= base^legs, the layout's "value exceeds the decomposition range") is counted by the kernel -- nothing
  *   traps, the process goes on -- and the call returns EZKL_ERR_INVALID with ezkl_hip_witness_last_error naming the op, record and
- *   element; the columns are then not a witness.  Scratch belongs to the plan (column pool): nothing is allocated per run, and a plan
+ *   element; the columns are then not a witness.  A lookup input outside its table (s < lo, s > lo + n - 1, |s| >= 2^62: the layout's
+ *   "lookup input outside the table range") is reported the same way, with that message.  Scratch belongs to the plan (column pool): nothing is allocated per run, and a plan
  *   runs one synthesis at a time.  HIP events around the run: ezkl_hip_last_kernel_ms("witness").
  * info: out = {k, n_advice, n_inputs, n_outputs, n_records, n_cells, n_ops (layout-op calls recorded), n_params}. */
 typedef struct ezkl_wplan_s* ezkl_wplan_t;

@@ -1,4 +1,5 @@
-"""Witness synthesis of the bench MLP (tools/bench_circuits.py kind="mlp"): the host path against the device path, per circuit size.
+"""Witness synthesis of the bench MLP (tools/bench_circuits.py kind="mlp"; --circuit conv: its kind="conv", ConvMnistCircuit(logrows=k) on
+the bench's image distribution): the host path against the device path, per circuit size.
 
     host_s          circuit.witness(x) + cols_to_mont -- what `execute.prove(synthesis="host")` does before create_proof: the yardstick
     record_plan_s   witness_plan.record_plan -- a SETUP cost (once per circuit, `execute.setup` writes the plan next to the key)
@@ -10,7 +11,7 @@ One process per size, every GPU step under its own time limit:
 
     timeout -k 10 600 python tools/synth_bench.py --k 14 --tag <tag> && timeout -k 10 900 python tools/synth_bench.py --k 17 --tag <tag>
 
-Each run merges its entry into profiles/<tag>_synth.json.  --skip-host leaves the host pass out (k = 20: over a minute of Python);
+Each run merges its entry into profiles/<tag>_synth.json (key "k<k>" for the MLP, "conv_k<k>" for --circuit conv).  --skip-host leaves the host pass out (k = 20: over a minute of Python);
 --plan-dir keeps recorded plans between runs (a plan depends only on the circuit)."""
 import argparse
 import json
@@ -28,6 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--k", type=int, required=True)
+    ap.add_argument("--circuit", choices=("mlp", "conv"), default="mlp")
     ap.add_argument("--tag", default="synth")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--base", type=int, default=None, help="decomposition base (default: the bench's 16384)")
@@ -39,20 +41,27 @@ def main():
     import ezkl_amd
     from ezkl_amd import backend as B, ezkl_layout as EL, witness_plan as WP
     ezkl_amd.init()
-    circuit, x = BC.mlp_circuit(a.k, np.random.default_rng(a.seed), base=a.base)
-    out = dict(k=a.k, circuit="MLP %d x (Gemm %dx%d + bias + ReLU), base %d" % (len(circuit.weights), len(circuit.weights[0]), len(circuit.weights[0]), circuit.base),
-               advice_columns=len(circuit.gc.cs.advice))
+    if a.circuit == "conv":
+        circuit = EL.ConvMnistCircuit(logrows=a.k, seed=a.seed)
+        img = np.random.default_rng(a.seed).integers(0, 16, (28, 28))        # MNIST pixels / 16, as tools/bench_circuits.py kind="conv" draws them
+        x, witness_in = [int(v) for v in img.reshape(-1)], img
+        what = "examples/conv2d_mnist: Conv 1->4 5x5 stride 2 on 28x28 + ReLU + Div{32} lookup + Linear 576->10"
+    else:
+        circuit, x = BC.mlp_circuit(a.k, np.random.default_rng(a.seed), base=a.base)
+        witness_in = x
+        what = "MLP %d x (Gemm %dx%d + bias + ReLU), base %d" % (len(circuit.weights), len(circuit.weights[0]), len(circuit.weights[0]), circuit.base)
+    out = dict(k=a.k, circuit=what, advice_columns=len(circuit.gc.cs.advice))
     host = None
     if not a.skip_host:
         t = time.perf_counter()
-        adv, inst = circuit.witness(x)
+        adv, inst = circuit.witness(witness_in)
         t1 = time.perf_counter()
         host = EL.cols_to_mont(adv, B)
         B.synchronize()
         t2 = time.perf_counter()
         out.update(host_witness_s=round(t1 - t, 3), host_cols_to_mont_s=round(t2 - t1, 3), host_s=round(t2 - t, 3))
         print("k=%d host: circuit.witness %.3f s + cols_to_mont %.3f s" % (a.k, t1 - t, t2 - t1), flush=True)
-    blob, path = None, a.plan_dir and os.path.join(a.plan_dir, "mlp_k%d_s%d_b%d.wplan" % (a.k, a.seed, circuit.base))
+    blob, path = None, a.plan_dir and os.path.join(a.plan_dir, "%s_k%d_s%d_b%d.wplan" % (a.circuit, a.k, a.seed, circuit.base))
     if path and os.path.exists(path):
         blob = open(path, "rb").read()
         if WP.peek(blob)["param_hash"] != WP.params_hash(circuit):
@@ -96,7 +105,7 @@ def main():
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     dst = os.path.join(ROOT, "profiles", "%s_synth.json" % a.tag)
     doc = json.load(open(dst)) if os.path.exists(dst) else {}
-    doc["k%d" % a.k] = out
+    doc[("k%d" if a.circuit == "mlp" else "conv_k%d") % a.k] = out
     json.dump(doc, open(dst, "w"), indent=1, sort_keys=True)
     print(json.dumps(out))
 
