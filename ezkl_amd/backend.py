@@ -863,7 +863,9 @@ class WitnessError(ValueError):
 
 class WitnessPlan:
     """a witness plan (witness_plan.WitnessPlan bytes) resident on the device: `run` synthesizes the advice columns of one proof
-    into DeviceBuffers (ezkl_hip_witness_run_dev) -- the columns native.create_proof takes as they are"""
+    into DeviceBuffers (ezkl_hip_witness_run_dev) -- the columns native.create_proof takes as they are.  A plan with phases
+    (n_phases > 1: second-phase advice) runs phase by phase, `run(phase=..., challenges=...)`, between the prover's commit stages:
+    `advice_fn` is the callable native.create_proof takes for that."""
 
     def __init__(self, blob):
         blob = bytes(blob)
@@ -876,18 +878,28 @@ class WitnessPlan:
         info = (C.c_uint32 * 8)()
         _l.check(L.ezkl_hip_witness_plan_info(self.h, info), "ezkl_hip_witness_plan_info")
         self.k, self.n_advice, self.n_inputs, self.n_outputs, self.n_records, self.n_cells, self.n_ops, self.n_params = [int(v) for v in info]
+        ph, col_phase = (C.c_uint32 * 2)(), (C.c_uint8 * self.n_advice)()
+        _l.check(L.ezkl_hip_witness_plan_phases(self.h, ph, col_phase), "ezkl_hip_witness_plan_phases")
+        self.n_phases, self.n_challenges = int(ph[0]), int(ph[1])
+        self.column_phase = [int(v) for v in col_phase]   # the phase each advice column belongs to
         self.last = None                             # counters of the last run
 
     def alloc_columns(self):
         return [DeviceBuffer(32 << self.k) for _ in range(self.n_advice)]
 
-    def run(self, inputs, columns=None, stream=None):
+    def run(self, inputs, columns=None, stream=None, phase=None, challenges=()):
         """inputs: the model inputs as (signed) integers -> (columns: n_advice DeviceBuffers of 2^k Montgomery words, outputs as ints).
         self.last = dict(cells_written, launches, device_ms).  Raises WitnessError, naming the op, when a value does not fit its
-        decomposition or its lookup table; the process goes on and the plan can run again."""
-        x = np.ascontiguousarray(np.asarray([int(v) for v in inputs], dtype=np.int64))
-        if len(x) != self.n_inputs:
-            raise ValueError("the plan takes %d inputs, got %d" % (self.n_inputs, len(x)))
+        decomposition or its lookup table, or an einsum operand its exact product; the process goes on and the plan can run again.
+        phase = p: that phase alone (ezkl_hip_witness_run_phase_dev) with the challenges squeezed so far as canonical ints -- it fills
+        the columns of its phase and leaves the others as they are; the inputs go with phase 0 (later phases ignore them), the outputs
+        come with the last phase ([] before).  phase = None is the one-call run of a plan without phases."""
+        if phase is not None and phase > 0:
+            x = np.zeros(0, np.int64)
+        else:
+            x = np.ascontiguousarray(np.asarray([int(v) for v in inputs], dtype=np.int64))
+            if len(x) != self.n_inputs:
+                raise ValueError("the plan takes %d inputs, got %d" % (self.n_inputs, len(x)))
         cols = columns if columns is not None else self.alloc_columns()
         if len(cols) != self.n_advice or any(c.nbytes < (32 << self.k) for c in cols):
             raise ValueError("the plan writes %d columns of %d bytes" % (self.n_advice, 32 << self.k))
@@ -895,16 +907,38 @@ class WitnessPlan:
         outs = np.zeros((max(1, self.n_outputs), 4), np.uint64)
         status = (C.c_uint64 * 4)()
         L = _l.load()
-        rc = L.ezkl_hip_witness_run_dev(self.h, _p(x), C.c_size_t(len(x)), ptrs, _p(outs), status, _stream_ptr(stream))
+        if phase is None:
+            rc = L.ezkl_hip_witness_run_dev(self.h, _p(x), C.c_size_t(len(x)), ptrs, _p(outs), status, _stream_ptr(stream))
+        else:
+            ch = b"".join((int(c) % (1 << 256)).to_bytes(32, "little") for c in challenges)      # canonical, as they are: the library refuses c >= r
+            rc = L.ezkl_hip_witness_run_phase_dev(self.h, C.c_uint32(phase), _p(x), C.c_size_t(len(x)), ch, C.c_size_t(len(ch) // 32), ptrs, _p(outs), status,
+                                                  _stream_ptr(stream))
         self.last = dict(failed=int(status[0]), first=(int(status[1]) >> 32, int(status[1]) & 0xffffffff), cells_written=int(status[2]), launches=int(status[3]))
         if rc == -3 and status[0]:
             if columns is None:
                 for c in cols:
                     c.free()
             raise WitnessError(L.ezkl_hip_witness_last_error().decode())
+        if rc == -3:
+            if columns is None:
+                for c in cols:
+                    c.free()
+            raise ValueError(L.ezkl_hip_witness_last_error().decode() or "ezkl_hip_witness_run_dev: invalid argument")
         _l.check(rc, "ezkl_hip_witness_run_dev")
         self.last["device_ms"] = last_kernel_ms("witness")
-        return cols, [_from_mont_int(outs[i]) for i in range(self.n_outputs)]
+        done = phase is None or phase == self.n_phases - 1
+        return cols, [_from_mont_int(outs[i]) for i in range(self.n_outputs)] if done else []
+
+    def advice_fn(self, inputs, columns):
+        """the per-phase witness callback of native.create_proof(..., device_columns=range(n_advice)): (phase, challenges) -> {column:
+        DeviceBuffer} of the phase just run, synthesized into `columns` (alloc_columns()).  self.phase_ms collects the device time of
+        each phase."""
+        self.phase_ms = {}
+        def fn(phase, challenges):
+            self.run(inputs, columns=columns, phase=int(phase), challenges=list(challenges))
+            self.phase_ms[int(phase)] = self.last["device_ms"]
+            return {c: columns[c] for c in range(self.n_advice) if self.column_phase[c] == phase}
+        return fn
 
     def free(self):
         if self.h:

@@ -14,6 +14,13 @@
 //    wit_dot_kernel.  The index arrays are step-major (step s of every dot, then step s + 1): a wave holds 4 dots x 16 row chunks, so
 //    one index read of a wave is 16 runs of 4 consecutive words, one run per chunk.
 //
+//  * the einsum family (second-phase advice: a plan with PHASES, one run per phase -- ezkl_hip_witness_run_phase_dev -- between the
+//    prover's commit stages).  matmul records: the exact integer product the prover witnesses, an LDS-tiled matmul over the gathered
+//    int64 inputs, see wit_matmul_kernel.  rlc records (RLCConfig::assign_rlc, /root/reference/src/circuit/ops/chip/einsum/mod.rs:785-866,
+//    at block width 1: out[t] = out[t-1] * c + c * v[t]): the chunked scan of the dot records with an affine map in the combine step,
+//    see wit_rlc_kernel.  The contraction "j,j->" is a dot record with w = 1; everything else is a copy.  An operand of a matmul
+//    outside |v| < 2^31 is reported as the range failures below are ("einsum operand outside the exact-product range").
+//
 // A value that does not fit its decomposition (|x| >= base^legs: the layout's "value exceeds the decomposition range") writes nothing
 // wrong silently, and neither does a lookup input outside its table (layouts.rs:5143-5222 `nonlinearity`; the layout's "lookup input
 // outside the table range"): the lane counts itself in status[0] and keeps the SMALLEST (record, element) in status[1] -- vector
@@ -184,6 +191,113 @@ __global__ __launch_bounds__(64) void wit_dot_kernel(WitCols cols, uint32_t k, c
     wit_count(wrote, status);
 }
 
+// sign and magnitude (< 2^127, two words) -> integer_rep_to_felt -> Montgomery form
+EZ_D fe_t wit_from_mag128(bool neg, uint64_t lo, uint64_t hi) {
+    fe_t v = Fr::zero();
+    v.v[0] = (uint32_t)lo; v.v[1] = (uint32_t)(lo >> 32); v.v[2] = (uint32_t)hi; v.v[3] = (uint32_t)(hi >> 32);
+    if (neg && (lo | hi)) {
+        uint32_t br = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) v.v[i] = subb32(FrP::MOD[i], v.v[i], br);
+    }
+    return Fr::to_mont(v);
+}
+
+// dst[i * n + j] = sum_t in[a[i * kd + t]] * in[b[t * n + j]] over the integers: MM_TILE x MM_TILE outputs per block, one per lane.  Per
+// k-step of MM_TILE every lane loads ONE operand of A and ONE of B through the index arrays into LDS -- checked there, once, for
+// |v| < 2^31, so the tiles hold int32 and a product is an exact int64 below 2^62 in magnitude -- and adds MM_TILE products into a
+// two-word accumulator (kd * 2^62 < 2^127).  Positions past m, n or kd load zeros.  A block that met a bad operand writes nothing:
+// every one of its outputs would read it or a neighbour's; the lane that loaded it reports (record, element) with element = the
+// operand's place in a, or m * kd + its place in b.
+constexpr uint32_t MM_TILE = 16;
+__global__ __launch_bounds__(MM_TILE * MM_TILE) void wit_matmul_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* __restrict__ a,
+                                                                     const uint32_t* __restrict__ b, uint32_t m, uint32_t kd, uint32_t n,
+                                                                     const int64_t* __restrict__ in, uint32_t rec, unsigned long long* status) {
+    __shared__ int32_t As[MM_TILE][MM_TILE + 1], Bs[MM_TILE][MM_TILE + 1];
+    const uint32_t tiles_n = (n + MM_TILE - 1) / MM_TILE;
+    const uint32_t tx = threadIdx.x % MM_TILE, ty = threadIdx.x / MM_TILE;
+    const uint32_t i = (blockIdx.x / tiles_n) * MM_TILE + ty, j = (blockIdx.x % tiles_n) * MM_TILE + tx;
+    uint64_t lo = 0;
+    int64_t hi = 0;
+    bool bad = false;
+    uint32_t bad_elem = 0xFFFFFFFFu;
+    for (uint32_t t0 = 0; t0 < kd; t0 += MM_TILE) {
+        int64_t va = 0, vb = 0;
+        if (i < m && t0 + tx < kd) {                         // A[i][t0 + tx]
+            const uint32_t e = i * kd + t0 + tx;
+            va = in[a[e]];
+            if (va >= ((int64_t)1 << 31) || va <= -((int64_t)1 << 31)) { bad = true; bad_elem = bad_elem < e ? bad_elem : e; va = 0; }
+        }
+        if (t0 + ty < kd && j < n) {                         // B[t0 + ty][j]
+            const uint32_t e = (t0 + ty) * n + j;
+            vb = in[b[e]];
+            if (vb >= ((int64_t)1 << 31) || vb <= -((int64_t)1 << 31)) { bad = true; bad_elem = bad_elem < m * kd + e ? bad_elem : m * kd + e; vb = 0; }
+        }
+        As[ty][tx] = (int32_t)va;
+        Bs[ty][tx] = (int32_t)vb;
+        __syncthreads();
+#pragma unroll
+        for (uint32_t t = 0; t < MM_TILE; t++) {
+            const int64_t p = (int64_t)As[ty][t] * (int64_t)Bs[t][tx];
+            lo += (uint64_t)p;
+            hi += (p >> 63) + (lo < (uint64_t)p ? 1 : 0);
+        }
+        __syncthreads();
+    }
+    const bool block_bad = __syncthreads_or(bad ? 1 : 0) != 0;
+    const bool live = i < m && j < n && !block_bad;
+    if (live) {
+        const bool neg = hi < 0;
+        uint64_t mlo = lo, mhi = (uint64_t)hi;
+        if (neg) {
+            mlo = ~lo + 1;
+            mhi = ~(uint64_t)hi + (mlo == 0 ? 1 : 0);
+        }
+        st_fe(wit_cell(cols, k, dst[i * n + j]), wit_from_mag128(neg, mlo, mhi));
+    }
+    wit_report(bad, rec, bad_elem, status);
+    wit_count(live ? 1u : 0u, status);
+}
+
+// RLC_LANES consecutive lanes share one scan out[t] = c * (out[t-1] + v[t]) (= out[t-1] * c + c * v[t]: field arithmetic is exact), out[-1] = 0;
+// step t of scan d reads cell a[t * n_scans + d] and writes cell dst[t * n_scans + d].  The chunked scan of wit_dot_kernel with an
+// affine map in the combine step.  Pass 1: a lane folds its chunk from zero (S) and builds P = c^len as it goes: the chunk maps a
+// carried-in x to P * x + S.  The shuffle scan over the group composes the maps -- (P1, S1) then (P2, S2) is (P1 * P2, S1 * P2 + S2) --
+// so S of the lane before is the running value at the start of a lane's chunk.  Pass 2: the lane walks its chunk again from the
+// carried-in value and writes every row: the bits of the row-by-row walk.
+constexpr uint32_t RLC_LANES = DOT_LANES;
+__global__ __launch_bounds__(64) void wit_rlc_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* __restrict__ a, uint32_t n_scans,
+                                                     uint32_t n_steps, fe_t c, unsigned long long* status) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t g = (uint32_t)(t % RLC_LANES), chunk = (n_steps + RLC_LANES - 1) / RLC_LANES;
+    const bool live = t / RLC_LANES < n_scans;                   // the same for every lane of a group
+    const uint32_t d = live ? (uint32_t)(t / RLC_LANES) : 0;
+    const uint32_t s0 = g * chunk < n_steps ? g * chunk : n_steps, s1 = s0 + chunk < n_steps ? s0 + chunk : n_steps;
+    fe_t S = Fr::zero(), P = Fr::one();
+    if (live)
+        for (uint32_t s = s0; s < s1; s++) {
+            S = Fr::mul(c, Fr::add(S, ld_fe(wit_cell(cols, k, a[(size_t)s * n_scans + d]))));
+            P = Fr::mul(P, c);
+        }
+    for (uint32_t off = 1; off < RLC_LANES; off <<= 1) {           // inclusive scan of the chunk maps over the group: the earlier map first
+        const fe_t Po = wit_shfl_up(P, off), So = wit_shfl_up(S, off);
+        if (g >= off) {
+            S = Fr::add(Fr::mul(So, P), S);
+            P = Fr::mul(Po, P);
+        }
+    }
+    fe_t acc = wit_shfl_up(S, 1);                                 // exclusive: the running value before this lane's first row
+    if (g == 0) acc = Fr::zero();
+    uint32_t wrote = 0;
+    if (live)
+        for (uint32_t s = s0; s < s1; s++) {
+            acc = Fr::mul(c, Fr::add(acc, ld_fe(wit_cell(cols, k, a[(size_t)s * n_scans + d]))));
+            st_fe(wit_cell(cols, k, dst[(size_t)s * n_scans + d]), acc);
+            wrote++;
+        }
+    wit_count(wrote, status);
+}
+
 __global__ __launch_bounds__(64) void wit_gather_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ cells, uint32_t n, fe_t* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) st_fe(out + i, ld_fe(wit_cell(cols, k, cells[i])));
@@ -203,6 +317,9 @@ struct DevPlan {
     fe_t* outs = nullptr;
     unsigned long long* status = nullptr;
     Ctx* ctx = nullptr;
+    // a plan with phases: the last phase that ran to its end since the last phase 0, and the columns it ran on
+    int done_phase = -1;
+    void* done_cols[MAX_ADVICE] = {nullptr};
 };
 thread_local std::string t_wit_error;
 
@@ -291,12 +408,27 @@ int ezkl_hip_witness_plan_info(ezkl_wplan_t plan, uint32_t out[8]) {
     return EZKL_OK;
 }
 
-int ezkl_hip_witness_run_dev(ezkl_wplan_t plan, const int64_t* inputs_host, size_t n_inputs, void* const* advice_cols_dev, void* outputs_host,
-                             uint64_t status[4], void* stream) {
-    if (!plan || !advice_cols_dev || !status || (n_inputs && !inputs_host)) return EZKL_ERR_INVALID;
+int ezkl_hip_witness_plan_phases(ezkl_wplan_t plan, uint32_t out[2], uint8_t* column_phase) {
+    if (!plan || !out) return EZKL_ERR_INVALID;
+    const Plan& h = reinterpret_cast<DevPlan*>(plan)->host;
+    out[0] = h.n_phases; out[1] = h.n_challenges;
+    if (column_phase) memcpy(column_phase, h.col_phase, h.n_advice);
+    return EZKL_OK;
+}
+
+int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int64_t* inputs_host, size_t n_inputs, const void* challenges, size_t n_challenges,
+                                   void* const* advice_cols_dev, void* outputs_host, uint64_t status[4], void* stream) {
+    if (!plan || !advice_cols_dev || !status) return EZKL_ERR_INVALID;
+    memset(status, 0, 4 * sizeof(uint64_t));
+    t_wit_error.clear();
     DevPlan* p = reinterpret_cast<DevPlan*>(plan);
     const Plan& h = p->host;
-    if (n_inputs != h.n_inputs || (!h.outputs.empty() && !outputs_host)) return EZKL_ERR_INVALID;
+    const bool first = phase == 0, last = phase + 1 == h.n_phases;
+    auto refuse = [&](const char* why) { t_wit_error = std::string("witness: ") + why; return EZKL_ERR_INVALID; };
+    if (phase >= h.n_phases) return refuse("no such phase");
+    if (first && (n_inputs != h.n_inputs || (n_inputs && !inputs_host))) return refuse("the inputs go with phase 0, all of them");
+    if (last && !h.outputs.empty() && !outputs_host) return EZKL_ERR_INVALID;
+    if (n_challenges && !challenges) return EZKL_ERR_INVALID;
     WitCols cols;
     for (uint32_t j = 0; j < MAX_ADVICE; j++) cols.p[j] = nullptr;
     for (uint32_t j = 0; j < h.n_advice; j++) {
@@ -305,7 +437,23 @@ int ezkl_hip_witness_run_dev(ezkl_wplan_t plan, const int64_t* inputs_host, size
             if (advice_cols_dev[i] == advice_cols_dev[j]) return EZKL_ERR_INVALID;
         cols.p[j] = static_cast<fe_t*>(advice_cols_dev[j]);
     }
-    memset(status, 0, 4 * sizeof(uint64_t));
+    // the challenges: canonical -> Montgomery here, handed to the kernels by value
+    std::vector<fe_t> chal(n_challenges);
+    for (size_t i = 0; i < n_challenges; i++) {
+        const uint8_t* c = static_cast<const uint8_t*>(challenges) + 32 * i;
+        if (!wplan::canonical(c)) return refuse("a challenge is not a canonical field element");
+        fe_t v;
+        memcpy(v.v, c, 32);
+        chal[i] = Fr::to_mont(v);
+    }
+    for (const Rec& r : h.recs)
+        if (r.phase == phase && r.kind == RLC && r.p0 >= n_challenges) return refuse("the phase reads a challenge that was not passed");
+    if (first) p->done_phase = -1;
+    else {                                                     // the cells of the earlier phases must be where this one reads them
+        bool same = p->done_phase >= (int)phase - 1;
+        for (uint32_t j = 0; same && j < h.n_advice; j++) same = p->done_cols[j] == advice_cols_dev[j];
+        if (!same) return refuse(("phase " + std::to_string(phase) + " before phase " + std::to_string(phase - 1) + " on these columns").c_str());
+    }
     EZ_CTX(c);
     if (c != p->ctx) return EZKL_ERR_INVALID;
     hipStream_t st = pick_stream(c, stream);
@@ -316,12 +464,17 @@ int ezkl_hip_witness_run_dev(ezkl_wplan_t plan, const int64_t* inputs_host, size
     int rc = ev_pair(c, "witness", &e0, &e1);
     if (rc) return rc;
     EZ_HIP(hipEventRecord(e0, st));
-    for (uint32_t j = 0; j < h.n_advice; j++, launches++) EZ_HIP(hipMemsetAsync(cols.p[j], 0, n * sizeof(fe_t), st));
+    for (uint32_t j = 0; j < h.n_advice; j++)                  // the columns of this phase only: the earlier phases' cells stay
+        if (h.col_phase[j] == phase) {
+            EZ_HIP(hipMemsetAsync(cols.p[j], 0, n * sizeof(fe_t), st));
+            launches++;
+        }
     EZ_HIP(hipMemsetAsync(p->status, 0, 32, st));
     launches++;
-    if (n_inputs) EZ_HIP(hipMemcpyAsync(p->inputs, inputs_host, n_inputs * 8, hipMemcpyHostToDevice, st));
-    for (size_t ri = 0; ri < h.recs.size(); ri++, launches++) {
+    if (first && n_inputs) EZ_HIP(hipMemcpyAsync(p->inputs, inputs_host, n_inputs * 8, hipMemcpyHostToDevice, st));
+    for (size_t ri = 0; ri < h.recs.size(); ri++) {
         const Rec& r = h.recs[ri];
+        if (r.phase != phase) continue;
         switch (r.kind) {
         case COPY: launch_elem<COPY>(st, cols, k, p, r, (uint32_t)ri); break;
         case CONST: launch_elem<CONST>(st, cols, k, p, r, (uint32_t)ri); break;
@@ -335,20 +488,32 @@ int ezkl_hip_witness_run_dev(ezkl_wplan_t plan, const int64_t* inputs_host, size
         case INVZ: launch_elem<INVZ>(st, cols, k, p, r, (uint32_t)ri); break;
         case TABLE: launch_elem<TABLE>(st, cols, k, p, r, (uint32_t)ri); break;
         case TBLIDX: launch_elem<TBLIDX>(st, cols, k, p, r, (uint32_t)ri); break;
+        case MATMUL: {
+            const uint32_t m = r.count / r.p1;
+            hipLaunchKernelGGL(wit_matmul_kernel, dim3(cdiv(m, MM_TILE) * cdiv(r.p1, MM_TILE)), dim3(MM_TILE * MM_TILE), 0, st, cols, k, p->pool + r.dst, p->pool + r.a,
+                               p->pool + r.b, m, r.p0, r.p1, (const int64_t*)p->inputs, (uint32_t)ri, p->status);
+            break;
+        }
+        case RLC:
+            hipLaunchKernelGGL(wit_rlc_kernel, dim3(cdiv((size_t)r.count * RLC_LANES, 64)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, r.count, r.p1, chal[r.p0],
+                               p->status);
+            break;
         default:
             hipLaunchKernelGGL(wit_dot_kernel, dim3(cdiv((size_t)r.count * DOT_LANES, 64)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, p->pool + r.b, r.count, r.p0, r.p1,
                                p->status);
         }
         EZ_HIP(hipGetLastError());
+        launches++;
     }
-    if (!h.outputs.empty()) {
+    const bool gather = last && !h.outputs.empty();
+    if (gather) {
         hipLaunchKernelGGL(wit_gather_kernel, dim3(cdiv(h.outputs.size(), 64)), dim3(64), 0, st, cols, k, p->outputs, (uint32_t)h.outputs.size(), p->outs);
         EZ_HIP(hipGetLastError());
         launches++;
     }
     EZ_HIP(hipEventRecord(e1, st));
     unsigned long long dev_status[4] = {0, 0, 0, 0};
-    if (!h.outputs.empty()) EZ_HIP(hipMemcpyAsync(outputs_host, p->outs, h.outputs.size() * 32, hipMemcpyDeviceToHost, st));
+    if (gather) EZ_HIP(hipMemcpyAsync(outputs_host, p->outs, h.outputs.size() * 32, hipMemcpyDeviceToHost, st));
     EZ_HIP(hipMemcpyAsync(dev_status, p->status, 32, hipMemcpyDeviceToHost, st));
     EZ_HIP(hipStreamSynchronize(st));
     status[0] = dev_status[0];
@@ -358,13 +523,30 @@ int ezkl_hip_witness_run_dev(ezkl_wplan_t plan, const int64_t* inputs_host, size
     if (dev_status[0]) {
         const uint32_t ri = (uint32_t)(status[1] >> 32), el = (uint32_t)status[1];
         const uint32_t kind = ri < h.recs.size() ? h.recs[ri].kind : (uint32_t)N_KINDS;
-        const char* what = kind == TABLE || kind == TBLIDX ? "witness: lookup input outside the table range (" : "witness: value exceeds the decomposition range (";
+        const char* what = kind == TABLE || kind == TBLIDX ? "witness: lookup input outside the table range ("
+                           : kind == MATMUL               ? "witness: einsum operand outside the exact-product range ("
+                                                          : "witness: value exceeds the decomposition range (";
         t_wit_error = std::string(what) + (kind < N_KINDS ? KIND_NAMES[kind] : "?") + " record " + std::to_string(ri) +
-                      ", element " + std::to_string(el) + "; " + std::to_string(dev_status[0]) + " cells in all)";
+                      ", element " + std::to_string(el) + "; " + std::to_string(dev_status[0]) + (kind == MATMUL ? " operand reads in all)" : " cells in all)");
         return EZKL_ERR_INVALID;
     }
+    p->done_phase = (int)phase;
+    if (first) memcpy(p->done_cols, advice_cols_dev, h.n_advice * sizeof(void*));
     t_wit_error.clear();
     return EZKL_OK;
+}
+
+int ezkl_hip_witness_run_dev(ezkl_wplan_t plan, const int64_t* inputs_host, size_t n_inputs, void* const* advice_cols_dev, void* outputs_host,
+                             uint64_t status[4], void* stream) {
+    if (!plan || !advice_cols_dev || !status || (n_inputs && !inputs_host)) return EZKL_ERR_INVALID;
+    const Plan& h = reinterpret_cast<DevPlan*>(plan)->host;
+    if (h.n_phases > 1) {
+        memset(status, 0, 4 * sizeof(uint64_t));
+        t_wit_error = "witness: a plan with " + std::to_string(h.n_phases) + " phases runs phase by phase: ezkl_hip_witness_run_phase_dev";
+        return EZKL_ERR_INVALID;
+    }
+    if (n_inputs != h.n_inputs || (!h.outputs.empty() && !outputs_host)) return EZKL_ERR_INVALID;
+    return ezkl_hip_witness_run_phase_dev(plan, 0, inputs_host, n_inputs, nullptr, 0, advice_cols_dev, outputs_host, status, stream);
 }
 
 }  // extern "C"

@@ -3,12 +3,23 @@
 // ezkl_prover_witness_plan_check so that the sanitizer build (tools/asan_run.sh) covers it.  witness_plan.validate is its Python mirror.
 //
 // Layout (little-endian): 20 x u32 header -- magic "EZWP", version, k, n_advice, n_records, n_inputs, n_params, n_consts, n_outputs,
-// n_cells, n_words, n_ops, n_tables, n_table_values, 6 reserved -- and the 32-byte parameter hash; then n_params x int64, n_consts x
-// 32 bytes (canonical Fr), n_records x {kind, count, p0, p1, dst, a, b, 0}, n_outputs x u32 cells, n_words x u32 pool, n_tables x
+// n_cells, n_words, n_ops, n_tables, n_table_values, n_challenges, n_phases (0 reads as 1), 4 reserved -- and the 32-byte parameter hash;
+// then n_params x int64, n_consts x
+// 32 bytes (canonical Fr), n_records x {kind, count, p0, p1, dst, a, b, phase}, n_outputs x u32 cells, n_words x u32 pool, n_tables x
 // {lo (int32), n, col_size, offset} and n_table_values x int64: the static lookup tables, f(lo + i) as signed integers (both sections
 // are empty in a plan without lookups: the two header words were reserved zeros).  Cells are numbered column * 2^k + row.
 // A TABLE / TBLIDX record: a = source cell, p0 = table index; with s the signed value of the cell, values[offset + (s - lo)] as a field
 // element / (s - lo) // col_size.  s outside [lo, lo + n - 1] is a run-time failure of the lane, as a value beyond its decomposition is.
+// PHASES (second-phase advice: the Freivalds einsum).  Header words 14 / 15 and the eighth word of a record were reserved zeros, so every
+// one-phase blob keeps its bytes.  A record is replayed by the run of its phase; phases are non-decreasing along the list and below
+// n_phases; a column belongs to the phase of the records that write it (two phases: refused; no record: phase 0); INPUT and MATMUL records
+// belong to phase 0, with which the inputs are uploaded.
+// A MATMUL record: count = m * n, p0 = kd, p1 = n; dst = m * n cells row-major, a = m * kd and b = kd * n INPUT indices;
+// dst[i * n + j] = sum_t in[a[i * kd + t]] * in[b[t * n + j]] over the integers, then integer_rep_to_felt.  Every operand must satisfy
+// |v| < 2^31 (kd * 2^62 < 2^127: two 64-bit words hold the sum); one outside is a run-time failure of the lane, element = its place in a, or
+// m * kd + its place in b.
+// An RLC record: count scans of p1 steps with challenge p0 (< n_challenges), step-major and dense (no 0xffffffff entries): out[0] = c * v[0],
+// out[t] = out[t - 1] * c + c * v[t], v[t] = cell a[t * count + d], out[t] -> cell dst[t * count + d].
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -19,19 +30,20 @@
 namespace ezkl {
 namespace wplan {
 
-constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64;
-enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, N_KINDS };
+constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64, MAX_PHASES = 3, MAX_CHALLENGES = 64;
+enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, N_KINDS };
 static const char* const KIND_NAMES[N_KINDS] = {"copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot",
-                                                "nonlinearity", "nonlinearity_index"};
+                                                "nonlinearity", "nonlinearity_index", "matmul", "rlc"};
 struct Rec {
-    uint32_t kind, count, p0, p1, dst, a, b, pad;
+    uint32_t kind, count, p0, p1, dst, a, b, phase;
 };
 struct Table {
     int32_t lo;
     uint32_t n, col_size, off;
 };
 struct Plan {
-    uint32_t k = 0, n_advice = 0, n_inputs = 0, n_cells = 0, n_ops = 0;
+    uint32_t k = 0, n_advice = 0, n_inputs = 0, n_cells = 0, n_ops = 0, n_challenges = 0, n_phases = 1;
+    uint8_t col_phase[MAX_ADVICE] = {0};       // the phase each column belongs to (a column no record writes: 0)
     uint8_t param_hash[32] = {0};
     std::vector<int64_t> params;
     std::vector<uint8_t> consts;       // 32 bytes each, canonical
@@ -40,7 +52,7 @@ struct Plan {
     std::vector<Table> tables;
     std::vector<int64_t> table_values;
 };
-// BN254 Fr modulus, little-endian bytes (a constant must be canonical)
+// BN254 Fr modulus, little-endian bytes (a constant, and a challenge, must be canonical)
 static const uint8_t FR_MOD_LE[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
                                       0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
 
@@ -69,9 +81,15 @@ public:
     void set(uint32_t cell) { const uint64_t i = at(cell); w[i >> 6] |= (uint64_t)1 << (i & 63); }
 };
 
+inline bool canonical(const uint8_t* c) {                 // below the modulus, compared from the top byte down
+    int j = 31;
+    while (j >= 0 && c[j] == FR_MOD_LE[j]) j--;
+    return j >= 0 && c[j] < FR_MOD_LE[j];
+}
+
 // parse + validate; false with `why` set when the blob is refused.  Everything the kernels index with is checked here: every cell
 // index < n_advice * 2^k, every table index in range, every pool span inside the pool, each cell written at most once and read only
-// after an EARLIER record has written it.
+// after an EARLIER record has written it; the phases are non-decreasing and every column is written in one phase only.
 inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
     auto fail = [&](const std::string& s) { why = "witness plan: " + s; return false; };
     auto at_rec = [&](size_t ri, uint32_t kind, const char* s) { return fail("record " + std::to_string(ri) + " (" + (kind < N_KINDS ? KIND_NAMES[kind] : "?") + "): " + s); };
@@ -83,9 +101,11 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
     if (h[1] != VERSION) return fail("version " + std::to_string(h[1]) + ", this build reads " + std::to_string(VERSION));
     const uint32_t k = h[2], n_adv = h[3], n_rec = h[4], n_in = h[5], n_par = h[6], n_con = h[7], n_out = h[8], n_cells = h[9], n_words = h[10], n_tab = h[12], n_val = h[13];
     if (k < 1 || k > 28 || n_adv == 0 || n_adv > MAX_ADVICE || ((uint64_t)n_adv << k) > ((uint64_t)1 << 32)) return fail("bad geometry");
+    const uint32_t n_chal = h[14], n_phases = h[15] ? h[15] : 1;
+    if (n_phases > MAX_PHASES || n_chal > MAX_CHALLENGES) return fail("bad phase or challenge count");
     const uint64_t want = (uint64_t)sizeof h + 32 + 8ull * n_par + 32ull * n_con + 32ull * n_rec + 4ull * n_out + 4ull * n_words + 16ull * n_tab + 8ull * n_val;
     if (want != len) return fail(std::to_string(len) + " bytes, its header says " + std::to_string(want));
-    out.k = k; out.n_advice = n_adv; out.n_inputs = n_in; out.n_cells = n_cells; out.n_ops = h[11];
+    out.k = k; out.n_advice = n_adv; out.n_inputs = n_in; out.n_cells = n_cells; out.n_ops = h[11]; out.n_challenges = n_chal; out.n_phases = n_phases;
     p += sizeof h;
     memcpy(out.param_hash, p, 32); p += 32;
     out.params.resize(n_par);   if (n_par) memcpy(out.params.data(), p, 8ull * n_par);   p += 8ull * n_par;
@@ -95,12 +115,8 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
     out.pool.resize(n_words);   if (n_words) memcpy(out.pool.data(), p, 4ull * n_words);  p += 4ull * n_words;
     out.tables.resize(n_tab);   if (n_tab) memcpy(out.tables.data(), p, 16ull * n_tab);   p += 16ull * n_tab;
     out.table_values.resize(n_val); if (n_val) memcpy(out.table_values.data(), p, 8ull * n_val);
-    for (uint32_t i = 0; i < n_con; i++) {               // canonical: below the modulus, compared from the top byte down
-        const uint8_t* c = out.consts.data() + 32ull * i;
-        int j = 31;
-        while (j >= 0 && c[j] == FR_MOD_LE[j]) j--;
-        if (j < 0 || c[j] > FR_MOD_LE[j]) return fail("a constant is not a canonical field element");
-    }
+    for (uint32_t i = 0; i < n_con; i++)
+        if (!canonical(out.consts.data() + 32ull * i)) return fail("a constant is not a canonical field element");
     for (size_t ti = 0; ti < out.tables.size(); ti++) {
         const Table& t = out.tables[ti];
         if (t.n < 1 || t.col_size < 1 || (int64_t)t.lo + t.n - 1 > 0x7fffffffll) return fail("table " + std::to_string(ti) + ": bad lookup table shape");
@@ -112,10 +128,17 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
     uint64_t total = 0;
     const std::vector<uint32_t>& P = out.pool;
     auto span_ok = [&](uint32_t off, uint64_t n) { return off <= P.size() && n <= P.size() - off; };
+    int col_phase[MAX_ADVICE];
+    for (uint32_t c = 0; c < MAX_ADVICE; c++) col_phase[c] = -1;
+    uint32_t last_phase = 0;
     for (size_t ri = 0; ri < out.recs.size(); ri++) {
         const Rec& r = out.recs[ri];
         if (r.kind >= N_KINDS) return at_rec(ri, r.kind, "unknown kind");
         if (r.count == 0) return at_rec(ri, r.kind, "empty");
+        if (r.phase >= n_phases) return at_rec(ri, r.kind, "phase out of range");
+        if (r.phase < last_phase) return at_rec(ri, r.kind, "phases decrease");
+        last_phase = r.phase;
+        if ((r.kind == INPUT || r.kind == MATMUL) && r.phase != 0) return at_rec(ri, r.kind, "input and matmul records belong to phase 0");
         uint64_t n_dst = r.count, n_a = r.count, n_b = 0;
         bool a_cells = false, b_cells = false;
         uint32_t a_lim = 0;
@@ -137,6 +160,17 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
         }
         case RCIDX: a_cells = true; if (r.p1 == 0) return at_rec(ri, r.kind, "zero table column size"); break;
         case TABLE: case TBLIDX: a_cells = true; if (r.p0 >= n_tab) return at_rec(ri, r.kind, "lookup table index out of range"); break;
+        case MATMUL: {                                   // p0 = kd, p1 = n, count = m * n: a = m * kd, b = kd * n input indices
+            if (r.p0 == 0 || r.p1 == 0 || r.count % r.p1 != 0) return at_rec(ri, r.kind, "bad matmul shape");
+            n_a = (uint64_t)(r.count / r.p1) * r.p0; n_b = (uint64_t)r.p0 * r.p1; a_lim = n_in;
+            if (!span_ok(r.dst, n_dst) || !span_ok(r.a, n_a) || !span_ok(r.b, n_b)) return at_rec(ri, r.kind, "bad matmul shape");
+            break;
+        }
+        case RLC:                                        // p0 = challenge, p1 = steps, count = scans
+            if (r.p0 >= n_chal) return at_rec(ri, r.kind, "challenge index out of range");
+            if (r.p1 == 0 || (uint64_t)r.count * r.p1 > P.size()) return at_rec(ri, r.kind, "bad rlc shape");
+            n_dst = n_a = (uint64_t)r.count * r.p1; a_cells = true;
+            break;
         case DOT:
             if (r.p0 == 0 || r.p1 == 0 || (uint64_t)r.count * r.p1 > P.size() || (uint64_t)r.count * r.p1 * r.p0 > P.size()) return at_rec(ri, r.kind, "bad dot shape");
             n_dst = (uint64_t)r.count * r.p1; n_a = n_b = n_dst * r.p0; a_cells = b_cells = true;
@@ -165,6 +199,10 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
                 if (P[r.a + i] != NONE) return at_rec(ri, r.kind, "a product with one operand");
                 continue;
             }
+            if (r.kind == MATMUL) {
+                if (x >= a_lim) return at_rec(ri, r.kind, "table index out of range");
+                continue;
+            }
             if (b_cells) {
                 if (x >= cells) return at_rec(ri, r.kind, "cell index out of range");
                 if (!written.get(x)) return at_rec(ri, r.kind, "a cell is read before an earlier record has written it");
@@ -183,10 +221,18 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
             written.set(x);
             total++;
         }
+        for (uint64_t i = 0; i < n_dst; i++) {
+            const uint32_t x = P[r.dst + i];
+            if (sparse && x == NONE) continue;
+            int& cp = col_phase[x >> k];
+            if (cp >= 0 && cp != (int)r.phase) return at_rec(ri, r.kind, "a column is written in two phases");
+            cp = (int)r.phase;
+        }
     }
     if (total != n_cells) return fail(std::to_string(total) + " cells written, its header says " + std::to_string(n_cells));
     for (uint32_t c : out.outputs)
         if (c >= cells || !written.get(c)) return fail("an output cell is never written");
+    for (uint32_t c = 0; c < n_adv; c++) out.col_phase[c] = col_phase[c] < 0 ? 0 : (uint8_t)col_phase[c];
     return true;
 }
 

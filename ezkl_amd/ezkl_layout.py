@@ -44,6 +44,11 @@ class Region:
             store[col.index] = [0] * self.n
         return store[col.index]
 
+    def put_cell(self, col, row, v):
+        """the value of one cell; answers what later ops read of it (the value itself: a recording region answers the cell's symbol)"""
+        self.column(col)[row] = v
+        return v
+
     def enable(self, selector, row):
         assert row < self.usable
         a = self.activations[selector.index]
@@ -96,6 +101,12 @@ class EinsumMatmulCircuit:
         cs.chunk_lookups()
         assert all(v.num_blocks() == 1 for v in self.einsums.inputs + self.einsums.outputs), "column overflow (duplication) is not laid out here"
         assert num_inner_cols == 1, "one inner column, as in the reference bench"
+        self.standalone = True                             # the columns are this circuit's own: a witness plan can be recorded
+
+    @property
+    def n_inputs(self):
+        """the entries of A, then of B, row-major: the input vector of a witness plan"""
+        return 2 * self.len * self.len
 
     @classmethod
     def over(cls, gc, length):
@@ -113,39 +124,29 @@ class EinsumMatmulCircuit:
         """region.assign_einsum: vals (list of Val) go to rows coord.. of `var`; a previously assigned value is copy-constrained,
         a constant is copy-constrained to the fixed column.  `live`: fill values (False in the phase that does not own the column)."""
         col = var.inner[0][0]
-        store = region.column(col) if live else None
         out = []
         for t, val in enumerate(vals):
             row = region.coord + t
             assert row < region.usable, "einsum column overflow"
-            if live:
-                store[row] = val.v
+            v = region.put_cell(col, row, val.v) if live else val.v
             cell = ("adv", col.index, row)
             if val.const:
                 region.copy(cell, region.constant(self.const_cols, val.v))
             elif val.cell is not None:
                 region.copy(cell, val.cell)
-            out.append(Val(val.v, cell))
+            out.append(Val(v, cell))
         return out
 
-    def _rlc(self, region, gate_idx, vals, challenge, rlc_len, phase, cur_phase):
-        """RLCConfig::assign_rlc with block width 1: out[0] = c*v0 (init), out[t] = out[t-1]*c + c*v[t] (acc)"""
+    def _rlc(self, region, gate_idx, vals, rlc, rlc_len, phase, cur_phase):
+        """RLCConfig::assign_rlc with block width 1: out[0] = c*v0 (init), out[t] = out[t-1]*c + c*v[t] (acc), c = challenge `gate_idx`;
+        the running values are `rlc`'s (see `sequence`)"""
         g = self.einsums.rlc[gate_idx]
         in_var = [self.einsums.inputs[0], self.einsums.inputs[2]][phase]
         out_var = self.einsums.outputs[1]
         results = []
-        c = challenge
         for s in range(0, len(vals), rlc_len):
-            chunk = vals[s:s + rlc_len]
-            self._assign(region, in_var, chunk, live=(phase == 0 or cur_phase == 1))
-            run, acc = [], 0
-            if cur_phase == 1:
-                for v in chunk:
-                    acc = (acc * c + c * v.v) % R
-                    run.append(Val(acc))
-            else:
-                run = [Val(0)] * len(chunk)
-            outs = self._assign(region, out_var, run, live=(cur_phase == 1))
+            chunk = self._assign(region, in_var, vals[s:s + rlc_len], live=(phase == 0 or cur_phase == 1))
+            outs = self._assign(region, out_var, rlc(chunk, gate_idx), live=(cur_phase == 1))
             init_s, acc_s = g["selectors"][(phase, 0)]
             region.enable(init_s, region.coord)
             for t in range(1, len(chunk)):
@@ -154,37 +155,28 @@ class EinsumMatmulCircuit:
             region.coord += len(chunk)
         return results
 
-    def synthesize(self, a, b, challenges=None, region=None):
-        """a, b: len x len integer arrays (values mod r).  challenges=None: first phase (first-phase columns, selectors, copies);
-        else the two challenges: everything.  Returns the Region (a fresh one unless the caller hands its own)."""
+    def sequence(self, region, A, B, O, rlc, dot, cur):
+        """assign_einsum for "ij,jk->ik", stated once: `synthesize` runs it on integers, the witness-plan recorder (witness_plan.py) on
+        symbols.  A, B: len x len Vals; O: the len * len Vals of the product, row-major; rlc(vals, challenge index) and dot(xs, ys)
+        answer the running values of a random linear combination / of a dot product over assigned Vals; cur: the phase being
+        synthesized (0: first-phase columns, selectors, copies; 1: everything)."""
         L = self.len
-        cur = 0 if challenges is None else 1
-        c0, c1 = (0, 0) if challenges is None else challenges
-        if region is None:
-            region = Region(self.cs, self.k)
         E = self.einsums
-        A = [[Val(int(a[i][j])) for j in range(L)] for i in range(L)]
-        B = [[Val(int(b[j][kk])) for kk in range(L)] for j in range(L)]
-        O = [Val(int(v)) for v in self.matmul(a, b).reshape(-1)]
         # assign_output: RLC along k (challenge 1, first-phase input), then along i (challenge 0, second-phase input)
-        inter = self._rlc(region, 1, O, c1, L, 0, cur)
-        inter = self._rlc(region, 0, inter, c0, L, 1, cur)
+        inter = self._rlc(region, 1, O, rlc, L, 0, cur)
+        inter = self._rlc(region, 0, inter, rlc, L, 1, cur)
         squashed_out = self._assign(region, E.outputs[1], inter, live=(cur == 1))[0]
         region.coord += 1
         # input reductions (reduction_planner::input_reductions("ij,jk->ik")): axis i, axis k, then the common axis j
         colsA = [A[i][j] for j in range(L) for i in range(L)]          # for every j: the slice A[:, j]
-        ra = self._rlc(region, 0, colsA, c0, L, 0, cur)
+        ra = self._rlc(region, 0, colsA, rlc, L, 0, cur)
         rowsB = [B[j][kk] for j in range(L) for kk in range(L)]        # for every j: the slice B[j, :]
-        rb = self._rlc(region, 1, rowsB, c1, L, 0, cur)
+        rb = self._rlc(region, 1, rowsB, rlc, L, 0, cur)
         # contraction "j,j->": dot of two second-phase vectors (einsum/layouts.rs `dot`, BothSecondPhase)
         sel = E.contraction_selectors
-        self._assign(region, E.inputs[2], ra, live=(cur == 1))
-        self._assign(region, E.inputs[3], rb, live=(cur == 1))
-        acc, run = 0, []
-        for x, y in zip(ra, rb):
-            acc = (acc + x.v * y.v) % R
-            run.append(Val(acc))
-        outs = self._assign(region, E.outputs[1], run, live=(cur == 1))
+        xa = self._assign(region, E.inputs[2], ra, live=(cur == 1))
+        xb = self._assign(region, E.inputs[3], rb, live=(cur == 1))
+        outs = self._assign(region, E.outputs[1], dot(xa, xb), live=(cur == 1))
         region.enable(sel[((EC.DOTINIT, EC.BOTH_SECOND), 0, 0)], region.coord)
         for t in range(1, L):
             region.enable(sel[((EC.DOT, EC.BOTH_SECOND), 0, 0)], region.coord + t)
@@ -196,6 +188,36 @@ class EinsumMatmulCircuit:
         region.coord += 1
         region.copy(squashed_in.cell, squashed_out.cell)
         return region
+
+    def synthesize(self, a, b, challenges=None, region=None):
+        """a, b: len x len integer arrays (values mod r).  challenges=None: first phase (first-phase columns, selectors, copies);
+        else the two challenges: everything.  Returns the Region (a fresh one unless the caller hands its own)."""
+        L = self.len
+        cur = 0 if challenges is None else 1
+        if region is None:
+            region = Region(self.cs, self.k)
+        A = [[Val(int(a[i][j])) for j in range(L)] for i in range(L)]
+        B = [[Val(int(b[j][kk])) for kk in range(L)] for j in range(L)]
+        O = [Val(int(v)) for v in self.matmul(a, b).reshape(-1)]
+        def rlc(vals, ci):
+            if cur == 0:
+                return [Val(0)] * len(vals)
+            c, acc, run = challenges[ci], 0, []
+            for v in vals:
+                acc = (acc * c + c * v.v) % R
+                run.append(Val(acc))
+            return run
+        def dot(xs, ys):
+            acc, run = 0, []
+            for x, y in zip(xs, ys):
+                acc = (acc + x.v * y.v) % R
+                run.append(Val(acc))
+            return run
+        return self.sequence(region, A, B, O, rlc, dot, cur)
+
+    def plan_identity(self):
+        """what a witness plan of this circuit depends on (witness_plan.params_hash)"""
+        return ("%s:k=%d:len=%d:ij,jk->ik" % (type(self).__name__, self.k, self.len)).encode()
 
     @staticmethod
     def matmul(a, b):

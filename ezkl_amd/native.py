@@ -374,19 +374,30 @@ def verify_proof_vk(circuit, vk_bytes, g2, s_g2, proof, instances=()):
     return bool(ok.value)
 
 
-def create_proof(pk, g, g_lagrange, advice_values, rng=None, seed=0, instances=(), timings=None, check_mode="UNSAFE", g2=None, s_g2=None):
+def create_proof(pk, g, g_lagrange, advice_values, rng=None, seed=0, instances=(), timings=None, check_mode="UNSAFE", g2=None, s_g2=None,
+                 device_columns=()):
     """advice_values: list of columns, or a callable advice_values(phase, challenges) -> {column: array} (second-phase advice).  A column
     is an (n, 4) uint64 array of Montgomery words (halo2's Fp), or the INTEGERS its cells were made from (ezkl's IntegerRep,
     src/fieldutils.rs:6-17): an (n,) int64 array, or an (n, 2) uint64 array of little-endian two's-complement 128-bit values -- 8 / 16
     bytes per cell across PCIe instead of 32, expanded on the device (ezkl_prover_create_proof_fmt); or a backend.DeviceBuffer of 2^k
     Montgomery words already on the device (a witness synthesized there, backend.WitnessPlan.run): it is not copied to the host and is
     left as it is; the proof bytes are the same in every case, and the kinds mix freely.  rng: object with .vec(m) -> (m,4) u64 Montgomery residues (None = the library's own
-    generator, seeded with `seed`, 0 = OS entropy); instances: list of lists of ints.  Returns the proof bytes."""
+    generator, seeded with `seed`, 0 = OS entropy); instances: list of lists of ints.  Returns the proof bytes.
+    device_columns (with a callable advice_values): the columns for which the callable returns a backend.DeviceBuffer -- a witness
+    synthesized on the device phase by phase (backend.WitnessPlan.advice_fn); every other column it returns is a Montgomery array.  A
+    column of the other kind than declared fails the callback."""
     cs = pk.circuit.cs
     n = cs.n
     keep = []
     adv_arr, adv_cb, adv_fmt = None, C.cast(None, ADVICE_FN), None
+    on_device = set(int(c) for c in device_columns)
+    if on_device and not callable(advice_values):
+        raise ValueError("device_columns goes with a callable advice_values (a list says column by column what it holds)")
+    if any(not 0 <= c < cs.n_advice for c in on_device):
+        raise ValueError("device_columns names an advice column the circuit does not have")
     if callable(advice_values):
+        if on_device:
+            adv_fmt = (C.c_uint8 * cs.n_advice)(*[3 if c in on_device else 0 for c in range(cs.n_advice)])
         _check(load().ezkl_prover_cs_set_advice_by_pointer(pk.circuit.h, 1), "ezkl_prover_cs_set_advice_by_pointer")
         def _cb(_user, phase, chal_ptr, n_chal, cols_ptr):
             try:
@@ -394,6 +405,16 @@ def create_proof(pk, g, g_lagrange, advice_values, rng=None, seed=0, instances=(
                 vals = advice_values(int(phase), [_pl.from_mont(c) for c in ch])
                 for c, a in vals.items():
                     if cs.advice_phase[c] != phase:
+                        continue
+                    resident = hasattr(a, "ptr") and hasattr(a, "nbytes")
+                    if resident != (c in on_device):          # never reinterpreted: a device pointer read as host memory, or the reverse
+                        raise TypeError("advice column %d: %s, device_columns says %s" % (c, "a device buffer" if resident else "a host array",
+                                                                                           "a device buffer" if c in on_device else "a host array"))
+                    if resident:
+                        if not a.ptr or a.nbytes < 32 * n:
+                            raise ValueError("advice column %d: a device column needs %d bytes" % (c, 32 * n))
+                        keep.append(a)
+                        cols_ptr[c] = a.ptr
                         continue
                     a = np.ascontiguousarray(a, np.uint64)
                     assert a.size == 4 * n

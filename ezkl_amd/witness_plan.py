@@ -1,4 +1,4 @@
-"""Witness plans: the layout of an MlpCircuit or a ConvMnistCircuit recorded ONCE, replayed for every proof.
+"""Witness plans: the layout of an MlpCircuit, a ConvMnistCircuit or an EinsumMatmulCircuit recorded ONCE, replayed for every proof.
 
 Which advice cell holds which value depends only on the circuit (BaseRegion places cells from the linear coordinate, the duplicated rows
 of `dot` from the block geometry; constants, weights and biases are the same for every input), so `record_plan` runs one witness-free
@@ -16,10 +16,11 @@ ReLU part at k = 17; by levels it is 25.  The MLP path keeps the latest-fit rule
 The plan is a flat little-endian blob (`WitnessPlan.to_bytes`):
 
     header   20 x u32: magic "EZWP", version, k, n_advice, n_records, n_inputs, n_params, n_consts, n_outputs, n_cells, n_words, n_ops,
-             n_tables, n_table_values, 6 reserved (zero); then the 32-byte parameter hash
+             n_tables, n_table_values, n_challenges, n_phases (0 reads as 1: a one-phase plan writes 0, the reserved word it was), 4 reserved
+             (zero); then the 32-byte parameter hash
     params   n_params  x int64        weights then biases (fixed at record time)
     consts   n_consts  x 32 bytes     canonical field elements
-    records  n_records x 8 u32        kind, count, p0, p1, dst, a, b, 0   (dst / a / b: word offsets into the pool)
+    records  n_records x 8 u32        kind, count, p0, p1, dst, a, b, phase   (dst / a / b: word offsets into the pool)
     outputs  n_outputs x u32          the cells that hold the circuit's outputs
     pool     n_words   x u32          cell indices (column * 2^k + row), table indices, per-element arguments
     tables   n_tables  x 4 u32        lo (int32), n (entries), col_size, offset into the values      } both sections are empty in a plan
@@ -41,6 +42,18 @@ A record of an element-wise kind has `count` destination cells pool[dst + i], pr
     TBLIDX a = source cell, p0 = table index: (s - lo) // col_size, the table column that holds s
            both: s < lo, s > lo + n - 1 or |s| >= 2^62 is the lookup-range failure ("lookup input outside the table range"), reported like the
            decomposition-range failure
+
+PHASES.  A circuit with second-phase advice (the Freivalds einsum) has columns that depend on challenges squeezed after the first-phase
+commitments: its plan has n_phases = 2, and every record carries the phase whose run replays it.  Phases are non-decreasing along the
+record list; a column belongs to the phase of the records that write it (never to two; a column no record writes: phase 0); INPUT and
+MATMUL records belong to phase 0, with which the inputs are uploaded.  A later phase reads the cells of an earlier one where they are.
+    MATMUL count = m * n outputs, p0 = kd, p1 = n: pool[dst + i * n + j] = sum_t in[pool[a + i * kd + t]] * in[pool[b + t * n + j]] over the
+           INTEGERS, then integer_rep_to_felt -- the product the prover witnesses (EinsumMatmulCircuit.matmul); a: m * kd, b: kd * n input
+           indices.  Every operand must satisfy |v| < 2^31 (the sum then fits 128 bits): one outside is the run-time failure "einsum operand
+           outside the exact-product range", reported like the decomposition-range failure with element = the operand's place in a, or m * kd +
+           its place in b
+    RLC    count scans of p1 steps with challenge p0, step-major and dense: out[0] = c * v[0], out[t] = out[t - 1] * c + c * v[t] with
+           v[t] = the cell pool[a + t * count + d], out[t] -> pool[dst + t * count + d]   (RLCConfig::assign_rlc at block width 1)
 
 COUPLING WITH ezkl_layout.py.  The recorder reuses BaseRegion's value expressions too, by operator overloading on the symbols below, and
 recognises them AS THEY ARE SPELT there.  Whoever rewrites one of these lines of BaseRegion must extend the symbol classes with it (the
@@ -69,11 +82,13 @@ from . import ezkl_layout as EL
 R = EL.R
 MAGIC, VERSION = 0x50575A45, 1                  # "EZWP"
 NONE = 0xFFFFFFFF
-COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX = range(13)
-KIND_NAMES = ["copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot", "nonlinearity", "nonlinearity_index"]
+COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC = range(15)
+KIND_NAMES = ["copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot", "nonlinearity", "nonlinearity_index", "matmul", "rlc"]
 _HEADER = struct.Struct("<20I32s")
 RANGE_ERROR = "value exceeds the decomposition range"
 LOOKUP_ERROR = "lookup input outside the table range"
+OPERAND_ERROR = "einsum operand outside the exact-product range"
+MAX_PHASES, MAX_CHALLENGES = 3, 64
 
 
 class PlanError(ValueError):
@@ -228,25 +243,28 @@ class _Records:
     """cell writes grouped by kind and data dependence"""
 
     def __init__(self, earliest=False):
-        self.recs = []                             # dict(kind, p0, p1, dst, a, b) / for DOT: dict(kind, p0, dots)
-        self.latest = {}                           # (kind, p0, p1) -> record index
-        self.of_key = {} if earliest else None     # earliest fit: (kind, p0, p1) -> its record indices, ascending
+        self.recs = []                             # dict(kind, p0, p1, phase, dst, a, b) / for DOT: dict(kind, p0, dots) / for RLC: scans
+        self.latest = {}                           # (kind, p0, p1, phase) -> record index
+        self.of_key = {} if earliest else None     # earliest fit: (kind, p0, p1, phase) -> its record indices, ascending
         self.rec_of = {}                           # cell -> record that writes it
 
-    def _slot(self, key, sources):
+    def _new(self, key):
+        self.recs.append(dict(kind=key[0], p0=key[1], p1=key[2], phase=key[3], dst=[], a=[], b=[], dots=[], scans=[]))
+        return len(self.recs) - 1
+
+    def _slot(self, key, sources, phase=0):
+        key += (phase,)
         need = 1 + max((self.rec_of[s] for s in sources), default=-1)
         if self.of_key is not None:                # the earliest record of the kind above every record the write reads from
             mine = self.of_key.setdefault(key, [])
             at = bisect.bisect_left(mine, need)
             if at < len(mine):
                 return mine[at]
-            mine.append(len(self.recs))
-            self.recs.append(dict(kind=key[0], p0=key[1], p1=key[2], dst=[], a=[], b=[], dots=[]))
+            mine.append(self._new(key))
             return mine[-1]
         ri = self.latest.get(key)
         if ri is None or ri < need:
-            ri = self.latest[key] = len(self.recs)
-            self.recs.append(dict(kind=key[0], p0=key[1], p1=key[2], dst=[], a=[], b=[], dots=[]))
+            ri = self.latest[key] = self._new(key)
         return ri
 
     def _claim(self, dst, ri):
@@ -254,27 +272,50 @@ class _Records:
             raise PlanError("advice cell %d is written twice: not a write-once layout" % dst)
         self.rec_of[dst] = ri
 
-    def emit(self, kind, dst, a, b=None, p0=0, p1=0, reads=()):
+    def emit(self, kind, dst, a, b=None, p0=0, p1=0, reads=(), phase=0):
         for s in reads:
             if s not in self.rec_of:
                 raise PlanError("advice cell %d is read before it is written" % s)
-        ri = self._slot((kind, p0, p1), reads)
+        ri = self._slot((kind, p0, p1), reads, phase)
         rec = self.recs[ri]
         rec["dst"].append(dst); rec["a"].append(a)
         if b is not None:
             rec["b"].append(b)
         self._claim(dst, ri)
 
-    def emit_dot(self, w, steps):
+    def emit_dot(self, w, steps, phase=0):
         """steps: [(dst, [(a, b), ...])]"""
         reads = [c for _, pairs in steps for ab in pairs for c in ab]
         for s in reads:
             if s not in self.rec_of:
                 raise PlanError("advice cell %d is read before it is written" % s)
-        ri = self._slot((DOT, w, 0), reads)
+        ri = self._slot((DOT, w, 0), reads, phase)
         self.recs[ri]["dots"].append(steps)
         for dst, _ in steps:
             self._claim(dst, ri)
+
+    def emit_scan(self, challenge, src, dst, phase):
+        """one RLC scan: step t reads cell src[t] and writes cell dst[t]"""
+        for s in src:
+            if s not in self.rec_of:
+                raise PlanError("advice cell %d is read before it is written" % s)
+        ri = self._slot((RLC, challenge, len(src)), src, phase)
+        self.recs[ri]["scans"].append((list(src), list(dst)))
+        for d in dst:
+            self._claim(d, ri)
+
+    def emit_matmul(self, m, kd, n, a, b):
+        """the record of an m x kd by kd x n integer product over the inputs a, b (row-major); its m * n destinations are claimed one by
+        one (`matmul_dst`) as the layout places them"""
+        ri = self._new((MATMUL, kd, n, 0))
+        self.recs[ri].update(dst=[None] * (m * n), a=list(a), b=list(b))
+        return ri
+
+    def matmul_dst(self, ri, at, dst):
+        if self.recs[ri]["dst"][at] is not None:
+            raise PlanError("a matmul output is placed twice")
+        self.recs[ri]["dst"][at] = dst
+        self._claim(dst, ri)
 
 
 class RecordingRegion(EL.BaseRegion):
@@ -455,10 +496,121 @@ class LookupRecordingRegion(RecordingRegion):
             super()._emit(v, dst)
 
 
+class _MatOut(_Sym):
+    """entry `at` of the integer product of matmul record `rec`"""
+
+    def __init__(self, rec, at): self.rec, self.at = rec, at
+
+
+class _Run:
+    """the running values of one RLC scan or one dot, pending until the layout has placed every step"""
+
+    def __init__(self, kind, p0, src): self.kind, self.p0, self.src, self.dst, self.left = kind, p0, src, [None] * len(src), len(src)
+
+
+class _Step(_Sym):
+    def __init__(self, run, t): self.run, self.t = run, t
+
+
+class EinsumRecordingRegion(EL.Region):
+    """Region with symbolic values for EinsumMatmulCircuit.sequence: the rows are those `_assign` computes from the shared coordinate,
+    `put_cell` records how the cell is produced and in which phase -- phase 0 for inputs and the integer product, at least 1 for
+    whatever a challenge enters, otherwise the latest phase among the cells read -- and refuses a value placed in a column of another
+    phase.  Records are grouped by kind, phase and dependence level."""
+
+    def __init__(self, circuit):
+        super().__init__(circuit.cs, circuit.k)
+        self.n_adv = len(circuit.cs.advice)
+        self.out = _Records(earliest=True)
+        self.consts, self.n_ops = [], 0
+        self.phase_of = {}                         # cell -> the phase that writes it
+
+    def copy(self, a, b):                          # copy constraints and selectors belong to keygen, not to the witness
+        pass
+
+    def enable(self, selector, row):
+        pass
+
+    def matmul(self, m, kd, n, a, b):
+        self.n_ops += 1
+        ri = self.out.emit_matmul(m, kd, n, a, b)
+        return [EL.Val(_MatOut(ri, at)) for at in range(m * n)]
+
+    def _cells(self, vals):
+        if not all(isinstance(v.v, _Cell) for v in vals):
+            raise PlanError("a reduction over values that are not assigned cells")
+        return [v.v.idx for v in vals]
+
+    def rlc(self, vals, challenge):
+        self.n_ops += 1
+        run = _Run(RLC, challenge, self._cells(vals))
+        return [EL.Val(_Step(run, t)) for t in range(len(vals))]
+
+    def dot(self, xs, ys):
+        self.n_ops += 1
+        run = _Run(DOT, 1, list(zip(self._cells(xs), self._cells(ys))))
+        return [EL.Val(_Step(run, t)) for t in range(len(xs))]
+
+    def put_cell(self, col, row, v):
+        dst = (col.index << self.k) + row
+        out = self.out
+        if isinstance(v, _Input):
+            phase = 0
+            out.emit(INPUT, dst, v.idx)
+        elif isinstance(v, _MatOut):
+            phase = 0
+            out.matmul_dst(v.rec, v.at, dst)
+        elif isinstance(v, _Cell):
+            phase = self.phase_of[v.idx]
+            out.emit(COPY, dst, v.idx, reads=(v.idx,), phase=phase)
+        elif isinstance(v, _Step):
+            run = v.run
+            if run.dst[v.t] is not None:
+                raise PlanError("a running value is placed twice")
+            run.dst[v.t] = dst
+            run.left -= 1
+            if run.left == len(run.src) - 1:       # the phase of the whole run: worked out once, at its first step
+                run.phase = max([1 if run.kind == RLC else 0] + [self.phase_of[c] for c in (run.src if run.kind == RLC else [c for ab in run.src for c in ab])])
+            phase = run.phase
+            if run.kind == RLC:
+                if not run.left:
+                    out.emit_scan(run.p0, run.src, run.dst, phase)
+            else:
+                if not run.left:
+                    out.emit_dot(run.p0, [(d, [ab]) for d, ab in zip(run.dst, run.src)], phase)
+        else:
+            raise PlanError("the witness plan recorder does not cover a %s value in an einsum" % type(v).__name__)
+        if phase != self.cs.advice[col.index].phase:
+            raise PlanError("advice column %d belongs to phase %d, the value placed in it to phase %d" % (col.index, self.cs.advice[col.index].phase, phase))
+        if dst in self.phase_of:
+            raise PlanError("advice cell %d is written twice: not a write-once layout" % dst)
+        self.phase_of[dst] = phase
+        return _Cell(dst)
+
+
+def _record_einsum(circuit):
+    """EinsumMatmulCircuit: its own `sequence` over symbols -- the inputs are A then B, row-major; the product is one MATMUL record"""
+    L = circuit.len
+    if (len(circuit.cs.advice) << circuit.k) > 1 << 32:
+        raise PlanError("cells are numbered in 32 bits")
+    reg = EinsumRecordingRegion(circuit)
+    Val = EL.Val
+    A = [[Val(_Input(i * L + j)) for j in range(L)] for i in range(L)]
+    B = [[Val(_Input(L * L + j * L + kk)) for kk in range(L)] for j in range(L)]
+    O = reg.matmul(L, L, L, range(L * L), range(L * L, 2 * L * L))
+    reg.out._slot((INPUT, 0, 0), ())               # the input record next: it reads no cell, and a reduction over inputs can then join the earliest of its kind
+    circuit.sequence(reg, A, B, O, reg.rlc, reg.dot, 1)
+    return WitnessPlan._from_recorder(circuit, reg, [], [], n_challenges=len(circuit.cs.challenges),
+                                      n_phases=1 + max(c.phase for c in circuit.cs.advice))
+
+
 def params_hash(circuit):
     """what a plan depends on besides the layout code: the circuit's shape options and its parameters (for a circuit with `layout`: its
     `plan_identity()` bytes and its static lookup tables)"""
     h = hashlib.sha256()
+    if type(circuit) is EL.EinsumMatmulCircuit:
+        h.update(b"phased:" + circuit.plan_identity())
+        return h.digest()
     if type(circuit) is not EL.MlpCircuit:
         h.update(("layout:%s:" % type(circuit).__name__).encode())
         h.update(circuit.plan_identity())
@@ -479,10 +631,13 @@ def record_plan(circuit):
     """one witness-free layout pass -> WitnessPlan, with the input vector and the parameters as symbols.  An MlpCircuit: the op sequence is
     MlpCircuit.synthesize's, restated here.  A circuit that states its op sequence itself -- `layout(reg, inputs, param) -> outputs`, which its
     own `synthesize` runs too, with `n_inputs` and `plan_identity()` (ConvMnistCircuit) -- is recorded from that, on a
-    LookupRecordingRegion.  Every other circuit class is refused by name."""
+    LookupRecordingRegion.  An EinsumMatmulCircuit with columns of its own (not one laid over another circuit's) is recorded from its
+    `sequence` into a two-phase plan.  Every other circuit class is refused by name."""
+    if type(circuit) is EL.EinsumMatmulCircuit and getattr(circuit, "standalone", False):
+        return _record_einsum(circuit)
     mlp = type(circuit) is EL.MlpCircuit
     if not mlp and not (callable(getattr(circuit, "layout", None)) and callable(getattr(circuit, "plan_identity", None))):
-        raise PlanError("witness plans cover MlpCircuit and circuits that state their `layout`, not %s (einsum, sum / prod and the surrogate "
+        raise PlanError("witness plans cover MlpCircuit and circuits that state their `layout`, not %s (sum / prod and the surrogate "
                         "circuits keep the host path)" % type(circuit).__name__)
     if any(c.phase != 0 for c in circuit.gc.cs.advice):
         raise PlanError("witness plans do not cover second-phase advice")
@@ -516,9 +671,11 @@ def record_plan(circuit):
 
 
 class WitnessPlan:
-    def __init__(self, k, n_advice, n_inputs, params, consts, records, outputs, pool, n_cells, n_ops, param_hash, tables=(), table_values=()):
+    def __init__(self, k, n_advice, n_inputs, params, consts, records, outputs, pool, n_cells, n_ops, param_hash, tables=(), table_values=(),
+                 n_challenges=0, n_phases=1):
         """tables: (lo, n, col_size, offset into table_values) per static lookup table"""
         self.k, self.n_advice, self.n_inputs = k, n_advice, n_inputs
+        self.n_challenges, self.n_phases = n_challenges, n_phases or 1
         self.tables = [tuple(int(v) for v in t) for t in tables]
         self.table_values = np.ascontiguousarray(table_values, np.int64).reshape(-1)
         self.params = np.ascontiguousarray(params, np.int64)
@@ -529,7 +686,7 @@ class WitnessPlan:
         self.n_cells, self.n_ops, self.param_hash = n_cells, n_ops, bytes(param_hash)
 
     @classmethod
-    def _from_recorder(cls, circuit, reg, params, outputs):
+    def _from_recorder(cls, circuit, reg, params, outputs, n_challenges=0, n_phases=1):
         pool, records, n_cells = [], [], 0
         off = 0
         def push(a):
@@ -538,8 +695,18 @@ class WitnessPlan:
             pool.append(a)
             off += len(a)
             return off - len(a)
-        for rec in reg.out.recs:
-            if rec["kind"] == DOT:
+        for rec in sorted(reg.out.recs, key=lambda r: r["phase"]):     # stable: a record reads cells of its own phase or an earlier one
+            phase = rec["phase"]
+            if rec["kind"] == RLC:
+                src, dst = (np.array([sc[t] for sc in rec["scans"]], np.uint32).T for t in (0, 1))     # step-major
+                n_cells += dst.size
+                records.append([RLC, len(rec["scans"]), rec["p0"], rec["p1"], push(dst), push(src), 0, phase])
+            elif rec["kind"] == MATMUL:
+                if None in rec["dst"]:
+                    raise PlanError("a matmul output is never placed")
+                n_cells += len(rec["dst"])
+                records.append([MATMUL, len(rec["dst"]), rec["p0"], rec["p1"], push(rec["dst"]), push(rec["a"]), push(rec["b"]), phase])
+            elif rec["kind"] == DOT:
                 w, dots = rec["p0"], rec["dots"]
                 nd, ns = len(dots), max(len(d) for d in dots)
                 dst = np.full((ns, nd), NONE, np.uint32)
@@ -551,24 +718,24 @@ class WitnessPlan:
                         for j, (x, y) in enumerate(pairs):
                             a[s, j, d], b[s, j, d] = x, y
                     n_cells += len(steps)
-                records.append([DOT, nd, w, ns, push(dst), push(a), push(b), 0])
+                records.append([DOT, nd, w, ns, push(dst), push(a), push(b), phase])
             else:
                 n = len(rec["dst"])
                 n_cells += n
-                records.append([rec["kind"], n, rec["p0"], rec["p1"], push(rec["dst"]), push(rec["a"]), push(rec["b"]) if rec["b"] else 0, 0])
+                records.append([rec["kind"], n, rec["p0"], rec["p1"], push(rec["dst"]), push(rec["a"]), push(rec["b"]) if rec["b"] else 0, phase])
         tables, values = [], []
         for lo, col_size, vals in getattr(reg, "tables", ()):
             tables.append((lo, len(vals), col_size, sum(len(v) for v in values)))
             values.append(vals)
         return cls(circuit.k, reg.n_adv, circuit.n_inputs, params, reg.consts, records, outputs,
                    np.concatenate(pool) if pool else np.zeros(0, np.uint32), n_cells, reg.n_ops, params_hash(circuit),
-                   tables, np.concatenate(values) if values else ())
+                   tables, np.concatenate(values) if values else (), n_challenges, n_phases)
 
     # ---- the blob ------------------------------------------------------------------------------------------------------------------------
     def to_bytes(self):
         head = _HEADER.pack(MAGIC, VERSION, self.k, self.n_advice, len(self.records), self.n_inputs, len(self.params), len(self.consts),
-                            len(self.outputs), self.n_cells, len(self.pool), self.n_ops, len(self.tables), len(self.table_values), 0, 0, 0, 0, 0, 0,
-                            self.param_hash)
+                            len(self.outputs), self.n_cells, len(self.pool), self.n_ops, len(self.tables), len(self.table_values), self.n_challenges,
+                            self.n_phases if self.n_phases > 1 else 0, 0, 0, 0, 0, self.param_hash)
         directory = b"".join(struct.pack("<iIII", *t) for t in self.tables)
         return b"".join([head, self.params.astype("<i8").tobytes(), b"".join(c.to_bytes(32, "little") for c in self.consts),
                          self.records.astype("<u4").tobytes(), self.outputs.astype("<u4").tobytes(), self.pool.astype("<u4").tobytes(),
@@ -598,7 +765,7 @@ class WitnessPlan:
         pool = np.frombuffer(blob, "<u4", n_words, o[4])
         tables = [struct.unpack_from("<iIII", blob, o[5] + 16 * i) for i in range(n_tab)]
         values = np.frombuffer(blob[o[6]:o[7]], "<i8")
-        return cls(k, n_adv, n_in, params, consts, records, outputs, pool, n_cells, n_ops, f[20], tables, values)
+        return cls(k, n_adv, n_in, params, consts, records, outputs, pool, n_cells, n_ops, f[20], tables, values, f[14], f[15])
 
     def __eq__(self, other):
         return isinstance(other, WitnessPlan) and self.to_bytes() == other.to_bytes()
@@ -620,7 +787,7 @@ def peek(blob):
     if f[0] != MAGIC or f[1] != VERSION:
         raise PlanError("witness plan: bad magic or version")
     names = ["k", "n_advice", "n_records", "n_inputs", "n_params", "n_consts", "n_outputs", "n_cells", "n_words", "n_ops", "n_tables", "n_table_values"]
-    return dict(zip(names, f[2:14]), param_hash=f[20])
+    return dict(zip(names, f[2:14]), n_challenges=f[14], n_phases=f[15] or 1, param_hash=f[20])
 
 
 def _span(plan, off, n, what, ri):
@@ -654,10 +821,12 @@ class _Written:
 def validate(plan):
     """the check ezkl_hip_witness_plan_upload makes before anything reaches the device, mirrored line by line: geometry, every cell index below
     n_advice * 2^k, every table index in range, every lookup table inside the table values, every cell written at most once and read only
-    after an EARLIER record wrote it"""
+    after an EARLIER record wrote it, the phases non-decreasing and below n_phases, every column written in one phase only"""
     if not 1 <= plan.k <= 28 or not 0 < plan.n_advice <= 64 or (plan.n_advice << plan.k) > 1 << 32:
         raise PlanError("witness plan: bad geometry")
     cells = plan.n_advice << plan.k
+    if not 1 <= plan.n_phases <= MAX_PHASES or plan.n_challenges > MAX_CHALLENGES:
+        raise PlanError("witness plan: bad phase or challenge count")
     if any(c >= R for c in plan.consts):
         raise PlanError("witness plan: a constant is not a canonical field element")
     if plan.n_cells > len(plan.pool):
@@ -669,12 +838,36 @@ def validate(plan):
             raise PlanError("witness plan: table %d: runs past the table values" % ti)
     written = _Written(cells, plan.pool)
     total = 0
-    for ri, (kind, count, p0, p1, dst, a, b, _) in enumerate(plan.records.tolist()):
-        if kind > TBLIDX:
+    col_phase, last_phase = [None] * plan.n_advice, 0
+    for ri, (kind, count, p0, p1, dst, a, b, phase) in enumerate(plan.records.tolist()):
+        if kind > RLC:
             raise PlanError("witness plan: record %d: unknown kind %d" % (ri, kind))
         if count == 0:
             raise PlanError("witness plan: record %d is empty" % ri)
-        if kind == DOT:
+        if phase >= plan.n_phases:
+            raise PlanError("witness plan: record %d (%s): phase out of range" % (ri, KIND_NAMES[kind]))
+        if phase < last_phase:
+            raise PlanError("witness plan: record %d (%s): phases decrease" % (ri, KIND_NAMES[kind]))
+        last_phase = phase
+        if kind in (INPUT, MATMUL) and phase != 0:
+            raise PlanError("witness plan: record %d (%s): input and matmul records belong to phase 0" % (ri, KIND_NAMES[kind]))
+        if kind == MATMUL:
+            kd, nn = p0, p1
+            if kd == 0 or nn == 0 or count % nn != 0 or any(off > len(plan.pool) or n > len(plan.pool) - off for off, n in
+                                                             ((dst, count), (a, count // nn * kd), (b, kd * nn))):
+                raise PlanError("witness plan: record %d (%s): bad matmul shape" % (ri, KIND_NAMES[kind]))
+            d = _span(plan, dst, count, "dst", ri)
+            if (_span(plan, a, count // nn * kd, "a", ri) >= plan.n_inputs).any() or (_span(plan, b, kd * nn, "b", ri) >= plan.n_inputs).any():
+                raise PlanError("witness plan: record %d (%s): table index out of range" % (ri, KIND_NAMES[kind]))
+            srcs = np.zeros(0, np.uint32)
+        elif kind == RLC:
+            if p0 >= plan.n_challenges:
+                raise PlanError("witness plan: record %d (%s): challenge index out of range" % (ri, KIND_NAMES[kind]))
+            if p1 == 0 or count * p1 > len(plan.pool):
+                raise PlanError("witness plan: record %d (%s): bad rlc shape" % (ri, KIND_NAMES[kind]))
+            d = _span(plan, dst, count * p1, "dst", ri)
+            srcs = _span(plan, a, count * p1, "a", ri)
+        elif kind == DOT:
             w, ns = p0, p1
             if w == 0 or ns == 0 or count * ns * w > len(plan.pool):
                 raise PlanError("witness plan: record %d: bad dot shape" % ri)
@@ -713,6 +906,10 @@ def validate(plan):
             raise PlanError("witness plan: record %d (%s): a cell is written twice" % (ri, KIND_NAMES[kind]))
         written.set(d)
         total += len(d)
+        for c in np.unique(d >> plan.k).tolist():
+            if col_phase[c] is not None and col_phase[c] != phase:
+                raise PlanError("witness plan: record %d (%s): a column is written in two phases" % (ri, KIND_NAMES[kind]))
+            col_phase[c] = phase
     if total != plan.n_cells:
         raise PlanError("witness plan: %d cells written, its header says %d" % (total, plan.n_cells))
     if (plan.outputs >= cells).any() or not written.get(plan.outputs).all():
@@ -723,17 +920,55 @@ def _signed(v):
     return v if v < R // 2 else v - R
 
 
-def run_plan_host(plan, x):
+def column_phases(plan):
+    """the phase each advice column belongs to: that of the records that write it (`validate` refuses two), 0 for a column no record writes"""
+    out = [0] * plan.n_advice
+    for kind, count, p0, p1, dst, a, b, phase in plan.records.tolist():
+        n = count * p1 if kind in (DOT, RLC) else count
+        d = plan.pool[dst:dst + n]
+        for c in np.unique(d[d != NONE] >> plan.k).tolist():
+            out[c] = phase
+    return out
+
+
+def run_plan_host(plan, x, challenges=None, phase=None):
     """interpret the plan with Python integers -> (advice columns as lists of canonical ints, outputs).  Record by record, element by
-    element, what one lane of the device kernels does."""
+    element, what one lane of the device kernels does.  A plan with phases: with `challenges` (canonical ints) every phase is
+    interpreted; phase=0 interprets the first phase alone (the later columns stay zero, and so do the outputs)."""
     validate(plan)
     if len(x) != plan.n_inputs:
         raise ValueError("the plan takes %d inputs, got %d" % (plan.n_inputs, len(x)))
+    if phase not in (None, 0):
+        raise ValueError("the host interpreter runs every phase, or phase 0 alone")
+    challenges = [int(c) % R for c in challenges] if challenges is not None else []
+    if phase is None and plan.n_phases > 1 and len(challenges) < plan.n_challenges:
+        raise ValueError("the plan takes %d challenges, got %d" % (plan.n_challenges, len(challenges)))
     n = 1 << plan.k
     cells = [0] * (plan.n_advice * n)
     P, params, consts = plan.pool.tolist(), plan.params.tolist(), plan.consts
     xs = [int(v) for v in x]
-    for ri, (kind, count, p0, p1, dst, a, b, _) in enumerate(plan.records.tolist()):
+    for ri, (kind, count, p0, p1, dst, a, b, rec_phase) in enumerate(plan.records.tolist()):
+        if phase is not None and rec_phase > phase:
+            break
+        if kind == MATMUL:
+            kd, nn = p0, p1
+            m = count // nn
+            ia, ib = P[a:a + m * kd], P[b:b + kd * nn]
+            for e, i in enumerate(ia + ib):                # every operand a lane reads, the smallest failing element first
+                if abs(xs[i]) >= 1 << 31:
+                    raise AssertionError("%s (%s record %d, element %d)" % (OPERAND_ERROR, KIND_NAMES[kind], ri, e))
+            for i in range(m):
+                for j in range(nn):
+                    cells[P[dst + i * nn + j]] = sum(xs[ia[i * kd + t]] * xs[ib[t * nn + j]] for t in range(kd)) % R
+            continue
+        if kind == RLC:
+            c = challenges[p0]
+            for d in range(count):
+                acc = 0
+                for t in range(p1):
+                    acc = (acc * c + c * cells[P[a + t * count + d]]) % R
+                    cells[P[dst + t * count + d]] = acc
+            continue
         if kind == DOT:
             w, ns = p0, p1
             for d in range(count):
@@ -776,4 +1011,5 @@ def run_plan_host(plan, x):
                     raise AssertionError("%s (%s record %d, element %d)" % (RANGE_ERROR, KIND_NAMES[kind], ri, i))
                 v = ((s > 0) - (s < 0)) % R if e == NONE else (abs(s) // p0 ** e) % p0
             cells[P[dst + i]] = v
-    return [cells[c * n:(c + 1) * n] for c in range(plan.n_advice)], [cells[c] for c in plan.outputs.tolist()]
+    done = phase is None or phase == plan.n_phases - 1
+    return [cells[c * n:(c + 1) * n] for c in range(plan.n_advice)], [cells[c] for c in plan.outputs.tolist()] if done else []

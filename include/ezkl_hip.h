@@ -249,7 +249,7 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *      (nonlinearity :5143-5222), which with those ops is the conv2d_mnist example's layout ----
  * A PLAN is the layout recorded once per circuit (ezkl_amd/witness_plan.py; byte layout: csrc/witness_plan.hpp): a list of records, each a
  * batch of cell writes of one kind (copy, const, input, param, add / sub / mult, decompose hint, range-check index, inverse-or-zero, dot,
- * static-lookup output, static-lookup table-column index) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
+ * static-lookup output, static-lookup table-column index, integer matmul, random linear combination) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
  * of constants and -- header words 12 / 13 (n_tables, n_table_values; zero, as reserved words were, in a plan without lookups), after the
  * pool -- a directory of {lo (int32), n, col_size, offset} per static lookup table and the tables' values f(lo + i) as int64.  The version
  * word stays 1.  A lookup record names its source cells and a table: with s the signed value of the cell, the output kind writes
@@ -267,13 +267,32 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *   element; the columns are then not a witness.  A lookup input outside its table (s < lo, s > lo + n - 1, |s| >= 2^62: the layout's
  *   "lookup input outside the table range") is reported the same way, with that message.  Scratch belongs to the plan (column pool): nothing is allocated per run, and a plan
  *   runs one synthesis at a time.  HIP events around the run: ezkl_hip_last_kernel_ms("witness").
- * info: out = {k, n_advice, n_inputs, n_outputs, n_records, n_cells, n_ops (layout-op calls recorded), n_params}. */
+ * info: out = {k, n_advice, n_inputs, n_outputs, n_records, n_cells, n_ops (layout-op calls recorded), n_params}.
+ * PHASES (second-phase advice: the Freivalds einsum, /root/reference/src/circuit/ops/chip/einsum/mod.rs:96-309).  Header word 14 of the blob is
+ *   n_challenges, word 15 n_phases (0 reads as 1), the eighth word of a record its phase -- all three were reserved zeros, so every one-phase
+ *   blob keeps its bytes and the version word stays 1.  Phases are non-decreasing along the record list; a column belongs to the phase of the
+ *   records that write it (never to two; a column no record writes: phase 0); input and matmul records belong to phase 0.  Two record kinds
+ *   serve the einsum: matmul -- count = m * n, p0 = kd, p1 = n, a / b = m * kd / kd * n input indices: dst[i * n + j] = sum_t in[a[i * kd + t]] *
+ *   in[b[t * n + j]] over the integers, then integer_rep_to_felt; every operand must satisfy |v| < 2^31, one outside is reported as a value
+ *   beyond its decomposition is ("einsum operand outside the exact-product range", element = its place in a, or m * kd + its place in b) --
+ *   and rlc -- count scans of p1 steps with challenge p0, step-major and dense: out[0] = c * v[0], out[t] = out[t - 1] * c + c * v[t].
+ * run_phase: one phase of a plan, between the prover's commit stages.  challenges = n_challenges x 32 bytes, little-endian CANONICAL scalars
+ *   (the ones squeezed so far; a non-canonical one: EZKL_ERR_INVALID).  The run zero-fills and writes the columns of ITS phase only; the
+ *   inputs are taken with phase 0 (later phases ignore inputs_host / n_inputs), the outputs are gathered by the last phase (outputs_host may
+ *   be NULL before).  Phase p > 0 needs a phase p - 1 that ran to its end on the same column pointers since the last phase 0 -- it reads
+ *   those cells where they are -- and is refused otherwise (EZKL_ERR_INVALID, "phase 1 before phase 0 ...", nothing is launched).  status as
+ *   for run, per phase.  ezkl_hip_witness_run_dev on a one-phase plan is run_phase(0); on a plan with phases it returns EZKL_ERR_INVALID and
+ *   names this call.
+ * phases: out = {n_phases, n_challenges}; column_phase (may be NULL): n_advice bytes, the phase each column belongs to. */
 typedef struct ezkl_wplan_s* ezkl_wplan_t;
 int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out_plan);
 int ezkl_hip_witness_plan_free(ezkl_wplan_t plan);
 int ezkl_hip_witness_plan_info(ezkl_wplan_t plan, uint32_t out[8]);
 int ezkl_hip_witness_run_dev(ezkl_wplan_t plan, const int64_t* inputs_host, size_t n_inputs, void* const* advice_cols_dev, void* outputs_host,
                              uint64_t status[4], void* stream);
+int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int64_t* inputs_host, size_t n_inputs, const void* challenges, size_t n_challenges,
+                                   void* const* advice_cols_dev, void* outputs_host, uint64_t status[4], void* stream);
+int ezkl_hip_witness_plan_phases(ezkl_wplan_t plan, uint32_t out[2], uint8_t* column_phase);
 const char* ezkl_hip_witness_last_error(void);   /* the calling thread's last refusal (upload) or range failure (run); "" after a success */
 /* A commit batch fed as its columns become final: begin; push (one column / several: fused into groups as the one-call batch does) any
  * number of times; finish returns the points in push order and closes the batch (also after an error).  A push returns once the MSMs

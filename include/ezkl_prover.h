@@ -202,7 +202,11 @@ int ezkl_prover_create_proof(ezkl_pk_t pk, ezkl_bases_t g, ezkl_bases_t g_lagran
  * EZKL_COLUMN_DEVICE_FP: advice[c] is a DEVICE column of 2^k x 32 bytes (ezkl_hip_malloc), e.g. a witness synthesized on the device
  * (ezkl_hip_witness_run_dev): it is taken without a host round trip and left unmodified -- the blinding rows go into the prover's own
  * copy, as for host columns.  Host and device columns mix freely in one call; the proof is byte for byte that of the host columns.
- * Single-context proving only: EZKL_ERR_INVALID on a sharded constraint system. */
+ * Single-context proving only: EZKL_ERR_INVALID on a sharded constraint system.
+ * With advice_fn on a constraint system set to by-pointer advice the formats describe what the callback leaves in columns[c]: for
+ * EZKL_COLUMN_DEVICE_FP a device column, e.g. the one a phase of a witness plan has just filled (ezkl_hip_witness_run_phase_dev with the
+ * challenges the callback receives, Montgomery -> canonical).  Device columns are left untouched, so the first-phase cells are still in
+ * place when the second-phase run reads them. */
 int ezkl_prover_create_proof_fmt(ezkl_pk_t pk, ezkl_bases_t g, ezkl_bases_t g_lagrange, const void* const* advice, const uint8_t* advice_formats,
                                  ezkl_advice_fn advice_fn, void* advice_user, const void* const* instances, const uint32_t* instance_lens, ezkl_rng_fn rng,
                                  void* rng_user, uint64_t seed, void* proof_out, size_t cap, size_t* proof_len, double* timings);

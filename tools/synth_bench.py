@@ -11,7 +11,15 @@ One process per size, every GPU step under its own time limit:
 
     timeout -k 10 600 python tools/synth_bench.py --k 14 --tag <tag> && timeout -k 10 900 python tools/synth_bench.py --k 17 --tag <tag>
 
-Each run merges its entry into profiles/<tag>_synth.json (key "k<k>" for the MLP, "conv_k<k>" for --circuit conv).  --skip-host leaves the host pass out (k = 20: over a minute of Python);
+--circuit einsum: the bench's EinsumMatmulCircuit (tools/bench_circuits.py kind="einsum": len 64 / 180 / 512 at k = 14 / 17 / 20), whose
+second-phase columns depend on the proof's challenges, so the host pass runs INSIDE create_proof, once per phase:
+
+    host_s              both phases of circuit.advice_fn + cols_to_mont -- what the per-phase callback of create_proof costs: the yardstick
+    device_phase0/1_*   the phase-0 run and the phase-1 run of the plan, HIP events around each: first run, minimum and median of --repeat
+    create_proof_*_s    wall time of native.create_proof with the host callable and with the device callable (backend.WitnessPlan.advice_fn),
+                        same key and seed; the proof bytes must be equal (--skip-proof leaves the pair out)
+
+Each run merges its entry into profiles/<tag>_synth.json (key "k<k>" for the MLP, "conv_k<k>" for --circuit conv, "einsum_k<k>").  --skip-host leaves the host pass out (k = 20: over a minute of Python);
 --plan-dir keeps recorded plans between runs (a plan depends only on the circuit)."""
 import argparse
 import json
@@ -29,7 +37,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--k", type=int, required=True)
-    ap.add_argument("--circuit", choices=("mlp", "conv"), default="mlp")
+    ap.add_argument("--circuit", choices=("mlp", "conv", "einsum"), default="mlp")
+    ap.add_argument("--skip-proof", action="store_true", help="einsum: leave the create_proof pair out")
     ap.add_argument("--tag", default="synth")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--base", type=int, default=None, help="decomposition base (default: the bench's 16384)")
@@ -41,6 +50,8 @@ def main():
     import ezkl_amd
     from ezkl_amd import backend as B, ezkl_layout as EL, witness_plan as WP
     ezkl_amd.init()
+    if a.circuit == "einsum":
+        return einsum(a)
     if a.circuit == "conv":
         circuit = EL.ConvMnistCircuit(logrows=a.k, seed=a.seed)
         img = np.random.default_rng(a.seed).integers(0, 16, (28, 28))        # MNIST pixels / 16, as tools/bench_circuits.py kind="conv" draws them
@@ -106,6 +117,100 @@ def main():
     dst = os.path.join(ROOT, "profiles", "%s_synth.json" % a.tag)
     doc = json.load(open(dst)) if os.path.exists(dst) else {}
     doc[("k%d" if a.circuit == "mlp" else "conv_k%d") % a.k] = out
+    json.dump(doc, open(dst, "w"), indent=1, sort_keys=True)
+    print(json.dumps(out))
+
+
+EINSUM_LEN = {20: 512, 17: 180, 14: 64, 12: 30, 10: 14}
+EINSUM_CHALLENGES = [0x1234567890abcdef1234567890abcdef1234567890abcdef1234567890abcdef, 0x0fedcba0987654321fedcba0987654321fedcba0987654321fedcba098765432]
+
+
+def einsum(a):
+    from ezkl_amd import backend as B, ezkl_layout as EL, native as NV, witness_plan as WP
+    k, L = a.k, EINSUM_LEN[a.k]
+    n = 1 << k
+    circuit = EL.EinsumMatmulCircuit(k, L)
+    rng = np.random.default_rng(a.seed)
+    ma, mb = rng.integers(-128, 128, (L, L)), rng.integers(-128, 128, (L, L))        # as tools/bench_circuits.py kind="einsum" draws them
+    x = [int(v) for v in ma.reshape(-1)] + [int(v) for v in mb.reshape(-1)]
+    n_adv = len(circuit.cs.advice)
+    chal = [c % EL.R for c in EINSUM_CHALLENGES]
+    out = dict(k=k, circuit="accum_einsum_matmul ij,jk->ik len %d, Freivalds" % L, advice_columns=n_adv)
+    fn = circuit.advice_fn(ma, mb, n_adv)
+    def host_fn(phase, challenges):
+        cols = fn(phase, challenges)
+        idx = sorted(cols)
+        return dict(zip(idx, EL.cols_to_mont([cols[i] for i in idx], B)))
+    host = None
+    if not a.skip_host:
+        t = time.perf_counter()
+        p0 = fn(0, [])
+        t1 = time.perf_counter()
+        p1 = fn(1, chal)
+        t2 = time.perf_counter()
+        cols = {**p0, **p1}
+        host = EL.cols_to_mont([cols[i] for i in range(n_adv)], B)
+        B.synchronize()
+        t3 = time.perf_counter()
+        out.update(host_phase0_s=round(t1 - t, 3), host_phase1_s=round(t2 - t1, 3), host_cols_to_mont_s=round(t3 - t2, 3), host_s=round(t3 - t, 3))
+        print("k=%d host: advice_fn phase 0 %.3f s + phase 1 %.3f s + cols_to_mont %.3f s" % (k, t1 - t, t2 - t1, t3 - t2), flush=True)
+    t = time.perf_counter()
+    plan = WP.record_plan(circuit)
+    out["record_plan_s"] = round(time.perf_counter() - t, 3)
+    blob = plan.to_bytes()
+    t = time.perf_counter()
+    dev = B.WitnessPlan(blob)
+    out.update(plan_bytes=len(blob), records=plan.n_records, cells=plan.n_cells, plan_upload_s=round(time.perf_counter() - t, 3))
+    cols = dev.alloc_columns()
+    ms = {0: [], 1: []}
+    launches = written = 0
+    for it in range(a.repeat + 1):
+        for phase in (0, 1):
+            dev.run(x, columns=cols, phase=phase, challenges=chal if phase else ())
+            ms[phase].append(dev.last["device_ms"])
+            if it == 0:
+                launches += dev.last["launches"]
+                written += dev.last["cells_written"]
+        if it == 0:
+            assert written == plan.n_cells
+            if host is not None:                 # the run that is timed computes what the host computes
+                for c, r in zip(cols, host):
+                    assert c.to_numpy(shape=(n, 4)).tobytes() == np.ascontiguousarray(r).tobytes()
+                out["columns_equal_host"] = True
+    for phase in (0, 1):
+        out.update({"device_phase%d_first_ms" % phase: round(ms[phase][0], 4), "device_phase%d_ms_min" % phase: round(min(ms[phase][1:]), 4),
+                    "device_phase%d_ms_median" % phase: round(float(np.median(ms[phase][1:])), 4)})
+    out.update(launches=launches, cells_written=written, repeat=a.repeat,
+               device_ms_min=round(min(ms[0][1:]) + min(ms[1][1:]), 4), device_ms_median=round(float(np.median(ms[0][1:]) + np.median(ms[1][1:])), 4))
+    print("k=%d device: phase 0 %.3f ms + phase 1 %.3f ms (median of %d; first %.3f + %.3f ms); %d launches for %d records; plan %d bytes, %d cells"
+          % (k, out["device_phase0_ms_median"], out["device_phase1_ms_median"], a.repeat, ms[0][0], ms[1][0], launches, plan.n_records, len(blob), plan.n_cells), flush=True)
+    if not a.skip_proof:
+        t = time.perf_counter()
+        cs, fixed, copies, rows = circuit.keygen_inputs(ma, mb)
+        bg, bgl = B.gen_srs(k, 0x5eed)
+        pk = NV.NativeProvingKey(NV.NativeCircuit(cs), bg, EL.cols_to_mont(fixed, B), copies)
+        out["keygen_s"] = round(time.perf_counter() - t, 3)
+        NV.create_proof(pk, bg, bgl, dev.advice_fn(x, cols), seed=7, device_columns=range(n_adv))          # warm: the sweep kernel, the tables
+        t = time.perf_counter()
+        got = NV.create_proof(pk, bg, bgl, dev.advice_fn(x, cols), seed=7, device_columns=range(n_adv))
+        out["create_proof_device_s"] = round(time.perf_counter() - t, 4)
+        out["create_proof_device_witness_ms"] = round(sum(dev.phase_ms.values()), 4)
+        if not a.skip_host:
+            t = time.perf_counter()
+            ref = NV.create_proof(pk, bg, bgl, host_fn, seed=7)
+            out["create_proof_host_s"] = round(time.perf_counter() - t, 4)
+            assert got == ref, "the proof from the device callable differs from the host callable's"
+            out["proof_bytes_equal"] = True
+        print("k=%d create_proof: device callable %.4f s%s" % (k, out["create_proof_device_s"],
+              ", host callable %.4f s, same bytes" % out["create_proof_host_s"] if "create_proof_host_s" in out else ""), flush=True)
+        bg.free(); bgl.free()
+    for c in cols:
+        c.free()
+    dev.free()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    dst = os.path.join(ROOT, "profiles", "%s_synth.json" % a.tag)
+    doc = json.load(open(dst)) if os.path.exists(dst) else {}
+    doc["einsum_k%d" % k] = out
     json.dump(doc, open(dst, "w"), indent=1, sort_keys=True)
     print(json.dumps(out))
 
