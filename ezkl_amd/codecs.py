@@ -30,12 +30,31 @@ from . import backend as _b
 def read_srs(buf):
     k = struct.unpack_from("<I", buf, 0)[0]
     n = 1 << k
-    if len(buf) != 4 + 128 * n + 256:
+    if len(buf) != _srs_len(k):
         raise ValueError("SRS length %d does not match k=%d" % (len(buf), k))
     g = np.frombuffer(buf, np.uint64, 8 * n, 4).reshape(n, 8)
     gl = np.frombuffer(buf, np.uint64, 8 * n, 4 + 64 * n).reshape(n, 8)
     off = 4 + 128 * n
     return dict(k=k, g=g, g_lagrange=gl, g2=bytes(buf[off:off + 128]), s_g2=bytes(buf[off + 128:off + 256]))
+
+
+def _srs_len(k):
+    return 4 + 128 * (1 << k) + 256
+
+
+def read_srs_g2(path):
+    """(g2, s_g2) of an SRS FILE without reading its G1 sets: the header for k, the length check of read_srs, the last 256 bytes -- all
+    a verifier needs of a file that is 128 MB at k = 20"""
+    import os
+    with open(path, "rb") as f:
+        head = f.read(4)
+        size = f.seek(0, os.SEEK_END)
+        k = struct.unpack("<I", head)[0] if len(head) == 4 else 32
+        if k >= 32 or size != _srs_len(k):
+            raise ValueError("SRS length %d does not match k=%d" % (size, k))
+        f.seek(size - 256)
+        tail = f.read(256)
+    return tail[:128], tail[128:]
 
 
 def write_srs(srs):

@@ -326,17 +326,30 @@ def _plan_for(circuit, pk_path):
     return WP.record_plan(circuit).to_bytes()
 
 
-def _device_witness(circuit, pk_path, x, mode):
-    """synthesis on the device (backend.WitnessPlan): -> (resident advice columns, instance column, the run's counters), or None when
-    mode is "auto" and the device path is not to be taken: the gate is closed (ezkl_amd.enabled), there is no device, or the inputs do
-    not fit int64, or the recorder refuses the circuit (WP.PlanError).  mode "device" raises instead."""
+def _read_witness(circuit, witness_path, synthesis, parsed=None):
+    """the GraphWitness file checked against the circuit, before anything is loaded for it: -> (the parsed file, the inputs as signed
+    integers).  synthesis "device" refuses here an input the plan's int64 lanes cannot hold."""
+    w = parsed if parsed is not None else codecs.read_witness_json(open(witness_path).read())
+    if len(w["inputs"]) != 1 or len(w["inputs"][0]) != circuit.n_inputs:
+        raise ValueError("witness does not match the circuit's input shape")
+    signed = lambda v: v if v < EL.R // 2 else v - EL.R
+    x = [signed(v) for v in w["inputs"][0]]
+    if synthesis == "device" and any(not -(1 << 63) <= v < 1 << 63 for v in x):
+        raise ValueError("synthesis=\"device\": an input does not fit int64")
+    return w, x
+
+
+def _open_plan(circuit, pk_path, mode):
+    """the witness plan on the device (backend.WitnessPlan), validated and uploaded, or None when mode is "auto" and the device path
+    is not to be taken: the gate is closed (ezkl_amd.enabled), there is no device, or the recorder refuses the circuit (WP.PlanError).
+    mode "device" raises instead."""
     import ezkl_amd
     forced = mode == "device"
     if not forced and not ezkl_amd.enabled(circuit.k):
         return None
-    if any(not -(1 << 63) <= v < 1 << 63 for v in x) or len(circuit.gc.cs.advice) > 64:
+    if len(circuit.gc.cs.advice) > 64:
         if forced:
-            raise ValueError("synthesis=\"device\": an input does not fit int64, or the circuit has more than 64 advice columns")
+            raise ValueError("synthesis=\"device\": the circuit has more than 64 advice columns")
         return None
     try:
         blob = _plan_for(circuit, pk_path)
@@ -345,16 +358,170 @@ def _device_witness(circuit, pk_path, x, mode):
             raise
         return None
     try:
-        dev = B.WitnessPlan(blob)
+        return B.WitnessPlan(blob)
     except ezkl_amd.EzklHipError as e:
         if forced or e.code != -1:                       # EZKL_ERR_NO_DEVICE: the host path, as before
             raise
+        return None
+
+
+def _device_witness(circuit, pk_path, x, mode):
+    """one synthesis on the device outside a session: -> (resident advice columns, instance column, the run's counters), or None when
+    mode is "auto" and the device path is not to be taken (_open_plan, or an input that does not fit int64).  mode "device" raises
+    instead."""
+    if any(not -(1 << 63) <= v < 1 << 63 for v in x):
+        if mode == "device":
+            raise ValueError("synthesis=\"device\": an input does not fit int64")
+        return None
+    dev = _open_plan(circuit, pk_path, mode)
+    if dev is None:
         return None
     try:
         cols, outs = dev.run(x)
         return cols, [outs], dev.last
     finally:
         dev.free()
+
+
+class Prover:
+    """A proving session: everything `prove` needs that does not depend on the witness is loaded ONCE and stays resident until close() --
+    the circuit and its constraint system (rebuilt from the key's selector rows, _plonk_cs), the proving key (NativeProvingKey.from_file),
+    both base sets (an SRS file larger than the circuit is downsized on the device and the two sets downsize returns are kept as they
+    are), g2 / s_g2, and -- where the witness is made on the device -- the witness plan with ONE set of advice columns that every proof
+    writes again.  A proof is then the plan's replay plus create_proof.
+
+        with Prover(compiled_circuit, pk_path, srs_path) as p:
+            for w in witness_files:
+                proof = p.prove(w, w + ".proof.json")
+
+    recommit / synthesis: as for `prove` below (the plan rules are the same: "host" opens no plan, "device" raises where the plan cannot
+    be had, "auto" takes it when the GPU gate is open and falls back to the host layout otherwise).
+    .opened: the load stages and their wall seconds.  A witness the device refuses (backend.WitnessError) or whose outputs disagree with
+    the circuit's raises and leaves the session as it was: the next prove() runs on the same buffers."""
+
+    def __init__(self, compiled_circuit, pk_path, srs_path, recommit=False, synthesis="auto", _circuit=None):
+        import time
+        if synthesis not in ("auto", "host", "device"):
+            raise ValueError("synthesis must be \"auto\", \"host\" or \"device\"")
+        self.synthesis, self.opened = synthesis, {}
+        self.circuit = self.native = self.pk = self.bg = self.bgl = self.plan = self.g2 = self.s_g2 = None
+        self._cols, self._open = [], False
+        def stage(name, t0):
+            self.opened[name] = self.opened.get(name, 0.0) + time.perf_counter() - t0
+            return time.perf_counter()
+        try:
+            t = time.perf_counter()
+            self.circuit = _circuit if _circuit is not None else _load_circuit(compiled_circuit)[0]      # (`prove` has loaded it already)
+            t = stage("circuit", t)
+            self.native = NV.NativeCircuit(_plonk_cs(self.circuit, pk_path))
+            t = stage("constraint_system", t)
+            srs = codecs.read_srs(open(srs_path, "rb").read())
+            k = self.circuit.k
+            if srs["k"] < k:
+                raise ValueError("SRS too small: k=%d < logrows=%d" % (srs["k"], k))
+            self.g2, self.s_g2 = srs["g2"], srs["s_g2"]
+            t = stage("srs_read", t)
+            if srs["k"] > k:                                     # load_params_prover's downsize, its two resident sets kept
+                big = B.Bases(np.ascontiguousarray(srs["g"][:1 << k]))
+                try:
+                    self.bg, self.bgl = big.downsize(k)
+                finally:
+                    big.free()
+            else:
+                self.bg = B.Bases(srs["g"])
+                self.bgl = B.Bases(srs["g_lagrange"])
+            del srs
+            self.bg.prepare(); self.bgl.prepare()                # the window tables build while the key is read
+            t = stage("srs_to_device", t)
+            # recommit: the key file's commitments were made under ANOTHER SRS (the reference's fixture key: the public powers of tau)
+            self.pk = NV.NativeProvingKey.from_file(self.native, pk_path, recommit=self.bg if recommit else None)
+            t = stage("key", t)
+            if synthesis != "host":
+                self.plan = _open_plan(self.circuit, pk_path, synthesis)
+                if self.plan is not None:
+                    for _ in range(self.plan.n_advice):
+                        self._cols.append(B.DeviceBuffer(32 << self.plan.k))
+            t = stage("plan", t)
+        except BaseException:
+            self._free()
+            raise
+        self._open = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _free(self):
+        for c in self._cols:
+            c.free()
+        self._cols = []
+        for name in ("plan", "pk", "bg", "bgl", "native"):
+            h = getattr(self, name)
+            if h is not None:
+                h.free()
+            setattr(self, name, None)
+        self.circuit = self.g2 = self.s_g2 = None
+
+    def close(self):
+        """free everything the session holds (device and host); a later prove() raises.  Closing twice is harmless."""
+        self._open = False
+        self._free()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def prove(self, witness_path, proof_path=None, check_mode=CheckMode.UNSAFE, seed=0, report=None, _witness=None):
+        """one proof of this session's circuit: GraphWitness file -> proof bytes (written as proof.json to proof_path when one is given).
+        seed, check_mode and what report receives are `prove`'s below; report["stages"] adds the wall seconds of each stage of this call
+        (witness_read, synthesis, [host_columns,] create_proof, [proof_write]) and report["create_proof_breakdown"] the prover's own
+        split of create_proof."""
+        import time
+        if not self._open:
+            raise RuntimeError("this Prover is closed")
+        stages = {}
+        t = time.perf_counter()
+        def stage(name):
+            nonlocal t
+            now = time.perf_counter()
+            stages[name] = now - t
+            t = now
+        circuit = self.circuit
+        w, x = _witness if _witness is not None else _read_witness(circuit, witness_path, self.synthesis)      # (`prove` has read it already)
+        stage("witness_read")
+        on_device = self.plan is not None and all(-(1 << 63) <= v < 1 << 63 for v in x)      # "auto": wider inputs take the host layout
+        if on_device:
+            _, outs = self.plan.run(x, columns=self._cols)                      # into the session's columns, whatever they held
+            adv, inst = self._cols, [outs]
+            how = dict(self.plan.last, path="device")
+        else:
+            adv, inst = circuit.witness(x)                                      # GraphCircuit::synthesize
+            how = dict(path="host")
+        stage("synthesis")
+        if report is not None:
+            report.clear()
+            report.update(how)
+            report["stages"] = stages
+        if w["outputs"] and inst != w["outputs"]:
+            raise ValueError("the witness file's outputs do not match the circuit's outputs")
+        if not on_device:
+            adv = EL.cols_to_mont(adv, B)
+            stage("host_columns")
+        tm = {}
+        proof = NV.create_proof(self.pk, self.bg, self.bgl, adv, seed=seed, instances=inst, check_mode=check_mode, g2=self.g2, s_g2=self.s_g2,
+                                timings=tm)
+        stage("create_proof")
+        if report is not None:
+            report["create_proof_breakdown"] = tm
+        if proof_path is not None:
+            open(proof_path, "w").write(codecs.write_proof_json(proof, inst))
+            stage("proof_write")
+        return proof
 
 
 def prove(witness_path, compiled_circuit, pk_path, proof_path, srs_path, check_mode=CheckMode.UNSAFE, seed=0, recommit=False, synthesis="auto",
@@ -365,85 +532,105 @@ def prove(witness_path, compiled_circuit, pk_path, proof_path, srs_path, check_m
     "device": the witness plan replayed by HIP kernels into resident columns that create_proof takes as they are (raises if that cannot
     be done); "auto": the device when the GPU gate is open (ezkl_amd.enabled(k)) and a device is there, else the host.  The proof bytes
     are the same either way.  report (a dict, may be None) receives how the witness was made: {"path": "host"} or {"path": "device",
-    "cells_written", "launches", "device_ms", ...} -- the counters of backend.WitnessPlan.run."""
+    "cells_written", "launches", "device_ms", ...} -- the counters of backend.WitnessPlan.run.
+    One proof per call: a Prover session opened, used once and closed.  Whoever proves more than once keeps the Prover."""
     if synthesis not in ("auto", "host", "device"):
         raise ValueError("synthesis must be \"auto\", \"host\" or \"device\"")
-    w = codecs.read_witness_json(open(witness_path).read())
-    circuit, j = _load_circuit(compiled_circuit)
-    if len(w["inputs"]) != 1 or len(w["inputs"][0]) != circuit.n_inputs:
-        raise ValueError("witness does not match the circuit's input shape")
-    signed = lambda v: v if v < EL.R // 2 else v - EL.R
-    cs = circuit.gc.cs
-    x = [signed(v) for v in w["inputs"][0]]
-    made = _device_witness(circuit, pk_path, x, synthesis) if synthesis != "host" else None
-    if made is None:
-        adv, inst = circuit.witness(x)                                          # GraphCircuit::synthesize
-        how = dict(path="host")
-    else:
-        adv, inst, counters = made                                              # the same columns, already on the device
-        how = dict(counters, path="device")
-    if report is not None:
-        report.clear()
-        report.update(how)
-    resident = adv if made is not None else []                                  # DeviceBuffers to give back, whatever happens below
+    # the witness is read and checked against the circuit first, as ever: a file that does not fit is refused before the SRS, the key
+    # and the plan are loaded for it
+    parsed = codecs.read_witness_json(open(witness_path).read())
+    circuit, _ = _load_circuit(compiled_circuit)
+    witness = _read_witness(circuit, witness_path, synthesis, parsed)
+    how = {} if report is not None else None
     try:
-        if w["outputs"] and inst != w["outputs"]:
-            raise ValueError("the witness file's outputs do not match the circuit's outputs")
-        ncs = _plonk_cs(circuit)
-        srs = load_params_prover(srs_path, circuit.k)                           # downsizes an SRS file larger than the circuit
-        bg, bgl = B.Bases(srs["g"]), B.Bases(srs["g_lagrange"])
-        try:
-            # recommit: the key file's commitments were made under ANOTHER SRS (the reference's fixture key: the public powers of tau)
-            pk = NV.NativeProvingKey.from_bytes(NV.NativeCircuit(ncs), open(pk_path, "rb").read(), recommit=bg if recommit else None)
-            proof = NV.create_proof(pk, bg, bgl, adv if made is not None else EL.cols_to_mont(adv, B), seed=seed, instances=inst,
-                                    check_mode=check_mode, g2=srs["g2"], s_g2=srs["s_g2"])
-        finally:
-            bg.free(); bgl.free()
+        with Prover(compiled_circuit, pk_path, srs_path, recommit=recommit, synthesis=synthesis, _circuit=circuit) as session:
+            return session.prove(witness_path, proof_path, check_mode=check_mode, seed=seed, report=how, _witness=witness)
     finally:
-        for c in resident:
-            c.free()
-    open(proof_path, "w").write(codecs.write_proof_json(proof, inst))
-    return proof
+        if how:                                                                 # what it always held, from the moment the witness is made; the
+            report.clear()                                                      # session's timings stay with the session
+            report.update({a: b for a, b in how.items() if a not in ("stages", "create_proof_breakdown")})
 
 
 def verify(proof_path, compiled_circuit, vk_path=None, srs_path=None, recommit=False, pk_path=None):
     """-> True / False, from the proof, the compiled circuit (settings), vk.key and the SRS's g2 / s_g2 -- what the reference's `verify`
-    reads (src/execute.rs:1651).  Host only: no GPU, no proving key, none of the prover's private weights.  A pk.key path works too (vk.key
-    is its prefix).  recommit=True (a key whose commitments were made under another SRS, re-committed by `prove`) needs the proving key and
-    a device: the fixed / permutation polynomials are committed again under this SRS first."""
+    reads (src/execute.rs:1651).  Host only: no GPU, no proving key, none of the prover's private weights, and no layout of the circuit:
+    the constraint system is rebuilt from the key's own selector rows (_plonk_cs).  A pk.key path works too (vk.key is its prefix, and only
+    that prefix is read).  recommit=True (a key whose commitments were made under another SRS, re-committed by `prove`) needs the proving
+    key and a device: the fixed / permutation polynomials are committed again under this SRS first."""
     if vk_path is None:
         vk_path = pk_path                                                       # the parameter's former name (ADVICE r03): keyword callers keep working
     if vk_path is None or srs_path is None:
         raise TypeError("verify needs a vk.key (or pk.key) path and an SRS path")
     circuit, j = _load_circuit(compiled_circuit)
     pr = codecs.read_proof_json(open(proof_path).read())
-    srs = codecs.read_srs(open(srs_path, "rb").read())
-    if recommit:
-        cs_ = _plonk_cs(circuit)
-        # the exact length of a vk.key of this constraint system (codecs.py): header, the fixed + permutation commitments AND the bit-packed
-        # selector rows (80 selectors at k = 20 are 10 MB: ADVICE r04 -- a bound without them let a vk-only file through to a later,
-        # misleading "proving key truncated")
-        vk_len = 7 + 64 * (cs_.n_fixed + len(cs_.perm)) + cs_.n_selectors * (((1 << cs_.k) + 7) // 8)
-        if os.path.getsize(vk_path) <= vk_len:                                  # a vk-only file has no polynomials to commit again
-            raise ValueError("recommit=True needs the PROVING key file (its polynomials are committed again under this SRS); %s is a verifying key" % vk_path)
+    cs_, vk_bytes = _key_system(circuit, vk_path)
     if not recommit:
-        return NV.verify_proof_vk(NV.NativeCircuit(_plonk_cs(circuit)), open(vk_path, "rb").read(), srs["g2"], srs["s_g2"], pr["proof"], pr["instances"])
+        g2, s_g2 = codecs.read_srs_g2(srs_path)
+        return NV.verify_proof_vk(NV.NativeCircuit(cs_), vk_bytes, g2, s_g2, pr["proof"], pr["instances"])
+    # len(vk_bytes) is the exact length of a vk.key of this constraint system (codecs.py): header, the fixed + permutation commitments AND
+    # the bit-packed selector rows (80 selectors at k = 20 are 10 MB: ADVICE r04 -- a bound without them let a vk-only file through to a
+    # later, misleading "proving key truncated")
+    if os.path.getsize(vk_path) <= len(vk_bytes):                               # a vk-only file has no polynomials to commit again
+        raise ValueError("recommit=True needs the PROVING key file (its polynomials are committed again under this SRS); %s is a verifying key" % vk_path)
+    srs = codecs.read_srs(open(srs_path, "rb").read())
     bg = B.Bases(srs["g"])
     try:
-        pk = NV.NativeProvingKey.from_bytes(NV.NativeCircuit(_plonk_cs(circuit)), open(vk_path, "rb").read(), recommit=bg)
+        pk = NV.NativeProvingKey.from_file(NV.NativeCircuit(cs_), vk_path, recommit=bg)
         return NV.verify_proof(pk, srs["g2"], srs["s_g2"], pr["proof"], pr["instances"])
     finally:
         bg.free()
 
 
-def _plonk_cs(circuit):
-    """the constraint system as keygen saw it: re-running `configure` + selector compression (halo2 does the same on load_pk,
-    src/pfsys/mod.rs:627) -- a fresh synthesis pass without witness values gives the selector activations"""
-    return _fresh_keygen_inputs(circuit)[0]
+def _key_system(circuit, key):
+    """(the constraint system as keygen saw it, the key's vk.key bytes), WITHOUT laying the circuit out: halo2's key file carries every
+    selector's rows bit-packed (vk.key, which pk.key starts with), and `configure` + selector compression on those rows is what halo2 itself
+    does on load_pk (src/pfsys/mod.rs:627).  key: a path or the bytes.  Of a file only the vk prefix is read -- a pk.key is GiBs at k = 20.
+    The permutation-column and selector counts are the configured system's, the fixed-column count is the file's; a key whose header or
+    whose count of fixed columns after compression says it was made for another circuit is a ValueError, one too short for its
+    selector section the loader's own RuntimeError."""
+    import struct
+    fresh = EL.MlpCircuit(circuit.k, circuit.w, circuit.weights, circuit.biases, circuit.base, circuit.legs,
+                          total_assignments=circuit.settings.total_assignments, relu_last=circuit.relu_last, n_inputs=circuit.n_inputs,
+                          relu_first=circuit.relu_first)                       # compress_selectors rewrites the system in place: a fresh one
+    cs0 = fresh.gc.cs
+    n_perm, n_sel = len(cs0.permutation), len(cs0.selectors)
+    def vk_len(head):
+        if len(head) < 7:
+            raise RuntimeError("verifying key truncated: %d bytes" % len(head))
+        if head[0] != 3:
+            raise ValueError("unsupported key version %d" % head[0])
+        if head[1] != circuit.k:
+            raise ValueError("the key does not belong to this circuit: it was made for k = %d, the circuit has k = %d" % (head[1], circuit.k))
+        return 7 + 64 * (struct.unpack_from("<I", head, 3)[0] + n_perm) + n_sel * (((1 << circuit.k) + 7) // 8)
+    if isinstance(key, (bytes, bytearray, memoryview)):
+        want = vk_len(bytes(key[:7]))
+        raw = bytes(key[:want])
+    else:
+        with open(key, "rb") as f:
+            head = f.read(7)
+            want = vk_len(head)
+            raw = head + f.read(want - 7)
+    if len(raw) < want:
+        raise RuntimeError("verifying key truncated (selector section): %d bytes of %d" % (len(raw), want))
+    vk = codecs.read_vk(raw, n_perm, n_sel)
+    cs0.compress_selectors(list(vk["selectors"]))
+    cs = cs0.to_plonk(circuit.k)
+    if cs.n_fixed != vk["fixed_commitments"].shape[0]:
+        raise ValueError("the key does not belong to this circuit: it commits to %d fixed columns, the circuit's selector rows in it compress to %d"
+                         % (vk["fixed_commitments"].shape[0], cs.n_fixed))
+    return cs, raw
+
+
+def _plonk_cs(circuit, key=None):
+    """the constraint system as keygen saw it, from the key (a path or bytes) and the configured circuit: see _key_system.  Without a
+    key (`mock` has none) the selector activations come from a fresh layout pass, as long as the host synthesis is."""
+    if key is None:
+        return _fresh_keygen_inputs(circuit)[0]
+    return _key_system(circuit, key)[0]
 
 
 def _fresh_keygen_inputs(circuit):
-    """(cs, fixed, copies, region) of a fresh synthesis pass without witness values: what keygen saw"""
+    """(cs, fixed, copies, region) of a fresh synthesis pass without witness values: what keygen saw (`mock`, which has no key)"""
     fresh = EL.MlpCircuit(circuit.k, circuit.w, circuit.weights, circuit.biases, circuit.base, circuit.legs,
                           total_assignments=circuit.settings.total_assignments, relu_last=circuit.relu_last, n_inputs=circuit.n_inputs,
                           relu_first=circuit.relu_first)

@@ -10,7 +10,7 @@ ASAN_LIB=$(gcc -print-file-name=libasan.so)
 UBSAN_LIB=$(gcc -print-file-name=libubsan.so)
 ARGS=("$@")
 if [ ${#ARGS[@]} -eq 0 ]; then
-  ARGS=(tests/test_native_prover.py tests/test_execute.py tests/test_gen_witness.py tests/test_bench_cache.py tests/test_contexts_cpu.py tests/test_capi.py tests/test_witness_plan_cpu.py tests/test_witness_plan_lookup_cpu.py tests/test_witness_plan_phases_cpu.py -m "not gpu")
+  ARGS=(tests/test_native_prover.py tests/test_execute.py tests/test_gen_witness.py tests/test_bench_cache.py tests/test_contexts_cpu.py tests/test_capi.py tests/test_witness_plan_cpu.py tests/test_witness_plan_lookup_cpu.py tests/test_witness_plan_phases_cpu.py tests/test_structure_from_key.py -m "not gpu")
 fi
 cd "$R"
 LD_PRELOAD="$ASAN_LIB:$UBSAN_LIB" ASAN_OPTIONS=detect_leaks=0:abort_on_error=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
