@@ -914,15 +914,12 @@ class WitnessPlan:
             rc = L.ezkl_hip_witness_run_phase_dev(self.h, C.c_uint32(phase), _p(x), C.c_size_t(len(x)), ch, C.c_size_t(len(ch) // 32), ptrs, _p(outs), status,
                                                   _stream_ptr(stream))
         self.last = dict(failed=int(status[0]), first=(int(status[1]) >> 32, int(status[1]) & 0xffffffff), cells_written=int(status[2]), launches=int(status[3]))
-        if rc == -3 and status[0]:
-            if columns is None:
-                for c in cols:
-                    c.free()
-            raise WitnessError(L.ezkl_hip_witness_last_error().decode())
         if rc == -3:
             if columns is None:
                 for c in cols:
                     c.free()
+            if status[0]:                            # a lane reported: the witness is refused, not the call
+                raise WitnessError(L.ezkl_hip_witness_last_error().decode())
             raise ValueError(L.ezkl_hip_witness_last_error().decode() or "ezkl_hip_witness_run_dev: invalid argument")
         _l.check(rc, "ezkl_hip_witness_run_dev")
         self.last["device_ms"] = last_kernel_ms("witness")

@@ -30,26 +30,41 @@ class CheckMode:
     SAFE, UNSAFE = "SAFE", "UNSAFE"
 
 
-def _load_circuit(path):
-    """the reference's own `model.compiled` (bincode of GraphCircuit, codecs.read_compiled_circuit) or this package's JSON description"""
+def _read_compiled(path, any_visibility=False):
+    """the reference's own `model.compiled` (bincode of GraphCircuit, codecs.read_compiled_circuit) or this package's JSON description
+    -> (what it says of the op family, as plain data; the parsed file).  settings: the file's GraphSettings (the JSON description has
+    none); any_visibility: see _mlp_of_graph."""
     raw = open(path, "rb").read()
     if raw[:1] == b"{":
         j = json.loads(raw)
         if j.get("model") != "mlp":
             raise ValueError("unsupported compiled circuit: %r" % j.get("model"))
-        ra = j["run_args"]
-        return EL.MlpCircuit(ra["logrows"], ra["num_inner_cols"], j["weights"], j["biases"], ra["decomp_base"], ra["decomp_legs"],
-                             total_assignments=j.get("total_assignments"), relu_last=j.get("relu_last", True),
-                             n_inputs=j.get("n_inputs"), relu_first=j.get("relu_first", False)), j
+        ra, weights = j["run_args"], j["weights"]
+        scale = ra.get("input_scale", 0) if not weights else 0                      # a Gemm-free graph keeps its input scale (ezkl's default: 7)
+        return dict(weights=weights, biases=j["biases"], relu_last=j.get("relu_last", True), relu_first=j.get("relu_first", False),
+                    n_inputs=j.get("n_inputs", len(weights[0][0]) if weights else None), run_args=ra, settings=None,
+                    total_assignments=j.get("total_assignments"), in_scale=scale, out_scale=scale, datum_type="F32", input_decomp=True,
+                    visibility=dict(input=ra.get("input_visibility", "Private"), params=ra.get("param_visibility", "Private"),
+                                    output=ra.get("output_visibility", "Public"))), j
     c = codecs.read_compiled_circuit(raw)
-    weights, biases, relu_last, relu_first, n_inputs = _mlp_of_graph(c["model"])
-    st, ra = c["settings"], c["settings"]["run_args"]
-    want = [(-1, 1), (0, ra["decomp_base"] - 1)]
-    if [tuple(x) for x in st["required_range_checks"]] != want or st["required_lookups"] or st["num_dynamic_lookups"] or st["num_shuffles"] \
-            or st["einsum_params"]["equations"]:
-        raise ValueError("unsupported compiled circuit: its settings ask for arguments outside the MLP family")
-    return EL.MlpCircuit(ra["logrows"], ra["num_inner_cols"], weights, biases, ra["decomp_base"], ra["decomp_legs"],
-                         total_assignments=st["total_assignments"], relu_last=relu_last, n_inputs=n_inputs, relu_first=relu_first), c
+    weights, biases, relu_last, relu_first, n_inputs = _mlp_of_graph(c["model"], any_visibility)
+    st, in_op = c["settings"], c["model"]["nodes"][c["model"]["inputs"][0]]["opkind"]
+    return dict(weights=weights, biases=biases, relu_last=relu_last, relu_first=relu_first, n_inputs=n_inputs, run_args=st["run_args"], settings=st,
+                total_assignments=st["total_assignments"], in_scale=st["model_input_scales"][0], out_scale=st["model_output_scales"][0],
+                datum_type=in_op.get("datum_type", "F32"), input_decomp=in_op.get("decomp", True), visibility=c["model"]["visibility"]), c
+
+
+def _load_circuit(path):
+    """the compiled circuit (_read_compiled) as an MlpCircuit -> (circuit, the parsed file)"""
+    d, parsed = _read_compiled(path)
+    st, ra = d["settings"], d["run_args"]
+    if st is not None:
+        want = [(-1, 1), (0, ra["decomp_base"] - 1)]
+        if [tuple(x) for x in st["required_range_checks"]] != want or st["required_lookups"] or st["num_dynamic_lookups"] or st["num_shuffles"] \
+                or st["einsum_params"]["equations"]:
+            raise ValueError("unsupported compiled circuit: its settings ask for arguments outside the MLP family")
+    return EL.MlpCircuit(ra["logrows"], ra["num_inner_cols"], d["weights"], d["biases"], ra["decomp_base"], ra["decomp_legs"],
+                         total_assignments=d["total_assignments"], relu_last=d["relu_last"], n_inputs=d["n_inputs"], relu_first=d["relu_first"]), parsed
 
 
 def _mlp_of_graph(model, any_visibility=False):
@@ -63,13 +78,12 @@ def _mlp_of_graph(model, any_visibility=False):
     if len(model["inputs"]) != 1 or len(model["outputs"]) != 1 or \
             (not any_visibility and (vis["input"], vis["params"], vis["output"]) != ("Private", "Private", "Public")):
         raise ValueError("unsupported compiled circuit: visibility / arity")
-    signed = lambda v: v if v < EL.R // 2 else v - EL.R
     def const(idx, dims_ok):
         op = nodes[idx]["opkind"]
         if op["kind"] != "Constant" or not dims_ok(op["quantized_values"]["dims"]):
             raise ValueError("unsupported compiled circuit: node %d is not the expected constant" % idx)
         q = op["quantized_values"]
-        return [signed(v) for v in q["inner"]], q["dims"]
+        return [EL.signed(v) for v in q["inner"]], q["dims"]
     cur = model["inputs"][0]
     order = sorted(k for k in nodes if nodes[k]["opkind"]["kind"] == "Linear")
     gemm_free = all(nodes[k]["opkind"]["op"] == "LeakyReLU" for k in order)
@@ -133,24 +147,35 @@ def gen_srs(srs_path, logrows, secret=None):
     return len(data)
 
 
-def load_params_prover(srs_path, logrows):
-    """execute.rs:1739-1750: read the SRS and, if the file is larger than the circuit (the normal case with a shared kzg22.srs),
-    `params.downsize(logrows)`: the coefficient basis is truncated, the Lagrange basis of the smaller domain is rebuilt on the device by an
-    inverse NTT over G1 (ezkl_hip_bases_downsize = halo2's g_to_lagrange)"""
+def _read_srs(srs_path, logrows):
+    """the SRS file, parsed; one smaller than the circuit is refused"""
     srs = codecs.read_srs(open(srs_path, "rb").read())
     if srs["k"] < logrows:
         raise ValueError("SRS too small: k=%d < logrows=%d" % (srs["k"], logrows))
+    return srs
+
+
+def _downsized(srs, logrows):
+    """`params.downsize(logrows)` of an SRS larger than the circuit -> the two resident base sets (g, g_lagrange): the coefficient basis
+    is truncated, the Lagrange basis of the smaller domain is rebuilt on the device by an inverse NTT over G1 (ezkl_hip_bases_downsize =
+    halo2's g_to_lagrange)"""
+    big = B.Bases(np.ascontiguousarray(srs["g"][:1 << logrows]))
+    try:
+        return big.downsize(logrows)
+    finally:
+        big.free()
+
+
+def load_params_prover(srs_path, logrows):
+    """execute.rs:1739-1750: read the SRS and, if the file is larger than the circuit (the normal case with a shared kzg22.srs),
+    downsize it (_downsized); -> host arrays"""
+    srs = _read_srs(srs_path, logrows)
     if srs["k"] > logrows:
-        n = 1 << logrows
-        big = B.Bases(np.ascontiguousarray(srs["g"][:n]))
+        g, gl = _downsized(srs, logrows)
         try:
-            g, gl = big.downsize(logrows)
-            try:
-                srs = dict(k=logrows, g=g.download(), g_lagrange=gl.download(), g2=srs["g2"], s_g2=srs["s_g2"])
-            finally:
-                g.free(); gl.free()
+            srs = dict(k=logrows, g=g.download(), g_lagrange=gl.download(), g2=srs["g2"], s_g2=srs["s_g2"])
         finally:
-            big.free()
+            g.free(); gl.free()
     return srs
 
 
@@ -229,24 +254,10 @@ def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None
       blinding factors (here: any file at vk_path; the count is read off the constraint system);  without an SRS the processed value stays
       None, as in the reference ("SRS for poly commit does not exist (will be ignored)").  Hashed (Poseidon) visibility is refused.
     The statistics fields are what the reference's dummy layout reports for this family: no lookups (0, 0), max_range_size."""
-    raw = open(compiled_circuit, "rb").read()
-    if raw[:1] == b"{":
-        j = json.loads(raw)
-        if j.get("model") != "mlp":
-            raise ValueError("unsupported compiled circuit: %r" % j.get("model"))
-        ra = j["run_args"]
-        weights, biases, relu_last = j["weights"], j["biases"], j.get("relu_last", True)
-        relu_first, n_inputs = j.get("relu_first", False), j.get("n_inputs", len(weights[0][0]) if weights else None)
-        vis = dict(input=ra.get("input_visibility", "Private"), params=ra.get("param_visibility", "Private"), output=ra.get("output_visibility", "Public"))
-        in_scale = out_scale = ra.get("input_scale", 0) if not weights else 0       # a Gemm-free graph keeps its input scale (ezkl's default: 7)
-        datum_type, input_decomp = "F32", True
-    else:
-        c = codecs.read_compiled_circuit(raw)
-        weights, biases, relu_last, relu_first, n_inputs = _mlp_of_graph(c["model"], any_visibility=True)
-        ra, vis = c["settings"]["run_args"], c["model"]["visibility"]
-        in_node = c["model"]["nodes"][c["model"]["inputs"][0]]
-        in_scale, out_scale = c["settings"]["model_input_scales"][0], c["settings"]["model_output_scales"][0]
-        datum_type, input_decomp = in_node["opkind"].get("datum_type", "F32"), in_node["opkind"].get("decomp", True)
+    d, _ = _read_compiled(compiled_circuit, any_visibility=True)
+    weights, biases, relu_last, relu_first, n_inputs = d["weights"], d["biases"], d["relu_last"], d["relu_first"], d["n_inputs"]
+    ra, vis, in_scale, out_scale = d["run_args"], d["visibility"], d["in_scale"], d["out_scale"]
+    datum_type, input_decomp = d["datum_type"], d["input_decomp"]
     for what, v in vis.items():
         if isinstance(v, dict):
             raise ValueError("unsupported visibility: %s is Hashed (Poseidon modules are outside this package's scope)" % what)
@@ -259,8 +270,7 @@ def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None
     if len(cols) != 1 or len(cols[0]) != n_inputs:
         raise ValueError("input data does not match the circuit's input shape")
     x = [_quantize(v, in_scale, datum_type) for v in cols[0]]
-    signed = lambda v: v if v < EL.R // 2 else v - EL.R
-    x = [signed(v % EL.R) for v in x]
+    x = [EL.signed(v % EL.R) for v in x]
     limit = base ** legs
     ranged = False
     def decomposed(vals, where):
@@ -326,16 +336,22 @@ def _plan_for(circuit, pk_path):
     return WP.record_plan(circuit).to_bytes()
 
 
+def _fits_plan(x, mode):
+    """whether the plan's int64 lanes hold the inputs x; mode "device" raises where they do not ("auto" then takes the host layout)"""
+    fits = all(-(1 << 63) <= v < 1 << 63 for v in x)
+    if not fits and mode == "device":
+        raise ValueError("synthesis=\"device\": an input does not fit int64")
+    return fits
+
+
 def _read_witness(circuit, witness_path, synthesis, parsed=None):
     """the GraphWitness file checked against the circuit, before anything is loaded for it: -> (the parsed file, the inputs as signed
     integers).  synthesis "device" refuses here an input the plan's int64 lanes cannot hold."""
     w = parsed if parsed is not None else codecs.read_witness_json(open(witness_path).read())
     if len(w["inputs"]) != 1 or len(w["inputs"][0]) != circuit.n_inputs:
         raise ValueError("witness does not match the circuit's input shape")
-    signed = lambda v: v if v < EL.R // 2 else v - EL.R
-    x = [signed(v) for v in w["inputs"][0]]
-    if synthesis == "device" and any(not -(1 << 63) <= v < 1 << 63 for v in x):
-        raise ValueError("synthesis=\"device\": an input does not fit int64")
+    x = [EL.signed(v) for v in w["inputs"][0]]
+    _fits_plan(x, synthesis)
     return w, x
 
 
@@ -369,9 +385,7 @@ def _device_witness(circuit, pk_path, x, mode):
     """one synthesis on the device outside a session: -> (resident advice columns, instance column, the run's counters), or None when
     mode is "auto" and the device path is not to be taken (_open_plan, or an input that does not fit int64).  mode "device" raises
     instead."""
-    if any(not -(1 << 63) <= v < 1 << 63 for v in x):
-        if mode == "device":
-            raise ValueError("synthesis=\"device\": an input does not fit int64")
+    if not _fits_plan(x, mode):
         return None
     dev = _open_plan(circuit, pk_path, mode)
     if dev is None:
@@ -415,18 +429,12 @@ class Prover:
             t = stage("circuit", t)
             self.native = NV.NativeCircuit(_plonk_cs(self.circuit, pk_path))
             t = stage("constraint_system", t)
-            srs = codecs.read_srs(open(srs_path, "rb").read())
             k = self.circuit.k
-            if srs["k"] < k:
-                raise ValueError("SRS too small: k=%d < logrows=%d" % (srs["k"], k))
+            srs = _read_srs(srs_path, k)
             self.g2, self.s_g2 = srs["g2"], srs["s_g2"]
             t = stage("srs_read", t)
             if srs["k"] > k:                                     # load_params_prover's downsize, its two resident sets kept
-                big = B.Bases(np.ascontiguousarray(srs["g"][:1 << k]))
-                try:
-                    self.bg, self.bgl = big.downsize(k)
-                finally:
-                    big.free()
+                self.bg, self.bgl = _downsized(srs, k)
             else:
                 self.bg = B.Bases(srs["g"])
                 self.bgl = B.Bases(srs["g_lagrange"])
@@ -494,7 +502,7 @@ class Prover:
         circuit = self.circuit
         w, x = _witness if _witness is not None else _read_witness(circuit, witness_path, self.synthesis)      # (`prove` has read it already)
         stage("witness_read")
-        on_device = self.plan is not None and all(-(1 << 63) <= v < 1 << 63 for v in x)      # "auto": wider inputs take the host layout
+        on_device = self.plan is not None and _fits_plan(x, self.synthesis)                 # "auto": wider inputs take the host layout
         if on_device:
             _, outs = self.plan.run(x, columns=self._cols)                      # into the session's columns, whatever they held
             adv, inst = self._cols, [outs]
@@ -589,10 +597,7 @@ def _key_system(circuit, key):
     whose count of fixed columns after compression says it was made for another circuit is a ValueError, one too short for its
     selector section the loader's own RuntimeError."""
     import struct
-    fresh = EL.MlpCircuit(circuit.k, circuit.w, circuit.weights, circuit.biases, circuit.base, circuit.legs,
-                          total_assignments=circuit.settings.total_assignments, relu_last=circuit.relu_last, n_inputs=circuit.n_inputs,
-                          relu_first=circuit.relu_first)                       # compress_selectors rewrites the system in place: a fresh one
-    cs0 = fresh.gc.cs
+    cs0 = circuit.fresh().gc.cs                                                 # compress_selectors rewrites the system in place: a fresh one
     n_perm, n_sel = len(cs0.permutation), len(cs0.selectors)
     def vk_len(head):
         if len(head) < 7:
@@ -631,10 +636,7 @@ def _plonk_cs(circuit, key=None):
 
 def _fresh_keygen_inputs(circuit):
     """(cs, fixed, copies, region) of a fresh synthesis pass without witness values: what keygen saw (`mock`, which has no key)"""
-    fresh = EL.MlpCircuit(circuit.k, circuit.w, circuit.weights, circuit.biases, circuit.base, circuit.legs,
-                          total_assignments=circuit.settings.total_assignments, relu_last=circuit.relu_last, n_inputs=circuit.n_inputs,
-                          relu_first=circuit.relu_first)
-    return fresh.keygen_inputs([0] * circuit.n_inputs)
+    return circuit.fresh().keygen_inputs([0] * circuit.n_inputs)
 
 
 class MockError(ValueError):
@@ -658,10 +660,8 @@ def mock(witness_path, compiled_circuit):
     naming the first failures (gate / row, lookup / input / row, the two cells of a copy)."""
     w = codecs.read_witness_json(open(witness_path).read())
     circuit, j = _load_circuit(compiled_circuit)
-    if len(w["inputs"]) != 1 or len(w["inputs"][0]) != circuit.n_inputs:
-        raise ValueError("witness does not match the circuit's input shape")
-    signed = lambda v: v if v < EL.R // 2 else v - EL.R
-    adv, inst = circuit.witness([signed(v) for v in w["inputs"][0]])            # GraphCircuit::synthesize
+    w, x = _read_witness(circuit, witness_path, "host", w)
+    adv, inst = circuit.witness(x)                                              # GraphCircuit::synthesize
     public = [list(c) for c in w["outputs"]] if w["outputs"] else inst
     cs, fixed, copies, _ = _fresh_keygen_inputs(circuit)
     records, totals = NV.mock(cs, EL.cols_to_mont(fixed, B), copies, EL.cols_to_mont(adv, B), instances=public, seed=1, cap=MOCK_CAP)

@@ -24,6 +24,11 @@ from .halo2_cs import ConstraintSystem
 R = P.R
 
 
+def signed(v):
+    """a canonical field element as the signed integer it stands for"""
+    return v if v < R // 2 else v - R
+
+
 class Region:
     """cells, selector activations and copy constraints of one synthesis pass"""
 
@@ -664,20 +669,37 @@ class MlpCircuit(LayoutCircuit):
         m = len(self.weights[-1]) if self.weights else self.n_inputs
         return c + 2 * dec(m) + m + 64
 
-    def synthesize(self, x, witness=True):
-        reg = BaseRegion(self.gc, witness)
-        vals = [Val(int(v)) for v in x]
-        _, vals = reg.decompose(vals, self.base, self.legs)                     # input range check
+    def layout(self, reg, inputs, param):
+        """the op sequence, stated once: `synthesize` runs it on a BaseRegion with the input's values, witness_plan.record_plan on a
+        recording region with symbols.  inputs: the input vector as Vals; param(v) -> the Val of a circuit parameter (they are asked for
+        in a fixed order: per layer, each weight row, then the biases)"""
+        _, vals = reg.decompose(inputs, self.base, self.legs)                   # input range check
         if self.relu_first:
             vals = reg.relu(vals, self.base, self.legs)
         for i, (W, b) in enumerate(zip(self.weights, self.biases)):
-            outs = [reg.dot(vals, [Val(wv) for wv in row]) for row in W]           # einsum_with_base_ops: one dot per output
-            vals = reg.pairwise(outs, [Val(bv) for bv in b], EC.ADD)
+            outs = [reg.dot(vals, [param(wv) for wv in row]) for row in W]         # einsum_with_base_ops: one dot per output
+            vals = reg.pairwise(outs, [param(bv) for bv in b], EC.ADD)
             if i + 1 < len(self.weights) or self.relu_last:
                 vals = reg.relu(vals, self.base, self.legs)
         reg.output_equals_instance(vals, self.gc.instance, 0, self.base, self.legs)
+        return vals                                                              # the values the final equality is made on
+
+    def plan_identity(self):
+        """what a witness plan of this circuit depends on besides the layout code (witness_plan.params_hash)"""
+        shape = [self.k, self.w, self.base, self.legs, int(self.relu_last), int(self.relu_first), self.n_inputs, len(self.weights)]
+        per_layer = [a for W, b in zip(self.weights, self.biases) for a in ([len(W), len(W[0]), len(b)], W, b)]
+        return b"".join(np.asarray(a, np.int64).tobytes() for a in [shape] + per_layer)
+
+    def fresh(self):
+        """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
+        return MlpCircuit(self.k, self.w, self.weights, self.biases, self.base, self.legs, total_assignments=self.settings.total_assignments,
+                          relu_last=self.relu_last, n_inputs=self.n_inputs, relu_first=self.relu_first)
+
+    def synthesize(self, x, witness=True):
+        reg = BaseRegion(self.gc, witness)
+        outs = self.layout(reg, [Val(int(v)) for v in x], Val)
         reg.finish(self.gc.const_cols)
-        self.outputs = [v.v for v in vals]
+        self.outputs = [v.v for v in outs]
         return reg
 
 
@@ -867,7 +889,6 @@ class TransformerSurrogateCircuit:
     # ---- one unit ---------------------------------------------------------------------------------------------------------------------
     def _unit(self, witness=True):
         reg = BaseRegion(self.gc, witness)
-        signed = lambda v: v if v < R // 2 else v - R
         clamp = lambda v: max(-self.lookup_max, min(self.lookup_max, v))
         d = self.d
         _, x = reg.decompose([Val(v) for v in self.x], self.base, self.legs)                  # input range check

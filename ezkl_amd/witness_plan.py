@@ -1,13 +1,15 @@
 """Witness plans: the layout of an MlpCircuit, a ConvMnistCircuit or an EinsumMatmulCircuit recorded ONCE, replayed for every proof.
 
 Which advice cell holds which value depends only on the circuit (BaseRegion places cells from the linear coordinate, the duplicated rows
-of `dot` from the block geometry; constants, weights and biases are the same for every input), so `record_plan` runs one witness-free
-layout pass over a BaseRegion subclass whose VALUES are symbols: the placement code that runs is BaseRegion's own (cell_of, flush,
-_dup_inputs, the duplicate row at the top of a new column, every layouts.rs op as BaseRegion lays it out), and every `put` records how
-the cell it wrote is produced from earlier cells, a model input, a circuit parameter or a constant.  The cell writes are grouped into
-RECORDS -- one kernel launch each on the device (csrc/witness.hip) -- by data dependence: a write joins the latest record of its kind
-when everything it reads was written by an earlier record, so the 650 dot products of a layer are one record, not 650.  (A circuit that
-states its op sequence itself -- `layout`, see record_plan -- is grouped by dependence LEVEL: a write joins the EARLIEST record of its kind
+of `dot` from the block geometry; constants and the circuit's parameters are the same for every input), so `record_plan` runs one
+witness-free layout pass over a BaseRegion subclass whose VALUES are symbols: the op sequence that runs is the circuit's own, stated once
+(`layout`, which its `synthesize` runs on values; the einsum's `sequence`) -- no circuit's ops or parameters are spelt out in this module
+--, the placement code is BaseRegion's own (cell_of, flush, _dup_inputs, the duplicate row at the top of a new column, every layouts.rs
+op as BaseRegion lays it out), and every `put` records how the cell it wrote is produced from earlier cells, a model input, a circuit
+parameter or a constant.  The cell writes are grouped into RECORDS -- one kernel launch each on the device (csrc/witness.hip) -- by data
+dependence.  An MlpCircuit is recorded on a RecordingRegion: a write joins the latest record of its kind when everything it reads was
+written by an earlier record, so the 650 dot products of a layer are one record, not 650.  (Every other circuit with a `layout` is
+recorded on a LookupRecordingRegion and grouped by dependence LEVEL: a write joins the EARLIEST record of its kind
 that comes after every record it reads from.  A cell is written once and read only by writes later in program order, so no element
 of an existing record can depend on the cell that joins it.  The conv loop alternates dot and add and copies its patches from early
 cells: under the latest-fit rule every patch copy lands behind the previous dot and forces a new dot record, 1751 records for the conv +
@@ -18,7 +20,7 @@ The plan is a flat little-endian blob (`WitnessPlan.to_bytes`):
     header   20 x u32: magic "EZWP", version, k, n_advice, n_records, n_inputs, n_params, n_consts, n_outputs, n_cells, n_words, n_ops,
              n_tables, n_table_values, n_challenges, n_phases (0 reads as 1: a one-phase plan writes 0, the reserved word it was), 4 reserved
              (zero); then the 32-byte parameter hash
-    params   n_params  x int64        weights then biases (fixed at record time)
+    params   n_params  x int64        in the order the circuit's `layout` asks for them (fixed at record time)
     consts   n_consts  x 32 bytes     canonical field elements
     records  n_records x 8 u32        kind, count, p0, p1, dst, a, b, phase   (dst / a / b: word offsets into the pool)
     outputs  n_outputs x u32          the cells that hold the circuit's outputs
@@ -76,7 +78,6 @@ import struct
 
 import numpy as np
 
-from . import ezkl_circuit as EC
 from . import ezkl_layout as EL
 
 R = EL.R
@@ -605,69 +606,49 @@ def _record_einsum(circuit):
 
 
 def params_hash(circuit):
-    """what a plan depends on besides the layout code: the circuit's shape options and its parameters (for a circuit with `layout`: its
-    `plan_identity()` bytes and its static lookup tables)"""
+    """what a plan depends on besides the layout code: the circuit's `plan_identity()` bytes -- its shape options and its parameters -- and
+    its static lookup tables.  (The domain prefix is keyed on the circuit: none for an MlpCircuit, whose hashes stay what they were.)"""
     h = hashlib.sha256()
     if type(circuit) is EL.EinsumMatmulCircuit:
         h.update(b"phased:" + circuit.plan_identity())
         return h.digest()
     if type(circuit) is not EL.MlpCircuit:
         h.update(("layout:%s:" % type(circuit).__name__).encode())
-        h.update(circuit.plan_identity())
-        for name, table in sorted(circuit.gc.base.static_tables.items()):
-            h.update(name.encode() + struct.pack("<3q", table.range[0], table.range[1], table.col_size))
-            h.update(_table_values(table).tobytes())
-        return h.digest()
-    h.update(struct.pack("<8q", circuit.k, circuit.w, circuit.base, circuit.legs, int(circuit.relu_last), int(circuit.relu_first), circuit.n_inputs,
-                         len(circuit.weights)))
-    for W, b in zip(circuit.weights, circuit.biases):
-        h.update(struct.pack("<3q", len(W), len(W[0]), len(b)))
-        h.update(np.asarray(W, np.int64).tobytes())
-        h.update(np.asarray(b, np.int64).tobytes())
+    h.update(circuit.plan_identity())
+    for name, table in sorted(circuit.gc.base.static_tables.items()):
+        h.update(name.encode() + struct.pack("<3q", table.range[0], table.range[1], table.col_size))
+        h.update(_table_values(table).tobytes())
     return h.digest()
 
 
 def record_plan(circuit):
-    """one witness-free layout pass -> WitnessPlan, with the input vector and the parameters as symbols.  An MlpCircuit: the op sequence is
-    MlpCircuit.synthesize's, restated here.  A circuit that states its op sequence itself -- `layout(reg, inputs, param) -> outputs`, which its
-    own `synthesize` runs too, with `n_inputs` and `plan_identity()` (ConvMnistCircuit) -- is recorded from that, on a
-    LookupRecordingRegion.  An EinsumMatmulCircuit with columns of its own (not one laid over another circuit's) is recorded from its
-    `sequence` into a two-phase plan.  Every other circuit class is refused by name."""
+    """one witness-free layout pass -> WitnessPlan, with the input vector and the parameters as symbols.  A circuit built on BaseRegion
+    states its op sequence itself -- `layout(reg, inputs, param) -> outputs`, which its own `synthesize` runs too, with `n_inputs` and
+    `plan_identity()` (MlpCircuit, ConvMnistCircuit) -- and is recorded from that; the parameters enter the blob in the order `layout` asks
+    for them.  Only the recording region is chosen here: an MlpCircuit keeps RecordingRegion (latest-fit grouping, `nonlinearity` refused
+    by name: its blobs stay what they were), any other such circuit gets a LookupRecordingRegion.  An EinsumMatmulCircuit with columns of
+    its own (not one laid over another circuit's) is recorded from its `sequence` into a two-phase plan.  Every other circuit class is
+    refused by name."""
     if type(circuit) is EL.EinsumMatmulCircuit and getattr(circuit, "standalone", False):
         return _record_einsum(circuit)
-    mlp = type(circuit) is EL.MlpCircuit
-    if not mlp and not (callable(getattr(circuit, "layout", None)) and callable(getattr(circuit, "plan_identity", None))):
+    if not (callable(getattr(circuit, "layout", None)) and callable(getattr(circuit, "plan_identity", None))):
         raise PlanError("witness plans cover MlpCircuit and circuits that state their `layout`, not %s (sum / prod and the surrogate "
                         "circuits keep the host path)" % type(circuit).__name__)
     if any(c.phase != 0 for c in circuit.gc.cs.advice):
         raise PlanError("witness plans do not cover second-phase advice")
-    reg = RecordingRegion(circuit.gc) if mlp else LookupRecordingRegion(circuit.gc)
+    reg = RecordingRegion(circuit.gc) if type(circuit) is EL.MlpCircuit else LookupRecordingRegion(circuit.gc)
     if (len(circuit.gc.cs.advice) << circuit.k) > 1 << 32:
         raise PlanError("cells are numbered in 32 bits")
-    Val = EL.Val
     params = []
     def param(v):
         v = int(v)
         if not -(1 << 63) <= v < 1 << 63:
             raise PlanError("a parameter beyond int64")
         params.append(v)
-        return Val(_Param(len(params) - 1))
-    vals = [Val(_Input(i)) for i in range(circuit.n_inputs)]
-    if not mlp:
-        outs = circuit.layout(reg, vals, param)
-        return WitnessPlan._from_recorder(circuit, reg, params, [v.v.idx for v in outs])
-    _, vals = reg.decompose(vals, circuit.base, circuit.legs)
-    if circuit.relu_first:
-        vals = reg.relu(vals, circuit.base, circuit.legs)
-    for i, (W, b) in enumerate(zip(circuit.weights, circuit.biases)):
-        outs = [reg.dot(vals, [param(wv) for wv in row]) for row in W]
-        vals = reg.pairwise(outs, [param(bv) for bv in b], EC.ADD)
-        if i + 1 < len(circuit.weights) or circuit.relu_last:
-            vals = reg.relu(vals, circuit.base, circuit.legs)
-    outputs = [v.v.idx for v in vals]                          # MlpCircuit.outputs: the values the final equality is made on
-    reg.output_equals_instance(vals, circuit.gc.instance, 0, circuit.base, circuit.legs)
+        return EL.Val(_Param(len(params) - 1))
+    outs = circuit.layout(reg, [EL.Val(_Input(i)) for i in range(circuit.n_inputs)], param)
     # (reg.finish writes the fixed constant column: keygen's, not the witness's)
-    return WitnessPlan._from_recorder(circuit, reg, params, outputs)
+    return WitnessPlan._from_recorder(circuit, reg, params, [v.v.idx for v in outs])
 
 
 class WitnessPlan:
@@ -916,10 +897,6 @@ def validate(plan):
         raise PlanError("witness plan: an output cell is never written")
 
 
-def _signed(v):
-    return v if v < R // 2 else v - R
-
-
 def column_phases(plan):
     """the phase each advice column belongs to: that of the records that write it (`validate` refuses two), 0 for a column no record writes"""
     out = [0] * plan.n_advice
@@ -996,17 +973,17 @@ def run_plan_host(plan, x, challenges=None, phase=None):
             elif kind == INVZ: v = pow(cells[ia], -1, R) if cells[ia] else 0
             elif kind in (TABLE, TBLIDX):
                 t_lo, t_n, t_col, t_off = plan.tables[p0]
-                s = _signed(cells[ia])
+                s = EL.signed(cells[ia])
                 if s < t_lo or s > t_lo + t_n - 1 or abs(s) >= 1 << 62:
                     raise AssertionError("%s (%s record %d, element %d)" % (LOOKUP_ERROR, KIND_NAMES[kind], ri, i))
                 v = int(plan.table_values[t_off + s - t_lo]) % R if kind == TABLE else (s - t_lo) // t_col
             elif kind == RCIDX:
-                s = _signed(cells[ia])
+                s = EL.signed(cells[ia])
                 if abs(s) >= 1 << 62:                 # what a lane holds in 64 bits; the layout only range-checks signs and digits
                     raise AssertionError("%s (%s record %d, element %d)" % (RANGE_ERROR, KIND_NAMES[kind], ri, i))
                 v = abs(s - lo) // p1
             else:
-                s, e = _signed(cells[ia]), P[b + i]
+                s, e = EL.signed(cells[ia]), P[b + i]
                 if abs(s) >= p0 ** p1:
                     raise AssertionError("%s (%s record %d, element %d)" % (RANGE_ERROR, KIND_NAMES[kind], ri, i))
                 v = ((s > 0) - (s < 0)) % R if e == NONE else (abs(s) // p0 ** e) % p0

@@ -10,11 +10,28 @@ import hashlib
 import numpy as np
 import pytest
 
-from test_witness_plan_cpu import _mlp
+from test_witness_plan_cpu import CASES as MLP_CASES, _mlp
 
-# sha256 of record_plan(_mlp(9, 2)[0]).to_bytes() (tests/test_witness_plan_cpu.py), taken on commit 05df2094cb08ff47267e800d503f02d542bd0088,
-# the last one whose plan format had no table section
-MLP_K9_W2_SHA256 = "b352394d5d9bb4650f74b8253d9c35401ec15b1721734fb292121a46b6cda58a"
+# name -> (records, sha256 of record_plan(circuit).to_bytes(), the first 16 hex digits of params_hash(circuit)).  The MLP rows are the cases
+# of tests/test_witness_plan_cpu.py; mlp_k9_w2's digest was taken on commit 05df2094cb08ff47267e800d503f02d542bd0088, the last one whose
+# plan format had no table section, every other figure on commit 50e40f7, the last one whose recorder restated the MLP's op sequence and
+# packed its parameters itself (there mlp_k9_w2 still had the digest of 05df209)
+MLP_PINS = {
+    "golden_k6_5_blocks": (52, "ffe47266be64e9c78ee373572843f7e77f7a0d53d665e86e509cfa117c56b1e0", "8adc4d7fb3f4fcdf"),
+    "mlp_k9_w2_3_blocks": (98, "b352394d5d9bb4650f74b8253d9c35401ec15b1721734fb292121a46b6cda58a", "32d93f091822c46c"),
+    "mlp_k9_w1_5_blocks": (98, "621528fd4387d381fb30dcdf417c1545cb445b6cf808f4108d14e76d4e17f77f", "7770728dbcb89168"),
+    "1l_relu_k8": (46, "fe1787de709d463145514ed530d7681334c07f98cb75def100d5ca8182f9aa35", "a1bd617a1d2e51fa"),
+    "mlp_k9_w2_no_relu_last_2_blocks": (79, "c71aba0e0428a819d0e105d727e06c5a434d4cda75803ac90536d09e9d51e70a", "b6c1e1f0454241fa"),
+    "1l_relu_k8_w1": (46, "3023bb14d07f5059e7165fd428676dbf2a022b666f65020ce7a48f873011d13c", "8a664557d6a8a4c9"),
+    "mlp_k7_w1_dot_crosses_a_column_top": (75, "f3ec7c4de427912cb7fefe2afae30b68efd7e7bc43f1d70bffe04dd14c488642", "3c9e48c40b666896"),
+    "mlp_k7_w2_dot_crosses_a_column_top": (75, "7b1f029195b409ab32b27d053de8d2c78892513118dc2d41640c5c8ff0edeabf", "a7b4be905d566f60"),
+}
+CONV_PINS = {
+    "conv_k10_w1": (31, "ff0aa0f09047756db62b068c211d991aa70c43e82c45bf45cf658448453f86d7", "69e83bedafaccb66"),
+    "conv_k10_w2": (31, "1c035ddcdf5d92165b1b65577210bd1cb75508ae3e36c07527597f192583547a", "3390acee145d45f8"),
+    "conv_k6_w1_4_blocks_4_table_columns": (31, "c807c7eb5eec3cf379ec375ec27b17ba06ac9a5ed198cf01c7e0ef0a18dc8825", "977044005eb45851"),
+    "conv_k6_w2_2_blocks_4_table_columns": (31, "987b271317c69abcd9454589b50fdb6f8120b38911b4a7813393cb982f6c966f", "871bb318bf19bebc"),
+}
 
 
 def _case_a(w):
@@ -116,12 +133,29 @@ def test_params_hash_tells_conv_circuits_apart_and_leaves_the_mlp_alone():
     assert WP.params_hash(_mlp(9, 2)[0]).hex() == WP.peek(WP.record_plan(_mlp(9, 2)[0]).to_bytes())["param_hash"].hex()
 
 
-def test_mlp_plans_keep_their_bytes():
+def _assert_pinned(circuit, pin):
     from ezkl_amd import witness_plan as WP
-    blob = WP.record_plan(_mlp(9, 2)[0]).to_bytes()
-    assert hashlib.sha256(blob).hexdigest() == MLP_K9_W2_SHA256
+    records, sha, param_hash = pin
+    plan = WP.record_plan(circuit)
+    blob = plan.to_bytes()
+    assert plan.n_records == records
+    assert hashlib.sha256(blob).hexdigest() == sha
+    assert WP.params_hash(circuit).hex()[:16] == param_hash == WP.peek(blob)["param_hash"].hex()[:16]
+    return blob
+
+
+@pytest.mark.parametrize("name", list(MLP_PINS))
+def test_mlp_plans_keep_their_bytes(name):
+    from ezkl_amd import witness_plan as WP
+    assert set(MLP_PINS) == set(MLP_CASES)
+    blob = _assert_pinned(MLP_CASES[name]()[0], MLP_PINS[name])
     assert WP.VERSION == 1 and WP.peek(blob)["n_tables"] == 0 and WP.peek(blob)["n_table_values"] == 0
     assert WP.WitnessPlan.from_bytes(blob).tables == []
+
+
+@pytest.mark.parametrize("name", list(CONV_PINS))
+def test_conv_plans_keep_their_bytes(name):
+    _assert_pinned(CASES[name]()[0], CONV_PINS[name])
 
 
 def _conv_records(plan, kind):

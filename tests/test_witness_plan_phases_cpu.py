@@ -68,6 +68,19 @@ def test_host_interpreter_reproduces_the_einsum_layout_phase_by_phase(k, L):
         WP.run_plan_host(plan, x)
 
 
+# (k, L) -> (sha256 of the recorded blob, the first 16 hex digits of params_hash), taken on commit 50e40f7
+PINS = {(6, 3): ("0e654702bf8063410af28610c93314b9dc9350958cce4c6235f80d2b7612ebc8", "8dfda4fe13ce79f1"),
+        (10, 17): ("d7b905c435ba69a10cd0ebe780fd5a71fa8086fe1e54f5c3d82b91bd3e2c8d9d", "60b3fbc27bb4cfae")}
+
+
+@pytest.mark.parametrize("k,L", SIZES)
+def test_einsum_plans_keep_their_bytes(k, L):
+    import hashlib
+    from ezkl_amd import witness_plan as WP
+    c, _, _, _, plan = recorded(k, L)
+    assert (plan.n_records, hashlib.sha256(plan.to_bytes()).hexdigest(), WP.params_hash(c).hex()[:16]) == (8,) + PINS[(k, L)]
+
+
 def test_blob_keeps_version_1_and_the_record_count_does_not_follow_the_matrix():
     from ezkl_amd import ezkl_layout as EL, witness_plan as WP
     (c3, _, _, _, p3), (c17, _, _, _, p17) = recorded(6, 3), recorded(10, 17)
