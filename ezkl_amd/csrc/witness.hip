@@ -7,8 +7,9 @@
 // here does to one element what one iteration of its loops does.
 //
 //  * element-wise records (copy, const, input, param, add / sub / mult, decompose hints, range-check index, inverse-or-zero, static
-//    lookup output and its table-column index): one lane per destination cell; the index arrays are read coalesced, and where they
-//    hold contiguous runs (they mostly do: the layout advances a linear coordinate) so are the 32-byte cells;
+//    lookup output and its table-column index, the rounded division by a constant of `div`, layouts.rs:219-267): one lane per
+//    destination cell; the index arrays are read coalesced, and where they hold contiguous runs (they mostly do: the layout advances
+//    a linear coordinate) so are the 32-byte cells;
 //  * dot records (the running sum of w products per row, layouts.rs:532-610, with the duplicated row at the top of a new column as
 //    a step without products): all dots of a record run in parallel, 16 lanes to a dot -- a chunked scan over its rows, see
 //    wit_dot_kernel.  The index arrays are step-major (step s of every dot, then step s + 1): a wave holds 4 dots x 16 row chunks, so
@@ -23,9 +24,10 @@
 //
 // A value that does not fit its decomposition (|x| >= base^legs: the layout's "value exceeds the decomposition range") writes nothing
 // wrong silently, and neither does a lookup input outside its table (layouts.rs:5143-5222 `nonlinearity`; the layout's "lookup input
-// outside the table range"): the lane counts itself in status[0] and keeps the SMALLEST (record, element) in status[1] -- vector
-// atomics in plain C++, as the mock prover's kernels in vecops.hip -- and the host call returns EZKL_ERR_INVALID naming the op.
-// Nothing traps.
+// outside the table range"), and neither does a dividend of `div` beyond the range in which the integer quotient is the reference's f64
+// one (|s| >= 2^52: "rebase dividend outside the exact-division range"): the lane counts itself in status[0] and keeps the SMALLEST
+// (record, element) in status[1] -- vector atomics in plain C++, as the mock prover's kernels in vecops.hip -- and the host call
+// returns EZKL_ERR_INVALID naming the op.  Nothing traps.
 // The only device memory written is the destination columns, the plan's own scratch (inputs, outputs) and the status words; the plan's
 // index pool, parameters, constants and lookup-table values are read-only after upload.
 #include "common.hpp"
@@ -121,6 +123,12 @@ __global__ __launch_bounds__(256) void wit_elem_kernel(WitCols cols, uint32_t k,
                     uint64_t d = 1;
                     for (uint32_t t = 0; t < e; t++) d *= p0;
                     v = Fr::from_u64((mag / d) % p0);
+                }
+            } else if (KIND == DIVC) {                                                        // sgn(s) * ((|s| + d / 2) / d), d = p0 >= 1: checked on upload
+                fail = !fits || (mag >> 52) != 0;
+                if (!fail) {
+                    const uint64_t q = (mag + p0 / 2) / p0;                                   // < 2^52 + 2^31
+                    v = wit_from_i64(neg ? -(int64_t)q : (int64_t)q);
                 }
             } else if (KIND == RCIDX) {                                                       // |x - lo| // col_size
                 fail = !fits;                                                                 // |x| >= 2^62: as run_plan_host refuses it
@@ -488,6 +496,7 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
         case INVZ: launch_elem<INVZ>(st, cols, k, p, r, (uint32_t)ri); break;
         case TABLE: launch_elem<TABLE>(st, cols, k, p, r, (uint32_t)ri); break;
         case TBLIDX: launch_elem<TBLIDX>(st, cols, k, p, r, (uint32_t)ri); break;
+        case DIVC: launch_elem<DIVC>(st, cols, k, p, r, (uint32_t)ri); break;
         case MATMUL: {
             const uint32_t m = r.count / r.p1;
             hipLaunchKernelGGL(wit_matmul_kernel, dim3(cdiv(m, MM_TILE) * cdiv(r.p1, MM_TILE)), dim3(MM_TILE * MM_TILE), 0, st, cols, k, p->pool + r.dst, p->pool + r.a,
@@ -525,6 +534,7 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
         const uint32_t kind = ri < h.recs.size() ? h.recs[ri].kind : (uint32_t)N_KINDS;
         const char* what = kind == TABLE || kind == TBLIDX ? "witness: lookup input outside the table range ("
                            : kind == MATMUL               ? "witness: einsum operand outside the exact-product range ("
+                           : kind == DIVC                 ? "witness: rebase dividend outside the exact-division range ("
                                                           : "witness: value exceeds the decomposition range (";
         t_wit_error = std::string(what) + (kind < N_KINDS ? KIND_NAMES[kind] : "?") + " record " + std::to_string(ri) +
                       ", element " + std::to_string(el) + "; " + std::to_string(dev_status[0]) + (kind == MATMUL ? " operand reads in all)" : " cells in all)");

@@ -20,6 +20,8 @@
 // m * kd + its place in b.
 // An RLC record: count scans of p1 steps with challenge p0 (< n_challenges), step-major and dense (no 0xffffffff entries): out[0] = c * v[0],
 // out[t] = out[t - 1] * c + c * v[t], v[t] = cell a[t * count + d], out[t] -> cell dst[t * count + d].
+// A DIVC record (the rebase division of an MLP layer, layouts.rs:219-267 `div`): a = source cell, p0 = d >= 1 (zero: refused); with s the
+// signed value of the cell, sgn(s) * ((|s| + d / 2) / d) -- s / d rounded half away from zero.  |s| >= 2^52 is a run-time failure of the lane.
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -31,9 +33,9 @@ namespace ezkl {
 namespace wplan {
 
 constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64, MAX_PHASES = 3, MAX_CHALLENGES = 64;
-enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, N_KINDS };
+enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC, N_KINDS };
 static const char* const KIND_NAMES[N_KINDS] = {"copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot",
-                                                "nonlinearity", "nonlinearity_index", "matmul", "rlc"};
+                                                "nonlinearity", "nonlinearity_index", "matmul", "rlc", "div"};
 struct Rec {
     uint32_t kind, count, p0, p1, dst, a, b, phase;
 };
@@ -159,6 +161,7 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
             break;
         }
         case RCIDX: a_cells = true; if (r.p1 == 0) return at_rec(ri, r.kind, "zero table column size"); break;
+        case DIVC: a_cells = true; if (r.p0 == 0) return at_rec(ri, r.kind, "zero divisor"); break;
         case TABLE: case TBLIDX: a_cells = true; if (r.p0 >= n_tab) return at_rec(ri, r.kind, "lookup table index out of range"); break;
         case MATMUL: {                                   // p0 = kd, p1 = n, count = m * n: a = m * kd, b = kd * n input indices
             if (r.p0 == 0 || r.p1 == 0 || r.count % r.p1 != 0) return at_rec(ri, r.kind, "bad matmul shape");

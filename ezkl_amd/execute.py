@@ -14,7 +14,10 @@ reference's fixture `prove` runs from the reference's artefact files alone (test
 CONTAIN here is the op family ezkl_layout.MlpCircuit lays out (Input -> Gemm as Einsum "mk,nk->mn" + bias + LeakyReLU slope 0, private
 parameters, public output): ezkl's general layout lives in 6.8k lines of Rust (out of scope) and any other graph
 is refused by name.  On the fixture model that layout reproduces the reference's pk.key bit for bit (tests/test_ezkl_circuit.py).  A JSON
-description of the same family ({"model": "mlp", "run_args": {...}, "weights": [...], "biases": [...]}) is accepted as well.
+description of the same family ({"model": "mlp", "run_args": {...}, "weights": [...], "biases": [...]}) is accepted as well; with
+"rebase": [d per layer] every Gemm is wrapped in the RebaseScale division ezkl puts around it at non-zero scales (layouts.rs:219-267 `div`):
+the input is then quantized at run_args.input_scale and the outputs are reported at input_scale + sum(param_scale - log2 d), or at
+"output_scale" where a divisor is no power of two.
 Errors surface as exceptions with the reference's wording where it has one."""
 import json
 import os
@@ -41,15 +44,28 @@ def _read_compiled(path, any_visibility=False):
             raise ValueError("unsupported compiled circuit: %r" % j.get("model"))
         ra, weights = j["run_args"], j["weights"]
         scale = ra.get("input_scale", 0) if not weights else 0                      # a Gemm-free graph keeps its input scale (ezkl's default: 7)
-        return dict(weights=weights, biases=j["biases"], relu_last=j.get("relu_last", True), relu_first=j.get("relu_first", False),
+        in_scale = out_scale = scale
+        rebase = j.get("rebase")
+        if rebase is not None:                                                       # every Gemm wrapped in a RebaseScale: the scales are the run args'
+            rebase = [int(d) for d in rebase]
+            if len(rebase) != len(weights) or any(not 1 <= d < 1 << 32 for d in rebase):
+                raise ValueError("compiled circuit: \"rebase\" takes one divisor in [1, 2^32) per layer")
+            in_scale = ra.get("input_scale", 0)
+            if "output_scale" in j:
+                out_scale = int(j["output_scale"])
+            elif all(d & (d - 1) == 0 for d in rebase) and "param_scale" in ra:       # a layer adds the parameter scale, its rebase takes log2 d off
+                out_scale = in_scale + sum(ra["param_scale"] - (d.bit_length() - 1) for d in rebase)
+            else:
+                raise ValueError("compiled circuit: \"output_scale\" is required where a rebase divisor is not a power of two (or run_args has no param_scale)")
+        return dict(weights=weights, biases=j["biases"], relu_last=j.get("relu_last", True), relu_first=j.get("relu_first", False), rebase=rebase,
                     n_inputs=j.get("n_inputs", len(weights[0][0]) if weights else None), run_args=ra, settings=None,
-                    total_assignments=j.get("total_assignments"), in_scale=scale, out_scale=scale, datum_type="F32", input_decomp=True,
+                    total_assignments=j.get("total_assignments"), in_scale=in_scale, out_scale=out_scale, datum_type="F32", input_decomp=True,
                     visibility=dict(input=ra.get("input_visibility", "Private"), params=ra.get("param_visibility", "Private"),
                                     output=ra.get("output_visibility", "Public"))), j
     c = codecs.read_compiled_circuit(raw)
     weights, biases, relu_last, relu_first, n_inputs = _mlp_of_graph(c["model"], any_visibility)
     st, in_op = c["settings"], c["model"]["nodes"][c["model"]["inputs"][0]]["opkind"]
-    return dict(weights=weights, biases=biases, relu_last=relu_last, relu_first=relu_first, n_inputs=n_inputs, run_args=st["run_args"], settings=st,
+    return dict(weights=weights, biases=biases, relu_last=relu_last, relu_first=relu_first, rebase=None, n_inputs=n_inputs, run_args=st["run_args"], settings=st,
                 total_assignments=st["total_assignments"], in_scale=st["model_input_scales"][0], out_scale=st["model_output_scales"][0],
                 datum_type=in_op.get("datum_type", "F32"), input_decomp=in_op.get("decomp", True), visibility=c["model"]["visibility"]), c
 
@@ -64,7 +80,8 @@ def _load_circuit(path):
                 or st["einsum_params"]["equations"]:
             raise ValueError("unsupported compiled circuit: its settings ask for arguments outside the MLP family")
     return EL.MlpCircuit(ra["logrows"], ra["num_inner_cols"], d["weights"], d["biases"], ra["decomp_base"], ra["decomp_legs"],
-                         total_assignments=d["total_assignments"], relu_last=d["relu_last"], n_inputs=d["n_inputs"], relu_first=d["relu_first"]), parsed
+                         total_assignments=d["total_assignments"], relu_last=d["relu_last"], n_inputs=d["n_inputs"], relu_first=d["relu_first"],
+                         rebase=d["rebase"]), parsed
 
 
 def _mlp_of_graph(model, any_visibility=False):
@@ -247,7 +264,8 @@ def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None
 
     * inputs are quantized as load_graph_input does (datum-type round trip, times 2^scale, half away from zero);
     * the forward pass is the integer arithmetic of the op family this package lays out (_mlp_of_graph: Einsum "mk,nk->mn", Add,
-      LeakyReLU slope 0 at scale 0) with the range checks the layout would make: a value outside (-base^legs, base^legs) where the
+      LeakyReLU slope 0 at scale 0; a JSON description with "rebase" divides every Gemm's output by its layer's divisor, rounded half away
+      from zero as the circuit's `div` claims it -- ezkl_layout.round_div -- and reports the outputs at the rebased scale) with the range checks the layout would make: a value outside (-base^legs, base^legs) where the
       circuit decomposes it is the reference's decomposition error, here a ValueError; max_range_size = decomp_base - 1;
     * KZGCommit visibility of the input / parameters / output ("polycommit"): PolyCommitChip::commit on the GPU (backend.polycommit_commit:
       one commit_lagrange MSM per column of 2^k - (blinding factors + 1) values) -- needs srs_path, and like the reference a vk to know the
@@ -285,8 +303,15 @@ def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None
     if relu_first:
         decomposed(x, "LeakyReLU input")
         x = [v if v > 0 else 0 for v in x]
+    rebase = d["rebase"] or [1] * len(weights)
     for li, (W, bvec) in enumerate(zip(weights, biases)):
-        x = [sum(a * w for a, w in zip(x, row)) + bvec[o] for o, row in enumerate(W)]
+        x = [sum(a * w for a, w in zip(x, row)) for row in W]
+        if rebase[li] != 1:                              # RebaseScale around the Gemm: `div` claims the rounded quotient and decomposes it
+            if any(abs(v) >= 1 << 52 for v in x):
+                raise ValueError("layer %d: %s" % (li, EL.DIV_ERROR))
+            x = [EL.round_div(v, rebase[li]) for v in x]
+            decomposed(x + [rebase[li]], "rebase quotient of layer %d" % li)        # (the divisor: d - |remainder| is decomposed too)
+        x = [v + bvec[o] for o, v in enumerate(x)]
         if li + 1 < len(weights) or relu_last:
             decomposed(x, "LeakyReLU input of layer %d" % li)
             x = [v if v > 0 else 0 for v in x]

@@ -29,6 +29,19 @@ def signed(v):
     return v if v < R // 2 else v - R
 
 
+DIV_ERROR = "rebase dividend outside the exact-division range"
+
+
+def round_div(s, d):
+    """the signed integer s over the constant d >= 1, rounded half away from zero: `((a as f64) / denom).round()` of const_div
+    (/root/reference/src/tensor/ops.rs:2326-2331) as exact integer arithmetic, q = sgn(s) * ((|s| + d // 2) // d).  The two agree for
+    |s| < 2^52 and d < 2^32: |s| and d are exact in f64, the f64 quotient is off by less than 1 / (2d) -- the least distance of s / d from
+    a half that is not one -- and an exact half is representable.  Beyond 2^52 the dividend is refused."""
+    mag = abs(s)
+    assert mag < 1 << 52, DIV_ERROR
+    return ((s > 0) - (s < 0)) * ((mag + d // 2) // d)
+
+
 class Region:
     """cells, selector activations and copy constraints of one synthesis pass"""
 
@@ -341,6 +354,7 @@ class BaseRegion(Region):
         self.witness = witness
         self.first_const = {}                          # value -> first advice cell holding it
         self.const_order = []                          # (value, advice cell) in order of first use: the floor planner's fixed cells
+        self.decomp = None                             # RegionCtx's (base, legs), region.rs `base()` / `legs()`: set by the circuit's layout
 
     def cell_of(self, var, linear):
         x, y, z = var.cartesian_coord(linear)
@@ -491,9 +505,10 @@ class BaseRegion(Region):
             return acc
         return self._accumulate(vals, EC.CUMPRODINIT, EC.CUMPROD, 1, fold)
 
-    def decompose(self, vals, base, legs):
-        """layouts.rs:6321-6423 (zero_sign_matters = false): hints [sign, digits..] on the output VarTensor, range checks, recomposition
-        by dot products with the base powers, multiplication by the sign, equality with the input"""
+    def decompose(self, vals, base, legs, zero_sign_matters=False):
+        """layouts.rs:6321-6423: hints [sign, digits..] on the output VarTensor, range checks, recomposition by dot products with the base
+        powers, multiplication by the sign, equality with the input.  zero_sign_matters (:6389-6403): is_zero(input) * sign == 0, between
+        the two range checks -- a zero input must carry the sign 0"""
         if any(v.cell is None and not v.const for v in vals):
             vals = self.assign(self.inputs[0], vals)   # not yet assigned (model input / instance): placed without advancing
         hints = []
@@ -508,6 +523,10 @@ class BaseRegion(Region):
         signs = [claimed[t] for t in range(0, len(claimed), legs + 1)]
         rest = [claimed[t] for t in range(len(claimed)) if t % (legs + 1)]
         signs = self.range_check(signs, (-1, 1))
+        if zero_sign_matters:
+            is_zero = self.equals_zero(vals)
+            sign_is_zero = self.pairwise(signs, is_zero, EC.MULT)
+            self.enforce_equality(sign_is_zero, [Val(0, const=True)] * len(sign_is_zero))
         rest = self.range_check(rest, (0, base - 1))
         bases = [Val(base ** (legs - 1 - t), const=True) for t in range(legs)]
         recomposed = [self.dot(rest[i * legs:(i + 1) * legs], bases) for i in range(len(vals))]
@@ -531,6 +550,51 @@ class BaseRegion(Region):
         diff = self.pairwise(sign, [Val(1, const=True)] * len(sign), EC.SUB)
         mask = self.equals_zero(diff)
         return self.pairwise(vals, mask, EC.MULT)
+
+    def sign(self, vals, zero_sign_matters=False):
+        """layouts.rs:6425-6445: the sign hints of a decomposition at the region's base and legs"""
+        base, legs = self.decomp
+        claimed, _ = self.decompose(vals, base, legs, zero_sign_matters)
+        return [claimed[t] for t in range(0, len(claimed), legs + 1)]
+
+    def abs(self, vals):
+        """layouts.rs:6447-6455"""
+        return self.pairwise(vals, self.sign(vals), EC.MULT)
+
+    def equals(self, a, b):
+        """layouts.rs:3494-3501"""
+        return self.equals_zero(self.pairwise(a, b, EC.SUB))
+
+    def greater(self, a, b):
+        """layouts.rs:3112-3128: sign(a - b) with the zero's sign pinned, then sign == 1"""
+        sg = self.sign(self.pairwise(a, b, EC.SUB), True)
+        return self.equals(sg, [Val(1, const=True)] * len(sg))
+
+    def less(self, a, b):
+        """layouts.rs:3236-3243"""
+        return self.greater(b, a)
+
+    def l1_distance(self, a, b):
+        """layouts.rs:58-67"""
+        return self.abs(self.pairwise(a, b, EC.SUB))
+
+    def diff_less_than(self, a, b, constant):
+        """layouts.rs:156-172: |a - b| < constant, enforced"""
+        distance = self.l1_distance(a, b)
+        is_less = self.less(distance, [Val(constant, const=True)] * len(distance))
+        self.enforce_equality(is_less, [Val(1, const=True)] * len(is_less))
+
+    def div(self, vals, d):
+        """layouts.rs:219-267, the rebase of a RebaseScale node with an integer denominator (HybridOp::Div, hybrid.rs:279-286): the prover
+        claims the rounded quotient (`round_div`), the claim is range-checked by decomposition, and |input - claim * d| < d is enforced"""
+        if d == 1:                                     # :225-227
+            return vals
+        claimed = [Val(round_div(signed(v.v), d)) for v in vals]
+        base, legs = self.decomp
+        _, claimed = self.decompose(claimed, base, legs)
+        product = self.pairwise(claimed, [Val(d, const=True)] * len(claimed), EC.MULT)
+        self.diff_less_than(vals, product, d)
+        return claimed
 
     def nonlinearity(self, vals, name):
         """layouts.rs:5143-5222: x into the lookup input VarTensor, f(x) into the output VarTensor, the table-column index of x into
@@ -635,14 +699,19 @@ class MlpCircuit(LayoutCircuit):
     input and parameters, public output, inputs / outputs range-checked by decomposition (src/graph/model.rs:1132-1258)."""
 
     def __init__(self, logrows, num_inner_cols, weights, biases, decomp_base, decomp_legs, total_assignments=None, relu_last=True,
-                 n_inputs=None, relu_first=False):
-        """relu_first / n_inputs: a LeakyReLU (slope 0) straight on the input, before any Gemm -- with no layers at all that is
+                 n_inputs=None, relu_first=False, rebase=None):
+        """rebase: one positive integer per layer, the denominator of the RebaseScale that wraps the layer's Einsum node (node.rs:143-205:
+        `div` of the Gemm's output, before the bias is added; 1 = the layer is not rescaled), or None for none.
+        relu_first / n_inputs: a LeakyReLU (slope 0) straight on the input, before any Gemm -- with no layers at all that is
         examples/onnx/1l_relu (gen.py: nn.ReLU on a vector of 3), BASELINE configs[0]'s model; n_inputs is needed when there is no weight
         matrix to read the input length from"""
         self.k, self.w = logrows, num_inner_cols
         self.weights = [[[int(v) for v in row] for row in W] for W in weights]
         self.biases = [[int(v) for v in b] for b in biases]
         self.base, self.legs, self.relu_last, self.relu_first = decomp_base, decomp_legs, relu_last, bool(relu_first)
+        self.rebase = [1] * len(self.weights) if rebase is None else [int(d) for d in rebase]
+        if len(self.rebase) != len(self.weights) or any(not 1 <= d < 1 << 32 for d in self.rebase):
+            raise ValueError("MlpCircuit: rebase takes one divisor in [1, 2^32) per layer")
         self.n_inputs = int(n_inputs) if n_inputs is not None else (len(self.weights[0][0]) if self.weights else None)
         if self.n_inputs is None or (self.weights and len(self.weights[0][0]) != self.n_inputs):
             raise ValueError("MlpCircuit: the input length is unknown or does not match the first weight matrix")
@@ -664,6 +733,8 @@ class MlpCircuit(LayoutCircuit):
         for i, W in enumerate(self.weights):
             m, kk = len(W), len(W[0])
             c = al(c) + m * al(kk) + m
+            if self.rebase[i] != 1:                    # div: three decompositions (claim, |diff|, d - |diff|) and 16 cells of pairwise / equality ops
+                c += 3 * (dec(m) + w) + 16 * m
             if i + 1 < len(self.weights) or self.relu_last:
                 c += dec(m) + 6 * m
         m = len(self.weights[-1]) if self.weights else self.n_inputs
@@ -673,11 +744,13 @@ class MlpCircuit(LayoutCircuit):
         """the op sequence, stated once: `synthesize` runs it on a BaseRegion with the input's values, witness_plan.record_plan on a
         recording region with symbols.  inputs: the input vector as Vals; param(v) -> the Val of a circuit parameter (they are asked for
         in a fixed order: per layer, each weight row, then the biases)"""
+        reg.decomp = (self.base, self.legs)
         _, vals = reg.decompose(inputs, self.base, self.legs)                   # input range check
         if self.relu_first:
             vals = reg.relu(vals, self.base, self.legs)
         for i, (W, b) in enumerate(zip(self.weights, self.biases)):
             outs = [reg.dot(vals, [param(wv) for wv in row]) for row in W]         # einsum_with_base_ops: one dot per output
+            outs = reg.div(outs, self.rebase[i])                                   # RebaseScale around the Einsum node
             vals = reg.pairwise(outs, [param(bv) for bv in b], EC.ADD)
             if i + 1 < len(self.weights) or self.relu_last:
                 vals = reg.relu(vals, self.base, self.legs)
@@ -688,12 +761,13 @@ class MlpCircuit(LayoutCircuit):
         """what a witness plan of this circuit depends on besides the layout code (witness_plan.params_hash)"""
         shape = [self.k, self.w, self.base, self.legs, int(self.relu_last), int(self.relu_first), self.n_inputs, len(self.weights)]
         per_layer = [a for W, b in zip(self.weights, self.biases) for a in ([len(W), len(W[0]), len(b)], W, b)]
-        return b"".join(np.asarray(a, np.int64).tobytes() for a in [shape] + per_layer)
+        rebase = [self.rebase] if any(d != 1 for d in self.rebase) else []      # (a circuit that rescales nothing keeps its hash)
+        return b"".join(np.asarray(a, np.int64).tobytes() for a in [shape] + per_layer + rebase)
 
     def fresh(self):
         """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
         return MlpCircuit(self.k, self.w, self.weights, self.biases, self.base, self.legs, total_assignments=self.settings.total_assignments,
-                          relu_last=self.relu_last, n_inputs=self.n_inputs, relu_first=self.relu_first)
+                          relu_last=self.relu_last, n_inputs=self.n_inputs, relu_first=self.relu_first, rebase=self.rebase)
 
     def synthesize(self, x, witness=True):
         reg = BaseRegion(self.gc, witness)
@@ -719,8 +793,7 @@ class ConvMnistConfig(EC.GraphConfig):
         base = self.base = EC.BaseConfig(cs, [inp, params], out)
         base.configure_range_check(inp, params, (-1, 1), logrows)
         base.configure_range_check(inp, params, (0, decomp_base - 1), logrows)
-        half = denom // 2
-        self.div = lambda x: (abs(x) + half) // denom * (1 if x >= 0 else -1)           # f64::round of x / denom (tensor/ops.rs:2326-2331)
+        self.div = lambda x: round_div(x, denom)
         base.configure_lookup(inp, out, params, tuple(lookup_range), logrows, "div_%d" % denom, self.div)
         self.instance = cs.instance_column()
         cs.enable_equality(self.instance)

@@ -7,7 +7,8 @@ witness-free layout pass over a BaseRegion subclass whose VALUES are symbols: th
 --, the placement code is BaseRegion's own (cell_of, flush, _dup_inputs, the duplicate row at the top of a new column, every layouts.rs
 op as BaseRegion lays it out), and every `put` records how the cell it wrote is produced from earlier cells, a model input, a circuit
 parameter or a constant.  The cell writes are grouped into RECORDS -- one kernel launch each on the device (csrc/witness.hip) -- by data
-dependence.  An MlpCircuit is recorded on a RecordingRegion: a write joins the latest record of its kind when everything it reads was
+dependence.  An MlpCircuit -- with or without the rebase division of its layers (`BaseRegion.div`: one DIVC record per layer for the claimed
+quotients, everything else of the op is records of the kinds the family already had) -- is recorded on a RecordingRegion: a write joins the latest record of its kind when everything it reads was
 written by an earlier record, so the 650 dot products of a layer are one record, not 650.  (Every other circuit with a `layout` is
 recorded on a LookupRecordingRegion and grouped by dependence LEVEL: a write joins the EARLIEST record of its kind
 that comes after every record it reads from.  A cell is written once and read only by writes later in program order, so no element
@@ -36,6 +37,9 @@ A record of an element-wise kind has `count` destination cells pool[dst + i], pr
     RCIDX  a = source cell: |x - p0| // p1 (p0 = the range's lower end as int32, p1 = the table column size); |x| >= 2^62 -- more than a lane
            holds in 64 bits, never a sign or a digit -- is reported like a decomposition-range failure, here and on the device
     INVZ   a = source cell: 1 / x, or 0 for x = 0
+    DIVC   a = source cell, p0 = d (u32, >= 1), p1 = 0: with s the signed value of the cell, sgn(s) * ((|s| + d // 2) // d) -- s / d rounded half
+           away from zero, the claimed quotient of `div` (ezkl_layout.round_div); |s| >= 2^52 is the run-time failure "rebase dividend outside
+           the exact-division range", reported like the decomposition-range failure
     DOT    count dot products of p1 steps of p0 products each, step-major: step s of dot d writes the running sum to pool[dst + s * count + d]
            (0xffffffff: no such step) after adding the products of pool[a + (s * p0 + j) * count + d] and pool[b + ...] (0xffffffff: none --
            the duplicated running sum at the top of a new column is a step without products)
@@ -66,6 +70,7 @@ equality tests of tests/test_witness_plan_cpu.py fail loudly -- an assert or a P
     pairwise                  `x + y`, `x - y`, `x * y` on two assigned cells
     dot                       `acc = (acc + sum(x.v * y.v for ...)) % R` with acc and sum() starting from the integer 0
     equals_zero               `pow(v, -1, R) if v else 0`   (the truth value of a cell symbol is True: INVZ covers both branches)
+    div (round_div)           `mag = abs(s)`, `assert mag < 1 << 52` (recorded as the run-time check), `((s > 0) - (s < 0)) * ((mag + d // 2) // d)`
     nonlinearity              `assert table.range[0] <= signed(v) <= table.range[1]` (recorded as the run-time check), `table.f(signed(v)) % R`,
                               `(signed(v) - table.range[0]) // table.col_size` -- LookupRecordingRegion only; `table` is its stand-in there
     Val.__init__ and the ops  `... % R` on any symbol is the symbol
@@ -83,12 +88,14 @@ from . import ezkl_layout as EL
 R = EL.R
 MAGIC, VERSION = 0x50575A45, 1                  # "EZWP"
 NONE = 0xFFFFFFFF
-COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC = range(15)
-KIND_NAMES = ["copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot", "nonlinearity", "nonlinearity_index", "matmul", "rlc"]
+COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC = range(16)
+KIND_NAMES = ["copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot", "nonlinearity", "nonlinearity_index", "matmul", "rlc",
+              "div"]
 _HEADER = struct.Struct("<20I32s")
 RANGE_ERROR = "value exceeds the decomposition range"
 LOOKUP_ERROR = "lookup input outside the table range"
 OPERAND_ERROR = "einsum operand outside the exact-product range"
+DIV_ERROR = EL.DIV_ERROR
 MAX_PHASES, MAX_CHALLENGES = 3, 64
 
 
@@ -188,6 +195,10 @@ class _Cmp(_Sym):
 
 class _Sign(_Sym):
     def __init__(self, a): self.a = a.idx
+    def __mul__(self, o):                          # sgn(s) * ((|s| + d // 2) // d): round_div
+        if not (isinstance(o, _MagDiv) and o.half is not None and o.mag.a == self.a):
+            self._no()
+        return _Div(self.a, o.div, o.mag.bound)
 
 
 class _Mag(_Sym):
@@ -195,20 +206,37 @@ class _Mag(_Sym):
 
     def __init__(self, a): self.a, self.bound = a.idx, None
     def __floordiv__(self, d): return _MagDiv(self, d)
+    def __add__(self, half): return _MagHalf(self, half)
     def __lt__(self, bound):
         self.bound = bound
         return True
 
 
-class _MagDiv(_Sym):
-    """|x| // base^e, then `% base`: a digit"""
+class _MagHalf(_Sym):
+    """|x| + d // 2, then `// d`: the magnitude of a rounded quotient"""
 
-    def __init__(self, mag, div, base=None): self.mag, self.div, self.base = mag, div, base
+    def __init__(self, mag, half): self.mag, self.half = mag, half
+    def __floordiv__(self, d):
+        if self.half != d // 2:
+            self._no()
+        return _MagDiv(self.mag, d, half=self.half)
+
+
+class _MagDiv(_Sym):
+    """|x| // base^e, then `% base`: a digit; with `half`, (|x| + d // 2) // d"""
+
+    def __init__(self, mag, div, base=None, half=None): self.mag, self.div, self.base, self.half = mag, div, base, half
     def __mod__(self, m):
         if self.base is None:
             return _MagDiv(self.mag, self.div, m)
         assert m == R
         return self
+
+
+class _Div(_Sym):
+    """the signed value of cell a over the constant d, rounded half away from zero"""
+
+    def __init__(self, a, d, bound): self.a, self.d, self.bound = a, d, bound
 
 
 class _Shift(_Sym):
@@ -367,7 +395,13 @@ class RecordingRegion(EL.BaseRegion):
         elif isinstance(v, _Sign):
             base, legs = self._decomp
             out.emit(HINT, dst, v.a, NONE, p0=base, p1=legs, reads=(v.a,))
-        elif isinstance(v, _MagDiv) and v.base is not None:
+        elif isinstance(v, _Div):
+            if v.bound != 1 << 52:
+                raise PlanError("a division hint without the layout's range assertion")
+            if not 1 <= v.d < 1 << 32:
+                raise PlanError("a divisor beyond 32 bits")
+            out.emit(DIVC, dst, v.a, p0=v.d, reads=(v.a,))
+        elif isinstance(v, _MagDiv) and v.base is not None and v.half is None:
             base, legs = self._decomp
             if v.base != base or v.mag.bound != base ** legs:
                 raise PlanError("a digit hint without the layout's range assertion")
@@ -394,12 +428,12 @@ class RecordingRegion(EL.BaseRegion):
         return op
     pairwise, enforce_equality, range_check = _counted("pairwise"), _counted("enforce_equality"), _counted("range_check")
 
-    def decompose(self, vals, base, legs):
+    def decompose(self, vals, base, legs, zero_sign_matters=False):
         self.n_ops += 1
         self._decomp = (base, legs)
         if base ** legs >= 1 << 62:
             raise PlanError("decomposition range beyond 62 bits")
-        return super().decompose(vals, base, legs)
+        return super().decompose(vals, base, legs, zero_sign_matters)
 
     def dot(self, a, b):
         self.n_ops += 1
@@ -415,7 +449,7 @@ class RecordingRegion(EL.BaseRegion):
     def _refused(name):
         def op(self, *a, **kw):
             raise PlanError("witness plans do not cover `%s` (the MLP op family only: decompose, range_check, dot, pairwise, "
-                            "enforce_equality, equals_zero, relu, output_equals_instance)" % name)
+                            "enforce_equality, equals_zero, relu, div, output_equals_instance)" % name)
         return op
     nonlinearity, sum, prod, _accumulate = _refused("nonlinearity"), _refused("sum"), _refused("prod"), _refused("sum / prod")
     dynamic_lookup, shuffle, _lookup_any = _refused("dynamic_lookup"), _refused("shuffle"), _refused("lookup_any")
@@ -821,7 +855,7 @@ def validate(plan):
     total = 0
     col_phase, last_phase = [None] * plan.n_advice, 0
     for ri, (kind, count, p0, p1, dst, a, b, phase) in enumerate(plan.records.tolist()):
-        if kind > RLC:
+        if kind > DIVC:
             raise PlanError("witness plan: record %d: unknown kind %d" % (ri, kind))
         if count == 0:
             raise PlanError("witness plan: record %d is empty" % ri)
@@ -863,7 +897,7 @@ def validate(plan):
             d = _span(plan, dst, count, "dst", ri)
             x = _span(plan, a, count, "a", ri)
             srcs = np.zeros(0, np.uint32)
-            if kind in (COPY, ADD, SUB, MUL, HINT, RCIDX, INVZ, TABLE, TBLIDX):
+            if kind in (COPY, ADD, SUB, MUL, HINT, RCIDX, INVZ, TABLE, TBLIDX, DIVC):
                 srcs = x
             else:
                 lim = {CONST: len(plan.consts), INPUT: plan.n_inputs, PARAM: len(plan.params)}[kind]
@@ -877,6 +911,8 @@ def validate(plan):
                     raise PlanError("witness plan: record %d: bad decomposition" % ri)
             if kind == RCIDX and p1 == 0:
                 raise PlanError("witness plan: record %d: zero table column size" % ri)
+            if kind == DIVC and p0 == 0:
+                raise PlanError("witness plan: record %d: zero divisor" % ri)
             if kind in (TABLE, TBLIDX) and p0 >= len(plan.tables):
                 raise PlanError("witness plan: record %d (%s): lookup table index out of range" % (ri, KIND_NAMES[kind]))
         if (d >= cells).any() or (srcs >= cells).any():
@@ -977,6 +1013,11 @@ def run_plan_host(plan, x, challenges=None, phase=None):
                 if s < t_lo or s > t_lo + t_n - 1 or abs(s) >= 1 << 62:
                     raise AssertionError("%s (%s record %d, element %d)" % (LOOKUP_ERROR, KIND_NAMES[kind], ri, i))
                 v = int(plan.table_values[t_off + s - t_lo]) % R if kind == TABLE else (s - t_lo) // t_col
+            elif kind == DIVC:
+                s = EL.signed(cells[ia])
+                if abs(s) >= 1 << 52:
+                    raise AssertionError("%s (%s record %d, element %d)" % (DIV_ERROR, KIND_NAMES[kind], ri, i))
+                v = EL.round_div(s, p0) % R
             elif kind == RCIDX:
                 s = EL.signed(cells[ia])
                 if abs(s) >= 1 << 62:                 # what a lane holds in 64 bits; the layout only range-checks signs and digits

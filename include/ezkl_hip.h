@@ -249,7 +249,7 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *      (nonlinearity :5143-5222), which with those ops is the conv2d_mnist example's layout ----
  * A PLAN is the layout recorded once per circuit (ezkl_amd/witness_plan.py; byte layout: csrc/witness_plan.hpp): a list of records, each a
  * batch of cell writes of one kind (copy, const, input, param, add / sub / mult, decompose hint, range-check index, inverse-or-zero, dot,
- * static-lookup output, static-lookup table-column index, integer matmul, random linear combination) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
+ * static-lookup output, static-lookup table-column index, integer matmul, random linear combination, rounded division by a constant) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
  * of constants and -- header words 12 / 13 (n_tables, n_table_values; zero, as reserved words were, in a plan without lookups), after the
  * pool -- a directory of {lo (int32), n, col_size, offset} per static lookup table and the tables' values f(lo + i) as int64.  The version
  * word stays 1.  A lookup record names its source cells and a table: with s the signed value of the cell, the output kind writes
@@ -265,7 +265,9 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *   not fit its decomposition (|x| >= base^legs, the layout's "value exceeds the decomposition range") is counted by the kernel -- nothing
  *   traps, the process goes on -- and the call returns EZKL_ERR_INVALID with ezkl_hip_witness_last_error naming the op, record and
  *   element; the columns are then not a witness.  A lookup input outside its table (s < lo, s > lo + n - 1, |s| >= 2^62: the layout's
- *   "lookup input outside the table range") is reported the same way, with that message.  Scratch belongs to the plan (column pool): nothing is allocated per run, and a plan
+ *   "lookup input outside the table range") is reported the same way, with that message.  So is the dividend of a division record (kind 15:
+ *   a = source cell, p0 = d >= 1, a zero divisor is refused on upload; with s the signed value of the cell it writes sgn(s) * ((|s| + d / 2) / d),
+ *   the rounded quotient layouts.rs:219-267 `div` claims) with |s| >= 2^52: "rebase dividend outside the exact-division range".  Scratch belongs to the plan (column pool): nothing is allocated per run, and a plan
  *   runs one synthesis at a time.  HIP events around the run: ezkl_hip_last_kernel_ms("witness").
  * info: out = {k, n_advice, n_inputs, n_outputs, n_records, n_cells, n_ops (layout-op calls recorded), n_params}.
  * PHASES (second-phase advice: the Freivalds einsum, /root/reference/src/circuit/ops/chip/einsum/mod.rs:96-309).  Header word 14 of the blob is

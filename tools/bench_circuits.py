@@ -203,9 +203,12 @@ def mlp_circuit(k, rng, **kw):
     # fill (percent): lay out only that share of the cells but keep the column allocation of `blocks` full blocks (total_assignments is
     # what gen-settings would report for the full model): the Python layout engine needs ~15 us per cell, and every kernel of the
     # prover except the witness MSMs costs the same whatever the cells hold
-    c = EL.MlpCircuit(k, 2, Ws, bs, base, 2)
+    # rebase = d: every Gemm wrapped in the RebaseScale division by d (tools/synth_bench.py --rebase); the cell count, and with it the
+    # number of blocks, grows by what `div` lays out per layer
+    rebase = [kw["rebase"]] * layers if kw.get("rebase") else None
+    c = EL.MlpCircuit(k, 2, Ws, bs, base, 2, rebase=rebase)
     if fill and c.settings.total_assignments < int((blocks - 0.1) * cap):
-        c = EL.MlpCircuit(k, 2, Ws, bs, base, 2, total_assignments=int((blocks - 0.1) * cap))
+        c = EL.MlpCircuit(k, 2, Ws, bs, base, 2, total_assignments=int((blocks - 0.1) * cap), rebase=rebase)
     return c, x
 
 

@@ -19,6 +19,9 @@ second-phase columns depend on the proof's challenges, so the host pass runs INS
     create_proof_*_s    wall time of native.create_proof with the host callable and with the device callable (backend.WitnessPlan.advice_fn),
                         same key and seed; the proof bytes must be equal (--skip-proof leaves the pair out)
 
+--rebase D (MLP): every Gemm of the bench MLP wrapped in the RebaseScale division by D (layouts.rs:219-267 `div`, ezkl_layout.BaseRegion.div):
+the circuit ezkl lays out at non-zero scales; its entry is keyed "k<k>_rebase<D>".
+
 Each run merges its entry into profiles/<tag>_synth.json (key "k<k>" for the MLP, "conv_k<k>" for --circuit conv, "einsum_k<k>").  --skip-host leaves the host pass out (k = 20: over a minute of Python);
 --plan-dir keeps recorded plans between runs (a plan depends only on the circuit)."""
 import argparse
@@ -42,6 +45,7 @@ def main():
     ap.add_argument("--tag", default="synth")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--base", type=int, default=None, help="decomposition base (default: the bench's 16384)")
+    ap.add_argument("--rebase", type=int, default=None, help="mlp: wrap every Gemm in the RebaseScale division by this integer (key \"k<k>_rebase<d>\")")
     ap.add_argument("--repeat", type=int, default=10)
     ap.add_argument("--skip-host", action="store_true")
     ap.add_argument("--plan-dir", default=None)
@@ -58,9 +62,10 @@ def main():
         x, witness_in = [int(v) for v in img.reshape(-1)], img
         what = "examples/conv2d_mnist: Conv 1->4 5x5 stride 2 on 28x28 + ReLU + Div{32} lookup + Linear 576->10"
     else:
-        circuit, x = BC.mlp_circuit(a.k, np.random.default_rng(a.seed), base=a.base)
+        circuit, x = BC.mlp_circuit(a.k, np.random.default_rng(a.seed), base=a.base, rebase=a.rebase)
         witness_in = x
-        what = "MLP %d x (Gemm %dx%d + bias + ReLU), base %d" % (len(circuit.weights), len(circuit.weights[0]), len(circuit.weights[0]), circuit.base)
+        what = "MLP %d x (Gemm %dx%d%s + bias + ReLU), base %d" % (len(circuit.weights), len(circuit.weights[0]), len(circuit.weights[0]),
+                                                                  " / %d" % a.rebase if a.rebase else "", circuit.base)
     out = dict(k=a.k, circuit=what, advice_columns=len(circuit.gc.cs.advice))
     host = None
     if not a.skip_host:
@@ -72,7 +77,7 @@ def main():
         t2 = time.perf_counter()
         out.update(host_witness_s=round(t1 - t, 3), host_cols_to_mont_s=round(t2 - t1, 3), host_s=round(t2 - t, 3))
         print("k=%d host: circuit.witness %.3f s + cols_to_mont %.3f s" % (a.k, t1 - t, t2 - t1), flush=True)
-    blob, path = None, a.plan_dir and os.path.join(a.plan_dir, "%s_k%d_s%d_b%d.wplan" % (a.circuit, a.k, a.seed, circuit.base))
+    blob, path = None, a.plan_dir and os.path.join(a.plan_dir, "%s_k%d_s%d_b%d%s.wplan" % (a.circuit, a.k, a.seed, circuit.base, "_r%d" % a.rebase if a.rebase else ""))
     if path and os.path.exists(path):
         blob = open(path, "rb").read()
         if WP.peek(blob)["param_hash"] != WP.params_hash(circuit):
@@ -116,7 +121,7 @@ def main():
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     dst = os.path.join(ROOT, "profiles", "%s_synth.json" % a.tag)
     doc = json.load(open(dst)) if os.path.exists(dst) else {}
-    doc[("k%d" if a.circuit == "mlp" else "conv_k%d") % a.k] = out
+    doc[("k%d" if a.circuit == "mlp" else "conv_k%d") % a.k + ("_rebase%d" % a.rebase if a.rebase and a.circuit == "mlp" else "")] = out
     json.dump(doc, open(dst, "w"), indent=1, sort_keys=True)
     print(json.dumps(out))
 
