@@ -325,7 +325,8 @@ struct DevPlan {
     fe_t* outs = nullptr;
     unsigned long long* status = nullptr;
     Ctx* ctx = nullptr;
-    // a plan with phases: the last phase that ran to its end since the last phase 0, and the columns it ran on
+    // a plan with phases: the last phase that ran to its end since the last phase 0 with no earlier phase started again since, and the
+    // columns it ran on
     int done_phase = -1;
     void* done_cols[MAX_ADVICE] = {nullptr};
 };
@@ -461,6 +462,9 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
         bool same = p->done_phase >= (int)phase - 1;
         for (uint32_t j = 0; same && j < h.n_advice; j++) same = p->done_cols[j] == advice_cols_dev[j];
         if (!same) return refuse(("phase " + std::to_string(phase) + " before phase " + std::to_string(phase - 1) + " on these columns").c_str());
+        // this run zero-fills and rewrites the columns of its phase: until it has finished clean nothing later may read them, whatever an
+        // earlier run of this phase or a later one had finished
+        p->done_phase = (int)phase - 1;
     }
     EZ_CTX(c);
     if (c != p->ctx) return EZKL_ERR_INVALID;
