@@ -74,11 +74,24 @@ __device__ __forceinline__ uint32_t msm_lane_len(const uint32_t* offsets, uint32
 // several lane boundaries of the accumulate kernel; with 7 x 20 + 6 x 19 bits no bucket outgrows a lane.
 // Batched launches: one launch serves `gridDim.z` MSMs of the same size whose scratch slabs have the same layout `bstride` bytes
 // apart; a kernel shifts every scratch pointer it is given by blockIdx.z * bstride (bstride = 0 / gridDim.z = 1: a single MSM).
-template <class T> __device__ __forceinline__ T* bshift(T* p, size_t bytes) {
-    return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + bytes);
+// The shift is BYTE-POINTER arithmetic, never a round trip through an integer: a pointer rebuilt from a uintptr_t no longer derives from its
+// kernel argument, the compiler cannot place it in the global address space any more and every access through it becomes a FLAT instruction,
+// which counts on vmcnt AND lgkmcnt -- each wait for an LDS result then drains the outstanding global loads and stores as well, and each wait
+// for a load is a full drain instead of a counted vmcnt(N) (tests/test_msm_isa_cpu.py holds the kernels of the chain to zero flat accesses).
+template <class T> __device__ __forceinline__ T* bshift(T* p, size_t bytes) { return reinterpret_cast<T*>(reinterpret_cast<char*>(p) + bytes); }
+template <class T> __device__ __forceinline__ const T* bshift(const T* p, size_t bytes) {
+    return reinterpret_cast<const T*>(reinterpret_cast<const char*>(p) + bytes);
 }
 #define BSH(p) p = bshift(p, _bo)
 #define BOFF() const size_t _bo = (size_t)blockIdx.z * bstride
+// The scalar columns of a fused group travel BY VALUE in the kernel arguments (128 bytes): a column pointer read from a list in memory is a
+// pointer of unknown address space (flat loads of every scalar word again), and the list cost a host-to-device copy in front of every group.
+static constexpr size_t MSM_MAX_GROUP = 16;       // MSMs fused into one sequence of launches (gridDim.z)
+struct MsmCols {
+    const fe_t* col[MSM_MAX_GROUP];
+};
+// this workgroup's column: a uniform read of the kernel-argument segment at blockIdx.z (one scalar load, no copy of the struct)
+__device__ __forceinline__ const fe_t* msm_col(const MsmCols& cols) { return cols.col[blockIdx.z]; }
 
 struct WinPlan {
     uint32_t W, base, rem;
@@ -138,7 +151,6 @@ struct MsmSlot {
     uint32_t* pinned = nullptr;       // per MSM of the group: 1 + 22 planes of 36 limbs (g1x29_t), 32 records apart
     void* pinned_dev = nullptr;       // the same buffer as the device addresses it (hipHostGetDevicePointer): the planes kernel writes into it
     size_t pinned_msms = 0;
-    const fe_t** list_pinned = nullptr;   // the group's scalar-column pointers, staged for the device
     hipEvent_t done = nullptr;
     uint32_t bits = 0;
     uint32_t count = 0;               // MSMs in flight in this slot (one fused group)
@@ -310,11 +322,11 @@ __device__ __forceinline__ uint32_t msm_block_scan(uint32_t v, uint32_t* wsum, u
 // No global atomics: every workgroup histograms its slice of scalars in LDS and stores the row; a column scan turns the
 // rows into per-(workgroup, partition) start slots; the partition pass ranks its pairs with LDS atomics into an LDS
 // staging area grouped by partition and writes them out in staged order (runs of one partition leave as whole cache lines).
-__global__ __launch_bounds__(256) void msm_hist_kernel(const fe_t* scalars, size_t n, size_t per_block, WinPlan wp,
+__global__ __launch_bounds__(256) void msm_hist_kernel(MsmCols cols, size_t n, size_t per_block, WinPlan wp,
                                                        uint32_t LB, uint32_t NP, uint32_t* wg_hist, uint32_t* wg_cnt,
-                                                       const fe_t* const* scal_list, uint32_t* zero_base, uint32_t zero_words, size_t bstride) {
+                                                       uint32_t* zero_base, uint32_t zero_words, size_t bstride) {
     BOFF(); BSH(wg_hist); BSH(wg_cnt);
-    if (scal_list) scalars = scal_list[blockIdx.z];
+    const fe_t* scalars = msm_col(cols);
     if (zero_base) {                                                      // the chain's counters, bin totals and planes start at zero
         BSH(zero_base);
         for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < zero_words; i += gridDim.x * 256) zero_base[i] = 0;
@@ -428,12 +440,12 @@ __global__ __launch_bounds__(1024) void msm_part_scan_kernel(const uint32_t* par
 //     slot = part_base[p] + (pairs of partition p in earlier workgroups) + (index - start[p]).
 // The 13.6 M pairs of a 2^20-point MSM used to leave as 13.6 M scattered 8-byte stores, one L2 request each (~100 of the
 // kernel's 146 us); staged, a run of ~13 pairs of one partition is two cache lines.
-__global__ __launch_bounds__(1024) void msm_partition_kernel(const fe_t* scalars, size_t n, size_t per_block, WinPlan wp,
+__global__ __launch_bounds__(1024) void msm_partition_kernel(MsmCols cols, size_t n, size_t per_block, WinPlan wp,
                                                              uint32_t LB, uint32_t NP, size_t base_offset, size_t tab_stride,
                                                              const uint32_t* part_base, const uint32_t* wg_hist, const uint32_t* wg_cnt, uint2* entries,
-                                                             uint32_t* vals, const fe_t* const* scal_list, size_t bstride) {
+                                                             uint32_t* vals, size_t bstride) {
     BOFF(); BSH(part_base); BSH(wg_hist); BSH(wg_cnt); BSH(entries); BSH(vals);
-    if (scal_list) scalars = scal_list[blockIdx.z];
+    const fe_t* scalars = msm_col(cols);
     extern __shared__ uint32_t plds[];
     __shared__ uint32_t tsum[1024];
     const uint32_t NQ = NP + 1;                // partitions incl. bucket 0's (msm_part_of); the arrays below are padded to NQ + 1 words
@@ -631,7 +643,7 @@ __global__ __launch_bounds__(512) void msm_bigsort_scatter_kernel(const uint2* e
         __syncthreads();
         msm_bins_scan(cnt, tsum, nbins, p, beg, part_base, blockIdx.x == 0, offsets, buckets);     // cnt[j] = start of bin j in the partition
         const uint32_t* mine = block_off + ((size_t)y * MSM_BIG_BLOCKS + blockIdx.x) * nbins;      // + this workgroup's range inside each bin
-        for (uint32_t j = t; j < nbins; j += 512) cnt[j] += mine[j];
+        for (uint32_t j = t; j < nbins; j += 512) atomicAdd(&cnt[j], mine[j]);                     // an LDS add without return: waits for the load alone
         __syncthreads();
         for (uint32_t e = s0 + t; e < s1; e += 512) {
             const uint2 v = entries[e];
@@ -675,7 +687,14 @@ __global__ __launch_bounds__(256, 3) void msm_accumulate_kernel(const g1a_t* tab
     }
     uint32_t b = lo, bin_end = offsets[b + 1];
     // everything the next iteration needs is loaded ONE ITERATION AHEAD: the end of the bucket after this one, the payload of the pair
-    // after next (the address of the next gather) and the next table record -- no load sits on the path of the iteration that uses it
+    // after next (the address of the next gather) and the next table record -- no load sits on the path of the iteration that uses it.
+    // What the ISA does with it (all accesses are global_*, so vmcnt alone orders them and LDS / scalar waits never touch them): per iteration
+    // the loop issues, in this order, [the nine stores of a finished bucket,] offsets[b + 2], the five loads of the gathered record and
+    // vals[k + 2], then runs the whole mixed addition with all of them in flight; the loop latch, where `nxt` becomes `cur`, waits with
+    // COUNTED vmcnt(3) / vmcnt(1) / vmcnt(0) as the record's words are copied (loads return in issue order: the bucket end and the record come
+    // back before the payload, which is needed last, as the next gather's address).  Nothing inside the common path of the bucket-end branch
+    // waits; only the rare empty-bucket probes and their binary search wait for their own loads.  Until this form every access was flat_*
+    // (the scratch pointers went through an integer), each of these waits was vmcnt(0) lgkmcnt(0), and the branch drained its own stores.
     uint32_t end_next = offsets[b + 2 <= nb ? b + 2 : nb];
     lane_first[t] = b;                          // the bucket holding this lane's first pair (msm_fixup_boundary_kernel)
     bool started_before = offsets[b] < k0;
@@ -698,17 +717,20 @@ __global__ __launch_bounds__(256, 3) void msm_accumulate_kernel(const g1a_t* tab
                 uint32_t probes = 1;
                 while (bin_end == k && probes < 4) { b++; bin_end = offsets[b + 1]; probes++; }
                 if (bin_end == k) {
-                    uint32_t lo2 = b + 1, hi2 = nb;          // offsets[lo2] == k, offsets[hi2] = total > k
+                    uint32_t lo2 = b + 1, hi2 = nb, vhi = total;   // offsets[lo2] == k, offsets[hi2] = vhi > k
                     while (hi2 - lo2 > 1) {
-                        uint32_t mid = (lo2 + hi2) >> 1;
-                        if (offsets[mid] <= k) lo2 = mid; else hi2 = mid;
+                        const uint32_t mid = (lo2 + hi2) >> 1, vm = offsets[mid];
+                        if (vm <= k) lo2 = mid; else { hi2 = mid; vhi = vm; }
                     }
                     b = lo2;
-                    bin_end = offsets[b + 1];
+                    bin_end = vhi;                           // = offsets[b + 1], already compared inside the search: no load is pending at the join
                 }
             }
-            end_next = offsets[b + 2 <= nb ? b + 2 : nb];
         }
+        // the end of the bucket after this one: re-read EVERY iteration (the same cached word for a whole bucket), next to the other loads and
+        // outside the branch -- loaded inside it, the value reached the join as a pending load, and the wait for it also drained the nine
+        // stores of the bucket just finished (on gfx9 loads and stores share vmcnt and return in order), in nearly every iteration of a wave
+        end_next = offsets[b + 2 <= nb ? b + 2 : nb];
         const MsmRec cur = nxt;
         // no divergent region around the loads (round 5: the `if (k + 1 < k1)` around them cost 3.7 % of the kernel, 0.916 -> 0.886 ms,
         // profiles/r05y_msm_ab.log): past the lane's last pair a record is fetched and never used
@@ -741,7 +763,7 @@ EZ_D g1x29_t g1x29_shfl_down(const g1x29_t& p, uint32_t d) {
     for (int k = 0; k < 36; k++) o[k] = __shfl_down(s[k], d);
     return r;
 }
-__global__ __launch_bounds__(256) void msm_fixup_boundary_tree_kernel(const uint32_t* offsets, uint32_t nb, uint32_t nlanes,
+__global__ __launch_bounds__(256, 3) void msm_fixup_boundary_tree_kernel(const uint32_t* offsets, uint32_t nb, uint32_t nlanes,
                                                                       const uint32_t* lane_first, const g1x29_t* head, const g1x29_t* tail, g1x29_t* buckets,
                                                                       uint32_t* heavy_list, uint32_t* heavy_count, uint32_t* chunk_list, uint32_t lmin,
                                                                       uint32_t span_heavy, size_t bstride) {
@@ -974,12 +996,10 @@ void msm_table_drop(const Bases* b) {
     }
 }
 
-static constexpr size_t MSM_MAX_GROUP = 16;       // MSMs fused into one sequence of launches (gridDim.z)
 static int slot_prepare(MsmSlot& sl, size_t bytes, size_t msms = 1) {
     if (!sl.st) {
         EZ_HIP(stream_create_prio(&sl.st, "EZKL_HIP_PRIO_MSM", 0));
         EZ_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-        EZ_HIP(hipHostMalloc((void**)&sl.list_pinned, MSM_MAX_GROUP * sizeof(void*), hipHostMallocDefault));
     }
     if (msms > sl.pinned_msms) {
         if (sl.pinned) {
@@ -1052,7 +1072,6 @@ static int msm_enqueue(Ctx* c, MsmSlot& sl, hipStream_t st, MsmTable* T, size_t 
     int rc = EZKL_OK;
     if (count < 1 || count > MSM_MAX_GROUP) return EZKL_ERR_INVALID;
     const unsigned Z = (unsigned)count;
-    const fe_t* scalars = cols[0];
     const WinPlan wp = T->wp;
     const uint32_t W = wp.W, bits = wp.cmax() - 1;
     const uint32_t nb = 1u << bits;
@@ -1131,7 +1150,6 @@ static int msm_enqueue(Ctx* c, MsmSlot& sl, hipStream_t st, MsmTable* T, size_t 
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     size_t off = 0;
     auto carve = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    size_t o_list = carve(MSM_MAX_GROUP * sizeof(void*));   // (first slab only) the group's scalar-column pointers
     size_t o_ent = carve(npairs * 8), o_vals = carve(npairs * 4), o_offs = carve(((size_t)nb + 1) * 4);
     const uint32_t NQ = NP + 1;                          // + bucket 0's own partition (msm_part_of)
     size_t o_pcnt = carve((NQ + 1) * 4), o_pbase = carve((NQ + 1) * 4), o_wgh = carve((size_t)sgrid * NQ * 4), o_wgc = carve((size_t)sgrid * NQ * 4);
@@ -1152,12 +1170,8 @@ static int msm_enqueue(Ctx* c, MsmSlot& sl, hipStream_t st, MsmTable* T, size_t 
     rc = slot_prepare(sl, off * count, count);
     if (rc) return rc;
     uint8_t* S = sl.scratch;
-    const fe_t* const* scal_list = nullptr;
-    if (count > 1) {
-        for (size_t j = 0; j < count; j++) sl.list_pinned[j] = cols[j];
-        EZ_HIP(hipMemcpyAsync(S + o_list, sl.list_pinned, count * sizeof(void*), hipMemcpyHostToDevice, st));
-        scal_list = (const fe_t* const*)(S + o_list);
-    }
+    MsmCols kcols;                                        // the group's scalar columns, by value (a single MSM: col[0], the same path)
+    for (size_t j = 0; j < MSM_MAX_GROUP; j++) kcols.col[j] = cols[j < count ? j : 0];
     uint2* entries = (uint2*)(S + o_ent);
     uint32_t* vals = (uint32_t*)(S + o_vals);
     uint32_t* offs = (uint32_t*)(S + o_offs);
@@ -1187,12 +1201,12 @@ static int msm_enqueue(Ctx* c, MsmSlot& sl, hipStream_t st, MsmTable* T, size_t 
         if (timed_chain) EZ_HIP(hipEventRecord(m0, st));
     }
     // the chain's counters, bin totals and planes are zeroed by the histogram kernel (no memset command in front of the chain: round 5)
-    hipLaunchKernelGGL(msm_hist_kernel, dim3(sgrid, 1, Z), dim3(256), 0, st, scalars, n, per_block, wp, LB, NP, wghist, wgcnt, scal_list, hcnt,
+    hipLaunchKernelGGL(msm_hist_kernel, dim3(sgrid, 1, Z), dim3(256), 0, st, kcols, n, per_block, wp, LB, NP, wghist, wgcnt, hcnt,
                        (uint32_t)(zero_bytes / 4), bstride);
     hipLaunchKernelGGL(msm_hist_scan_kernel, dim3(cdiv(NQ, 32), 1, Z), dim3(1024), 0, st, wghist, sgrid, NQ, pcnt, bstride);
     hipLaunchKernelGGL(msm_part_scan_kernel, dim3(1, 1, Z), dim3(1024), 0, st, pcnt, NQ, pbase, bflag, blist, bcnt, bstride);
-    hipLaunchKernelGGL(msm_partition_kernel, dim3(sgrid, 1, Z), dim3((unsigned)per_block), (3 * ((size_t)NQ + 1) + 2 * per_block * W) * 4, st, scalars, n, per_block, wp,
-                       LB, NP, base_offset, T->n, pbase, wghist, wgcnt, entries, vals, scal_list, bstride);
+    hipLaunchKernelGGL(msm_partition_kernel, dim3(sgrid, 1, Z), dim3((unsigned)per_block), (3 * ((size_t)NQ + 1) + 2 * per_block * W) * 4, st, kcols, n, per_block, wp,
+                       LB, NP, base_offset, T->n, pbase, wghist, wgcnt, entries, vals, bstride);
     hipLaunchKernelGGL(msm_binsort_kernel, dim3(NP + MSM_BIG_BLOCKS * MSM_BIG_ROWS, 1, Z), dim3(512), MSM_BINSORT_STAGE * 4, st, entries, pbase, LB, NP, bflag, offs,
                        vals, bkt, blist, bcnt, btot, boff, bstride);
     hipLaunchKernelGGL(msm_bigsort_scatter_kernel, dim3(MSM_BIG_BLOCKS, MSM_BIG_ROWS, Z), dim3(512), 0, st, entries, pbase, LB, blist, bcnt, btot, boff, offs,
