@@ -266,6 +266,31 @@ struct Field {
         o.v[0] = 1;
         return mul(a, o);
     }
+    // a / R mod p, canonical: the value from_mont returns, by the eight reduction rounds of the product alone (a * 1 has no a * b half to
+    // compute).  Per round m = t[0] * INV and t = (t + m p) / 2^32: the eight products m * p[j] + t[j] cannot overflow 64 bits and are
+    // independent of each other, one carry chain then adds each low half to the high half below it.  Every round keeps t < 2^256
+    // ((2^256 + 2^32 p) / 2^32 < 2^224 + p), the last leaves t <= p for any 256-bit a, so one conditional subtraction makes it canonical.
+    // 8 x (1 + 8 + 8) + 24 instructions, inlined, against the ~260 of the generic product and its call.
+    EZ_HD static fe_t redc(const fe_t& a) {
+        uint32_t t[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) t[i] = a.v[i];
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const uint32_t m = t[0] * P::INV;
+            uint64_t pr[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) pr[j] = mad_wide(m, P::MOD[j], t[j]);       // the low half of pr[0] is 0 by the choice of m
+            uint32_t c = 0;
+#pragma unroll
+            for (int j = 0; j < 7; j++) t[j] = addc32((uint32_t)pr[j + 1], (uint32_t)(pr[j] >> 32), c);
+            t[7] = (uint32_t)(pr[7] >> 32) + c;
+        }
+        fe_t r;
+#pragma unroll
+        for (int i = 0; i < 8; i++) r.v[i] = t[i];
+        return reduce_once(r);
+    }
     EZ_HD static fe_t to_mont(const fe_t& a) { return mul(a, r2()); }
 
     // a^e, e given as 8 x u32 little-endian (host or device; used for inversion / omega powers)

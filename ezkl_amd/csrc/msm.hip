@@ -12,9 +12,10 @@
 //                      chosen by the cost model n*W + 4*#buckets.
 //   * hist / scans / partition : scalar -> canonical -> (s > r/2 ? r - s, negated) -> signed digits (the r - s trick turns
 //                      witness-like small negative values, src/fieldutils.rs:9-17, into one-digit scalars).  No global atomics:
-//                      every workgroup histograms its slice in LDS, a column scan gives (workgroup, partition) start slots, the
-//                      partition pass ranks its (bucket, table index | sign) pairs in 104 KiB of LDS by the LOW bucket bits and
-//                      writes them out in staged order; bucket 0 (+-1 digits, carries) is a partition of its own.
+//                      every workgroup histograms its slice (tile) in LDS, a column scan gives (tile, partition) start slots, the
+//                      partition pass (persistent workgroups, one per CU, walking the tiles) ranks a tile's (bucket, table index | sign)
+//                      pairs in 104 KiB of LDS by the LOW bucket bits and writes them out in staged order; bucket 0 (+-1 digits,
+//                      carries) is a partition of its own.  Both passes: Fr::redc, then msm_recode (a bit buffer fed limb by limb).
 //   * binsort        : one workgroup per partition, counting sort on the remaining bucket bits in LDS, contiguous output, bucket
 //                      offsets + empty-bucket marks; oversized partitions (skewed witnesses) go through bigsort_{count,scatter}.
 //   * accumulate     : balanced SEGMENTED lanes -- lane t owns sorted pairs [t*L, (t+1)*L) whatever the bucket boundaries, L
@@ -232,8 +233,8 @@ __device__ __forceinline__ bool gt_half_r(const fe_t& s) {      // s > (r-1)/2  
 }
 // canonical scalar, negated into [0, (r-1)/2] when that is shorter: s*P = (r-s)*(-P).  Small negative
 // witness values (src/fieldutils.rs:9-17) thereby become single-digit scalars.
-__device__ __forceinline__ fe_t msm_canon(const fe_t* scalars, size_t i, uint32_t& neg) {
-    fe_t s = Fr::from_mont(ld_fe(scalars + i));
+__device__ __forceinline__ fe_t msm_canon(const fe_t& mont, uint32_t& neg) {
+    fe_t s = Fr::redc(mont);                   // field.hpp: the reduction rounds alone, inlined (no a * 1 product, no call that drains the loads)
     neg = 0;
     if (gt_half_r(s)) {
         uint32_t br = 0;
@@ -243,47 +244,43 @@ __device__ __forceinline__ fe_t msm_canon(const fe_t* scalars, size_t i, uint32_
     }
     return s;
 }
-// the low c bits of s (c < 32), then s >>= c.  The windows are consumed by SHIFTING the scalar down: indexing its limbs with a
-// run-time window offset (s.v[off >> 5]) put every scalar of the sort passes into scratch memory (144 B per lane in the
-// histogram pass) and each digit cost two scratch loads.
-__device__ __forceinline__ uint32_t msm_take_bits(fe_t& s, uint32_t c) {
-    const uint32_t d = s.v[0] & ((1u << c) - 1u);
+// The signed-digit recoding of Q scalars side by side: calls f(q, w, bucket, sign) for every non-zero signed digit of scalar q in window w
+// (bucket = |digit| - 1), window by window, the Q scalars interleaved inside a window.
+// The limbs are walked by an outer loop that is unrolled at COMPILE time and feed a 64-bit bit buffer per scalar; a window is emitted while
+// the buffer holds at least its width.  Nothing is indexed at run time (s.v[off >> 5] with a run-time window offset put every scalar of the
+// sort passes into scratch memory), and nothing dead is shifted: the form before this one shifted all eight limbs down at every window, 8
+// instructions per digit where one 64-bit shift does.  `have` (bits in the buffer), w and the width are wave-uniform.
+// Before a refill have < width <= 23, so have + 32 <= 54 bits fit; a plan covers 254 <= 256 bits (pick_plan), so the last window has been
+// emitted when the eighth limb is in.  Recoding: raw = window bits + carry; raw > half is the negative digit raw - 2^c with a carry into the
+// next window (raw == 2^c: digit 0 with a carry); the sign of a digit is flipped by `neg` (msm_canon).
+template <int Q, class F>
+__device__ __forceinline__ void msm_recode(const fe_t (&s)[Q], const uint32_t (&neg)[Q], const WinPlan& wp, F&& f) {
+    uint64_t buf[Q];
+    uint32_t carry[Q];
 #pragma unroll
-    for (int k = 0; k < 7; k++) s.v[k] = __builtin_amdgcn_alignbit(s.v[k + 1], s.v[k], c);
-    s.v[7] >>= c;
-    return d;
-}
-// calls f(w, bucket, sign) for every non-zero signed c-bit digit (bucket = |digit| - 1)
-template <class F>
-__device__ __forceinline__ void msm_foreach_digit(fe_t s, uint32_t neg, const WinPlan& wp, F&& f) {
-    uint32_t carry = 0;
-    for (uint32_t w = 0; w < wp.W; w++) {
-        const uint32_t c = wp.width(w), half = 1u << (c - 1);
-        uint32_t raw = msm_take_bits(s, c) + carry;
-        if (raw > half) {                       // negative digit raw - 2^c, carry into the next window
-            carry = 1;
-            if (raw != (1u << c)) f(w, (1u << c) - raw - 1u, neg ^ 1u);   // raw == 2^c: digit 0 with a carry
-        } else {
-            carry = 0;
-            if (raw) f(w, raw - 1u, neg);
+    for (int q = 0; q < Q; q++) { buf[q] = 0; carry[q] = 0; }
+    uint32_t have = 0, w = 0, c = wp.width(0);
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+#pragma unroll
+        for (int q = 0; q < Q; q++) buf[q] |= (uint64_t)s[q].v[k] << have;
+        have += 32;
+        while (have >= c && w < wp.W) {
+            const uint32_t full = 1u << c, half = full >> 1;
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                const uint32_t raw = ((uint32_t)buf[q] & (full - 1u)) + carry[q];
+                buf[q] >>= c;
+                const uint32_t minus = raw > half ? 1u : 0u;
+                const uint32_t mag = minus ? full - raw : raw;
+                carry[q] = minus;
+                if (mag) f(q, w, mag - 1u, neg[q] ^ minus);
+            }
+            have -= c;
+            w++;
+            c = wp.width(w);
         }
     }
-}
-
-// one window of the recoding above (consumed from s), for loops that interleave several scalars: returns whether the digit is non-zero
-__device__ __forceinline__ bool msm_digit_step(fe_t& s, uint32_t neg, uint32_t c, uint32_t& carry, uint32_t& bucket, uint32_t& sign) {
-    const uint32_t half = 1u << (c - 1);
-    const uint32_t raw = msm_take_bits(s, c) + carry;
-    if (raw > half) {
-        carry = 1;
-        bucket = (1u << c) - raw - 1u;
-        sign = neg ^ 1u;
-        return raw != (1u << c);
-    }
-    carry = 0;
-    bucket = raw - 1u;
-    sign = neg;
-    return raw != 0;
 }
 
 // inclusive prefix sum of one value per thread over the workgroup (blockDim.x a multiple of 64, at most 1024): shuffles inside the waves, the
@@ -323,9 +320,9 @@ __device__ __forceinline__ uint32_t msm_block_scan(uint32_t v, uint32_t* wsum, u
 // rows into per-(workgroup, partition) start slots; the partition pass ranks its pairs with LDS atomics into an LDS
 // staging area grouped by partition and writes them out in staged order (runs of one partition leave as whole cache lines).
 __global__ __launch_bounds__(256) void msm_hist_kernel(MsmCols cols, size_t n, size_t per_block, WinPlan wp,
-                                                       uint32_t LB, uint32_t NP, uint32_t* wg_hist, uint32_t* wg_cnt,
+                                                       uint32_t LB, uint32_t NP, uint32_t* wg_hist,
                                                        uint32_t* zero_base, uint32_t zero_words, size_t bstride) {
-    BOFF(); BSH(wg_hist); BSH(wg_cnt);
+    BOFF(); BSH(wg_hist);
     const fe_t* scalars = msm_col(cols);
     if (zero_base) {                                                      // the chain's counters, bin totals and planes start at zero
         BSH(zero_base);
@@ -336,61 +333,90 @@ __global__ __launch_bounds__(256) void msm_hist_kernel(MsmCols cols, size_t n, s
     for (uint32_t p = threadIdx.x; p < NQ; p += 256) lh[p] = 0;
     __syncthreads();
     size_t lo = (size_t)blockIdx.x * per_block, hi = lo + per_block < n ? lo + per_block : n;
-    for (size_t i0 = lo + threadIdx.x; i0 < hi; i0 += 4 * 256) {          // four scalars in flight per thread
+    for (size_t i0 = lo + threadIdx.x; i0 < hi; i0 += 4 * 256) {
+        // four scalars per thread: their eight 16-byte loads are all issued here, ahead of the first reduction (which is inlined arithmetic,
+        // so the compiler waits for each scalar with a counted vmcnt and the other loads stay in flight): one HBM round trip per thread
         fe_t s[4];
-        uint32_t neg[4], carry[4] = {0, 0, 0, 0};
+        uint32_t neg[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const size_t i = i0 + (size_t)q * 256;
-            if (i < hi) s[q] = msm_canon(scalars, i, neg[q]);
-            else { s[q] = Fr::zero(); neg[q] = 0; }
+            s[q] = i < hi ? ld_fe(scalars + i) : Fr::zero();
         }
-        for (uint32_t w = 0; w < wp.W; w++) {
-            const uint32_t c = wp.width(w);
 #pragma unroll
-            for (int q = 0; q < 4; q++) {
-                uint32_t bucket, sign;
-                if (msm_digit_step(s[q], neg[q], c, carry[q], bucket, sign)) atomicAdd(&lh[msm_part_of(bucket, NP)], 1u);
-            }
-        }
+        for (int q = 0; q < 4; q++) s[q] = msm_canon(s[q], neg[q]);
+        msm_recode<4>(s, neg, wp, [&](int, uint32_t, uint32_t bucket, uint32_t) { atomicAdd(&lh[msm_part_of(bucket, NP)], 1u); });
     }
     __syncthreads();
-    for (uint32_t p = threadIdx.x; p < NQ; p += 256) {                 // row of this workgroup, coalesced; wg_hist is scanned in place later,
-        wg_hist[(size_t)blockIdx.x * NQ + p] = lh[p];                   // wg_cnt keeps the raw counts for the partition pass's local ranking
-        wg_cnt[(size_t)blockIdx.x * NQ + p] = lh[p];
-    }
+    // row of this workgroup, coalesced; wg_hist is scanned in place later (the partition pass takes the raw counts back as row differences)
+    for (uint32_t p = threadIdx.x; p < NQ; p += 256) wg_hist[(size_t)blockIdx.x * NQ + p] = lh[p];
 }
-// wg_hist[g][p] (G workgroups x NP partitions) -> in place, the exclusive prefix over g of column p; part_count[p] = column
-// total.  One workgroup per 32 columns: thread (c, j) sums the j-th chunk of G/32 rows of column c (a row segment of 32
-// columns is one 128-byte line), the 32 chunk sums of a column are scanned in LDS, then the rows are rewritten.
+// wg_hist[g][p] (G workgroups x NP partitions) -> in place, the exclusive prefix over g of column p; part_count[p] = column total.
+// One workgroup per FOUR columns, so that a table of 1025 columns is scanned by 257 workgroups (one per CU) and not by 33: thread (c, j)
+// owns the j-th chunk of ceil(G / 256) rows of column c -- four rows at G = 1024 -- loads them all before it adds any (up to eight at
+// a time, which stay in registers for the rewrite), the 256 chunk sums of a column are scanned with shuffles (stride 4) and one hop
+// through LDS, then the rows are rewritten.  Workgroups are independent of each other.
+// A 128-byte line of a row is shared by eight workgroups.  Workgroups b and b + 8 run on the same XCD, so the strips are dealt to let
+// those eight be neighbours there and the line be fetched into one L2 (placement is a matter of speed only: any bijection is correct).
+static constexpr uint32_t MSM_SCAN_COLS = 4;
 __global__ __launch_bounds__(1024) void msm_hist_scan_kernel(uint32_t* wg_hist, uint32_t G, uint32_t NP, uint32_t* part_count, size_t bstride) {
     BOFF(); BSH(wg_hist); BSH(part_count);
-    __shared__ uint32_t sums[32][33];
-    const uint32_t c = threadIdx.x & 31, j = threadIdx.x >> 5;
-    const uint32_t p = blockIdx.x * 32 + c;
-    const uint32_t chunk = (G + 31) / 32, g0 = j * chunk, g1 = g0 + chunk < G ? g0 + chunk : G;
-    uint32_t s = 0;
-    if (p < NP)
-        for (uint32_t g = g0; g < g1; g++) s += wg_hist[(size_t)g * NP + p];
-    sums[j][c] = s;
+    __shared__ uint32_t wsum[64];
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const uint32_t c = t & (MSM_SCAN_COLS - 1u), j = t / MSM_SCAN_COLS;               // 256 chunks of rows
+    const uint32_t nstrips = gridDim.x, sq = nstrips / 8, sr = nstrips % 8, xcd = blockIdx.x % 8;
+    const uint32_t strip = (xcd < sr ? xcd * (sq + 1) : sr * (sq + 1) + (xcd - sr) * sq) + blockIdx.x / 8;
+    const uint32_t p = strip * MSM_SCAN_COLS + c;
+    const uint32_t chunk = (G + 255) / 256, g0 = j * chunk, g1 = p < NP ? (g0 + chunk < G ? g0 + chunk : G) : 0;
+    uint32_t v[8], sum = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q++) v[q] = g0 + q < g1 ? wg_hist[(size_t)(g0 + q) * NP + p] : 0u;
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q++) sum += v[q];
+    for (uint32_t gb = g0 + 8; gb < g1; gb += 8) {                                     // G > 2048 only
+        uint32_t u[8];
+#pragma unroll
+        for (uint32_t q = 0; q < 8; q++) u[q] = gb + q < g1 ? wg_hist[(size_t)(gb + q) * NP + p] : 0u;
+#pragma unroll
+        for (uint32_t q = 0; q < 8; q++) sum += u[q];
+    }
+    // inclusive scan over j for each c: lanes 4 apart inside the wave, then the 16 x 4 wave totals by wave 0
+    uint32_t x = sum;
+#pragma unroll
+    for (uint32_t d = MSM_SCAN_COLS; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    if (lane >= 64 - MSM_SCAN_COLS) wsum[wave * MSM_SCAN_COLS + c] = x;
     __syncthreads();
-    if (j == 0) {                                  // 32 threads, one per column: serial exclusive scan over the 32 chunks
-        uint32_t run = 0;
-        for (uint32_t q = 0; q < 32; q++) {
-            uint32_t v = sums[q][c];
-            sums[q][c] = run;
-            run += v;
+    if (wave == 0) {
+        uint32_t s = wsum[lane];
+#pragma unroll
+        for (uint32_t d = MSM_SCAN_COLS; d < 64; d <<= 1) {
+            const uint32_t y = __shfl_up(s, d, 64);
+            if (lane >= d) s += y;
         }
-        if (p < NP) part_count[p] = run;
+        wsum[lane] = s;
     }
     __syncthreads();
-    if (p < NP) {
-        uint32_t run = sums[j][c];
-        for (uint32_t g = g0; g < g1; g++) {
-            uint32_t v = wg_hist[(size_t)g * NP + p];
-            wg_hist[(size_t)g * NP + p] = run;
-            run += v;
+    uint32_t run = x - sum + (wave ? wsum[(wave - 1) * MSM_SCAN_COLS + c] : 0u);
+    if (j == 0 && p < NP) part_count[p] = wsum[15 * MSM_SCAN_COLS + c];
+#pragma unroll
+    for (uint32_t q = 0; q < 8; q++)
+        if (g0 + q < g1) {
+            wg_hist[(size_t)(g0 + q) * NP + p] = run;
+            run += v[q];
         }
+    for (uint32_t gb = g0 + 8; gb < g1; gb += 8) {
+        uint32_t u[8];
+#pragma unroll
+        for (uint32_t q = 0; q < 8; q++) u[q] = gb + q < g1 ? wg_hist[(size_t)(gb + q) * NP + p] : 0u;
+#pragma unroll
+        for (uint32_t q = 0; q < 8; q++)
+            if (gb + q < g1) {
+                wg_hist[(size_t)(gb + q) * NP + p] = run;
+                run += u[q];
+            }
     }
 }
 // exclusive scan of <= 5120 partition counts (five per thread); part_base[NQ] = the number of pairs.  Also lists the oversized
@@ -434,17 +460,24 @@ __global__ __launch_bounds__(1024) void msm_part_scan_kernel(const uint32_t* par
     __shared__ uint32_t sh[1024];
     msm_part_scan_body(part_count, NQ, part_base, big_flag, big_list, big_count, sh);
 }
-// One pass, one scalar per thread.  A workgroup first ranks its (up to MSM_PART_STAGE) pairs into LDS grouped by partition
-// (start[p] = exclusive scan of its own histogram row, cursors advanced with LDS atomics), then writes them out in staged order:
+// One scalar per thread and tile.  A workgroup first ranks the (up to MSM_PART_STAGE) pairs of its tile into LDS grouped by partition
+// (start[p] = exclusive scan of the tile's histogram row, cursors advanced with LDS atomics), then writes them out in staged order:
 // consecutive lanes hold consecutive pairs of the same partition, i.e. consecutive global slots
-//     slot = part_base[p] + (pairs of partition p in earlier workgroups) + (index - start[p]).
+//     slot = part_base[p] + (pairs of partition p in earlier tiles) + (index - start[p]).
 // The 13.6 M pairs of a 2^20-point MSM used to leave as 13.6 M scattered 8-byte stores, one L2 request each (~100 of the
 // kernel's 146 us); staged, a run of ~13 pairs of one partition is two cache lines.
-__global__ __launch_bounds__(1024) void msm_partition_kernel(MsmCols cols, size_t n, size_t per_block, WinPlan wp,
+// The workgroups are PERSISTENT: min(G, one per CU) of them (144 KiB of LDS: one fits a CU) loop over the tiles blockIdx.x, blockIdx.x +
+// gridDim.x, ...; the TILE index is the row of wg_hist and the slice of scalars, so a pair lands where one workgroup per tile put it.
+// A tile's raw counts are the differences of its scanned row and the next one (part_count for the last row).  Before a workgroup
+// writes a tile out it loads what its next tile starts with -- the scalar and the first MSM_PART_PF counts per thread of both rows
+// (all of them while there are at most MSM_PART_PF partitions per thread: 1025 partitions, 1024 threads) -- so only a workgroup's first
+// tile starts cold.
+static constexpr uint32_t MSM_PART_PF = 2;
+__global__ __launch_bounds__(1024) void msm_partition_kernel(MsmCols cols, size_t n, size_t per_block, uint32_t G, WinPlan wp,
                                                              uint32_t LB, uint32_t NP, size_t base_offset, size_t tab_stride,
-                                                             const uint32_t* part_base, const uint32_t* wg_hist, const uint32_t* wg_cnt, uint2* entries,
+                                                             const uint32_t* part_base, const uint32_t* wg_hist, const uint32_t* part_count, uint2* entries,
                                                              uint32_t* vals, size_t bstride) {
-    BOFF(); BSH(part_base); BSH(wg_hist); BSH(wg_cnt); BSH(entries); BSH(vals);
+    BOFF(); BSH(part_base); BSH(wg_hist); BSH(part_count); BSH(entries); BSH(vals);
     const fe_t* scalars = msm_col(cols);
     extern __shared__ uint32_t plds[];
     __shared__ uint32_t tsum[1024];
@@ -454,43 +487,77 @@ __global__ __launch_bounds__(1024) void msm_partition_kernel(MsmCols cols, size_
     uint32_t* gbase = plds + 2 * (NQ + 1);     // NQ: global slot of the workgroup's first pair of partition p
     uint2* stage = reinterpret_cast<uint2*>(plds + 3 * (NQ + 1));
     const uint32_t t = threadIdx.x, T = blockDim.x;
-    // exclusive scan of this workgroup's histogram row: K consecutive partitions per thread, then a scan over threads
-    const uint32_t K = (NQ + T - 1) / T;
-    uint32_t loc = 0;
-    for (uint32_t q = 0; q < K; q++) {
-        const uint32_t p = t * K + q;
-        if (p < NQ) loc += wg_cnt[(size_t)blockIdx.x * NQ + p];
-    }
-    uint32_t total;
-    uint32_t run = msm_block_scan(loc, tsum, total) - loc;
-    for (uint32_t q = 0; q < K; q++) {
-        const uint32_t p = t * K + q;
-        if (p < NQ) {
-            start[p] = run;
-            cursor[p] = run;
-            gbase[p] = part_base[p] + wg_hist[(size_t)blockIdx.x * NQ + p];
-            run += wg_cnt[(size_t)blockIdx.x * NQ + p];
-        }
-    }
-    __syncthreads();
-    const size_t lo = (size_t)blockIdx.x * per_block, hi = lo + per_block < n ? lo + per_block : n;
-    const size_t i = lo + t;
-    if (i < hi) {
-        uint32_t neg;
-        fe_t s = msm_canon(scalars, i, neg);
-        msm_foreach_digit(s, neg, wp, [&](uint32_t w, uint32_t bucket, uint32_t sign) {
-            const uint32_t r = atomicAdd(&cursor[msm_part_of(bucket, NP)], 1u);
-            stage[r] = make_uint2((uint32_t)(w * tab_stride + base_offset + i) | (sign << 31), bucket);
-        });
-    }
-    __syncthreads();
+    const uint32_t K = (NQ + T - 1) / T;       // consecutive partitions per thread
     const uint32_t PB = 31 - __clz(NP);
-    for (uint32_t idx = t; idx < total; idx += T) {
-        const uint2 e = stage[idx];
-        const uint32_t p = msm_part_of(e.y, NP);
-        const uint32_t slot = gbase[p] + (idx - start[p]);
-        if (p) entries[slot] = make_uint2(e.x, e.y >> PB);
-        else vals[slot] = e.x;                              // bucket 0: already in its final place (its partition comes first)
+    // scanned count of (tile, p) and of the row after it
+    auto row = [&](uint32_t tile, uint32_t p) { return wg_hist[(size_t)tile * NQ + p]; };
+    auto row_next = [&](uint32_t tile, uint32_t p) { return tile + 1 < G ? wg_hist[(size_t)(tile + 1) * NQ + p] : part_count[p]; };
+    fe_t sm[1];
+    uint32_t h0[MSM_PART_PF], h1[MSM_PART_PF];
+    auto fetch = [&](uint32_t tile) {
+        const size_t lo = (size_t)tile * per_block, hi = lo + per_block < n ? lo + per_block : n;
+        sm[0] = lo + t < hi ? ld_fe(scalars + lo + t) : Fr::zero();
+#pragma unroll
+        for (uint32_t q = 0; q < MSM_PART_PF; q++) {
+            const uint32_t p = t * K + q;
+            const bool in = q < K && p < NQ;
+            h0[q] = in ? row(tile, p) : 0u;
+            h1[q] = in ? row_next(tile, p) : 0u;
+        }
+    };
+    if (blockIdx.x < G) fetch(blockIdx.x);
+    for (uint32_t tile = blockIdx.x; tile < G; tile += gridDim.x) {
+        // exclusive scan of the tile's raw counts: K consecutive partitions per thread, then a scan over threads (its first barrier also
+        // ends the previous tile's write-out before start / cursor / gbase / stage are written again)
+        uint32_t loc = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < MSM_PART_PF; q++) loc += h1[q] - h0[q];
+        for (uint32_t q = MSM_PART_PF; q < K; q++) {
+            const uint32_t p = t * K + q;
+            if (p < NQ) loc += row_next(tile, p) - row(tile, p);
+        }
+        uint32_t total;
+        uint32_t run = msm_block_scan(loc, tsum, total) - loc;
+#pragma unroll
+        for (uint32_t q = 0; q < MSM_PART_PF; q++) {
+            const uint32_t p = t * K + q;
+            if (q < K && p < NQ) {
+                start[p] = run;
+                cursor[p] = run;
+                gbase[p] = part_base[p] + h0[q];
+                run += h1[q] - h0[q];
+            }
+        }
+        for (uint32_t q = MSM_PART_PF; q < K; q++) {
+            const uint32_t p = t * K + q;
+            if (p < NQ) {
+                const uint32_t r0 = row(tile, p);
+                start[p] = run;
+                cursor[p] = run;
+                gbase[p] = part_base[p] + r0;
+                run += row_next(tile, p) - r0;
+            }
+        }
+        __syncthreads();
+        const size_t lo = (size_t)tile * per_block, hi = lo + per_block < n ? lo + per_block : n;
+        const size_t i = lo + t;
+        if (i < hi) {
+            uint32_t neg[1];
+            sm[0] = msm_canon(sm[0], neg[0]);
+            msm_recode<1>(sm, neg, wp, [&](int, uint32_t w, uint32_t bucket, uint32_t sign) {
+                const uint32_t r = atomicAdd(&cursor[msm_part_of(bucket, NP)], 1u);
+                stage[r] = make_uint2((uint32_t)(w * tab_stride + base_offset + i) | (sign << 31), bucket);
+            });
+        }
+        __syncthreads();
+        if (tile + gridDim.x < G) fetch(tile + gridDim.x);     // the next tile's loads travel under this tile's write-out
+        for (uint32_t idx = t; idx < total; idx += T) {
+            const uint2 e = stage[idx];
+            const uint32_t p = msm_part_of(e.y, NP);
+            const uint32_t slot = gbase[p] + (idx - start[p]);
+            if (p) entries[slot] = make_uint2(e.x, e.y >> PB);
+            else vals[slot] = e.x;                              // bucket 0: already in its final place (its partition comes first)
+        }
     }
 }
 // atomicAdd(&cnt[key], 1) for every active lane, with ONE atomic when the whole wave holds the same key (a heavy bucket:
@@ -1152,7 +1219,7 @@ static int msm_enqueue(Ctx* c, MsmSlot& sl, hipStream_t st, MsmTable* T, size_t 
     auto carve = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
     size_t o_ent = carve(npairs * 8), o_vals = carve(npairs * 4), o_offs = carve(((size_t)nb + 1) * 4);
     const uint32_t NQ = NP + 1;                          // + bucket 0's own partition (msm_part_of)
-    size_t o_pcnt = carve((NQ + 1) * 4), o_pbase = carve((NQ + 1) * 4), o_wgh = carve((size_t)sgrid * NQ * 4), o_wgc = carve((size_t)sgrid * NQ * 4);
+    size_t o_pcnt = carve((NQ + 1) * 4), o_pbase = carve((NQ + 1) * 4), o_wgh = carve((size_t)sgrid * NQ * 4);
     size_t o_heavy = carve((size_t)nb * 4), o_chunks = carve(((size_t)nlanes + 1) * 4);
     const size_t nbins = (size_t)1 << LB;
     // ONE region that starts every chain at zero: the counters (hcnt[0..2]), the bin totals of the multi-workgroup
@@ -1175,7 +1242,7 @@ static int msm_enqueue(Ctx* c, MsmSlot& sl, hipStream_t st, MsmTable* T, size_t 
     uint2* entries = (uint2*)(S + o_ent);
     uint32_t* vals = (uint32_t*)(S + o_vals);
     uint32_t* offs = (uint32_t*)(S + o_offs);
-    uint32_t *pcnt = (uint32_t*)(S + o_pcnt), *pbase = (uint32_t*)(S + o_pbase), *wghist = (uint32_t*)(S + o_wgh), *wgcnt = (uint32_t*)(S + o_wgc);
+    uint32_t *pcnt = (uint32_t*)(S + o_pcnt), *pbase = (uint32_t*)(S + o_pbase), *wghist = (uint32_t*)(S + o_wgh);
     uint32_t *heavy = (uint32_t*)(S + o_heavy), *hcnt = (uint32_t*)(S + o_hcnt), *chunks = (uint32_t*)(S + o_chunks);   // hcnt[0] buckets, [1] chunks
     uint32_t* lfirst = (uint32_t*)(S + o_lfirst);
     uint32_t *bflag = (uint32_t*)(S + o_bflag), *blist = (uint32_t*)(S + o_blist), *btot = (uint32_t*)(S + o_btot), *boff = (uint32_t*)(S + o_boff);
@@ -1201,12 +1268,14 @@ static int msm_enqueue(Ctx* c, MsmSlot& sl, hipStream_t st, MsmTable* T, size_t 
         if (timed_chain) EZ_HIP(hipEventRecord(m0, st));
     }
     // the chain's counters, bin totals and planes are zeroed by the histogram kernel (no memset command in front of the chain: round 5)
-    hipLaunchKernelGGL(msm_hist_kernel, dim3(sgrid, 1, Z), dim3(256), 0, st, kcols, n, per_block, wp, LB, NP, wghist, wgcnt, hcnt,
+    hipLaunchKernelGGL(msm_hist_kernel, dim3(sgrid, 1, Z), dim3(256), 0, st, kcols, n, per_block, wp, LB, NP, wghist, hcnt,
                        (uint32_t)(zero_bytes / 4), bstride);
-    hipLaunchKernelGGL(msm_hist_scan_kernel, dim3(cdiv(NQ, 32), 1, Z), dim3(1024), 0, st, wghist, sgrid, NQ, pcnt, bstride);
+    hipLaunchKernelGGL(msm_hist_scan_kernel, dim3(cdiv(NQ, MSM_SCAN_COLS), 1, Z), dim3(1024), 0, st, wghist, sgrid, NQ, pcnt, bstride);
     hipLaunchKernelGGL(msm_part_scan_kernel, dim3(1, 1, Z), dim3(1024), 0, st, pcnt, NQ, pbase, bflag, blist, bcnt, bstride);
-    hipLaunchKernelGGL(msm_partition_kernel, dim3(sgrid, 1, Z), dim3((unsigned)per_block), (3 * ((size_t)NQ + 1) + 2 * per_block * W) * 4, st, kcols, n, per_block, wp,
-                       LB, NP, base_offset, T->n, pbase, wghist, wgcnt, entries, vals, bstride);
+    // persistent: one workgroup per CU (its 144 KiB of LDS leave room for no second one) walks the tiles
+    const unsigned pgrid = sgrid < (unsigned)c->num_cus ? sgrid : (unsigned)c->num_cus;
+    hipLaunchKernelGGL(msm_partition_kernel, dim3(pgrid, 1, Z), dim3((unsigned)per_block), (3 * ((size_t)NQ + 1) + 2 * per_block * W) * 4, st, kcols, n, per_block,
+                       (uint32_t)sgrid, wp, LB, NP, base_offset, T->n, pbase, wghist, pcnt, entries, vals, bstride);
     hipLaunchKernelGGL(msm_binsort_kernel, dim3(NP + MSM_BIG_BLOCKS * MSM_BIG_ROWS, 1, Z), dim3(512), MSM_BINSORT_STAGE * 4, st, entries, pbase, LB, NP, bflag, offs,
                        vals, bkt, blist, bcnt, btot, boff, bstride);
     hipLaunchKernelGGL(msm_bigsort_scatter_kernel, dim3(MSM_BIG_BLOCKS, MSM_BIG_ROWS, Z), dim3(512), 0, st, entries, pbase, LB, blist, bcnt, btot, boff, offs,
