@@ -22,292 +22,17 @@
 #include <unistd.h>
 #include "ezkl_hip.hpp"
 #include "ezkl_prover.h"
-#include "hostfield.hpp"
-#include "transcript.hpp"
-#include "pairing.hpp"
+#include "cs.hpp"
+#include "keyfile.hpp"
+#include "verify.hpp"
 #include "../witness_plan.hpp"
 
 namespace ezkl_prover {
 using ezkl_hip::check;
 using ezkl_hip::DeviceColumn;
-using ezkl_hip::Error;
 using Col = std::shared_ptr<DeviceColumn>;
 
 static thread_local std::string g_last_error;
-// blinding factors: halo2's ConstraintSystem::blinding_factors() = max(3, most queries of one advice column) + 2, carried by the
-// blob or derived from the queries; ezkl's circuits give 5 (/root/reference/src/graph/mod.rs:100).  The last blinding+1 rows are unusable.
-
-// ------------------------------------------------------------------ constraint system
-enum NodeOp : uint32_t { N_CONST = 0, N_ADV, N_FIX, N_INST, N_CHAL, N_NEG, N_ADD, N_SUB, N_MUL };
-struct Node {
-    uint32_t op, a, b;
-    Fe c;
-};
-struct Query {
-    uint32_t col;
-    int32_t rot;
-    bool operator<(const Query& o) const { return col != o.col ? col < o.col : rot < o.rot; }
-    bool operator==(const Query& o) const { return col == o.col && rot == o.rot; }
-};
-struct Lookup {
-    std::vector<std::vector<uint32_t>> inputs;
-    std::vector<uint32_t> table;
-};
-// MSMs sharded by points (ezkl_prover_cs_set_shard): this rank's SRS handles hold points [lo, hi) only
-struct Shard {
-    uint32_t lo = 0, hi = 0;          // hi == 0: not sharded
-    ezkl_fold_fn fold = nullptr;
-    void* user = nullptr;
-    ezkl_gather_fn gather = nullptr;  // optional: the quotient sweep sharded by rows (ezkl_prover_cs_set_sweep_gather)
-    void* gather_user = nullptr;
-    // optional: columns and arguments have owners (ezkl_prover_cs_set_shard_exchange)
-    ezkl_allgather_host_fn allgather_host = nullptr;
-    ezkl_exchange_fn exchange = nullptr;
-    void* xuser = nullptr;
-    mutable uint64_t sharded_sweeps = 0;
-    mutable uint64_t stats[4] = {0, 0, 0, 0};     // ezkl_prover_cs_shard_stats
-    // the SRS handles hold ALL 2^k points on every rank (ezkl_prover_cs_set_shard_full_bases; 288 GB of HBM per GPU: a 2^22 base set
-    // with its window tables is 3.5 GB): a commit batch is then divided by COLUMNS -- whole MSMs, which keep the per-call tail of a
-    // 2^k-point MSM off the critical path instead of paying it on every 2^k / world slice -- and by point ranges inside a column
-    // only when the batch has fewer columns than there are ranks
-    bool full_bases = false;
-    bool on() const { return hi != 0; }
-    // equal power-of-two slices: rank / log2(world) of this one, or false
-    bool geometry(uint32_t n, uint32_t& rank, uint32_t& log_world) const {
-        const uint32_t len = hi - lo;
-        if (!on() || len == 0 || n % len || lo % len) return false;
-        const uint32_t world = n / len;
-        if (world & (world - 1)) return false;
-        rank = lo / len;
-        log_world = 0;
-        while ((1u << log_world) < world) log_world++;
-        return true;
-    }
-};
-// Who does what in one proof.  One rank (or a sharded prover without the exchange callbacks): everything is mine.  Owner mode: witness
-// column / argument number i belongs to rank i mod world; only its owner computes, transforms and commits it.
-struct Topo {
-    uint32_t world = 1, rank = 0, log_world = 0;
-    bool owners = false;
-    bool mine(size_t i) const { return !owners || (uint32_t)(i % world) == rank; }
-    uint32_t owner(size_t i) const { return owners ? (uint32_t)(i % world) : rank; }
-};
-struct ConstraintSystem {
-    uint32_t k = 0, n = 0, n_advice = 0, n_fixed = 0, n_instance = 0, n_challenges = 0;
-    std::vector<uint32_t> advice_phase;
-    std::vector<Node> nodes;
-    std::vector<uint32_t> gates;
-    std::vector<std::pair<uint32_t, uint32_t>> perm;      // (kind = N_ADV | N_FIX | N_INST, col)
-    std::vector<Lookup> lookups;
-    uint32_t usable = 0, degree = 0, chunk = 0, ext_k = 0, n_chunks = 0;
-    uint32_t blinding = 0, minimum_degree = 0;           // 0 = derive / none (blob version 1)
-    uint32_t n_selectors = 0;                             // halo2 selectors behind the fixed columns: sizes the selector section of vk / pk files
-    bool queries_given = false;                           // halo2's order of first query (blob version 2)
-    bool advice_by_pointer = false;                       // ezkl_prover_cs_set_advice_by_pointer
-    std::vector<uint8_t> unblinded;                       // per advice column: unusable rows hold Blind::default() = 1
-    std::array<uint8_t, 32> blob_hash{};                  // keccak256 of the blob: binds gates / lookups / queries into the vk digest
-    std::vector<Query> advice_queries, fixed_queries, instance_queries;
-    std::vector<uint32_t> deg_memo;
-    Shard shard;
-
-    uint32_t deg(uint32_t id) {
-        if (deg_memo[id] != UINT32_MAX) return deg_memo[id];
-        const Node& nd = nodes[id];
-        uint32_t d;
-        switch (nd.op) {
-        case N_CONST: case N_CHAL: d = 0; break;
-        case N_ADV: case N_FIX: case N_INST: d = 1; break;
-        case N_NEG: d = deg(nd.a); break;
-        case N_ADD: case N_SUB: d = std::max(deg(nd.a), deg(nd.b)); break;
-        default: d = deg(nd.a) + deg(nd.b); break;
-        }
-        return deg_memo[id] = d;
-    }
-    void collect(uint32_t id, std::set<Query> out[3], std::vector<uint8_t>& seen) const {
-        if (seen[id]) return;
-        seen[id] = 1;
-        const Node& nd = nodes[id];
-        if (nd.op == N_ADV || nd.op == N_FIX || nd.op == N_INST) out[nd.op - N_ADV].insert(Query{nd.a, (int32_t)nd.b});
-        else if (nd.op == N_NEG) collect(nd.a, out, seen);
-        else if (nd.op >= N_ADD) { collect(nd.a, out, seen); collect(nd.b, out, seen); }
-    }
-    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> perm_chunks() const {
-        std::vector<std::vector<std::pair<uint32_t, uint32_t>>> out;
-        for (size_t i = 0; i < perm.size(); i += chunk) out.emplace_back(perm.begin() + i, perm.begin() + std::min(perm.size(), i + chunk));
-        return out;
-    }
-    void finalize() {
-        n = 1u << k;
-        deg_memo.assign(nodes.size(), UINT32_MAX);
-        uint32_t d = 3;
-        for (uint32_t g : gates) d = std::max(d, deg(g));
-        for (auto& l : lookups) {                          // l_active * phi * prod(f_j + beta) * (t + beta)
-            uint32_t s = 2, tmax = 0;
-            for (auto& t : l.inputs) {
-                uint32_t m = 0;
-                for (uint32_t e : t) m = std::max(m, deg(e));
-                s += m;
-            }
-            for (uint32_t e : l.table) tmax = std::max(tmax, deg(e));
-            d = std::max(d, s + tmax);
-        }
-        degree = d = std::max(d, minimum_degree);
-        chunk = d - 2;
-        ext_k = k;
-        while ((1ull << ext_k) < (uint64_t)n * (d - 1)) ext_k++;
-        std::set<Query> qs[3];
-        std::vector<uint8_t> seen(nodes.size(), 0);
-        for (uint32_t g : gates) collect(g, qs, seen);
-        for (auto& pc : perm) qs[pc.first - N_ADV].insert(Query{pc.second, 0});
-        for (auto& l : lookups) {
-            for (auto& t : l.inputs)
-                for (uint32_t e : t) collect(e, qs, seen);
-            for (uint32_t e : l.table) collect(e, qs, seen);
-        }
-        if (queries_given) {                              // must cover what the expressions read, without duplicates
-            std::vector<Query>* given[3] = {&advice_queries, &fixed_queries, &instance_queries};
-            for (int t = 0; t < 3; t++) {
-                std::set<Query> have(given[t]->begin(), given[t]->end());
-                if (have.size() != given[t]->size()) throw Error(EZKL_ERR_INVALID, "duplicate query");
-                for (auto& q : qs[t])
-                    if (!have.count(q)) throw Error(EZKL_ERR_INVALID, "query lists do not cover the expressions");
-            }
-        } else {
-            advice_queries.assign(qs[0].begin(), qs[0].end());
-            fixed_queries.assign(qs[1].begin(), qs[1].end());
-            instance_queries.assign(qs[2].begin(), qs[2].end());
-        }
-        if (blinding == 0) {                              // halo2 ConstraintSystem::blinding_factors
-            std::map<uint32_t, uint32_t> per_col;
-            uint32_t most = 1;
-            for (auto& q : advice_queries) most = std::max(most, ++per_col[q.col]);
-            blinding = std::max(3u, most) + 2;
-        }
-        if (blinding + 2 > n) throw Error(EZKL_ERR_INVALID, "no usable rows");
-        usable = n - blinding - 1;
-        n_chunks = perm.empty() ? 0 : (uint32_t)((perm.size() + chunk - 1) / chunk);
-    }
-};
-
-struct Reader {
-    const uint8_t* p;
-    size_t left;
-    uint32_t u32() {
-        if (left < 4) throw Error(EZKL_ERR_INVALID, "constraint system blob truncated");
-        uint32_t v;
-        std::memcpy(&v, p, 4);
-        p += 4; left -= 4;
-        return v;
-    }
-    void bytes(void* out, size_t m) {
-        if (left < m) throw Error(EZKL_ERR_INVALID, "constraint system blob truncated");
-        std::memcpy(out, p, m);
-        p += m; left -= m;
-    }
-};
-static void invalid(bool cond, const char* what) {
-    if (cond) throw Error(EZKL_ERR_INVALID, what);
-}
-static std::unique_ptr<ConstraintSystem> parse_cs(const void* blob, size_t len) {
-    Reader r{(const uint8_t*)blob, len};
-    invalid(r.u32() != 0x53435a45u, "bad magic");
-    const uint32_t version = r.u32();
-    invalid(version != 1 && version != 2, "unsupported version");
-    auto cs = std::make_unique<ConstraintSystem>();
-    cs->blob_hash = keccak256((const uint8_t*)blob, len);
-    cs->k = r.u32(); cs->n_advice = r.u32(); cs->n_fixed = r.u32(); cs->n_instance = r.u32(); cs->n_challenges = r.u32();
-    invalid(cs->k < 4 || cs->k > 28, "k out of range");
-    invalid(cs->n_advice > (1u << 16) || cs->n_fixed > (1u << 16) || cs->n_instance > (1u << 16) || cs->n_challenges > (1u << 16), "column count out of range");
-    for (uint32_t i = 0; i < cs->n_advice; i++) {
-        cs->advice_phase.push_back(r.u32());
-        invalid(cs->advice_phase.back() > 1, "advice phase must be 0 or 1");
-    }
-    cs->unblinded.assign(cs->n_advice, 0);
-    if (version >= 2) {
-        cs->blinding = r.u32();
-        cs->minimum_degree = r.u32();
-        invalid(cs->blinding > 64 || cs->minimum_degree > 64, "blinding / minimum degree out of range");
-        const uint32_t nu = r.u32();
-        invalid((size_t)nu * 4 > r.left, "unblinded list truncated");
-        for (uint32_t i = 0; i < nu; i++) {
-            const uint32_t c = r.u32();
-            invalid(c >= cs->n_advice, "unblinded column out of range");
-            cs->unblinded[c] = 1;
-        }
-        cs->n_selectors = r.u32();
-        invalid(cs->n_selectors > (1u << 20), "selector count out of range");
-    }
-    const uint32_t nn = r.u32();
-    invalid((size_t)nn * 48 > r.left, "node table truncated");
-    for (uint32_t i = 0; i < nn; i++) {
-        Node nd;
-        nd.op = r.u32(); nd.a = r.u32(); nd.b = r.u32();
-        r.u32();
-        r.bytes(nd.c.v.data(), 32);
-        invalid(nd.op > N_MUL, "bad node op");
-        if (nd.op == N_CONST) invalid(cmp(nd.c.v, FR.p) >= 0, "non-canonical constant");
-        if (nd.op == N_ADV) invalid(nd.a >= cs->n_advice, "advice column out of range");
-        if (nd.op == N_FIX) invalid(nd.a >= cs->n_fixed, "fixed column out of range");
-        if (nd.op == N_INST) invalid(nd.a >= cs->n_instance, "instance column out of range");
-        if (nd.op == N_CHAL) invalid(nd.a >= cs->n_challenges, "challenge index out of range");
-        if (nd.op >= N_NEG) invalid(nd.a >= i, "child must precede parent");
-        if (nd.op >= N_ADD) invalid(nd.b >= i, "child must precede parent");
-        cs->nodes.push_back(nd);
-    }
-    auto node_list = [&](std::vector<uint32_t>& out) {
-        const uint32_t m = r.u32();
-        invalid((size_t)m * 4 > r.left, "list truncated");
-        for (uint32_t i = 0; i < m; i++) {
-            out.push_back(r.u32());
-            invalid(out.back() >= nn, "node id out of range");
-        }
-    };
-    node_list(cs->gates);
-    const uint32_t np = r.u32();
-    invalid((size_t)np * 8 > r.left, "permutation list truncated");
-    for (uint32_t i = 0; i < np; i++) {
-        uint32_t kind = r.u32(), col = r.u32();
-        invalid(kind < N_ADV || kind > N_INST, "bad permutation column kind");
-        invalid(col >= (kind == N_ADV ? cs->n_advice : kind == N_FIX ? cs->n_fixed : cs->n_instance), "permutation column out of range");
-        cs->perm.emplace_back(kind, col);
-    }
-    const uint32_t nl = r.u32();
-    for (uint32_t i = 0; i < nl; i++) {
-        Lookup l;
-        const uint32_t ni = r.u32();
-        invalid(ni == 0 || (size_t)ni * 4 > r.left, "lookup without inputs");
-        for (uint32_t j = 0; j < ni; j++) {
-            l.inputs.emplace_back();
-            node_list(l.inputs.back());
-            invalid(l.inputs.back().empty(), "empty lookup tuple");
-        }
-        node_list(l.table);
-        for (auto& t : l.inputs) invalid(t.size() != l.table.size(), "lookup arity mismatch");
-        cs->lookups.push_back(std::move(l));
-    }
-    if (version >= 2) {
-        cs->queries_given = r.u32() != 0;
-        if (cs->queries_given) {
-            std::vector<Query>* lists[3] = {&cs->advice_queries, &cs->fixed_queries, &cs->instance_queries};
-            const uint32_t limits[3] = {cs->n_advice, cs->n_fixed, cs->n_instance};
-            for (int t = 0; t < 3; t++) {
-                const uint32_t m = r.u32();
-                invalid((size_t)m * 8 > r.left, "query list truncated");
-                for (uint32_t i = 0; i < m; i++) {
-                    Query q;
-                    q.col = r.u32();
-                    q.rot = (int32_t)r.u32();
-                    invalid(q.col >= limits[t], "query column out of range");
-                    lists[t]->push_back(q);
-                }
-            }
-        }
-    }
-    invalid(r.left != 0, "trailing bytes");
-    cs->finalize();
-    return cs;
-}
-
 // ------------------------------------------------------------------ gate programs (GraphEvaluator)
 struct Src {
     uint32_t kind, idx, rot;
@@ -379,10 +104,7 @@ struct Program {
         for (auto& c : cols) ptrs.push_back(c->ptr());
         run_ptrs(ptrs, chal, out);
     }
-    // compile / load the kernel without running it (ezkl_hip_eval_h_prepare): nothing is read through the column pointers
-    void prepare(size_t n_cols, size_t n_chal) const {
-        std::vector<const void*> ptrs(n_cols ? n_cols : 1, nullptr);
-        std::vector<Fe> chal(n_chal ? n_chal : 1, Fe::zero());
+    ezkl_program_t describe(const void* const* cols, size_t n_cols, const std::vector<Fe>& chal, size_t n_chal) const {
         ezkl_program_t p{};
         p.code = code.data();
         p.n_instr = (uint32_t)(code.size() / 8);
@@ -391,31 +113,25 @@ struct Program {
         p.n_constants = (uint32_t)constants.size();
         p.rotations = rotations.data();
         p.n_rotations = (uint32_t)rotations.size();
-        p.columns = ptrs.data();
+        p.columns = cols;
         p.n_columns = (uint32_t)n_cols;
         p.challenges = chal.data();
         p.n_challenges = (uint32_t)n_chal;
         p.k = k;
         p.ext_k = ext_k;
+        return p;
+    }
+    // compile / load the kernel without running it (ezkl_hip_eval_h_prepare): nothing is read through the column pointers
+    void prepare(size_t n_cols, size_t n_chal) const {
+        const std::vector<const void*> ptrs(n_cols ? n_cols : 1, nullptr);
+        const std::vector<Fe> chal(n_chal ? n_chal : 1, Fe::zero());
+        const ezkl_program_t p = describe(ptrs.data(), n_cols, chal, n_chal);
         check(ezkl_hip_eval_h_prepare(&p), "ezkl_hip_eval_h_prepare");
     }
     void run_ptrs(std::vector<const void*> ptrs, const std::vector<Fe>& chal, void* out) const {
-        const uint32_t n_cols = (uint32_t)ptrs.size();
+        const size_t n_cols = ptrs.size();
         if (ptrs.empty()) ptrs.push_back(nullptr);
-        ezkl_program_t p{};
-        p.code = code.data();
-        p.n_instr = (uint32_t)(code.size() / 8);
-        p.n_intermediates = n_int;
-        p.constants = constants.data();
-        p.n_constants = (uint32_t)constants.size();
-        p.rotations = rotations.data();
-        p.n_rotations = (uint32_t)rotations.size();
-        p.columns = ptrs.data();
-        p.n_columns = n_cols;
-        p.challenges = chal.data();
-        p.n_challenges = (uint32_t)chal.size();
-        p.k = k;
-        p.ext_k = ext_k;
+        const ezkl_program_t p = describe(ptrs.data(), n_cols, chal, chal.size());
         check(ezkl_hip_eval_h_dev(&p, out, nullptr), "ezkl_hip_eval_h_dev");
     }
 };
@@ -946,7 +662,7 @@ struct Backend {
 
 // ------------------------------------------------------------------ keys
 struct ProvingKey {
-    ConstraintSystem* cs = nullptr;
+    VerifyingKey vk;                         // the constraint system, the commitments and the digest (verify.hpp)
     std::vector<Col> fixed_values, fixed_polys, fixed_cosets, sigma_values, sigma_polys, sigma_cosets;
     Col omega_col, l0, l_last, l_active, x_coset;
     // which cosets of the extended domain the *_cosets / l0 / l_last / l_active / x_coset columns hold: [coset_first, coset_first +
@@ -956,29 +672,8 @@ struct ProvingKey {
     // the degraded mode (EZKL_KEY_COSETS, check_key_fits): fixed_cosets / sigma_cosets hold NULL columns -- the key is values + coefficients
     // (+ l_0 / l_last / l_active / X on the cosets: four columns) and create_proof streams the extended domain one coset at a time
     bool stream = false;
-    std::vector<G1> fixed_commitments, sigma_commitments;
     std::vector<uint8_t> selector_bits;      // n_selectors x n/8 bytes, bit-packed rows as in halo2's vk files (zero if the key was made here)
-    Fe digest;
 };
-static Fe vk_digest(const ProvingKey& pk) {
-    const ConstraintSystem& cs = *pk.cs;
-    // keccak256(keccak256(constraint-system blob) || fixed commitments || permutation commitments): the whole description of
-    // the circuit -- columns, gates, lookups, permutation, query order -- is bound into the transcript, as halo2's
-    // vk.transcript_repr binds its pinned constraint system
-    std::vector<uint8_t> t(cs.blob_hash.begin(), cs.blob_hash.end());
-    auto put = [&](const G1& p) {
-        U256 x, y;
-        p.canonical(x, y);
-        uint8_t b[64];
-        to_be32(x, b);
-        to_be32(y, b + 32);
-        t.insert(t.end(), b, b + 64);
-    };
-    for (auto& p : pk.fixed_commitments) put(p);
-    for (auto& p : pk.sigma_commitments) put(p);
-    auto h = keccak256(t.data(), t.size());
-    return Fe::from_canonical(reduce_fr(from_be32(h.data())));
-}
 // Before a key is built or loaded (keygen, pk_read, pk_read_file): will it fit, and in which form?  -> true: the key is held STREAMED.
 // Resident (the fast form): (fixed + permutation columns) x (values + coefficients + this rank's cosets of the extended domain) + l_0 /
 // l_last / l_active / X on those cosets, 32 bytes per element -- at k = 22 / 30 advice columns 61 GB, and a proof holds its witness columns
@@ -1076,7 +771,7 @@ static std::unique_ptr<ProvingKey> keygen(ConstraintSystem& cs, ezkl_bases_t g, 
         be.stream_cosets = check_key_fits(cs, count, "keygen", !be.topo.owners && !cs.shard.on());
     }
     auto pk = std::make_unique<ProvingKey>();
-    pk->cs = &cs;
+    pk->vk.cs = &cs;
     pk->stream = be.stream_cosets;
     // EZKL_PROVER_KEYGEN_TIMING=1: stage times on stderr
     const bool timing = getenv("EZKL_PROVER_KEYGEN_TIMING") != nullptr;
@@ -1130,25 +825,20 @@ static std::unique_ptr<ProvingKey> keygen(ConstraintSystem& cs, ezkl_bases_t g, 
     pk->x_coset = be.key_cosets(be.indicator(1, 2), cs.ext_k);
     be.key_range(cs.ext_k, pk->coset_first, pk->coset_count);
     lap("l0 / l_last / l_active / X");
-    pk->fixed_commitments = be.commit(pk->fixed_polys);
-    pk->sigma_commitments = be.commit(pk->sigma_polys);
-    pk->digest = vk_digest(*pk);
+    pk->vk.fixed_commitments = be.commit(pk->fixed_polys);
+    pk->vk.sigma_commitments = be.commit(pk->sigma_polys);
+    pk->vk.digest = vk_digest(pk->vk);
     lap("commitments");
     return pk;
 }
 
 // ------------------------------------------------------------------ key files (halo2 ProvingKey::{write, read}, SerdeFormat::RawBytes)
-// The layout of the reference's vk.key / pk.key (/root/reference/src/pfsys/mod.rs:593-683; verified on tests/assets in
-// SURVEY.md §8(c) item 3):  VK = [3, k, compress_selectors] | u32 LE #fixed | #fixed x G1 | #perm x G1 | selectors (none
-// here: selectors are plain fixed columns);  PK = VK | poly l0 | poly l_last | poly l_active_row | vec fixed_values |
-// vec fixed_polys | vec fixed_cosets | vec permutations | vec perm_polys | vec perm_cosets, with
-// poly = u32 BE len | len x 32 B and vec = u32 BE count | count x u32 BE len | count x poly.  Field and curve bytes are
-// the resident Montgomery bytes, copied unchanged in both directions.
+// The layout is described, and walked, in keyfile.hpp.
 static void put_be32(std::vector<uint8_t>& o, uint32_t v) {
     for (int i = 3; i >= 0; i--) o.push_back((uint8_t)(v >> (8 * i)));
 }
 static std::vector<uint8_t> pk_write(const ProvingKey& pk) {
-    const ConstraintSystem& cs = *pk.cs;
+    const ConstraintSystem& cs = *pk.vk.cs;
     Backend be(cs.k, cs.n, nullptr, nullptr);
     std::vector<uint8_t> o = {3, (uint8_t)cs.k, 1};
     const uint32_t nf = cs.n_fixed;
@@ -1157,8 +847,8 @@ static std::vector<uint8_t> pk_write(const ProvingKey& pk) {
         const uint8_t* b = reinterpret_cast<const uint8_t*>(v.data());
         o.insert(o.end(), b, b + 64 * v.size());
     };
-    put_points(pk.fixed_commitments);
-    put_points(pk.sigma_commitments);
+    put_points(pk.vk.fixed_commitments);
+    put_points(pk.vk.sigma_commitments);
     {
         const size_t sel_bytes = (size_t)cs.n_selectors * ((cs.n + 7) / 8);
         if (pk.selector_bits.size() == sel_bytes) o.insert(o.end(), pk.selector_bits.begin(), pk.selector_bits.end());
@@ -1209,84 +899,37 @@ static std::vector<uint8_t> pk_write(const ProvingKey& pk) {
 static std::unique_ptr<ProvingKey> pk_read(ConstraintSystem& cs, const uint8_t* buf, size_t len) {
     Backend be(cs.k, cs.n, nullptr, nullptr);
     const bool stream = check_key_fits(cs, 1u << (cs.ext_k - cs.k), "pk_read", !cs.shard.on());   // the file's complete extended columns
-    size_t off = 0;
-    auto need = [&](size_t m) { invalid(off + m > len, "proving key truncated"); };
-    need(7);
-    invalid(buf[0] != 3, "unsupported key version");
-    invalid(buf[1] != cs.k, "key was made for another k");
-    uint32_t nf = 0;
-    for (int i = 0; i < 4; i++) nf |= (uint32_t)buf[3 + i] << (8 * i);
-    invalid(nf != cs.n_fixed, "key has another number of fixed columns");
-    off = 7;
+    const KeyLayout at = walk_key(cs, buf, len, true);
     auto pk = std::make_unique<ProvingKey>();
-    pk->cs = &cs;
-    auto get_points = [&](std::vector<G1>& v, size_t m) {
-        need(64 * m);
-        v.resize(m);
-        if (m) std::memcpy(v.data(), buf + off, 64 * m);
-        off += 64 * m;
-    };
-    get_points(pk->fixed_commitments, cs.n_fixed);
-    get_points(pk->sigma_commitments, cs.perm.size());
-    {
-        // halo2 does not store the selector count: it re-runs configure (src/pfsys/mod.rs:627); here the constraint system carries it
-        const size_t sel_bytes = (size_t)cs.n_selectors * ((cs.n + 7) / 8);
-        need(sel_bytes);
-        pk->selector_bits.assign(buf + off, buf + off + sel_bytes);
-        off += sel_bytes;
-    }
-    auto be32 = [&]() {
-        need(4);
-        uint32_t v = ((uint32_t)buf[off] << 24) | ((uint32_t)buf[off + 1] << 16) | ((uint32_t)buf[off + 2] << 8) | buf[off + 3];
-        off += 4;
-        return v;
-    };
-    auto get_poly = [&](size_t m) {
-        invalid(be32() != m, "polynomial of unexpected length in the key");
-        need(32 * m);
-        for (size_t i = 0; i < m; i++) {                               // every element must be a canonical residue
+    pk->vk.cs = &cs;
+    read_commitments(pk->vk, at, buf);
+    pk->selector_bits.assign(buf + at.selectors, buf + at.selectors + at.selector_bytes);
+    auto get_poly = [&](const KeySection& sec) {
+        for (size_t i = 0; i < sec.rows; i++) {                        // every element must be a canonical residue
             U256 e;
-            std::memcpy(e.data(), buf + off + 32 * i, 32);
+            std::memcpy(e.data(), buf + sec.off + 32 * i, 32);
             invalid(cmp(e, FR.p) >= 0, "non-canonical field element in the key");
         }
-        Col c = be.upload(buf + off, m);
-        off += 32 * m;
-        return c;
+        return be.upload(buf + sec.off, sec.rows);
     };
-    auto get_vec = [&](std::vector<Col>& cols, size_t count, size_t m) {
-        invalid(be32() != count, "vector of unexpected length in the key");
-        for (size_t i = 0; i < count; i++) invalid(be32() != m, "polynomial of unexpected length in the key");
-        for (size_t i = 0; i < count; i++) cols.push_back(get_poly(m));
+    // streamed key: the extended sections of the file are passed over, never uploaded
+    auto get_vec = [&](std::vector<Col>& cols, const std::vector<KeySection>& secs, bool skip = false) {
+        for (auto& sec : secs) cols.push_back(skip ? Col() : get_poly(sec));
     };
-    const size_t n = cs.n, ne = (size_t)1 << cs.ext_k;
     // extended columns: natural order in the file, coset-major in HBM
     auto cm = [&](const Col& c) { return be.cosets_reorder(c, cs.ext_k, false); };
-    pk->l0 = cm(get_poly(ne)); pk->l_last = cm(get_poly(ne)); pk->l_active = cm(get_poly(ne));
-    // streamed key: the extended sections of the file are checked for their shape and passed over, never uploaded
-    auto skip_vec = [&](std::vector<Col>& cols, size_t count, size_t m) {
-        invalid(be32() != count, "vector of unexpected length in the key");
-        for (size_t i = 0; i < count; i++) invalid(be32() != m, "polynomial of unexpected length in the key");
-        for (size_t i = 0; i < count; i++) {
-            invalid(be32() != m, "polynomial of unexpected length in the key");
-            need(32 * m);
-            off += 32 * m;
-            cols.push_back(Col());
-        }
-    };
+    pk->l0 = cm(get_poly(at.l0)); pk->l_last = cm(get_poly(at.l_last)); pk->l_active = cm(get_poly(at.l_active_row));
     pk->stream = stream;
-    get_vec(pk->fixed_values, cs.n_fixed, n); get_vec(pk->fixed_polys, cs.n_fixed, n);
-    if (stream) skip_vec(pk->fixed_cosets, cs.n_fixed, ne); else get_vec(pk->fixed_cosets, cs.n_fixed, ne);
-    get_vec(pk->sigma_values, cs.perm.size(), n); get_vec(pk->sigma_polys, cs.perm.size(), n);
-    if (stream) skip_vec(pk->sigma_cosets, cs.perm.size(), ne); else get_vec(pk->sigma_cosets, cs.perm.size(), ne);
+    get_vec(pk->fixed_values, at.fixed_values); get_vec(pk->fixed_polys, at.fixed_polys); get_vec(pk->fixed_cosets, at.fixed_cosets, stream);
+    get_vec(pk->sigma_values, at.permutations); get_vec(pk->sigma_polys, at.perm_polys); get_vec(pk->sigma_cosets, at.perm_cosets, stream);
     for (auto& c : pk->fixed_cosets) if (c) c = cm(c);
     for (auto& c : pk->sigma_cosets) if (c) c = cm(c);
-    invalid(off != len, "trailing bytes in the proving key");
     // derived columns that the file does not hold
     pk->omega_col = be.omega_powers();
     pk->x_coset = be.coeff_to_extended(be.indicator(1, 2), cs.ext_k);
     pk->coset_first = 0;
     pk->coset_count = 1u << (cs.ext_k - cs.k);               // the file's complete extended columns
-    pk->digest = vk_digest(*pk);
+    pk->vk.digest = vk_digest(pk->vk);
     return pk;
 }
 
@@ -1313,68 +956,25 @@ static std::unique_ptr<ProvingKey> pk_read_file(ConstraintSystem& cs, const char
         be.key_range(cs.ext_k, first, count);
         be.stream_cosets = check_key_fits(cs, count, "pk_read_file", !be.topo.owners && !cs.shard.on());
     }
-    size_t off = 0;
-    auto need = [&](size_t m) { invalid(off + m > len, "proving key truncated"); };
-    need(7);
-    invalid(buf[0] != 3, "unsupported key version");
-    invalid(buf[1] != cs.k, "key was made for another k");
-    uint32_t nf = 0;
-    for (int i = 0; i < 4; i++) nf |= (uint32_t)buf[3 + i] << (8 * i);
-    invalid(nf != cs.n_fixed, "key has another number of fixed columns");
-    off = 7;
+    const KeyLayout at = walk_key(cs, buf, len, true);
     auto pk = std::make_unique<ProvingKey>();
     pk->stream = be.stream_cosets;
-    pk->cs = &cs;
-    const size_t n = cs.n, ne = (size_t)1 << cs.ext_k, np = cs.perm.size();
-    need(64 * (nf + np));
-    pk->fixed_commitments.resize(nf);
-    pk->sigma_commitments.resize(np);
-    if (nf) std::memcpy(pk->fixed_commitments.data(), buf + off, 64 * (size_t)nf);
-    off += 64 * (size_t)nf;
-    if (np) std::memcpy(pk->sigma_commitments.data(), buf + off, 64 * np);
-    off += 64 * np;
-    const size_t sel_bytes = (size_t)cs.n_selectors * ((cs.n + 7) / 8);
-    need(sel_bytes);
-    pk->selector_bits.assign(buf + off, buf + off + sel_bytes);
-    off += sel_bytes;
-    auto be32 = [&]() {
-        need(4);
-        uint32_t v = ((uint32_t)buf[off] << 24) | ((uint32_t)buf[off + 1] << 16) | ((uint32_t)buf[off + 2] << 8) | buf[off + 3];
-        off += 4;
-        return v;
-    };
-    auto skip_poly = [&](size_t m) {
-        invalid(be32() != m, "polynomial of unexpected length in the key");
-        need(32 * m);
-        off += 32 * m;
-    };
-    auto vec_header = [&](size_t count, size_t m) {
-        invalid(be32() != count, "vector of unexpected length in the key");
-        for (size_t i = 0; i < count; i++) invalid(be32() != m, "polynomial of unexpected length in the key");
-    };
-    // the n-row sections are only LOCATED here; they travel afterwards, all at once (load_sections below)
+    pk->vk.cs = &cs;
+    const size_t n = cs.n;
+    read_commitments(pk->vk, at, buf);
+    pk->selector_bits.assign(buf + at.selectors, buf + at.selectors + at.selector_bytes);
+    // the n-row sections were only LOCATED by the walker; they travel now, all at once.  l0, l_last, l_active_row, the coefficient
+    // forms and the extended cosets are recomputed
     struct Section { size_t off; Col dst; };
     std::vector<Section> sections;
-    auto load_values = [&](std::vector<Col>& cols, size_t count) {
-        vec_header(count, n);
-        for (size_t i = 0; i < count; i++) {
-            invalid(be32() != n, "polynomial of unexpected length in the key");
-            need(32 * n);
+    auto load_values = [&](std::vector<Col>& cols, const std::vector<KeySection>& secs) {
+        for (auto& sec : secs) {
             cols.push_back(be.alloc(n));
-            sections.push_back(Section{off, cols.back()});
-            off += 32 * n;
+            sections.push_back(Section{sec.off, cols.back()});
         }
     };
-    auto skip_vec = [&](size_t count, size_t m) {
-        vec_header(count, m);
-        for (size_t i = 0; i < count; i++) skip_poly(m);
-    };
-    skip_poly(ne); skip_poly(ne); skip_poly(ne);                    // l0, l_last, l_active_row: recomputed
-    load_values(pk->fixed_values, nf);
-    skip_vec(nf, n); skip_vec(nf, ne);
-    load_values(pk->sigma_values, np);
-    skip_vec(np, n); skip_vec(np, ne);
-    invalid(off != len, "trailing bytes in the proving key");
+    load_values(pk->fixed_values, at.fixed_values);
+    load_values(pk->sigma_values, at.permutations);
     // File -> HBM as a pipeline: a few reader threads pread their sections into page-locked buffers (one copy out of the page cache,
     // no page fault per 4 KiB as through the mapping) and check them (canonical residues: the top limb decides all but 2^-60 of the
     // cases), this thread uploads each buffer as it fills (PCIe at the pinned rate).  Measured on the k = 20 MLP key (34 sections of
@@ -1467,18 +1067,18 @@ static std::unique_ptr<ProvingKey> pk_read_file(ConstraintSystem& cs, const char
     pk->omega_col = be.omega_powers();
     pk->x_coset = be.key_cosets(be.indicator(1, 2), cs.ext_k);
     be.key_range(cs.ext_k, pk->coset_first, pk->coset_count);
-    pk->digest = vk_digest(*pk);
+    pk->vk.digest = vk_digest(pk->vk);
     return pk;
 }
 
 // commitments of the fixed / permutation polynomials under another SRS (a key file made with the public SRS, proved here under a
 // test SRS): the resident polynomials are committed again and the digest follows
 static void pk_recommit(ProvingKey& pk, ezkl_bases_t g) {
-    ConstraintSystem& cs = *pk.cs;
+    ConstraintSystem& cs = *pk.vk.cs;
     Backend be(cs.k, cs.n, g, nullptr, cs.shard);
-    pk.fixed_commitments = be.commit(pk.fixed_polys);
-    pk.sigma_commitments = be.commit(pk.sigma_polys);
-    pk.digest = vk_digest(pk);
+    pk.vk.fixed_commitments = be.commit(pk.fixed_polys);
+    pk.vk.sigma_commitments = be.commit(pk.sigma_polys);
+    pk.vk.digest = vk_digest(pk.vk);
 }
 
 // ------------------------------------------------------------------ randomness
@@ -1561,92 +1161,17 @@ struct OpenQuery {
     Fe point, eval;
     bool mine = true;                // this rank carries the polynomial through the opening (every polynomial has exactly one such rank)
 };
-struct PolyEvals {
-    Col poly;
-    bool mine;
-    std::map<U256, std::pair<Fe, Fe>> ev;      // canonical point -> (point, eval)
-};
-static bool u256_less(const U256& a, const U256& b) { return cmp(a, b) < 0; }
-// coefficients (low first) of the polynomial of degree < len(points) through (points, values)
-static std::vector<Fe> interpolate(const std::vector<Fe>& pts, const std::vector<Fe>& vals) {
-    const size_t m = pts.size();
-    std::vector<Fe> coeffs(m, Fe::zero()), den(m, Fe::one()), pre(m + 1, Fe::one());
-    std::vector<std::vector<Fe>> nums(m);
-    for (size_t i = 0; i < m; i++) {
-        std::vector<Fe> num = {Fe::one()};
-        for (size_t j = 0; j < m; j++) {
-            if (j == i) continue;
-            std::vector<Fe> nn(num.size() + 1, Fe::zero());
-            for (size_t t = 0; t < num.size(); t++) {            // num * (X - pts[j])
-                nn[t + 1] = nn[t + 1] + num[t];
-                nn[t] = nn[t] - pts[j] * num[t];
-            }
-            num = nn;
-            den[i] = den[i] * (pts[i] - pts[j]);
-        }
-        nums[i] = num;
-        pre[i + 1] = pre[i] * den[i];
-    }
-    Fe inv_all = pre[m].inv();                                   // one field inversion (254 squarings on the host) for the m denominators
-    for (size_t i = m; i-- > 0;) {
-        const Fe s = vals[i] * (inv_all * pre[i]);
-        inv_all = inv_all * den[i];
-        for (size_t t = 0; t < nums[i].size(); t++) coeffs[t] = coeffs[t] + s * nums[i][t];
-    }
-    return coeffs;
-}
-static Fe eval_small(const std::vector<Fe>& c, const Fe& x) {
-    Fe acc = Fe::zero();
-    for (size_t i = c.size(); i-- > 0;) acc = acc * x + c[i];
-    return acc;
-}
 // The opening is LINEAR in the polynomials: q_S = sum_i ys^i p_i, h = sum_S v^S (q_S - r_S) / Z_S, L = sum_S c_S (q_S - r_S(u)) - c h.
 // A sharded prover in owner mode therefore never moves a polynomial: every rank forms the same expressions over the polynomials it
 // owns (with the global coefficients ys^i, v^S, c_S and the partial evaluations of ITS polynomials: each partial q_S - r_S still
 // vanishes on S, so the divisions stay exact), commits its partial h and L with the whole base set, and the two folds add the
 // points.  With one rank (or replicated columns) every polynomial is `mine` and this is the plain prover.
 static void shplonk_prove(Backend& be, EvmTranscript& T, const std::vector<OpenQuery>& qs, uint32_t n) {
-    // group queries by polynomial (first appearance), then polynomials by their point set (first appearance)
-    std::vector<PolyEvals> polys;
-    std::map<std::vector<uint32_t>, size_t> by_key;
-    for (auto& q : qs) {
-        auto it = by_key.find(q.key);
-        if (it == by_key.end()) {
-            it = by_key.emplace(q.key, polys.size()).first;
-            polys.push_back(PolyEvals{q.poly, q.mine, {}});
-        }
-        polys[it->second].ev[q.point.canonical()] = {q.point, q.eval};
-    }
-    struct Group {
-        std::vector<U256> pts;                 // sorted canonical points
-        std::vector<Fe> pts_fe;
-        std::vector<size_t> members;
-    };
-    std::vector<Group> groups;
-    for (size_t i = 0; i < polys.size(); i++) {
-        std::vector<U256> pts;
-        for (auto& e : polys[i].ev) pts.push_back(e.first);      // std::map<U256>: lexicographic on LE limbs, re-sort numerically
-        std::sort(pts.begin(), pts.end(), u256_less);
-        size_t gi = 0;
-        for (; gi < groups.size(); gi++)
-            if (groups[gi].pts == pts) break;
-        if (gi == groups.size()) {
-            Group gnew;
-            gnew.pts = pts;
-            for (auto& p : pts) gnew.pts_fe.push_back(polys[i].ev[p].first);
-            groups.push_back(gnew);
-        }
-        groups[gi].members.push_back(i);
-    }
+    OpeningSets sets;                          // queries grouped by polynomial, polynomials by their point set: as the verifier groups them
+    for (auto& q : qs) sets.add(q.key, q.point, q.eval);
+    sets.finish();
+    const std::vector<OpeningSets::Group>& groups = sets.groups;
     const Fe ys = T.squeeze_challenge();
-    std::vector<U256> all_pts;
-    for (auto& gr : groups)
-        for (auto& p : gr.pts) all_pts.push_back(p);
-    std::sort(all_pts.begin(), all_pts.end(), u256_less);
-    all_pts.erase(std::unique(all_pts.begin(), all_pts.end()), all_pts.end());
-    std::map<U256, Fe> pt_fe;
-    for (auto& gr : groups)
-        for (size_t i = 0; i < gr.pts.size(); i++) pt_fe[gr.pts[i]] = gr.pts_fe[i];
     struct Combo {
         Col q;                 // null: this rank owns no member of the group
         std::vector<Fe> r;
@@ -1657,10 +1182,11 @@ static void shplonk_prove(Backend& be, EvmTranscript& T, const std::vector<OpenQ
         std::vector<Col> members;
         Fe pw = Fe::one();
         for (size_t mi : gr.members) {
-            if (polys[mi].mine) {
-                members.push_back(polys[mi].poly);
+            const OpenQuery& q0 = qs[sets.polys[mi].first];      // the polynomial's payload: as its first query has it
+            if (q0.mine) {
+                members.push_back(q0.poly);
                 cf.push_back(pw);
-                for (size_t i = 0; i < gr.pts.size(); i++) evs[i] = evs[i] + pw * polys[mi].ev[gr.pts[i]].second;
+                for (size_t i = 0; i < gr.pts.size(); i++) evs[i] = evs[i] + pw * sets.polys[mi].ev.at(gr.pts[i]).second;
             }
             pw = pw * ys;
         }
@@ -1692,8 +1218,7 @@ static void shplonk_prove(Backend& be, EvmTranscript& T, const std::vector<OpenQ
     }
     T.write_point(be.commit_sum(be.g, h));
     const Fe u = T.squeeze_challenge();
-    Fe zt_u = Fe::one();
-    for (auto& z : all_pts) zt_u = zt_u * (u - pt_fe[z]);
+    const Fe zt_u = sets.z_outside({}, u);
     Col L = be.alloc(n);
     pw = Fe::one();
     Fe const_term = Fe::zero();
@@ -1702,9 +1227,7 @@ static void shplonk_prove(Backend& be, EvmTranscript& T, const std::vector<OpenQ
         std::vector<Fe> cf;
         Fe norm = Fe::one();                               // halo2 normalises by the first set's coefficient: 1 / Z_{T \ S_0}(u)
         for (size_t gi = 0; gi < groups.size(); gi++) {
-            Fe zdiff = Fe::one();
-            for (auto& z : all_pts)
-                if (!std::binary_search(groups[gi].pts.begin(), groups[gi].pts.end(), z, u256_less)) zdiff = zdiff * (u - pt_fe[z]);
+            const Fe zdiff = sets.z_outside(groups[gi].pts, u);
             if (gi == 0) norm = zdiff.inv();
             const Fe c = pw * zdiff * norm;
             if (combos[gi].q) {
@@ -1896,7 +1419,7 @@ static Quotient quotient_program(const ConstraintSystem& cs, const ProvingKey& p
 // are a function of the constraint system alone (challenges and columns are run-time operands), so what is built here with placeholder
 // columns has the code bytes create_proof will build.  Best effort: a failure only means the first proof compiles it itself.
 static void prepare_quotient(const ProvingKey& pk) {
-    const ConstraintSystem& cs = *pk.cs;
+    const ConstraintSystem& cs = *pk.vk.cs;
     try {
         std::vector<Col> adv(cs.n_advice), zc(cs.n_chunks), mc(cs.lookups.size()), pc(cs.lookups.size()), ic(cs.n_instance);
         std::vector<Fe> uc(cs.n_challenges, Fe::zero());
@@ -1908,7 +1431,7 @@ static void prepare_quotient(const ProvingKey& pk) {
 }
 // what one launch of this key's sweep does per row: [instructions, Montgomery products (MUL, SQUARE, HORNER_STEP), column slots, programs]
 static void sweep_stats(const ProvingKey& pk, uint64_t out[4]) {
-    const ConstraintSystem& cs = *pk.cs;
+    const ConstraintSystem& cs = *pk.vk.cs;
     std::vector<Col> adv(cs.n_advice), zc(cs.n_chunks), mc(cs.lookups.size()), pc(cs.lookups.size()), ic(cs.n_instance);
     std::vector<Fe> uc(cs.n_challenges, Fe::zero());
     Quotient Q = quotient_program(cs, pk, adv, zc, Fe::one(), Fe::one(), Fe::one(), Fe::one(), mc, pc, ic, uc);
@@ -2080,24 +1603,11 @@ static void mock(ConstraintSystem& cs, const void* const* fixed_values, const ui
         }
         std::vector<const void*> ptrs;
         for (auto& c : cols) ptrs.push_back(c->ptr());
-        const uint32_t n_cols = (uint32_t)ptrs.size();
+        const size_t n_cols = ptrs.size();
         if (ptrs.empty()) ptrs.push_back(nullptr);
         std::vector<Fe> chal = user_chal;
         if (chal.empty()) chal.push_back(Fe::zero());
-        ezkl_program_t p{};
-        p.code = prog.code.data();
-        p.n_instr = (uint32_t)(prog.code.size() / 8);
-        p.n_intermediates = prog.n_int;
-        p.constants = prog.constants.data();
-        p.n_constants = (uint32_t)prog.constants.size();
-        p.rotations = prog.rotations.data();
-        p.n_rotations = (uint32_t)prog.rotations.size();
-        p.columns = ptrs.data();
-        p.n_columns = n_cols;
-        p.challenges = chal.data();
-        p.n_challenges = (uint32_t)user_chal.size();
-        p.k = k;
-        p.ext_k = k;
+        const ezkl_program_t p = prog.describe(ptrs.data(), n_cols, chal, user_chal.size());
         KindOut o = collect(1, [&](void* rec, uint32_t c0, void* cnt) {
             check(ezkl_hip_eval_check_dev(&p, slots.data(), (uint32_t)slots.size(), 0, u, rec, c0, cnt, nullptr), "ezkl_hip_eval_check_dev");
         });
@@ -2174,7 +1684,7 @@ static int64_t centred(int64_t rot, int64_t n) {
 static std::vector<uint8_t> create_proof(ProvingKey& pk, ezkl_bases_t g, ezkl_bases_t gl, const void* const* advice, ezkl_advice_fn advice_fn, void* advice_user,
                                          const void* const* instances, const uint32_t* instance_lens, Rng& rng, double* timings,
                                          const uint8_t* advice_formats = nullptr) {
-    ConstraintSystem& cs = *pk.cs;
+    ConstraintSystem& cs = *pk.vk.cs;
     const uint32_t n = cs.n, k = cs.k, u = cs.usable;
     // the helper chains of a proof are hundreds of small device-only calls: queued on the library stream without a host round trip
     // each (ezkl_hip_set_async); every call that returns host data still synchronises by itself.  EZKL_PROVER_SYNC_CALLS=1: off.
@@ -2198,7 +1708,7 @@ static std::vector<uint8_t> create_proof(ProvingKey& pk, ezkl_bases_t g, ezkl_ba
     for (auto& x : cs.shard.stats) x = 0;
     Stopwatch sw(timings);
     EvmTranscript T;
-    T.common_scalar(pk.digest);
+    T.common_scalar(pk.vk.digest);
     // 0. instances: absorbed, never committed (halo2 KZG: QUERY_INSTANCE = false)
     std::vector<Col> inst_cols;
     for (uint32_t i = 0; i < cs.n_instance; i++) {
@@ -2764,291 +2274,6 @@ static std::vector<uint8_t> create_proof(ProvingKey& pk, ezkl_bases_t g, ezkl_ba
     return T.proof();
 }
 
-
-// ------------------------------------------------------------------ verify_proof (the SAFE self-check, verify_proof_circuit)
-// halo2's verifier for the proofs create_proof above emits (/root/reference/src/pfsys/mod.rs:557-590 verify_proof_circuit, and the
-// CheckMode::SAFE branch of create_proof_circuit :470-480): replay the transcript, recompute the quotient identity at x from the
-// claimed evaluations, and check the SHPLONK opening with one pairing product against the SRS's g2 / s_g2.  O(#columns) field and
-// group operations on the host (pairing.hpp); no device work.
-struct ProofReader {
-    const uint8_t* p;
-    size_t len, off = 0;
-    std::vector<uint8_t> buf;
-    void need(size_t m) {
-        if (off + m > len) throw Error(EZKL_ERR_INVALID, "proof truncated");
-    }
-    void common_scalar(const Fe& s) {
-        uint8_t b[32];
-        to_be32(s.canonical(), b);
-        buf.insert(buf.end(), b, b + 32);
-    }
-    bn::P1 read_point() {
-        need(64);
-        const U256 x = from_be32(p + off), y = from_be32(p + off + 32);
-        if (cmp(x, FQ.p) >= 0 || cmp(y, FQ.p) >= 0) throw Error(EZKL_ERR_INVALID, "non-canonical point in the proof");
-        buf.insert(buf.end(), p + off, p + off + 64);
-        off += 64;
-        bn::P1 r;
-        r.x = bn::Fq{mont_mul(x, FQ.r2, FQ)};
-        r.y = bn::Fq{mont_mul(y, FQ.r2, FQ)};
-        r.inf = r.x.is_zero() && r.y.is_zero();
-        if (!r.inf && !(r.y * r.y == r.x * r.x * r.x + bn::Fq::from_u64(3))) throw Error(EZKL_ERR_INVALID, "point not on the curve");
-        return r;
-    }
-    Fe read_scalar() {
-        need(32);
-        const U256 c = from_be32(p + off);
-        if (cmp(c, FR.p) >= 0) throw Error(EZKL_ERR_INVALID, "non-canonical scalar in the proof");
-        buf.insert(buf.end(), p + off, p + off + 32);
-        off += 32;
-        return Fe::from_canonical(c);
-    }
-    Fe squeeze_challenge() {
-        if (buf.size() == 32) buf.push_back(0x01);
-        auto h = keccak256(buf.data(), buf.size());
-        buf.assign(h.begin(), h.end());
-        return Fe::from_canonical(reduce_fr(from_be32(h.data())));
-    }
-};
-
-static bool verify_proof(ConstraintSystem& cs, const std::vector<G1>& fixed_commitments, const std::vector<G1>& sigma_commitments, const Fe& digest,
-                         const bn::G2& g2, const bn::G2& s_g2, const uint8_t* proof, size_t proof_len, const void* const* instances,
-                         const uint32_t* instance_lens) {
-    using bn::P1;
-    const uint32_t n = cs.n, k = cs.k, u = cs.usable;
-    ProofReader T{proof, proof_len, 0, {}};
-    T.common_scalar(digest);
-    std::vector<std::vector<Fe>> inst(cs.n_instance);
-    for (uint32_t i = 0; i < cs.n_instance; i++) {
-        if (instance_lens[i] > u) return false;
-        for (uint32_t j = 0; j < instance_lens[i]; j++) {
-            U256 v;
-            std::memcpy(v.data(), (const uint8_t*)instances[i] + 32 * j, 32);
-            if (cmp(v, FR.p) >= 0) return false;
-            inst[i].push_back(Fe{v});
-            T.common_scalar(Fe{v});
-        }
-    }
-    std::vector<P1> adv_c(cs.n_advice);
-    std::vector<Fe> user_chal;
-    for (uint32_t phase = 0; phase < 2; phase++) {
-        bool any = false;
-        for (uint32_t c = 0; c < cs.n_advice; c++)
-            if (cs.advice_phase[c] == phase) { adv_c[c] = T.read_point(); any = true; }
-        if (phase == 0 && any)
-            for (uint32_t i = 0; i < cs.n_challenges; i++) user_chal.push_back(T.squeeze_challenge());
-    }
-    const size_t nl = cs.lookups.size();
-    Fe theta = Fe::zero();
-    std::vector<P1> m_c, phi_c, z_c, h_c;
-    if (nl) {
-        theta = T.squeeze_challenge();
-        for (size_t i = 0; i < nl; i++) m_c.push_back(T.read_point());
-    }
-    const Fe beta = T.squeeze_challenge(), gamma = T.squeeze_challenge();
-    for (uint32_t j = 0; j < cs.n_chunks; j++) z_c.push_back(T.read_point());
-    for (size_t i = 0; i < nl; i++) phi_c.push_back(T.read_point());
-    const P1 rnd_c = T.read_point();
-    const Fe y = T.squeeze_challenge();
-    for (uint32_t i = 0; i + 1 < cs.degree; i++) h_c.push_back(T.read_point());
-    const Fe x = T.squeeze_challenge();
-    std::map<std::pair<uint32_t, int32_t>, Fe> ev[3];        // advice, fixed, instance evaluations by (column, rotation)
-    for (auto& q : cs.advice_queries) ev[0][{q.col, q.rot}] = T.read_scalar();
-    for (auto& q : cs.fixed_queries) ev[1][{q.col, q.rot}] = T.read_scalar();
-    const Fe random_eval = T.read_scalar();
-    std::vector<Fe> sigma_ev;
-    for (size_t i = 0; i < cs.perm.size(); i++) sigma_ev.push_back(T.read_scalar());
-    struct ZE { Fe e0, e1, e2; bool has2; };
-    std::vector<ZE> z_ev;
-    for (uint32_t j = 0; j < cs.n_chunks; j++) {
-        ZE z{T.read_scalar(), T.read_scalar(), Fe::zero(), j + 1 < cs.n_chunks};
-        if (z.has2) z.e2 = T.read_scalar();
-        z_ev.push_back(z);
-    }
-    struct LE { Fe phi, phi_next, m; };
-    std::vector<LE> lk_ev;
-    for (size_t i = 0; i < nl; i++) lk_ev.push_back(LE{T.read_scalar(), T.read_scalar(), T.read_scalar()});
-    const Fe w = omega(k);
-    auto rot_point = [&](int32_t r) { return x * w.pow((uint64_t)(r >= 0 ? (uint32_t)r % n : n - ((uint32_t)(-r) % n))); };
-    const Fe xn = x.pow((uint64_t)n), zx = xn - Fe::one(), ninv = Fe::from_u64(n).inv();
-    auto lagrange = [&](const Fe& at, const Fe& at_n_minus_1, uint32_t i) {   // l_i(at) = omega^i (at^n - 1) / (n (at - omega^i))
-        const Fe wi = w.pow((uint64_t)i);
-        return wi * at_n_minus_1 * ninv * (at - wi).inv();
-    };
-    for (auto& q : cs.instance_queries) {                     // instance columns are evaluated by the verifier from the public values
-        const Fe z = rot_point(q.rot), zn1 = z.pow((uint64_t)n) - Fe::one();
-        Fe acc = Fe::zero();
-        for (size_t i = 0; i < inst[q.col].size(); i++) acc = acc + inst[q.col][i] * lagrange(z, zn1, (uint32_t)i);
-        ev[2][{q.col, q.rot}] = acc;
-    }
-    const Fe l0 = lagrange(x, zx, 0), llast = lagrange(x, zx, u);
-    Fe lblind = Fe::zero();
-    for (uint32_t i = u; i < n; i++) lblind = lblind + lagrange(x, zx, i);
-    const Fe lact = Fe::one() - lblind;
-    std::vector<Fe> memo(cs.nodes.size());
-    std::vector<uint8_t> have(cs.nodes.size(), 0);
-    std::function<Fe(uint32_t)> evalx = [&](uint32_t id) -> Fe {
-        if (have[id]) return memo[id];
-        const Node& nd = cs.nodes[id];
-        Fe r;
-        switch (nd.op) {
-        case N_CONST: r = nd.c; break;
-        case N_ADV: case N_FIX: case N_INST: {
-            auto it = ev[nd.op - N_ADV].find({nd.a, (int32_t)nd.b});
-            if (it == ev[nd.op - N_ADV].end()) throw Error(EZKL_ERR_INVALID, "expression reads an unqueried cell");
-            r = it->second;
-            break;
-        }
-        case N_CHAL: r = user_chal.at(nd.a); break;
-        case N_NEG: r = -evalx(nd.a); break;
-        case N_ADD: r = evalx(nd.a) + evalx(nd.b); break;
-        case N_SUB: r = evalx(nd.a) - evalx(nd.b); break;
-        default: r = evalx(nd.a) * evalx(nd.b); break;
-        }
-        have[id] = 1;
-        return memo[id] = r;
-    };
-    std::vector<Fe> terms;
-    for (uint32_t g : cs.gates) terms.push_back(evalx(g));
-    if (!cs.perm.empty()) {
-        terms.push_back(l0 * (Fe::one() - z_ev[0].e0));
-        const Fe zl = z_ev.back().e0;
-        terms.push_back(llast * (zl * zl - zl));
-        for (uint32_t j = 1; j < cs.n_chunks; j++) terms.push_back(l0 * (z_ev[j].e0 - z_ev[j - 1].e2));
-        uint32_t pos = 0;
-        const Fe delta{FR_DELTA};
-        Fe dpow = Fe::one();
-        uint32_t j = 0;
-        for (auto& chunk : cs.perm_chunks()) {
-            Fe left = z_ev[j].e1, right = z_ev[j].e0;
-            for (size_t i = 0; i < chunk.size(); i++) {
-                const Fe v = ev[chunk[i].first - N_ADV].at({chunk[i].second, 0});
-                left = left * (v + beta * sigma_ev[pos + i] + gamma);
-                right = right * (v + beta * dpow * x + gamma);
-                dpow = dpow * delta;
-            }
-            terms.push_back(lact * (left - right));
-            pos += (uint32_t)chunk.size();
-            j++;
-        }
-    }
-    auto compress = [&](const std::vector<uint32_t>& tup) {
-        Fe acc = evalx(tup[0]);
-        for (size_t i = 1; i < tup.size(); i++) acc = acc * theta + evalx(tup[i]);
-        return acc;
-    };
-    for (size_t li = 0; li < nl; li++) {
-        const Lookup& l = cs.lookups[li];
-        std::vector<Fe> fb;
-        for (auto& t : l.inputs) fb.push_back(compress(t) + beta);
-        const Fe tb = compress(l.table) + beta;
-        Fe prodf = Fe::one(), ssum = Fe::zero();
-        for (auto& f : fb) prodf = prodf * f;
-        for (size_t jj = 0; jj < fb.size(); jj++) {
-            Fe pj = Fe::one();
-            for (size_t i2 = 0; i2 < fb.size(); i2++)
-                if (i2 != jj) pj = pj * fb[i2];
-            ssum = ssum + pj;
-        }
-        const Fe lhs = (lk_ev[li].phi_next - lk_ev[li].phi) * prodf * tb, rhs = ssum * tb - lk_ev[li].m * prodf;
-        terms.push_back(l0 * lk_ev[li].phi);
-        terms.push_back(llast * lk_ev[li].phi);
-        terms.push_back(lact * (lhs - rhs));
-    }
-    Fe num = Fe::zero();
-    for (auto& t : terms) num = num * y + t;
-    const Fe h_eval = num * zx.inv();
-    // ---- the opening queries, in the prover's order: (commitment, point, evaluation) grouped like shplonk_prove
-    P1 hc{};
-    for (size_t i = h_c.size(); i-- > 0;) hc = bn::p1_add(bn::p1_mul(hc, xn), h_c[i]);
-    struct VQ { std::vector<uint32_t> key; P1 com; Fe point, eval; };
-    enum : uint32_t { K_ADV = 1, K_FIX, K_H, K_RND, K_SIGMA, K_Z, K_M, K_PHI };
-    std::vector<VQ> qs;
-    for (auto& q : cs.advice_queries) qs.push_back({{K_ADV, q.col}, adv_c[q.col], rot_point(q.rot), ev[0][{q.col, q.rot}]});
-    for (uint32_t j = 0; j < z_ev.size(); j++) {
-        qs.push_back({{K_Z, j}, z_c[j], x, z_ev[j].e0});
-        qs.push_back({{K_Z, j}, z_c[j], rot_point(1), z_ev[j].e1});
-        if (z_ev[j].has2) qs.push_back({{K_Z, j}, z_c[j], rot_point((int32_t)u), z_ev[j].e2});
-    }
-    for (uint32_t i = 0; i < nl; i++) {
-        qs.push_back({{K_PHI, i}, phi_c[i], x, lk_ev[i].phi});
-        qs.push_back({{K_PHI, i}, phi_c[i], rot_point(1), lk_ev[i].phi_next});
-        qs.push_back({{K_M, i}, m_c[i], x, lk_ev[i].m});
-    }
-    for (auto& q : cs.fixed_queries) qs.push_back({{K_FIX, q.col}, bn::p1_from(fixed_commitments[q.col]), rot_point(q.rot), ev[1][{q.col, q.rot}]});
-    for (uint32_t i = 0; i < sigma_ev.size(); i++) qs.push_back({{K_SIGMA, i}, bn::p1_from(sigma_commitments[i]), x, sigma_ev[i]});
-    qs.push_back({{K_H}, hc, x, h_eval});
-    qs.push_back({{K_RND}, rnd_c, x, random_eval});
-    struct VPoly { P1 com; std::map<U256, std::pair<Fe, Fe>> ev; };
-    std::vector<VPoly> polys;
-    std::map<std::vector<uint32_t>, size_t> by_key;
-    for (auto& q : qs) {
-        auto it = by_key.find(q.key);
-        if (it == by_key.end()) {
-            it = by_key.emplace(q.key, polys.size()).first;
-            polys.push_back(VPoly{q.com, {}});
-        }
-        polys[it->second].ev[q.point.canonical()] = {q.point, q.eval};
-    }
-    struct VGroup { std::vector<U256> pts; std::vector<Fe> pts_fe; std::vector<size_t> members; };
-    std::vector<VGroup> groups;
-    for (size_t i = 0; i < polys.size(); i++) {
-        std::vector<U256> pts;
-        for (auto& e : polys[i].ev) pts.push_back(e.first);
-        std::sort(pts.begin(), pts.end(), u256_less);
-        size_t gi = 0;
-        for (; gi < groups.size(); gi++)
-            if (groups[gi].pts == pts) break;
-        if (gi == groups.size()) {
-            VGroup gn;
-            gn.pts = pts;
-            for (auto& p : pts) gn.pts_fe.push_back(polys[i].ev[p].first);
-            groups.push_back(gn);
-        }
-        groups[gi].members.push_back(i);
-    }
-    const Fe ys = T.squeeze_challenge();
-    std::vector<U256> all_pts;
-    std::map<U256, Fe> pt_fe;
-    for (auto& gr : groups)
-        for (size_t i = 0; i < gr.pts.size(); i++) { all_pts.push_back(gr.pts[i]); pt_fe[gr.pts[i]] = gr.pts_fe[i]; }
-    std::sort(all_pts.begin(), all_pts.end(), u256_less);
-    all_pts.erase(std::unique(all_pts.begin(), all_pts.end()), all_pts.end());
-    const Fe v = T.squeeze_challenge();
-    const P1 pi1 = T.read_point();
-    const Fe uu = T.squeeze_challenge();
-    const P1 pi2 = T.read_point();
-    if (T.off != proof_len) return false;
-    Fe zt_u = Fe::one();
-    for (auto& p : all_pts) zt_u = zt_u * (uu - pt_fe[p]);
-    P1 gen;
-    gen.inf = false; gen.x = bn::Fq::one(); gen.y = bn::Fq::from_u64(2);
-    P1 L{};
-    Fe pw = Fe::one(), norm = Fe::one();
-    bool first = true;
-    for (auto& gr : groups) {
-        P1 qc{};
-        std::vector<Fe> evs(gr.pts.size(), Fe::zero());
-        Fe yp = Fe::one();
-        for (size_t mi : gr.members) {
-            qc = bn::p1_add(qc, bn::p1_mul(polys[mi].com, yp));
-            for (size_t i = 0; i < gr.pts.size(); i++) evs[i] = evs[i] + yp * polys[mi].ev[gr.pts[i]].second;
-            yp = yp * ys;
-        }
-        const std::vector<Fe> r = interpolate(gr.pts_fe, evs);
-        Fe zdiff = Fe::one();
-        for (auto& p : all_pts)
-            if (!std::binary_search(gr.pts.begin(), gr.pts.end(), p, u256_less)) zdiff = zdiff * (uu - pt_fe[p]);
-        if (first) { norm = zdiff.inv(); first = false; }    // halo2: coefficients normalised by the first set's
-        const P1 term = bn::p1_add(qc, bn::p1_neg(bn::p1_mul(gen, eval_small(r, uu))));
-        L = bn::p1_add(L, bn::p1_mul(term, pw * zdiff * norm));
-        pw = pw * v;
-    }
-    L = bn::p1_add(L, bn::p1_neg(bn::p1_mul(pi1, zt_u * norm)));
-    const P1 lhs = bn::p1_add(L, bn::p1_mul(pi2, uu));
-    return bn::pairing_check({{pi2, s_g2}, {bn::p1_neg(lhs), g2}});
-}
-
 }  // namespace ezkl_prover
 
 // ------------------------------------------------------------------ C ABI
@@ -3193,7 +2418,7 @@ int ezkl_prover_keygen(ezkl_cs_t cs, ezkl_bases_t g, const void* const* fixed_va
 int ezkl_prover_pk_residency(ezkl_pk_t pk, uint64_t out[4]) {
     if (!pk || !out) return EZKL_ERR_INVALID;
     const ProvingKey& k_ = *pk->pk;
-    const ConstraintSystem& cs = *k_.cs;
+    const ConstraintSystem& cs = *k_.vk.cs;
     const uint64_t E = 1ull << (cs.ext_k - cs.k), n = cs.n;
     out[0] = k_.coset_first; out[1] = k_.stream ? 0 : k_.coset_count; out[2] = E;        // a streamed key holds NO coset of its fixed / permutation columns
     const uint64_t small = (uint64_t)(k_.fixed_values.size() + k_.fixed_polys.size() + k_.sigma_values.size() + k_.sigma_polys.size() + 1) * n * 32;
@@ -3225,7 +2450,7 @@ int ezkl_prover_pk_read_file(ezkl_cs_t cs, const char* path, ezkl_pk_t* out) {
 int ezkl_prover_pk_set_selectors(ezkl_pk_t pk, const void* bits, size_t len) {
     return guarded([&] {
         if (!pk || (!bits && len)) throw Error(EZKL_ERR_INVALID, "null handle");
-        const ConstraintSystem& cs = *pk->pk->cs;
+        const ConstraintSystem& cs = *pk->pk->vk.cs;
         if (len != (size_t)cs.n_selectors * ((cs.n + 7) / 8)) throw Error(EZKL_ERR_INVALID, "selector section of unexpected length");
         pk->pk->selector_bits.assign((const uint8_t*)bits, (const uint8_t*)bits + len);
     });
@@ -3242,7 +2467,7 @@ int ezkl_prover_pk_free(ezkl_pk_t pk) {
 }
 int ezkl_prover_vk(ezkl_pk_t h, void* fixed_commitments, void* permutation_commitments, void* digest) {
     if (!h) return EZKL_ERR_INVALID;
-    const ProvingKey& pk = *h->pk;
+    const VerifyingKey& pk = h->pk->vk;
     if (fixed_commitments && !pk.fixed_commitments.empty()) std::memcpy(fixed_commitments, pk.fixed_commitments.data(), pk.fixed_commitments.size() * 64);
     if (permutation_commitments && !pk.sigma_commitments.empty()) std::memcpy(permutation_commitments, pk.sigma_commitments.data(), pk.sigma_commitments.size() * 64);
     if (digest) std::memcpy(digest, pk.digest.v.data(), 32);
@@ -3253,7 +2478,7 @@ int ezkl_prover_pk_set_transcript_repr(ezkl_pk_t h, const void* repr) {
     U256 v;
     std::memcpy(v.data(), repr, 32);
     if (cmp(v, FR.p) >= 0) return EZKL_ERR_INVALID;              // a canonical scalar, as halo2 transcript_repr is
-    h->pk->digest = Fe::from_canonical(v);
+    h->pk->vk.digest = Fe::from_canonical(v);
     return EZKL_OK;
 }
 int ezkl_prover_mock(ezkl_cs_t h, const void* const* fixed_values, const uint32_t* copies, size_t n_copies, const void* const* advice, ezkl_advice_fn advice_fn,
@@ -3282,10 +2507,10 @@ int ezkl_prover_create_proof_fmt(ezkl_pk_t pk, ezkl_bases_t g, ezkl_bases_t g_la
                                  ezkl_advice_fn advice_fn, void* advice_user, const void* const* instances, const uint32_t* instance_lens, ezkl_rng_fn rng,
                                  void* rng_user, uint64_t seed, void* proof_out, size_t cap, size_t* proof_len, double* timings) {
     if (!pk || !g || !g_lagrange || !proof_len) return EZKL_ERR_INVALID;
-    if (pk->pk->cs->n_instance && (!instances || !instance_lens)) return EZKL_ERR_INVALID;
+    if (pk->pk->vk.cs->n_instance && (!instances || !instance_lens)) return EZKL_ERR_INVALID;
     return guarded([&] {
-        const Shard& sh = pk->pk->cs->shard;
-        const size_t want = sh.on() && !sh.full_bases ? sh.hi - sh.lo : pk->pk->cs->n;
+        const Shard& sh = pk->pk->vk.cs->shard;
+        const size_t want = sh.on() && !sh.full_bases ? sh.hi - sh.lo : pk->pk->vk.cs->n;
         invalid(ezkl_hip_bases_len(g) < want || ezkl_hip_bases_len(g_lagrange) != want, "SRS size does not match 2^k (or this rank's slice)");
         Rng r(rng, rng_user, seed);
         if (sh.on() && !rng && seed == 0) {
@@ -3307,69 +2532,19 @@ int ezkl_prover_verify_proof(ezkl_pk_t pk, const void* g2, const void* s_g2, con
                              const uint32_t* instance_lens, int* accepted) {
     if (!pk || !g2 || !s_g2 || !proof || !accepted) return EZKL_ERR_INVALID;
     *accepted = 0;
-    if (pk->pk->cs->n_instance && (!instances || !instance_lens)) return EZKL_ERR_INVALID;
-    return guarded([&] {
-        const ProvingKey& k = *pk->pk;
-        const bn::G2 a = bn::g2_from_bytes((const uint8_t*)g2), b = bn::g2_from_bytes((const uint8_t*)s_g2);
-        if (!bn::g2_on_curve(a) || !bn::g2_on_curve(b) || a.inf || b.inf) throw Error(EZKL_ERR_INVALID, "g2 / s_g2 not on the twist");
-        bool ok = false;
-        try {
-            ok = verify_proof(*k.cs, k.fixed_commitments, k.sigma_commitments, k.digest, a, b, (const uint8_t*)proof, proof_len, instances, instance_lens);
-        } catch (const Error& e) {             // a malformed proof is a rejection, not a failure of the call
-            if (e.code != EZKL_ERR_INVALID) throw;
-            g_last_error = e.what();
-        }
-        *accepted = ok ? 1 : 0;
-    });
+    if (pk->pk->vk.cs->n_instance && (!instances || !instance_lens)) return EZKL_ERR_INVALID;
+    return guarded([&] { *accepted = verify_with(pk->pk->vk, g2, s_g2, proof, proof_len, instances, instance_lens, g_last_error) ? 1 : 0; });
 }
-// verify_proof from the verifying key ALONE (the reference's `verify` reads settings + vk.key, /root/reference/src/execute.rs:1651): the vk
-// file is halo2's raw-bytes layout [3, k, compress] | u32 LE #fixed | #fixed x G1 | #perm x G1 | selector bits; the constraint system
-// supplies the counts.  Host only: no device, no proving key, no private data.
+// verify_proof from the verifying key ALONE (the reference's `verify` reads settings + vk.key, /root/reference/src/execute.rs:1651): vk_read
+// and the verifier of verify.hpp.  Host only: no device, no proving key, no private data.
 int ezkl_prover_verify_proof_vk(ezkl_cs_t cs, const void* vk_buf, size_t vk_len, const void* g2, const void* s_g2, const void* proof, size_t proof_len,
                                 const void* const* instances, const uint32_t* instance_lens, int* accepted) {
     if (!cs || !vk_buf || !g2 || !s_g2 || !proof || !accepted) return EZKL_ERR_INVALID;
     *accepted = 0;
     if (cs->cs->n_instance && (!instances || !instance_lens)) return EZKL_ERR_INVALID;
     return guarded([&] {
-        ConstraintSystem& c = *cs->cs;
-        const uint8_t* b = (const uint8_t*)vk_buf;
-        const size_t np = c.perm.size(), want = 7 + 64 * ((size_t)c.n_fixed + np);
-        invalid(vk_len < want, "verifying key truncated");
-        invalid(b[0] != 3, "unsupported key version");
-        invalid(b[1] != c.k, "key was made for another k");
-        uint32_t nf = 0;
-        for (int i = 0; i < 4; i++) nf |= (uint32_t)b[3 + i] << (8 * i);
-        invalid(nf != c.n_fixed, "key has another number of fixed columns");
-        ProvingKey vk;                                   // only the verifying-key part is filled
-        vk.cs = &c;
-        vk.fixed_commitments.resize(nf);
-        vk.sigma_commitments.resize(np);
-        if (nf) std::memcpy(vk.fixed_commitments.data(), b + 7, 64 * (size_t)nf);
-        if (np) std::memcpy(vk.sigma_commitments.data(), b + 7 + 64 * (size_t)nf, 64 * np);
-        // a damaged or foreign key is rejected here, not fed to the pairing arithmetic: every commitment must be the identity
-        // encoding (0, 0) or a canonical point of the curve, and what follows the commitments must be a complete selector section (a vk.key
-        // ends there; a pk.key -- whose prefix the vk is -- goes on with the polynomials)
-        auto check_point = [&](const G1& p) {
-            invalid(cmp(p.x, FQ.p) >= 0 || cmp(p.y, FQ.p) >= 0, "non-canonical coordinate in the verifying key");
-            const bn::Fq x{p.x}, y{p.y};
-            if (x.is_zero() && y.is_zero()) return;
-            invalid(!(y * y == x * x * x + bn::Fq::from_u64(3)), "a commitment of the verifying key is not on the curve");
-        };
-        for (auto& p_ : vk.fixed_commitments) check_point(p_);
-        for (auto& p_ : vk.sigma_commitments) check_point(p_);
-        const size_t sel_bytes = (size_t)c.n_selectors * ((c.n + 7) / 8);
-        invalid(vk_len < want + sel_bytes, "verifying key truncated (selector section)");
-        const Fe digest = vk_digest(vk);
-        const bn::G2 a = bn::g2_from_bytes((const uint8_t*)g2), bb = bn::g2_from_bytes((const uint8_t*)s_g2);
-        if (!bn::g2_on_curve(a) || !bn::g2_on_curve(bb) || a.inf || bb.inf) throw Error(EZKL_ERR_INVALID, "g2 / s_g2 not on the twist");
-        bool ok = false;
-        try {
-            ok = verify_proof(c, vk.fixed_commitments, vk.sigma_commitments, digest, a, bb, (const uint8_t*)proof, proof_len, instances, instance_lens);
-        } catch (const Error& e) {
-            if (e.code != EZKL_ERR_INVALID) throw;
-            g_last_error = e.what();
-        }
-        *accepted = ok ? 1 : 0;
+        const VerifyingKey vk = vk_read(*cs->cs, (const uint8_t*)vk_buf, vk_len);
+        *accepted = verify_with(vk, g2, s_g2, proof, proof_len, instances, instance_lens, g_last_error) ? 1 : 0;
     });
 }
 int ezkl_prover_g2_mul_generator(const void* scalar, void* out128) {
@@ -3644,7 +2819,7 @@ int ezkl_prover_group_create_proof(ezkl_group_t grp, const void* const* advice, 
     std::vector<std::array<double, 12>> tm(grp->world);
     int rc = grp->run([&](int r) {
         if (!grp->pk[r] || !grp->g[r] || !grp->gl[r]) return (int)EZKL_ERR_INVALID;
-        if (grp->pk[r]->pk->cs->n_instance && (!instances || !instance_lens)) return (int)EZKL_ERR_INVALID;
+        if (grp->pk[r]->pk->vk.cs->n_instance && (!instances || !instance_lens)) return (int)EZKL_ERR_INVALID;
         return guarded([&] {
             Rng rng = master;
             proofs[r] = create_proof(*grp->pk[r]->pk, grp->g[r], grp->gl[r], advice, nullptr, nullptr, instances, instance_lens, rng, tm[r].data());
