@@ -590,9 +590,14 @@ def batch_invert(ptr, n, stream=None):
 def gen_srs(k, s):
     """test SRS with a KNOWN secret s (insecure, like the reference's gen_srs, src/pfsys/srs.rs:13-16):
     g[i] = s^i G, g_lagrange[i] = L_i(s) G with L_i(s) = (s^n - 1) w^i / (n (s - w^i)); everything on the device.
-    Returns (g, g_lagrange) as Bases."""
+    Returns (g, g_lagrange) as Bases.  A secret inside the domain (s^n = 1: s = 1, s = w^j) is refused: the closed form is 0 / 0 at row
+    j there (batch_invert maps the 0 to 0 and the common factor is 0 as well, so every point would come out as the identity), and such
+    an SRS commits the vanishing polynomial to the identity.  s = 0 is not in the domain and is legal."""
     n = 1 << k
-    w = pow(EvaluationDomain.ROOT, 1 << (28 - k), _R)
+    s = int(s) % _R
+    if pow(s, n, _R) == 1:
+        raise ValueError("gen_srs: the secret is a point of the 2^%d-point domain (s^n = 1): L_i(s) = (s^n - 1) w^i / (n (s - w^i)) "
+                         "does not apply there, and a KZG SRS with such a secret is unusable" % k)
     G = np.frombuffer((_MONT % _Q).to_bytes(32, "little") + (2 * _MONT % _Q).to_bytes(32, "little"), np.uint64).copy()
     spow = DeviceBuffer(n * 32)
     vec_fill(spow.ptr, _to_mont(s), n)

@@ -111,7 +111,9 @@ EZ_HD g1a_t g1a_neg(const g1a_t& p) {
     r.y = Fq::neg(p.y);
     return r;
 }
-// canonical affine: x = X/ZZ, y = Y/ZZZ ; identity -> (0,0)
+// canonical affine: x = X/ZZ, y = Y/ZZZ ; identity -> (0,0).  Only ZZ is looked at: every formula above multiplies ZZ by u^2 and ZZZ by
+// u^3 of the same u, so one is zero exactly when the other is (a doubling of a y = 0 input -- no such point is on this curve, the group
+// order is odd -- would zero both and come out as the identity, not as ZZ != 0 with ZZZ = 0)
 EZ_HD g1a_t g1x_to_affine(const g1x_t& p) {
     g1a_t r;
     if (g1x_is_id(p)) {

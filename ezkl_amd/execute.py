@@ -154,9 +154,9 @@ def gen_srs(srs_path, logrows, secret=None):
     mont_q = lambda v: np.frombuffer((v * (1 << 256) % B._Q).to_bytes(32, "little"), np.uint64)
     mont_r = lambda v: np.frombuffer((v * (1 << 256) % R_).to_bytes(32, "little"), np.uint64)
     g2 = np.concatenate([mont_q(c) for c in (G2_GENERATOR[0][0], G2_GENERATOR[0][1], G2_GENERATOR[1][0], G2_GENERATOR[1][1])])
-    s_g2 = B.msm_g2(g2[None], mont_r(secret)[None])
-    g, gl = B.gen_srs(logrows, secret)
+    g, gl = B.gen_srs(logrows, secret)                       # first: it refuses a secret inside the domain (ValueError) before any device work
     try:
+        s_g2 = B.msm_g2(g2[None], mont_r(secret)[None])
         data = codecs.write_srs(dict(k=logrows, g=g.download(), g_lagrange=gl.download(), g2=g2.tobytes(), s_g2=s_g2.tobytes()))
     finally:
         g.free(); gl.free()
