@@ -37,23 +37,10 @@
 #include "curve.hpp"
 #include "curve29.hpp"
 #include "host64.hpp"
+#include "msm_plan.hpp"   // constants, WinPlan / pick_plan, ReduceGeom and the launch plan (host-only arithmetic)
 #include <string.h>
 
 namespace ezkl {
-
-// (The compile-time variants of rounds 4-5 -- the loop without the one-iteration-ahead loads, the fused "lean" chain, unpack-first, the full
-// accumulator reset, conditional gathers -- were measured and removed; their A/B logs are profiles/r05q_msm_ab.log, r05y_msm_ab.log and
-// DESIGN.md §4.1.  What is here is the one shipped form.)
-static constexpr uint32_t MSM_MAX_PART_BITS = 12;   // <= 4096 partitions in the first sorting pass (1024 up to 2^20 points: msm_part_bits)
-static constexpr uint32_t MSM_SPAN_HEAVY = 16;      // buckets cut by more lane boundaries than this are folded by a whole workgroup
-static constexpr uint32_t MSM_PART_STAGE = 13312;     // pairs a partition workgroup stages in LDS (104 KiB): 1024 scalars x 13 windows
-static constexpr uint32_t MSM_BINSORT_STAGE = 15360;  // payloads a sort workgroup stages in LDS (60 KiB): 2 workgroups per CU
-static constexpr uint32_t MSM_HEAVY_CHUNK = 256;     // lane partials folded by one WAVE in the first heavy pass (four serial additions per lane + the wave tree)
-static constexpr uint32_t MSM_DIGIT_E = 8;          // serial elements per lane in the first reduce stage
-static constexpr uint32_t MSM_LMIN = 8;             // shortest lane of the accumulate kernel
-static constexpr uint32_t MSM_MAX_BIG = 64;         // oversized partitions sorted by several workgroups each (the rest: one workgroup)
-static constexpr uint32_t MSM_BIG_BLOCKS = 64;      // workgroups per oversized partition
-static constexpr uint32_t MSM_BIG_ROWS = 8;         // rows of such workgroups in a launch: row r takes the oversized partitions r, r + 8, ...
 
 // Partition of a bucket in the first sorting pass: its low bits -- except bucket 0, which gets a partition of its own
 // (index 0; ordinary partition p is index p + 1).  Bucket 0 holds the digits +-1: every carry of the signed recoding into an
@@ -69,10 +56,6 @@ __device__ __forceinline__ uint32_t msm_lane_len(const uint32_t* offsets, uint32
     return l < lmin ? lmin : l;
 }
 
-// Window plan: W signed-digit windows covering 254 bits (253-bit magnitudes after the r - s fold + the last carry),
-// the first `rem` windows base+1 bits wide, the others base bits.  Balanced widths instead of "c, c, ..., short top
-// window": a 14-bit top window under c = 20 pours 128 extra pairs into each of 2^13 buckets, which then get cut by
-// several lane boundaries of the accumulate kernel; with 7 x 20 + 6 x 19 bits no bucket outgrows a lane.
 // Batched launches: one launch serves `gridDim.z` MSMs of the same size whose scratch slabs have the same layout `bstride` bytes
 // apart; a kernel shifts every scratch pointer it is given by blockIdx.z * bstride (bstride = 0 / gridDim.z = 1: a single MSM).
 // The shift is BYTE-POINTER arithmetic, never a round trip through an integer: a pointer rebuilt from a uintptr_t no longer derives from its
@@ -87,19 +70,12 @@ template <class T> __device__ __forceinline__ const T* bshift(const T* p, size_t
 #define BOFF() const size_t _bo = (size_t)blockIdx.z * bstride
 // The scalar columns of a fused group travel BY VALUE in the kernel arguments (128 bytes): a column pointer read from a list in memory is a
 // pointer of unknown address space (flat loads of every scalar word again), and the list cost a host-to-device copy in front of every group.
-static constexpr size_t MSM_MAX_GROUP = 16;       // MSMs fused into one sequence of launches (gridDim.z)
 struct MsmCols {
     const fe_t* col[MSM_MAX_GROUP];
 };
 // this workgroup's column: a uniform read of the kernel-argument segment at blockIdx.z (one scalar load, no copy of the struct)
 __device__ __forceinline__ const fe_t* msm_col(const MsmCols& cols) { return cols.col[blockIdx.z]; }
 
-struct WinPlan {
-    uint32_t W, base, rem;
-    __host__ __device__ uint32_t width(uint32_t w) const { return base + (w < rem ? 1u : 0u); }
-    __host__ __device__ uint32_t offset(uint32_t w) const { return w * base + (w < rem ? w : rem); }
-    __host__ __device__ uint32_t cmax() const { return base + (rem ? 1u : 0u); }
-};
 struct MsmTable {
     g1a_t* tab = nullptr;    // W x n affine: T[w][i] = 2^offset(w) * P_i
     WinPlan wp{0, 0, 0};
@@ -173,7 +149,6 @@ struct MsmState {
     size_t tail_pinned_elems = 0;
     MsmUpload* open_upload = nullptr;
     MsmBatch* open_batch = nullptr;
-    bool attrs_set = false;
     int acc_blocks_per_cu = 0;
 };
 static MsmState& msm_state() {
@@ -182,20 +157,6 @@ static MsmState& msm_state() {
     return *static_cast<MsmState*>(c->msm_state);
 }
 
-
-static WinPlan pick_plan(size_t n) {
-    // cost model in point additions: n*W bucket additions + ~4 per bucket for the reduce phase (2^(cmax-1) buckets);
-    // ties go to the smaller W (fewer gathers, smaller table).  n = 2^20: W = 13 (7 x 20 + 6 x 19 bits, 26 pairs/bucket).
-    WinPlan best{0, 0, 0};
-    double best_cost = 0;
-    for (uint32_t W = 10; W <= 127; W++) {
-        WinPlan p{W, 254 / W, 254 % W};
-        if (p.cmax() > 23) continue;
-        const double cost = (double)n * W + 4.0 * (double)((size_t)1 << (p.cmax() - 1));
-        if (!best.W || cost < best_cost) { best = p; best_cost = cost; }
-    }
-    return best;
-}
 
 // ---- table precompute: T[w] = 2^width(w-1) * T[w-1] --------------------------------------------
 __global__ __launch_bounds__(256) void msm_precompute_kernel(const g1a_t* prev, g1a_t* next, size_t n, uint32_t c) {
@@ -358,7 +319,6 @@ __global__ __launch_bounds__(256) void msm_hist_kernel(MsmCols cols, size_t n, s
 // through LDS, then the rows are rewritten.  Workgroups are independent of each other.
 // A 128-byte line of a row is shared by eight workgroups.  Workgroups b and b + 8 run on the same XCD, so the strips are dealt to let
 // those eight be neighbours there and the line be fetched into one L2 (placement is a matter of speed only: any bijection is correct).
-static constexpr uint32_t MSM_SCAN_COLS = 4;
 __global__ __launch_bounds__(1024) void msm_hist_scan_kernel(uint32_t* wg_hist, uint32_t G, uint32_t NP, uint32_t* part_count, size_t bstride) {
     BOFF(); BSH(wg_hist); BSH(part_count);
     __shared__ uint32_t wsum[64];
@@ -928,18 +888,7 @@ __global__ __launch_bounds__(256) void msm_fixup_heavy2_kernel(const uint32_t* o
     }
 }
 
-// ---- reduce: sum_pos weight(pos) * B_pos ---------------------------------------------------------
-// A bucket position splits into three bit-fields A (lowest), B, C; its weight is 1 + dA*2^wsA + dB*2^wsB +
-// dC*2^wsC.  So the weighted sum is TOTAL + sum over fields of 2^ws * sum_d d * S_field[d], with S_field[d] the
-// plain sum of the buckets whose field equals d.  S_A comes from column sums; S_B and S_C come from the row
-// sums T[dC,dB] = sum_dA B: two passes over the buckets, each a shallow reduction (no running sums, whose
-// dependent chains are latency-bound on a GPU), then per-bit plane sums; the final Horner over <= 22 planes
-// runs on the host.
-struct ReduceGeom {
-    uint32_t wA, wB, wC;          // field widths (pos bits: A = [0,wA), B = [wA,wA+wB), C = rest)
-    uint32_t wsA, wsB, wsC;       // weight shifts of the fields
-    uint32_t EA, GA, ET, GT;      // serial elements per lane / groups for column sums (A) and row sums (T)
-};
+// ---- reduce: sum_pos weight(pos) * B_pos (the split of a position into three bit-fields: ReduceGeom, msm_plan.hpp) ----
 __global__ __launch_bounds__(256, 2) void msm_reduce1_kernel(const g1x29_t* buckets, ReduceGeom g, g1x29_t* partA, g1x29_t* partT, size_t bstride) {
     BOFF(); BSH(buckets); BSH(partA); BSH(partT);
     const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1110,146 +1059,80 @@ static int msm_finish(MsmSlot& sl, void* out_host = nullptr, bool release = true
     return EZKL_OK;
 }
 
+// Every MSM tuning variable is read HERE (the table in include/ezkl_hip.h); a value outside 1..hi (nonsense included) keeps the default.
+// EZKL_MSM_L, EZKL_MSM_E and EZKL_MSM_GROUP are read at every call (tools/gpu_probe.py, tools/sweep_L.py and the tests set them inside a running
+// process), EZKL_MSM_LMIN, EZKL_MSM_SPAN, EZKL_MSM_GROUP_SMALL and EZKL_MSM_GROUP_BIG once per process.
+struct MsmKnobs : MsmTuning {
+    int group, group_small, group_big;                    // MSMs per fused group: both classes (0: unset), witness-shaped / general scalars
+};
+static int msm_env(const char* name, int hi, int dflt) { const char* e = getenv(name); const int v = e ? atoi(e) : 0; return v >= 1 && v <= hi ? v : dflt; }
+static MsmKnobs msm_tuning() {
+    static const int lmin = msm_env("EZKL_MSM_LMIN", 4096, (int)MSM_LMIN), span = msm_env("EZKL_MSM_SPAN", 4096, (int)MSM_SPAN_HEAVY);
+    static const int small = msm_env("EZKL_MSM_GROUP_SMALL", (int)MSM_MAX_GROUP, 6), big = msm_env("EZKL_MSM_GROUP_BIG", (int)MSM_MAX_GROUP, 4);
+    MsmKnobs k;
+    k.lmin = (uint32_t)lmin; k.span_heavy = (uint32_t)span; k.group_small = small; k.group_big = big;
+    k.L_override = (uint32_t)msm_env("EZKL_MSM_L", (1 << 20) - 1, 0);
+    const int e = msm_env("EZKL_MSM_E", 1024, 0);                 // a power of two
+    if (e && (e & (e - 1)) == 0) k.E = (uint32_t)e;
+    k.group = msm_env("EZKL_MSM_GROUP", (int)MSM_MAX_GROUP, 0);
+    return k;
+}
 // how many MSMs of this size are fused into one group (gridDim.z): small MSMs are launch- and latency-bound (at 2^17 points a lone MSM
 // is 0.12 ms of accumulation inside a 0.6 ms chain of ~17 launches)
-static size_t msm_group_size(const MsmTable* T, size_t n, bool small_scalars, size_t batch = 0) {
-    if (const char* e = getenv("EZKL_MSM_GROUP")) {
-        const int v = atoi(e);
-        if (v >= 1 && v <= (int)MSM_MAX_GROUP) return (size_t)v;
-    }
-    // Round 4, measured on whole proofs (tools/ab.sh group | circuits | matrix | slots, profiles/r04[e-v]_*; 8 proofs per setting, same bytes):
-    //   * general scalars (z, phi, h pieces): groups of FOUR at every size (round 3 left 2^20-point batches unfused: a lone fused group is
-    //     1.50 against 1.35 ms per MSM).  With the false dependency between the NTT stream and the helper programs gone (one scratch arena
-    //     per stream, capi.hip / common.hpp) groups of 1 / 2 / 4 on 2 / 3 / 4 / 6 slots all land within +-1.5 ms on the k = 20 MLP proof
-    //     (73-77 ms, box-to-box variation included); four keeps a phase to two or three streams and is best or tied at k = 20 (einsum, MLP)
-    //     and k = 22.
-    //   * witness-shaped columns (advice, multiplicities: one or two non-zero digits per scalar, every kernel of the chain latency-bound
-    //     whatever n is): groups of SIX (12 advice columns = 2 chains, 8 multiplicity columns = 6 + 2): 81.0 against 82.0 ms with four.
-    // EZKL_MSM_GROUP_SMALL / EZKL_MSM_GROUP_BIG override one class, EZKL_MSM_GROUP both.
-    (void)T; (void)n; (void)batch;
-    if (small_scalars) {
-        static const int small = [] { const char* e = getenv("EZKL_MSM_GROUP_SMALL"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= (int)MSM_MAX_GROUP ? v : 6; }();
-        return (size_t)small;
-    }
-    static const int big = [] { const char* e = getenv("EZKL_MSM_GROUP_BIG"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= (int)MSM_MAX_GROUP ? v : 4; }();
-    return (size_t)big;
+// Round 4, measured on whole proofs (tools/ab.sh group | circuits | matrix | slots, profiles/r04[e-v]_*; 8 proofs per setting, same bytes):
+//   * general scalars (z, phi, h pieces): groups of FOUR at every size (round 3 left 2^20-point batches unfused: a lone fused group is
+//     1.50 against 1.35 ms per MSM).  With the false dependency between the NTT stream and the helper programs gone (one scratch arena
+//     per stream, capi.hip / common.hpp) groups of 1 / 2 / 4 on 2 / 3 / 4 / 6 slots all land within +-1.5 ms on the k = 20 MLP proof
+//     (73-77 ms, box-to-box variation included); four keeps a phase to two or three streams and is best or tied at k = 20 (einsum, MLP)
+//     and k = 22.
+//   * witness-shaped columns (advice, multiplicities: one or two non-zero digits per scalar, every kernel of the chain latency-bound
+//     whatever n is): groups of SIX (12 advice columns = 2 chains, 8 multiplicity columns = 6 + 2): 81.0 against 82.0 ms with four.
+// EZKL_MSM_GROUP_SMALL / EZKL_MSM_GROUP_BIG override one class, EZKL_MSM_GROUP both.
+static size_t msm_group_size(bool small_scalars) {
+    const MsmKnobs k = msm_tuning();
+    return (size_t)(k.group ? k.group : small_scalars ? k.group_small : k.group_big);
 }
-// `count` MSMs of n points each (scalar columns cols[0..count)) as ONE sequence of launches with gridDim.z = count
+// once per context: the dynamic LDS the two sorting passes may ask for, and how many accumulate workgroups a CU holds (msm_plan sizes the lanes by it)
+static int msm_device_init(int& acc_blocks_per_cu) {
+    if (acc_blocks_per_cu) return EZKL_OK;
+    EZ_HIP(hipFuncSetAttribute((const void*)msm_binsort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MSM_BINSORT_LDS));
+    EZ_HIP(hipFuncSetAttribute((const void*)msm_partition_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MSM_PART_LDS));
+    EZ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&acc_blocks_per_cu, msm_accumulate_kernel, 256, 0));
+    if (acc_blocks_per_cu < 1) acc_blocks_per_cu = 1;
+    return EZKL_OK;
+}
+static_assert(sizeof(g1x29_t) == MSM_POINT_BYTES, "msm_plan lays the scratch out in points of this size");
+// `count` MSMs of n points each (scalar columns cols[0..count)) as ONE sequence of launches with gridDim.z = count.  The geometry of the
+// launches and the scratch layout are msm_plan's (msm_plan.hpp); this function reads the tuning, takes the pointers and launches.
 static int msm_enqueue(Ctx* c, MsmSlot& sl, hipStream_t st, MsmTable* T, size_t base_offset, const fe_t* const* cols, size_t count, size_t n, bool timed) {
     int rc = EZKL_OK;
     if (count < 1 || count > MSM_MAX_GROUP) return EZKL_ERR_INVALID;
     const unsigned Z = (unsigned)count;
-    const WinPlan wp = T->wp;
-    const uint32_t W = wp.W, bits = wp.cmax() - 1;
-    const uint32_t nb = 1u << bits;
-    const size_t npairs = n * W;
-    // partitions of the first sorting pass: 1024, or as many more (<= 4096) as it takes to keep a partition inside the second pass's LDS
-    // stage -- beyond 2^20 points a partition of the 1024 outgrew it and the second pass fell back to scattered stores (0.9 of the 6 ms of
-    // a 2^22-point MSM: profiles/r06u_size_sweep.log, tools/msm22_profile.py)
-    uint32_t PB = bits < 10 ? bits : 10;
-    while (PB < bits && PB < MSM_MAX_PART_BITS && (npairs >> PB) > (size_t)MSM_BINSORT_STAGE * 9 / 10) PB++;
-    const uint32_t LB = bits - PB, NP = 1u << PB;
-    // ---- lane length for the accumulate kernel: fill the resident lanes an integer number of times ----
+    const MsmKnobs tu = msm_tuning();
     int& acc_blocks_per_cu = msm_state().acc_blocks_per_cu;
-    if (!acc_blocks_per_cu) {
-        EZ_HIP(hipFuncSetAttribute((const void*)msm_binsort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        EZ_HIP(hipFuncSetAttribute((const void*)msm_partition_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-        EZ_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&acc_blocks_per_cu, msm_accumulate_kernel, 256, 0));
-        if (acc_blocks_per_cu < 1) acc_blocks_per_cu = 1;
-    }
-    const size_t resident = (size_t)acc_blocks_per_cu * 256 * c->num_cus;
-    // 40..80 pairs per lane at 2^20 points: few cut buckets, whole waves of work.  Larger MSMs have more pairs per BUCKET (104 at 2^22), and a lane
-    // shorter than a bucket cuts every bucket several times (the boundary fold was 0.52 of a 2^22-point MSM's 6 ms): the lanes grow with the load
-    const size_t load = npairs >> bits, per_lane = load * 9 / 10 > 40 ? load * 9 / 10 : 40;
-    size_t rounds = npairs / (resident * per_lane);
-    if (rounds < 1) rounds = 1;
-    uint32_t L = (uint32_t)((npairs + resident * rounds - 1) / (resident * rounds));
-    if (L < 8) L = 8;
-    if (const char* e = getenv("EZKL_MSM_L")) {                        // tuning knob (tools/gpu_probe.py); nonsense keeps the default
-        const int v = atoi(e);
-        if (v > 0 && v < (1 << 20)) L = (uint32_t)v;
-    }
-    const uint32_t nlanes = cdiv(npairs, L);
-    // device-side floor of the lane length (columns with few non-zero digits) and the cut count above which a bucket takes the heavy path
-    static const uint32_t lmin = [] { const char* e = getenv("EZKL_MSM_LMIN"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 && v <= 4096 ? v : (int)MSM_LMIN); }();
+    if ((rc = msm_device_init(acc_blocks_per_cu))) return rc;
+    const MsmPlan p = msm_plan(n, T->wp, count, c->num_cus, acc_blocks_per_cu, tu);
+    const WinPlan wp = T->wp;
+    const ReduceGeom rg = p.rg;
+    const uint32_t nb = p.nb, LB = p.LB, NP = p.NP, NQ = p.NQ, nlanes = p.nlanes, lmin = tu.lmin, span_heavy = tu.span_heavy;
+    const size_t per_block = p.per_block, bstride = p.bstride;
     // cooperative (quad) additions in the latency-bound trees (curve29.hpp: g1x29_add_quad) -- bit 0: reduce2, 1: planes, 2: heavy; bit 3 (the
     // planes kernel's four wave totals cooperatively as well) was measured level and stays off (profiles/r05aj_coop15.log)
     constexpr uint32_t coop = 7;
-    // (the planes kernel writes its sums into the slot's page-locked landing buffer itself: no copy command after it)
-    static const uint32_t span_heavy = [] { const char* e = getenv("EZKL_MSM_SPAN"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 1 && v <= 4096 ? v : (int)MSM_SPAN_HEAVY); }();
-    // ---- field geometry of the reduce phase (positions: pos = (bucket & (NP-1)) << LB | bucket >> PB) ----
-    ReduceGeom rg;
-    memset(&rg, 0, sizeof rg);
-    if (LB > 0) {
-        rg.wA = LB; rg.wsA = PB;                          // A = high bucket bits
-        rg.wB = (PB + 1) / 2; rg.wsB = 0;                 // B, C = low bucket bits
-        rg.wC = PB - rg.wB; rg.wsC = rg.wB;
-    } else {                                              // small MSM: pos == bucket
-        rg.wA = (bits + 2) / 3; rg.wsA = 0;
-        rg.wB = (bits - rg.wA + 1) / 2; rg.wsB = rg.wA;
-        rg.wC = bits - rg.wA - rg.wB; rg.wsC = rg.wA + rg.wB;
-    }
-    {
-        const uint32_t rows = 1u << (rg.wB + rg.wC), cols = 1u << rg.wA;
-        uint32_t E = MSM_DIGIT_E;
-        if (const char* e = getenv("EZKL_MSM_E")) {                          // tuning knob: a power of two; nonsense keeps the default
-            const int v = atoi(e);
-            if (v > 0 && v <= 1024 && (v & (v - 1)) == 0) E = (uint32_t)v;
-        }
-        rg.EA = rows < E ? rows : E; rg.GA = rows / rg.EA;
-        rg.ET = cols < E ? cols : E; rg.GT = cols / rg.ET;
-    }
-    const uint32_t nA = 1u << rg.wA, nT = 1u << (rg.wB + rg.wC);
-    const uint32_t n_partA = nA * rg.GA, n_partT = nT * rg.GT;
-    const uint32_t nplanes = 1 + bits;
-    // ---- sort geometry: sgrid workgroups, each owning per_block consecutive scalars ----
-    // (one scalar per thread of the partition pass; all of a workgroup's pairs must fit its LDS staging area)
-    size_t per_block = MSM_PART_STAGE / W / 64 * 64;
-    {
-        const size_t lds_words = (144u << 10) / 4, fixed = 3 * ((size_t)NP + 2);       // the partition kernel's 144 KiB: three arrays of NQ + 1 words, then 2 W words per scalar
-        const size_t fit = lds_words > fixed ? (lds_words - fixed) / (2 * (size_t)W) / 64 * 64 : 64;
-        if (per_block > fit) per_block = fit;
-    }
-    if (per_block > 1024) per_block = 1024;
-    if (per_block < 64) per_block = 64;
-    const unsigned sgrid = cdiv(n, per_block);
-    // ---- carve scratch ----
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    size_t o_ent = carve(npairs * 8), o_vals = carve(npairs * 4), o_offs = carve(((size_t)nb + 1) * 4);
-    const uint32_t NQ = NP + 1;                          // + bucket 0's own partition (msm_part_of)
-    size_t o_pcnt = carve((NQ + 1) * 4), o_pbase = carve((NQ + 1) * 4), o_wgh = carve((size_t)sgrid * NQ * 4);
-    size_t o_heavy = carve((size_t)nb * 4), o_chunks = carve(((size_t)nlanes + 1) * 4);
-    const size_t nbins = (size_t)1 << LB;
-    // ONE region that starts every chain at zero: the counters (hcnt[0..2]), the bin totals of the multi-workgroup
-    // sort, the planes
-    size_t o_hcnt = carve(256), o_btot = carve(MSM_MAX_BIG * nbins * 4), o_planes = carve((size_t)nplanes * sizeof(g1x29_t));
-    const size_t zero_bytes = off - o_hcnt;
-    size_t o_bflag = carve((size_t)NP * 4), o_blist = carve(MSM_MAX_BIG * 4),
-           o_boff = carve((size_t)MSM_MAX_BIG * MSM_BIG_BLOCKS * nbins * 4);
-    size_t o_lfirst = carve((size_t)nlanes * 4);
-    size_t o_bkt = carve((size_t)nb * sizeof(g1x29_t));
-    size_t o_head = carve((size_t)nlanes * sizeof(g1x29_t)), o_tail = carve((size_t)nlanes * sizeof(g1x29_t));
-    size_t o_partA = carve((size_t)n_partA * sizeof(g1x29_t)), o_partT = carve((size_t)n_partT * sizeof(g1x29_t));
-    size_t o_SA = carve((size_t)nA * sizeof(g1x29_t)), o_T = carve((size_t)nT * sizeof(g1x29_t));
-    const size_t bstride = count > 1 ? off : 0;           // every MSM of the group owns one slab of this layout
-    rc = slot_prepare(sl, off * count, count);
+    rc = slot_prepare(sl, p.slab_bytes * count, count);
     if (rc) return rc;
     uint8_t* S = sl.scratch;
     MsmCols kcols;                                        // the group's scalar columns, by value (a single MSM: col[0], the same path)
     for (size_t j = 0; j < MSM_MAX_GROUP; j++) kcols.col[j] = cols[j < count ? j : 0];
-    uint2* entries = (uint2*)(S + o_ent);
-    uint32_t* vals = (uint32_t*)(S + o_vals);
-    uint32_t* offs = (uint32_t*)(S + o_offs);
-    uint32_t *pcnt = (uint32_t*)(S + o_pcnt), *pbase = (uint32_t*)(S + o_pbase), *wghist = (uint32_t*)(S + o_wgh);
-    uint32_t *heavy = (uint32_t*)(S + o_heavy), *hcnt = (uint32_t*)(S + o_hcnt), *chunks = (uint32_t*)(S + o_chunks);   // hcnt[0] buckets, [1] chunks
-    uint32_t* lfirst = (uint32_t*)(S + o_lfirst);
-    uint32_t *bflag = (uint32_t*)(S + o_bflag), *blist = (uint32_t*)(S + o_blist), *btot = (uint32_t*)(S + o_btot), *boff = (uint32_t*)(S + o_boff);
+    auto u32 = [&](size_t o) { return (uint32_t*)(S + o); };
+    auto pt = [&](size_t o) { return (g1x29_t*)(S + o); };
+    uint2* entries = (uint2*)(S + p.o.ent);
+    uint32_t *vals = u32(p.o.vals), *offs = u32(p.o.offs), *pcnt = u32(p.o.pcnt), *pbase = u32(p.o.pbase), *wghist = u32(p.o.wghist);
+    uint32_t *heavy = u32(p.o.heavy), *hcnt = u32(p.o.hcnt), *chunks = u32(p.o.chunks), *lfirst = u32(p.o.lfirst);
+    uint32_t *bflag = u32(p.o.bflag), *blist = u32(p.o.blist), *btot = u32(p.o.btot), *boff = u32(p.o.boff);
     uint32_t* bcnt = hcnt + 2;                                // hcnt[0] heavy buckets, [1] chunks, [2] oversized partitions
-    g1x29_t *bkt = (g1x29_t*)(S + o_bkt), *head = (g1x29_t*)(S + o_head), *tail = (g1x29_t*)(S + o_tail);
-    g1x29_t *partA = (g1x29_t*)(S + o_partA), *partT = (g1x29_t*)(S + o_partT), *SA = (g1x29_t*)(S + o_SA), *TT = (g1x29_t*)(S + o_T);
-    g1x29_t* planes = (g1x29_t*)(S + o_planes);
+    g1x29_t *bkt = pt(p.o.bkt), *head = pt(p.o.head), *tail = pt(p.o.tail), *planes = pt(p.o.planes);
+    g1x29_t *partA = pt(p.o.partA), *partT = pt(p.o.partT), *SA = pt(p.o.SA), *TT = pt(p.o.T);
 
     hipEvent_t m0 = nullptr, m1 = nullptr, a0 = nullptr, a1 = nullptr;
     // EZKL_HIP_TIMING (read at every call): which event pairs a synchronous call records -- "all" (default): the whole chain ("msm") and the
@@ -1268,14 +1151,12 @@ static int msm_enqueue(Ctx* c, MsmSlot& sl, hipStream_t st, MsmTable* T, size_t 
         if (timed_chain) EZ_HIP(hipEventRecord(m0, st));
     }
     // the chain's counters, bin totals and planes are zeroed by the histogram kernel (no memset command in front of the chain: round 5)
-    hipLaunchKernelGGL(msm_hist_kernel, dim3(sgrid, 1, Z), dim3(256), 0, st, kcols, n, per_block, wp, LB, NP, wghist, hcnt,
-                       (uint32_t)(zero_bytes / 4), bstride);
-    hipLaunchKernelGGL(msm_hist_scan_kernel, dim3(cdiv(NQ, MSM_SCAN_COLS), 1, Z), dim3(1024), 0, st, wghist, sgrid, NQ, pcnt, bstride);
+    hipLaunchKernelGGL(msm_hist_kernel, dim3(p.sgrid, 1, Z), dim3(256), 0, st, kcols, n, per_block, wp, LB, NP, wghist, hcnt,
+                       (uint32_t)(p.zero_bytes / 4), bstride);
+    hipLaunchKernelGGL(msm_hist_scan_kernel, dim3(cdiv(NQ, MSM_SCAN_COLS), 1, Z), dim3(1024), 0, st, wghist, p.sgrid, NQ, pcnt, bstride);
     hipLaunchKernelGGL(msm_part_scan_kernel, dim3(1, 1, Z), dim3(1024), 0, st, pcnt, NQ, pbase, bflag, blist, bcnt, bstride);
-    // persistent: one workgroup per CU (its 144 KiB of LDS leave room for no second one) walks the tiles
-    const unsigned pgrid = sgrid < (unsigned)c->num_cus ? sgrid : (unsigned)c->num_cus;
-    hipLaunchKernelGGL(msm_partition_kernel, dim3(pgrid, 1, Z), dim3((unsigned)per_block), (3 * ((size_t)NQ + 1) + 2 * per_block * W) * 4, st, kcols, n, per_block,
-                       (uint32_t)sgrid, wp, LB, NP, base_offset, T->n, pbase, wghist, pcnt, entries, vals, bstride);
+    hipLaunchKernelGGL(msm_partition_kernel, dim3(p.pgrid, 1, Z), dim3((unsigned)per_block), p.part_lds, st, kcols, n, per_block,
+                       (uint32_t)p.sgrid, wp, LB, NP, base_offset, T->n, pbase, wghist, pcnt, entries, vals, bstride);
     hipLaunchKernelGGL(msm_binsort_kernel, dim3(NP + MSM_BIG_BLOCKS * MSM_BIG_ROWS, 1, Z), dim3(512), MSM_BINSORT_STAGE * 4, st, entries, pbase, LB, NP, bflag, offs,
                        vals, bkt, blist, bcnt, btot, boff, bstride);
     hipLaunchKernelGGL(msm_bigsort_scatter_kernel, dim3(MSM_BIG_BLOCKS, MSM_BIG_ROWS, Z), dim3(512), 0, st, entries, pbase, LB, blist, bcnt, btot, boff, offs,
@@ -1286,45 +1167,25 @@ static int msm_enqueue(Ctx* c, MsmSlot& sl, hipStream_t st, MsmTable* T, size_t 
                        lfirst, lmin, bstride);
     if (timed) EZ_HIP(hipEventRecord(a1, st));
     if (nlanes > 1)
-    {
         hipLaunchKernelGGL(msm_fixup_boundary_tree_kernel, dim3(cdiv(nlanes - 1, 256), 1, Z), dim3(256), 0, st, offs, nb, nlanes, lfirst, head, tail, bkt,
                            heavy, hcnt, chunks, lmin, span_heavy, bstride);
-    }
-    {
-        size_t max_heavy = nlanes / span_heavy + 1;
-        const size_t heavy_wgs = (max_heavy + 3) / 4;                           // four buckets (waves) per workgroup
-        unsigned hb = (unsigned)(heavy_wgs < (size_t)c->num_cus * 4 ? heavy_wgs : (size_t)c->num_cus * 4);
-        size_t max_chunks = nlanes / MSM_HEAVY_CHUNK + max_heavy;
-        const size_t chunk_wgs = (max_chunks + 3) / 4;                         // four chunks (waves) per workgroup
-        unsigned cb = (unsigned)(chunk_wgs < (size_t)c->num_cus * 4 ? chunk_wgs : (size_t)c->num_cus * 4);
-        hipLaunchKernelGGL(msm_fixup_heavy1_kernel, dim3(cb, 1, Z), dim3(256), 0, st, offs, nb, nlanes, lfirst, head, tail, bkt, chunks, hcnt, lmin, coop & 4u, bstride);
-        hipLaunchKernelGGL(msm_fixup_heavy2_kernel, dim3(hb, 1, Z), dim3(256), 0, st, offs, nb, nlanes, head, tail, heavy, hcnt, bkt, lmin, coop & 4u, bstride);
-    }
+    hipLaunchKernelGGL(msm_fixup_heavy1_kernel, dim3(p.cb, 1, Z), dim3(256), 0, st, offs, nb, nlanes, lfirst, head, tail, bkt, chunks, hcnt, lmin, coop & 4u, bstride);
+    hipLaunchKernelGGL(msm_fixup_heavy2_kernel, dim3(p.hb, 1, Z), dim3(256), 0, st, offs, nb, nlanes, head, tail, heavy, hcnt, bkt, lmin, coop & 4u, bstride);
     // reduce
-    {
-        const uint32_t th = n_partA > n_partT ? n_partA : n_partT;
-        hipLaunchKernelGGL(msm_reduce1_kernel, dim3(cdiv(th, 256), 2, Z), dim3(256), 0, st, bkt, rg, partA, partT, bstride);
-        auto pow2_le = [](uint32_t x) { uint32_t p = 1; while (p * 2 <= x) p *= 2; return p; };
-        uint32_t lanesA = pow2_le(rg.GA < 64 ? rg.GA : 64), lanesT = pow2_le(rg.GT < 64 ? rg.GT : 64);
-        auto waves = [&](uint32_t nout, uint32_t lanes) { return cdiv(nout, 64 / lanes); };
-        while (waves(nA, lanesA) + waves(nT, lanesT) > (unsigned)c->num_cus * 4 && (lanesA > 1 || lanesT > 1)) {
-            if (lanesT > 1 && waves(nT, lanesT) >= waves(nA, lanesA)) lanesT >>= 1; else if (lanesA > 1) lanesA >>= 1; else lanesT >>= 1;
-        }
-        const uint32_t blocksA = waves(nA, lanesA);
-        hipLaunchKernelGGL(msm_reduce2_kernel, dim3(blocksA + waves(nT, lanesT), 1, Z), dim3(64), 0, st, partA, partT, rg, SA, TT, lanesA, lanesT, blocksA, coop & 1u, bstride);
-        hipLaunchKernelGGL(msm_planes_kernel, dim3(nplanes, 1, Z), dim3(256), 0, st, SA, TT, rg, planes, (g1x29_t*)sl.pinned_dev,
-                           coop & 10u, bstride);
-    }
+    hipLaunchKernelGGL(msm_reduce1_kernel, dim3(p.r1grid, 2, Z), dim3(256), 0, st, bkt, rg, partA, partT, bstride);
+    hipLaunchKernelGGL(msm_reduce2_kernel, dim3(p.r2grid, 1, Z), dim3(64), 0, st, partA, partT, rg, SA, TT, p.lanesA, p.lanesT, p.blocksA, coop & 1u, bstride);
+    // (the planes kernel writes its sums into the slot's page-locked landing buffer itself: no copy command after it)
+    hipLaunchKernelGGL(msm_planes_kernel, dim3(p.nplanes, 1, Z), dim3(256), 0, st, SA, TT, rg, planes, (g1x29_t*)sl.pinned_dev, coop & 10u, bstride);
     EZ_HIP(hipGetLastError());
     if (getenv("EZKL_MSM_DEBUG")) {
         uint32_t hc = 0;
         EZ_HIP(hipMemcpyAsync(&hc, hcnt, 4, hipMemcpyDeviceToHost, st));
         EZ_HIP(hipStreamSynchronize(st));
-        fprintf(stderr, "[msm] n=%zu W=%u bits=%u L=%u nlanes=%u heavy=%u\n", n, W, bits, L, nlanes, hc);
+        fprintf(stderr, "[msm] n=%zu W=%u bits=%u L=%u nlanes=%u heavy=%u\n", n, p.W, p.bits, p.L, nlanes, hc);
     }
     if (timed_chain) EZ_HIP(hipEventRecord(m1, st));
     EZ_HIP(hipEventRecord(sl.done, st));
-    sl.bits = bits;
+    sl.bits = p.bits;
     sl.count = (uint32_t)count;
     sl.busy = true;
     return EZKL_OK;
@@ -1334,7 +1195,7 @@ static int msm_enqueue(Ctx* c, MsmSlot& sl, hipStream_t st, MsmTable* T, size_t 
 // after wait_ev[j] (the upload phase's copy events).
 static int msm_run_groups(Ctx* c, MsmTable* T, size_t base_offset, const fe_t* const* cols, size_t batch, size_t n, void* out_host,
                           const hipEvent_t* wait_ev, bool small_scalars) {
-    const size_t G = msm_group_size(T, n, small_scalars, batch);
+    const size_t G = msm_group_size(small_scalars);
     static const bool dbg = getenv("EZKL_MSM_DEBUG") != nullptr;
     if (dbg) fprintf(stderr, "[ezkl_hip] msm batch: %zu columns of %zu points, %s scalars, groups of %zu\n", batch, n, small_scalars ? "witness-shaped" : "general", G);
     int rc = EZKL_OK;
@@ -1369,7 +1230,18 @@ static int msm_run_groups(Ctx* c, MsmTable* T, size_t base_offset, const fe_t* c
     return rc;
 }
 
-struct MsmBatch;
+// EZKL_MSM_HOST_TIMING: where a synchronous call (msm_run, msm_run_concurrent) spends its host time, one line per 50 calls
+static bool msm_host_timing() { static const bool on = getenv("EZKL_MSM_HOST_TIMING") != nullptr; return on; }
+static double msm_now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+static void msm_host_timing_add(size_t n, double t0, double t1, double t2, double t3) {
+    static double acc[3] = {0, 0, 0};
+    static int calls = 0;
+    acc[0] += t1 - t0; acc[1] += t2 - t1; acc[2] += t3 - t2;
+    if (++calls % 50 == 0) {
+        fprintf(stderr, "[msm host] n=%zu per call: enqueue %.1f us, wait for the GPU %.1f us, host tail %.1f us\n", n, acc[0] / 50, acc[1] / 50, acc[2] / 50);
+        acc[0] = acc[1] = acc[2] = 0;
+    }
+}
 static MsmBatch* g_open_batch_fwd();
 int msm_run(Ctx* c, hipStream_t st, const Bases* b, size_t base_offset, const fe_t* scalars, size_t n, void* out_host) {
     if (g_open_batch_fwd()) return EZKL_ERR_INVALID;
@@ -1379,26 +1251,15 @@ int msm_run(Ctx* c, hipStream_t st, const Bases* b, size_t base_offset, const fe
     if (rc) return rc;
     MsmSlot& sl = g_slots[0];
     if (sl.busy) return EZKL_ERR_INVALID;
-    static const bool host_timing = getenv("EZKL_MSM_HOST_TIMING") != nullptr;      // where a synchronous call spends its host time
-    if (!host_timing) {
-        if ((rc = msm_enqueue(c, sl, st, T, base_offset, &scalars, 1, n, true))) return rc;
-        return msm_finish(sl, out_host);
-    }
-    auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    static double acc[3] = {0, 0, 0};
-    static int calls = 0;
-    const double t0 = now();
+    const bool host_timing = msm_host_timing();
+    const double t0 = host_timing ? msm_now_us() : 0;
     if ((rc = msm_enqueue(c, sl, st, T, base_offset, &scalars, 1, n, true))) return rc;
-    const double t1 = now();
+    if (!host_timing) return msm_finish(sl, out_host);
+    const double t1 = msm_now_us();
     EZ_HIP(hipEventSynchronize(sl.done));
-    const double t2 = now();
+    const double t2 = msm_now_us();
     rc = msm_finish(sl, out_host);
-    const double t3 = now();
-    acc[0] += t1 - t0; acc[1] += t2 - t1; acc[2] += t3 - t2;
-    if (++calls % 50 == 0) {
-        fprintf(stderr, "[msm host] n=%zu per call: enqueue %.1f us, wait for the GPU %.1f us, host tail %.1f us\n", n, acc[0] / 50, acc[1] / 50, acc[2] / 50);
-        acc[0] = acc[1] = acc[2] = 0;
-    }
+    msm_host_timing_add(n, t0, t1, t2, msm_now_us());
     return rc;
 }
 
@@ -1468,24 +1329,16 @@ int msm_run_concurrent(Ctx* c, std::unique_lock<std::recursive_mutex>& lk, const
     if (g_open_batch_fwd()) return EZKL_ERR_INVALID;
     if (n == 0) { memset(out_host, 0, 64); return EZKL_OK; }
     int k = -1;
-    static const bool host_timing = getenv("EZKL_MSM_HOST_TIMING") != nullptr;      // where a synchronous call spends its host time
-    auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = host_timing ? now() : 0;
+    const bool host_timing = msm_host_timing();
+    const double t0 = host_timing ? msm_now_us() : 0;
     int rc = msm_call_start(c, lk, b, base_offset, scalars, n, &k);
     if (rc) return rc;
     if (!host_timing) return msm_call_finish(c, lk, k, out_host);
-    static double acc[3] = {0, 0, 0};
-    static int calls = 0;
-    const double t1 = now();
+    const double t1 = msm_now_us();
     (void)hipEventSynchronize(g_call_slots[k].done);
-    const double t2 = now();
+    const double t2 = msm_now_us();
     rc = msm_call_finish(c, lk, k, out_host);
-    const double t3 = now();
-    acc[0] += t1 - t0; acc[1] += t2 - t1; acc[2] += t3 - t2;
-    if (++calls % 50 == 0) {
-        fprintf(stderr, "[msm host] n=%zu per call: enqueue %.1f us, wait for the GPU %.1f us, host tail %.1f us\n", n, acc[0] / 50, acc[1] / 50, acc[2] / 50);
-        acc[0] = acc[1] = acc[2] = 0;
-    }
+    msm_host_timing_add(n, t0, t1, t2, msm_now_us());
     return rc;
 }
 
@@ -1685,7 +1538,7 @@ int msm_batch_push_many(Ctx* c, MsmBatch* mb, const fe_t* const* cols, size_t co
     if (mb->n == 0) { mb->pushed += count; return EZKL_OK; }
     if (!mb->order_ev) EZ_HIP(hipEventCreateWithFlags(&mb->order_ev, hipEventDisableTiming));
     EZ_HIP(hipEventRecord(mb->order_ev, after));
-    const size_t G = msm_group_size(mb->T, mb->n, false);
+    const size_t G = msm_group_size(false);
     int rc = EZKL_OK;
     for (size_t j0 = 0; j0 < count; j0 += G) {
         const size_t cnt = count - j0 < G ? count - j0 : G;

@@ -59,6 +59,8 @@ extern "C" {
  *   EZKL_HIP_DEBUG, EZKL_MSM_DEBUG, EZKL_HIP_JIT_DEBUG, EZKL_HIP_JIT_DUMP=<file>     diagnostics on stderr / the generated sweep source
  *  tuning knobs whose defaults are the measured optimum (NOTEBOOK.md §4; tools/ab.sh sweeps them)
  *   EZKL_MSM_SLOTS 4 | EZKL_MSM_GROUP / _SMALL 6 / _BIG 4 | EZKL_MSM_L (device-chosen) | EZKL_MSM_LMIN 8 | EZKL_MSM_SPAN 16 | EZKL_MSM_E 8
+ *     read at every call: EZKL_MSM_GROUP, EZKL_MSM_L, EZKL_MSM_E;  once per process: EZKL_MSM_SLOTS, _GROUP_SMALL, _GROUP_BIG, _LMIN, _SPAN
+ *     (msm.hip: msm_tuning and msm_slots_init read them all; a value outside the accepted range keeps the default)
  *   EZKL_NTT_MAXR 8 (9 / 10: 2048- / 4096-element tiles) | EZKL_PROVER_SWEEP_TERMS 0 | EZKL_PROVER_SWEEP_INSTRS 640
  *  comparison switches kept because tests or the multi-rank fallbacks use them
  *   EZKL_EVALH_MODE=interp (the sweep interpreter instead of the JIT kernel), EZKL_EVALH_NO_SCHEDULE, EZKL_COMM_UNPACKED=1 (one send / recv per

@@ -4,8 +4,8 @@ partition pass that takes its raw counts from row differences.  Every result is 
 scalars, and every case runs twice into the same call slot and must give the same point both times (a counter or cursor that is not
 re-initialised between tiles or calls shows up there).
 
-Values: the edges of the recoding and of the reduction -- see _edge_values.  Sizes, with the plan and the tiling each one runs at (msm.hip:
-pick_plan and the sort geometry):
+Values: the edges of the recoding and of the reduction -- see _edge_values.  Sizes, with the plan and the tiling each one runs at
+(msm_plan.hpp: pick_plan and msm_plan; tests/cpp/test_msm_plan.cpp pins this table and the geometry at every other size without a device):
     1            W = 64 windows of 4 / 3 bits, one tile
     255          W = 29, one tile of 448 scalars, partly filled
     512, 513     W = 26: exactly one tile of 512, and one tile plus one scalar
