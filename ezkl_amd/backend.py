@@ -63,6 +63,14 @@ class DeviceBuffer:
         _l.check(_l.load().ezkl_hip_memcpy_d2h(_p(out), _vp(self.ptr), C.c_size_t(self.nbytes)), "d2h")
         return out.reshape(shape) if shape is not None else out
 
+    def words(self, first, count=1):
+        """`count` 32-byte words from word `first` on: (count, 4) uint64 -- a few cells of a resident column without the column"""
+        if not 0 <= first <= first + count <= self.nbytes // 32:
+            raise ValueError("words %d .. %d of a buffer of %d" % (first, first + count, self.nbytes // 32))
+        out = np.empty((count, 4), np.uint64)
+        _l.check(_l.load().ezkl_hip_memcpy_d2h(_p(out), _vp(self.ptr + 32 * first), C.c_size_t(32 * count)), "d2h")
+        return out
+
     def free(self):
         if self.ptr:
             _l.load().ezkl_hip_free(_vp(self.ptr))
@@ -862,8 +870,28 @@ def kernel_ms_stats(which, reset=False):
 
 
 class WitnessError(ValueError):
-    """a synthesis on the device met a value outside its decomposition range, or a lookup input outside its table (the layout's own
-    assertions on the host path)"""
+    """a synthesis on the device met a value outside its decomposition range, a lookup input outside its table or a gather index outside
+    its table (the layout's own assertions on the host path)"""
+
+
+def witness_tile(columns, k, unit_rows, tiles, pairs, stream=None):
+    """a tiled circuit from its unit (ezkl_hip_witness_tile_dev): for every (dst, src) of `pairs`, column indices into `columns`
+    (DeviceBuffers of 2^k Montgomery words), rows [t * U, (t + 1) * U) of dst get rows [0, U) of src -- every t < tiles for a block copy,
+    t >= 1 for a column tiled onto itself.  Rows past tiles * unit_rows and columns outside the pairs stay as they are.  One launch,
+    not waited for (device time: last_kernel_ms("witness_tile")).  Raises ValueError, nothing launched, on a geometry or a pair list
+    the library refuses."""
+    if any(c.nbytes < (32 << k) for c in columns):
+        raise ValueError("a column shorter than 2^%d words" % k)
+    pairs = [(int(d), int(s)) for d, s in pairs]
+    if any(not 0 <= v < 1 << 32 for p in pairs for v in p) or not (0 <= unit_rows < 1 << 32 and 0 <= tiles < 1 << 32):
+        raise ValueError("witness_tile: an argument outside 32 bits")
+    ptrs = (_vp * len(columns))(*[c.ptr for c in columns])
+    dst, src = (np.ascontiguousarray([p[i] for p in pairs], dtype=np.uint32) for i in (0, 1))
+    rc = _l.load().ezkl_hip_witness_tile_dev(ptrs, C.c_uint32(len(columns)), C.c_uint32(k), C.c_uint32(unit_rows), C.c_uint32(tiles), _p(dst), _p(src),
+                                             C.c_uint32(len(pairs)), _stream_ptr(stream))
+    if rc == -3:
+        raise ValueError("witness_tile: refused (unit_rows %d x tiles %d at k = %d, %d pairs)" % (unit_rows, tiles, k, len(pairs)))
+    _l.check(rc, "ezkl_hip_witness_tile_dev")
 
 
 class WitnessPlan:

@@ -22,6 +22,14 @@
 //    see wit_rlc_kernel.  The contraction "j,j->" is a dot record with w = 1; everything else is a copy.  An operand of a matmul
 //    outside |v| < 2^31 is reported as the range failures below are ("einsum operand outside the exact-product range").
 //
+//  * the surrogate's ops.  sum / prod records (BaseRegion._accumulate, layouts.rs:2472-2621: the running sum or product of w cells per
+//    row): the chunked scan of the dot records with one operand per entry and addition or the Montgomery product as the monoid, see
+//    wit_acc_kernel.  gather records (row `index` of a dynamic table, the structure of `select`, layouts.rs:1483-1581): an element-wise
+//    kind -- the signed index, the bounds test, then one index load and one cell copy; an index outside the table is reported as the
+//    range failures below are ("gather index outside the table") and is never used as an address.  clamp records: min(max(s, lo), hi),
+//    element-wise, never failing.  ezkl_hip_witness_tile_dev repeats the unit rows [0, U) a plan wrote down its columns and into the
+//    columns of the other blocks, see wit_tile_kernel.
+//
 // A value that does not fit its decomposition (|x| >= base^legs: the layout's "value exceeds the decomposition range") writes nothing
 // wrong silently, and neither does a lookup input outside its table (layouts.rs:5143-5222 `nonlinearity`; the layout's "lookup input
 // outside the table range"), and neither does a dividend of `div` beyond the range in which the integer quotient is the reference's f64
@@ -96,6 +104,7 @@ __global__ __launch_bounds__(256) void wit_elem_kernel(WitCols cols, uint32_t k,
                                                        const int64_t* __restrict__ ints, const fe_t* __restrict__ consts, uint32_t rec,
                                                        unsigned long long* status) {
     // TABLE / TBLIDX: the launcher has resolved the table directory -- ints = the table's values, p0 = lo (int32), p1 = n, p2 = col_size
+    // GATHER: b = the table's cell list (pool + p0), p1 = its length
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < count;
     bool fail = false;
@@ -130,6 +139,17 @@ __global__ __launch_bounds__(256) void wit_elem_kernel(WitCols cols, uint32_t k,
                     const uint64_t q = (mag + p0 / 2) / p0;                                   // < 2^52 + 2^31
                     v = wit_from_i64(neg ? -(int64_t)q : (int64_t)q);
                 }
+            } else if (KIND == GATHER) {                                                      // the cell b[s], 0 <= s < p1: tested before b[s] is read
+                fail = !fits || neg || mag >= p1;
+                if (!fail) v = ld_fe(wit_cell(cols, k, b[mag]));
+            } else if (KIND == CLAMP) {                                                       // min(max(s, lo), hi); beyond 62 bits: by the sign
+                const int64_t lo = (int32_t)p0, hi = (int32_t)p1;
+                int64_t s = neg ? lo : hi;
+                if (fits) {
+                    s = neg ? -(int64_t)mag : (int64_t)mag;
+                    s = s < lo ? lo : s > hi ? hi : s;
+                }
+                v = wit_from_i64(s);
             } else if (KIND == RCIDX) {                                                       // |x - lo| // col_size
                 fail = !fits;                                                                 // |x| >= 2^62: as run_plan_host refuses it
                 const int64_t s = neg ? -(int64_t)mag : (int64_t)mag, diff = s - (int64_t)(int32_t)p0;
@@ -193,6 +213,52 @@ __global__ __launch_bounds__(64) void wit_dot_kernel(WitCols cols, uint32_t k, c
             const uint32_t cell = dst[(size_t)s * n_dots + d];
             if (cell == NONE) continue;
             acc = wit_dot_row(cols, k, a, b, n_dots, w, s, d, acc);
+            st_fe(wit_cell(cols, k, cell), acc);
+            wrote++;
+        }
+    wit_count(wrote, status);
+}
+
+// The running sum (SUMACC) or product (PRODACC) of w cells per row: wit_dot_kernel with one operand per entry and the fold as the monoid.
+// DOT_LANES consecutive lanes share one scan; step s of scan d: dst[s * n_scans + d], operands a[(s * w + j) * n_scans + d], j < w
+// (0xffffffff: none).  Pass 1: a lane folds its chunk of steps from the identity.  The shuffle scan over the group's lanes gives each
+// lane the running value at the start of its chunk.  Pass 2: the lane walks its chunk again and writes every row.  Field addition and
+// the Montgomery product are exact, associative and commutative: the bits are those of the row-by-row walk.
+template <uint32_t KIND>
+EZ_D fe_t wit_fold(const fe_t& x, const fe_t& y) { return KIND == SUMACC ? Fr::add(x, y) : Fr::mul(x, y); }
+template <uint32_t KIND>
+EZ_D fe_t wit_acc_row(const WitCols& cols, uint32_t k, const uint32_t* __restrict__ a, uint32_t n_scans, uint32_t w, uint32_t s, uint32_t d, fe_t acc) {
+    for (uint32_t j = 0; j < w; j++) {
+        const uint32_t ia = a[((size_t)s * w + j) * n_scans + d];
+        if (ia != NONE) acc = wit_fold<KIND>(acc, ld_fe(wit_cell(cols, k, ia)));
+    }
+    return acc;
+}
+template <uint32_t KIND>
+__global__ __launch_bounds__(64) void wit_acc_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* __restrict__ a, uint32_t n_scans,
+                                                     uint32_t w, uint32_t n_steps, unsigned long long* status) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t g = (uint32_t)(t % DOT_LANES), chunk = (n_steps + DOT_LANES - 1) / DOT_LANES;
+    const bool live = t / DOT_LANES < n_scans;                   // the same for every lane of a group
+    const uint32_t d = live ? (uint32_t)(t / DOT_LANES) : 0;
+    const uint32_t s0 = g * chunk < n_steps ? g * chunk : n_steps, s1 = s0 + chunk < n_steps ? s0 + chunk : n_steps;
+    const fe_t id = KIND == SUMACC ? Fr::zero() : Fr::one();
+    fe_t run = id;
+    if (live)
+        for (uint32_t s = s0; s < s1; s++)
+            if (dst[(size_t)s * n_scans + d] != NONE) run = wit_acc_row<KIND>(cols, k, a, n_scans, w, s, d, run);
+    for (uint32_t off = 1; off < DOT_LANES; off <<= 1) {           // inclusive scan of the chunk folds over the group
+        const fe_t o = wit_shfl_up(run, off);
+        if (g >= off) run = wit_fold<KIND>(run, o);
+    }
+    fe_t acc = wit_shfl_up(run, 1);                               // exclusive: the running value before this lane's first row
+    if (g == 0) acc = id;
+    uint32_t wrote = 0;
+    if (live)
+        for (uint32_t s = s0; s < s1; s++) {
+            const uint32_t cell = dst[(size_t)s * n_scans + d];
+            if (cell == NONE) continue;
+            acc = wit_acc_row<KIND>(cols, k, a, n_scans, w, s, d, acc);
             st_fe(wit_cell(cols, k, cell), acc);
             wrote++;
         }
@@ -311,6 +377,22 @@ __global__ __launch_bounds__(64) void wit_gather_kernel(WitCols cols, uint32_t k
     if (i < n) st_fe(out + i, ld_fe(wit_cell(cols, k, cells[i])));
 }
 
+// ezkl_hip_witness_tile_dev: rows [t * U, (t + 1) * U) of dst[pair] get rows [0, U) of src[pair].  One lane per destination cell, a
+// 32-byte copy each; consecutive lanes take consecutive rows, so both sides coalesce.  Grid: x over the T * U rows, y over the pairs.
+// A self-pair (dst == src) skips t = 0: it reads rows [0, U) and writes rows [U, T * U) of its column, disjoint by construction, and
+// the host has refused a source that is another pair's destination -- no lane reads a cell that a lane of this launch writes.
+struct WitTile {
+    fe_t* dst[MAX_ADVICE];
+    const fe_t* src[MAX_ADVICE];
+};
+__global__ __launch_bounds__(256) void wit_tile_kernel(WitTile t, uint32_t unit_rows, uint32_t rows) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;       // rows = T * U <= 2^28
+    fe_t* dst = t.dst[blockIdx.y];
+    const fe_t* src = t.src[blockIdx.y];
+    if (i >= rows || (dst == src && i < unit_rows)) return;
+    st_fe(dst + i, ld_fe(src + i % unit_rows));
+}
+
 struct DevPlan {
     Plan host;                      // the validated blob: records, outputs and counts drive the launches; pool / params / consts are
                                     // released once they are on the device (n_params is kept for ezkl_hip_witness_plan_info)
@@ -346,7 +428,8 @@ void launch_elem(hipStream_t st, const WitCols& cols, uint32_t k, const DevPlan*
         ints = p->table_values + t.off;
         p0 = (uint32_t)t.lo; p1 = t.n; p2 = t.col_size;
     }
-    hipLaunchKernelGGL(wit_elem_kernel<KIND>, dim3(cdiv(r.count, 256)), dim3(256), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, p->pool + r.b, r.count, p0, p1, p2,
+    const uint32_t* b = p->pool + (KIND == GATHER ? r.p0 : r.b);     // GATHER: the table's cell list, inside the pool: checked on upload
+    hipLaunchKernelGGL(wit_elem_kernel<KIND>, dim3(cdiv(r.count, 256)), dim3(256), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, b, r.count, p0, p1, p2,
                        ints, (const fe_t*)p->consts, ri, p->status);
 }
 }  // namespace
@@ -501,6 +584,16 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
         case TABLE: launch_elem<TABLE>(st, cols, k, p, r, (uint32_t)ri); break;
         case TBLIDX: launch_elem<TBLIDX>(st, cols, k, p, r, (uint32_t)ri); break;
         case DIVC: launch_elem<DIVC>(st, cols, k, p, r, (uint32_t)ri); break;
+        case GATHER: launch_elem<GATHER>(st, cols, k, p, r, (uint32_t)ri); break;
+        case CLAMP: launch_elem<CLAMP>(st, cols, k, p, r, (uint32_t)ri); break;
+        case SUMACC:
+            hipLaunchKernelGGL(wit_acc_kernel<SUMACC>, dim3(cdiv((size_t)r.count * DOT_LANES, 64)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, r.count, r.p0, r.p1,
+                               p->status);
+            break;
+        case PRODACC:
+            hipLaunchKernelGGL(wit_acc_kernel<PRODACC>, dim3(cdiv((size_t)r.count * DOT_LANES, 64)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, r.count, r.p0, r.p1,
+                               p->status);
+            break;
         case MATMUL: {
             const uint32_t m = r.count / r.p1;
             hipLaunchKernelGGL(wit_matmul_kernel, dim3(cdiv(m, MM_TILE) * cdiv(r.p1, MM_TILE)), dim3(MM_TILE * MM_TILE), 0, st, cols, k, p->pool + r.dst, p->pool + r.a,
@@ -539,6 +632,7 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
         const char* what = kind == TABLE || kind == TBLIDX ? "witness: lookup input outside the table range ("
                            : kind == MATMUL               ? "witness: einsum operand outside the exact-product range ("
                            : kind == DIVC                 ? "witness: rebase dividend outside the exact-division range ("
+                           : kind == GATHER               ? "witness: gather index outside the table ("
                                                           : "witness: value exceeds the decomposition range (";
         t_wit_error = std::string(what) + (kind < N_KINDS ? KIND_NAMES[kind] : "?") + " record " + std::to_string(ri) +
                       ", element " + std::to_string(el) + "; " + std::to_string(dev_status[0]) + (kind == MATMUL ? " operand reads in all)" : " cells in all)");
@@ -547,6 +641,42 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
     p->done_phase = (int)phase;
     if (first) memcpy(p->done_cols, advice_cols_dev, h.n_advice * sizeof(void*));
     t_wit_error.clear();
+    return EZKL_OK;
+}
+
+int ezkl_hip_witness_tile_dev(void* const* advice_cols_dev, uint32_t n_advice, uint32_t k, uint32_t unit_rows, uint32_t tiles, const uint32_t* dst_cols,
+                              const uint32_t* src_cols, uint32_t n_pairs, void* stream) {
+    if (!advice_cols_dev || n_advice == 0 || n_advice > MAX_ADVICE || k < 1 || k > 28 || (n_pairs && (!dst_cols || !src_cols))) return EZKL_ERR_INVALID;
+    if (unit_rows == 0 || tiles == 0 || (uint64_t)unit_rows * tiles > ((uint64_t)1 << k)) return EZKL_ERR_INVALID;
+    bool is_dst[MAX_ADVICE] = {false}, is_src_of_other[MAX_ADVICE] = {false};
+    for (uint32_t i = 0; i < n_pairs; i++) {
+        const uint32_t d = dst_cols[i], s = src_cols[i];
+        if (d >= n_advice || s >= n_advice || !advice_cols_dev[d] || !advice_cols_dev[s]) return EZKL_ERR_INVALID;
+        if (is_dst[d]) return EZKL_ERR_INVALID;                      // a column appears twice as dst
+        is_dst[d] = true;
+        if (d != s) is_src_of_other[s] = true;
+    }
+    WitTile t;
+    for (uint32_t i = 0; i < n_pairs; i++) {
+        const uint32_t d = dst_cols[i], s = src_cols[i];
+        if (d != s && is_src_of_other[d]) return EZKL_ERR_INVALID;   // its rows [0, U) would be written while another pair reads them
+        for (uint32_t j = 0; j < n_pairs; j++)                       // two columns on one buffer: the same hazards under other names
+            for (const uint32_t o : {dst_cols[j], src_cols[j]})
+                if ((o != d && advice_cols_dev[o] == advice_cols_dev[d]) || (o != s && advice_cols_dev[o] == advice_cols_dev[s])) return EZKL_ERR_INVALID;
+        t.dst[i] = static_cast<fe_t*>(advice_cols_dev[d]);
+        t.src[i] = static_cast<const fe_t*>(advice_cols_dev[s]);
+    }
+    if (n_pairs == 0) return EZKL_OK;
+    EZ_CTX(c);
+    hipStream_t st = pick_stream(c, stream);
+    hipEvent_t e0, e1;
+    int rc = ev_pair(c, "witness_tile", &e0, &e1);
+    if (rc) return rc;
+    const uint32_t rows = unit_rows * tiles;
+    EZ_HIP(hipEventRecord(e0, st));
+    hipLaunchKernelGGL(wit_tile_kernel, dim3(cdiv(rows, 256), n_pairs), dim3(256), 0, st, t, unit_rows, rows);
+    EZ_HIP(hipGetLastError());
+    EZ_HIP(hipEventRecord(e1, st));
     return EZKL_OK;
 }
 

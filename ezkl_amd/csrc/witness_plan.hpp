@@ -22,6 +22,18 @@
 // out[t] = out[t - 1] * c + c * v[t], v[t] = cell a[t * count + d], out[t] -> cell dst[t * count + d].
 // A DIVC record (the rebase division of an MLP layer, layouts.rs:219-267 `div`): a = source cell, p0 = d >= 1 (zero: refused); with s the
 // signed value of the cell, sgn(s) * ((|s| + d / 2) / d) -- s / d rounded half away from zero.  |s| >= 2^52 is a run-time failure of the lane.
+// Kind 16 is unassigned (refused as an unknown kind); SUMACC, PRODACC, GATHER and CLAMP are 17 .. 20.
+// A SUMACC / PRODACC record (BaseRegion._accumulate, layouts.rs:2472-2621 `sum` / `prod`): count scans of p1 steps with p0 operands each,
+// step-major as DOT is; step s of scan d folds the cells a[(s * p0 + j) * count + d], j < p0 (0xffffffff: no operand -- the duplicated row
+// at the top of a new column), into the running value (0 at the start of a sum, 1 of a product) and writes it to dst[s * count + d]
+// (0xffffffff: the scan has no such step: a ragged record).  b is unused and zero.  p0 or p1 zero, or an index array past the pool: "bad
+// scan shape".
+// A GATHER record: a = the cell holding the index, p0 = the pool offset of the table's cell list, p1 = its length n >= 1 ("empty gather
+// table", "gather table runs past the pool"); with s the signed value of the index cell the destination gets the value of cell
+// pool[p0 + s].  Every cell of the list is one a lane can read: in range and written by an earlier record.  s < 0, s >= n or |s| >= 2^62
+// is a run-time failure of the lane ("gather index outside the table"), tested before pool[p0 + s] is read.
+// A CLAMP record: a = source cell, p0 = lo, p1 = hi (int32, lo <= hi, else "bad clamp bounds"): min(max(s, lo), hi); a value beyond 62 bits
+// clamps by its sign.  It never fails.
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -33,9 +45,9 @@ namespace ezkl {
 namespace wplan {
 
 constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64, MAX_PHASES = 3, MAX_CHALLENGES = 64;
-enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC, N_KINDS };
+enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC, UNASSIGNED, SUMACC, PRODACC, GATHER, CLAMP, N_KINDS };     // 16 names nothing: refused as unknown
 static const char* const KIND_NAMES[N_KINDS] = {"copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot",
-                                                "nonlinearity", "nonlinearity_index", "matmul", "rlc", "div"};
+                                                "nonlinearity", "nonlinearity_index", "matmul", "rlc", "div", "?", "sum", "prod", "gather", "clamp"};
 struct Rec {
     uint32_t kind, count, p0, p1, dst, a, b, phase;
 };
@@ -135,7 +147,7 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
     uint32_t last_phase = 0;
     for (size_t ri = 0; ri < out.recs.size(); ri++) {
         const Rec& r = out.recs[ri];
-        if (r.kind >= N_KINDS) return at_rec(ri, r.kind, "unknown kind");
+        if (r.kind >= N_KINDS || r.kind == UNASSIGNED) return at_rec(ri, r.kind, "unknown kind");
         if (r.count == 0) return at_rec(ri, r.kind, "empty");
         if (r.phase >= n_phases) return at_rec(ri, r.kind, "phase out of range");
         if (r.phase < last_phase) return at_rec(ri, r.kind, "phases decrease");
@@ -174,17 +186,33 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
             if (r.p1 == 0 || (uint64_t)r.count * r.p1 > P.size()) return at_rec(ri, r.kind, "bad rlc shape");
             n_dst = n_a = (uint64_t)r.count * r.p1; a_cells = true;
             break;
+        case SUMACC: case PRODACC:                       // p0 = operands per step, p1 = steps, count = scans
+            if (r.p0 == 0 || r.p1 == 0 || !span_ok(r.dst, (uint64_t)r.count * r.p1) || !span_ok(r.a, (uint64_t)r.count * r.p1 * r.p0)) return at_rec(ri, r.kind, "bad scan shape");
+            n_dst = (uint64_t)r.count * r.p1; n_a = n_dst * r.p0; a_cells = true;
+            break;
+        case GATHER: {                                   // p0 = pool offset of the table's cell list, p1 = its length
+            a_cells = true;
+            if (r.p1 == 0) return at_rec(ri, r.kind, "empty gather table");
+            if (!span_ok(r.p0, r.p1)) return at_rec(ri, r.kind, "gather table runs past the pool");
+            for (uint32_t i = 0; i < r.p1; i++) {        // every cell of the table is one a lane can read
+                const uint32_t x = P[r.p0 + i];
+                if (x >= cells) return at_rec(ri, r.kind, "cell index out of range");
+                if (!written.get(x)) return at_rec(ri, r.kind, "a cell is read before an earlier record has written it");
+            }
+            break;
+        }
+        case CLAMP: a_cells = true; if ((int32_t)r.p0 > (int32_t)r.p1) return at_rec(ri, r.kind, "bad clamp bounds"); break;
         case DOT:
             if (r.p0 == 0 || r.p1 == 0 || (uint64_t)r.count * r.p1 > P.size() || (uint64_t)r.count * r.p1 * r.p0 > P.size()) return at_rec(ri, r.kind, "bad dot shape");
             n_dst = (uint64_t)r.count * r.p1; n_a = n_b = n_dst * r.p0; a_cells = b_cells = true;
             break;
         }
         if (!span_ok(r.dst, n_dst) || !span_ok(r.a, n_a) || !span_ok(r.b, n_b)) return at_rec(ri, r.kind, "an index array runs past the pool");
-        const bool sparse = r.kind == DOT;               // 0xffffffff = no entry
+        const bool sparse = r.kind == DOT || r.kind == SUMACC || r.kind == PRODACC;     // 0xffffffff = no entry
         for (uint64_t i = 0; i < n_a; i++) {
             const uint32_t x = P[r.a + i];
             if (sparse && x == NONE) {
-                if (P[r.b + i] != NONE) return at_rec(ri, r.kind, "a product with one operand");
+                if (r.kind == DOT && P[r.b + i] != NONE) return at_rec(ri, r.kind, "a product with one operand");
                 continue;
             }
             if (a_cells) {

@@ -30,6 +30,12 @@ def signed(v):
 
 
 DIV_ERROR = "rebase dividend outside the exact-division range"
+GATHER_ERROR = "gather index outside the table"
+
+
+def clamped(s, lo, hi):
+    """the signed value s held to [lo, hi] (a recording region's symbol answers for itself: a CLAMP record)"""
+    return s.clamped(lo, hi) if hasattr(s, "clamped") else min(max(s, lo), hi)
 
 
 def round_div(s, d):
@@ -211,11 +217,15 @@ class EinsumMatmulCircuit:
         """a, b: len x len integer arrays (values mod r).  challenges=None: first phase (first-phase columns, selectors, copies);
         else the two challenges: everything.  Returns the Region (a fresh one unless the caller hands its own)."""
         L = self.len
-        cur = 0 if challenges is None else 1
         if region is None:
             region = Region(self.cs, self.k)
         A = [[Val(int(a[i][j])) for j in range(L)] for i in range(L)]
         B = [[Val(int(b[j][kk])) for kk in range(L)] for j in range(L)]
+        return self.sequence(region, A, B, *self.host_ops(a, b, challenges))
+
+    def host_ops(self, a, b, challenges=None):
+        """what `sequence` takes besides the operands when it runs on integers: (the product's Vals, rlc, dot, the phase being synthesized)"""
+        cur = 0 if challenges is None else 1
         O = [Val(int(v)) for v in self.matmul(a, b).reshape(-1)]
         def rlc(vals, ci):
             if cur == 0:
@@ -231,7 +241,7 @@ class EinsumMatmulCircuit:
                 acc = (acc + x.v * y.v) % R
                 run.append(Val(acc))
             return run
-        return self.sequence(region, A, B, O, rlc, dot, cur)
+        return O, rlc, dot, cur
 
     def plan_identity(self):
         """what a witness plan of this circuit depends on (witness_plan.params_hash)"""
@@ -618,21 +628,29 @@ class BaseRegion(Region):
         the linear coordinate -- one tuple per cell position -- with that position's input selector on"""
         tabs = self.gc.advices[3:6]
         dyn = getattr(self, "dyn", 0)
+        free = lambda x: Val(x.v) if isinstance(x, Val) else Val(int(x))     # the value alone: neither side of the argument is copy-constrained
+        placed = []
         for r, tri in enumerate(table_rows):
-            for t in range(3):
-                col = tabs[t].inner[0][0]
-                assert dyn + r < tabs[t].col_size, "dynamic table column overflow"
-                if self.witness:
-                    self.column(col)[dyn + r] = int(tri[t]) % R
+            assert all(dyn + r < tabs[t].col_size for t in range(3)), "dynamic table column overflow"
+            placed.append([self.put(tabs[t], dyn + r, free(tri[t])) for t in range(3)])      # one column per VarTensor: linear = row
             self.enable(table_sel, dyn + r)
         self.dyn = dyn + len(table_rows)
+        self.dyn_table = (table_rows, placed)          # the table just written, cell by cell: what `row_at` picks of it read
         vars3 = [self.inputs[0], self.inputs[1], self.output]
         for j, tri in enumerate(picks):
             x, y, z = self.inputs[0].cartesian_coord(self.linear + j)
             for t in range(3):
-                self.put(vars3[t], self.linear + j, Val(int(tri[t])))
+                self.put(vars3[t], self.linear + j, free(tri[t]))
             self.enable(input_sels[(0, (x, y))], z)
         self.increment(len(picks))
+
+    def row_at(self, table_rows, index):
+        """row `index` (a Val) of `table_rows`, as a pick of a dynamic lookup over that table whose keys are its positions 0 .. n - 1: a
+        row chosen by a VALUE (an embedding gather).  The structure of the reference's `select` (layouts.rs:1483-1581): the table keys
+        are the positions, the lookup key is the index."""
+        s = signed(index.v)
+        assert 0 <= s < len(table_rows), GATHER_ERROR
+        return table_rows[s]
 
     def dynamic_lookup(self, table_rows, picks):
         """layouts.rs `dynamic_lookup`: every pick is a row of the table (a gather / embedding lookup)"""
@@ -641,6 +659,12 @@ class BaseRegion(Region):
     def shuffle(self, rows, order):
         """layouts.rs `shuffles`: the inputs are the rows of the reference side in another order (sort / transpose)"""
         self._lookup_any(self.base.shuffle_output_selectors[0], self.base.shuffle_input_selectors, rows, [rows[i] for i in order])
+
+    def einsum(self, ein, A, B, challenges=None):
+        """assign_einsum of an EinsumMatmulCircuit laid over this region's configuration (EinsumMatmulCircuit.over), in this region, at
+        the einsum coordinate: A, B are len x len Vals"""
+        ints = lambda M: np.array([[signed(v.v) for v in row] for row in M], np.int64)
+        ein.sequence(self, A, B, *ein.host_ops(ints(A), ints(B), challenges))
 
     def constrain_instance(self, vals, inst_col, inst_offset=0):
         """Layouter::constrain_instance: the cells are tied to the instance column directly (what a hand-written halo2 circuit does)"""
@@ -897,6 +921,37 @@ class SumProdCircuit(LayoutCircuit):
         return reg
 
 
+class SumProdLayoutCircuit(SumProdCircuit):
+    """SumProdCircuit with its op sequence stated once (`layout`), so that witness_plan.record_plan can run it on symbols: the same
+    cells, values, selectors and copies as its parent's `synthesize`.  length: the number of inputs."""
+
+    def __init__(self, logrows, num_inner_cols, capacity, length):
+        super().__init__(logrows, num_inner_cols, capacity)
+        self.n_inputs = int(length)
+
+    def layout(self, reg, inputs, param):
+        vals = reg.assign(reg.inputs[0], inputs)
+        reg.increment(len(vals))
+        s = reg.sum(vals)
+        p = reg.prod(vals)
+        pw = reg.pairwise(vals[:-1], vals[1:], EC.MULT)
+        sp = reg.sum(pw)
+        outs = [s, p, sp]
+        reg.constrain_instance(outs, self.gc.instance)
+        return outs
+
+    def plan_identity(self):
+        return np.asarray([self.k, self.w, self.n_inputs, self.gc.advices[0].num_blocks()], np.int64).tobytes()
+
+    def synthesize(self, x, witness=True):
+        assert len(x) == self.n_inputs
+        reg = BaseRegion(self.gc, witness)
+        outs = self.layout(reg, [Val(int(v) % R) for v in x], Val)
+        reg.finish(self.gc.const_cols)
+        self.outputs = [v.v for v in outs]
+        return reg
+
+
 class _CopyArray:
     """copy constraints as the (count, 4) uint32 array the native keygen takes (native._copies_array reads `.array`); iterable as pairs
     for the Python keygen of small circuits"""
@@ -960,32 +1015,60 @@ class TransformerSurrogateCircuit:
         self.B = rng.integers(-8, 8, (einsum_len, einsum_len))
 
     # ---- one unit ---------------------------------------------------------------------------------------------------------------------
-    def _unit(self, witness=True):
-        reg = BaseRegion(self.gc, witness)
-        clamp = lambda v: max(-self.lookup_max, min(self.lookup_max, v))
-        d = self.d
-        _, x = reg.decompose([Val(v) for v in self.x], self.base, self.legs)                  # input range check
+    @property
+    def n_inputs(self):
+        """x (d), the tokens (2 d), A then B (L x L each, row-major): the input vector of `layout`, of `build` and of a witness plan"""
+        return 3 * self.d + 2 * self.L * self.L
+
+    def default_inputs(self):
+        """the seeded vectors the circuit is built with when nothing else is given"""
+        return [int(v) for v in list(self.x) + list(self.tokens) + list(np.asarray(self.A).reshape(-1)) + list(np.asarray(self.B).reshape(-1))]
+
+    def _split(self, inputs):
+        d, L = self.d, self.L
+        assert len(inputs) == self.n_inputs, "the surrogate takes %d inputs" % self.n_inputs
+        mat = lambda flat: [flat[i * L:(i + 1) * L] for i in range(L)]
+        return inputs[:d], inputs[d:3 * d], mat(inputs[3 * d:3 * d + L * L]), mat(inputs[3 * d + L * L:])
+
+    def layout(self, reg, inputs, param):
+        """the unit, stated once: `build` runs it on a BaseRegion with the inputs' values, witness_plan.record_plan on a recording region
+        with symbols.  inputs: `n_inputs` Vals; param(v) -> the Val of a circuit parameter (asked for in a fixed order: Wq, W2, b2, the
+        embedding rows, perm_rows).  Returns the values tied to the instance column."""
+        lm, d = self.lookup_max, self.d
+        clamp = lambda v: Val(clamped(signed(v.v), -lm, lm))           # the surrogate's stand-in for a rescale: not copy-constrained
+        xs, tokens, A, B = self._split(list(inputs))
+        _, x = reg.decompose(xs, self.base, self.legs)                                        # input range check
         # attention scores -> softmax: exp lookup, sum, reciprocal lookup, scaling
-        q = [reg.dot(x, [Val(w_) for w_ in row]) for row in self.Wq]
-        e = reg.nonlinearity([Val(clamp(signed(v.v))) for v in q], "exp")
+        q = [reg.dot(x, [param(w_) for w_ in row]) for row in self.Wq]
+        e = reg.nonlinearity([clamp(v) for v in q], "exp")
         tot = reg.sum(e)
-        inv = reg.nonlinearity([Val(clamp(signed(tot.v)))], "recip")
+        inv = reg.nonlinearity([clamp(tot)], "recip")
         reg.pairwise(e, [inv[0]] * d, EC.MULT)
         # layer norm: sum of squares, rsqrt lookup, scaling
         ss = reg.dot(x, x)
-        rs = reg.nonlinearity([Val(clamp(signed(ss.v)))], "rsqrt")
+        rs = reg.nonlinearity([clamp(ss)], "rsqrt")
         reg.pairwise(x, [rs[0]] * d, EC.MULT)
         # MLP: Gemm + bias + ReLU (sign by decomposition)
-        outs = [reg.dot(x, [Val(w_) for w_ in row]) for row in self.W2]
-        h = reg.pairwise(outs, [Val(b) for b in self.b2], EC.ADD)
+        outs = [reg.dot(x, [param(w_) for w_ in row]) for row in self.W2]
+        h = reg.pairwise(outs, [param(b) for b in self.b2], EC.ADD)
         h = reg.relu(h, self.base, self.legs)
-        # embedding gather (dynamic lookup) and a transpose (shuffle)
-        reg.dynamic_lookup(self.emb, [self.emb[t] for t in self.tokens])
-        reg.shuffle(self.perm_rows, self.perm)
-        return reg, h
+        # embedding gather (dynamic lookup: the row a token's VALUE names) and a transpose (shuffle)
+        emb = [tuple(param(v) for v in row) for row in self.emb]
+        reg.dynamic_lookup(emb, [reg.row_at(emb, t) for t in tokens])
+        perm_rows = [tuple(param(v) for v in row) for row in self.perm_rows]
+        reg.shuffle(perm_rows, self.perm)
+        # the Freivalds einsum over the second-phase columns, then the public outputs
+        reg.einsum(self.ein, A, B)
+        reg.output_equals_instance(h, self.gc.instance, 0, self.base, self.legs)
+        return h
 
-    def _einsum(self, reg, challenges):
-        return self.ein.synthesize(self.A, self.B, challenges, region=reg)
+    def plan_identity(self):
+        """what a witness plan of this circuit depends on besides the layout code and the lookup tables (witness_plan.params_hash)"""
+        shape = [self.k, self.blocks, self.d, self.L, self.base, self.legs, self.lookup_max]
+        return b"".join(np.asarray(a, np.int64).tobytes() for a in (shape, self.perm, self.Wq, self.W2, self.b2, self.emb, self.perm_rows))
+
+    def _einsum(self, reg, challenges, A, B):
+        return self.ein.synthesize(A, B, challenges, region=reg)
 
     # ---- the tiling --------------------------------------------------------------------------------------------------------------------
     def _geometry(self, reg):
@@ -994,15 +1077,26 @@ class TransformerSurrogateCircuit:
         rows = max(-(-reg.linear // w), getattr(reg, "dyn", 0), reg.coord) + 1
         return rows, reg.usable // rows
 
-    def build(self, gpu=None, tiles=None, as_ints=False):
+    def build(self, gpu=None, tiles=None, as_ints=False, inputs=None, synthesis="host"):
         """-> dict(cs, fixed, copies, advice (callable(phase, challenges) -> {column: Montgomery array}), instances, info): the inputs of
         keygen and create_proof.  tiles: repeat the unit this many times down the rows (default: as many as fit).  as_ints: the advice
-        callback returns lists of canonical ints (the MockProver's input) instead of Montgomery arrays."""
+        callback returns lists of canonical ints (the MockProver's input) instead of Montgomery arrays.  inputs: the `n_inputs` integers
+        of the unit (default: the seeded vectors).  synthesis: "host" -- the unit laid out in Python, tiled with numpy, converted and
+        uploaded per phase -- or "device" (needs gpu = ezkl_amd.backend): both phases and the tiling run on the device from the circuit's
+        witness plan; `advice` then returns {column: DeviceBuffer} of one resident set of columns, `device_columns` names them for
+        native.create_proof(..., device_columns=...), `witness` holds what to free (`free()`), and the instance vector comes from the
+        plan's outputs."""
+        if synthesis not in ("host", "device"):
+            raise ValueError("synthesis is \"host\" or \"device\", not %r" % (synthesis,))
+        if synthesis == "device" and (gpu is None or as_ints):
+            raise ValueError("synthesis=\"device\" needs a gpu backend and returns device columns")
         gc, cs0, n = self.gc, self.gc.cs, 1 << self.k
-        reg, h = self._unit(witness=True)
-        self._einsum(reg, None)
-        reg.output_equals_instance(h, gc.instance, 0, self.base, self.legs)
+        inputs = self.default_inputs() if inputs is None else [int(v) for v in inputs]
+        reg = BaseRegion(gc, True)
+        h = self.layout(reg, [Val(v) for v in inputs], Val)
         reg.finish(gc.const_cols)
+        _, _, A_in, B_in = self._split(inputs)
+        A_in, B_in = np.array(A_in, np.int64), np.array(B_in, np.int64)
         U, T = self._geometry(reg)
         if tiles is not None:
             T = min(T, tiles)
@@ -1109,7 +1203,7 @@ class TransformerSurrogateCircuit:
                     cols = first
                 else:
                     r2 = Region(cs0, self.k)
-                    self._einsum(r2, tuple(challenges[:2]))
+                    self._einsum(r2, tuple(challenges[:2]), A_in, B_in)
                     cols = columns_of(r2, 1)
                 idx = sorted(cols)
                 cache[key] = cols if as_ints else dict(zip(idx, limbs_to_mont([cols[i] for i in idx], gpu)))
@@ -1119,7 +1213,65 @@ class TransformerSurrogateCircuit:
                             "one unit of %d rows tiled %d x %d times, k=%d" % (self.L, self.L, U, T, B, self.k),
                     unit_rows=U, tiles=T, blocks=B, cells_used=int(reg.linear) * T * B)
         self.outputs = [v.v for v in h]
-        return dict(cs=cs, fixed=fixed, copies=copies, advice=advice, instances=[self.outputs], info=info)
+        out = dict(cs=cs, fixed=fixed, copies=copies, advice=advice, instances=[self.outputs], info=info)
+        if synthesis == "device":
+            out["witness"] = dev = _DeviceSurrogateWitness(self, gpu, inputs, U, T, colmap)
+            out.update(advice=dev.advice, device_columns=list(range(len(cs0.advice))))
+            try:
+                dev.advice(0, [])                                              # (a failing lane raises here, as the host layout's assertion does above)
+                out["instances"] = [dev.read_outputs()]
+            except Exception:
+                dev.free()
+                raise
+        return out
+
+
+class _DeviceSurrogateWitness:
+    """the surrogate's witness made on the device: phase p replays phase p of the circuit's plan into rows [0, U) of the block-0 and
+    shared columns of one resident set, then tiles the columns of that phase (backend.witness_tile) -- U rows repeated T times down
+    each column and into the columns of the other blocks.  phase_ms[p] = (run, tile) device milliseconds of the last call."""
+
+    def __init__(self, circuit, gpu, inputs, U, T, colmap):
+        from . import witness_plan as WP
+        self.gpu, self.inputs, self.U, self.T, self.k = gpu, list(inputs), U, T, circuit.k
+        host_plan = WP.record_plan(circuit)
+        self.out_cells = [int(c) for c in host_plan.outputs]
+        self.plan = gpu.WitnessPlan(host_plan.to_bytes())
+        self.columns = self.plan.alloc_columns()
+        # the columns the plan writes are tiled onto themselves and, those of block 0, into their blocks; the run of a phase zero-fills every
+        # column of that phase first, the columns of blocks > 0 and the ones no record writes (phase 0) among them
+        written, phase_of = sorted(WP.written_columns(host_plan)), self.plan.column_phase
+        assert all(len(colmap.get(c, [c])) == 1 or colmap[c][0] == c for c in written), "the plan writes block-0 and shared columns only"
+        self.pairs = {p: [(cb, c) for c in written if phase_of[c] == p for cb in colmap.get(c, [c])] for p in range(self.plan.n_phases)}
+        self.outputs, self.phase_ms = None, {}
+
+    def advice(self, phase, challenges):
+        phase = int(phase)
+        _, outs = self.plan.run(self.inputs, columns=self.columns, phase=phase, challenges=list(challenges))
+        run_ms = self.plan.last["device_ms"]
+        self.gpu.witness_tile(self.columns, self.k, self.U, self.T, self.pairs[phase])
+        self.phase_ms[phase] = (run_ms, self.gpu.last_kernel_ms("witness_tile"))   # (reading the tile's events waits for it: the columns are final)
+        if phase == self.plan.n_phases - 1:
+            self.outputs = outs
+        return {c: self.columns[c] for c in range(self.plan.n_advice) if self.plan.column_phase[c] == phase}
+
+    def set_inputs(self, inputs):
+        """the inputs of the runs that follow (phase 0 takes them)"""
+        if len(inputs) != self.plan.n_inputs:
+            raise ValueError("the plan takes %d inputs, got %d" % (self.plan.n_inputs, len(inputs)))
+        self.inputs = [int(v) for v in inputs]
+
+    def read_outputs(self):
+        """the circuit's outputs as canonical ints, read where phase 0 wrote them (the plan gathers them with its last phase)"""
+        M_inv = pow(1 << 256, -1, R)
+        words = [self.columns[c >> self.k].words(c & ((1 << self.k) - 1)) for c in self.out_cells]
+        return [int.from_bytes(w.tobytes(), "little") * M_inv % R for w in words]
+
+    def free(self):
+        for c in self.columns:
+            c.free()
+        self.columns = []
+        self.plan.free()
 
 
 def limbs_to_mont(cols, gpu=None):

@@ -1,4 +1,5 @@
-"""Witness plans: the layout of an MlpCircuit, a ConvMnistCircuit or an EinsumMatmulCircuit recorded ONCE, replayed for every proof.
+"""Witness plans: the layout of an MlpCircuit, a ConvMnistCircuit, an EinsumMatmulCircuit, a SumProdLayoutCircuit or the
+TransformerSurrogateCircuit's unit recorded ONCE, replayed for every proof.
 
 Which advice cell holds which value depends only on the circuit (BaseRegion places cells from the linear coordinate, the duplicated rows
 of `dot` from the block geometry; constants and the circuit's parameters are the same for every input), so `record_plan` runs one
@@ -15,6 +16,14 @@ that comes after every record it reads from.  A cell is written once and read on
 of an existing record can depend on the cell that joins it.  The conv loop alternates dot and add and copies its patches from early
 cells: under the latest-fit rule every patch copy lands behind the previous dot and forces a new dot record, 1751 records for the conv +
 ReLU part at k = 17; by levels it is 25.  The MLP path keeps the latest-fit rule: its blobs stay what they were.)
+The LookupRecordingRegion also records the rest of the layout engine's ops: `sum` / `prod` (one SUMACC / PRODACC scan each), `dynamic_lookup`
+and `shuffle` (both sides of the argument are placed through `put`: parameter, constant, input or copy records; a pick whose row is chosen
+by a VALUE -- `BaseRegion.row_at`, the embedding gather -- is the index itself in the key coordinate and a GATHER element over the cells of
+the dynamic table in every other one; a shuffle in a data-dependent order is refused by name) and `ezkl_layout.clamped` (a CLAMP record).
+The MLP recorder keeps refusing them by name.  The TransformerSurrogateCircuit lays its einsum over its own configuration
+(`BaseRegion.einsum`): it is recorded on a PhasedLookupRecordingRegion -- the lookup region with the einsum region's `put_cell`, matmul
+record, running values and phase bookkeeping -- into a TWO-phase plan of the unit's rows; the tiling is the device's
+(ezkl_hip_witness_tile_dev).
 
 The plan is a flat little-endian blob (`WitnessPlan.to_bytes`):
 
@@ -40,9 +49,18 @@ A record of an element-wise kind has `count` destination cells pool[dst + i], pr
     DIVC   a = source cell, p0 = d (u32, >= 1), p1 = 0: with s the signed value of the cell, sgn(s) * ((|s| + d // 2) // d) -- s / d rounded half
            away from zero, the claimed quotient of `div` (ezkl_layout.round_div); |s| >= 2^52 is the run-time failure "rebase dividend outside
            the exact-division range", reported like the decomposition-range failure
+    GATHER a = the cell holding the index, p0 = the pool offset of the table's cell list, p1 = its length n >= 1: with s the signed value of
+           the index cell, the value of cell pool[p0 + s].  s < 0, s >= n or |s| >= 2^62 is the run-time failure "gather index outside the table",
+           reported like the decomposition-range failure; the lane tests s before it reads pool[p0 + s]
+    CLAMP  a = source cell, p0 = lo, p1 = hi (int32, lo <= hi): min(max(s, lo), hi); a value beyond 62 bits clamps by its sign; never fails
     DOT    count dot products of p1 steps of p0 products each, step-major: step s of dot d writes the running sum to pool[dst + s * count + d]
            (0xffffffff: no such step) after adding the products of pool[a + (s * p0 + j) * count + d] and pool[b + ...] (0xffffffff: none --
            the duplicated running sum at the top of a new column is a step without products)
+    (kind 16 is unassigned: a plan that uses it is refused as an unknown kind; the four kinds below are 17 .. 20)
+    SUMACC / PRODACC   count scans of p1 steps with p0 operands each, step-major as DOT is: step s of scan d folds the cells
+           pool[a + (s * p0 + j) * count + d], j < p0 (0xffffffff: no operand -- the duplicated row at the top of a new column), into the running
+           value (0 at the start of a sum, 1 of a product) and writes it to pool[dst + s * count + d] (0xffffffff: the scan has no such step: a
+           ragged record); b is unused and zero   (BaseRegion._accumulate, layouts.rs:2472-2621)
     TABLE  a = source cell, p0 = table index: with s the signed value of the cell, values[offset + (s - lo)] as a field element (a negative
            value as integer_rep_to_felt maps it)
     TBLIDX a = source cell, p0 = table index: (s - lo) // col_size, the table column that holds s
@@ -69,6 +87,10 @@ equality tests of tests/test_witness_plan_cpu.py fail loudly -- an assert or a P
     range_check               `abs(s - lo) // col_size`
     pairwise                  `x + y`, `x - y`, `x * y` on two assigned cells
     dot                       `acc = (acc + sum(x.v * y.v for ...)) % R` with acc and sum() starting from the integer 0
+    sum (_accumulate)         `(acc + sum(chunk)) % R` with acc and sum() starting from the integer 0, chunk = the w cells of the row
+    prod (_accumulate)        `acc = acc * v % R` over the w cells of the row, acc starting from the integer 1
+    clamped (module level)    `s.clamped(lo, hi)` when the signed value is a symbol, `min(max(s, lo), hi)` otherwise
+    row_at                    overridden: `assert 0 <= signed(index.v) < len(table_rows)` is the run-time check of GATHER
     equals_zero               `pow(v, -1, R) if v else 0`   (the truth value of a cell symbol is True: INVZ covers both branches)
     div (round_div)           `mag = abs(s)`, `assert mag < 1 << 52` (recorded as the run-time check), `((s > 0) - (s < 0)) * ((mag + d // 2) // d)`
     nonlinearity              `assert table.range[0] <= signed(v) <= table.range[1]` (recorded as the run-time check), `table.f(signed(v)) % R`,
@@ -89,13 +111,16 @@ R = EL.R
 MAGIC, VERSION = 0x50575A45, 1                  # "EZWP"
 NONE = 0xFFFFFFFF
 COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC = range(16)
+UNASSIGNED = 16                                    # the kind after DIVC names nothing and never will: both validators refuse it as unknown
+SUMACC, PRODACC, GATHER, CLAMP = range(17, 21)
 KIND_NAMES = ["copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot", "nonlinearity", "nonlinearity_index", "matmul", "rlc",
-              "div"]
+              "div", "?", "sum", "prod", "gather", "clamp"]
 _HEADER = struct.Struct("<20I32s")
 RANGE_ERROR = "value exceeds the decomposition range"
 LOOKUP_ERROR = "lookup input outside the table range"
 OPERAND_ERROR = "einsum operand outside the exact-product range"
 DIV_ERROR = EL.DIV_ERROR
+GATHER_ERROR = "gather index outside the table"
 MAX_PHASES, MAX_CHALLENGES = 3, 64
 
 
@@ -138,6 +163,15 @@ class _Cell(_Sym):
     def __pow__(self, e, m=None):
         assert e == -1 and m == R
         return _Un(INVZ, self)
+    def __radd__(self, o):                         # sum(chunk) starts from 0: the operands of one step of `sum`
+        if not (isinstance(o, int) and o == 0):
+            self._no()
+        return _Operands([self.idx])
+    def __rmul__(self, o):                         # `acc * v` with acc = 1: the first operand of the first step of `prod`
+        if not (isinstance(o, int) and o == 1):
+            self._no()
+        return _Fold(PRODACC, None, [self.idx])
+    def clamped(self, lo, hi): return _Clamp(self, lo, hi)      # ezkl_layout.clamped on the signed value
 
 
 class _Input(_Sym):
@@ -182,6 +216,57 @@ class _Acc(_Sym):
 
 class _Un(_Sym):
     def __init__(self, kind, a): self.kind, self.a = kind, a.idx
+
+
+class _Operands(_Sym):
+    """the w cells one step of `sum` adds"""
+
+    def __init__(self, cells): self.cells = cells
+    def __add__(self, o):
+        if not isinstance(o, _Cell):
+            self._no()
+        return _Operands(self.cells + [o.idx])
+    def __radd__(self, o):                         # acc + sum(chunk), acc = 0 on the first step
+        if not (isinstance(o, int) and o == 0):
+            self._no()
+        return _Fold(SUMACC, None, self.cells)
+
+
+class _Fold(_Sym):
+    """a running sum or product (`_accumulate`): the previous running value (None on the first step) folded with this step's cells; `cell`
+    once it has been put"""
+
+    def __init__(self, kind, prev, cells): self.kind, self.prev, self.cells, self.cell = kind, prev, cells, None
+    def __add__(self, o):
+        if not (self.kind == SUMACC and isinstance(o, _Operands) and self.cell is not None):
+            self._no()
+        return _Fold(SUMACC, self, o.cells)
+    def __mul__(self, o):                          # the next operand of this step, or -- once the running value is placed -- of the next
+        if not (self.kind == PRODACC and isinstance(o, _Cell)):
+            self._no()
+        return _Fold(PRODACC, self, [o.idx]) if self.cell is not None else _Fold(PRODACC, self.prev, self.cells + [o.idx])
+
+
+class _Clamp(_Sym):
+    def __init__(self, a, lo, hi): self.a, self.lo, self.hi = a.idx, lo, hi
+
+
+class _Pick:
+    """one data-dependent pick of a dynamic lookup (`row_at`): the table's rows, and the cell its key coordinate was placed in"""
+
+    def __init__(self, rows): self.rows, self.key = rows, None
+
+
+class _PickKey(_Sym):
+    """the key coordinate of a pick: the index value itself"""
+
+    def __init__(self, pick, inner): self.pick, self.inner = pick, inner
+
+
+class _Gathered(_Sym):
+    """coordinate t of the table row the pick's key names"""
+
+    def __init__(self, pick, t): self.pick, self.t = pick, t
 
 
 class _Cmp(_Sym):
@@ -320,6 +405,17 @@ class _Records:
                 raise PlanError("advice cell %d is read before it is written" % s)
         ri = self._slot((DOT, w, 0), reads, phase)
         self.recs[ri]["dots"].append(steps)
+        for dst, _ in steps:
+            self._claim(dst, ri)
+
+    def emit_acc(self, kind, w, steps, phase=0):
+        """one running sum / product: steps = [(dst, [cells])]"""
+        reads = [c for _, cells in steps for c in cells]
+        for s in reads:
+            if s not in self.rec_of:
+                raise PlanError("advice cell %d is read before it is written" % s)
+        ri = self._slot((kind, w, 0), reads, phase)
+        self.recs[ri]["scans"].append(steps)
         for dst, _ in steps:
             self._claim(dst, ri)
 
@@ -507,17 +603,88 @@ class LookupRecordingRegion(RecordingRegion):
         self.tables = []
         self.base = _SymBase(gc.base, self)
         self._lookup_src = {}                      # source cell -> (its symbol, table) of the lookups recorded so far
+        self._scan = None                          # the steps of the `sum` / `prod` being laid out
+        self.gather_tables, self._gather_idx = [], {}     # the cell lists GATHER records index, in order of first use
+        self.param_values = None                   # record_plan's parameter list: what a _Param stands for
 
     def nonlinearity(self, vals, name):
         self.n_ops += 1
         return EL.BaseRegion.nonlinearity(self, vals, name)
+
+    # ---- sum / prod: BaseRegion._accumulate on symbols -> one SUMACC / PRODACC scan ----------------------------------------------------------
+    sum, prod = EL.BaseRegion.sum, EL.BaseRegion.prod
+
+    def _accumulate(self, vals, init_op, op, unit, fold):
+        self.n_ops += 1
+        self._scan = []
+        try:
+            last = EL.BaseRegion._accumulate(self, vals, init_op, op, unit, fold)
+            steps = self._scan
+        finally:
+            self._scan = None
+        kinds = {kind for _, _, kind in steps if kind is not None}
+        if kinds != {SUMACC if unit == 0 else PRODACC}:
+            raise PlanError("a running value of another fold than its op's")
+        self.out.emit_acc(kinds.pop(), self.w, [(dst, cells) for dst, cells, _ in steps])
+        return last
+
+    # ---- dynamic_lookup / shuffle: both sides are placed through `put` (BaseRegion._lookup_any) ------------------------------------------------
+    _lookup_any = EL.BaseRegion._lookup_any
+
+    def dynamic_lookup(self, table_rows, picks):
+        self.n_ops += 1
+        return EL.BaseRegion.dynamic_lookup(self, table_rows, picks)
+
+    def shuffle(self, rows, order):
+        self.n_ops += 1
+        if not all(isinstance(i, (int, np.integer)) for i in order):
+            raise PlanError("witness plans do not cover `shuffle` with a data-dependent order (sort, top-k): the order must be integers")
+        return EL.BaseRegion.shuffle(self, rows, order)
+
+    def row_at(self, table_rows, index):
+        """BaseRegion.row_at on symbols: the key coordinate is the index value itself, every other coordinate a GATHER element over the
+        cells of the dynamic table the pick is looked up in -- which must be this very list, with the positions 0 .. n - 1 as its keys"""
+        for r, row in enumerate(table_rows):
+            key = row[0].v if isinstance(row[0], EL.Val) else row[0]
+            if isinstance(key, _Param) and self.param_values is not None:
+                key = self.param_values[key.idx]
+            if not isinstance(key, (int, np.integer)) or key % R != r:
+                raise PlanError("a gather over a table whose keys are not its positions")
+        if not isinstance(index.v, (_Input, _Cell)):
+            raise PlanError("a gather index that is a %s value" % type(index.v).__name__)
+        pick = _Pick(table_rows)
+        return (EL.Val(_PickKey(pick, index.v)),) + tuple(EL.Val(_Gathered(pick, t)) for t in range(1, len(table_rows[0])))
 
     def _asserted(self, cell, table):
         if (getattr(cell, "lo", None), getattr(cell, "hi", None)) != table.range:
             raise PlanError("a lookup without the layout's range assertion")
 
     def _emit(self, v, dst):
-        if isinstance(v, _Looked):
+        if self._scan is not None and isinstance(v, _Cell) and self._scan and v.idx == self._scan[-1][0]:
+            self._scan.append((dst, [], None))     # the running value duplicated at the top of a new column: a step without operands
+        elif isinstance(v, _Fold):
+            folded = [cell for cell, cells, _ in self._scan or [] if cells]
+            if self._scan is None or v.cell is not None or (v.prev is None) != (not folded) or (folded and v.prev.cell != folded[-1]):
+                raise PlanError("a running value outside the sum / prod it belongs to")
+            v.cell = dst
+            self._scan.append((dst, v.cells, v.kind))
+        elif isinstance(v, _Clamp):
+            if not -(1 << 31) <= v.lo <= v.hi < 1 << 31:
+                raise PlanError("clamp bounds beyond 32 bits")
+            self.out.emit(CLAMP, dst, v.a, p0=v.lo & NONE, p1=v.hi & NONE, reads=(v.a,))
+        elif isinstance(v, _PickKey):
+            self._emit(v.inner, dst)
+            v.pick.key = dst
+        elif isinstance(v, _Gathered):
+            rows, placed = getattr(self, "dyn_table", (None, None))
+            if rows is not v.pick.rows or v.pick.key is None:
+                raise PlanError("a gather pick outside the dynamic lookup over its table")
+            cells = tuple(placed[r][v.t].v.idx for r in range(len(rows)))
+            if cells not in self._gather_idx:
+                self._gather_idx[cells] = len(self.gather_tables)
+                self.gather_tables.append(cells)
+            self.out.emit(GATHER, dst, v.pick.key, p0=self._gather_idx[cells], p1=len(cells), reads=(v.pick.key,) + cells)
+        elif isinstance(v, _Looked):
             self._asserted(v.cell, v.table)
             self._lookup_src[v.cell.idx] = (v.cell, v.table)
             self.out.emit(TABLE, dst, v.cell.idx, p0=v.table.index, reads=(v.cell.idx,))
@@ -553,9 +720,10 @@ class EinsumRecordingRegion(EL.Region):
     whatever a challenge enters, otherwise the latest phase among the cells read -- and refuses a value placed in a column of another
     phase.  Records are grouped by kind, phase and dependence level."""
 
-    def __init__(self, circuit):
-        super().__init__(circuit.cs, circuit.k)
-        self.n_adv = len(circuit.cs.advice)
+    def __init__(self, circuit, k=None):
+        cs, k = (circuit.cs, circuit.k) if k is None else (circuit, k)     # a circuit, or -- as Region -- its constraint system and k
+        super().__init__(cs, k)
+        self.n_adv = len(cs.advice)
         self.out = _Records(earliest=True)
         self.consts, self.n_ops = [], 0
         self.phase_of = {}                         # cell -> the phase that writes it
@@ -623,6 +791,28 @@ class EinsumRecordingRegion(EL.Region):
         return _Cell(dst)
 
 
+class PhasedLookupRecordingRegion(LookupRecordingRegion, EinsumRecordingRegion):
+    """LookupRecordingRegion for a circuit that lays an einsum over its own configuration (`BaseRegion.einsum`): the model ops are
+    placed by `put` (phase 0), the einsum's cells by EinsumRecordingRegion's `put_cell` with its matmul record, running values and phase
+    bookkeeping -- one record list, one cell numbering.  (The constructor chain ends in EinsumRecordingRegion's, as a Region's.)"""
+
+    def put(self, var, linear, val):
+        placed = super().put(var, linear, val)
+        dst = placed.v.idx
+        if self.cs.advice[dst >> self.k].phase != 0:
+            raise PlanError("advice column %d belongs to phase %d, the model op placed in it to phase 0" % (dst >> self.k, self.cs.advice[dst >> self.k].phase))
+        self.phase_of[dst] = 0
+        return placed
+
+    def einsum(self, ein, A, B, challenges=None):
+        L = ein.len
+        flat = [v.v for M in (A, B) for row in M for v in row]
+        if not all(isinstance(v, _Input) for v in flat):
+            raise PlanError("an einsum over operands that are not model inputs")
+        O = self.matmul(L, L, L, [v.idx for v in flat[:L * L]], [v.idx for v in flat[L * L:]])
+        ein.sequence(self, A, B, O, self.rlc, lambda xs, ys: EinsumRecordingRegion.dot(self, xs, ys), 1)
+
+
 def _record_einsum(circuit):
     """EinsumMatmulCircuit: its own `sequence` over symbols -- the inputs are A then B, row-major; the product is one MATMUL record"""
     L = circuit.len
@@ -666,11 +856,13 @@ def record_plan(circuit):
     if type(circuit) is EL.EinsumMatmulCircuit and getattr(circuit, "standalone", False):
         return _record_einsum(circuit)
     if not (callable(getattr(circuit, "layout", None)) and callable(getattr(circuit, "plan_identity", None))):
-        raise PlanError("witness plans cover MlpCircuit and circuits that state their `layout`, not %s (sum / prod and the surrogate "
-                        "circuits keep the host path)" % type(circuit).__name__)
-    if any(c.phase != 0 for c in circuit.gc.cs.advice):
+        raise PlanError("witness plans cover MlpCircuit and circuits that state their `layout`, not %s" % type(circuit).__name__)
+    if getattr(circuit, "gc", None) is None:
+        raise PlanError("witness plans are recorded from a configured circuit: this %s has no configuration" % type(circuit).__name__)
+    phased = type(circuit) is EL.TransformerSurrogateCircuit      # its einsum is laid over its own configuration: a two-phase plan
+    if any(c.phase != 0 for c in circuit.gc.cs.advice) and not phased:
         raise PlanError("witness plans do not cover second-phase advice")
-    reg = RecordingRegion(circuit.gc) if type(circuit) is EL.MlpCircuit else LookupRecordingRegion(circuit.gc)
+    reg = RecordingRegion(circuit.gc) if type(circuit) is EL.MlpCircuit else (PhasedLookupRecordingRegion if phased else LookupRecordingRegion)(circuit.gc)
     if (len(circuit.gc.cs.advice) << circuit.k) > 1 << 32:
         raise PlanError("cells are numbered in 32 bits")
     params = []
@@ -680,8 +872,12 @@ def record_plan(circuit):
             raise PlanError("a parameter beyond int64")
         params.append(v)
         return EL.Val(_Param(len(params) - 1))
+    reg.param_values = params
     outs = circuit.layout(reg, [EL.Val(_Input(i)) for i in range(circuit.n_inputs)], param)
     # (reg.finish writes the fixed constant column: keygen's, not the witness's)
+    if phased:
+        return WitnessPlan._from_recorder(circuit, reg, params, [v.v.idx for v in outs], n_challenges=len(circuit.gc.cs.challenges),
+                                          n_phases=1 + max(c.phase for c in circuit.gc.cs.advice))
     return WitnessPlan._from_recorder(circuit, reg, params, [v.v.idx for v in outs])
 
 
@@ -721,6 +917,21 @@ class WitnessPlan:
                     raise PlanError("a matmul output is never placed")
                 n_cells += len(rec["dst"])
                 records.append([MATMUL, len(rec["dst"]), rec["p0"], rec["p1"], push(rec["dst"]), push(rec["a"]), push(rec["b"]), phase])
+            elif rec["kind"] in (SUMACC, PRODACC):
+                w, scans = rec["p0"], rec["scans"]
+                nd, ns = len(scans), max(len(sc) for sc in scans)
+                dst = np.full((ns, nd), NONE, np.uint32)
+                a = np.full((ns, w, nd), NONE, np.uint32)
+                for d, steps in enumerate(scans):
+                    for s, (cell, cells) in enumerate(steps):
+                        dst[s, d] = cell
+                        a[s, :len(cells), d] = cells
+                    n_cells += len(steps)
+                records.append([rec["kind"], nd, w, ns, push(dst), push(a), 0, phase])
+            elif rec["kind"] == GATHER:
+                n = len(rec["dst"])
+                n_cells += n
+                records.append([GATHER, n, push(reg.gather_tables[rec["p0"]]), rec["p1"], push(rec["dst"]), push(rec["a"]), 0, phase])
             elif rec["kind"] == DOT:
                 w, dots = rec["p0"], rec["dots"]
                 nd, ns = len(dots), max(len(d) for d in dots)
@@ -805,6 +1016,10 @@ def peek(blob):
     return dict(zip(names, f[2:14]), n_challenges=f[14], n_phases=f[15] or 1, param_hash=f[20])
 
 
+def _i32(w):
+    return w - (1 << 32) if w >> 31 else w
+
+
 def _span(plan, off, n, what, ri):
     if off > len(plan.pool) or n > len(plan.pool) - off:
         raise PlanError("witness plan: record %d: %s runs past the pool" % (ri, what))
@@ -855,7 +1070,7 @@ def validate(plan):
     total = 0
     col_phase, last_phase = [None] * plan.n_advice, 0
     for ri, (kind, count, p0, p1, dst, a, b, phase) in enumerate(plan.records.tolist()):
-        if kind > DIVC:
+        if kind > CLAMP or kind == UNASSIGNED:
             raise PlanError("witness plan: record %d: unknown kind %d" % (ri, kind))
         if count == 0:
             raise PlanError("witness plan: record %d is empty" % ri)
@@ -882,6 +1097,14 @@ def validate(plan):
                 raise PlanError("witness plan: record %d (%s): bad rlc shape" % (ri, KIND_NAMES[kind]))
             d = _span(plan, dst, count * p1, "dst", ri)
             srcs = _span(plan, a, count * p1, "a", ri)
+        elif kind in (SUMACC, PRODACC):
+            w, ns = p0, p1
+            if w == 0 or ns == 0 or any(off > len(plan.pool) or n > len(plan.pool) - off for off, n in ((dst, count * ns), (a, count * ns * w))):
+                raise PlanError("witness plan: record %d (%s): bad scan shape" % (ri, KIND_NAMES[kind]))
+            d = _span(plan, dst, count * ns, "dst", ri)
+            srcs = _span(plan, a, count * ns * w, "a", ri)
+            srcs = srcs[srcs != NONE]
+            d = d[d != NONE]
         elif kind == DOT:
             w, ns = p0, p1
             if w == 0 or ns == 0 or count * ns * w > len(plan.pool):
@@ -897,7 +1120,7 @@ def validate(plan):
             d = _span(plan, dst, count, "dst", ri)
             x = _span(plan, a, count, "a", ri)
             srcs = np.zeros(0, np.uint32)
-            if kind in (COPY, ADD, SUB, MUL, HINT, RCIDX, INVZ, TABLE, TBLIDX, DIVC):
+            if kind in (COPY, ADD, SUB, MUL, HINT, RCIDX, INVZ, TABLE, TBLIDX, DIVC, GATHER, CLAMP):
                 srcs = x
             else:
                 lim = {CONST: len(plan.consts), INPUT: plan.n_inputs, PARAM: len(plan.params)}[kind]
@@ -913,6 +1136,14 @@ def validate(plan):
                 raise PlanError("witness plan: record %d: zero table column size" % ri)
             if kind == DIVC and p0 == 0:
                 raise PlanError("witness plan: record %d: zero divisor" % ri)
+            if kind == GATHER:                            # every cell of the table is one a lane can read
+                if p1 == 0:
+                    raise PlanError("witness plan: record %d (%s): empty gather table" % (ri, KIND_NAMES[kind]))
+                if p0 > len(plan.pool) or p1 > len(plan.pool) - p0:
+                    raise PlanError("witness plan: record %d (%s): gather table runs past the pool" % (ri, KIND_NAMES[kind]))
+                srcs = np.concatenate([srcs, plan.pool[p0:p0 + p1]])
+            if kind == CLAMP and _i32(p0) > _i32(p1):
+                raise PlanError("witness plan: record %d (%s): bad clamp bounds" % (ri, KIND_NAMES[kind]))
             if kind in (TABLE, TBLIDX) and p0 >= len(plan.tables):
                 raise PlanError("witness plan: record %d (%s): lookup table index out of range" % (ri, KIND_NAMES[kind]))
         if (d >= cells).any() or (srcs >= cells).any():
@@ -937,10 +1168,19 @@ def column_phases(plan):
     """the phase each advice column belongs to: that of the records that write it (`validate` refuses two), 0 for a column no record writes"""
     out = [0] * plan.n_advice
     for kind, count, p0, p1, dst, a, b, phase in plan.records.tolist():
-        n = count * p1 if kind in (DOT, RLC) else count
+        n = count * p1 if kind in (DOT, RLC, SUMACC, PRODACC) else count
         d = plan.pool[dst:dst + n]
         for c in np.unique(d[d != NONE] >> plan.k).tolist():
             out[c] = phase
+    return out
+
+
+def written_columns(plan):
+    """the advice columns some record writes a cell of (every other column is all zeros after its phase has run)"""
+    out = set()
+    for kind, count, p0, p1, dst, a, b, phase in plan.records.tolist():
+        d = plan.pool[dst:dst + (count * p1 if kind in (DOT, RLC, SUMACC, PRODACC) else count)]
+        out.update((d[d != NONE] >> plan.k).tolist())
     return out
 
 
@@ -996,6 +1236,20 @@ def run_plan_host(plan, x, challenges=None, phase=None):
                             acc = (acc + cells[ia] * cells[P[b + (s * w + j) * count + d]]) % R
                     cells[cell] = acc
             continue
+        if kind in (SUMACC, PRODACC):
+            w, ns = p0, p1
+            for d in range(count):
+                acc = 0 if kind == SUMACC else 1
+                for s in range(ns):
+                    cell = P[dst + s * count + d]
+                    if cell == NONE:
+                        continue
+                    for j in range(w):
+                        ia = P[a + (s * w + j) * count + d]
+                        if ia != NONE:
+                            acc = (acc + cells[ia]) % R if kind == SUMACC else acc * cells[ia] % R
+                    cells[cell] = acc
+            continue
         lo = p0 - (1 << 32) if p0 >> 31 else p0
         for i in range(count):
             ia = P[a + i]
@@ -1018,6 +1272,13 @@ def run_plan_host(plan, x, challenges=None, phase=None):
                 if abs(s) >= 1 << 52:
                     raise AssertionError("%s (%s record %d, element %d)" % (DIV_ERROR, KIND_NAMES[kind], ri, i))
                 v = EL.round_div(s, p0) % R
+            elif kind == GATHER:                          # the index is tested before it is used
+                s = EL.signed(cells[ia])
+                if s < 0 or s >= p1 or abs(s) >= 1 << 62:
+                    raise AssertionError("%s (%s record %d, element %d)" % (GATHER_ERROR, KIND_NAMES[kind], ri, i))
+                v = cells[P[p0 + s]]
+            elif kind == CLAMP:                           # beyond 62 bits: by its sign, as the lane does
+                v = min(max(EL.signed(cells[ia]), lo), _i32(p1)) % R
             elif kind == RCIDX:
                 s = EL.signed(cells[ia])
                 if abs(s) >= 1 << 62:                 # what a lane holds in 64 bits; the layout only range-checks signs and digits

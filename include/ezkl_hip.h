@@ -251,7 +251,7 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *      (nonlinearity :5143-5222), which with those ops is the conv2d_mnist example's layout ----
  * A PLAN is the layout recorded once per circuit (ezkl_amd/witness_plan.py; byte layout: csrc/witness_plan.hpp): a list of records, each a
  * batch of cell writes of one kind (copy, const, input, param, add / sub / mult, decompose hint, range-check index, inverse-or-zero, dot,
- * static-lookup output, static-lookup table-column index, integer matmul, random linear combination, rounded division by a constant) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
+ * static-lookup output, static-lookup table-column index, integer matmul, random linear combination, rounded division by a constant, running sum, running product, gather, clamp) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
  * of constants and -- header words 12 / 13 (n_tables, n_table_values; zero, as reserved words were, in a plan without lookups), after the
  * pool -- a directory of {lo (int32), n, col_size, offset} per static lookup table and the tables' values f(lo + i) as int64.  The version
  * word stays 1.  A lookup record names its source cells and a table: with s the signed value of the cell, the output kind writes
@@ -287,7 +287,23 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *   those cells where they are -- and is refused otherwise (EZKL_ERR_INVALID, "phase 1 before phase 0 ...", nothing is launched).  status as
  *   for run, per phase.  ezkl_hip_witness_run_dev on a one-phase plan is run_phase(0); on a plan with phases it returns EZKL_ERR_INVALID and
  *   names this call.
- * phases: out = {n_phases, n_challenges}; column_phase (may be NULL): n_advice bytes, the phase each column belongs to. */
+ * phases: out = {n_phases, n_challenges}; column_phase (may be NULL): n_advice bytes, the phase each column belongs to.
+ * THE SURROGATE'S OPS (kinds 17 - 20, appended; kind 16 stays unassigned and is refused as unknown; the version word stays 1 and every earlier
+ *   blob keeps its bytes).  sum / prod (17 / 18:
+ *   BaseRegion._accumulate, layouts.rs:2472-2621) -- count scans of p1 steps with p0 operands each, step-major as dot is: step s of scan d folds
+ *   the cells a[(s * p0 + j) * count + d], j < p0 (0xffffffff: no operand), into the running value (0 for a sum, 1 for a product) and writes it to
+ *   dst[s * count + d] (0xffffffff: no such step); b is unused.  gather (19) -- element-wise: a = the cell holding the index, p0 = the pool offset
+ *   of the table's cell list, p1 = its length n >= 1; with s the signed value of the index cell the destination gets the value of cell
+ *   pool[p0 + s]; every listed cell must have been written by an earlier record.  s < 0, s >= n or |s| >= 2^62 is reported as a value beyond
+ *   its decomposition is ("gather index outside the table"); the lane tests s before it reads pool[p0 + s].  clamp (20) -- element-wise:
+ *   a = source cell, p0 = lo, p1 = hi (int32, lo <= hi): min(max(s, lo), hi); a value beyond 62 bits clamps by its sign; it never fails.
+ * tile: a plan of a tiled circuit writes rows [0, U) of the block-0 and shared columns; the circuit is those U rows repeated T times down every
+ *   column and copied into the columns of the other blocks.  For every pair, rows [t * U, (t + 1) * U) of column dst get rows [0, U) of column
+ *   src: t = 0 .. T - 1 when dst != src, t = 1 .. T - 1 when dst == src.  Rows >= T * U and columns outside the pair list are left as they are.
+ *   One launch on `stream` (NULL: the library stream), not waited for; HIP events around it: ezkl_hip_last_kernel_ms("witness_tile").  Nothing
+ *   is launched and the call returns EZKL_ERR_INVALID when U = 0 or T = 0, U * T > 2^k, a column index >= n_advice (<= 64), a column appears twice
+ *   as dst, a column that is some pair's src is another pair's dst with dst != src (its rows [0, U) would be written while they are read), or
+ *   two of the columns named share a buffer. */
 typedef struct ezkl_wplan_s* ezkl_wplan_t;
 int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out_plan);
 int ezkl_hip_witness_plan_free(ezkl_wplan_t plan);
@@ -297,6 +313,8 @@ int ezkl_hip_witness_run_dev(ezkl_wplan_t plan, const int64_t* inputs_host, size
 int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int64_t* inputs_host, size_t n_inputs, const void* challenges, size_t n_challenges,
                                    void* const* advice_cols_dev, void* outputs_host, uint64_t status[4], void* stream);
 int ezkl_hip_witness_plan_phases(ezkl_wplan_t plan, uint32_t out[2], uint8_t* column_phase);
+int ezkl_hip_witness_tile_dev(void* const* advice_cols_dev, uint32_t n_advice, uint32_t k, uint32_t unit_rows, uint32_t tiles, const uint32_t* dst_cols,
+                              const uint32_t* src_cols, uint32_t n_pairs, void* stream);
 const char* ezkl_hip_witness_last_error(void);   /* the calling thread's last refusal (upload) or range failure (run); "" after a success */
 /* A commit batch fed as its columns become final: begin; push (one column / several: fused into groups as the one-call batch does) any
  * number of times; finish returns the points in push order and closes the batch (also after an error).  A push returns once the MSMs

@@ -22,7 +22,17 @@ second-phase columns depend on the proof's challenges, so the host pass runs INS
 --rebase D (MLP): every Gemm of the bench MLP wrapped in the RebaseScale division by D (layouts.rs:219-267 `div`, ezkl_layout.BaseRegion.div):
 the circuit ezkl lays out at non-zero scales; its entry is keyed "k<k>_rebase<D>".
 
-Each run merges its entry into profiles/<tag>_synth.json (key "k<k>" for the MLP, "conv_k<k>" for --circuit conv, "einsum_k<k>").  --skip-host leaves the host pass out (k = 20: over a minute of Python);
+--circuit transformer: the bench's TransformerSurrogateCircuit (tools/bench_circuits.py kind="transformer"), the one circuit that is TILED: the host
+path lays one unit out in Python, tiles it with numpy, converts and uploads every column -- phase 0 once, phase 1 inside create_proof for every
+proof --, the device path replays the circuit's two-phase plan and tiles on the device (build(synthesis="device")):
+
+    host_unit_layout_s  one Python pass of the unit (BaseRegion + `layout`): part of what build() does before anything else
+    host_phase0/1_s     build()'s advice(0, []) / advice(1, challenges), uncached -- phase 1 is the Freivalds pass, the tile and the Montgomery
+                        conversion of three columns --, each followed by the upload of its columns (host_phase*_upload_s, included): the yardstick
+    device_phase0/1_*   HIP events of the plan's run and of the tile launch of that phase: first call, minimum and median of --repeat
+    create_proof_*_s    wall time of native.create_proof with the host callable and with the device callable on one key and seed; the bytes are compared
+
+Each run merges its entry into profiles/<tag>_synth.json (key "k<k>" for the MLP, "conv_k<k>" for --circuit conv, "einsum_k<k>", "transformer_k<k>").  --skip-host leaves the host pass out (k = 20: over a minute of Python);
 --plan-dir keeps recorded plans between runs (a plan depends only on the circuit)."""
 import argparse
 import json
@@ -40,7 +50,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--k", type=int, required=True)
-    ap.add_argument("--circuit", choices=("mlp", "conv", "einsum"), default="mlp")
+    ap.add_argument("--circuit", choices=("mlp", "conv", "einsum", "transformer"), default="mlp")
     ap.add_argument("--skip-proof", action="store_true", help="einsum: leave the create_proof pair out")
     ap.add_argument("--tag", default="synth")
     ap.add_argument("--seed", type=int, default=1)
@@ -56,6 +66,8 @@ def main():
     ezkl_amd.init()
     if a.circuit == "einsum":
         return einsum(a)
+    if a.circuit == "transformer":
+        return transformer(a)
     if a.circuit == "conv":
         circuit = EL.ConvMnistCircuit(logrows=a.k, seed=a.seed)
         img = np.random.default_rng(a.seed).integers(0, 16, (28, 28))        # MNIST pixels / 16, as tools/bench_circuits.py kind="conv" draws them
@@ -216,6 +228,95 @@ def einsum(a):
     dst = os.path.join(ROOT, "profiles", "%s_synth.json" % a.tag)
     doc = json.load(open(dst)) if os.path.exists(dst) else {}
     doc["einsum_k%d" % k] = out
+    json.dump(doc, open(dst, "w"), indent=1, sort_keys=True)
+    print(json.dumps(out))
+
+
+def transformer(a):
+    from ezkl_amd import backend as B, ezkl_layout as EL, native as NV
+    k = a.k
+    n = 1 << k
+    small = k < 16                                    # as tools/bench_circuits.py kind="transformer" shapes it
+    make = lambda: EL.TransformerSurrogateCircuit(k, blocks=4, d=4 if small else 64, einsum_len=3 if small else 48, decomp_base=a.base or (16 if small else 16384),
+                                                  lookup_max=(1 << k) // 16 if small else None, seed=a.seed)
+    chal = [c % EL.R for c in EINSUM_CHALLENGES]
+    c = make()
+    t = time.perf_counter()
+    reg = EL.BaseRegion(c.gc, True)
+    c.layout(reg, [EL.Val(v) for v in c.default_inputs()], EL.Val)
+    out = dict(k=k, host_unit_layout_s=round(time.perf_counter() - t, 4))
+    t = time.perf_counter()
+    host = make().build(gpu=B)
+    out["host_build_s"] = round(time.perf_counter() - t, 3)
+    n_adv = host["cs"].n_advice
+    out.update(circuit=host["info"]["circuit"], advice_columns=n_adv, unit_rows=host["info"]["unit_rows"], tiles=host["info"]["tiles"], blocks=host["info"]["blocks"])
+    host_cols = {}
+    for phase in (0, 1):                              # the host callable as create_proof calls it, then the upload create_proof makes of what it returns
+        B.synchronize()
+        t = time.perf_counter()
+        cols = host["advice"](phase, chal if phase else [])
+        t1 = time.perf_counter()
+        up = [B.DeviceBuffer.from_numpy(cols[i]) for i in sorted(cols)]
+        B.synchronize()
+        t2 = time.perf_counter()
+        for u in up:
+            u.free()
+        host_cols.update(cols)
+        out.update({"host_phase%d_s" % phase: round(t2 - t, 4), "host_phase%d_upload_s" % phase: round(t2 - t1, 4), "host_phase%d_columns" % phase: len(cols)})
+    out["host_s"] = round(out["host_phase0_s"] + out["host_phase1_s"], 4)
+    print("k=%d host: unit layout %.3f s, build %.3f s; advice(0) %.3f s (upload %.3f s) + advice(1) %.3f s (upload %.3f s)"
+          % (k, out["host_unit_layout_s"], out["host_build_s"], out["host_phase0_s"], out["host_phase0_upload_s"], out["host_phase1_s"], out["host_phase1_upload_s"]), flush=True)
+    t = time.perf_counter()
+    dev = make().build(gpu=B, synthesis="device")
+    out["device_build_s"] = round(time.perf_counter() - t, 3)
+    w = dev["witness"]
+    out.update(records=w.plan.n_records, cells=w.plan.n_cells, tile_pairs=[len(w.pairs[0]), len(w.pairs[1])])
+    ms = {(p, what): [] for p in (0, 1) for what in ("run", "tile")}
+    for it in range(a.repeat + 1):
+        got = {}
+        for phase in (0, 1):
+            got.update(dev["advice"](phase, chal if phase else []))
+            ms[(phase, "run")].append(w.phase_ms[phase][0])
+            ms[(phase, "tile")].append(w.phase_ms[phase][1])
+        if it == 0:                                   # the run that is timed computes what the host computes
+            for i in range(n_adv):
+                assert got[i].to_numpy(shape=(n, 4)).tobytes() == np.ascontiguousarray(host_cols[i]).tobytes(), "advice column %d differs from the host callable's" % i
+            out["columns_equal_host"] = True
+    for (phase, what), v in ms.items():
+        out.update({"device_phase%d_%s_first_ms" % (phase, what): round(v[0], 4), "device_phase%d_%s_ms_min" % (phase, what): round(min(v[1:]), 4),
+                    "device_phase%d_%s_ms_median" % (phase, what): round(float(np.median(v[1:])), 4)})
+    out.update(repeat=a.repeat, device_ms_median=round(sum(float(np.median(v[1:])) for v in ms.values()), 4), device_ms_min=round(sum(min(v[1:]) for v in ms.values()), 4))
+    print("k=%d device (median of %d): phase 0 run %.3f + tile %.3f ms, phase 1 run %.3f + tile %.3f ms; %d records, unit %d rows x %d tiles x %d blocks"
+          % (k, a.repeat, *[out["device_phase%d_%s_ms_median" % pw] for pw in ((0, "run"), (0, "tile"), (1, "run"), (1, "tile"))], w.plan.n_records,
+             out["unit_rows"], out["tiles"], out["blocks"]), flush=True)
+    if not a.skip_proof:
+        t = time.perf_counter()
+        bg, bgl = B.gen_srs(k, 0x5eed)
+        pk = NV.NativeProvingKey(NV.NativeCircuit(host["cs"]), bg, EL.cols_to_mont(host["fixed"], B), host["copies"])
+        out["keygen_s"] = round(time.perf_counter() - t, 3)
+        prove_dev = lambda: NV.create_proof(pk, bg, bgl, dev["advice"], seed=7, instances=dev["instances"], device_columns=dev["device_columns"])
+        prove_dev()                                   # warm: the sweep kernel, the tables
+        t = time.perf_counter()
+        got = prove_dev()
+        out["create_proof_device_s"] = round(time.perf_counter() - t, 4)
+        out["create_proof_device_witness_ms"] = round(sum(sum(v) for v in w.phase_ms.values()), 4)
+        fresh = make().build(gpu=B)                   # an advice callable with nothing cached: what a proof of new inputs pays
+        t = time.perf_counter()
+        ref = NV.create_proof(pk, bg, bgl, fresh["advice"], seed=7, instances=fresh["instances"])
+        out["create_proof_host_s"] = round(time.perf_counter() - t, 4)
+        t = time.perf_counter()
+        again = NV.create_proof(pk, bg, bgl, fresh["advice"], seed=7, instances=fresh["instances"])
+        out["create_proof_host_cached_s"] = round(time.perf_counter() - t, 4)      # the same challenges again: the callable answers from its cache
+        assert got == ref == again, "the proof from the device callable differs from the host callable's"
+        out["proof_bytes_equal"] = True
+        print("k=%d create_proof: device callable %.4f s, host callable %.4f s (its cache warm: %.4f s), same bytes"
+              % (k, out["create_proof_device_s"], out["create_proof_host_s"], out["create_proof_host_cached_s"]), flush=True)
+        bg.free(); bgl.free()
+    w.free()
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    dst = os.path.join(ROOT, "profiles", "%s_synth.json" % a.tag)
+    doc = json.load(open(dst)) if os.path.exists(dst) else {}
+    doc["transformer_k%d" % k] = out
     json.dump(doc, open(dst, "w"), indent=1, sort_keys=True)
     print(json.dumps(out))
 
