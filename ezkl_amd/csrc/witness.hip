@@ -30,13 +30,20 @@
 //    element-wise, never failing.  ezkl_hip_witness_tile_dev repeats the unit rows [0, U) a plan wrote down its columns and into the
 //    columns of the other blocks, see wit_tile_kernel.
 //
+//  * sort / argsort records (layouts.rs:1158-1275 `_sort_ascending` and the claimed indices of `shuffles`, :1624-1760: the one step of the
+//    layout engine whose cell ORDER depends on the values): segments of n cells sorted by (signed value, position) -- a total order, so a
+//    bitonic network gives the cells of any other correct sort -- see wit_sort_lds_kernel: SORT_TILE keys per workgroup in LDS, whole
+//    segments side by side when they are short; a longer segment goes through the plan's key scratch, one launch per stride at or above
+//    the tile and one LDS launch for the strides below it.  A source beyond 62 bits is reported as the range failures below are ("sort
+//    key beyond 62 bits") and its segment writes none of its cells.
+//
 // A value that does not fit its decomposition (|x| >= base^legs: the layout's "value exceeds the decomposition range") writes nothing
 // wrong silently, and neither does a lookup input outside its table (layouts.rs:5143-5222 `nonlinearity`; the layout's "lookup input
 // outside the table range"), and neither does a dividend of `div` beyond the range in which the integer quotient is the reference's f64
 // one (|s| >= 2^52: "rebase dividend outside the exact-division range"): the lane counts itself in status[0] and keeps the SMALLEST
 // (record, element) in status[1] -- vector atomics in plain C++, as the mock prover's kernels in vecops.hip -- and the host call
 // returns EZKL_ERR_INVALID naming the op.  Nothing traps.
-// The only device memory written is the destination columns, the plan's own scratch (inputs, outputs) and the status words; the plan's
+// The only device memory written is the destination columns, the plan's own scratch (inputs, outputs, sort keys) and the status words; the plan's
 // index pool, parameters, constants and lookup-table values are read-only after upload.
 #include "common.hpp"
 #include "witness_plan.hpp"
@@ -393,6 +400,165 @@ __global__ __launch_bounds__(256) void wit_tile_kernel(WitTile t, uint32_t unit_
     st_fe(dst + i, ld_fe(src + i % unit_rows));
 }
 
+// SORT / ARGSORT.  A key is (signed value, tie) with tie = the element's position in its segment (mode 0) or n - 1 - position (mode 1), compared
+// lexicographically; a segment of n keys is padded with (INT64_MAX, 0xffffffff) to P = the next power of two.  A source beyond 62 bits
+// enters as (INT64_MAX, 0xfffffffe): above every key that fits, below the pads.  So after the sort the key at place n - 1 of a segment is
+// the segment's flag -- value INT64_MAX: some source did not fit, none of the segment's cells is written -- rewritten by every run, in
+// LDS or in the scratch, never status[0], which an earlier record may have set.  The network: stage `size` = 2, 4 .. P, strides size / 2
+// .. 1; the pair (i, i | stride) is put in ascending order when bit `size` of i's place in its segment is clear, in descending order
+// otherwise (the last stage, size = P, is ascending throughout).  Every loop bound is a function of P and SORT_TILE.
+struct alignas(16) SortKey {
+    int64_t v;
+    uint32_t tie, pad;
+};
+constexpr int64_t SORT_PAD = INT64_MAX;
+constexpr uint32_t SORT_THREADS = 256, SORT_TIE_PAD = 0xFFFFFFFFu, SORT_TIE_BAD = 0xFFFFFFFEu;
+static_assert(SORT_TILE % (2 * SORT_THREADS) == 0 && (SORT_TILE & (SORT_TILE - 1)) == 0, "a tile is a power of two of whole rounds of pairs");
+
+// the key of source element e = seg * n + i of record `rec` (live: the element exists), reported when it does not fit
+EZ_D void wit_sort_load(const WitCols& cols, uint32_t k, const uint32_t* __restrict__ a, bool live, size_t e, uint32_t i, uint32_t n, uint32_t mode, uint32_t rec,
+                        unsigned long long* status, int64_t& v, uint32_t& tie) {
+    v = SORT_PAD; tie = SORT_TIE_PAD;
+    bool fail = false;
+    if (live) {
+        bool neg, fits;
+        uint64_t mag;
+        wit_signed(ld_fe(wit_cell(cols, k, a[e])), neg, mag, fits);
+        fail = !fits;
+        v = fail ? SORT_PAD : neg ? -(int64_t)mag : (int64_t)mag;
+        tie = fail ? SORT_TIE_BAD : mode ? n - 1 - i : i;
+    }
+    wit_report(fail, rec, (uint32_t)e, status);
+}
+EZ_D bool wit_sort_above(int64_t xv, uint32_t xt, int64_t yv, uint32_t yt) { return xv > yv || (xv == yv && xt > yt); }
+// strides stride0, stride0 / 2 .. 1 of stage `size` on the SORT_TILE keys in LDS; `base`: the place in its segment of slot 0, P - 1: mask
+EZ_D void wit_sort_lds_strides(int64_t* key, uint32_t* tie, uint32_t base, uint32_t mask, uint32_t size, uint32_t stride0) {
+    for (uint32_t stride = stride0; stride; stride >>= 1) {
+        __syncthreads();
+#pragma unroll
+        for (uint32_t q = 0; q < SORT_TILE / (2 * SORT_THREADS); q++) {
+            const uint32_t t = threadIdx.x + q * SORT_THREADS;
+            const uint32_t i = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), j = i | stride;       // j < SORT_TILE: t < SORT_TILE / 2
+            const bool asc = (((base + i) & mask) & size) == 0;
+            const int64_t xv = key[i], yv = key[j];
+            const uint32_t xt = tie[i], yt = tie[j];
+            if (wit_sort_above(xv, xt, yv, yt) == asc) {
+                key[i] = yv; key[j] = xv;
+                tie[i] = yt; tie[j] = xt;
+            }
+        }
+    }
+    __syncthreads();
+}
+// what destination element (seg, i) gets from the key at its place: the value, or the position the tie stands for
+template <uint32_t KIND>
+EZ_D fe_t wit_sort_out(int64_t v, uint32_t tie, uint32_t n, uint32_t mode) {
+    return KIND == SORT ? wit_from_i64(v) : Fr::from_u64(mode ? n - 1 - tie : tie);
+}
+
+// P <= SORT_TILE: one workgroup sorts SORT_TILE / P whole segments, slot j of the tile = element j % P of segment blockIdx.x * (SORT_TILE / P)
+// + j / P.  Load (wit_signed), the network in LDS up to size P, store.
+template <uint32_t KIND>
+__global__ __launch_bounds__(SORT_THREADS) void wit_sort_lds_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* __restrict__ a,
+                                                                    uint32_t n_segs, uint32_t n, uint32_t P, uint32_t mode, uint32_t rec, unsigned long long* status) {
+    __shared__ int64_t key[SORT_TILE];
+    __shared__ uint32_t tie[SORT_TILE];
+    const uint32_t per = SORT_TILE / P, seg0 = blockIdx.x * per;           // seg0 < n_segs: the grid is cdiv(n_segs, per)
+#pragma unroll
+    for (uint32_t q = 0; q < SORT_TILE / SORT_THREADS; q++) {
+        const uint32_t j = threadIdx.x + q * SORT_THREADS, i = j & (P - 1);
+        const uint32_t seg = seg0 + j / P;
+        const bool live = seg < n_segs && i < n;
+        wit_sort_load(cols, k, a, live, (size_t)seg * n + i, i, n, mode, rec, status, key[j], tie[j]);
+    }
+    for (uint32_t size = 2; size <= P; size <<= 1) wit_sort_lds_strides(key, tie, 0, P - 1, size, size >> 1);
+    __syncthreads();                                                      // (P = 1: no stage has run)
+    uint32_t wrote = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < SORT_TILE / SORT_THREADS; q++) {
+        const uint32_t j = threadIdx.x + q * SORT_THREADS, i = j & (P - 1);
+        const uint32_t seg = seg0 + j / P;
+        if (seg < n_segs && i < n && key[(j & ~(P - 1)) + n - 1] != SORT_PAD) {
+            st_fe(wit_cell(cols, k, dst[(size_t)seg * n + i]), wit_sort_out<KIND>(key[j], tie[j], n, mode));
+            wrote++;
+        }
+    }
+    wit_count(wrote, status);
+}
+
+// P > SORT_TILE.  keys: n_segs * P slots of the plan's scratch, segment-major.  Tile kernel: workgroup b loads slots [b * SORT_TILE, + SORT_TILE)
+// from the cells, sorts them in LDS through stage SORT_TILE -- in alternating directions: bit SORT_TILE of the place -- and writes the scratch.
+__global__ __launch_bounds__(SORT_THREADS) void wit_sort_tile_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ a, SortKey* __restrict__ keys, uint32_t n,
+                                                                     uint32_t P, uint32_t mode, uint32_t rec, unsigned long long* status) {
+    __shared__ int64_t key[SORT_TILE];
+    __shared__ uint32_t tie[SORT_TILE];
+    const size_t slot0 = (size_t)blockIdx.x * SORT_TILE;                  // the grid is n_segs * P / SORT_TILE
+    const uint32_t seg = (uint32_t)(slot0 / P), base = (uint32_t)(slot0 & (P - 1));
+#pragma unroll
+    for (uint32_t q = 0; q < SORT_TILE / SORT_THREADS; q++) {
+        const uint32_t j = threadIdx.x + q * SORT_THREADS, i = base + j;
+        wit_sort_load(cols, k, a, i < n, (size_t)seg * n + i, i, n, mode, rec, status, key[j], tie[j]);
+    }
+    for (uint32_t size = 2; size <= SORT_TILE; size <<= 1) wit_sort_lds_strides(key, tie, base, P - 1, size, size >> 1);
+#pragma unroll
+    for (uint32_t q = 0; q < SORT_TILE / SORT_THREADS; q++) {
+        const uint32_t j = threadIdx.x + q * SORT_THREADS;
+        keys[slot0 + j] = SortKey{key[j], tie[j], 0};
+    }
+}
+// one stride >= SORT_TILE of stage `size`: one lane per pair of the n_segs * P / 2 (`pairs`), both keys in the scratch
+__global__ __launch_bounds__(SORT_THREADS) void wit_sort_global_kernel(SortKey* __restrict__ keys, size_t pairs, uint32_t P, uint32_t size, uint32_t stride) {
+    const size_t t = (size_t)blockIdx.x * SORT_THREADS + threadIdx.x;
+    if (t >= pairs) return;
+    const size_t i = ((t & ~(size_t)(stride - 1)) << 1) | (t & (stride - 1)), j = i | stride;     // j < 2 * pairs
+    const bool asc = (((uint32_t)i & (P - 1)) & size) == 0;
+    const SortKey x = keys[i], y = keys[j];
+    if (wit_sort_above(x.v, x.tie, y.v, y.tie) == asc) {
+        keys[i] = y;
+        keys[j] = x;
+    }
+}
+// the strides below SORT_TILE of stage `size` > SORT_TILE: a tile of the scratch through LDS
+__global__ __launch_bounds__(SORT_THREADS) void wit_sort_merge_kernel(SortKey* __restrict__ keys, uint32_t P, uint32_t size) {
+    __shared__ int64_t key[SORT_TILE];
+    __shared__ uint32_t tie[SORT_TILE];
+    const size_t slot0 = (size_t)blockIdx.x * SORT_TILE;
+#pragma unroll
+    for (uint32_t q = 0; q < SORT_TILE / SORT_THREADS; q++) {
+        const uint32_t j = threadIdx.x + q * SORT_THREADS;
+        const SortKey x = keys[slot0 + j];
+        key[j] = x.v; tie[j] = x.tie;
+    }
+    wit_sort_lds_strides(key, tie, (uint32_t)(slot0 & (P - 1)), P - 1, size, SORT_TILE >> 1);
+#pragma unroll
+    for (uint32_t q = 0; q < SORT_TILE / SORT_THREADS; q++) {
+        const uint32_t j = threadIdx.x + q * SORT_THREADS;
+        keys[slot0 + j] = SortKey{key[j], tie[j], 0};
+    }
+}
+// the sorted scratch -> the cells: one lane per destination element
+template <uint32_t KIND>
+__global__ __launch_bounds__(SORT_THREADS) void wit_sort_store_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const SortKey* __restrict__ keys,
+                                                                      uint32_t count, uint32_t n, uint32_t P, uint32_t mode, unsigned long long* status) {
+    const uint32_t e = blockIdx.x * SORT_THREADS + threadIdx.x;            // count <= 2^28
+    uint32_t wrote = 0;
+    if (e < count) {
+        const uint32_t seg = e / n, i = e - seg * n;
+        const SortKey* s = keys + (size_t)seg * P;
+        if (s[n - 1].v != SORT_PAD) {
+            const SortKey x = s[i];
+            st_fe(wit_cell(cols, k, dst[e]), wit_sort_out<KIND>(x.v, x.tie, n, mode));
+            wrote = 1;
+        }
+    }
+    wit_count(wrote, status);
+}
+EZ_HD uint32_t wit_sort_padded(uint32_t n) {                              // the next power of two: n <= 2^28
+    uint32_t P = 1;
+    while (P < n) P <<= 1;
+    return P;
+}
+
 struct DevPlan {
     Plan host;                      // the validated blob: records, outputs and counts drive the launches; pool / params / consts are
                                     // released once they are on the device (n_params is kept for ezkl_hip_witness_plan_info)
@@ -406,6 +572,7 @@ struct DevPlan {
     int64_t* inputs = nullptr;
     fe_t* outs = nullptr;
     unsigned long long* status = nullptr;
+    SortKey* sort_keys = nullptr;   // the padded keys of the largest sort record with segments above SORT_TILE (one slot when there is none)
     Ctx* ctx = nullptr;
     // a plan with phases: the last phase that ran to its end since the last phase 0 with no earlier phase started again since, and the
     // columns it ran on
@@ -415,7 +582,7 @@ struct DevPlan {
 thread_local std::string t_wit_error;
 
 void plan_release(DevPlan* p) {
-    for (void* q : {(void*)p->pool, (void*)p->outputs, (void*)p->params, (void*)p->consts, (void*)p->table_values, (void*)p->inputs, (void*)p->outs, (void*)p->status})
+    for (void* q : {(void*)p->pool, (void*)p->outputs, (void*)p->params, (void*)p->consts, (void*)p->table_values, (void*)p->inputs, (void*)p->outs, (void*)p->status, (void*)p->sort_keys})
         if (q) (void)ezkl_hip_free(q);
     delete p;
 }
@@ -431,6 +598,30 @@ void launch_elem(hipStream_t st, const WitCols& cols, uint32_t k, const DevPlan*
     const uint32_t* b = p->pool + (KIND == GATHER ? r.p0 : r.b);     // GATHER: the table's cell list, inside the pool: checked on upload
     hipLaunchKernelGGL(wit_elem_kernel<KIND>, dim3(cdiv(r.count, 256)), dim3(256), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, b, r.count, p0, p1, p2,
                        ints, (const fe_t*)p->consts, ri, p->status);
+}
+// a SORT / ARGSORT record: one launch when a padded segment fits a tile, else tile sort, per stage the strides at or above the tile one launch
+// each and one for those below it, store.  -> the number of launches
+template <uint32_t KIND>
+uint32_t launch_sort(hipStream_t st, const WitCols& cols, uint32_t k, const DevPlan* p, const Rec& r, uint32_t ri) {
+    const uint32_t n = r.p0, n_segs = r.count / n, P = wit_sort_padded(n);
+    if (P <= SORT_TILE) {
+        hipLaunchKernelGGL(wit_sort_lds_kernel<KIND>, dim3(cdiv(n_segs, SORT_TILE / P)), dim3(SORT_THREADS), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, n_segs, n, P, r.p1, ri,
+                           p->status);
+        return 1;
+    }
+    const size_t slots = (size_t)n_segs * P;                             // <= 2^29: count <= 2^28 and P < 2 n
+    const uint32_t tiles = (uint32_t)(slots / SORT_TILE);
+    uint32_t launches = 2;
+    hipLaunchKernelGGL(wit_sort_tile_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, cols, k, p->pool + r.a, p->sort_keys, n, P, r.p1, ri, p->status);
+    for (uint32_t size = 2 * SORT_TILE; size <= P; size <<= 1) {
+        for (uint32_t stride = size >> 1; stride >= SORT_TILE; stride >>= 1, launches++)
+            hipLaunchKernelGGL(wit_sort_global_kernel, dim3((uint32_t)cdiv(slots / 2, SORT_THREADS)), dim3(SORT_THREADS), 0, st, p->sort_keys, slots / 2, P, size, stride);
+        hipLaunchKernelGGL(wit_sort_merge_kernel, dim3(tiles), dim3(SORT_THREADS), 0, st, p->sort_keys, P, size);
+        launches++;
+    }
+    hipLaunchKernelGGL(wit_sort_store_kernel<KIND>, dim3(cdiv(r.count, SORT_THREADS)), dim3(SORT_THREADS), 0, st, cols, k, p->pool + r.dst, (const SortKey*)p->sort_keys, r.count, n, P,
+                       r.p1, p->status);
+    return launches;
 }
 }  // namespace
 }  // namespace ezkl
@@ -461,11 +652,16 @@ int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out
         memcpy(v.v, h.consts.data() + 32 * i, 32);
         consts[i] = Fr::to_mont(v);
     }
+    size_t sort_bytes = 0;                                        // segments * P * 16 B of the largest sort that leaves LDS
+    for (const Rec& r : h.recs)
+        if ((r.kind == SORT || r.kind == ARGSORT) && wit_sort_padded(r.p0) > SORT_TILE)
+            sort_bytes = std::max(sort_bytes, (size_t)(r.count / r.p0) * wit_sort_padded(r.p0) * sizeof(SortKey));
     struct Up { void** dev; const void* src; size_t bytes; };
     const Up ups[] = {{(void**)&p->pool, h.pool.data(), h.pool.size() * 4},       {(void**)&p->outputs, h.outputs.data(), h.outputs.size() * 4},
                       {(void**)&p->params, h.params.data(), h.params.size() * 8}, {(void**)&p->consts, consts.data(), consts.size() * 32},
                       {(void**)&p->inputs, nullptr, (size_t)h.n_inputs * 8},      {(void**)&p->outs, nullptr, h.outputs.size() * 32},
-                      {(void**)&p->status, nullptr, 32},                          {(void**)&p->table_values, h.table_values.data(), h.table_values.size() * 8}};
+                      {(void**)&p->status, nullptr, 32},                          {(void**)&p->table_values, h.table_values.data(), h.table_values.size() * 8},
+                      {(void**)&p->sort_keys, nullptr, sort_bytes}};
     int rc = EZKL_OK;
     for (const Up& u : ups) {
         if ((rc = ezkl_hip_malloc(u.dev, u.bytes ? u.bytes : 1))) break;
@@ -594,6 +790,8 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
             hipLaunchKernelGGL(wit_acc_kernel<PRODACC>, dim3(cdiv((size_t)r.count * DOT_LANES, 64)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, r.count, r.p0, r.p1,
                                p->status);
             break;
+        case SORT: launches += launch_sort<SORT>(st, cols, k, p, r, (uint32_t)ri) - 1; break;
+        case ARGSORT: launches += launch_sort<ARGSORT>(st, cols, k, p, r, (uint32_t)ri) - 1; break;
         case MATMUL: {
             const uint32_t m = r.count / r.p1;
             hipLaunchKernelGGL(wit_matmul_kernel, dim3(cdiv(m, MM_TILE) * cdiv(r.p1, MM_TILE)), dim3(MM_TILE * MM_TILE), 0, st, cols, k, p->pool + r.dst, p->pool + r.a,
@@ -633,6 +831,7 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
                            : kind == MATMUL               ? "witness: einsum operand outside the exact-product range ("
                            : kind == DIVC                 ? "witness: rebase dividend outside the exact-division range ("
                            : kind == GATHER               ? "witness: gather index outside the table ("
+                           : kind == SORT || kind == ARGSORT ? "witness: sort key beyond 62 bits ("
                                                           : "witness: value exceeds the decomposition range (";
         t_wit_error = std::string(what) + (kind < N_KINDS ? KIND_NAMES[kind] : "?") + " record " + std::to_string(ri) +
                       ", element " + std::to_string(el) + "; " + std::to_string(dev_status[0]) + (kind == MATMUL ? " operand reads in all)" : " cells in all)");

@@ -34,6 +34,13 @@
 // is a run-time failure of the lane ("gather index outside the table"), tested before pool[p0 + s] is read.
 // A CLAMP record: a = source cell, p0 = lo, p1 = hi (int32, lo <= hi, else "bad clamp bounds"): min(max(s, lo), hi); a value beyond 62 bits
 // clamps by its sign.  It never fails.
+// A SORT (21) / ARGSORT (22) record (layouts.rs:1158-1275 `_sort_ascending`, the witness of its sorted tensor and of the claimed indices of
+// `shuffles`): count destination cells dst[e] in segments of p0 = n elements (n >= 1, count % n == 0, count <= 2^28, else "bad sort shape"),
+// p1 = mode (0 or 1, else "bad sort shape"), a = the source cells, segment-major and dense, b unused and zero.  The order of a segment is
+// by (signed value, position), the position ascending among equal values for mode 0 and descending for mode 1: a total order.  SORT:
+// dst[s * n + i] gets the i-th smallest signed value of the cells a[s * n .. + n) as integer_rep_to_felt maps it; ARGSORT: the position, in
+// [0, n), of that element in its segment.  A source with |s| >= 2^62 is a run-time failure of the lane ("sort key beyond 62 bits"), element
+// = its place in a; its segment writes none of its cells.  SORT_TILE is the number of keys one workgroup of csrc/witness.hip sorts in LDS.
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -44,10 +51,11 @@
 namespace ezkl {
 namespace wplan {
 
-constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64, MAX_PHASES = 3, MAX_CHALLENGES = 64;
-enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC, UNASSIGNED, SUMACC, PRODACC, GATHER, CLAMP, N_KINDS };     // 16 names nothing: refused as unknown
+constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64, MAX_PHASES = 3, MAX_CHALLENGES = 64, SORT_TILE = 2048,
+                   MAX_SORT_COUNT = 1u << 28;
+enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC, UNASSIGNED, SUMACC, PRODACC, GATHER, CLAMP, SORT, ARGSORT, N_KINDS };     // 16 names nothing: refused as unknown
 static const char* const KIND_NAMES[N_KINDS] = {"copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot",
-                                                "nonlinearity", "nonlinearity_index", "matmul", "rlc", "div", "?", "sum", "prod", "gather", "clamp"};
+                                                "nonlinearity", "nonlinearity_index", "matmul", "rlc", "div", "?", "sum", "prod", "gather", "clamp", "sort", "argsort"};
 struct Rec {
     uint32_t kind, count, p0, p1, dst, a, b, phase;
 };
@@ -202,6 +210,10 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
             break;
         }
         case CLAMP: a_cells = true; if ((int32_t)r.p0 > (int32_t)r.p1) return at_rec(ri, r.kind, "bad clamp bounds"); break;
+        case SORT: case ARGSORT:                         // p0 = segment length, p1 = mode, count = segments * p0
+            if (r.p0 == 0 || r.count % r.p0 != 0 || r.p1 > 1 || r.count > MAX_SORT_COUNT) return at_rec(ri, r.kind, "bad sort shape");
+            a_cells = true;
+            break;
         case DOT:
             if (r.p0 == 0 || r.p1 == 0 || (uint64_t)r.count * r.p1 > P.size() || (uint64_t)r.count * r.p1 * r.p0 > P.size()) return at_rec(ri, r.kind, "bad dot shape");
             n_dst = (uint64_t)r.count * r.p1; n_a = n_b = n_dst * r.p0; a_cells = b_cells = true;

@@ -31,6 +31,8 @@ def signed(v):
 
 DIV_ERROR = "rebase dividend outside the exact-division range"
 GATHER_ERROR = "gather index outside the table"
+SORT_ERROR = "sort key beyond 62 bits"
+SORT_MODES = ("unsorted", "smallest_index_first", "largest_index_first")       # layouts.rs:1124-1131 SortCollisionMode
 
 
 def clamped(s, lo, hi):
@@ -365,6 +367,7 @@ class BaseRegion(Region):
         self.first_const = {}                          # value -> first advice cell holding it
         self.const_order = []                          # (value, advice cell) in order of first use: the floor planner's fixed cells
         self.decomp = None                             # RegionCtx's (base, legs), region.rs `base()` / `legs()`: set by the circuit's layout
+        self.shuffle_index = 0                         # region.shuffle_index(): the constant that keeps the sorts of a region apart in the argument
 
     def cell_of(self, var, linear):
         x, y, z = var.cartesian_coord(linear)
@@ -584,6 +587,35 @@ class BaseRegion(Region):
         """layouts.rs:3236-3243"""
         return self.greater(b, a)
 
+    def greater_equal(self, a, b):
+        """layouts.rs:3161-3172: a + 1 > b"""
+        return self.greater(self.pairwise(a, [Val(1, const=True)] * len(a), EC.ADD), b)
+
+    def less_equal(self, a, b):
+        """layouts.rs:3277-3284"""
+        return self.greater_equal(b, a)
+
+    def boolean_identity(self, vals):
+        """layouts.rs:4885-4904 with assign = true: the values on the output VarTensor, and a (0, 1) range check of them"""
+        out = self.assign(self.output, vals)
+        self.increment(len(out))
+        self.range_check(vals, (0, 1))
+        return out
+
+    def iff(self, mask, a, b):
+        """layouts.rs:3818-3841: mask * a + (1 - mask) * b with the mask held to a boolean"""
+        mask = self.boolean_identity(mask)
+        rest = self.pairwise([Val(1, const=True)] * len(mask), mask, EC.SUB)
+        return self.pairwise(self.pairwise(a, mask, EC.MULT), self.pairwise(b, rest, EC.MULT), EC.ADD)
+
+    def and_(self, a, b):
+        """layouts.rs:3345-3357 `and` (a keyword here): the product of two booleans"""
+        return self.pairwise(self.boolean_identity(a), self.boolean_identity(b), EC.MULT)
+
+    def or_(self, a, b):
+        """layouts.rs:3414-3431 `or`: iff(a, a, b)"""
+        return self.iff(a, a, self.boolean_identity(b))
+
     def l1_distance(self, a, b):
         """layouts.rs:58-67"""
         return self.abs(self.pairwise(a, b, EC.SUB))
@@ -622,13 +654,18 @@ class BaseRegion(Region):
         self.increment(len(w))
         return out
 
-    def _lookup_any(self, table_sel, input_sels, table_rows, picks):
+    def _lookup_any(self, table_sel, input_sels, table_rows, picks, constrained=False):
         """the two sides of a lookup_any argument of BaseConfig::_configure_any (chip.rs:619-833): `table_rows` (3-tuples) go to the three
         single-column table VarTensors at the dynamic coordinate with the table selector on; `picks` go to (input 0, input 1, output) at
-        the linear coordinate -- one tuple per cell position -- with that position's input selector on"""
+        the linear coordinate -- one tuple per cell position -- with that position's input selector on.  constrained: a Val that has a
+        cell is copied from it and a constant is a constant (what `region.assign` does: a sort proves nothing about cells the argument
+        does not read); otherwise the value alone is placed.  -> the table side as placed, row by row"""
         tabs = self.gc.advices[3:6]
         dyn = getattr(self, "dyn", 0)
-        free = lambda x: Val(x.v) if isinstance(x, Val) else Val(int(x))     # the value alone: neither side of the argument is copy-constrained
+        if constrained:
+            free = lambda x: x if isinstance(x, Val) else Val(int(x), const=True)
+        else:
+            free = lambda x: Val(x.v) if isinstance(x, Val) else Val(int(x))     # the value alone: neither side of the argument is copy-constrained
         placed = []
         for r, tri in enumerate(table_rows):
             assert all(dyn + r < tabs[t].col_size for t in range(3)), "dynamic table column overflow"
@@ -643,6 +680,7 @@ class BaseRegion(Region):
                 self.put(vars3[t], self.linear + j, free(tri[t]))
             self.enable(input_sels[(0, (x, y))], z)
         self.increment(len(picks))
+        return placed
 
     def row_at(self, table_rows, index):
         """row `index` (a Val) of `table_rows`, as a pick of a dynamic lookup over that table whose keys are its positions 0 .. n - 1: a
@@ -659,6 +697,53 @@ class BaseRegion(Region):
     def shuffle(self, rows, order):
         """layouts.rs `shuffles`: the inputs are the rows of the reference side in another order (sort / transpose)"""
         self._lookup_any(self.base.shuffle_output_selectors[0], self.base.shuffle_input_selectors, rows, [rows[i] for i in order])
+
+    def _sorted(self, vals, mode):
+        """the one data-dependent step of a sort: -> (the values in ascending order, the position each came from).  The order is by (signed
+        value, position), the position ascending -- descending for `largest_index_first` -- among equal values: what the claimed-index
+        search of `shuffles` (layouts.rs:1662-1704: the first unused position in input order, reversed for the third mode) yields, the
+        only witness the indexed modes accept, and a total order.  (A recording region overrides this, as it overrides `row_at`.)"""
+        s = [signed(v.v) for v in vals]
+        for x in s:
+            assert abs(x) < 1 << 62, SORT_ERROR
+        order = sorted(range(len(s)), key=lambda j: (s[j], -j if mode == "largest_index_first" else j))
+        return [s[j] % R for j in order], order
+
+    def sort_ascending(self, vals, mode="unsorted"):
+        """layouts.rs:1158-1275 `_sort_ascending` -> (sorted, indices): the sorted values on the first input VarTensor, the permutation
+        argument of `shuffles` (:1624-1760) -- table side (sorted_i, the region's shuffle index, the claimed source index_i), input side
+        (input_j, the same constant, j) -- and the ordering constraints of the collision mode over consecutive pairs"""
+        assert mode in SORT_MODES, mode
+        vals = list(vals)
+        if len(vals) == 1:                             # :1167-1169
+            return vals, [Val(0, const=True)]
+        values, positions = self._sorted(vals, mode)
+        srt = self.assign(self.inputs[0], [Val(v) for v in values])
+        self.increment(len(srt))
+        index = Val(self.shuffle_index, const=True)
+        placed = self._lookup_any(self.base.shuffle_output_selectors[0], self.base.shuffle_input_selectors,
+                                  [(srt[i], index, Val(positions[i])) for i in range(len(srt))],
+                                  [(v, index, Val(j, const=True)) for j, v in enumerate(vals)], constrained=True)
+        self.shuffle_index += 1
+        idx = [row[2] for row in placed]               # the claimed indices, where the argument reads them
+        a, b, ia, ib = srt[:-1], srt[1:], idx[:-1], idx[1:]
+        if mode == "unsorted":
+            ordered = self.greater_equal(b, a)
+        else:                                          # strictly ascending, or equal with the source indices in the mode's order
+            greater, equal = self.greater(b, a), self.equals(b, a)
+            by_index = self.greater(ib, ia) if mode == "smallest_index_first" else self.less(ib, ia)
+            ordered = self.or_(greater, self.and_(equal, by_index))
+        self.enforce_equality([Val(1, const=True)] * len(ordered), ordered)
+        return srt, idx
+
+    def topk(self, vals, k, largest=True):
+        """layouts.rs:1298-1315 `_select_topk`: an `unsorted` sort, reversed for the largest, its first k"""
+        srt, _ = self.sort_ascending(vals, "unsorted")
+        return (srt[::-1] if largest else srt)[:k]
+
+    def topk_axes(self, rows, k, largest=True):
+        """layouts.rs:1343-1361 `topk_axes` over a list of equal-length rows (the slices along the axis)"""
+        return [self.topk(row, k, largest) for row in rows]
 
     def einsum(self, ein, A, B, challenges=None):
         """assign_einsum of an EinsumMatmulCircuit laid over this region's configuration (EinsumMatmulCircuit.over), in this region, at
@@ -695,7 +780,10 @@ class LayoutCircuit:
         reg = self.synthesize(x, witness=with_witness)
         n = 1 << self.k
         cs0 = self.gc.cs
-        sel_cols = cs0.compress_selectors(reg.selector_rows(dense=False))
+        rows = reg.selector_rows(dense=False)
+        if all(a is None for a in rows):               # no selector is ever on (a sort of one element): the columns still have n rows
+            rows = reg.selector_rows()
+        sel_cols = cs0.compress_selectors(rows)
         if n <= 1 << 12:
             sel_cols = [c.tolist() for c in sel_cols]
         cs = cs0.to_plonk(self.k)
@@ -942,6 +1030,45 @@ class SumProdLayoutCircuit(SumProdCircuit):
 
     def plan_identity(self):
         return np.asarray([self.k, self.w, self.n_inputs, self.gc.advices[0].num_blocks()], np.int64).tobytes()
+
+    def synthesize(self, x, witness=True):
+        assert len(x) == self.n_inputs
+        reg = BaseRegion(self.gc, witness)
+        outs = self.layout(reg, [Val(int(v) % R) for v in x], Val)
+        reg.finish(self.gc.const_cols)
+        self.outputs = [v.v for v in outs]
+        return reg
+
+
+class SortTopkCircuit(LayoutCircuit):
+    """a top-k and a full sort of one private vector (layouts.rs `topk_axes` / `_sort_ascending`): instance = the k_top largest (or
+    smallest) values, then the whole vector in ascending order under `mode`.  The op sequence is stated once (`layout`), so that
+    witness_plan.record_plan can run it on symbols.  The settings carry the range checks of the decomposition, (-1, 1) and (0, base - 1),
+    the (0, 1) check of `and` / `or` in the indexed modes, and the shuffle argument."""
+
+    def __init__(self, logrows, num_inner_cols, capacity, length, k_top, largest=True, mode="unsorted", decomp_base=16, decomp_legs=2):
+        assert mode in SORT_MODES and 1 <= k_top <= length
+        self.k, self.w, self.n_inputs = logrows, num_inner_cols, int(length)
+        self.k_top, self.largest, self.mode, self.base, self.legs = int(k_top), bool(largest), mode, decomp_base, decomp_legs
+        checks = [(-1, 1), (0, decomp_base - 1)] + ([(0, 1)] if mode != "unsorted" else [])
+        self.settings = EC.GraphSettings(logrows, num_inner_cols, capacity, total_const_size=4, required_range_checks=checks,
+                                         model_instance_shapes=[[1, self.k_top + self.n_inputs]], total_shuffle_col_size=2 * self.n_inputs,
+                                         num_shuffles=1)
+        self.gc = EC.GraphConfig(self.settings)
+
+    def layout(self, reg, inputs, param):
+        reg.decomp = (self.base, self.legs)
+        vals = reg.assign(reg.inputs[0], inputs)
+        reg.increment(len(vals))
+        top = reg.topk(vals, self.k_top, self.largest)
+        srt, _ = reg.sort_ascending(vals, self.mode)
+        outs = top + srt
+        reg.constrain_instance(outs, self.gc.instance)
+        return outs
+
+    def plan_identity(self):
+        shape = [self.k, self.w, self.n_inputs, self.k_top, int(self.largest), SORT_MODES.index(self.mode), self.base, self.legs, self.gc.advices[0].num_blocks()]
+        return np.asarray(shape, np.int64).tobytes()
 
     def synthesize(self, x, witness=True):
         assert len(x) == self.n_inputs

@@ -1,4 +1,4 @@
-"""Witness plans: the layout of an MlpCircuit, a ConvMnistCircuit, an EinsumMatmulCircuit, a SumProdLayoutCircuit or the
+"""Witness plans: the layout of an MlpCircuit, a ConvMnistCircuit, an EinsumMatmulCircuit, a SumProdLayoutCircuit, a SortTopkCircuit or the
 TransformerSurrogateCircuit's unit recorded ONCE, replayed for every proof.
 
 Which advice cell holds which value depends only on the circuit (BaseRegion places cells from the linear coordinate, the duplicated rows
@@ -19,7 +19,9 @@ ReLU part at k = 17; by levels it is 25.  The MLP path keeps the latest-fit rule
 The LookupRecordingRegion also records the rest of the layout engine's ops: `sum` / `prod` (one SUMACC / PRODACC scan each), `dynamic_lookup`
 and `shuffle` (both sides of the argument are placed through `put`: parameter, constant, input or copy records; a pick whose row is chosen
 by a VALUE -- `BaseRegion.row_at`, the embedding gather -- is the index itself in the key coordinate and a GATHER element over the cells of
-the dynamic table in every other one; a shuffle in a data-dependent order is refused by name) and `ezkl_layout.clamped` (a CLAMP record).
+the dynamic table in every other one; `shuffle` in a data-dependent order is refused by name), `ezkl_layout.clamped` (a CLAMP record) and
+`sort_ascending` / `topk` (`BaseRegion._sorted`, the one data-dependent step, is a SORT segment for the sorted values and an ARGSORT segment
+for the claimed indices; everything around it is records of the other kinds).
 The MLP recorder keeps refusing them by name.  The TransformerSurrogateCircuit lays its einsum over its own configuration
 (`BaseRegion.einsum`): it is recorded on a PhasedLookupRecordingRegion -- the lookup region with the einsum region's `put_cell`, matmul
 record, running values and phase bookkeeping -- into a TWO-phase plan of the unit's rows; the tiling is the device's
@@ -67,6 +69,14 @@ A record of an element-wise kind has `count` destination cells pool[dst + i], pr
            both: s < lo, s > lo + n - 1 or |s| >= 2^62 is the lookup-range failure ("lookup input outside the table range"), reported like the
            decomposition-range failure
 
+    SORT / ARGSORT (21 / 22)   count destination cells pool[dst + e] in segments of p0 = n elements (n >= 1, count % n == 0, count <= 2^28), p1 =
+           mode (0: position ascending among equal values, 1: descending), a = the source cells, segment-major and dense, b = 0.  The order of
+           a segment is by (signed value, position) -- a total order.  SORT: destination s * n + i gets the i-th smallest signed value of the
+           cells pool[a + s * n .. + n) as integer_rep_to_felt maps it; ARGSORT: the position, in [0, n), of that element in its segment
+           (BaseRegion.sort_ascending, layouts.rs:1158-1275 with the claimed indices of `shuffles`, :1624-1760).  A source with |s| >= 2^62 is
+           the run-time failure "sort key beyond 62 bits", reported like the decomposition-range failure with element = its place in a; on
+           the device its segment writes none of its cells
+
 PHASES.  A circuit with second-phase advice (the Freivalds einsum) has columns that depend on challenges squeezed after the first-phase
 commitments: its plan has n_phases = 2, and every record carries the phase whose run replays it.  Phases are non-decreasing along the
 record list; a column belongs to the phase of the records that write it (never to two; a column no record writes: phase 0); INPUT and
@@ -90,6 +100,7 @@ equality tests of tests/test_witness_plan_cpu.py fail loudly -- an assert or a P
     sum (_accumulate)         `(acc + sum(chunk)) % R` with acc and sum() starting from the integer 0, chunk = the w cells of the row
     prod (_accumulate)        `acc = acc * v % R` over the w cells of the row, acc starting from the integer 1
     clamped (module level)    `s.clamped(lo, hi)` when the signed value is a symbol, `min(max(s, lo), hi)` otherwise
+    _sorted                   overridden: `assert abs(s) < 1 << 62` is the run-time check of SORT / ARGSORT
     row_at                    overridden: `assert 0 <= signed(index.v) < len(table_rows)` is the run-time check of GATHER
     equals_zero               `pow(v, -1, R) if v else 0`   (the truth value of a cell symbol is True: INVZ covers both branches)
     div (round_div)           `mag = abs(s)`, `assert mag < 1 << 52` (recorded as the run-time check), `((s > 0) - (s < 0)) * ((mag + d // 2) // d)`
@@ -113,19 +124,28 @@ NONE = 0xFFFFFFFF
 COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC = range(16)
 UNASSIGNED = 16                                    # the kind after DIVC names nothing and never will: both validators refuse it as unknown
 SUMACC, PRODACC, GATHER, CLAMP = range(17, 21)
+SORT, ARGSORT = 21, 22
 KIND_NAMES = ["copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot", "nonlinearity", "nonlinearity_index", "matmul", "rlc",
               "div", "?", "sum", "prod", "gather", "clamp"]
+_LATER_KIND_NAMES = {SORT: "sort", ARGSORT: "argsort"}          # KIND_NAMES is the list of the kinds up to CLAMP, as tests pin it: later kinds are named here
+SORT_TILE, MAX_SORT_COUNT = 2048, 1 << 28                       # csrc/witness_plan.hpp: the keys one workgroup sorts in LDS; the most cells of a sort record
 _HEADER = struct.Struct("<20I32s")
 RANGE_ERROR = "value exceeds the decomposition range"
 LOOKUP_ERROR = "lookup input outside the table range"
 OPERAND_ERROR = "einsum operand outside the exact-product range"
 DIV_ERROR = EL.DIV_ERROR
 GATHER_ERROR = "gather index outside the table"
+SORT_ERROR = EL.SORT_ERROR
 MAX_PHASES, MAX_CHALLENGES = 3, 64
 
 
 class PlanError(ValueError):
     pass
+
+
+def kind_name(kind):
+    """the name a message gives a record kind: KIND_NAMES up to CLAMP, "sort" / "argsort" after it, "?" for anything else"""
+    return KIND_NAMES[kind] if 0 <= kind < len(KIND_NAMES) else _LATER_KIND_NAMES.get(kind, "?")
 
 
 # ---- symbolic values: what a Val's .v holds during the recording pass -------------------------------------------------------------------
@@ -267,6 +287,26 @@ class _Gathered(_Sym):
     """coordinate t of the table row the pick's key names"""
 
     def __init__(self, pick, t): self.pick, self.t = pick, t
+
+
+class _Segment:
+    """one sort (`BaseRegion._sorted`): its source cells, its mode, and the cells its sorted values / their positions were placed in"""
+
+    def __init__(self, src, mode):
+        self.src, self.mode = src, mode
+        self.dst = {SORT: [None] * len(src), ARGSORT: [None] * len(src)}
+
+
+class _Sorted(_Sym):
+    """the i-th smallest value of a segment"""
+    kind = SORT
+
+    def __init__(self, seg, i): self.seg, self.i = seg, i
+
+
+class _SortedIndex(_Sorted):
+    """the position in its segment of the i-th smallest value"""
+    kind = ARGSORT
 
 
 class _Cmp(_Sym):
@@ -419,6 +459,16 @@ class _Records:
         for dst, _ in steps:
             self._claim(dst, ri)
 
+    def emit_sort(self, kind, mode, src, dst, phase=0):
+        """one segment of a SORT / ARGSORT record: destination i gets the i-th smallest of the cells src (its value / its position)"""
+        for s in src:
+            if s not in self.rec_of:
+                raise PlanError("advice cell %d is read before it is written" % s)
+        ri = self._slot((kind, len(src), mode), src, phase)
+        self.recs[ri]["scans"].append((list(src), list(dst)))
+        for d in dst:
+            self._claim(d, ri)
+
     def emit_scan(self, challenge, src, dst, phase):
         """one RLC scan: step t reads cell src[t] and writes cell dst[t]"""
         for s in src:
@@ -549,6 +599,7 @@ class RecordingRegion(EL.BaseRegion):
         return op
     nonlinearity, sum, prod, _accumulate = _refused("nonlinearity"), _refused("sum"), _refused("prod"), _refused("sum / prod")
     dynamic_lookup, shuffle, _lookup_any = _refused("dynamic_lookup"), _refused("shuffle"), _refused("lookup_any")
+    sort_ascending, topk, _sorted = _refused("sort_ascending"), _refused("topk"), _refused("sort_ascending")
     del _counted, _refused
 
 
@@ -641,6 +692,21 @@ class LookupRecordingRegion(RecordingRegion):
             raise PlanError("witness plans do not cover `shuffle` with a data-dependent order (sort, top-k): the order must be integers")
         return EL.BaseRegion.shuffle(self, rows, order)
 
+    # ---- sort / top-k: BaseRegion's ops around `_sorted` ----------------------------------------------------------------------------------------
+    def sort_ascending(self, vals, mode="unsorted"):
+        self.n_ops += 1
+        return EL.BaseRegion.sort_ascending(self, vals, mode)
+
+    topk = EL.BaseRegion.topk
+
+    def _sorted(self, vals, mode):
+        """BaseRegion._sorted on symbols: one segment over the cells the values are assigned in; its sorted values and their positions are
+        collected as the layout places them and emitted, each list as one segment, once it is whole"""
+        if not all(isinstance(v.v, _Cell) for v in vals):
+            raise PlanError("a sort over values that are not assigned cells")
+        seg = _Segment([v.v.idx for v in vals], int(mode == "largest_index_first"))
+        return [_Sorted(seg, i) for i in range(len(vals))], [_SortedIndex(seg, i) for i in range(len(vals))]
+
     def row_at(self, table_rows, index):
         """BaseRegion.row_at on symbols: the key coordinate is the index value itself, every other coordinate a GATHER element over the
         cells of the dynamic table the pick is looked up in -- which must be this very list, with the positions 0 .. n - 1 as its keys"""
@@ -668,6 +734,13 @@ class LookupRecordingRegion(RecordingRegion):
                 raise PlanError("a running value outside the sum / prod it belongs to")
             v.cell = dst
             self._scan.append((dst, v.cells, v.kind))
+        elif isinstance(v, _Sorted):
+            placed = v.seg.dst[v.kind]
+            if placed[v.i] is not None:
+                raise PlanError("a sorted value is placed twice")
+            placed[v.i] = dst
+            if None not in placed:
+                self.out.emit_sort(v.kind, v.seg.mode, v.seg.src, placed)
         elif isinstance(v, _Clamp):
             if not -(1 << 31) <= v.lo <= v.hi < 1 << 31:
                 raise PlanError("clamp bounds beyond 32 bits")
@@ -928,6 +1001,10 @@ class WitnessPlan:
                         a[s, :len(cells), d] = cells
                     n_cells += len(steps)
                 records.append([rec["kind"], nd, w, ns, push(dst), push(a), 0, phase])
+            elif rec["kind"] in (SORT, ARGSORT):
+                src, dst = ([c for sc in rec["scans"] for c in sc[t]] for t in (0, 1))     # segment-major
+                n_cells += len(dst)
+                records.append([rec["kind"], len(dst), rec["p0"], rec["p1"], push(dst), push(src), 0, phase])
             elif rec["kind"] == GATHER:
                 n = len(rec["dst"])
                 n_cells += n
@@ -1070,14 +1147,14 @@ def validate(plan):
     total = 0
     col_phase, last_phase = [None] * plan.n_advice, 0
     for ri, (kind, count, p0, p1, dst, a, b, phase) in enumerate(plan.records.tolist()):
-        if kind > CLAMP or kind == UNASSIGNED:
+        if kind > ARGSORT or kind == UNASSIGNED:
             raise PlanError("witness plan: record %d: unknown kind %d" % (ri, kind))
         if count == 0:
             raise PlanError("witness plan: record %d is empty" % ri)
         if phase >= plan.n_phases:
-            raise PlanError("witness plan: record %d (%s): phase out of range" % (ri, KIND_NAMES[kind]))
+            raise PlanError("witness plan: record %d (%s): phase out of range" % (ri, kind_name(kind)))
         if phase < last_phase:
-            raise PlanError("witness plan: record %d (%s): phases decrease" % (ri, KIND_NAMES[kind]))
+            raise PlanError("witness plan: record %d (%s): phases decrease" % (ri, kind_name(kind)))
         last_phase = phase
         if kind in (INPUT, MATMUL) and phase != 0:
             raise PlanError("witness plan: record %d (%s): input and matmul records belong to phase 0" % (ri, KIND_NAMES[kind]))
@@ -1105,6 +1182,11 @@ def validate(plan):
             srcs = _span(plan, a, count * ns * w, "a", ri)
             srcs = srcs[srcs != NONE]
             d = d[d != NONE]
+        elif kind in (SORT, ARGSORT):
+            if p0 == 0 or count % p0 != 0 or p1 > 1 or count > MAX_SORT_COUNT:
+                raise PlanError("witness plan: record %d (%s): bad sort shape" % (ri, kind_name(kind)))
+            d = _span(plan, dst, count, "dst", ri)
+            srcs = _span(plan, a, count, "a", ri)
         elif kind == DOT:
             w, ns = p0, p1
             if w == 0 or ns == 0 or count * ns * w > len(plan.pool):
@@ -1147,16 +1229,16 @@ def validate(plan):
             if kind in (TABLE, TBLIDX) and p0 >= len(plan.tables):
                 raise PlanError("witness plan: record %d (%s): lookup table index out of range" % (ri, KIND_NAMES[kind]))
         if (d >= cells).any() or (srcs >= cells).any():
-            raise PlanError("witness plan: record %d (%s): cell index out of range" % (ri, KIND_NAMES[kind]))
+            raise PlanError("witness plan: record %d (%s): cell index out of range" % (ri, kind_name(kind)))
         if not written.get(srcs).all():
-            raise PlanError("witness plan: record %d (%s): a cell is read before an earlier record has written it" % (ri, KIND_NAMES[kind]))
+            raise PlanError("witness plan: record %d (%s): a cell is read before an earlier record has written it" % (ri, kind_name(kind)))
         if written.get(d).any() or len(np.unique(d)) != len(d):
-            raise PlanError("witness plan: record %d (%s): a cell is written twice" % (ri, KIND_NAMES[kind]))
+            raise PlanError("witness plan: record %d (%s): a cell is written twice" % (ri, kind_name(kind)))
         written.set(d)
         total += len(d)
         for c in np.unique(d >> plan.k).tolist():
             if col_phase[c] is not None and col_phase[c] != phase:
-                raise PlanError("witness plan: record %d (%s): a column is written in two phases" % (ri, KIND_NAMES[kind]))
+                raise PlanError("witness plan: record %d (%s): a column is written in two phases" % (ri, kind_name(kind)))
             col_phase[c] = phase
     if total != plan.n_cells:
         raise PlanError("witness plan: %d cells written, its header says %d" % (total, plan.n_cells))
@@ -1249,6 +1331,16 @@ def run_plan_host(plan, x, challenges=None, phase=None):
                         if ia != NONE:
                             acc = (acc + cells[ia]) % R if kind == SUMACC else acc * cells[ia] % R
                     cells[cell] = acc
+            continue
+        if kind in (SORT, ARGSORT):
+            vals = [EL.signed(cells[c]) for c in P[a:a + count]]
+            for e, sv in enumerate(vals):                  # every source a lane reads, the smallest failing element first
+                if abs(sv) >= 1 << 62:
+                    raise AssertionError("%s (%s record %d, element %d)" % (SORT_ERROR, kind_name(kind), ri, e))
+            for g in range(0, count, p0):
+                seg = vals[g:g + p0]
+                for i, j in enumerate(sorted(range(p0), key=lambda j: (seg[j], -j if p1 else j))):
+                    cells[P[dst + g + i]] = seg[j] % R if kind == SORT else j
             continue
         lo = p0 - (1 << 32) if p0 >> 31 else p0
         for i in range(count):

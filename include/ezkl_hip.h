@@ -251,7 +251,7 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *      (nonlinearity :5143-5222), which with those ops is the conv2d_mnist example's layout ----
  * A PLAN is the layout recorded once per circuit (ezkl_amd/witness_plan.py; byte layout: csrc/witness_plan.hpp): a list of records, each a
  * batch of cell writes of one kind (copy, const, input, param, add / sub / mult, decompose hint, range-check index, inverse-or-zero, dot,
- * static-lookup output, static-lookup table-column index, integer matmul, random linear combination, rounded division by a constant, running sum, running product, gather, clamp) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
+ * static-lookup output, static-lookup table-column index, integer matmul, random linear combination, rounded division by a constant, running sum, running product, gather, clamp, sort, argsort) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
  * of constants and -- header words 12 / 13 (n_tables, n_table_values; zero, as reserved words were, in a plan without lookups), after the
  * pool -- a directory of {lo (int32), n, col_size, offset} per static lookup table and the tables' values f(lo + i) as int64.  The version
  * word stays 1.  A lookup record names its source cells and a table: with s the signed value of the cell, the output kind writes
@@ -297,6 +297,16 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *   pool[p0 + s]; every listed cell must have been written by an earlier record.  s < 0, s >= n or |s| >= 2^62 is reported as a value beyond
  *   its decomposition is ("gather index outside the table"); the lane tests s before it reads pool[p0 + s].  clamp (20) -- element-wise:
  *   a = source cell, p0 = lo, p1 = hi (int32, lo <= hi): min(max(s, lo), hi); a value beyond 62 bits clamps by its sign; it never fails.
+ * SORT AND TOP-K (kinds 21 / 22, appended; the version word stays 1 and every earlier blob keeps its bytes): the witness of layouts.rs:1158-1275
+ *   `_sort_ascending` -- the sorted tensor and the claimed indices of its permutation argument.  sort (21) / argsort (22): count destination
+ *   cells dst[e] in segments of p0 = n elements (n >= 1, count % n == 0, count <= 2^28), p1 = mode (0: the position ascending among equal values,
+ *   1: descending), a = the source cells, segment-major and dense, b unused; anything else is refused on upload ("bad sort shape").  The order of a
+ *   segment is by (signed value, position), a total order.  sort: dst[s * n + i] gets the i-th smallest signed value of the cells a[s * n .. + n)
+ *   as a field element (negative: r - |v|); argsort: the position, in [0, n), of that element in its segment.  A source with |s| >= 2^62 is
+ *   reported as a value beyond its decomposition is ("sort key beyond 62 bits", element = its place in a, once per record that reads it) and
+ *   its SEGMENT writes none of its cells; the other segments of the record are written.  Segments of up to 2048 elements (padded to a power of
+ *   two) are sorted in ONE launch, 2048 keys to a workgroup; a longer one takes several launches on the stream through key scratch the plan owns
+ *   (the largest record's segments x padded length x 16 bytes, from the column pool at upload): `launches` counts them all.
  * tile: a plan of a tiled circuit writes rows [0, U) of the block-0 and shared columns; the circuit is those U rows repeated T times down every
  *   column and copied into the columns of the other blocks.  For every pair, rows [t * U, (t + 1) * U) of column dst get rows [0, U) of column
  *   src: t = 0 .. T - 1 when dst != src, t = 1 .. T - 1 when dst == src.  Rows >= T * U and columns outside the pair list are left as they are.
