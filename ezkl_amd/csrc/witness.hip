@@ -37,6 +37,15 @@
 //    the tile and one LDS launch for the strides below it.  A source beyond 62 bits is reported as the range failures below are ("sort
 //    key beyond 62 bits") and its segment writes none of its cells.
 //
+//  * recip / sqrt records (the claims of layouts.rs:300-385 `recip` and :408-459 `sqrt`, which the reference computes in f64 and enforces
+//    with `optimum_convex_function`, :114-143): element-wise, one lane per destination cell, exact 64-bit integers.  recip: the smallest
+//    integer minimiser of |y * x - S| in closed form -- x > 0: (2S + x - 1) / (2x), x < 0: -((2S + |x|) / (2|x|)), one unsigned 64-bit
+//    division per lane (a software sequence on this hardware, small beside the two Montgomery conversions of the lane); x = 0 takes the
+//    circuit's zero_inverse constant.  This is the value the gates accept: where x > 0 divides 2S but not S the f64 formula rounds the
+//    tie up and the gates refuse it.  sqrt: T = x * scale, the floor root from a double estimate corrected by integer comparison, then
+//    r + (T - r^2 > r).  An operand beyond 62 bits, or T >= 2^62, is reported as the range failures below are ("reciprocal operand beyond
+//    62 bits", "square-root operand outside the exact range") and writes nothing.
+//
 // A value that does not fit its decomposition (|x| >= base^legs: the layout's "value exceeds the decomposition range") writes nothing
 // wrong silently, and neither does a lookup input outside its table (layouts.rs:5143-5222 `nonlinearity`; the layout's "lookup input
 // outside the table range"), and neither does a dividend of `div` beyond the range in which the integer quotient is the reference's f64
@@ -112,6 +121,7 @@ __global__ __launch_bounds__(256) void wit_elem_kernel(WitCols cols, uint32_t k,
                                                        unsigned long long* status) {
     // TABLE / TBLIDX: the launcher has resolved the table directory -- ints = the table's values, p0 = lo (int32), p1 = n, p2 = col_size
     // GATHER: b = the table's cell list (pool + p0), p1 = its length
+    // RECIP: p0 | p1 << 32 = S, p2 = the index in consts of the value a zero input takes; ISQRT: p0 = the input scale
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < count;
     bool fail = false;
@@ -157,6 +167,33 @@ __global__ __launch_bounds__(256) void wit_elem_kernel(WitCols cols, uint32_t k,
                     s = s < lo ? lo : s > hi ? hi : s;
                 }
                 v = wit_from_i64(s);
+            } else if (KIND == RECIP) {                                                       // the smallest integer minimiser of |y * x - S|, S = p0 | p1 << 32
+                fail = !fits;
+                if (!fail) {
+                    if (mag == 0) v = ld_fe(consts + p2);                                     // zero_inverse: p2 = its constant index, checked on upload
+                    else {                                                                    // S < 2^62 (upload), mag < 2^62 (fits): 2S + mag < 2^64, 2 mag < 2^63
+                        const uint64_t S = (uint64_t)p0 | ((uint64_t)p1 << 32);
+                        const uint64_t q = (2 * S + mag - (neg ? 0 : 1)) / (2 * mag);          // x > 0: ceil((2S - x) / (2x)); x < 0: floor((2S + |x|) / (2|x|))
+                        v = wit_from_i64(neg ? -(int64_t)q : (int64_t)q);                     // q <= S + 1 / 2 < 2^62
+                    }
+                }
+            } else if (KIND == ISQRT) {                                                       // the integer nearest to sqrt(T), T = x * p0; T <= 0: zero
+                const uint64_t T = mag * p0;                                                  // the low word; the high one decides with it whether T fits
+                fail = !fits || (!neg && (__umul64hi(mag, (uint64_t)p0) != 0 || (T >> 62) != 0));
+                if (!fail) {
+                    uint64_t r = 0;
+                    if (!neg && T) {
+                        r = (uint64_t)sqrt((double)T);                                        // within one of the floor root: T < 2^62, the estimate is off by < 2^-20
+                        if (r > 0x7fffffffull) r = 0x7fffffffull;                             // floor(sqrt(2^62 - 1)) = 2^31 - 1: r * r and (r + 1)^2 below fit 64 bits
+#pragma unroll
+                        for (int t = 0; t < 2; t++) {                                         // corrected by integer comparison, both ways
+                            if (r * r > T) r--;
+                            else if ((r + 1) * (r + 1) <= T) r++;
+                        }
+                        r += (T - r * r > r) ? 1 : 0;                                         // T - r^2 > r  <=>  T > (r + 1/2)^2: the nearer integer is r + 1
+                    }
+                    v = Fr::from_u64(r);
+                }
             } else if (KIND == RCIDX) {                                                       // |x - lo| // col_size
                 fail = !fits;                                                                 // |x| >= 2^62: as run_plan_host refuses it
                 const int64_t s = neg ? -(int64_t)mag : (int64_t)mag, diff = s - (int64_t)(int32_t)p0;
@@ -595,7 +632,8 @@ void launch_elem(hipStream_t st, const WitCols& cols, uint32_t k, const DevPlan*
         ints = p->table_values + t.off;
         p0 = (uint32_t)t.lo; p1 = t.n; p2 = t.col_size;
     }
-    const uint32_t* b = p->pool + (KIND == GATHER ? r.p0 : r.b);     // GATHER: the table's cell list, inside the pool: checked on upload
+    if (KIND == RECIP) p2 = r.b;                                      // the constant a zero input takes: r.b < the constants, checked on upload
+    const uint32_t* b = p->pool + (KIND == GATHER ? r.p0 : KIND == RECIP ? 0 : r.b);     // GATHER: the table's cell list, inside the pool: checked on upload
     hipLaunchKernelGGL(wit_elem_kernel<KIND>, dim3(cdiv(r.count, 256)), dim3(256), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, b, r.count, p0, p1, p2,
                        ints, (const fe_t*)p->consts, ri, p->status);
 }
@@ -782,6 +820,8 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
         case DIVC: launch_elem<DIVC>(st, cols, k, p, r, (uint32_t)ri); break;
         case GATHER: launch_elem<GATHER>(st, cols, k, p, r, (uint32_t)ri); break;
         case CLAMP: launch_elem<CLAMP>(st, cols, k, p, r, (uint32_t)ri); break;
+        case RECIP: launch_elem<RECIP>(st, cols, k, p, r, (uint32_t)ri); break;
+        case ISQRT: launch_elem<ISQRT>(st, cols, k, p, r, (uint32_t)ri); break;
         case SUMACC:
             hipLaunchKernelGGL(wit_acc_kernel<SUMACC>, dim3(cdiv((size_t)r.count * DOT_LANES, 64)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, r.count, r.p0, r.p1,
                                p->status);
@@ -826,14 +866,16 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
     status[3] = launches;
     if (dev_status[0]) {
         const uint32_t ri = (uint32_t)(status[1] >> 32), el = (uint32_t)status[1];
-        const uint32_t kind = ri < h.recs.size() ? h.recs[ri].kind : (uint32_t)N_KINDS;
+        const uint32_t kind = ri < h.recs.size() ? h.recs[ri].kind : (uint32_t)KINDS_END;
         const char* what = kind == TABLE || kind == TBLIDX ? "witness: lookup input outside the table range ("
                            : kind == MATMUL               ? "witness: einsum operand outside the exact-product range ("
                            : kind == DIVC                 ? "witness: rebase dividend outside the exact-division range ("
                            : kind == GATHER               ? "witness: gather index outside the table ("
                            : kind == SORT || kind == ARGSORT ? "witness: sort key beyond 62 bits ("
+                           : kind == RECIP                ? "witness: reciprocal operand beyond 62 bits ("
+                           : kind == ISQRT                ? "witness: square-root operand outside the exact range ("
                                                           : "witness: value exceeds the decomposition range (";
-        t_wit_error = std::string(what) + (kind < N_KINDS ? KIND_NAMES[kind] : "?") + " record " + std::to_string(ri) +
+        t_wit_error = std::string(what) + kind_name(kind) + " record " + std::to_string(ri) +
                       ", element " + std::to_string(el) + "; " + std::to_string(dev_status[0]) + (kind == MATMUL ? " operand reads in all)" : " cells in all)");
         return EZKL_ERR_INVALID;
     }

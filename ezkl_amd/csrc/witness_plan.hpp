@@ -41,6 +41,17 @@
 // dst[s * n + i] gets the i-th smallest signed value of the cells a[s * n .. + n) as integer_rep_to_felt maps it; ARGSORT: the position, in
 // [0, n), of that element in its segment.  A source with |s| >= 2^62 is a run-time failure of the lane ("sort key beyond 62 bits"), element
 // = its place in a; its segment writes none of its cells.  SORT_TILE is the number of keys one workgroup of csrc/witness.hip sorts in LDS.
+// Kind 23 (N_KINDS, the end of KIND_NAMES) is unassigned as 16 is; RECIP and ISQRT are 24 and 25, KINDS_END follows them, `kind_name`
+// names every kind.
+// A RECIP record (the claimed reciprocal of `recip`, layouts.rs:300-385): a = source cell, b = the index of `zero_inverse` in the constants
+// section (a scalar word, not a pool offset: past the constants is "zero-inverse index past the constants"), S = p0 | p1 << 32 = input
+// scale * output scale, 1 <= S < 2^62 (else "reciprocal scale outside [1, 2^62)").  With x the signed value of the cell: x = 0 -> the
+// constant; x > 0 -> ceil((2S - x) / (2x)) = (2S + x - 1) / (2x); x < 0 -> -((2S + |x|) / (2|x|)) -- the one value the gates of
+// `optimum_convex_function` accept, the smallest integer minimiser of |y * x - S|.  |x| >= 2^62 is a run-time failure of the lane
+// ("reciprocal operand beyond 62 bits").
+// An ISQRT record (the claimed root of `sqrt`, layouts.rs:408-459): a = source cell, b = 0, p0 = input scale >= 1 ("zero square-root
+// scale"), p1 = 0 ("a square-root record with a second parameter").  With T = x * p0: T <= 0 -> 0; else r = floor(sqrt(T)), r + (T - r * r > r),
+// the integer nearest to sqrt(T).  |x| >= 2^62 or T >= 2^62 is a run-time failure of the lane ("square-root operand outside the exact range").
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -53,9 +64,12 @@ namespace wplan {
 
 constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64, MAX_PHASES = 3, MAX_CHALLENGES = 64, SORT_TILE = 2048,
                    MAX_SORT_COUNT = 1u << 28;
-enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC, UNASSIGNED, SUMACC, PRODACC, GATHER, CLAMP, SORT, ARGSORT, N_KINDS };     // 16 names nothing: refused as unknown
+enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC, UNASSIGNED, SUMACC, PRODACC, GATHER, CLAMP, SORT, ARGSORT, N_KINDS,     // 16 names nothing: refused as unknown
+                       RECIP = 24, ISQRT = 25, KINDS_END };                        // N_KINDS ends KIND_NAMES and, as a kind (23), names nothing either
 static const char* const KIND_NAMES[N_KINDS] = {"copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot",
                                                 "nonlinearity", "nonlinearity_index", "matmul", "rlc", "div", "?", "sum", "prod", "gather", "clamp", "sort", "argsort"};
+// the name a message gives a kind: KIND_NAMES up to ARGSORT, the later kinds by hand, "?" for a kind that names nothing
+inline const char* kind_name(uint32_t kind) { return kind < N_KINDS ? KIND_NAMES[kind] : kind == RECIP ? "recip" : kind == ISQRT ? "sqrt" : "?"; }
 struct Rec {
     uint32_t kind, count, p0, p1, dst, a, b, phase;
 };
@@ -114,7 +128,7 @@ inline bool canonical(const uint8_t* c) {                 // below the modulus, 
 // after an EARLIER record has written it; the phases are non-decreasing and every column is written in one phase only.
 inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
     auto fail = [&](const std::string& s) { why = "witness plan: " + s; return false; };
-    auto at_rec = [&](size_t ri, uint32_t kind, const char* s) { return fail("record " + std::to_string(ri) + " (" + (kind < N_KINDS ? KIND_NAMES[kind] : "?") + "): " + s); };
+    auto at_rec = [&](size_t ri, uint32_t kind, const char* s) { return fail("record " + std::to_string(ri) + " (" + kind_name(kind) + "): " + s); };
     const uint8_t* p = static_cast<const uint8_t*>(blob);
     uint32_t h[20];
     if (!blob || len < sizeof h + 32) return fail("shorter than its header");
@@ -155,7 +169,7 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
     uint32_t last_phase = 0;
     for (size_t ri = 0; ri < out.recs.size(); ri++) {
         const Rec& r = out.recs[ri];
-        if (r.kind >= N_KINDS || r.kind == UNASSIGNED) return at_rec(ri, r.kind, "unknown kind");
+        if (r.kind >= KINDS_END || r.kind == N_KINDS || r.kind == UNASSIGNED) return at_rec(ri, r.kind, "unknown kind");
         if (r.count == 0) return at_rec(ri, r.kind, "empty");
         if (r.phase >= n_phases) return at_rec(ri, r.kind, "phase out of range");
         if (r.phase < last_phase) return at_rec(ri, r.kind, "phases decrease");
@@ -214,12 +228,25 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
             if (r.p0 == 0 || r.count % r.p0 != 0 || r.p1 > 1 || r.count > MAX_SORT_COUNT) return at_rec(ri, r.kind, "bad sort shape");
             a_cells = true;
             break;
+        case RECIP: {                                    // S = p0 | p1 << 32, b = the constant a zero input takes
+            a_cells = true;
+            const uint64_t S = (uint64_t)r.p0 | ((uint64_t)r.p1 << 32);
+            if (S == 0 || S >= ((uint64_t)1 << 62)) return at_rec(ri, r.kind, "reciprocal scale outside [1, 2^62)");
+            if (r.b >= n_con) return at_rec(ri, r.kind, "zero-inverse index past the constants");
+            break;
+        }
+        case ISQRT:
+            a_cells = true;
+            if (r.p0 == 0) return at_rec(ri, r.kind, "zero square-root scale");
+            if (r.p1 != 0) return at_rec(ri, r.kind, "a square-root record with a second parameter");
+            break;
         case DOT:
             if (r.p0 == 0 || r.p1 == 0 || (uint64_t)r.count * r.p1 > P.size() || (uint64_t)r.count * r.p1 * r.p0 > P.size()) return at_rec(ri, r.kind, "bad dot shape");
             n_dst = (uint64_t)r.count * r.p1; n_a = n_b = n_dst * r.p0; a_cells = b_cells = true;
             break;
         }
-        if (!span_ok(r.dst, n_dst) || !span_ok(r.a, n_a) || !span_ok(r.b, n_b)) return at_rec(ri, r.kind, "an index array runs past the pool");
+        if (!span_ok(r.dst, n_dst) || !span_ok(r.a, n_a) || (r.kind != RECIP && !span_ok(r.b, n_b)))     // (RECIP: b is no pool offset)
+            return at_rec(ri, r.kind, "an index array runs past the pool");
         const bool sparse = r.kind == DOT || r.kind == SUMACC || r.kind == PRODACC;     // 0xffffffff = no entry
         for (uint64_t i = 0; i < n_a; i++) {
             const uint32_t x = P[r.a + i];

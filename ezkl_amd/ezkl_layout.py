@@ -15,6 +15,8 @@ One linear coordinate (`einsum_col_coord`) is shared by the six einsum VarTensor
 columns it touches.  Column overflow into a second block (assign_einsum_with_duplication) is not needed at the bench sizes and is
 refused loudly.
 """
+import math
+
 import numpy as np
 
 from . import ezkl_circuit as EC
@@ -33,6 +35,8 @@ DIV_ERROR = "rebase dividend outside the exact-division range"
 GATHER_ERROR = "gather index outside the table"
 SORT_ERROR = "sort key beyond 62 bits"
 SORT_MODES = ("unsorted", "smallest_index_first", "largest_index_first")       # layouts.rs:1124-1131 SortCollisionMode
+RECIP_ERROR = "reciprocal operand beyond 62 bits"
+SQRT_ERROR = "square-root operand outside the exact range"
 
 
 def clamped(s, lo, hi):
@@ -48,6 +52,43 @@ def round_div(s, d):
     mag = abs(s)
     assert mag < 1 << 52, DIV_ERROR
     return ((s > 0) - (s < 0)) * ((mag + d // 2) // d)
+
+
+def recip_claim(s, S, zero_inverse):
+    """the reciprocal the prover claims in `recip` for the signed input s at S = input_scale * output_scale: `zero_inverse` for s = 0, else
+    the smallest integer minimiser of |y * s - S| -- the one value the gates of `optimum_convex_function` accept (f(y) <= f(y + 1) and
+    f(y) < f(y - 1)) -- in exact integers: s > 0: ceil((2S - s) / (2s)); s < 0: -floor((2S + |s|) / (2|s|)).  The reference computes
+    `(out_scale * (1 / (s / in_scale))).round()` in f64 (/root/reference/src/tensor/ops.rs:2353-2370): the same value except at an exact tie with
+    s > 0 (s divides 2S but not S), where the f64 rounds up to y + 1 and the reference's own `less(f(y + 1), f(y))` refuses it.  (A
+    recording region's symbol answers for itself: a RECIP record.)"""
+    if hasattr(s, "recip_claim"):
+        return s.recip_claim(S, zero_inverse)
+    assert abs(s) < 1 << 62, RECIP_ERROR
+    if s == 0:
+        return zero_inverse
+    if s > 0:
+        return -((s - 2 * S) // (2 * s))
+    return -((2 * S - s) // (-2 * s))
+
+
+def sqrt_claim(s, scale):
+    """the root the prover claims in `sqrt` for the signed input s: with T = s * scale, 0 for T <= 0, else the integer nearest to sqrt(T)
+    (a tie would need T = r^2 + r + 1/4) -- `(scale * (s / scale).sqrt()).round()` of /root/reference/src/tensor/ops.rs:1844-1852 in exact
+    integers, and the one value the gates accept.  (A recording region's symbol answers for itself: an ISQRT record.)"""
+    if hasattr(s, "sqrt_claim"):
+        return s.sqrt_claim(scale)
+    T = s * scale
+    assert abs(s) < 1 << 62 and T < 1 << 62, SQRT_ERROR
+    if T <= 0:
+        return 0
+    r = math.isqrt(T)
+    return r + (T - r * r > r)
+
+
+def zero_recip(output_scale, eps):
+    """`zero_recip` (/root/reference/src/tensor/ops.rs:2385-2395): (out_scale * (1 / (0 + eps))).round(), the constant `recip` gives a zero input"""
+    v = float(output_scale) * (1.0 / (0.0 + eps))
+    return int(math.copysign(math.floor(abs(v) + 0.5), v))
 
 
 class Region:
@@ -745,6 +786,97 @@ class BaseRegion(Region):
         """layouts.rs:1343-1361 `topk_axes` over a list of equal-length rows (the slices along the axis)"""
         return [self.topk(row, k, largest) for row in rows]
 
+    def not_(self, mask):
+        """layouts.rs:3727-3740 `not` (a keyword here): iff(mask, 0, 1)"""
+        n = len(mask)
+        return self.iff(mask, [Val(0, const=True)] * n, [Val(1, const=True)] * n)
+
+    def optimum_convex_function(self, x, f):
+        """layouts.rs:114-143: 1 where x is the smallest minimiser of the convex f over the integers: f(x) <= f(x + 1) and f(x) < f(x - 1)"""
+        one = [Val(1, const=True)] * len(x)
+        f_x = f(x)
+        f_x_plus_1 = f(self.pairwise(x, one, EC.ADD))
+        f_x_minus_1 = f(self.pairwise(x, one, EC.SUB))
+        is_opt_rhs = self.less_equal(f_x, f_x_plus_1)
+        is_opt_lhs = self.less(f_x, f_x_minus_1)
+        return self.and_(is_opt_lhs, is_opt_rhs)
+
+    def recip(self, vals, input_scale, output_scale, eps):
+        """layouts.rs:300-385: the prover claims round(input_scale * output_scale / x) (`recip_claim`), the claim is range-checked by
+        decomposition, a zero input is held to `zero_inverse` = round(output_scale / eps) by the two masks, and everywhere else the claim
+        must minimise |claim * x - input_scale * output_scale|"""
+        n = len(vals)
+        S = int(input_scale) * int(output_scale)
+        zero_inverse = zero_recip(output_scale, eps)
+        claimed = [Val(recip_claim(signed(v.v), S, zero_inverse)) for v in vals]
+        base, legs = self.decomp
+        _, claimed = self.decompose(claimed, base, legs)
+        equal_zero_mask = self.equals_zero(vals)
+        not_equal_zero_mask = self.not_(equal_zero_mask)
+        equal_inverse_mask = self.equals(claimed, [Val(zero_inverse, const=True)] * n)
+        masked_unit_scale = self.pairwise([Val(S, const=True)] * n, not_equal_zero_mask, EC.MULT)
+        self.enforce_equality(equal_zero_mask, equal_inverse_mask)
+        def err_func(x):
+            return self.l1_distance(self.pairwise(x, vals, EC.MULT), masked_unit_scale)
+        is_opt = self.optimum_convex_function(claimed, err_func)
+        is_opt = self.pairwise(is_opt, equal_zero_mask, EC.ADD)           # a zero input is excused from the optimum
+        self.enforce_equality(is_opt, [Val(1, const=True)] * n)
+        return claimed
+
+    def sqrt(self, vals, input_scale):
+        """layouts.rs:408-459: the prover claims round(sqrt(x * input_scale)) (`sqrt_claim`), `abs` holds the claim to its range and to a
+        sign, and the claim must minimise |claim^2 - x * input_scale|"""
+        n = len(vals)
+        claimed = [Val(sqrt_claim(signed(v.v), int(input_scale))) for v in vals]
+        claimed = self.abs(claimed)
+        rescaled_input = self.pairwise(vals, [Val(int(input_scale), const=True)] * n, EC.MULT)
+        def err_func(x):
+            return self.l1_distance(self.pairwise(x, x, EC.MULT), rescaled_input)
+        is_opt = self.optimum_convex_function(claimed, err_func)
+        self.enforce_equality(is_opt, [Val(1, const=True)] * n)
+        return claimed
+
+    def rsqrt(self, vals, input_scale, output_scale, eps):
+        """layouts.rs:482-505: the reciprocal of the square root"""
+        return self.recip(self.sqrt(vals, input_scale), input_scale, output_scale, eps)
+
+    def max(self, vals):
+        """layouts.rs:5390-5400: the last of an `unsorted` ascending sort"""
+        return self.sort_ascending(vals, "unsorted")[0][-1]
+
+    def min(self, vals):
+        """layouts.rs:5403-5413: the first of an `unsorted` ascending sort"""
+        return self.sort_ascending(vals, "unsorted")[0][0]
+
+    def percent(self, vals, input_scale, output_scale, eps):
+        """layouts.rs:6632-6661: every value times the reciprocal of their sum"""
+        if any(v.cell is None and not v.const for v in vals):
+            vals = self.assign(self.inputs[0], vals)
+            self.increment(len(vals))
+        denom = self.sum(vals)
+        inv_denom = self.recip([denom], input_scale, output_scale, eps)
+        return self.pairwise(vals, [inv_denom[0]] * len(vals), EC.MULT)
+
+    def softmax(self, vals, input_scale, output_scale, eps, exp="exp"):
+        """layouts.rs:6687-6711: the maximum is subtracted, the static lookup `exp` (LookupOp::Exp at the input scale) is applied, `percent`"""
+        max_val = self.max(vals)
+        sub = self.pairwise(vals, [max_val] * len(vals), EC.SUB)
+        ex = self.nonlinearity(sub, exp)
+        return self.percent(ex, input_scale, output_scale, eps)
+
+    def softmax_axes(self, rows, input_scale, output_scale, eps, exp="exp"):
+        """layouts.rs:6610-6629 `softmax_axes` over a list of equal-length rows (the slices along the axis)"""
+        return [self.softmax(row, input_scale, output_scale, eps, exp) for row in rows]
+
+    def mean_of_squares(self, rows):
+        """layouts.rs:3022-3035 `mean_of_squares_axes` over a list of equal-length rows: the squares (`pow` 2: `pairwise` MULT with itself),
+        their sum per row, `div` by the row length -> one value per row"""
+        length = len(rows[0])
+        flat = [v for row in rows for v in row]
+        squared = self.pairwise(flat, flat, EC.MULT)
+        sum_squared = [self.sum(squared[i * length:(i + 1) * length]) for i in range(len(rows))]
+        return self.div(sum_squared, length)
+
     def einsum(self, ein, A, B, challenges=None):
         """assign_einsum of an EinsumMatmulCircuit laid over this region's configuration (EinsumMatmulCircuit.over), in this region, at
         the einsum coordinate: A, B are len x len Vals"""
@@ -1069,6 +1201,58 @@ class SortTopkCircuit(LayoutCircuit):
     def plan_identity(self):
         shape = [self.k, self.w, self.n_inputs, self.k_top, int(self.largest), SORT_MODES.index(self.mode), self.base, self.legs, self.gc.advices[0].num_blocks()]
         return np.asarray(shape, np.int64).tobytes()
+
+    def synthesize(self, x, witness=True):
+        assert len(x) == self.n_inputs
+        reg = BaseRegion(self.gc, witness)
+        outs = self.layout(reg, [Val(int(v) % R) for v in x], Val)
+        reg.finish(self.gc.const_cols)
+        self.outputs = [v.v for v in outs]
+        return reg
+
+
+class NormCircuit(LayoutCircuit):
+    """the two normalisations of a transformer on `rows` x `length` private inputs, instance = the outputs, row by row.  Softmax
+    (layouts.rs `softmax_axes` along the rows): max by an `unsorted` sort, the exp table, sum, the claimed reciprocal, MULT -- outputs at
+    input_scale * output_scale.  With layer_norm: x - mean (`sum`, `div`), `mean_of_squares`, `rsqrt` (the claimed root, then the claimed
+    reciprocal), MULT, `div` by the input scale -- outputs at the output scale.  The op sequence is stated once (`layout`), so that
+    witness_plan.record_plan can run it on symbols.  The settings carry the range checks of the decomposition, (-1, 1) and (0, base - 1),
+    the (0, 1) check of `and` / `iff`, and for the softmax the shuffle argument of the sort and the exp table over `lookup_range`.  eps:
+    what `recip` adds to a zero input (zero_inverse = round(output_scale / eps) must fit the decomposition, as every |claim * x - S| must)."""
+
+    def __init__(self, logrows, num_inner_cols, capacity, rows, length, input_scale=8, output_scale=64, eps=1.0 / 128, layer_norm=False,
+                 decomp_base=128, decomp_legs=2, lookup_range=(-255, 0)):
+        self.k, self.w, self.rows, self.length, self.n_inputs = logrows, num_inner_cols, int(rows), int(length), int(rows) * int(length)
+        self.input_scale, self.output_scale, self.eps, self.layer_norm = int(input_scale), int(output_scale), float(eps), bool(layer_norm)
+        self.base, self.legs, self.lookup_range = decomp_base, decomp_legs, tuple(lookup_range)
+        assert self.input_scale >= 1 and self.output_scale >= 1 and abs(zero_recip(self.output_scale, self.eps)) < decomp_base ** decomp_legs
+        scale = self.input_scale
+        self.exp = lambda x: int(math.floor(scale * math.exp(x / scale) + 0.5))         # LookupOp::Exp { scale, base: e } (ops.rs `exp`)
+        softmax = dict(required_lookups=[("exp", self.exp)], lookup_range=self.lookup_range, total_shuffle_col_size=self.n_inputs, num_shuffles=1)
+        self.settings = EC.GraphSettings(logrows, num_inner_cols, capacity, total_const_size=8, required_range_checks=[(-1, 1), (0, decomp_base - 1), (0, 1)],
+                                         model_instance_shapes=[[self.rows, self.length]], **({} if self.layer_norm else softmax))
+        self.gc = EC.GraphConfig(self.settings)
+
+    def layout(self, reg, inputs, param):
+        reg.decomp = (self.base, self.legs)
+        L, si, so, eps = self.length, self.input_scale, self.output_scale, self.eps
+        vals = reg.assign(reg.inputs[0], inputs)
+        reg.increment(len(vals))
+        rows = [vals[i * L:(i + 1) * L] for i in range(self.rows)]
+        if self.layer_norm:
+            means = reg.div([reg.sum(row) for row in rows], L)
+            centred = [reg.pairwise(row, [mean] * L, EC.SUB) for row, mean in zip(rows, means)]
+            inv = reg.rsqrt(reg.mean_of_squares(centred), si, so, eps)
+            outs = [v for row, r in zip(centred, inv) for v in reg.div(reg.pairwise(row, [r] * L, EC.MULT), si)]
+        else:
+            outs = [v for row in reg.softmax_axes(rows, si, so, eps) for v in row]
+        reg.constrain_instance(outs, self.gc.instance)
+        return outs
+
+    def plan_identity(self):
+        shape = [self.k, self.w, self.rows, self.length, self.input_scale, self.output_scale, int(self.layer_norm), self.base, self.legs,
+                 self.lookup_range[0], self.lookup_range[1], self.gc.advices[0].num_blocks()]
+        return np.asarray(shape, np.int64).tobytes() + np.float64(self.eps).tobytes()
 
     def synthesize(self, x, witness=True):
         assert len(x) == self.n_inputs

@@ -1,5 +1,5 @@
-"""Witness plans: the layout of an MlpCircuit, a ConvMnistCircuit, an EinsumMatmulCircuit, a SumProdLayoutCircuit, a SortTopkCircuit or the
-TransformerSurrogateCircuit's unit recorded ONCE, replayed for every proof.
+"""Witness plans: the layout of an MlpCircuit, a ConvMnistCircuit, an EinsumMatmulCircuit, a SumProdLayoutCircuit, a SortTopkCircuit, a
+NormCircuit or the TransformerSurrogateCircuit's unit recorded ONCE, replayed for every proof.
 
 Which advice cell holds which value depends only on the circuit (BaseRegion places cells from the linear coordinate, the duplicated rows
 of `dot` from the block geometry; constants and the circuit's parameters are the same for every input), so `record_plan` runs one
@@ -21,7 +21,10 @@ and `shuffle` (both sides of the argument are placed through `put`: parameter, c
 by a VALUE -- `BaseRegion.row_at`, the embedding gather -- is the index itself in the key coordinate and a GATHER element over the cells of
 the dynamic table in every other one; `shuffle` in a data-dependent order is refused by name), `ezkl_layout.clamped` (a CLAMP record) and
 `sort_ascending` / `topk` (`BaseRegion._sorted`, the one data-dependent step, is a SORT segment for the sorted values and an ARGSORT segment
-for the claimed indices; everything around it is records of the other kinds).
+for the claimed indices; everything around it is records of the other kinds), and `recip` / `sqrt` with what is built on them (`rsqrt`,
+`percent`, `softmax`, `mean_of_squares`): the claimed reciprocal is a RECIP element, the claimed root an ISQRT element
+(`ezkl_layout.recip_claim` / `sqrt_claim`, the two data-dependent steps), the masks, products, distances and comparisons of
+`optimum_convex_function` around them are records of the other kinds, `max` is a sort and `exp` a static lookup.
 The MLP recorder keeps refusing them by name.  The TransformerSurrogateCircuit lays its einsum over its own configuration
 (`BaseRegion.einsum`): it is recorded on a PhasedLookupRecordingRegion -- the lookup region with the einsum region's `put_cell`, matmul
 record, running values and phase bookkeeping -- into a TWO-phase plan of the unit's rows; the tiling is the device's
@@ -77,6 +80,16 @@ A record of an element-wise kind has `count` destination cells pool[dst + i], pr
            the run-time failure "sort key beyond 62 bits", reported like the decomposition-range failure with element = its place in a; on
            the device its segment writes none of its cells
 
+    (kind 23 is unassigned as 16 is; the two kinds below are 24 and 25)
+    RECIP  a = source cell, b = the index in the constants section of `zero_inverse` (ONE word for the record, not a pool offset), p0 / p1 =
+           the low / high word of S = input_scale * output_scale, 1 <= S < 2^62.  With x the signed value of the cell: x = 0 -> that
+           constant; x > 0 -> ceil((2S - x) / (2x)); x < 0 -> -floor((2S + |x|) / (2|x|)): the smallest integer minimiser of |y * x - S|
+           (ezkl_layout.recip_claim).  |x| >= 2^62 is the run-time failure "reciprocal operand beyond 62 bits", reported like the
+           decomposition-range failure
+    ISQRT  a = source cell, b = 0, p0 = the input scale >= 1, p1 = 0.  With T = x * p0: T <= 0 -> 0, else r = isqrt(T), r + (T - r * r > r):
+           the integer nearest to sqrt(T) (ezkl_layout.sqrt_claim).  |x| >= 2^62 or T >= 2^62 is the run-time failure "square-root operand
+           outside the exact range", reported like the decomposition-range failure
+
 PHASES.  A circuit with second-phase advice (the Freivalds einsum) has columns that depend on challenges squeezed after the first-phase
 commitments: its plan has n_phases = 2, and every record carries the phase whose run replays it.  Phases are non-decreasing along the
 record list; a column belongs to the phase of the records that write it (never to two; a column no record writes: phase 0); INPUT and
@@ -100,6 +113,9 @@ equality tests of tests/test_witness_plan_cpu.py fail loudly -- an assert or a P
     sum (_accumulate)         `(acc + sum(chunk)) % R` with acc and sum() starting from the integer 0, chunk = the w cells of the row
     prod (_accumulate)        `acc = acc * v % R` over the w cells of the row, acc starting from the integer 1
     clamped (module level)    `s.clamped(lo, hi)` when the signed value is a symbol, `min(max(s, lo), hi)` otherwise
+    recip_claim (module level) `s.recip_claim(S, zero_inverse)` when the signed value is a symbol; in `recip`: `recip_claim(signed(v.v), S, zero_inverse)`
+    sqrt_claim (module level) `s.sqrt_claim(scale)` when the signed value is a symbol; in `sqrt`: `sqrt_claim(signed(v.v), int(input_scale))`
+                              (`signed`: `v if v < R // 2 else v - R`, as above: the symbol IS the signed value)
     _sorted                   overridden: `assert abs(s) < 1 << 62` is the run-time check of SORT / ARGSORT
     row_at                    overridden: `assert 0 <= signed(index.v) < len(table_rows)` is the run-time check of GATHER
     equals_zero               `pow(v, -1, R) if v else 0`   (the truth value of a cell symbol is True: INVZ covers both branches)
@@ -125,9 +141,11 @@ COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX,
 UNASSIGNED = 16                                    # the kind after DIVC names nothing and never will: both validators refuse it as unknown
 SUMACC, PRODACC, GATHER, CLAMP = range(17, 21)
 SORT, ARGSORT = 21, 22
+UNASSIGNED_2 = 23                                  # the kind after ARGSORT names nothing either: N_KINDS of csrc/witness_plan.hpp, the end of its name table
+RECIP, ISQRT = 24, 25
 KIND_NAMES = ["copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot", "nonlinearity", "nonlinearity_index", "matmul", "rlc",
               "div", "?", "sum", "prod", "gather", "clamp"]
-_LATER_KIND_NAMES = {SORT: "sort", ARGSORT: "argsort"}          # KIND_NAMES is the list of the kinds up to CLAMP, as tests pin it: later kinds are named here
+_LATER_KIND_NAMES = {SORT: "sort", ARGSORT: "argsort", RECIP: "recip", ISQRT: "sqrt"}          # KIND_NAMES is the list of the kinds up to CLAMP, as tests pin it: later kinds are named here
 SORT_TILE, MAX_SORT_COUNT = 2048, 1 << 28                       # csrc/witness_plan.hpp: the keys one workgroup sorts in LDS; the most cells of a sort record
 _HEADER = struct.Struct("<20I32s")
 RANGE_ERROR = "value exceeds the decomposition range"
@@ -136,6 +154,7 @@ OPERAND_ERROR = "einsum operand outside the exact-product range"
 DIV_ERROR = EL.DIV_ERROR
 GATHER_ERROR = "gather index outside the table"
 SORT_ERROR = EL.SORT_ERROR
+RECIP_ERROR, SQRT_ERROR = EL.RECIP_ERROR, EL.SQRT_ERROR
 MAX_PHASES, MAX_CHALLENGES = 3, 64
 
 
@@ -192,6 +211,8 @@ class _Cell(_Sym):
             self._no()
         return _Fold(PRODACC, None, [self.idx])
     def clamped(self, lo, hi): return _Clamp(self, lo, hi)      # ezkl_layout.clamped on the signed value
+    def recip_claim(self, S, zero_inverse): return _Recip(self, S, zero_inverse)     # ezkl_layout.recip_claim on the signed value
+    def sqrt_claim(self, scale): return _Isqrt(self, scale)                          # ezkl_layout.sqrt_claim on the signed value
 
 
 class _Input(_Sym):
@@ -269,6 +290,18 @@ class _Fold(_Sym):
 
 class _Clamp(_Sym):
     def __init__(self, a, lo, hi): self.a, self.lo, self.hi = a.idx, lo, hi
+
+
+class _Recip(_Sym):
+    """the claimed reciprocal of cell a at S = input_scale * output_scale; `zero_inverse` for a zero"""
+
+    def __init__(self, a, S, zero_inverse): self.a, self.S, self.zero_inverse = a.idx, S, zero_inverse
+
+
+class _Isqrt(_Sym):
+    """the claimed square root of cell a times `scale`"""
+
+    def __init__(self, a, scale): self.a, self.scale = a.idx, scale
 
 
 class _Pick:
@@ -403,7 +436,7 @@ class _Records:
         self.rec_of = {}                           # cell -> record that writes it
 
     def _new(self, key):
-        self.recs.append(dict(kind=key[0], p0=key[1], p1=key[2], phase=key[3], dst=[], a=[], b=[], dots=[], scans=[]))
+        self.recs.append(dict(kind=key[0], p0=key[1], p1=key[2], phase=key[-1], scalar=key[3] if len(key) == 5 else None, dst=[], a=[], b=[], dots=[], scans=[]))
         return len(self.recs) - 1
 
     def _slot(self, key, sources, phase=0):
@@ -435,6 +468,15 @@ class _Records:
         rec["dst"].append(dst); rec["a"].append(a)
         if b is not None:
             rec["b"].append(b)
+        self._claim(dst, ri)
+
+    def emit_recip(self, dst, a, S, zero_inverse, phase=0):
+        """one element of a RECIP record: the records are kept apart by S and by the constant a zero input takes (its index: the record's b)"""
+        if a not in self.rec_of:
+            raise PlanError("advice cell %d is read before it is written" % a)
+        ri = self._slot((RECIP, S & NONE, S >> 32, zero_inverse), (a,), phase)
+        rec = self.recs[ri]
+        rec["dst"].append(dst); rec["a"].append(a)
         self._claim(dst, ri)
 
     def emit_dot(self, w, steps, phase=0):
@@ -600,6 +642,8 @@ class RecordingRegion(EL.BaseRegion):
     nonlinearity, sum, prod, _accumulate = _refused("nonlinearity"), _refused("sum"), _refused("prod"), _refused("sum / prod")
     dynamic_lookup, shuffle, _lookup_any = _refused("dynamic_lookup"), _refused("shuffle"), _refused("lookup_any")
     sort_ascending, topk, _sorted = _refused("sort_ascending"), _refused("topk"), _refused("sort_ascending")
+    recip, sqrt, rsqrt, max, min = _refused("recip"), _refused("sqrt"), _refused("rsqrt"), _refused("max"), _refused("min")
+    percent, softmax, softmax_axes, mean_of_squares = _refused("percent"), _refused("softmax"), _refused("softmax_axes"), _refused("mean_of_squares")
     del _counted, _refused
 
 
@@ -699,6 +743,18 @@ class LookupRecordingRegion(RecordingRegion):
 
     topk = EL.BaseRegion.topk
 
+    # ---- recip / sqrt and what is built on them: BaseRegion's ops around `recip_claim` / `sqrt_claim` ----------------------------------------------
+    def recip(self, vals, input_scale, output_scale, eps):
+        self.n_ops += 1
+        return EL.BaseRegion.recip(self, vals, input_scale, output_scale, eps)
+
+    def sqrt(self, vals, input_scale):
+        self.n_ops += 1
+        return EL.BaseRegion.sqrt(self, vals, input_scale)
+
+    rsqrt, max, min, percent = EL.BaseRegion.rsqrt, EL.BaseRegion.max, EL.BaseRegion.min, EL.BaseRegion.percent
+    softmax, softmax_axes, mean_of_squares = EL.BaseRegion.softmax, EL.BaseRegion.softmax_axes, EL.BaseRegion.mean_of_squares
+
     def _sorted(self, vals, mode):
         """BaseRegion._sorted on symbols: one segment over the cells the values are assigned in; its sorted values and their positions are
         collected as the layout places them and emitted, each list as one segment, once it is whole"""
@@ -745,6 +801,14 @@ class LookupRecordingRegion(RecordingRegion):
             if not -(1 << 31) <= v.lo <= v.hi < 1 << 31:
                 raise PlanError("clamp bounds beyond 32 bits")
             self.out.emit(CLAMP, dst, v.a, p0=v.lo & NONE, p1=v.hi & NONE, reads=(v.a,))
+        elif isinstance(v, _Recip):
+            if not 1 <= v.S < 1 << 62:
+                raise PlanError("a reciprocal at a scale outside [1, 2^62)")
+            self.out.emit_recip(dst, v.a, v.S, self._const(v.zero_inverse))
+        elif isinstance(v, _Isqrt):
+            if not 1 <= v.scale < 1 << 32:
+                raise PlanError("a square root at a scale outside [1, 2^32)")
+            self.out.emit(ISQRT, dst, v.a, p0=v.scale, reads=(v.a,))
         elif isinstance(v, _PickKey):
             self._emit(v.inner, dst)
             v.pick.key = dst
@@ -1005,6 +1069,9 @@ class WitnessPlan:
                 src, dst = ([c for sc in rec["scans"] for c in sc[t]] for t in (0, 1))     # segment-major
                 n_cells += len(dst)
                 records.append([rec["kind"], len(dst), rec["p0"], rec["p1"], push(dst), push(src), 0, phase])
+            elif rec["kind"] == RECIP:
+                n_cells += len(rec["dst"])
+                records.append([RECIP, len(rec["dst"]), rec["p0"], rec["p1"], push(rec["dst"]), push(rec["a"]), rec["scalar"], phase])
             elif rec["kind"] == GATHER:
                 n = len(rec["dst"])
                 n_cells += n
@@ -1147,7 +1214,7 @@ def validate(plan):
     total = 0
     col_phase, last_phase = [None] * plan.n_advice, 0
     for ri, (kind, count, p0, p1, dst, a, b, phase) in enumerate(plan.records.tolist()):
-        if kind > ARGSORT or kind == UNASSIGNED:
+        if kind > ISQRT or kind in (UNASSIGNED, UNASSIGNED_2):
             raise PlanError("witness plan: record %d: unknown kind %d" % (ri, kind))
         if count == 0:
             raise PlanError("witness plan: record %d is empty" % ri)
@@ -1202,7 +1269,7 @@ def validate(plan):
             d = _span(plan, dst, count, "dst", ri)
             x = _span(plan, a, count, "a", ri)
             srcs = np.zeros(0, np.uint32)
-            if kind in (COPY, ADD, SUB, MUL, HINT, RCIDX, INVZ, TABLE, TBLIDX, DIVC, GATHER, CLAMP):
+            if kind in (COPY, ADD, SUB, MUL, HINT, RCIDX, INVZ, TABLE, TBLIDX, DIVC, GATHER, CLAMP, RECIP, ISQRT):
                 srcs = x
             else:
                 lim = {CONST: len(plan.consts), INPUT: plan.n_inputs, PARAM: len(plan.params)}[kind]
@@ -1226,6 +1293,16 @@ def validate(plan):
                 srcs = np.concatenate([srcs, plan.pool[p0:p0 + p1]])
             if kind == CLAMP and _i32(p0) > _i32(p1):
                 raise PlanError("witness plan: record %d (%s): bad clamp bounds" % (ri, KIND_NAMES[kind]))
+            if kind == RECIP:                             # S = p0 | p1 << 32; b: the constant a zero input takes
+                if not 1 <= (p0 | p1 << 32) < 1 << 62:
+                    raise PlanError("witness plan: record %d (%s): reciprocal scale outside [1, 2^62)" % (ri, kind_name(kind)))
+                if b >= len(plan.consts):
+                    raise PlanError("witness plan: record %d (%s): zero-inverse index past the constants" % (ri, kind_name(kind)))
+            if kind == ISQRT:
+                if p0 == 0:
+                    raise PlanError("witness plan: record %d (%s): zero square-root scale" % (ri, kind_name(kind)))
+                if p1 != 0:
+                    raise PlanError("witness plan: record %d (%s): a square-root record with a second parameter" % (ri, kind_name(kind)))
             if kind in (TABLE, TBLIDX) and p0 >= len(plan.tables):
                 raise PlanError("witness plan: record %d (%s): lookup table index out of range" % (ri, KIND_NAMES[kind]))
         if (d >= cells).any() or (srcs >= cells).any():
@@ -1371,6 +1448,16 @@ def run_plan_host(plan, x, challenges=None, phase=None):
                 v = cells[P[p0 + s]]
             elif kind == CLAMP:                           # beyond 62 bits: by its sign, as the lane does
                 v = min(max(EL.signed(cells[ia]), lo), _i32(p1)) % R
+            elif kind == RECIP:                           # the claim rule is the layout's, in exact integers
+                s = EL.signed(cells[ia])
+                if abs(s) >= 1 << 62:
+                    raise AssertionError("%s (%s record %d, element %d)" % (RECIP_ERROR, kind_name(kind), ri, i))
+                v = consts[b] if s == 0 else EL.recip_claim(s, p0 | p1 << 32, 0) % R
+            elif kind == ISQRT:
+                s = EL.signed(cells[ia])
+                if abs(s) >= 1 << 62 or s * p0 >= 1 << 62:
+                    raise AssertionError("%s (%s record %d, element %d)" % (SQRT_ERROR, kind_name(kind), ri, i))
+                v = EL.sqrt_claim(s, p0)
             elif kind == RCIDX:
                 s = EL.signed(cells[ia])
                 if abs(s) >= 1 << 62:                 # what a lane holds in 64 bits; the layout only range-checks signs and digits

@@ -251,7 +251,8 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *      (nonlinearity :5143-5222), which with those ops is the conv2d_mnist example's layout ----
  * A PLAN is the layout recorded once per circuit (ezkl_amd/witness_plan.py; byte layout: csrc/witness_plan.hpp): a list of records, each a
  * batch of cell writes of one kind (copy, const, input, param, add / sub / mult, decompose hint, range-check index, inverse-or-zero, dot,
- * static-lookup output, static-lookup table-column index, integer matmul, random linear combination, rounded division by a constant, running sum, running product, gather, clamp, sort, argsort) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
+ * static-lookup output, static-lookup table-column index, integer matmul, random linear combination, rounded division by a constant, running sum, running product, gather, clamp, sort, argsort,
+ * claimed reciprocal, claimed square root) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
  * of constants and -- header words 12 / 13 (n_tables, n_table_values; zero, as reserved words were, in a plan without lookups), after the
  * pool -- a directory of {lo (int32), n, col_size, offset} per static lookup table and the tables' values f(lo + i) as int64.  The version
  * word stays 1.  A lookup record names its source cells and a table: with s the signed value of the cell, the output kind writes
@@ -307,6 +308,16 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *   its SEGMENT writes none of its cells; the other segments of the record are written.  Segments of up to 2048 elements (padded to a power of
  *   two) are sorted in ONE launch, 2048 keys to a workgroup; a longer one takes several launches on the stream through key scratch the plan owns
  *   (the largest record's segments x padded length x 16 bytes, from the column pool at upload): `launches` counts them all.
+ * RECIPROCAL AND SQUARE ROOT (kinds 24 / 25; kind 23 stays unassigned as 16 does, the version word stays 1 and every earlier blob keeps its
+ *   bytes): the claims of layouts.rs:300-385 `recip` and :408-459 `sqrt`, in exact integers.  recip (24) -- element-wise: a = source cell,
+ *   b = the index of `zero_inverse` in the constants section (one word, not a pool offset), p0 / p1 = the low / high word of S = input scale *
+ *   output scale, 1 <= S < 2^62.  With x the signed value of the cell: x = 0 -> that constant; x > 0 -> ceil((2S - x) / (2x)); x < 0 ->
+ *   -floor((2S + |x|) / (2|x|)): the smallest integer minimiser of |y * x - S|, the one value the gates of `optimum_convex_function` accept
+ *   (the f64 formula of the reference differs from it at exact ties with x > 0, where the reference's own gates refuse the f64 value).
+ *   |x| >= 2^62 is reported as a value beyond its decomposition is ("reciprocal operand beyond 62 bits").  sqrt (25) -- element-wise: a =
+ *   source cell, b = 0, p0 = input scale >= 1, p1 = 0.  With T = x * p0: T <= 0 -> 0; else r = floor(sqrt(T)), r + (T - r * r > r), the
+ *   integer nearest to sqrt(T).  |x| >= 2^62 or T >= 2^62 is reported likewise ("square-root operand outside the exact range").  S = 0,
+ *   S >= 2^62, a constant index past the constants, a zero scale or p1 != 0 on sqrt are refused on upload.
  * tile: a plan of a tiled circuit writes rows [0, U) of the block-0 and shared columns; the circuit is those U rows repeated T times down every
  *   column and copied into the columns of the other blocks.  For every pair, rows [t * U, (t + 1) * U) of column dst get rows [0, U) of column
  *   src: t = 0 .. T - 1 when dst != src, t = 1 .. T - 1 when dst == src.  Rows >= T * U and columns outside the pair list are left as they are.
