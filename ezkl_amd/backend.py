@@ -871,7 +871,7 @@ def kernel_ms_stats(which, reset=False):
 
 class WitnessError(ValueError):
     """a synthesis on the device met a value outside its decomposition range, a lookup input outside its table, a gather index outside
-    its table or a sort key beyond 62 bits (the layout's own assertions on the host path)"""
+    its table or a sort or arg-extremum key beyond 62 bits (the layout's own assertions on the host path)"""
 
 
 def witness_tile(columns, k, unit_rows, tiles, pairs, stream=None):

@@ -46,13 +46,19 @@
 //    r + (T - r^2 > r).  An operand beyond 62 bits, or T >= 2^62, is reported as the range failures below are ("reciprocal operand beyond
 //    62 bits", "square-root operand outside the exact range") and writes nothing.
 //
+//  * arg-extremum records (the index `argmax` / `argmin` claim before the sort that checks it, layouts.rs:5225-5293): count segments of n
+//    source cells, one destination cell each -- the smallest position of the greatest (least) signed value.  See wit_argext_wave_kernel: up
+//    to 64 sources a segment, whole segments side by side in a wave and cross-lane steps only; up to ARGEXT_CHUNK, a workgroup per segment;
+//    above, a workgroup per chunk into the plan's key scratch and a second launch over the slots.  A source beyond 62 bits is reported as
+//    the range failures below are ("arg-extremum key beyond 62 bits") and its segment's cell is not written.
+//
 // A value that does not fit its decomposition (|x| >= base^legs: the layout's "value exceeds the decomposition range") writes nothing
 // wrong silently, and neither does a lookup input outside its table (layouts.rs:5143-5222 `nonlinearity`; the layout's "lookup input
 // outside the table range"), and neither does a dividend of `div` beyond the range in which the integer quotient is the reference's f64
 // one (|s| >= 2^52: "rebase dividend outside the exact-division range"): the lane counts itself in status[0] and keeps the SMALLEST
 // (record, element) in status[1] -- vector atomics in plain C++, as the mock prover's kernels in vecops.hip -- and the host call
 // returns EZKL_ERR_INVALID naming the op.  Nothing traps.
-// The only device memory written is the destination columns, the plan's own scratch (inputs, outputs, sort keys) and the status words; the plan's
+// The only device memory written is the destination columns, the plan's own scratch (inputs, outputs, sort keys or arg-extremum slots) and the status words; the plan's
 // index pool, parameters, constants and lookup-table values are read-only after upload.
 #include "common.hpp"
 #include "witness_plan.hpp"
@@ -596,6 +602,127 @@ EZ_HD uint32_t wit_sort_padded(uint32_t n) {                              // the
     return P;
 }
 
+// ARGEXT.  A key is (signed value, position in the segment) with the value negated for argmin (|s| < 2^62: the negation fits), so that both
+// modes keep the GREATER value and, at equal values, the SMALLER position: a total order, the combine is associative and commutative, and any
+// reduction tree gives the host's answer.  A lane past a segment's end, and a source beyond 62 bits, hold the identity (INT64_MIN, 0xffffffff),
+// which no source that fits equals; `bad` -- some source of the segment did not fit -- is carried through the same reduction, so the one
+// lane that would store the segment's cell decides not to.  Three regimes by the segment length n: up to 64, 64 / P whole segments to a wave
+// (P = the next power of two), log2 P cross-lane steps, no LDS; up to ARGEXT_CHUNK, one workgroup per segment; above, one workgroup per chunk
+// into a 16-byte slot of the plan's key scratch (SortKey: v, tie = position, pad = bad), then one workgroup per segment over its slots.
+constexpr uint32_t ARGEXT_THREADS = 256, ARGEXT_NO_POS = 0xFFFFFFFFu;
+static_assert(ARGEXT_CHUNK % ARGEXT_THREADS == 0 && ARGEXT_THREADS % 64 == 0, "a chunk is whole rounds of a workgroup of whole waves");
+
+// (v, pos, bad) combined with the key (yv, ypos, ybad): the greater value, at equal values the smaller position; bad if either is.  (Three
+// scalars on purpose: a struct handed on by reference ends up in the lane's scratch memory.)
+EZ_D void wit_argext_take(int64_t& v, uint32_t& pos, uint32_t& bad, int64_t yv, uint32_t ypos, uint32_t ybad) {
+    const bool keep = v > yv || (v == yv && pos <= ypos);
+    v = keep ? v : yv;
+    pos = keep ? pos : ypos;
+    bad |= ybad;
+}
+// the key of source element e = seg * n + i of record `rec` (live: the element exists) combined into (v, pos, bad); reported when it does not fit
+EZ_D void wit_argext_load(const WitCols& cols, uint32_t k, const uint32_t* __restrict__ a, bool live, uint32_t e, uint32_t i, uint32_t mode, uint32_t rec,
+                          unsigned long long* status, int64_t& v, uint32_t& pos, uint32_t& bad) {
+    int64_t yv = INT64_MIN;
+    uint32_t ypos = ARGEXT_NO_POS;
+    bool fail = false;
+    if (live) {
+        bool neg, fits;
+        uint64_t mag;
+        wit_signed(ld_fe(wit_cell(cols, k, a[e])), neg, mag, fits);
+        fail = !fits;
+        const int64_t s = neg ? -(int64_t)mag : (int64_t)mag;
+        yv = fail ? INT64_MIN : mode ? -s : s;
+        ypos = fail ? ARGEXT_NO_POS : i;
+    }
+    wit_report(fail, rec, e, status);
+    wit_argext_take(v, pos, bad, yv, ypos, fail ? 1u : 0u);
+}
+// over aligned groups of `width` lanes (a power of two <= 64): every lane of a group ends with the group's key
+EZ_D void wit_argext_lanes(int64_t& v, uint32_t& pos, uint32_t& bad, uint32_t width) {
+    for (uint32_t off = width >> 1; off; off >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, (int)off), hi = (uint32_t)__shfl_xor((int)(uint32_t)((uint64_t)v >> 32), (int)off);
+        const uint32_t ypos = (uint32_t)__shfl_xor((int)pos, (int)off), ybad = (uint32_t)__shfl_xor((int)bad, (int)off);
+        wit_argext_take(v, pos, bad, (int64_t)((uint64_t)lo | ((uint64_t)hi << 32)), ypos, ybad);
+    }
+}
+// over the workgroup: waves, then the ARGEXT_THREADS / 64 partials through LDS; every lane ends with the workgroup's key
+EZ_D void wit_argext_group(int64_t& v, uint32_t& pos, uint32_t& bad, int64_t* part_v, uint32_t* part_pos, uint32_t* part_bad) {
+    wit_argext_lanes(v, pos, bad, 64);
+    if ((threadIdx.x & 63) == 0) {
+        part_v[threadIdx.x >> 6] = v;
+        part_pos[threadIdx.x >> 6] = pos;
+        part_bad[threadIdx.x >> 6] = bad;
+    }
+    __syncthreads();
+    v = part_v[0]; pos = part_pos[0]; bad = part_bad[0];
+#pragma unroll
+    for (uint32_t w = 1; w < ARGEXT_THREADS / 64; w++) wit_argext_take(v, pos, bad, part_v[w], part_pos[w], part_bad[w]);
+}
+// one lane stores a segment's cell unless a source of the segment did not fit
+EZ_D void wit_argext_store(const WitCols& cols, uint32_t k, const uint32_t* __restrict__ dst, uint32_t seg, bool mine, uint32_t pos, uint32_t bad, unsigned long long* status) {
+    uint32_t wrote = 0;
+    if (mine && !bad) {
+        st_fe(wit_cell(cols, k, dst[seg]), Fr::from_u64(pos));
+        wrote = 1;
+    }
+    wit_count(wrote, status);
+}
+
+// n <= 64: lane l of a wave holds element l % P of the wave's segment l / P; the grid is cdiv(n_segs, (ARGEXT_THREADS / 64) * (64 / P))
+__global__ __launch_bounds__(ARGEXT_THREADS) void wit_argext_wave_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* __restrict__ a,
+                                                                         uint32_t n_segs, uint32_t n, uint32_t P, uint32_t mode, uint32_t rec, unsigned long long* status) {
+    const uint32_t lane = threadIdx.x & 63, wave = blockIdx.x * (ARGEXT_THREADS / 64) + (threadIdx.x >> 6);
+    const uint32_t seg = wave * (64 / P) + lane / P, i = lane & (P - 1);
+    const bool live = seg < n_segs && i < n;                              // live: seg * n + i < count <= 2^28
+    int64_t v = INT64_MIN;
+    uint32_t pos = ARGEXT_NO_POS, bad = 0;
+    wit_argext_load(cols, k, a, live, seg * n + i, i, mode, rec, status, v, pos, bad);
+    wit_argext_lanes(v, pos, bad, P);
+    wit_argext_store(cols, k, dst, seg, live && i == 0, pos, bad, status);
+}
+// n > 64: workgroup b reduces chunk b % chunks -- elements [c * ARGEXT_CHUNK, + ARGEXT_CHUNK) below n -- of segment b / chunks; chunks == 1:
+// into the segment's cell, else into slot b of the scratch
+__global__ __launch_bounds__(ARGEXT_THREADS) void wit_argext_group_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* __restrict__ a,
+                                                                          uint32_t n, uint32_t chunks, uint32_t mode, uint32_t rec, SortKey* __restrict__ slots,
+                                                                          unsigned long long* status) {
+    __shared__ int64_t part_v[ARGEXT_THREADS / 64];
+    __shared__ uint32_t part_pos[ARGEXT_THREADS / 64], part_bad[ARGEXT_THREADS / 64];
+    const uint32_t seg = blockIdx.x / chunks, c = blockIdx.x - seg * chunks;
+    const uint32_t i0 = c * ARGEXT_CHUNK, i1 = n - i0 < ARGEXT_CHUNK ? n : i0 + ARGEXT_CHUNK;     // i0 < n: chunks = cdiv(n, ARGEXT_CHUNK)
+    int64_t v = INT64_MIN;
+    uint32_t pos = ARGEXT_NO_POS, bad = 0;
+    for (uint32_t base = i0; base < i1; base += ARGEXT_THREADS) {          // the same rounds for every lane: wit_report ballots
+        const uint32_t i = base + threadIdx.x;
+        wit_argext_load(cols, k, a, i < i1, seg * n + i, i, mode, rec, status, v, pos, bad);
+    }
+    wit_argext_group(v, pos, bad, part_v, part_pos, part_bad);
+    if (chunks > 1) {
+        if (threadIdx.x == 0) slots[blockIdx.x] = SortKey{v, pos, bad};
+        return;
+    }
+    wit_argext_store(cols, k, dst, seg, threadIdx.x == 0, pos, bad, status);
+}
+// the slots of segment blockIdx.x -> its cell
+__global__ __launch_bounds__(ARGEXT_THREADS) void wit_argext_final_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const SortKey* __restrict__ slots,
+                                                                          uint32_t chunks, unsigned long long* status) {
+    __shared__ int64_t part_v[ARGEXT_THREADS / 64];
+    __shared__ uint32_t part_pos[ARGEXT_THREADS / 64], part_bad[ARGEXT_THREADS / 64];
+    const SortKey* s = slots + (size_t)blockIdx.x * chunks;
+    int64_t v = INT64_MIN;
+    uint32_t pos = ARGEXT_NO_POS, bad = 0;
+    for (uint32_t j = threadIdx.x; j < chunks; j += ARGEXT_THREADS) {
+        const SortKey y = s[j];
+        wit_argext_take(v, pos, bad, y.v, y.tie, y.pad);
+    }
+    wit_argext_group(v, pos, bad, part_v, part_pos, part_bad);
+    wit_argext_store(cols, k, dst, blockIdx.x, threadIdx.x == 0, pos, bad, status);
+}
+EZ_HD size_t wit_argext_slots(uint32_t n_segs, uint32_t n) {               // the scratch slots of a record: none unless a segment has several chunks
+    const uint32_t chunks = (n + ARGEXT_CHUNK - 1) / ARGEXT_CHUNK;
+    return chunks > 1 ? (size_t)n_segs * chunks : 0;
+}
+
 struct DevPlan {
     Plan host;                      // the validated blob: records, outputs and counts drive the launches; pool / params / consts are
                                     // released once they are on the device (n_params is kept for ezkl_hip_witness_plan_info)
@@ -609,7 +736,8 @@ struct DevPlan {
     int64_t* inputs = nullptr;
     fe_t* outs = nullptr;
     unsigned long long* status = nullptr;
-    SortKey* sort_keys = nullptr;   // the padded keys of the largest sort record with segments above SORT_TILE (one slot when there is none)
+    SortKey* sort_keys = nullptr;   // the padded keys of the largest sort record with segments above SORT_TILE, or the chunk slots of the
+                                    // largest arg-extremum record with segments above ARGEXT_CHUNK, whichever is more (one slot when there is none)
     Ctx* ctx = nullptr;
     // a plan with phases: the last phase that ran to its end since the last phase 0 with no earlier phase started again since, and the
     // columns it ran on
@@ -661,6 +789,23 @@ uint32_t launch_sort(hipStream_t st, const WitCols& cols, uint32_t k, const DevP
                        r.p1, p->status);
     return launches;
 }
+// an ARGEXT record: one launch up to ARGEXT_CHUNK sources a segment, else the chunks into the scratch and the slots into the cells.  -> the
+// number of launches
+uint32_t launch_argext(hipStream_t st, const WitCols& cols, uint32_t k, const DevPlan* p, const Rec& r, uint32_t ri) {
+    const uint32_t n = r.p0, n_segs = r.count;                           // n_segs * n <= 2^28, checked on upload
+    if (n <= 64) {
+        const uint32_t P = wit_sort_padded(n);
+        hipLaunchKernelGGL(wit_argext_wave_kernel, dim3(cdiv(n_segs, (ARGEXT_THREADS / 64) * (64 / P))), dim3(ARGEXT_THREADS), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, n_segs,
+                           n, P, r.p1, ri, p->status);
+        return 1;
+    }
+    const uint32_t chunks = cdiv(n, ARGEXT_CHUNK);                       // n_segs * chunks <= 2^28 / ARGEXT_CHUNK + n_segs
+    hipLaunchKernelGGL(wit_argext_group_kernel, dim3(n_segs * chunks), dim3(ARGEXT_THREADS), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, n, chunks, r.p1, ri, p->sort_keys,
+                       p->status);
+    if (chunks == 1) return 1;
+    hipLaunchKernelGGL(wit_argext_final_kernel, dim3(n_segs), dim3(ARGEXT_THREADS), 0, st, cols, k, p->pool + r.dst, (const SortKey*)p->sort_keys, chunks, p->status);
+    return 2;
+}
 }  // namespace
 }  // namespace ezkl
 
@@ -694,6 +839,8 @@ int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out
     for (const Rec& r : h.recs)
         if ((r.kind == SORT || r.kind == ARGSORT) && wit_sort_padded(r.p0) > SORT_TILE)
             sort_bytes = std::max(sort_bytes, (size_t)(r.count / r.p0) * wit_sort_padded(r.p0) * sizeof(SortKey));
+        else if (r.kind == ARGEXT)                                // the records run one after another on the stream: they share the scratch
+            sort_bytes = std::max(sort_bytes, wit_argext_slots(r.count, r.p0) * sizeof(SortKey));
     struct Up { void** dev; const void* src; size_t bytes; };
     const Up ups[] = {{(void**)&p->pool, h.pool.data(), h.pool.size() * 4},       {(void**)&p->outputs, h.outputs.data(), h.outputs.size() * 4},
                       {(void**)&p->params, h.params.data(), h.params.size() * 8}, {(void**)&p->consts, consts.data(), consts.size() * 32},
@@ -832,6 +979,7 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
             break;
         case SORT: launches += launch_sort<SORT>(st, cols, k, p, r, (uint32_t)ri) - 1; break;
         case ARGSORT: launches += launch_sort<ARGSORT>(st, cols, k, p, r, (uint32_t)ri) - 1; break;
+        case ARGEXT: launches += launch_argext(st, cols, k, p, r, (uint32_t)ri) - 1; break;
         case MATMUL: {
             const uint32_t m = r.count / r.p1;
             hipLaunchKernelGGL(wit_matmul_kernel, dim3(cdiv(m, MM_TILE) * cdiv(r.p1, MM_TILE)), dim3(MM_TILE * MM_TILE), 0, st, cols, k, p->pool + r.dst, p->pool + r.a,
@@ -874,6 +1022,7 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
                            : kind == SORT || kind == ARGSORT ? "witness: sort key beyond 62 bits ("
                            : kind == RECIP                ? "witness: reciprocal operand beyond 62 bits ("
                            : kind == ISQRT                ? "witness: square-root operand outside the exact range ("
+                           : kind == ARGEXT               ? "witness: arg-extremum key beyond 62 bits ("
                                                           : "witness: value exceeds the decomposition range (";
         t_wit_error = std::string(what) + kind_name(kind) + " record " + std::to_string(ri) +
                       ", element " + std::to_string(el) + "; " + std::to_string(dev_status[0]) + (kind == MATMUL ? " operand reads in all)" : " cells in all)");

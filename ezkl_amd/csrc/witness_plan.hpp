@@ -52,6 +52,14 @@
 // An ISQRT record (the claimed root of `sqrt`, layouts.rs:408-459): a = source cell, b = 0, p0 = input scale >= 1 ("zero square-root
 // scale"), p1 = 0 ("a square-root record with a second parameter").  With T = x * p0: T <= 0 -> 0; else r = floor(sqrt(T)), r + (T - r * r > r),
 // the integer nearest to sqrt(T).  |x| >= 2^62 or T >= 2^62 is a run-time failure of the lane ("square-root operand outside the exact range").
+// Kind 26 (KINDS_END) is unassigned as 16 and 23 are; ARGEXT is 27 and KINDS_LIMIT follows it.
+// An ARGEXT record (the claimed index of `argmax` / `argmin`, layouts.rs:5225-5293, which the prover states BEFORE the sort that checks it):
+// count = the number of segments = the number of destination cells dst[s], p0 = n >= 1 the segment length, p1 = mode (0: argmax, 1: argmin),
+// a = count * n source cells, segment-major and dense, b unused and zero.  p0 == 0, p1 > 1, count * p0 > 2^28 or an array past the pool:
+// "bad arg-extremum shape".  dst[s] gets the SMALLEST position j in [0, n) whose signed value is the greatest (mode 0) or the least (mode 1)
+// of the cells a[s * n .. + n): the reference's max_by_key((value, -idx)) / min_by_key((value, idx)), the one claim the gates accept.  A
+// source with |s| >= 2^62 is a run-time failure of the lane ("arg-extremum key beyond 62 bits"), element = its place in a; its segment's
+// cell is not written.  ARGEXT_CHUNK is the number of sources one workgroup of csrc/witness.hip reduces.
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -63,13 +71,14 @@ namespace ezkl {
 namespace wplan {
 
 constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64, MAX_PHASES = 3, MAX_CHALLENGES = 64, SORT_TILE = 2048,
-                   MAX_SORT_COUNT = 1u << 28;
+                   MAX_SORT_COUNT = 1u << 28, ARGEXT_CHUNK = 4096;
 enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC, UNASSIGNED, SUMACC, PRODACC, GATHER, CLAMP, SORT, ARGSORT, N_KINDS,     // 16 names nothing: refused as unknown
-                       RECIP = 24, ISQRT = 25, KINDS_END };                        // N_KINDS ends KIND_NAMES and, as a kind (23), names nothing either
+                       RECIP = 24, ISQRT = 25, KINDS_END,                         // N_KINDS ends KIND_NAMES and, as a kind (23), names nothing either
+                       ARGEXT = 27, KINDS_LIMIT };                                 // KINDS_END (26) names nothing either; KINDS_LIMIT is the first kind past them all
 static const char* const KIND_NAMES[N_KINDS] = {"copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot",
                                                 "nonlinearity", "nonlinearity_index", "matmul", "rlc", "div", "?", "sum", "prod", "gather", "clamp", "sort", "argsort"};
 // the name a message gives a kind: KIND_NAMES up to ARGSORT, the later kinds by hand, "?" for a kind that names nothing
-inline const char* kind_name(uint32_t kind) { return kind < N_KINDS ? KIND_NAMES[kind] : kind == RECIP ? "recip" : kind == ISQRT ? "sqrt" : "?"; }
+inline const char* kind_name(uint32_t kind) { return kind < N_KINDS ? KIND_NAMES[kind] : kind == RECIP ? "recip" : kind == ISQRT ? "sqrt" : kind == ARGEXT ? "argext" : "?"; }
 struct Rec {
     uint32_t kind, count, p0, p1, dst, a, b, phase;
 };
@@ -169,7 +178,7 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
     uint32_t last_phase = 0;
     for (size_t ri = 0; ri < out.recs.size(); ri++) {
         const Rec& r = out.recs[ri];
-        if (r.kind >= KINDS_END || r.kind == N_KINDS || r.kind == UNASSIGNED) return at_rec(ri, r.kind, "unknown kind");
+        if (r.kind >= KINDS_LIMIT || r.kind == KINDS_END || r.kind == N_KINDS || r.kind == UNASSIGNED) return at_rec(ri, r.kind, "unknown kind");
         if (r.count == 0) return at_rec(ri, r.kind, "empty");
         if (r.phase >= n_phases) return at_rec(ri, r.kind, "phase out of range");
         if (r.phase < last_phase) return at_rec(ri, r.kind, "phases decrease");
@@ -239,6 +248,11 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
             a_cells = true;
             if (r.p0 == 0) return at_rec(ri, r.kind, "zero square-root scale");
             if (r.p1 != 0) return at_rec(ri, r.kind, "a square-root record with a second parameter");
+            break;
+        case ARGEXT:                                     // p0 = segment length, p1 = mode, count = segments = destination cells
+            if (r.p0 == 0 || r.p1 > 1 || (uint64_t)r.count * r.p0 > MAX_SORT_COUNT || !span_ok(r.dst, r.count) || !span_ok(r.a, (uint64_t)r.count * r.p0))
+                return at_rec(ri, r.kind, "bad arg-extremum shape");
+            n_a = (uint64_t)r.count * r.p0; a_cells = true;
             break;
         case DOT:
             if (r.p0 == 0 || r.p1 == 0 || (uint64_t)r.count * r.p1 > P.size() || (uint64_t)r.count * r.p1 * r.p0 > P.size()) return at_rec(ri, r.kind, "bad dot shape");

@@ -37,6 +37,7 @@ SORT_ERROR = "sort key beyond 62 bits"
 SORT_MODES = ("unsorted", "smallest_index_first", "largest_index_first")       # layouts.rs:1124-1131 SortCollisionMode
 RECIP_ERROR = "reciprocal operand beyond 62 bits"
 SQRT_ERROR = "square-root operand outside the exact range"
+ARGEXT_ERROR = "arg-extremum key beyond 62 bits"
 
 
 def clamped(s, lo, hi):
@@ -409,6 +410,7 @@ class BaseRegion(Region):
         self.const_order = []                          # (value, advice cell) in order of first use: the floor planner's fixed cells
         self.decomp = None                             # RegionCtx's (base, legs), region.rs `base()` / `legs()`: set by the circuit's layout
         self.shuffle_index = 0                         # region.shuffle_index(): the constant that keeps the sorts of a region apart in the argument
+        self.dynamic_lookup_index = 0                  # region.dynamic_lookup_index(): the same for the `select`s of a region
 
     def cell_of(self, var, linear):
         x, y, z = var.cartesian_coord(linear)
@@ -715,10 +717,10 @@ class BaseRegion(Region):
         self.dyn = dyn + len(table_rows)
         self.dyn_table = (table_rows, placed)          # the table just written, cell by cell: what `row_at` picks of it read
         vars3 = [self.inputs[0], self.inputs[1], self.output]
+        self.dyn_picks = []                            # the input side as placed, pick by pick: what `select` returns of it
         for j, tri in enumerate(picks):
             x, y, z = self.inputs[0].cartesian_coord(self.linear + j)
-            for t in range(3):
-                self.put(vars3[t], self.linear + j, free(tri[t]))
+            self.dyn_picks.append([self.put(vars3[t], self.linear + j, free(tri[t])) for t in range(3)])
             self.enable(input_sels[(0, (x, y))], z)
         self.increment(len(picks))
         return placed
@@ -876,6 +878,94 @@ class BaseRegion(Region):
         squared = self.pairwise(flat, flat, EC.MULT)
         sum_squared = [self.sum(squared[i * length:(i + 1) * length]) for i in range(len(rows))]
         return self.div(sum_squared, length)
+
+    def _arg_extremum(self, vals, mode):
+        """the one data-dependent step of `argmax` / `argmin`: the SMALLEST position whose signed value is the greatest (mode "max") or the
+        least ("min") -- the reference's `max_by_key((value, -idx))` / `min_by_key((value, idx))` (layouts.rs:5231-5237, :5265-5271), and the
+        only claim the gates accept: the sort that checks it is `largest_index_first` with the claim held to its LAST index for the maximum,
+        `smallest_index_first` with the claim held to its FIRST for the minimum.  (A recording region overrides this, as it overrides
+        `_sorted`.)"""
+        assert mode in ("max", "min"), mode
+        s = [signed(v.v) for v in vals]
+        for x in s:
+            assert abs(x) < 1 << 62, ARGEXT_ERROR
+        return s.index(max(s) if mode == "max" else min(s))
+
+    def select(self, vals, index):
+        """layouts.rs:1363-1396 `select`: the element of `vals` the cell `index` names, through a dynamic lookup (:1483-1581) -- table side
+        (the position as a constant, vals_j, the region's dynamic-lookup index), input side (the index cell, the claimed element, the same
+        constant).  -> the claimed element where the argument reads it"""
+        lookup_index = Val(self.dynamic_lookup_index, const=True)
+        table_rows = [(Val(j, const=True), v, lookup_index) for j, v in enumerate(vals)]
+        row = self.row_at(table_rows, index)
+        pick = (Val(row[0].v, index.cell), Val(row[1].v), lookup_index)
+        self._lookup_any(self.base.dynamic_table_selectors[0], self.base.dynamic_lookup_selectors, table_rows, [pick], constrained=True)
+        self.dynamic_lookup_index += 1
+        return self.dyn_picks[0][1]
+
+    def _arg(self, vals, mode):
+        vals = list(vals)
+        claim = self.assign(self.inputs[1], [Val(self._arg_extremum(vals, mode))])      # "this is safe because we later constrain it"
+        self.increment(1)
+        claimed_val = self.select(vals, claim[0])
+        srt, idx = self.sort_ascending(vals, "largest_index_first" if mode == "max" else "smallest_index_first")
+        at = -1 if mode == "max" else 0
+        self.enforce_equality([claimed_val], [srt[at]])
+        self.enforce_equality(claim, [idx[at]])
+        return claim[0]
+
+    def argmax(self, vals):
+        """layouts.rs:5225-5256: the claimed index on the second input VarTensor, `select` of it, a `largest_index_first` sort, and the
+        claimed element and index held to the sort's last value and last index"""
+        return self._arg(vals, "max")
+
+    def argmin(self, vals):
+        """layouts.rs:5259-5293: as `argmax` with a `smallest_index_first` sort and its first value and first index"""
+        return self._arg(vals, "min")
+
+    def argmax_axes(self, rows):
+        """layouts.rs:2781-2856 `argmax_axes` over a list of equal-length rows (the slices along the axis)"""
+        return [self.argmax(row) for row in rows]
+
+    def argmin_axes(self, rows):
+        """layouts.rs:2859-2905 `argmin_axes` over a list of equal-length rows"""
+        return [self.argmin(row) for row in rows]
+
+    @staticmethod
+    def _padded(image, channels, height, width, padding):
+        """`Tensor::pad` over the two spatial axes of a canonical (batch 1) NCHW image given row-major: zeros as constants, padding =
+        ((top, bottom), (left, right)) -> (the padded image as [channel][row][column], its height, its width)"""
+        assert len(image) == channels * height * width
+        (top, bottom), (left, right) = padding
+        zero = Val(0, const=True)
+        H, W = top + height + bottom, left + width + right
+        out = [[[image[(c * height + i - top) * width + j - left] if top <= i < top + height and left <= j < left + width else zero
+                 for j in range(W)] for i in range(H)] for c in range(channels)]
+        return out, H, W
+
+    def max_pool(self, image, channels, height, width, padding, stride, pool):
+        """layouts.rs:4008-4087 on a canonical NCHW image of batch 1: zero padding, then one `max` per output position in the order of the
+        cartesian product (channel, row, column) -> the pooled image, row-major"""
+        img, H, W = self._padded(image, channels, height, width, padding)
+        slides = [(H - pool[0]) // stride[0] + 1, (W - pool[1]) // stride[1] + 1]
+        return [self.max([img[c][i * stride[0] + a][j * stride[1] + b] for a in range(pool[0]) for b in range(pool[1])])
+                for c in range(channels) for i in range(slides[0]) for j in range(slides[1])]
+
+    def sumpool(self, image, channels, height, width, padding, stride, kernel, normalized):
+        """layouts.rs:3907-3980 on a canonical NCHW image of batch 1: the unit kernel is assigned once on the second input VarTensor, every
+        channel is convolved with it (`conv`, :4499-4661, without a bias: one `dot` of each window with the kernel cells) and the sums are
+        divided by the kernel size when `normalized` -> the pooled image, row-major"""
+        img, H, W = self._padded(image, channels, height, width, padding)
+        unit = self.assign(self.inputs[1], [Val(1, const=True)] * (kernel[0] * kernel[1]))
+        self.increment(len(unit))
+        slides = [(H - kernel[0]) // stride[0] + 1, (W - kernel[1]) // stride[1] + 1]
+        out = []
+        for c in range(channels):
+            for i in range(slides[0]):
+                for j in range(slides[1]):
+                    out.append(self.dot([img[c][i * stride[0] + a][j * stride[1] + b] for a in range(kernel[0]) for b in range(kernel[1])], unit))
+                    self.flush()
+        return self.div(out, kernel[0] * kernel[1]) if normalized else out
 
     def einsum(self, ein, A, B, challenges=None):
         """assign_einsum of an EinsumMatmulCircuit laid over this region's configuration (EinsumMatmulCircuit.over), in this region, at
@@ -1258,6 +1348,98 @@ class NormCircuit(LayoutCircuit):
         assert len(x) == self.n_inputs
         reg = BaseRegion(self.gc, witness)
         outs = self.layout(reg, [Val(int(v) % R) for v in x], Val)
+        reg.finish(self.gc.const_cols)
+        self.outputs = [v.v for v in outs]
+        return reg
+
+
+class PoolClassifierCircuit(LayoutCircuit):
+    """a LeNet-shaped classifier on a private `image` x `image` picture: a convolution with bias (one `dot` per output and a bias addition,
+    as ConvMnistCircuit lays it out), `relu`, a pooling layer -- pool = "max": `max_pool`, "sum": `sumpool`, normalized --, a linear layer
+    with bias and `argmax` of its logits; instance = the logits, then the class index.  The op sequence is stated once (`layout`), so that
+    witness_plan.record_plan can run it on symbols.  The settings carry the range checks of the decomposition, (-1, 1) and (0, base - 1),
+    the (0, 1) check of the indexed sort of `argmax`, the shuffle argument of the sorts and the dynamic lookup of `select`.  Parameters
+    are seeded synthetic integers, as ConvMnistCircuit's are."""
+
+    def __init__(self, logrows, num_inner_cols, capacity, image=8, kernel=3, out_channels=2, stride=1, pool_size=2, pool_stride=2, classes=4,
+                 pool="max", decomp_base=128, decomp_legs=3, seed=0):
+        assert pool in ("max", "sum"), pool
+        self.k, self.w, self.capacity = logrows, num_inner_cols, capacity
+        self.image, self.kernel, self.oc, self.stride, self.classes = image, kernel, out_channels, stride, classes
+        self.pool, self.pool_size, self.pool_stride, self.seed = pool, pool_size, pool_stride, seed
+        self.base, self.legs = decomp_base, decomp_legs
+        self.slides = (image - kernel) // stride + 1
+        self.pooled = (self.slides - pool_size) // pool_stride + 1
+        self.n_inputs = image * image
+        self.length = out_channels * self.pooled * self.pooled
+        rng = np.random.default_rng(seed)
+        self.kernels = rng.integers(-4, 5, (out_channels, kernel, kernel))
+        self.conv_bias = rng.integers(-8, 9, out_channels)
+        self.fc_w = rng.integers(-4, 5, (classes, self.length))
+        self.fc_b = rng.integers(-16, 17, classes)
+        windows = self.length if pool == "max" and pool_size > 1 else 0        # one sort per window; a `max` of one element sorts nothing
+        sort_rows = windows * pool_size * pool_size + (classes if classes > 1 else 0)
+        self.settings = EC.GraphSettings(logrows, num_inner_cols, capacity, total_const_size=16, required_range_checks=[(-1, 1), (0, decomp_base - 1), (0, 1)],
+                                         model_instance_shapes=[[1, classes + 1]], total_dynamic_col_size=classes, num_dynamic_lookups=1,
+                                         total_shuffle_col_size=max(sort_rows, 1), num_shuffles=windows + 1)
+        self.gc = EC.GraphConfig(self.settings)
+
+    def model(self, img):
+        """the integer forward pass the circuit proves: the logits, then the first index of their maximum"""
+        img = np.asarray(img, np.int64).reshape(self.image, self.image)
+        s, K, st, q, P, ps = self.slides, self.kernel, self.stride, self.pooled, self.pool_size, self.pool_stride
+        conv = np.array([[[max(int((img[i * st:i * st + K, j * st:j * st + K] * self.kernels[o]).sum()) + int(self.conv_bias[o]), 0)
+                           for j in range(s)] for i in range(s)] for o in range(self.oc)])
+        win = lambda o, i, j: conv[o, i * ps:i * ps + P, j * ps:j * ps + P]
+        if self.pool == "max":
+            act = [int(win(o, i, j).max()) for o in range(self.oc) for i in range(q) for j in range(q)]
+        else:
+            act = [round_div(int(win(o, i, j).sum()), P * P) for o in range(self.oc) for i in range(q) for j in range(q)]
+        logits = [int(v) for v in self.fc_w @ np.array(act, np.int64) + self.fc_b]
+        return logits + [max(range(len(logits)), key=lambda j: (logits[j], -j))]
+
+    def layout(self, reg, inputs, param):
+        """inputs: the image, row-major, as Vals; param(v) -> the Val of a circuit parameter (asked for in a fixed order: kernels, then per
+        output its conv bias, the linear layer's rows, its biases)"""
+        reg.decomp = (self.base, self.legs)
+        s, K, st = self.slides, self.kernel, self.stride
+        ker = reg.assign(reg.inputs[0], [param(v) for v in self.kernels.reshape(-1)])
+        im = reg.assign(reg.inputs[1], inputs)
+        reg.increment(max(len(ker), len(im)))
+        ker = [ker[o * K * K:(o + 1) * K * K] for o in range(self.oc)]
+        vals = []
+        for o in range(self.oc):
+            for i in range(s):
+                for j in range(s):
+                    patch = [im[(i * st + a) * self.image + j * st + b] for a in range(K) for b in range(K)]
+                    res = reg.dot(patch, ker[o])
+                    res = reg.pairwise([res], [param(self.conv_bias[o])], EC.ADD)
+                    reg.flush()
+                    vals.append(res[0])
+        vals = reg.relu(vals, self.base, self.legs)
+        geometry = (self.oc, s, s, ((0, 0), (0, 0)), (self.pool_stride,) * 2, (self.pool_size,) * 2)
+        vals = reg.max_pool(vals, *geometry) if self.pool == "max" else reg.sumpool(vals, *geometry, True)
+        logits = [reg.dot([param(v) for v in row], vals) for row in self.fc_w]
+        logits = reg.pairwise(logits, [param(v) for v in self.fc_b], EC.ADD)
+        outs = logits + [reg.argmax(logits)]
+        reg.constrain_instance(outs, self.gc.instance)
+        return outs
+
+    def plan_identity(self):
+        shape = [self.k, self.w, self.image, self.kernel, self.oc, self.stride, self.pool_size, self.pool_stride, self.classes,
+                 int(self.pool == "max"), self.base, self.legs, self.gc.advices[0].num_blocks()]
+        return b"".join(np.asarray(a, np.int64).tobytes() for a in (shape, self.kernels, self.conv_bias, self.fc_w, self.fc_b))
+
+    def fresh(self):
+        """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
+        return PoolClassifierCircuit(self.k, self.w, self.capacity, self.image, self.kernel, self.oc, self.stride, self.pool_size, self.pool_stride,
+                                     self.classes, self.pool, self.base, self.legs, self.seed)
+
+    def synthesize(self, img, witness=True):
+        reg = BaseRegion(self.gc, witness)
+        img = np.asarray(img, np.int64).reshape(-1)
+        assert len(img) == self.n_inputs
+        outs = self.layout(reg, [Val(int(v) % R) for v in img], lambda v: Val(int(v) % R))
         reg.finish(self.gc.const_cols)
         self.outputs = [v.v for v in outs]
         return reg

@@ -1,5 +1,5 @@
 """Witness plans: the layout of an MlpCircuit, a ConvMnistCircuit, an EinsumMatmulCircuit, a SumProdLayoutCircuit, a SortTopkCircuit, a
-NormCircuit or the TransformerSurrogateCircuit's unit recorded ONCE, replayed for every proof.
+NormCircuit, a PoolClassifierCircuit or the TransformerSurrogateCircuit's unit recorded ONCE, replayed for every proof.
 
 Which advice cell holds which value depends only on the circuit (BaseRegion places cells from the linear coordinate, the duplicated rows
 of `dot` from the block geometry; constants and the circuit's parameters are the same for every input), so `record_plan` runs one
@@ -24,7 +24,9 @@ the dynamic table in every other one; `shuffle` in a data-dependent order is ref
 for the claimed indices; everything around it is records of the other kinds), and `recip` / `sqrt` with what is built on them (`rsqrt`,
 `percent`, `softmax`, `mean_of_squares`): the claimed reciprocal is a RECIP element, the claimed root an ISQRT element
 (`ezkl_layout.recip_claim` / `sqrt_claim`, the two data-dependent steps), the masks, products, distances and comparisons of
-`optimum_convex_function` around them are records of the other kinds, `max` is a sort and `exp` a static lookup.
+`optimum_convex_function` around them are records of the other kinds, `max` is a sort and `exp` a static lookup.  `argmax` / `argmin`
+claim their index BEFORE the sort that checks it (`BaseRegion._arg_extremum`, the one data-dependent step): the claim is one segment of an
+ARGEXT record, the `select` around it a gather, the rest a sort; `max_pool` is a `max` per window and `sumpool` a `dot` per window plus `div`.
 The MLP recorder keeps refusing them by name.  The TransformerSurrogateCircuit lays its einsum over its own configuration
 (`BaseRegion.einsum`): it is recorded on a PhasedLookupRecordingRegion -- the lookup region with the einsum region's `put_cell`, matmul
 record, running values and phase bookkeeping -- into a TWO-phase plan of the unit's rows; the tiling is the device's
@@ -90,6 +92,14 @@ A record of an element-wise kind has `count` destination cells pool[dst + i], pr
            the integer nearest to sqrt(T) (ezkl_layout.sqrt_claim).  |x| >= 2^62 or T >= 2^62 is the run-time failure "square-root operand
            outside the exact range", reported like the decomposition-range failure
 
+    (kind 26 is unassigned as 16 and 23 are; the kind below is 27)
+    ARGEXT count segments of p0 = n >= 1 source cells and as many destination cells pool[dst + s], p1 = mode (0: argmax, 1: argmin), a = the
+           count * n source cells, segment-major and dense, b = 0; count * n <= 2^28.  Destination s gets the SMALLEST position j in [0, n)
+           whose signed value is the greatest (mode 0) or the least (mode 1) of the cells pool[a + s * n .. + n): the claimed index of
+           `argmax` / `argmin` (BaseRegion._arg_extremum, layouts.rs:5225-5293), the one claim the gates accept.  A source with |s| >= 2^62 is
+           the run-time failure "arg-extremum key beyond 62 bits", reported like the decomposition-range failure with element = its place in
+           a; on the device its segment's cell is not written.  ARGEXT_CHUNK is the number of sources one workgroup reduces
+
 PHASES.  A circuit with second-phase advice (the Freivalds einsum) has columns that depend on challenges squeezed after the first-phase
 commitments: its plan has n_phases = 2, and every record carries the phase whose run replays it.  Phases are non-decreasing along the
 record list; a column belongs to the phase of the records that write it (never to two; a column no record writes: phase 0); INPUT and
@@ -118,6 +128,7 @@ equality tests of tests/test_witness_plan_cpu.py fail loudly -- an assert or a P
                               (`signed`: `v if v < R // 2 else v - R`, as above: the symbol IS the signed value)
     _sorted                   overridden: `assert abs(s) < 1 << 62` is the run-time check of SORT / ARGSORT
     row_at                    overridden: `assert 0 <= signed(index.v) < len(table_rows)` is the run-time check of GATHER
+    _arg_extremum             overridden: `assert abs(x) < 1 << 62` is the run-time check of ARGEXT
     equals_zero               `pow(v, -1, R) if v else 0`   (the truth value of a cell symbol is True: INVZ covers both branches)
     div (round_div)           `mag = abs(s)`, `assert mag < 1 << 52` (recorded as the run-time check), `((s > 0) - (s < 0)) * ((mag + d // 2) // d)`
     nonlinearity              `assert table.range[0] <= signed(v) <= table.range[1]` (recorded as the run-time check), `table.f(signed(v)) % R`,
@@ -143,10 +154,13 @@ SUMACC, PRODACC, GATHER, CLAMP = range(17, 21)
 SORT, ARGSORT = 21, 22
 UNASSIGNED_2 = 23                                  # the kind after ARGSORT names nothing either: N_KINDS of csrc/witness_plan.hpp, the end of its name table
 RECIP, ISQRT = 24, 25
+UNASSIGNED_3 = 26                                  # the kind after ISQRT names nothing either: KINDS_END of csrc/witness_plan.hpp
+ARGEXT = 27
 KIND_NAMES = ["copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot", "nonlinearity", "nonlinearity_index", "matmul", "rlc",
               "div", "?", "sum", "prod", "gather", "clamp"]
-_LATER_KIND_NAMES = {SORT: "sort", ARGSORT: "argsort", RECIP: "recip", ISQRT: "sqrt"}          # KIND_NAMES is the list of the kinds up to CLAMP, as tests pin it: later kinds are named here
+_LATER_KIND_NAMES = {SORT: "sort", ARGSORT: "argsort", RECIP: "recip", ISQRT: "sqrt", ARGEXT: "argext"}         # KIND_NAMES is the list of the kinds up to CLAMP, as tests pin it: later kinds are named here
 SORT_TILE, MAX_SORT_COUNT = 2048, 1 << 28                       # csrc/witness_plan.hpp: the keys one workgroup sorts in LDS; the most cells of a sort record
+ARGEXT_CHUNK = 4096                                             # csrc/witness_plan.hpp: the sources one workgroup of an arg-extremum reduces
 _HEADER = struct.Struct("<20I32s")
 RANGE_ERROR = "value exceeds the decomposition range"
 LOOKUP_ERROR = "lookup input outside the table range"
@@ -155,6 +169,7 @@ DIV_ERROR = EL.DIV_ERROR
 GATHER_ERROR = "gather index outside the table"
 SORT_ERROR = EL.SORT_ERROR
 RECIP_ERROR, SQRT_ERROR = EL.RECIP_ERROR, EL.SQRT_ERROR
+ARGEXT_ERROR = EL.ARGEXT_ERROR
 MAX_PHASES, MAX_CHALLENGES = 3, 64
 
 
@@ -342,6 +357,12 @@ class _SortedIndex(_Sorted):
     kind = ARGSORT
 
 
+class _ArgExt(_Sym):
+    """the position of the extremum of a segment (`BaseRegion._arg_extremum`): its source cells and its mode (0: max, 1: min)"""
+
+    def __init__(self, src, mode): self.src, self.mode = src, mode
+
+
 class _Cmp(_Sym):
     def __init__(self, a, op, c):
         assert c == 0
@@ -511,6 +532,15 @@ class _Records:
         for d in dst:
             self._claim(d, ri)
 
+    def emit_argext(self, mode, src, dst, phase=0):
+        """one segment of an ARGEXT record: the destination gets the position of the extremum of the cells src"""
+        for s in src:
+            if s not in self.rec_of:
+                raise PlanError("advice cell %d is read before it is written" % s)
+        ri = self._slot((ARGEXT, len(src), mode), src, phase)
+        self.recs[ri]["scans"].append((list(src), dst))
+        self._claim(dst, ri)
+
     def emit_scan(self, challenge, src, dst, phase):
         """one RLC scan: step t reads cell src[t] and writes cell dst[t]"""
         for s in src:
@@ -644,6 +674,8 @@ class RecordingRegion(EL.BaseRegion):
     sort_ascending, topk, _sorted = _refused("sort_ascending"), _refused("topk"), _refused("sort_ascending")
     recip, sqrt, rsqrt, max, min = _refused("recip"), _refused("sqrt"), _refused("rsqrt"), _refused("max"), _refused("min")
     percent, softmax, softmax_axes, mean_of_squares = _refused("percent"), _refused("softmax"), _refused("softmax_axes"), _refused("mean_of_squares")
+    select, argmax, argmin, argmax_axes, argmin_axes = _refused("select"), _refused("argmax"), _refused("argmin"), _refused("argmax_axes"), _refused("argmin_axes")
+    max_pool, sumpool, _arg_extremum = _refused("max_pool"), _refused("sumpool"), _refused("argmax / argmin")
     del _counted, _refused
 
 
@@ -755,6 +787,25 @@ class LookupRecordingRegion(RecordingRegion):
     rsqrt, max, min, percent = EL.BaseRegion.rsqrt, EL.BaseRegion.max, EL.BaseRegion.min, EL.BaseRegion.percent
     softmax, softmax_axes, mean_of_squares = EL.BaseRegion.softmax, EL.BaseRegion.softmax_axes, EL.BaseRegion.mean_of_squares
 
+    # ---- argmax / argmin and the pooling ops: BaseRegion's ops around `_arg_extremum` -------------------------------------------------------------
+    def argmax(self, vals):
+        self.n_ops += 1
+        return EL.BaseRegion.argmax(self, vals)
+
+    def argmin(self, vals):
+        self.n_ops += 1
+        return EL.BaseRegion.argmin(self, vals)
+
+    select, argmax_axes, argmin_axes = EL.BaseRegion.select, EL.BaseRegion.argmax_axes, EL.BaseRegion.argmin_axes
+    max_pool, sumpool = EL.BaseRegion.max_pool, EL.BaseRegion.sumpool
+
+    def _arg_extremum(self, vals, mode):
+        """BaseRegion._arg_extremum on symbols: one segment of an ARGEXT record over the cells the values are assigned in, emitted when the
+        layout places the claim"""
+        if not all(isinstance(v.v, _Cell) for v in vals):
+            raise PlanError("an arg-extremum over values that are not assigned cells")
+        return _ArgExt([v.v.idx for v in vals], {"max": 0, "min": 1}[mode])
+
     def _sorted(self, vals, mode):
         """BaseRegion._sorted on symbols: one segment over the cells the values are assigned in; its sorted values and their positions are
         collected as the layout places them and emitted, each list as one segment, once it is whole"""
@@ -797,6 +848,8 @@ class LookupRecordingRegion(RecordingRegion):
             placed[v.i] = dst
             if None not in placed:
                 self.out.emit_sort(v.kind, v.seg.mode, v.seg.src, placed)
+        elif isinstance(v, _ArgExt):
+            self.out.emit_argext(v.mode, v.src, dst)
         elif isinstance(v, _Clamp):
             if not -(1 << 31) <= v.lo <= v.hi < 1 << 31:
                 raise PlanError("clamp bounds beyond 32 bits")
@@ -1069,6 +1122,10 @@ class WitnessPlan:
                 src, dst = ([c for sc in rec["scans"] for c in sc[t]] for t in (0, 1))     # segment-major
                 n_cells += len(dst)
                 records.append([rec["kind"], len(dst), rec["p0"], rec["p1"], push(dst), push(src), 0, phase])
+            elif rec["kind"] == ARGEXT:
+                src, dst = [c for sc in rec["scans"] for c in sc[0]], [sc[1] for sc in rec["scans"]]     # segment-major
+                n_cells += len(dst)
+                records.append([ARGEXT, len(dst), rec["p0"], rec["p1"], push(dst), push(src), 0, phase])
             elif rec["kind"] == RECIP:
                 n_cells += len(rec["dst"])
                 records.append([RECIP, len(rec["dst"]), rec["p0"], rec["p1"], push(rec["dst"]), push(rec["a"]), rec["scalar"], phase])
@@ -1214,7 +1271,7 @@ def validate(plan):
     total = 0
     col_phase, last_phase = [None] * plan.n_advice, 0
     for ri, (kind, count, p0, p1, dst, a, b, phase) in enumerate(plan.records.tolist()):
-        if kind > ISQRT or kind in (UNASSIGNED, UNASSIGNED_2):
+        if kind > ARGEXT or kind in (UNASSIGNED, UNASSIGNED_2, UNASSIGNED_3):
             raise PlanError("witness plan: record %d: unknown kind %d" % (ri, kind))
         if count == 0:
             raise PlanError("witness plan: record %d is empty" % ri)
@@ -1254,6 +1311,12 @@ def validate(plan):
                 raise PlanError("witness plan: record %d (%s): bad sort shape" % (ri, kind_name(kind)))
             d = _span(plan, dst, count, "dst", ri)
             srcs = _span(plan, a, count, "a", ri)
+        elif kind == ARGEXT:                              # p0 = segment length, p1 = mode, count = segments = destination cells
+            if (p0 == 0 or p1 > 1 or count * p0 > MAX_SORT_COUNT or dst > len(plan.pool) or count > len(plan.pool) - dst
+                    or a > len(plan.pool) or count * p0 > len(plan.pool) - a):
+                raise PlanError("witness plan: record %d (%s): bad arg-extremum shape" % (ri, kind_name(kind)))
+            d = _span(plan, dst, count, "dst", ri)
+            srcs = _span(plan, a, count * p0, "a", ri)
         elif kind == DOT:
             w, ns = p0, p1
             if w == 0 or ns == 0 or count * ns * w > len(plan.pool):
@@ -1408,6 +1471,15 @@ def run_plan_host(plan, x, challenges=None, phase=None):
                         if ia != NONE:
                             acc = (acc + cells[ia]) % R if kind == SUMACC else acc * cells[ia] % R
                     cells[cell] = acc
+            continue
+        if kind == ARGEXT:
+            vals = [EL.signed(cells[c]) for c in P[a:a + count * p0]]
+            for e, sv in enumerate(vals):                  # every source a lane reads, the smallest failing element first
+                if abs(sv) >= 1 << 62:
+                    raise AssertionError("%s (%s record %d, element %d)" % (ARGEXT_ERROR, kind_name(kind), ri, e))
+            for g in range(count):
+                seg = vals[g * p0:(g + 1) * p0]
+                cells[P[dst + g]] = seg.index(min(seg) if p1 else max(seg))     # the first position that holds the extremum
             continue
         if kind in (SORT, ARGSORT):
             vals = [EL.signed(cells[c]) for c in P[a:a + count]]

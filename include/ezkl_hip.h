@@ -252,7 +252,7 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  * A PLAN is the layout recorded once per circuit (ezkl_amd/witness_plan.py; byte layout: csrc/witness_plan.hpp): a list of records, each a
  * batch of cell writes of one kind (copy, const, input, param, add / sub / mult, decompose hint, range-check index, inverse-or-zero, dot,
  * static-lookup output, static-lookup table-column index, integer matmul, random linear combination, rounded division by a constant, running sum, running product, gather, clamp, sort, argsort,
- * claimed reciprocal, claimed square root) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
+ * claimed reciprocal, claimed square root, claimed arg-extremum) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
  * of constants and -- header words 12 / 13 (n_tables, n_table_values; zero, as reserved words were, in a plan without lookups), after the
  * pool -- a directory of {lo (int32), n, col_size, offset} per static lookup table and the tables' values f(lo + i) as int64.  The version
  * word stays 1.  A lookup record names its source cells and a table: with s the signed value of the cell, the output kind writes
@@ -318,6 +318,16 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *   source cell, b = 0, p0 = input scale >= 1, p1 = 0.  With T = x * p0: T <= 0 -> 0; else r = floor(sqrt(T)), r + (T - r * r > r), the
  *   integer nearest to sqrt(T).  |x| >= 2^62 or T >= 2^62 is reported likewise ("square-root operand outside the exact range").  S = 0,
  *   S >= 2^62, a constant index past the constants, a zero scale or p1 != 0 on sqrt are refused on upload.
+ * ARGMAX AND ARGMIN (kind 27; kind 26 stays unassigned as 16 and 23 do, the version word stays 1 and every earlier blob keeps its bytes): the
+ *   index layouts.rs:5225-5293 `argmax` / `argmin` claim before the sort that checks it.  argext (27): count segments of p0 = n >= 1 source
+ *   cells and as many destination cells dst[s], p1 = mode (0: argmax, 1: argmin), a = the count * n source cells, segment-major and dense, b
+ *   unused; n = 0, a mode above 1, count * n > 2^28 or an array past the pool is refused on upload ("bad arg-extremum shape").  dst[s] gets the
+ *   SMALLEST position in [0, n) whose signed value is the greatest (least) of the cells a[s * n .. + n): max_by_key((value, -idx)) /
+ *   min_by_key((value, idx)) of the reference, the one claim its gates accept.  A source with |s| >= 2^62 is reported as a value beyond its
+ *   decomposition is ("arg-extremum key beyond 62 bits", element = its place in a) and its segment's cell is not written; the other segments
+ *   of the record are.  Segments of up to 64 sources are reduced side by side in a wave, up to 4096 by one workgroup each, in ONE launch; a
+ *   longer one takes two launches through the key scratch the plan owns (shared with the sort kinds, sized at upload to the larger need):
+ *   `launches` counts them all.
  * tile: a plan of a tiled circuit writes rows [0, U) of the block-0 and shared columns; the circuit is those U rows repeated T times down every
  *   column and copied into the columns of the other blocks.  For every pair, rows [t * U, (t + 1) * U) of column dst get rows [0, U) of column
  *   src: t = 0 .. T - 1 when dst != src, t = 1 .. T - 1 when dst == src.  Rows >= T * U and columns outside the pair list are left as they are.
