@@ -52,13 +52,21 @@
 //    above, a workgroup per chunk into the plan's key scratch and a second launch over the slots.  A source beyond 62 bits is reported as
 //    the range failures below are ("arg-extremum key beyond 62 bits") and its segment's cell is not written.
 //
+//  * scatter / complement / one-hot records (the three claims of the indexed family that depend on the data -- layouts.rs:2313-2379
+//    `scatter_elements`, :2213-2286 `get_missing_set_elements`, :1398-1442 `one_hot`): the scattered tensor by a last-writer-wins scatter --
+//    an atomicMax of the element number per target, so the result does not depend on scheduling --, the positions no index names by mark, scan
+//    and compact, the one-hot vector element-wise.  See wit_scatter_lds_kernel and wit_compl_lds_kernel: up to SCATTER_TILE destinations one
+//    workgroup in LDS, above it launches through the plan's scratch.  A scatter index outside its dimension is reported as the range failures
+//    below are ("scatter index outside the tensor") and its record writes none of its cells; a one-hot index outside the classes likewise
+//    ("one-hot index outside the classes"); a complement never fails.
+//
 // A value that does not fit its decomposition (|x| >= base^legs: the layout's "value exceeds the decomposition range") writes nothing
 // wrong silently, and neither does a lookup input outside its table (layouts.rs:5143-5222 `nonlinearity`; the layout's "lookup input
 // outside the table range"), and neither does a dividend of `div` beyond the range in which the integer quotient is the reference's f64
 // one (|s| >= 2^52: "rebase dividend outside the exact-division range"): the lane counts itself in status[0] and keeps the SMALLEST
 // (record, element) in status[1] -- vector atomics in plain C++, as the mock prover's kernels in vecops.hip -- and the host call
 // returns EZKL_ERR_INVALID naming the op.  Nothing traps.
-// The only device memory written is the destination columns, the plan's own scratch (inputs, outputs, sort keys or arg-extremum slots) and the status words; the plan's
+// The only device memory written is the destination columns, the plan's own scratch (inputs, outputs, sort keys, arg-extremum slots, scatter winners or complement flags) and the status words; the plan's
 // index pool, parameters, constants and lookup-table values are read-only after upload.
 #include "common.hpp"
 #include "witness_plan.hpp"
@@ -128,6 +136,7 @@ __global__ __launch_bounds__(256) void wit_elem_kernel(WitCols cols, uint32_t k,
     // TABLE / TBLIDX: the launcher has resolved the table directory -- ints = the table's values, p0 = lo (int32), p1 = n, p2 = col_size
     // GATHER: b = the table's cell list (pool + p0), p1 = its length
     // RECIP: p0 | p1 << 32 = S, p2 = the index in consts of the value a zero input takes; ISQRT: p0 = the input scale
+    // ONEHOT: b = the position each element stands for, p0 = the number of classes
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < count;
     bool fail = false;
@@ -200,6 +209,9 @@ __global__ __launch_bounds__(256) void wit_elem_kernel(WitCols cols, uint32_t k,
                     }
                     v = Fr::from_u64(r);
                 }
+            } else if (KIND == ONEHOT) {                                                      // 1 at the position the index names, 0 <= s < p0 classes
+                fail = !fits || neg || mag >= p0;
+                if (!fail) v = mag == b[i] ? Fr::one() : Fr::zero();
             } else if (KIND == RCIDX) {                                                       // |x - lo| // col_size
                 fail = !fits;                                                                 // |x| >= 2^62: as run_plan_host refuses it
                 const int64_t s = neg ? -(int64_t)mag : (int64_t)mag, diff = s - (int64_t)(int32_t)p0;
@@ -723,6 +735,186 @@ EZ_HD size_t wit_argext_slots(uint32_t n_segs, uint32_t n) {               // th
     return chunks > 1 ? (size_t)n_segs * chunks : 0;
 }
 
+// SCATTER.  Element j of the m validates its index s_j -- 0 <= s_j < extent, the test before anything is addressed -- and claims its target
+// t_j = s_j * mult + off_j < n (the upload check: off_j + (extent - 1) * mult < n) with atomicMax(winner[t_j], j + 1): the GREATEST element
+// on a target wins, whatever the order the lanes arrive in, which is `tensor::ops::scatter`'s "the later element overwrites".  Destination i
+// then gets the source cell of element winner[i] - 1, or base cell i where nobody claimed it (the winners start from 0 = nobody; m < 2^31:
+// a record's 3m words are in the pool).  A failing element is reported (every one is counted) and raises the record's own failure flag
+// -- in LDS or in the scratch, never status[0], which an earlier record may have set -- and the record then stores nothing.
+// n <= SCATTER_TILE: one workgroup, the winners in LDS.  Longer: fill, mark and store launches through the plan's scratch: word 0 the
+// failure count, the winners from word 4 on.
+constexpr uint32_t SCATTER_THREADS = 256, SCATTER_HEAD = 4;
+static_assert(SCATTER_TILE % SCATTER_THREADS == 0 && SCATTER_THREADS % 64 == 0 && (SCATTER_TILE / SCATTER_THREADS) <= 32,
+              "a tile is whole rounds of a workgroup of whole waves, and a lane's positions of a complement fit a 32-bit mask");
+
+// element j of record `rec` (live: it exists): reported when its index is outside [0, extent); else its winner word is raised to j + 1
+EZ_D bool wit_scatter_mark(const WitCols& cols, uint32_t k, const uint32_t* __restrict__ b, uint32_t m, uint32_t mult, bool live, uint32_t j, uint32_t* winner, uint32_t rec,
+                           unsigned long long* status) {
+    bool fail = false;
+    if (live) {
+        bool neg, fits;
+        uint64_t mag;
+        wit_signed(ld_fe(wit_cell(cols, k, b[1 + j])), neg, mag, fits);
+        fail = !fits || neg || mag >= b[0];
+        if (!fail) atomicMax(&winner[mag * mult + b[1 + 2 * (size_t)m + j]], j + 1);       // < n: checked on upload
+    }
+    wit_report(fail, rec, j, status);
+    return fail;
+}
+// destination i: the source of the greatest element that claimed it, else its base cell
+EZ_D void wit_scatter_put(const WitCols& cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* __restrict__ base, const uint32_t* __restrict__ b, uint32_t m,
+                          uint32_t i, uint32_t won) {
+    st_fe(wit_cell(cols, k, dst[i]), ld_fe(wit_cell(cols, k, won ? b[1 + m + (won - 1)] : base[i])));
+}
+__global__ __launch_bounds__(SCATTER_THREADS) void wit_scatter_lds_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* __restrict__ base,
+                                                                          const uint32_t* __restrict__ b, uint32_t n, uint32_t m, uint32_t mult, uint32_t rec,
+                                                                          unsigned long long* status) {
+    __shared__ uint32_t winner[SCATTER_TILE];
+    for (uint32_t i = threadIdx.x; i < n; i += SCATTER_THREADS) winner[i] = 0;             // n <= SCATTER_TILE: the launcher's choice
+    __syncthreads();
+    bool bad = false;
+    for (uint32_t j0 = 0; j0 < m; j0 += SCATTER_THREADS)                                  // the same rounds for every lane: wit_report ballots
+        bad |= wit_scatter_mark(cols, k, b, m, mult, j0 + threadIdx.x < m, j0 + threadIdx.x, winner, rec, status);
+    const bool any_bad = __syncthreads_or(bad ? 1 : 0) != 0;
+    uint32_t wrote = 0;
+    if (!any_bad)
+        for (uint32_t i = threadIdx.x; i < n; i += SCATTER_THREADS, wrote++) wit_scatter_put(cols, k, dst, base, b, m, i, winner[i]);
+    wit_count(wrote, status);
+}
+// the first `head` words zero, the others `value`
+__global__ __launch_bounds__(SCATTER_THREADS) void wit_fill_kernel(uint32_t* __restrict__ w, size_t words, uint32_t head, uint32_t value) {
+    const size_t i = (size_t)blockIdx.x * SCATTER_THREADS + threadIdx.x;
+    if (i < words) w[i] = i < head ? 0u : value;
+}
+__global__ __launch_bounds__(SCATTER_THREADS) void wit_scatter_mark_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ b, uint32_t m, uint32_t mult,
+                                                                           uint32_t* __restrict__ scratch, uint32_t rec, unsigned long long* status) {
+    const uint32_t j = blockIdx.x * SCATTER_THREADS + threadIdx.x;
+    if (wit_scatter_mark(cols, k, b, m, mult, j < m, j, scratch + SCATTER_HEAD, rec, status)) atomicAdd(&scratch[0], 1u);
+}
+__global__ __launch_bounds__(SCATTER_THREADS) void wit_scatter_store_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* __restrict__ base,
+                                                                            const uint32_t* __restrict__ b, uint32_t n, uint32_t m, const uint32_t* __restrict__ scratch,
+                                                                            unsigned long long* status) {
+    const uint32_t i = blockIdx.x * SCATTER_THREADS + threadIdx.x;
+    const bool live = i < n && scratch[0] == 0;
+    if (live) wit_scatter_put(cols, k, dst, base, b, m, i, scratch[SCATTER_HEAD + i]);
+    wit_count(live ? 1u : 0u, status);
+}
+
+// COMPLEMENT.  A source cell whose signed value v lies in [0, n) raises flag v (every writer stores the same 1); the absent v, in ascending
+// order, are the destinations: the rank of an absent v is the number of absent values below it -- an exclusive scan -- and v is stored at its
+// rank when rank < count (more values than count are absent when sources repeat or lie outside the set: the first `count` are kept).  A
+// workgroup resolves SCATTER_TILE values: lane l owns the COMPL_PER consecutive values from l * COMPL_PER on (flag v sits at word v + v / 32 of
+// the LDS array, so that the lanes' strided reads fall on distinct banks), counts its absent ones, the counts are scanned with cross-lane steps
+// within a wave and through LDS across the waves, and the lane walks its values again.  n <= SCATTER_TILE: one launch.  Longer sets: the
+// flags are bytes of the plan's scratch (fill, mark), a launch leaves every workgroup's absent count behind them, one workgroup turns the
+// counts into offsets -- looping when there are more workgroups than lanes --, and a launch compacts.
+constexpr uint32_t COMPL_PER = SCATTER_TILE / SCATTER_THREADS, COMPL_WORDS = SCATTER_TILE + SCATTER_TILE / 32;
+EZ_D uint32_t wit_compl_at(uint32_t v) { return v + (v >> 5); }
+// the flag a source raises: its signed value when that lies in [0, n), else none (n itself)
+EZ_D uint32_t wit_compl_value(const WitCols& cols, uint32_t k, uint32_t cell, uint32_t n) {
+    bool neg, fits;
+    uint64_t mag;
+    wit_signed(ld_fe(wit_cell(cols, k, cell)), neg, mag, fits);
+    return fits && !neg && mag < n ? (uint32_t)mag : n;
+}
+// the exclusive scan of c over the workgroup (every lane calls it); total: the workgroup's sum.  part: SCATTER_THREADS / 64 words of LDS
+EZ_D uint32_t wit_compl_scan(uint32_t c, uint32_t* part, uint32_t& total) {
+    uint32_t incl = c;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)incl, off);
+        if ((threadIdx.x & 63) >= (uint32_t)off) incl += o;
+    }
+    __syncthreads();                                                      // (part may still be read from an earlier call)
+    if ((threadIdx.x & 63) == 63) part[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+    total = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < SCATTER_THREADS / 64; w++) {
+        before += w < (threadIdx.x >> 6) ? part[w] : 0;
+        total += part[w];
+    }
+    return before + incl - c;
+}
+// the values [v0, v0 + SCATTER_TILE) below n with their flags in LDS: absent v -> dst[rank] while rank < count, rank = offset + the absent below v
+// in the tile; STORE false: only the tile's absent count is returned
+template <bool STORE>
+EZ_D uint32_t wit_compl_tile(const WitCols& cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* flag, uint32_t* part, uint32_t v0, uint32_t n,
+                             uint32_t offset, uint32_t count, uint32_t& wrote) {
+    uint32_t absent = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < COMPL_PER; q++) {
+        const uint32_t t = threadIdx.x * COMPL_PER + q;
+        absent |= (t < n - v0 && !flag[wit_compl_at(t)] ? 1u : 0u) << q;                   // v0 < n: a tile starts inside the set
+    }
+    uint32_t total;
+    uint32_t rank = offset + wit_compl_scan(__popc(absent), part, total);
+    if (STORE)
+        for (uint32_t q = 0; q < COMPL_PER; q++)
+            if ((absent >> q) & 1) {
+                if (rank < count) {
+                    st_fe(wit_cell(cols, k, dst[rank]), Fr::from_u64(v0 + threadIdx.x * COMPL_PER + q));
+                    wrote++;
+                }
+                rank++;
+            }
+    return total;
+}
+__global__ __launch_bounds__(SCATTER_THREADS) void wit_compl_lds_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* __restrict__ a,
+                                                                        uint32_t n, uint32_t m, uint32_t count, unsigned long long* status) {
+    __shared__ uint32_t flag[COMPL_WORDS], part[SCATTER_THREADS / 64];
+    for (uint32_t i = threadIdx.x; i < COMPL_WORDS; i += SCATTER_THREADS) flag[i] = 0;
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < m; j += SCATTER_THREADS) {
+        const uint32_t v = wit_compl_value(cols, k, a[j], n);
+        if (v < n) flag[wit_compl_at(v)] = 1;                                             // n <= SCATTER_TILE: the launcher's choice
+    }
+    __syncthreads();
+    uint32_t wrote = 0;
+    wit_compl_tile<true>(cols, k, dst, flag, part, 0, n, 0, count, wrote);
+    wit_count(wrote, status);
+}
+__global__ __launch_bounds__(SCATTER_THREADS) void wit_compl_mark_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ a, uint32_t n, uint32_t m,
+                                                                         uint8_t* __restrict__ flags) {
+    const uint32_t j = blockIdx.x * SCATTER_THREADS + threadIdx.x;
+    if (j >= m) return;
+    const uint32_t v = wit_compl_value(cols, k, a[j], n);
+    if (v < n) flags[v] = 1;
+}
+// workgroup b over the values [b * SCATTER_TILE, + SCATTER_TILE): STORE false -> counts[b] = its absent count; true -> compacted from the offset counts[b]
+template <bool STORE>
+__global__ __launch_bounds__(SCATTER_THREADS) void wit_compl_tile_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const uint8_t* __restrict__ flags,
+                                                                         uint32_t* __restrict__ counts, uint32_t n, uint32_t count, unsigned long long* status) {
+    __shared__ uint32_t flag[COMPL_WORDS], part[SCATTER_THREADS / 64];
+    const uint32_t v0 = blockIdx.x * SCATTER_TILE;                                        // < n: the grid is cdiv(n, SCATTER_TILE)
+    for (uint32_t t = threadIdx.x; t < SCATTER_TILE; t += SCATTER_THREADS) flag[wit_compl_at(t)] = t < n - v0 ? flags[v0 + t] : 1u;
+    __syncthreads();
+    uint32_t wrote = 0;
+    const uint32_t total = wit_compl_tile<STORE>(cols, k, dst, flag, part, v0, n, STORE ? counts[blockIdx.x] : 0u, count, wrote);
+    if (!STORE && threadIdx.x == 0) counts[blockIdx.x] = total;
+    if (STORE) wit_count(wrote, status);
+}
+// counts[0 .. blocks) -> their exclusive prefix sums, in place: one workgroup, SCATTER_THREADS counts a round with the running total carried on
+__global__ __launch_bounds__(SCATTER_THREADS) void wit_compl_offsets_kernel(uint32_t* __restrict__ counts, uint32_t blocks) {
+    __shared__ uint32_t part[SCATTER_THREADS / 64];
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < blocks; base += SCATTER_THREADS) {                      // the same rounds for every lane: the scan has barriers
+        const uint32_t i = base + threadIdx.x;
+        uint32_t total;
+        const uint32_t before = wit_compl_scan(i < blocks ? counts[i] : 0u, part, total);
+        if (i < blocks) counts[i] = carry + before;
+        carry += total;
+    }
+}
+EZ_HD size_t wit_compl_flag_bytes(uint32_t n) { return ((size_t)n + 15) / 16 * 16; }       // the counts follow the flags, aligned
+// the scratch bytes of a SCATTER / COMPLEMENT record: none while one workgroup holds it in LDS
+EZ_HD size_t wit_scatter_scratch(const Rec& r) {
+    if (r.kind == SCATTER) return r.count > SCATTER_TILE ? ((size_t)r.count + SCATTER_HEAD) * 4 : 0;
+    if (r.kind == COMPLEMENT) return r.p0 > SCATTER_TILE ? wit_compl_flag_bytes(r.p0) + (((size_t)r.p0 + SCATTER_TILE - 1) / SCATTER_TILE) * 4 : 0;
+    return 0;
+}
+
 struct DevPlan {
     Plan host;                      // the validated blob: records, outputs and counts drive the launches; pool / params / consts are
                                     // released once they are on the device (n_params is kept for ezkl_hip_witness_plan_info)
@@ -737,7 +929,8 @@ struct DevPlan {
     fe_t* outs = nullptr;
     unsigned long long* status = nullptr;
     SortKey* sort_keys = nullptr;   // the padded keys of the largest sort record with segments above SORT_TILE, or the chunk slots of the
-                                    // largest arg-extremum record with segments above ARGEXT_CHUNK, whichever is more (one slot when there is none)
+                                    // largest arg-extremum record with segments above ARGEXT_CHUNK, or the winner words / the flags and counts of the
+                                    // largest scatter / complement record above SCATTER_TILE, whichever is more (one slot when there is none)
     Ctx* ctx = nullptr;
     // a plan with phases: the last phase that ran to its end since the last phase 0 with no earlier phase started again since, and the
     // columns it ran on
@@ -806,6 +999,45 @@ uint32_t launch_argext(hipStream_t st, const WitCols& cols, uint32_t k, const De
     hipLaunchKernelGGL(wit_argext_final_kernel, dim3(n_segs), dim3(ARGEXT_THREADS), 0, st, cols, k, p->pool + r.dst, (const SortKey*)p->sort_keys, chunks, p->status);
     return 2;
 }
+// a SCATTER record: one launch up to SCATTER_TILE destinations, else fill, mark and store through the scratch.  -> the number of launches
+uint32_t launch_scatter(hipStream_t st, const WitCols& cols, uint32_t k, const DevPlan* p, const Rec& r, uint32_t ri) {
+    const uint32_t n = r.count, m = r.p0;                                // n <= 2^28, m >= 1: checked on upload
+    const uint32_t *dst = p->pool + r.dst, *base = p->pool + r.a, *b = p->pool + r.b;
+    if (n <= SCATTER_TILE) {
+        hipLaunchKernelGGL(wit_scatter_lds_kernel, dim3(1), dim3(SCATTER_THREADS), 0, st, cols, k, dst, base, b, n, m, r.p1, ri, p->status);
+        return 1;
+    }
+    uint32_t* scratch = reinterpret_cast<uint32_t*>(p->sort_keys);        // SCATTER_HEAD + n words: sized on upload
+    hipLaunchKernelGGL(wit_fill_kernel, dim3((uint32_t)cdiv((size_t)n + SCATTER_HEAD, SCATTER_THREADS)), dim3(SCATTER_THREADS), 0, st, scratch, (size_t)n + SCATTER_HEAD, SCATTER_HEAD, 0u);
+    hipLaunchKernelGGL(wit_scatter_mark_kernel, dim3(cdiv(m, SCATTER_THREADS)), dim3(SCATTER_THREADS), 0, st, cols, k, b, m, r.p1, scratch, ri, p->status);
+    hipLaunchKernelGGL(wit_scatter_store_kernel, dim3(cdiv(n, SCATTER_THREADS)), dim3(SCATTER_THREADS), 0, st, cols, k, dst, base, b, n, m, (const uint32_t*)scratch, p->status);
+    return 3;
+}
+// a COMPLEMENT record: none when it has no cell, one launch up to SCATTER_TILE values, else fill, mark, count, offsets and compact through the
+// scratch.  -> the number of launches
+uint32_t launch_complement(hipStream_t st, const WitCols& cols, uint32_t k, const DevPlan* p, const Rec& r) {
+    const uint32_t n = r.p0, m = r.p1, count = r.count;                  // m <= n <= 2^28, count = n - m: checked on upload
+    if (count == 0) return 0;
+    const uint32_t *dst = p->pool + r.dst, *a = p->pool + r.a;
+    if (n <= SCATTER_TILE) {
+        hipLaunchKernelGGL(wit_compl_lds_kernel, dim3(1), dim3(SCATTER_THREADS), 0, st, cols, k, dst, a, n, m, count, p->status);
+        return 1;
+    }
+    uint8_t* flags = reinterpret_cast<uint8_t*>(p->sort_keys);            // the flag bytes, then one count per tile: sized on upload
+    uint32_t* counts = reinterpret_cast<uint32_t*>(flags + wit_compl_flag_bytes(n));
+    const uint32_t blocks = cdiv(n, SCATTER_TILE);
+    const size_t words = wit_compl_flag_bytes(n) / 4;
+    uint32_t launches = 4;
+    hipLaunchKernelGGL(wit_fill_kernel, dim3((uint32_t)cdiv(words, SCATTER_THREADS)), dim3(SCATTER_THREADS), 0, st, reinterpret_cast<uint32_t*>(flags), words, 0u, 0u);
+    if (m) {
+        hipLaunchKernelGGL(wit_compl_mark_kernel, dim3(cdiv(m, SCATTER_THREADS)), dim3(SCATTER_THREADS), 0, st, cols, k, a, n, m, flags);
+        launches++;
+    }
+    hipLaunchKernelGGL(wit_compl_tile_kernel<false>, dim3(blocks), dim3(SCATTER_THREADS), 0, st, cols, k, dst, (const uint8_t*)flags, counts, n, count, p->status);
+    hipLaunchKernelGGL(wit_compl_offsets_kernel, dim3(1), dim3(SCATTER_THREADS), 0, st, counts, blocks);
+    hipLaunchKernelGGL(wit_compl_tile_kernel<true>, dim3(blocks), dim3(SCATTER_THREADS), 0, st, cols, k, dst, (const uint8_t*)flags, counts, n, count, p->status);
+    return launches;
+}
 }  // namespace
 }  // namespace ezkl
 
@@ -841,6 +1073,8 @@ int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out
             sort_bytes = std::max(sort_bytes, (size_t)(r.count / r.p0) * wit_sort_padded(r.p0) * sizeof(SortKey));
         else if (r.kind == ARGEXT)                                // the records run one after another on the stream: they share the scratch
             sort_bytes = std::max(sort_bytes, wit_argext_slots(r.count, r.p0) * sizeof(SortKey));
+        else if (r.kind == SCATTER || r.kind == COMPLEMENT)
+            sort_bytes = std::max(sort_bytes, wit_scatter_scratch(r));
     struct Up { void** dev; const void* src; size_t bytes; };
     const Up ups[] = {{(void**)&p->pool, h.pool.data(), h.pool.size() * 4},       {(void**)&p->outputs, h.outputs.data(), h.outputs.size() * 4},
                       {(void**)&p->params, h.params.data(), h.params.size() * 8}, {(void**)&p->consts, consts.data(), consts.size() * 32},
@@ -980,6 +1214,14 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
         case SORT: launches += launch_sort<SORT>(st, cols, k, p, r, (uint32_t)ri) - 1; break;
         case ARGSORT: launches += launch_sort<ARGSORT>(st, cols, k, p, r, (uint32_t)ri) - 1; break;
         case ARGEXT: launches += launch_argext(st, cols, k, p, r, (uint32_t)ri) - 1; break;
+        case ONEHOT: launch_elem<ONEHOT>(st, cols, k, p, r, (uint32_t)ri); break;
+        case SCATTER: launches += launch_scatter(st, cols, k, p, r, (uint32_t)ri) - 1; break;
+        case COMPLEMENT: {
+            const uint32_t made = launch_complement(st, cols, k, p, r);
+            if (!made) continue;                                   // nothing missing: the record writes no cell
+            launches += made - 1;
+            break;
+        }
         case MATMUL: {
             const uint32_t m = r.count / r.p1;
             hipLaunchKernelGGL(wit_matmul_kernel, dim3(cdiv(m, MM_TILE) * cdiv(r.p1, MM_TILE)), dim3(MM_TILE * MM_TILE), 0, st, cols, k, p->pool + r.dst, p->pool + r.a,
@@ -1023,6 +1265,8 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
                            : kind == RECIP                ? "witness: reciprocal operand beyond 62 bits ("
                            : kind == ISQRT                ? "witness: square-root operand outside the exact range ("
                            : kind == ARGEXT               ? "witness: arg-extremum key beyond 62 bits ("
+                           : kind == SCATTER              ? "witness: scatter index outside the tensor ("
+                           : kind == ONEHOT               ? "witness: one-hot index outside the classes ("
                                                           : "witness: value exceeds the decomposition range (";
         t_wit_error = std::string(what) + kind_name(kind) + " record " + std::to_string(ri) +
                       ", element " + std::to_string(el) + "; " + std::to_string(dev_status[0]) + (kind == MATMUL ? " operand reads in all)" : " cells in all)");

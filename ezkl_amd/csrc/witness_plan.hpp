@@ -60,6 +60,23 @@
 // of the cells a[s * n .. + n): the reference's max_by_key((value, -idx)) / min_by_key((value, idx)), the one claim the gates accept.  A
 // source with |s| >= 2^62 is a run-time failure of the lane ("arg-extremum key beyond 62 bits"), element = its place in a; its segment's
 // cell is not written.  ARGEXT_CHUNK is the number of sources one workgroup of csrc/witness.hip reduces.
+// Kind 28 (KINDS_LIMIT) is unassigned as 16, 23 and 26 are; SCATTER, COMPLEMENT and ONEHOT are 29 .. 31 and KINDS_TOP follows them.
+// A SCATTER record (the claimed output of `scatter_elements`, layouts.rs:2313-2379, which the prover states BEFORE the gathers that check it):
+// ONE tensor -- count = n destination cells dst[i], a = the n base cells, p0 = m >= 1 elements, p1 = the multiplier of the scattered dimension
+// >= 1, b = the pool offset of 1 + 3m words: the extent of that dimension, m index cells, m source cells, m constant offsets (plain words).
+// With s_j the signed value of index cell j its target is t_j = s_j * p1 + off_j; dst[i] gets the value of source cell j for the GREATEST j
+// with t_j == i (tensor::ops::scatter: the later element wins), else the value of base cell i.  p0, p1 or the extent zero, count > 2^28, an
+// array past the pool or an offset with off_j + (extent - 1) * p1 >= count: "bad scatter shape" -- so every target of an index inside
+// [0, extent) is a destination.  s_j < 0, s_j >= extent or |s_j| >= 2^62 is a run-time failure of the lane ("scatter index outside the
+// tensor"), element = j, every such j counted; the record then writes none of its cells.  SCATTER_TILE is the number of destinations one
+// workgroup of csrc/witness.hip resolves in LDS.
+// A COMPLEMENT record (the claimed output of `get_missing_set_elements` over the positions, layouts.rs:2213-2286): p0 = n, the set {0 .. n - 1},
+// p1 = m <= n source cells at a, count = n - m destination cells (zero is legal: the record writes nothing), b unused and zero.  dst[i] gets
+// the i-th smallest v in [0, n) that is the signed value of no source cell; a source outside [0, n) or beyond 62 bits removes nothing.  It
+// never fails.  p1 > p0, count != p0 - p1, p0 > 2^28 or an array past the pool: "bad complement shape".
+// A ONEHOT record (the claimed vector of `one_hot`, layouts.rs:1398-1442), element-wise: a = the index cell of element e, b = the pool
+// offset of the per-element positions (plain words), p0 = num_classes >= 1 ("zero one-hot classes"), p1 = 0: 1 if the signed value equals
+// the position, else 0.  s < 0, s >= p0 or |s| >= 2^62 is a run-time failure of the lane ("one-hot index outside the classes").
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -71,14 +88,15 @@ namespace ezkl {
 namespace wplan {
 
 constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64, MAX_PHASES = 3, MAX_CHALLENGES = 64, SORT_TILE = 2048,
-                   MAX_SORT_COUNT = 1u << 28, ARGEXT_CHUNK = 4096;
+                   MAX_SORT_COUNT = 1u << 28, ARGEXT_CHUNK = 4096, SCATTER_TILE = 4096;
 enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC, UNASSIGNED, SUMACC, PRODACC, GATHER, CLAMP, SORT, ARGSORT, N_KINDS,     // 16 names nothing: refused as unknown
                        RECIP = 24, ISQRT = 25, KINDS_END,                         // N_KINDS ends KIND_NAMES and, as a kind (23), names nothing either
-                       ARGEXT = 27, KINDS_LIMIT };                                 // KINDS_END (26) names nothing either; KINDS_LIMIT is the first kind past them all
+                       ARGEXT = 27, KINDS_LIMIT,                                   // KINDS_END (26) names nothing either; KINDS_LIMIT (28) was the first kind past them all and names nothing
+                       SCATTER = 29, COMPLEMENT = 30, ONEHOT = 31, KINDS_TOP };    // KINDS_TOP is the first kind past them all
 static const char* const KIND_NAMES[N_KINDS] = {"copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot",
                                                 "nonlinearity", "nonlinearity_index", "matmul", "rlc", "div", "?", "sum", "prod", "gather", "clamp", "sort", "argsort"};
 // the name a message gives a kind: KIND_NAMES up to ARGSORT, the later kinds by hand, "?" for a kind that names nothing
-inline const char* kind_name(uint32_t kind) { return kind < N_KINDS ? KIND_NAMES[kind] : kind == RECIP ? "recip" : kind == ISQRT ? "sqrt" : kind == ARGEXT ? "argext" : "?"; }
+inline const char* kind_name(uint32_t kind) { return kind < N_KINDS ? KIND_NAMES[kind] : kind == RECIP ? "recip" : kind == ISQRT ? "sqrt" : kind == ARGEXT ? "argext" : kind == SCATTER ? "scatter" : kind == COMPLEMENT ? "complement" : kind == ONEHOT ? "one_hot" : "?"; }
 struct Rec {
     uint32_t kind, count, p0, p1, dst, a, b, phase;
 };
@@ -178,8 +196,8 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
     uint32_t last_phase = 0;
     for (size_t ri = 0; ri < out.recs.size(); ri++) {
         const Rec& r = out.recs[ri];
-        if (r.kind >= KINDS_LIMIT || r.kind == KINDS_END || r.kind == N_KINDS || r.kind == UNASSIGNED) return at_rec(ri, r.kind, "unknown kind");
-        if (r.count == 0) return at_rec(ri, r.kind, "empty");
+        if (r.kind >= KINDS_TOP || r.kind == KINDS_LIMIT || r.kind == KINDS_END || r.kind == N_KINDS || r.kind == UNASSIGNED) return at_rec(ri, r.kind, "unknown kind");
+        if (r.count == 0 && r.kind != COMPLEMENT) return at_rec(ri, r.kind, "empty");     // (nothing missing: a complement that writes no cell)
         if (r.phase >= n_phases) return at_rec(ri, r.kind, "phase out of range");
         if (r.phase < last_phase) return at_rec(ri, r.kind, "phases decrease");
         last_phase = r.phase;
@@ -254,12 +272,32 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
                 return at_rec(ri, r.kind, "bad arg-extremum shape");
             n_a = (uint64_t)r.count * r.p0; a_cells = true;
             break;
+        case SCATTER: {                                  // p0 = elements, p1 = multiplier, b: extent, index cells, source cells, offsets
+            if (r.p0 == 0 || r.p1 == 0 || r.count > MAX_SORT_COUNT || !span_ok(r.dst, r.count) || !span_ok(r.a, r.count) || !span_ok(r.b, 1 + 3ull * r.p0))
+                return at_rec(ri, r.kind, "bad scatter shape");
+            const uint32_t extent = P[r.b];
+            if (extent == 0) return at_rec(ri, r.kind, "bad scatter shape");
+            for (uint32_t j = 0; j < r.p0; j++)          // every target of an index inside [0, extent) is a destination: no overflow, both factors are 32-bit
+                if ((uint64_t)P[r.b + 1 + 2ull * r.p0 + j] + (uint64_t)(extent - 1) * r.p1 >= r.count) return at_rec(ri, r.kind, "bad scatter shape");
+            for (uint64_t j = 0; j < 2ull * r.p0; j++) {   // the index and source cells: ones a lane can read
+                const uint32_t x = P[r.b + 1 + j];
+                if (x >= cells) return at_rec(ri, r.kind, "cell index out of range");
+                if (!written.get(x)) return at_rec(ri, r.kind, "a cell is read before an earlier record has written it");
+            }
+            a_cells = true;
+            break;
+        }
+        case COMPLEMENT:                                 // p0 = n, p1 = sources, count = n - sources
+            if (r.p1 > r.p0 || r.count != r.p0 - r.p1 || r.p0 > MAX_SORT_COUNT || !span_ok(r.dst, r.count) || !span_ok(r.a, r.p1)) return at_rec(ri, r.kind, "bad complement shape");
+            n_a = r.p1; a_cells = true;
+            break;
+        case ONEHOT: a_cells = true; n_b = r.count; if (r.p0 == 0) return at_rec(ri, r.kind, "zero one-hot classes"); break;
         case DOT:
             if (r.p0 == 0 || r.p1 == 0 || (uint64_t)r.count * r.p1 > P.size() || (uint64_t)r.count * r.p1 * r.p0 > P.size()) return at_rec(ri, r.kind, "bad dot shape");
             n_dst = (uint64_t)r.count * r.p1; n_a = n_b = n_dst * r.p0; a_cells = b_cells = true;
             break;
         }
-        if (!span_ok(r.dst, n_dst) || !span_ok(r.a, n_a) || (r.kind != RECIP && !span_ok(r.b, n_b)))     // (RECIP: b is no pool offset)
+        if (!span_ok(r.dst, n_dst) || !span_ok(r.a, n_a) || (r.kind != RECIP && r.kind != SCATTER && !span_ok(r.b, n_b)))     // (RECIP: b is no pool offset; SCATTER: checked above)
             return at_rec(ri, r.kind, "an index array runs past the pool");
         const bool sparse = r.kind == DOT || r.kind == SUMACC || r.kind == PRODACC;     // 0xffffffff = no entry
         for (uint64_t i = 0; i < n_a; i++) {
@@ -279,6 +317,7 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
                 if (x != NONE && x >= r.p1) return at_rec(ri, r.kind, "bad decomposition");
                 continue;
             }
+            if (r.kind == ONEHOT) continue;              // positions: plain words
             if (sparse && x == NONE) {
                 if (P[r.a + i] != NONE) return at_rec(ri, r.kind, "a product with one operand");
                 continue;

@@ -38,6 +38,8 @@ SORT_MODES = ("unsorted", "smallest_index_first", "largest_index_first")       #
 RECIP_ERROR = "reciprocal operand beyond 62 bits"
 SQRT_ERROR = "square-root operand outside the exact range"
 ARGEXT_ERROR = "arg-extremum key beyond 62 bits"
+SCATTER_ERROR = "scatter index outside the tensor"
+ONEHOT_ERROR = "one-hot index outside the classes"
 
 
 def clamped(s, lo, hi):
@@ -967,6 +969,196 @@ class BaseRegion(Region):
                     self.flush()
         return self.div(out, kernel[0] * kernel[1]) if normalized else out
 
+    # ---- the indexed family: gather, scatter, one-hot ---------------------------------------------------------------------------------
+    def select_elements(self, vals, indices):
+        """layouts.rs:1363-1396 `select` for many picks in ONE dynamic lookup (:1483-1581): table side (the position as a constant, vals_j,
+        the region's dynamic-lookup index), input side one pick per index cell (the index cell, the claimed element, the same constant),
+        constrained as `select` does it.  -> the claimed elements where the argument reads them"""
+        lookup_index = Val(self.dynamic_lookup_index, const=True)
+        table_rows = [(Val(j, const=True), v, lookup_index) for j, v in enumerate(vals)]
+        picks = []
+        for index in indices:
+            row = self.row_at(table_rows, index)
+            picks.append((Val(row[0].v, index.cell, index.const), Val(row[1].v), lookup_index))
+        self._lookup_any(self.base.dynamic_table_selectors[0], self.base.dynamic_lookup_selectors, table_rows, picks, constrained=True)
+        self.dynamic_lookup_index += 1
+        return [pick[1] for pick in self.dyn_picks]
+
+    @staticmethod
+    def _strides(dims):
+        """the row-major multiplier of every dimension (`dim_multiplier`, layouts.rs:1947-1956)"""
+        out, acc = [], 1
+        for d in reversed(dims):
+            out.append(acc)
+            acc *= d
+        return out[::-1]
+
+    @staticmethod
+    def _coords(dims):
+        """the coordinates of `dims` in row-major order (`multi_cartesian_product`)"""
+        return [tuple(int(c) for c in coord) for coord in np.ndindex(*dims)]
+
+    def linearize_element_index(self, index, dims, dim, is_flat_index, index_dims=None):
+        """layouts.rs:1924-2012: the position in the flattened tensor of shape `dims` each index names along `dim` -- per element a
+        `pairwise` MULT by the constant multiplier of `dim` and a `pairwise` ADD of the constant offset of the other coordinates.  A flat
+        index (`gather`) is iterated over dims with dims[dim] = len(index); otherwise `index` has the shape `index_dims`, of the rank of
+        `dims`, and an index of rank 1 is returned as it is (:1942-1944)"""
+        dims = list(dims)
+        if not is_flat_index:
+            index_dims = [len(index)] if index_dims is None else list(index_dims)
+            assert len(index_dims) == len(dims)
+            if len(index_dims) == 1:
+                return list(index)
+        mult = self._strides(dims)
+        iteration_dims = dims[:dim] + [len(index)] + dims[dim + 1:] if is_flat_index else index_dims
+        out = []
+        for i, coord in enumerate(self._coords(iteration_dims)):
+            index_val = index[coord[dim]] if is_flat_index else index[i]
+            const_offset = sum(coord[t] * mult[t] for t in range(len(dims)) if t != dim)
+            res = self.pairwise([index_val], [Val(mult[dim], const=True)], EC.MULT)
+            out.append(self.pairwise(res, [Val(const_offset, const=True)], EC.ADD)[0])
+        return out
+
+    def gather(self, vals, dims, index, dim):
+        """layouts.rs:1822-1847: the slices of the tensor `vals` (shape `dims`, row-major) the flat `index` names along `dim` -> the output,
+        row-major, of shape dims with dims[dim] = len(index)"""
+        return self.select_elements(vals, self.linearize_element_index(index, dims, dim, True))
+
+    def gather_elements(self, vals, dims, index, index_dims, dim):
+        """layouts.rs:1850-1870: out[coord] = vals[coord with coord[dim] = index[coord]] over the shape of the index -> (output, linear index)"""
+        assert len(dims) == len(index_dims)
+        linear = self.linearize_element_index(index, dims, dim, False, index_dims)
+        return self.select_elements(vals, linear), linear
+
+    def _one_hot(self, s, num_classes):
+        """the one data-dependent step of `one_hot`: the vector with a one at the signed index s (`tensor::ops::one_hot`).  (A recording
+        region overrides this, as it overrides `_sorted`.)"""
+        assert 0 <= s < num_classes and abs(s) < 1 << 62, ONEHOT_ERROR
+        return [int(j == s) for j in range(num_classes)]
+
+    def one_hot(self, index, num_classes):
+        """layouts.rs:1398-1442 for one index cell: the claimed vector, `boolean_identity` of it with the index assigned beside it on the
+        first input VarTensor and the `max(len)` increment, `sum` == 1, and `gather` of the claim at the index == 1"""
+        claim = [Val(v) for v in self._one_hot(signed(index.v), num_classes)]
+        assigned_input = self.assign(self.inputs[0], [index])
+        assigned_output = self.boolean_identity(claim)
+        self.increment(max(len(assigned_output), len(assigned_input)))
+        unit = [Val(1, const=True)]
+        self.enforce_equality(unit, [self.sum(assigned_output)])
+        gathered = self.gather(assigned_output, [num_classes], assigned_input, 0)
+        self.enforce_equality(unit, gathered)
+        return assigned_output
+
+    def one_hot_axis(self, index, dims, num_classes, dim):
+        """layouts.rs:1769-1819 over the flat list of the index cells of a tensor of shape `dims`: one `one_hot` per cell, in order, arranged
+        into the shape dims with `num_classes` inserted at `dim` -> the output, row-major"""
+        dims = list(dims)
+        assert len(index) == int(np.prod(dims, dtype=np.int64))
+        ops = [self.one_hot(cell, num_classes) for cell in index]
+        strides = self._strides(dims)
+        out = []
+        for coord in self._coords(dims[:dim] + [num_classes] + dims[dim:]):
+            op_idx = coord[:dim] + coord[dim + 1:]
+            out.append(ops[sum(c * s for c, s in zip(op_idx, strides))][coord[dim]])
+        return out
+
+    def _claimed_indices(self, output, input):
+        """the one data-dependent step of `shuffles` over an arbitrary input side (layouts.rs:1662-1704, `unsorted`): for every output
+        element in turn the first position of the input, in input order, that holds its value and is not yet used; 0 where there is none
+        (`unwrap_or(&0)`: the permutation then cannot hold).  (A recording region overrides this, as it overrides `_sorted`.)"""
+        places = {}
+        for j, v in enumerate(input):
+            places.setdefault(signed(v.v), []).append(j)
+        taken = {}
+        out = []
+        for v in output:
+            x = signed(v.v)
+            at, mine = taken.get(x, 0), places.get(x, ())
+            out.append(mine[at] if at < len(mine) else 0)
+            taken[x] = at + 1
+        return out
+
+    def shuffles(self, output, input):
+        """layouts.rs:1624-1760 in `unsorted` mode: `output` is a permutation of `input` -- table side (output_i, the region's shuffle index,
+        the claimed source index_i), input side (input_j, the same constant, j) -> the claimed indices where the argument reads them"""
+        assert len(output) == len(input)
+        index = Val(self.shuffle_index, const=True)
+        claimed = self._claimed_indices(output, input)
+        placed = self._lookup_any(self.base.shuffle_output_selectors[0], self.base.shuffle_input_selectors,
+                                  [(o, index, Val(c)) for o, c in zip(output, claimed)],
+                                  [(v, index, Val(j, const=True)) for j, v in enumerate(input)], constrained=True)
+        self.shuffle_index += 1
+        return [row[2] for row in placed]
+
+    def _missing(self, vals, fullset):
+        """the one data-dependent step of `get_missing_set_elements` (layouts.rs:2229-2244): the first occurrence in `fullset` of each input
+        value in turn is deleted, the first len(fullset) - len(vals) of what remains are kept.  It never fails: a value not in the set
+        deletes nothing.  (A recording region overrides this, as it overrides `_sorted`.)"""
+        full = [signed(v.v) for v in fullset]
+        places = {}
+        for j, x in enumerate(full):
+            places.setdefault(x, []).append(j)
+        taken, gone = {}, [False] * len(full)
+        for v in vals:
+            x = signed(v.v)
+            at, mine = taken.get(x, 0), places.get(x, ())
+            if at < len(mine):
+                gone[mine[at]] = True
+                taken[x] = at + 1
+        rest = [x for x, g in zip(full, gone) if not g]
+        return [x % R for x in rest[:max(len(full) - len(vals), 0)]]
+
+    def get_missing_set_elements(self, vals, fullset, ordered):
+        """layouts.rs:2213-2286: the elements of `fullset` (distinct values) that `vals` lacks -- the claim on the output VarTensor, the
+        permutation argument of `shuffles` with output side vals ++ claim and input side fullset, then an `unsorted` ascending sort of the
+        claim when `ordered` (an empty claim has nothing to sort)"""
+        vals = list(vals)
+        claim = self.assign(self.output, [Val(v) for v in self._missing(vals, fullset)])
+        self.increment(len(claim))
+        self.shuffles(vals + claim, fullset)
+        if ordered and claim:
+            claim = self.sort_ascending(claim, "unsorted")[0]
+        return claim
+
+    def _scattered(self, input, index, src, dims, index_dims, dim):
+        """the one data-dependent step of `scatter_elements`, `tensor::ops::scatter` (/root/reference/src/tensor/ops.rs:744-778): a copy of the
+        input, then the elements of `src` (shape `index_dims`) in row-major order, each to its own coordinate with the one along `dim`
+        replaced by its index: a later element overwrites an earlier one at the same target.  An index outside [0, dims[dim]) -- or beyond
+        62 bits -- is the failure SCATTER_ERROR.  (A recording region overrides this, as it overrides `_sorted`.)"""
+        assert len(index) == len(src) and all(a <= b for t, (a, b) in enumerate(zip(index_dims, dims)) if t != dim)
+        out = [v.v for v in input]
+        mult = self._strides(dims)
+        for coord, i, v in zip(self._coords(index_dims), index, src):
+            s = signed(i.v)
+            assert 0 <= s < dims[dim] and abs(s) < 1 << 62, SCATTER_ERROR
+            out[s * mult[dim] + sum(coord[t] * mult[t] for t in range(len(dims)) if t != dim)] = v.v
+        return out
+
+    def scatter_elements(self, input, dims, index, index_dims, src, dim):
+        """layouts.rs:2313-2379, step for step: the index is assigned if it is not yet cells; the scattered tensor is CLAIMED on the output
+        VarTensor (`_scattered`); `gather_elements` of the claim at the index is held equal to `src`; the positions the index does not
+        name -- `get_missing_set_elements` of the linear index in the constants 0 .. n - 1, ordered -- are gathered from the flat claim
+        and looked up, with their positions, in (position, input): what was not written is the input's.  -> the claim.
+        Two elements on one target make the permutation argument unsatisfiable (the claim itself takes the later source)."""
+        assert len(dims) == len(index_dims) and len(input) == int(np.prod(dims, dtype=np.int64))
+        index = list(index)
+        if not all(v.cell is not None for v in index):                   # :2323-2326
+            index = self.assign(self.inputs[1], index)
+            self.increment(len(index))
+        claimed = self.assign(self.output, [Val(v) for v in self._scattered(input, index, src, dims, index_dims, dim)])
+        self.increment(len(claimed))
+        gather_src, linear_index = self.gather_elements(claimed, dims, index, index_dims, dim)
+        self.enforce_equality(gather_src, list(src))
+        full_index_set = [Val(j, const=True) for j in range(len(input))]
+        input_indices = self.get_missing_set_elements(linear_index, full_index_set, True)
+        gather_input, _ = self.gather_elements(claimed, [len(claimed)], input_indices, [len(input_indices)], 0)
+        lookup_index = Val(self.dynamic_lookup_index, const=True)
+        self._lookup_any(self.base.dynamic_table_selectors[0], self.base.dynamic_lookup_selectors,
+                         [(j, v, lookup_index) for j, v in zip(full_index_set, input)],
+                         [(i, g, lookup_index) for i, g in zip(input_indices, gather_input)], constrained=True)
+        self.dynamic_lookup_index += 1
+        return claimed
+
     def einsum(self, ein, A, B, challenges=None):
         """assign_einsum of an EinsumMatmulCircuit laid over this region's configuration (EinsumMatmulCircuit.over), in this region, at
         the einsum coordinate: A, B are len x len Vals"""
@@ -1440,6 +1632,67 @@ class PoolClassifierCircuit(LayoutCircuit):
         img = np.asarray(img, np.int64).reshape(-1)
         assert len(img) == self.n_inputs
         outs = self.layout(reg, [Val(int(v) % R) for v in img], lambda v: Val(int(v) % R))
+        reg.finish(self.gc.const_cols)
+        self.outputs = [v.v for v in outs]
+        return reg
+
+
+class ScatterGatherCircuit(LayoutCircuit):
+    """a table update and two lookups on private inputs -- a `rows` x `cols` table, an `m` x `cols` index, an `m` x `cols` source and `p`
+    row picks, in that order, each row-major: t = `scatter_elements`(table, index, src) along dim 0 (x[idx] = v, a cache update), g =
+    `gather`(t, picks) along dim 0 (an embedding lookup) and h = `one_hot`(picks[0], rows) (a label); instance = g, then h.  The op
+    sequence is stated once (`layout`), so that witness_plan.record_plan can run it on symbols.  For a satisfiable witness every COLUMN of
+    the index must hold distinct values in [0, rows): two elements on one target leave the permutation argument of the missing set without
+    a witness.  The settings carry the range checks of the decomposition, (-1, 1) and (0, base - 1), the (0, 1) check of `one_hot`, the
+    dynamic lookups of the gathers and the shuffle arguments of the missing set and its sort (base^legs must exceed rows * cols)."""
+
+    def __init__(self, logrows, num_inner_cols, capacity, rows=6, cols=3, m=2, picks=4, decomp_base=128, decomp_legs=2):
+        assert 1 <= m <= rows and cols >= 1 and picks >= 1 and decomp_base ** decomp_legs > rows * cols
+        self.k, self.w, self.capacity = logrows, num_inner_cols, capacity
+        self.rows, self.cols, self.m, self.picks, self.base, self.legs = int(rows), int(cols), int(m), int(picks), decomp_base, decomp_legs
+        n = self.rows * self.cols
+        self.n_inputs = n + 2 * self.m * self.cols + self.picks
+        self.settings = EC.GraphSettings(logrows, num_inner_cols, capacity, total_const_size=16, required_range_checks=[(-1, 1), (0, decomp_base - 1), (0, 1)],
+                                         model_instance_shapes=[[1, self.picks * self.cols + self.rows]], total_dynamic_col_size=4 * n + self.rows,
+                                         num_dynamic_lookups=5, total_shuffle_col_size=2 * n - self.m * self.cols, num_shuffles=2)
+        self.gc = EC.GraphConfig(self.settings)
+
+    def _split(self, x):
+        n, mc = self.rows * self.cols, self.m * self.cols
+        return x[:n], x[n:n + mc], x[n + mc:n + 2 * mc], x[n + 2 * mc:]
+
+    def model(self, x):
+        """the integer forward pass the circuit proves: the gathered rows of the updated table, then the one-hot vector of the first pick"""
+        table, index, src, picks = (np.asarray(a, np.int64) for a in self._split(list(x)))
+        t = table.reshape(self.rows, self.cols).copy()
+        np.put_along_axis(t, index.reshape(self.m, self.cols), src.reshape(self.m, self.cols), axis=0)
+        return [int(v) for v in np.take(t, picks, axis=0).reshape(-1)] + [int(j == picks[0]) for j in range(self.rows)]
+
+    def layout(self, reg, inputs, param):
+        reg.decomp = (self.base, self.legs)
+        vals = reg.assign(reg.inputs[0], inputs)
+        reg.increment(len(vals))
+        table, index, src, picks = self._split(vals)
+        t = reg.scatter_elements(table, [self.rows, self.cols], index, [self.m, self.cols], src, 0)
+        g = reg.gather(t, [self.rows, self.cols], picks, 0)
+        h = reg.one_hot(picks[0], self.rows)
+        outs = g + h
+        reg.constrain_instance(outs, self.gc.instance)
+        return outs
+
+    def plan_identity(self):
+        shape = [self.k, self.w, self.rows, self.cols, self.m, self.picks, self.base, self.legs, self.gc.advices[0].num_blocks()]
+        return np.asarray(shape, np.int64).tobytes()
+
+    def fresh(self):
+        """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
+        return ScatterGatherCircuit(self.k, self.w, self.capacity, self.rows, self.cols, self.m, self.picks, self.base, self.legs)
+
+    def synthesize(self, x, witness=True):
+        x = np.asarray(x, np.int64).reshape(-1)
+        assert len(x) == self.n_inputs
+        reg = BaseRegion(self.gc, witness)
+        outs = self.layout(reg, [Val(int(v) % R) for v in x], Val)
         reg.finish(self.gc.const_cols)
         self.outputs = [v.v for v in outs]
         return reg

@@ -1,5 +1,5 @@
 """Witness plans: the layout of an MlpCircuit, a ConvMnistCircuit, an EinsumMatmulCircuit, a SumProdLayoutCircuit, a SortTopkCircuit, a
-NormCircuit, a PoolClassifierCircuit or the TransformerSurrogateCircuit's unit recorded ONCE, replayed for every proof.
+NormCircuit, a PoolClassifierCircuit, a ScatterGatherCircuit or the TransformerSurrogateCircuit's unit recorded ONCE, replayed for every proof.
 
 Which advice cell holds which value depends only on the circuit (BaseRegion places cells from the linear coordinate, the duplicated rows
 of `dot` from the block geometry; constants and the circuit's parameters are the same for every input), so `record_plan` runs one
@@ -27,6 +27,10 @@ for the claimed indices; everything around it is records of the other kinds), an
 `optimum_convex_function` around them are records of the other kinds, `max` is a sort and `exp` a static lookup.  `argmax` / `argmin`
 claim their index BEFORE the sort that checks it (`BaseRegion._arg_extremum`, the one data-dependent step): the claim is one segment of an
 ARGEXT record, the `select` around it a gather, the rest a sort; `max_pool` is a `max` per window and `sumpool` a `dot` per window plus `div`.
+The indexed family -- `gather`, `gather_elements`, `scatter_elements`, `get_missing_set_elements`, `one_hot` -- has three claims that depend on the
+data: the scattered tensor, claimed before the gathers that check it (`BaseRegion._scattered`: one SCATTER record), the complement of the
+written positions (`_missing`: one COMPLEMENT record) and the one-hot vector (`_one_hot`: ONEHOT elements); the many-pick `select_elements`
+is GATHER elements over one table, the claimed indices of the missing set's permutation argument are copies, the rest records of the other kinds.
 The MLP recorder keeps refusing them by name.  The TransformerSurrogateCircuit lays its einsum over its own configuration
 (`BaseRegion.einsum`): it is recorded on a PhasedLookupRecordingRegion -- the lookup region with the einsum region's `put_cell`, matmul
 record, running values and phase bookkeeping -- into a TWO-phase plan of the unit's rows; the tiling is the device's
@@ -100,6 +104,25 @@ A record of an element-wise kind has `count` destination cells pool[dst + i], pr
            the run-time failure "arg-extremum key beyond 62 bits", reported like the decomposition-range failure with element = its place in
            a; on the device its segment's cell is not written.  ARGEXT_CHUNK is the number of sources one workgroup reduces
 
+    (kind 28 is unassigned as 16, 23 and 26 are; the three kinds below are 29 .. 31 and KINDS_TOP follows them)
+    SCATTER (29)   ONE tensor: count = n destination cells pool[dst + i], a = the n base cells, p0 = m >= 1 elements, p1 = the multiplier of
+           the scattered dimension >= 1, b = the pool offset of 1 + 3m words: the extent of that dimension, m index cells, m source cells, m
+           constant offsets (plain u32, not cells).  With s_j the signed value of index cell j its target is t_j = s_j * p1 + off_j;
+           destination i gets the value of source cell j for the GREATEST j with t_j == i, else the value of base cell i: the claimed output
+           of `scatter_elements` (BaseRegion._scattered, layouts.rs:2313-2379, `tensor::ops::scatter`: the later element wins).  s_j < 0,
+           s_j >= extent or |s_j| >= 2^62 is the run-time failure "scatter index outside the tensor", reported like the decomposition-range
+           failure with element = j, every such j counted; the record then writes none of its cells.  p0, p1 or the extent zero, count >
+           2^28, an array past the pool or an offset with off_j + (extent - 1) * p1 >= count: "bad scatter shape".  SCATTER_TILE is the
+           number of destinations one workgroup resolves in LDS
+    COMPLEMENT (30)   p0 = n: the set {0 .. n - 1}, p1 = m <= n source cells at a, count = n - m destination cells, b = 0.  Destination i
+           gets the i-th smallest v in [0, n) that is the signed value of no source cell: the claimed output of `get_missing_set_elements`
+           over the positions (BaseRegion._missing, layouts.rs:2213-2286).  A source outside [0, n) or beyond 62 bits removes nothing; the
+           kind never fails.  p1 > p0, count != p0 - p1, p0 > 2^28 or an array past the pool: "bad complement shape"
+    ONEHOT (31)   element-wise: a = the index cell of element e, b = the pool offset of the per-element positions (u32), p0 = num_classes
+           >= 1 ("zero one-hot classes"), p1 = 0: 1 if the signed value equals the position, else 0 (BaseRegion._one_hot,
+           layouts.rs:1398-1442).  s < 0, s >= p0 or |s| >= 2^62 is the run-time failure "one-hot index outside the classes", reported like
+           the decomposition-range failure; the lane writes nothing
+
 PHASES.  A circuit with second-phase advice (the Freivalds einsum) has columns that depend on challenges squeezed after the first-phase
 commitments: its plan has n_phases = 2, and every record carries the phase whose run replays it.  Phases are non-decreasing along the
 record list; a column belongs to the phase of the records that write it (never to two; a column no record writes: phase 0); INPUT and
@@ -129,6 +152,12 @@ equality tests of tests/test_witness_plan_cpu.py fail loudly -- an assert or a P
     _sorted                   overridden: `assert abs(s) < 1 << 62` is the run-time check of SORT / ARGSORT
     row_at                    overridden: `assert 0 <= signed(index.v) < len(table_rows)` is the run-time check of GATHER
     _arg_extremum             overridden: `assert abs(x) < 1 << 62` is the run-time check of ARGEXT
+    _scattered                overridden: `assert 0 <= s < dims[dim] and abs(s) < 1 << 62` is the run-time check of SCATTER; the offsets are
+                              `sum(coord[t] * mult[t] for t != dim)` of BaseRegion._strides / _coords
+    _missing                  overridden: the full set must be the constants 0 .. n - 1 (COMPLEMENT); it never fails
+    _one_hot                  overridden: `assert 0 <= s < num_classes and abs(s) < 1 << 62` is the run-time check of ONEHOT
+    _claimed_indices          overridden: over the constants 0 .. n - 1 the claimed index of an output element is its own value (a COPY)
+    select_elements           every pick goes through `row_at`, as `select`'s one pick does: GATHER elements over one table
     equals_zero               `pow(v, -1, R) if v else 0`   (the truth value of a cell symbol is True: INVZ covers both branches)
     div (round_div)           `mag = abs(s)`, `assert mag < 1 << 52` (recorded as the run-time check), `((s > 0) - (s < 0)) * ((mag + d // 2) // d)`
     nonlinearity              `assert table.range[0] <= signed(v) <= table.range[1]` (recorded as the run-time check), `table.f(signed(v)) % R`,
@@ -156,11 +185,16 @@ UNASSIGNED_2 = 23                                  # the kind after ARGSORT name
 RECIP, ISQRT = 24, 25
 UNASSIGNED_3 = 26                                  # the kind after ISQRT names nothing either: KINDS_END of csrc/witness_plan.hpp
 ARGEXT = 27
+UNASSIGNED_4 = 28                                  # the kind after ARGEXT names nothing either: KINDS_LIMIT of csrc/witness_plan.hpp
+SCATTER, COMPLEMENT, ONEHOT = 29, 30, 31
+KINDS_TOP = 32                                     # the first kind past them all
 KIND_NAMES = ["copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot", "nonlinearity", "nonlinearity_index", "matmul", "rlc",
               "div", "?", "sum", "prod", "gather", "clamp"]
-_LATER_KIND_NAMES = {SORT: "sort", ARGSORT: "argsort", RECIP: "recip", ISQRT: "sqrt", ARGEXT: "argext"}         # KIND_NAMES is the list of the kinds up to CLAMP, as tests pin it: later kinds are named here
+_LATER_KIND_NAMES = {SORT: "sort", ARGSORT: "argsort", RECIP: "recip", ISQRT: "sqrt", ARGEXT: "argext", SCATTER: "scatter", COMPLEMENT: "complement",
+                     ONEHOT: "one_hot"}         # KIND_NAMES is the list of the kinds up to CLAMP, as tests pin it: later kinds are named here
 SORT_TILE, MAX_SORT_COUNT = 2048, 1 << 28                       # csrc/witness_plan.hpp: the keys one workgroup sorts in LDS; the most cells of a sort record
 ARGEXT_CHUNK = 4096                                             # csrc/witness_plan.hpp: the sources one workgroup of an arg-extremum reduces
+SCATTER_TILE = 4096                                             # csrc/witness_plan.hpp: the destinations one workgroup of a scatter / a complement resolves in LDS
 _HEADER = struct.Struct("<20I32s")
 RANGE_ERROR = "value exceeds the decomposition range"
 LOOKUP_ERROR = "lookup input outside the table range"
@@ -170,6 +204,7 @@ GATHER_ERROR = "gather index outside the table"
 SORT_ERROR = EL.SORT_ERROR
 RECIP_ERROR, SQRT_ERROR = EL.RECIP_ERROR, EL.SQRT_ERROR
 ARGEXT_ERROR = EL.ARGEXT_ERROR
+SCATTER_ERROR, ONEHOT_ERROR = EL.SCATTER_ERROR, EL.ONEHOT_ERROR
 MAX_PHASES, MAX_CHALLENGES = 3, 64
 
 
@@ -363,6 +398,40 @@ class _ArgExt(_Sym):
     def __init__(self, src, mode): self.src, self.mode = src, mode
 
 
+class _ScatterJob:
+    """one scatter (`BaseRegion._scattered`): its base, index and source cells, the extent and multiplier of the scattered dimension, the
+    constant offset of every element, and the cells its claim was placed in"""
+
+    def __init__(self, base, index, src, extent, mult, offsets):
+        self.base, self.index, self.src, self.extent, self.mult, self.offsets = base, index, src, extent, mult, offsets
+        self.dst = [None] * len(base)
+
+
+class _Scattered(_Sym):
+    """element i of a scattered tensor"""
+
+    def __init__(self, job, i): self.job, self.i = job, i
+
+
+class _ComplementJob:
+    """one missing set (`BaseRegion._missing`) over the positions 0 .. n - 1: its source cells and the cells its claim was placed in"""
+
+    def __init__(self, n, src):
+        self.n, self.src, self.dst = n, src, [None] * (n - len(src))
+
+
+class _Missing(_Sym):
+    """the i-th smallest position no source names"""
+
+    def __init__(self, job, i): self.job, self.i = job, i
+
+
+class _OneHot(_Sym):
+    """entry `pos` of the one-hot vector of the index in cell a over `classes` (`BaseRegion._one_hot`)"""
+
+    def __init__(self, a, pos, classes): self.a, self.pos, self.classes = a, pos, classes
+
+
 class _Cmp(_Sym):
     def __init__(self, a, op, c):
         assert c == 0
@@ -460,9 +529,9 @@ class _Records:
         self.recs.append(dict(kind=key[0], p0=key[1], p1=key[2], phase=key[-1], scalar=key[3] if len(key) == 5 else None, dst=[], a=[], b=[], dots=[], scans=[]))
         return len(self.recs) - 1
 
-    def _slot(self, key, sources, phase=0):
+    def _slot(self, key, sources, phase=0, floor=0):
         key += (phase,)
-        need = 1 + max((self.rec_of[s] for s in sources), default=-1)
+        need = max(floor, 1 + max((self.rec_of[s] for s in sources), default=-1))     # floor: the record after which sources checked elsewhere are written
         if self.of_key is not None:                # the earliest record of the kind above every record the write reads from
             mine = self.of_key.setdefault(key, [])
             at = bisect.bisect_left(mine, need)
@@ -480,11 +549,11 @@ class _Records:
             raise PlanError("advice cell %d is written twice: not a write-once layout" % dst)
         self.rec_of[dst] = ri
 
-    def emit(self, kind, dst, a, b=None, p0=0, p1=0, reads=(), phase=0):
+    def emit(self, kind, dst, a, b=None, p0=0, p1=0, reads=(), phase=0, floor=0):
         for s in reads:
             if s not in self.rec_of:
                 raise PlanError("advice cell %d is read before it is written" % s)
-        ri = self._slot((kind, p0, p1), reads, phase)
+        ri = self._slot((kind, p0, p1), reads, phase, floor)
         rec = self.recs[ri]
         rec["dst"].append(dst); rec["a"].append(a)
         if b is not None:
@@ -540,6 +609,27 @@ class _Records:
         ri = self._slot((ARGEXT, len(src), mode), src, phase)
         self.recs[ri]["scans"].append((list(src), dst))
         self._claim(dst, ri)
+
+    def emit_scatter(self, job, phase=0):
+        """a SCATTER record: one tensor, never shared"""
+        reads = list(job.base) + list(job.index) + list(job.src)
+        for s in reads:
+            if s not in self.rec_of:
+                raise PlanError("advice cell %d is read before it is written" % s)
+        ri = self._new((SCATTER, len(job.index), job.mult, phase))
+        self.recs[ri]["scans"].append(job)
+        for d in job.dst:
+            self._claim(d, ri)
+
+    def emit_complement(self, job, phase=0):
+        """a COMPLEMENT record: one set, never shared"""
+        for s in job.src:
+            if s not in self.rec_of:
+                raise PlanError("advice cell %d is read before it is written" % s)
+        ri = self._new((COMPLEMENT, job.n, len(job.src), phase))
+        self.recs[ri]["scans"].append(job)
+        for d in job.dst:
+            self._claim(d, ri)
 
     def emit_scan(self, challenge, src, dst, phase):
         """one RLC scan: step t reads cell src[t] and writes cell dst[t]"""
@@ -676,6 +766,10 @@ class RecordingRegion(EL.BaseRegion):
     percent, softmax, softmax_axes, mean_of_squares = _refused("percent"), _refused("softmax"), _refused("softmax_axes"), _refused("mean_of_squares")
     select, argmax, argmin, argmax_axes, argmin_axes = _refused("select"), _refused("argmax"), _refused("argmin"), _refused("argmax_axes"), _refused("argmin_axes")
     max_pool, sumpool, _arg_extremum = _refused("max_pool"), _refused("sumpool"), _refused("argmax / argmin")
+    select_elements, linearize_element_index, gather, gather_elements = _refused("select_elements"), _refused("linearize_element_index"), _refused("gather"), _refused("gather_elements")
+    one_hot, one_hot_axis, _one_hot, shuffles, _claimed_indices = _refused("one_hot"), _refused("one_hot_axis"), _refused("one_hot"), _refused("shuffles"), _refused("shuffles")
+    get_missing_set_elements, _missing = _refused("get_missing_set_elements"), _refused("get_missing_set_elements")
+    scatter_elements, _scattered = _refused("scatter_elements"), _refused("scatter_elements")
     del _counted, _refused
 
 
@@ -732,6 +826,8 @@ class LookupRecordingRegion(RecordingRegion):
         self._lookup_src = {}                      # source cell -> (its symbol, table) of the lookups recorded so far
         self._scan = None                          # the steps of the `sum` / `prod` being laid out
         self.gather_tables, self._gather_idx = [], {}     # the cell lists GATHER records index, in order of first use
+        self._keyed_rows = None                           # the table whose keys `row_at` has found to be its positions: the latest one
+        self._gather_of = (None, None, None, 0)           # (the placed table, the coordinate, its cells, the record after them) of the latest pick
         self.param_values = None                   # record_plan's parameter list: what a _Param stands for
 
     def nonlinearity(self, vals, name):
@@ -799,6 +895,77 @@ class LookupRecordingRegion(RecordingRegion):
     select, argmax_axes, argmin_axes = EL.BaseRegion.select, EL.BaseRegion.argmax_axes, EL.BaseRegion.argmin_axes
     max_pool, sumpool = EL.BaseRegion.max_pool, EL.BaseRegion.sumpool
 
+    # ---- gather / scatter / one-hot: BaseRegion's ops around `_scattered`, `_missing`, `_one_hot` and `_claimed_indices` ------------------------------
+    def scatter_elements(self, input, dims, index, index_dims, src, dim):
+        self.n_ops += 1
+        return EL.BaseRegion.scatter_elements(self, input, dims, index, index_dims, src, dim)
+
+    def one_hot(self, index, num_classes):
+        self.n_ops += 1
+        if not isinstance(index.v, _Cell):                # (`signed` of any other symbol is refused without a name)
+            raise PlanError("a one-hot over an index that is not an assigned cell")
+        return EL.BaseRegion.one_hot(self, index, num_classes)
+
+    def gather(self, vals, dims, index, dim):
+        self.n_ops += 1
+        return EL.BaseRegion.gather(self, vals, dims, index, dim)
+
+    def gather_elements(self, vals, dims, index, index_dims, dim):
+        self.n_ops += 1
+        return EL.BaseRegion.gather_elements(self, vals, dims, index, index_dims, dim)
+
+    def get_missing_set_elements(self, vals, fullset, ordered):
+        self.n_ops += 1
+        return EL.BaseRegion.get_missing_set_elements(self, vals, fullset, ordered)
+
+    select_elements, linearize_element_index, one_hot_axis, shuffles = (EL.BaseRegion.select_elements, EL.BaseRegion.linearize_element_index,
+                                                                         EL.BaseRegion.one_hot_axis, EL.BaseRegion.shuffles)
+
+    @staticmethod
+    def _cells_of(vals, what):
+        if not all(isinstance(v.v, _Cell) for v in vals):
+            raise PlanError("%s over values that are not assigned cells" % what)
+        return [v.v.idx for v in vals]
+
+    def _positions(self, fullset):
+        """True when the full set is the constants 0 .. n - 1 in order"""
+        return all(v.const and isinstance(v.v, (int, np.integer)) and v.v == j for j, v in enumerate(fullset))
+
+    def _scattered(self, input, index, src, dims, index_dims, dim):
+        """BaseRegion._scattered on symbols: one SCATTER record over the cells the base, the index and the source are assigned in, emitted
+        once the layout has placed the whole claim"""
+        assert len(index) == len(src) and all(a <= b for t, (a, b) in enumerate(zip(index_dims, dims)) if t != dim)
+        mult = self._strides(dims)
+        offsets = [sum(coord[t] * mult[t] for t in range(len(dims)) if t != dim) for coord in self._coords(index_dims)]
+        job = _ScatterJob(self._cells_of(input, "a scatter"), self._cells_of(index, "a scatter"), self._cells_of(src, "a scatter"), dims[dim], mult[dim], offsets)
+        return [_Scattered(job, i) for i in range(len(input))]
+
+    def _missing(self, vals, fullset):
+        """BaseRegion._missing on symbols: one COMPLEMENT record over the cells the values are assigned in; the full set must be the
+        positions"""
+        if not self._positions(fullset):
+            raise PlanError("a missing-set over a full set that is not the positions 0 .. n - 1")
+        if len(vals) > len(fullset):
+            raise PlanError("a missing-set of more values than the full set holds")
+        job = _ComplementJob(len(fullset), self._cells_of(vals, "a missing-set"))
+        return [_Missing(job, i) for i in range(len(job.dst))]
+
+    def _one_hot(self, s, num_classes):
+        """BaseRegion._one_hot on the symbol of the index's signed value: ONEHOT elements"""
+        if not isinstance(s, _Cell):
+            raise PlanError("a one-hot over an index that is not an assigned cell")
+        if not 1 <= num_classes < 1 << 32:
+            raise PlanError("one-hot classes outside [1, 2^32)")
+        return [_OneHot(s, j, num_classes) for j in range(num_classes)]
+
+    def _claimed_indices(self, output, input):
+        """BaseRegion._claimed_indices on symbols: over the positions 0 .. n - 1 the first unused position that holds an output element's value
+        is that value itself -- a COPY of the element's cell"""
+        if not self._positions(input):
+            raise PlanError("a missing-set over a full set that is not the positions 0 .. n - 1")
+        self._cells_of(output, "a permutation argument")
+        return [v.v for v in output]
+
     def _arg_extremum(self, vals, mode):
         """BaseRegion._arg_extremum on symbols: one segment of an ARGEXT record over the cells the values are assigned in, emitted when the
         layout places the claim"""
@@ -817,12 +984,13 @@ class LookupRecordingRegion(RecordingRegion):
     def row_at(self, table_rows, index):
         """BaseRegion.row_at on symbols: the key coordinate is the index value itself, every other coordinate a GATHER element over the
         cells of the dynamic table the pick is looked up in -- which must be this very list, with the positions 0 .. n - 1 as its keys"""
-        for r, row in enumerate(table_rows):
+        for r, row in enumerate(() if table_rows is self._keyed_rows else table_rows):     # (the picks of one lookup share the list: checked once)
             key = row[0].v if isinstance(row[0], EL.Val) else row[0]
             if isinstance(key, _Param) and self.param_values is not None:
                 key = self.param_values[key.idx]
             if not isinstance(key, (int, np.integer)) or key % R != r:
                 raise PlanError("a gather over a table whose keys are not its positions")
+        self._keyed_rows = table_rows
         if not isinstance(index.v, (_Input, _Cell)):
             raise PlanError("a gather index that is a %s value" % type(index.v).__name__)
         pick = _Pick(table_rows)
@@ -850,6 +1018,15 @@ class LookupRecordingRegion(RecordingRegion):
                 self.out.emit_sort(v.kind, v.seg.mode, v.seg.src, placed)
         elif isinstance(v, _ArgExt):
             self.out.emit_argext(v.mode, v.src, dst)
+        elif isinstance(v, (_Scattered, _Missing)):
+            placed = v.job.dst
+            if placed[v.i] is not None:
+                raise PlanError("a claimed element is placed twice")
+            placed[v.i] = dst
+            if None not in placed:
+                (self.out.emit_scatter if isinstance(v, _Scattered) else self.out.emit_complement)(v.job)
+        elif isinstance(v, _OneHot):
+            self.out.emit(ONEHOT, dst, v.a.idx, v.pos, p0=v.classes, reads=(v.a.idx,))
         elif isinstance(v, _Clamp):
             if not -(1 << 31) <= v.lo <= v.hi < 1 << 31:
                 raise PlanError("clamp bounds beyond 32 bits")
@@ -869,11 +1046,17 @@ class LookupRecordingRegion(RecordingRegion):
             rows, placed = getattr(self, "dyn_table", (None, None))
             if rows is not v.pick.rows or v.pick.key is None:
                 raise PlanError("a gather pick outside the dynamic lookup over its table")
-            cells = tuple(placed[r][v.t].v.idx for r in range(len(rows)))
-            if cells not in self._gather_idx:
-                self._gather_idx[cells] = len(self.gather_tables)
-                self.gather_tables.append(cells)
-            self.out.emit(GATHER, dst, v.pick.key, p0=self._gather_idx[cells], p1=len(cells), reads=(v.pick.key,) + cells)
+            if self._gather_of[0] is not placed or self._gather_of[1] != v.t:       # the picks of one lookup share the table: its cells are listed, and looked up, once
+                cells = tuple(placed[r][v.t].v.idx for r in range(len(rows)))
+                for c in cells:
+                    if c not in self.out.rec_of:
+                        raise PlanError("advice cell %d is read before it is written" % c)
+                if cells not in self._gather_idx:
+                    self._gather_idx[cells] = len(self.gather_tables)
+                    self.gather_tables.append(cells)
+                self._gather_of = (placed, v.t, cells, 1 + max(self.out.rec_of[c] for c in cells))
+            _, _, cells, floor = self._gather_of
+            self.out.emit(GATHER, dst, v.pick.key, p0=self._gather_idx[cells], p1=len(cells), reads=(v.pick.key,), floor=floor)
         elif isinstance(v, _Looked):
             self._asserted(v.cell, v.table)
             self._lookup_src[v.cell.idx] = (v.cell, v.table)
@@ -1126,6 +1309,15 @@ class WitnessPlan:
                 src, dst = [c for sc in rec["scans"] for c in sc[0]], [sc[1] for sc in rec["scans"]]     # segment-major
                 n_cells += len(dst)
                 records.append([ARGEXT, len(dst), rec["p0"], rec["p1"], push(dst), push(src), 0, phase])
+            elif rec["kind"] == SCATTER:                   # b: the extent, the index cells, the source cells, the constant offsets
+                job = rec["scans"][0]
+                n_cells += len(job.dst)
+                records.append([SCATTER, len(job.dst), len(job.index), job.mult, push(job.dst), push(job.base),
+                                push([job.extent] + list(job.index) + list(job.src) + list(job.offsets)), phase])
+            elif rec["kind"] == COMPLEMENT:
+                job = rec["scans"][0]
+                n_cells += len(job.dst)
+                records.append([COMPLEMENT, len(job.dst), job.n, len(job.src), push(job.dst), push(job.src), 0, phase])
             elif rec["kind"] == RECIP:
                 n_cells += len(rec["dst"])
                 records.append([RECIP, len(rec["dst"]), rec["p0"], rec["p1"], push(rec["dst"]), push(rec["a"]), rec["scalar"], phase])
@@ -1271,9 +1463,9 @@ def validate(plan):
     total = 0
     col_phase, last_phase = [None] * plan.n_advice, 0
     for ri, (kind, count, p0, p1, dst, a, b, phase) in enumerate(plan.records.tolist()):
-        if kind > ARGEXT or kind in (UNASSIGNED, UNASSIGNED_2, UNASSIGNED_3):
+        if kind >= KINDS_TOP or kind in (UNASSIGNED, UNASSIGNED_2, UNASSIGNED_3, UNASSIGNED_4):
             raise PlanError("witness plan: record %d: unknown kind %d" % (ri, kind))
-        if count == 0:
+        if count == 0 and kind != COMPLEMENT:             # (nothing missing: a complement that writes no cell)
             raise PlanError("witness plan: record %d is empty" % ri)
         if phase >= plan.n_phases:
             raise PlanError("witness plan: record %d (%s): phase out of range" % (ri, kind_name(kind)))
@@ -1317,6 +1509,23 @@ def validate(plan):
                 raise PlanError("witness plan: record %d (%s): bad arg-extremum shape" % (ri, kind_name(kind)))
             d = _span(plan, dst, count, "dst", ri)
             srcs = _span(plan, a, count * p0, "a", ri)
+        elif kind == SCATTER:                             # p0 = elements, p1 = multiplier, b: extent, index cells, source cells, offsets
+            words = len(plan.pool)
+            ok = (p0 >= 1 and p1 >= 1 and count <= MAX_SORT_COUNT and dst <= words and count <= words - dst and a <= words and count <= words - a
+                  and b <= words and 1 + 3 * p0 <= words - b)
+            if ok:
+                extent = int(plan.pool[b])
+                ok = extent >= 1 and int(plan.pool[b + 1 + 2 * p0:b + 1 + 3 * p0].max()) + (extent - 1) * p1 < count
+            if not ok:
+                raise PlanError("witness plan: record %d (%s): bad scatter shape" % (ri, kind_name(kind)))
+            d = _span(plan, dst, count, "dst", ri)
+            srcs = np.concatenate([_span(plan, a, count, "a", ri), plan.pool[b + 1:b + 1 + 2 * p0]])
+        elif kind == COMPLEMENT:                          # p0 = n, p1 = sources, count = n - sources
+            words = len(plan.pool)
+            if p1 > p0 or count != p0 - p1 or p0 > MAX_SORT_COUNT or dst > words or count > words - dst or a > words or p1 > words - a:
+                raise PlanError("witness plan: record %d (%s): bad complement shape" % (ri, kind_name(kind)))
+            d = _span(plan, dst, count, "dst", ri)
+            srcs = _span(plan, a, p1, "a", ri)
         elif kind == DOT:
             w, ns = p0, p1
             if w == 0 or ns == 0 or count * ns * w > len(plan.pool):
@@ -1332,7 +1541,7 @@ def validate(plan):
             d = _span(plan, dst, count, "dst", ri)
             x = _span(plan, a, count, "a", ri)
             srcs = np.zeros(0, np.uint32)
-            if kind in (COPY, ADD, SUB, MUL, HINT, RCIDX, INVZ, TABLE, TBLIDX, DIVC, GATHER, CLAMP, RECIP, ISQRT):
+            if kind in (COPY, ADD, SUB, MUL, HINT, RCIDX, INVZ, TABLE, TBLIDX, DIVC, GATHER, CLAMP, RECIP, ISQRT, ONEHOT):
                 srcs = x
             else:
                 lim = {CONST: len(plan.consts), INPUT: plan.n_inputs, PARAM: len(plan.params)}[kind]
@@ -1366,6 +1575,10 @@ def validate(plan):
                     raise PlanError("witness plan: record %d (%s): zero square-root scale" % (ri, kind_name(kind)))
                 if p1 != 0:
                     raise PlanError("witness plan: record %d (%s): a square-root record with a second parameter" % (ri, kind_name(kind)))
+            if kind == ONEHOT:                            # b: the position each element stands for, plain words
+                _span(plan, b, count, "b", ri)
+                if p0 == 0:
+                    raise PlanError("witness plan: record %d (%s): zero one-hot classes" % (ri, kind_name(kind)))
             if kind in (TABLE, TBLIDX) and p0 >= len(plan.tables):
                 raise PlanError("witness plan: record %d (%s): lookup table index out of range" % (ri, KIND_NAMES[kind]))
         if (d >= cells).any() or (srcs >= cells).any():
@@ -1481,6 +1694,24 @@ def run_plan_host(plan, x, challenges=None, phase=None):
                 seg = vals[g * p0:(g + 1) * p0]
                 cells[P[dst + g]] = seg.index(min(seg) if p1 else max(seg))     # the first position that holds the extremum
             continue
+        if kind == SCATTER:                                # the greatest element on a target wins: the elements in order, each overwriting
+            extent, m = P[b], p0
+            idx = [EL.signed(cells[c]) for c in P[b + 1:b + 1 + m]]
+            for j, sv in enumerate(idx):                   # every index a lane reads, the smallest failing element first
+                if sv < 0 or sv >= extent or abs(sv) >= 1 << 62:
+                    raise AssertionError("%s (%s record %d, element %d)" % (SCATTER_ERROR, kind_name(kind), ri, j))
+            out = [cells[c] for c in P[a:a + count]]
+            for j, sv in enumerate(idx):
+                out[sv * p1 + P[b + 1 + 2 * m + j]] = cells[P[b + 1 + m + j]]
+            for i, v in enumerate(out):
+                cells[P[dst + i]] = v
+            continue
+        if kind == COMPLEMENT:                             # the positions no source names, ascending, as many as the record has cells
+            named = {EL.signed(cells[c]) for c in P[a:a + p1]}
+            rest = [v for v in range(p0) if v not in named]
+            for i in range(count):
+                cells[P[dst + i]] = rest[i]
+            continue
         if kind in (SORT, ARGSORT):
             vals = [EL.signed(cells[c]) for c in P[a:a + count]]
             for e, sv in enumerate(vals):                  # every source a lane reads, the smallest failing element first
@@ -1530,6 +1761,11 @@ def run_plan_host(plan, x, challenges=None, phase=None):
                 if abs(s) >= 1 << 62 or s * p0 >= 1 << 62:
                     raise AssertionError("%s (%s record %d, element %d)" % (SQRT_ERROR, kind_name(kind), ri, i))
                 v = EL.sqrt_claim(s, p0)
+            elif kind == ONEHOT:
+                s = EL.signed(cells[ia])
+                if s < 0 or s >= p0 or abs(s) >= 1 << 62:
+                    raise AssertionError("%s (%s record %d, element %d)" % (ONEHOT_ERROR, kind_name(kind), ri, i))
+                v = int(s == P[b + i])
             elif kind == RCIDX:
                 s = EL.signed(cells[ia])
                 if abs(s) >= 1 << 62:                 # what a lane holds in 64 bits; the layout only range-checks signs and digits

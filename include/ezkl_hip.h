@@ -252,7 +252,7 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  * A PLAN is the layout recorded once per circuit (ezkl_amd/witness_plan.py; byte layout: csrc/witness_plan.hpp): a list of records, each a
  * batch of cell writes of one kind (copy, const, input, param, add / sub / mult, decompose hint, range-check index, inverse-or-zero, dot,
  * static-lookup output, static-lookup table-column index, integer matmul, random linear combination, rounded division by a constant, running sum, running product, gather, clamp, sort, argsort,
- * claimed reciprocal, claimed square root, claimed arg-extremum) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
+ * claimed reciprocal, claimed square root, claimed arg-extremum, claimed scatter, claimed complement, claimed one-hot vector) with u32 cell indices column * 2^k + row, a table of int64 parameters, a table
  * of constants and -- header words 12 / 13 (n_tables, n_table_values; zero, as reserved words were, in a plan without lookups), after the
  * pool -- a directory of {lo (int32), n, col_size, offset} per static lookup table and the tables' values f(lo + i) as int64.  The version
  * word stays 1.  A lookup record names its source cells and a table: with s the signed value of the cell, the output kind writes
@@ -328,6 +328,24 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *   of the record are.  Segments of up to 64 sources are reduced side by side in a wave, up to 4096 by one workgroup each, in ONE launch; a
  *   longer one takes two launches through the key scratch the plan owns (shared with the sort kinds, sized at upload to the larger need):
  *   `launches` counts them all.
+ * GATHER, SCATTER AND ONE-HOT (kinds 29 - 31; kind 28 stays unassigned as 16, 23 and 26 do, the version word stays 1 and every earlier blob keeps
+ *   its bytes): the three claims of the indexed family that depend on the data.  scatter (29) -- ONE tensor, the claimed output of
+ *   layouts.rs:2313-2379 `scatter_elements`: count = n destination cells dst[i], a = the n base cells, p0 = m >= 1 elements, p1 = the multiplier
+ *   of the scattered dimension >= 1, b = the pool offset of 1 + 3m words: the extent of that dimension, m index cells, m source cells, m
+ *   constant offsets (plain words).  With s_j the signed value of index cell j its target is t_j = s_j * p1 + off_j; dst[i] gets the value of
+ *   source cell j for the GREATEST j with t_j == i (the later element wins), else the value of base cell i.  p0, p1 or the extent zero, count >
+ *   2^28, an array past the pool or an offset with off_j + (extent - 1) * p1 >= count is refused on upload ("bad scatter shape").  s_j < 0,
+ *   s_j >= extent or |s_j| >= 2^62 is reported as a value beyond its decomposition is ("scatter index outside the tensor", element = j, every
+ *   such j counted) and the record writes none of its cells.  complement (30) -- the claimed output of layouts.rs:2213-2286
+ *   `get_missing_set_elements` over the positions: p0 = n, p1 = m <= n source cells at a, count = n - m destination cells (zero is legal: no
+ *   cell, no launch), b unused; dst[i] gets the i-th smallest v in [0, n) that is the signed value of no source cell; a source outside [0, n)
+ *   or beyond 62 bits removes nothing; it never fails.  p1 > p0, count != p0 - p1, p0 > 2^28 or an array past the pool is refused on upload
+ *   ("bad complement shape").  one_hot (31) -- element-wise, the claimed vector of layouts.rs:1398-1442 `one_hot`: a = the index cell of the
+ *   element, b = the pool offset of the per-element positions (plain words), p0 = the number of classes >= 1 ("zero one-hot classes"), p1 = 0:
+ *   1 if the signed value equals the position, else 0.  s < 0, s >= p0 or |s| >= 2^62 is reported likewise ("one-hot index outside the
+ *   classes") and the lane writes nothing.  A scatter or a complement of up to 4096 cells runs in ONE launch, one workgroup with its winner
+ *   words or presence flags in LDS; a longer one takes three (fill, mark, store) or up to five (fill, mark, count, offsets, compact) launches
+ *   through the scratch the plan owns (shared with the sort and arg-extremum kinds, sized at upload to the largest need): `launches` counts them all.
  * tile: a plan of a tiled circuit writes rows [0, U) of the block-0 and shared columns; the circuit is those U rows repeated T times down every
  *   column and copied into the columns of the other blocks.  For every pair, rows [t * U, (t + 1) * U) of column dst get rows [0, U) of column
  *   src: t = 0 .. T - 1 when dst != src, t = 1 .. T - 1 when dst == src.  Rows >= T * U and columns outside the pair list are left as they are.
