@@ -938,6 +938,13 @@ struct DevPlan {
     void* done_cols[MAX_ADVICE] = {nullptr};
 };
 thread_local std::string t_wit_error;
+// the bytes of sort_keys a record's launchers go through
+size_t wit_scratch_bytes(const Rec& r) {
+    if (r.kind == SORT || r.kind == ARGSORT)                      // segments * P * 16 B of a sort that leaves LDS
+        return wit_sort_padded(r.p0) > SORT_TILE ? (size_t)(r.count / r.p0) * wit_sort_padded(r.p0) * sizeof(SortKey) : 0;
+    if (r.kind == ARGEXT) return wit_argext_slots(r.count, r.p0) * sizeof(SortKey);
+    return wit_scatter_scratch(r);                                // SCATTER, COMPLEMENT; every other kind: none
+}
 
 void plan_release(DevPlan* p) {
     for (void* q : {(void*)p->pool, (void*)p->outputs, (void*)p->params, (void*)p->consts, (void*)p->table_values, (void*)p->inputs, (void*)p->outs, (void*)p->status, (void*)p->sort_keys})
@@ -1067,14 +1074,8 @@ int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out
         memcpy(v.v, h.consts.data() + 32 * i, 32);
         consts[i] = Fr::to_mont(v);
     }
-    size_t sort_bytes = 0;                                        // segments * P * 16 B of the largest sort that leaves LDS
-    for (const Rec& r : h.recs)
-        if ((r.kind == SORT || r.kind == ARGSORT) && wit_sort_padded(r.p0) > SORT_TILE)
-            sort_bytes = std::max(sort_bytes, (size_t)(r.count / r.p0) * wit_sort_padded(r.p0) * sizeof(SortKey));
-        else if (r.kind == ARGEXT)                                // the records run one after another on the stream: they share the scratch
-            sort_bytes = std::max(sort_bytes, wit_argext_slots(r.count, r.p0) * sizeof(SortKey));
-        else if (r.kind == SCATTER || r.kind == COMPLEMENT)
-            sort_bytes = std::max(sort_bytes, wit_scatter_scratch(r));
+    size_t sort_bytes = 0;                                        // the records run one after another on the stream: they share the scratch
+    for (const Rec& r : h.recs) sort_bytes = std::max(sort_bytes, wit_scratch_bytes(r));
     struct Up { void** dev; const void* src; size_t bytes; };
     const Up ups[] = {{(void**)&p->pool, h.pool.data(), h.pool.size() * 4},       {(void**)&p->outputs, h.outputs.data(), h.outputs.size() * 4},
                       {(void**)&p->params, h.params.data(), h.params.size() * 8}, {(void**)&p->consts, consts.data(), consts.size() * 32},
@@ -1186,23 +1187,9 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
         const Rec& r = h.recs[ri];
         if (r.phase != phase) continue;
         switch (r.kind) {
-        case COPY: launch_elem<COPY>(st, cols, k, p, r, (uint32_t)ri); break;
-        case CONST: launch_elem<CONST>(st, cols, k, p, r, (uint32_t)ri); break;
-        case INPUT: launch_elem<INPUT>(st, cols, k, p, r, (uint32_t)ri); break;
-        case PARAM: launch_elem<PARAM>(st, cols, k, p, r, (uint32_t)ri); break;
-        case ADD: launch_elem<ADD>(st, cols, k, p, r, (uint32_t)ri); break;
-        case SUB: launch_elem<SUB>(st, cols, k, p, r, (uint32_t)ri); break;
-        case MUL: launch_elem<MUL>(st, cols, k, p, r, (uint32_t)ri); break;
-        case HINT: launch_elem<HINT>(st, cols, k, p, r, (uint32_t)ri); break;
-        case RCIDX: launch_elem<RCIDX>(st, cols, k, p, r, (uint32_t)ri); break;
-        case INVZ: launch_elem<INVZ>(st, cols, k, p, r, (uint32_t)ri); break;
-        case TABLE: launch_elem<TABLE>(st, cols, k, p, r, (uint32_t)ri); break;
-        case TBLIDX: launch_elem<TBLIDX>(st, cols, k, p, r, (uint32_t)ri); break;
-        case DIVC: launch_elem<DIVC>(st, cols, k, p, r, (uint32_t)ri); break;
-        case GATHER: launch_elem<GATHER>(st, cols, k, p, r, (uint32_t)ri); break;
-        case CLAMP: launch_elem<CLAMP>(st, cols, k, p, r, (uint32_t)ri); break;
-        case RECIP: launch_elem<RECIP>(st, cols, k, p, r, (uint32_t)ri); break;
-        case ISQRT: launch_elem<ISQRT>(st, cols, k, p, r, (uint32_t)ri); break;
+#define EZ_WIT_ELEM(KIND) case KIND: launch_elem<KIND>(st, cols, k, p, r, (uint32_t)ri); break;
+        EZ_WIT_ELEM(COPY) EZ_WIT_ELEM(CONST) EZ_WIT_ELEM(INPUT) EZ_WIT_ELEM(PARAM) EZ_WIT_ELEM(ADD) EZ_WIT_ELEM(SUB) EZ_WIT_ELEM(MUL) EZ_WIT_ELEM(HINT) EZ_WIT_ELEM(RCIDX)
+        EZ_WIT_ELEM(INVZ) EZ_WIT_ELEM(TABLE) EZ_WIT_ELEM(TBLIDX) EZ_WIT_ELEM(DIVC) EZ_WIT_ELEM(GATHER) EZ_WIT_ELEM(CLAMP) EZ_WIT_ELEM(RECIP) EZ_WIT_ELEM(ISQRT)
         case SUMACC:
             hipLaunchKernelGGL(wit_acc_kernel<SUMACC>, dim3(cdiv((size_t)r.count * DOT_LANES, 64)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, r.count, r.p0, r.p1,
                                p->status);
@@ -1214,7 +1201,8 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
         case SORT: launches += launch_sort<SORT>(st, cols, k, p, r, (uint32_t)ri) - 1; break;
         case ARGSORT: launches += launch_sort<ARGSORT>(st, cols, k, p, r, (uint32_t)ri) - 1; break;
         case ARGEXT: launches += launch_argext(st, cols, k, p, r, (uint32_t)ri) - 1; break;
-        case ONEHOT: launch_elem<ONEHOT>(st, cols, k, p, r, (uint32_t)ri); break;
+        EZ_WIT_ELEM(ONEHOT)                                        // (here, not above: the kernels are emitted in the order of their first use)
+#undef EZ_WIT_ELEM
         case SCATTER: launches += launch_scatter(st, cols, k, p, r, (uint32_t)ri) - 1; break;
         case COMPLEMENT: {
             const uint32_t made = launch_complement(st, cols, k, p, r);
@@ -1232,9 +1220,13 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
             hipLaunchKernelGGL(wit_rlc_kernel, dim3(cdiv((size_t)r.count * RLC_LANES, 64)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, r.count, r.p1, chal[r.p0],
                                p->status);
             break;
-        default:
+        case DOT:
             hipLaunchKernelGGL(wit_dot_kernel, dim3(cdiv((size_t)r.count * DOT_LANES, 64)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, p->pool + r.b, r.count, r.p0, r.p1,
                                p->status);
+            break;
+        default:                                                   // (`parse` refuses every kind this loop does not name)
+            t_wit_error = "witness: unhandled record kind " + std::to_string(r.kind);
+            return EZKL_ERR_INVALID;
         }
         EZ_HIP(hipGetLastError());
         launches++;
@@ -1256,20 +1248,9 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
     status[3] = launches;
     if (dev_status[0]) {
         const uint32_t ri = (uint32_t)(status[1] >> 32), el = (uint32_t)status[1];
-        const uint32_t kind = ri < h.recs.size() ? h.recs[ri].kind : (uint32_t)KINDS_END;
-        const char* what = kind == TABLE || kind == TBLIDX ? "witness: lookup input outside the table range ("
-                           : kind == MATMUL               ? "witness: einsum operand outside the exact-product range ("
-                           : kind == DIVC                 ? "witness: rebase dividend outside the exact-division range ("
-                           : kind == GATHER               ? "witness: gather index outside the table ("
-                           : kind == SORT || kind == ARGSORT ? "witness: sort key beyond 62 bits ("
-                           : kind == RECIP                ? "witness: reciprocal operand beyond 62 bits ("
-                           : kind == ISQRT                ? "witness: square-root operand outside the exact range ("
-                           : kind == ARGEXT               ? "witness: arg-extremum key beyond 62 bits ("
-                           : kind == SCATTER              ? "witness: scatter index outside the tensor ("
-                           : kind == ONEHOT               ? "witness: one-hot index outside the classes ("
-                                                          : "witness: value exceeds the decomposition range (";
-        t_wit_error = std::string(what) + kind_name(kind) + " record " + std::to_string(ri) +
-                      ", element " + std::to_string(el) + "; " + std::to_string(dev_status[0]) + (kind == MATMUL ? " operand reads in all)" : " cells in all)");
+        const uint32_t kind = ri < h.recs.size() ? h.recs[ri].kind : (uint32_t)KINDS_TOP;     // (KINDS_TOP: no such record)
+        t_wit_error = std::string("witness: ") + failure_words(kind) + " (" + kind_name(kind) + " record " + std::to_string(ri) + ", element " + std::to_string(el) + "; " +
+                      std::to_string(dev_status[0]) + " " + (kind < KINDS_TOP ? KINDS[kind].unit : "cells") + " in all)";
         return EZKL_ERR_INVALID;
     }
     p->done_phase = (int)phase;

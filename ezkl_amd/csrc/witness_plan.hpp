@@ -4,79 +4,17 @@
 //
 // Layout (little-endian): 20 x u32 header -- magic "EZWP", version, k, n_advice, n_records, n_inputs, n_params, n_consts, n_outputs,
 // n_cells, n_words, n_ops, n_tables, n_table_values, n_challenges, n_phases (0 reads as 1), 4 reserved -- and the 32-byte parameter hash;
-// then n_params x int64, n_consts x
-// 32 bytes (canonical Fr), n_records x {kind, count, p0, p1, dst, a, b, phase}, n_outputs x u32 cells, n_words x u32 pool, n_tables x
-// {lo (int32), n, col_size, offset} and n_table_values x int64: the static lookup tables, f(lo + i) as signed integers (both sections
-// are empty in a plan without lookups: the two header words were reserved zeros).  Cells are numbered column * 2^k + row.
-// A TABLE / TBLIDX record: a = source cell, p0 = table index; with s the signed value of the cell, values[offset + (s - lo)] as a field
-// element / (s - lo) // col_size.  s outside [lo, lo + n - 1] is a run-time failure of the lane, as a value beyond its decomposition is.
-// PHASES (second-phase advice: the Freivalds einsum).  Header words 14 / 15 and the eighth word of a record were reserved zeros, so every
-// one-phase blob keeps its bytes.  A record is replayed by the run of its phase; phases are non-decreasing along the list and below
-// n_phases; a column belongs to the phase of the records that write it (two phases: refused; no record: phase 0); INPUT and MATMUL records
-// belong to phase 0, with which the inputs are uploaded.
-// A MATMUL record: count = m * n, p0 = kd, p1 = n; dst = m * n cells row-major, a = m * kd and b = kd * n INPUT indices;
-// dst[i * n + j] = sum_t in[a[i * kd + t]] * in[b[t * n + j]] over the integers, then integer_rep_to_felt.  Every operand must satisfy
-// |v| < 2^31 (kd * 2^62 < 2^127: two 64-bit words hold the sum); one outside is a run-time failure of the lane, element = its place in a, or
-// m * kd + its place in b.
-// An RLC record: count scans of p1 steps with challenge p0 (< n_challenges), step-major and dense (no 0xffffffff entries): out[0] = c * v[0],
-// out[t] = out[t - 1] * c + c * v[t], v[t] = cell a[t * count + d], out[t] -> cell dst[t * count + d].
-// A DIVC record (the rebase division of an MLP layer, layouts.rs:219-267 `div`): a = source cell, p0 = d >= 1 (zero: refused); with s the
-// signed value of the cell, sgn(s) * ((|s| + d / 2) / d) -- s / d rounded half away from zero.  |s| >= 2^52 is a run-time failure of the lane.
-// Kind 16 is unassigned (refused as an unknown kind); SUMACC, PRODACC, GATHER and CLAMP are 17 .. 20.
-// A SUMACC / PRODACC record (BaseRegion._accumulate, layouts.rs:2472-2621 `sum` / `prod`): count scans of p1 steps with p0 operands each,
-// step-major as DOT is; step s of scan d folds the cells a[(s * p0 + j) * count + d], j < p0 (0xffffffff: no operand -- the duplicated row
-// at the top of a new column), into the running value (0 at the start of a sum, 1 of a product) and writes it to dst[s * count + d]
-// (0xffffffff: the scan has no such step: a ragged record).  b is unused and zero.  p0 or p1 zero, or an index array past the pool: "bad
-// scan shape".
-// A GATHER record: a = the cell holding the index, p0 = the pool offset of the table's cell list, p1 = its length n >= 1 ("empty gather
-// table", "gather table runs past the pool"); with s the signed value of the index cell the destination gets the value of cell
-// pool[p0 + s].  Every cell of the list is one a lane can read: in range and written by an earlier record.  s < 0, s >= n or |s| >= 2^62
-// is a run-time failure of the lane ("gather index outside the table"), tested before pool[p0 + s] is read.
-// A CLAMP record: a = source cell, p0 = lo, p1 = hi (int32, lo <= hi, else "bad clamp bounds"): min(max(s, lo), hi); a value beyond 62 bits
-// clamps by its sign.  It never fails.
-// A SORT (21) / ARGSORT (22) record (layouts.rs:1158-1275 `_sort_ascending`, the witness of its sorted tensor and of the claimed indices of
-// `shuffles`): count destination cells dst[e] in segments of p0 = n elements (n >= 1, count % n == 0, count <= 2^28, else "bad sort shape"),
-// p1 = mode (0 or 1, else "bad sort shape"), a = the source cells, segment-major and dense, b unused and zero.  The order of a segment is
-// by (signed value, position), the position ascending among equal values for mode 0 and descending for mode 1: a total order.  SORT:
-// dst[s * n + i] gets the i-th smallest signed value of the cells a[s * n .. + n) as integer_rep_to_felt maps it; ARGSORT: the position, in
-// [0, n), of that element in its segment.  A source with |s| >= 2^62 is a run-time failure of the lane ("sort key beyond 62 bits"), element
-// = its place in a; its segment writes none of its cells.  SORT_TILE is the number of keys one workgroup of csrc/witness.hip sorts in LDS.
-// Kind 23 (N_KINDS, the end of KIND_NAMES) is unassigned as 16 is; RECIP and ISQRT are 24 and 25, KINDS_END follows them, `kind_name`
-// names every kind.
-// A RECIP record (the claimed reciprocal of `recip`, layouts.rs:300-385): a = source cell, b = the index of `zero_inverse` in the constants
-// section (a scalar word, not a pool offset: past the constants is "zero-inverse index past the constants"), S = p0 | p1 << 32 = input
-// scale * output scale, 1 <= S < 2^62 (else "reciprocal scale outside [1, 2^62)").  With x the signed value of the cell: x = 0 -> the
-// constant; x > 0 -> ceil((2S - x) / (2x)) = (2S + x - 1) / (2x); x < 0 -> -((2S + |x|) / (2|x|)) -- the one value the gates of
-// `optimum_convex_function` accept, the smallest integer minimiser of |y * x - S|.  |x| >= 2^62 is a run-time failure of the lane
-// ("reciprocal operand beyond 62 bits").
-// An ISQRT record (the claimed root of `sqrt`, layouts.rs:408-459): a = source cell, b = 0, p0 = input scale >= 1 ("zero square-root
-// scale"), p1 = 0 ("a square-root record with a second parameter").  With T = x * p0: T <= 0 -> 0; else r = floor(sqrt(T)), r + (T - r * r > r),
-// the integer nearest to sqrt(T).  |x| >= 2^62 or T >= 2^62 is a run-time failure of the lane ("square-root operand outside the exact range").
-// Kind 26 (KINDS_END) is unassigned as 16 and 23 are; ARGEXT is 27 and KINDS_LIMIT follows it.
-// An ARGEXT record (the claimed index of `argmax` / `argmin`, layouts.rs:5225-5293, which the prover states BEFORE the sort that checks it):
-// count = the number of segments = the number of destination cells dst[s], p0 = n >= 1 the segment length, p1 = mode (0: argmax, 1: argmin),
-// a = count * n source cells, segment-major and dense, b unused and zero.  p0 == 0, p1 > 1, count * p0 > 2^28 or an array past the pool:
-// "bad arg-extremum shape".  dst[s] gets the SMALLEST position j in [0, n) whose signed value is the greatest (mode 0) or the least (mode 1)
-// of the cells a[s * n .. + n): the reference's max_by_key((value, -idx)) / min_by_key((value, idx)), the one claim the gates accept.  A
-// source with |s| >= 2^62 is a run-time failure of the lane ("arg-extremum key beyond 62 bits"), element = its place in a; its segment's
-// cell is not written.  ARGEXT_CHUNK is the number of sources one workgroup of csrc/witness.hip reduces.
-// Kind 28 (KINDS_LIMIT) is unassigned as 16, 23 and 26 are; SCATTER, COMPLEMENT and ONEHOT are 29 .. 31 and KINDS_TOP follows them.
-// A SCATTER record (the claimed output of `scatter_elements`, layouts.rs:2313-2379, which the prover states BEFORE the gathers that check it):
-// ONE tensor -- count = n destination cells dst[i], a = the n base cells, p0 = m >= 1 elements, p1 = the multiplier of the scattered dimension
-// >= 1, b = the pool offset of 1 + 3m words: the extent of that dimension, m index cells, m source cells, m constant offsets (plain words).
-// With s_j the signed value of index cell j its target is t_j = s_j * p1 + off_j; dst[i] gets the value of source cell j for the GREATEST j
-// with t_j == i (tensor::ops::scatter: the later element wins), else the value of base cell i.  p0, p1 or the extent zero, count > 2^28, an
-// array past the pool or an offset with off_j + (extent - 1) * p1 >= count: "bad scatter shape" -- so every target of an index inside
-// [0, extent) is a destination.  s_j < 0, s_j >= extent or |s_j| >= 2^62 is a run-time failure of the lane ("scatter index outside the
-// tensor"), element = j, every such j counted; the record then writes none of its cells.  SCATTER_TILE is the number of destinations one
-// workgroup of csrc/witness.hip resolves in LDS.
-// A COMPLEMENT record (the claimed output of `get_missing_set_elements` over the positions, layouts.rs:2213-2286): p0 = n, the set {0 .. n - 1},
-// p1 = m <= n source cells at a, count = n - m destination cells (zero is legal: the record writes nothing), b unused and zero.  dst[i] gets
-// the i-th smallest v in [0, n) that is the signed value of no source cell; a source outside [0, n) or beyond 62 bits removes nothing.  It
-// never fails.  p1 > p0, count != p0 - p1, p0 > 2^28 or an array past the pool: "bad complement shape".
-// A ONEHOT record (the claimed vector of `one_hot`, layouts.rs:1398-1442), element-wise: a = the index cell of element e, b = the pool
-// offset of the per-element positions (plain words), p0 = num_classes >= 1 ("zero one-hot classes"), p1 = 0: 1 if the signed value equals
-// the position, else 0.  s < 0, s >= p0 or |s| >= 2^62 is a run-time failure of the lane ("one-hot index outside the classes").
+// then n_params x int64, n_consts x 32 bytes (canonical Fr), n_records x {kind, count, p0, p1, dst, a, b, phase}, n_outputs x u32 cells,
+// n_words x u32 pool, n_tables x {lo (int32), n, col_size, offset} and n_table_values x int64: the static lookup tables, f(lo + i) as signed
+// integers (both sections are empty in a plan without lookups).  Cells are numbered column * 2^k + row.
+//
+// What every kind of record means, its parameters and its run-time failure: the module docstring of ezkl_amd/witness_plan.py, kind by kind;
+// `run_plan_host` there is the executable form.  KINDS below is the same table as KINDS there (tests/test_witness_plan_table.py).
+//
+// What `parse` guarantees to the kernels of csrc/witness.hip: every record is of a known kind with the parameters that kind allows; every
+// span a record names lies inside the pool; every word a lane uses as a cell is below n_advice * 2^k, every index below the section it
+// points into; a cell is written at most once and read only after an EARLIER record has written it; the phases are non-decreasing, below
+// n_phases, and every column is written in one phase only (INPUT and MATMUL records in phase 0, with which the inputs are uploaded).
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -89,14 +27,59 @@ namespace wplan {
 
 constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64, MAX_PHASES = 3, MAX_CHALLENGES = 64, SORT_TILE = 2048,
                    MAX_SORT_COUNT = 1u << 28, ARGEXT_CHUNK = 4096, SCATTER_TILE = 4096;
-enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC, UNASSIGNED, SUMACC, PRODACC, GATHER, CLAMP, SORT, ARGSORT, N_KINDS,     // 16 names nothing: refused as unknown
-                       RECIP = 24, ISQRT = 25, KINDS_END,                         // N_KINDS ends KIND_NAMES and, as a kind (23), names nothing either
-                       ARGEXT = 27, KINDS_LIMIT,                                   // KINDS_END (26) names nothing either; KINDS_LIMIT (28) was the first kind past them all and names nothing
-                       SCATTER = 29, COMPLEMENT = 30, ONEHOT = 31, KINDS_TOP };    // KINDS_TOP is the first kind past them all
-static const char* const KIND_NAMES[N_KINDS] = {"copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot",
-                                                "nonlinearity", "nonlinearity_index", "matmul", "rlc", "div", "?", "sum", "prod", "gather", "clamp", "sort", "argsort"};
-// the name a message gives a kind: KIND_NAMES up to ARGSORT, the later kinds by hand, "?" for a kind that names nothing
-inline const char* kind_name(uint32_t kind) { return kind < N_KINDS ? KIND_NAMES[kind] : kind == RECIP ? "recip" : kind == ISQRT ? "sqrt" : kind == ARGEXT ? "argext" : kind == SCATTER ? "scatter" : kind == COMPLEMENT ? "complement" : kind == ONEHOT ? "one_hot" : "?"; }
+// kinds 16, 23, 26 and 28 are unassigned and refused; KINDS_TOP is the first kind past them all
+enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC, SUMACC = 17, PRODACC, GATHER, CLAMP, SORT, ARGSORT,
+                       RECIP = 24, ISQRT, ARGEXT = 27, SCATTER = 29, COMPLEMENT, ONEHOT, KINDS_TOP };
+// what the words at a record's a or b are: cells a lane reads, indices below a limit the record's case names (DIGITS: 0xffffffff too, the
+// sign), plain words (none of them where the kind does not use the array), or no pool offset at all
+enum Role : uint8_t { CELLS, INDICES, DIGITS, WORDS, NOT_POOL };
+struct KindInfo {
+    const char* name;         // what a message calls the kind; "?": the number names nothing
+    const char* failure;      // the words of its run-time failure; nullptr: a lane of this kind never fails
+    const char* unit;         // what the count of a run-time failure counts
+    bool scan, sparse;        // count * p1 destination words, not count; 0xffffffff in dst, a or b is "no entry"
+    Role a, b;
+};
+static const KindInfo KINDS[KINDS_TOP] = {
+    {"copy", nullptr, "cells", false, false, CELLS, WORDS},                                                             //  0
+    {"const", nullptr, "cells", false, false, INDICES, WORDS},
+    {"input", nullptr, "cells", false, false, INDICES, WORDS},
+    {"param", nullptr, "cells", false, false, INDICES, WORDS},
+    {"add", nullptr, "cells", false, false, CELLS, CELLS},                                                              //  4
+    {"sub", nullptr, "cells", false, false, CELLS, CELLS},
+    {"mult", nullptr, "cells", false, false, CELLS, CELLS},
+    {"decompose", "value exceeds the decomposition range", "cells", false, false, CELLS, DIGITS},
+    {"range_check", "value exceeds the decomposition range", "cells", false, false, CELLS, WORDS},                      //  8
+    {"equals_zero", nullptr, "cells", false, false, CELLS, WORDS},
+    {"dot", nullptr, "cells", true, true, CELLS, CELLS},
+    {"nonlinearity", "lookup input outside the table range", "cells", false, false, CELLS, WORDS},
+    {"nonlinearity_index", "lookup input outside the table range", "cells", false, false, CELLS, WORDS},               // 12
+    {"matmul", "einsum operand outside the exact-product range", "operand reads", false, false, INDICES, INDICES},
+    {"rlc", nullptr, "cells", true, false, CELLS, WORDS},
+    {"div", "rebase dividend outside the exact-division range", "cells", false, false, CELLS, WORDS},
+    {"?", nullptr, "cells", false, false, WORDS, WORDS},                                                                // 16
+    {"sum", nullptr, "cells", true, true, CELLS, WORDS},
+    {"prod", nullptr, "cells", true, true, CELLS, WORDS},
+    {"gather", "gather index outside the table", "cells", false, false, CELLS, WORDS},
+    {"clamp", nullptr, "cells", false, false, CELLS, WORDS},                                                            // 20
+    {"sort", "sort key beyond 62 bits", "cells", false, false, CELLS, WORDS},
+    {"argsort", "sort key beyond 62 bits", "cells", false, false, CELLS, WORDS},
+    {"?", nullptr, "cells", false, false, WORDS, WORDS},
+    {"recip", "reciprocal operand beyond 62 bits", "cells", false, false, CELLS, NOT_POOL},                             // 24
+    {"sqrt", "square-root operand outside the exact range", "cells", false, false, CELLS, WORDS},
+    {"?", nullptr, "cells", false, false, WORDS, WORDS},
+    {"argext", "arg-extremum key beyond 62 bits", "cells", false, false, CELLS, WORDS},
+    {"?", nullptr, "cells", false, false, WORDS, WORDS},                                                                // 28
+    {"scatter", "scatter index outside the tensor", "cells", false, false, CELLS, WORDS},
+    {"complement", nullptr, "cells", false, false, CELLS, WORDS},
+    {"one_hot", "one-hot index outside the classes", "cells", false, false, CELLS, WORDS},
+};
+inline bool known(uint32_t kind) { return kind < KINDS_TOP && KINDS[kind].name[0] != '?'; }
+inline const char* kind_name(uint32_t kind) { return kind < KINDS_TOP ? KINDS[kind].name : "?"; }     // the name a message gives a kind
+// the words a lane's run-time failure is reported with; a kind that has none is reported as a value beyond its decomposition is
+inline const char* failure_words(uint32_t kind) { return kind < KINDS_TOP && KINDS[kind].failure ? KINDS[kind].failure : KINDS[HINT].failure; }
+// how many destination words a record has: every step of every scan, else one per element
+inline uint64_t dst_words(uint32_t kind, uint32_t count, uint32_t p1) { return kind < KINDS_TOP && KINDS[kind].scan ? (uint64_t)count * p1 : count; }
 struct Rec {
     uint32_t kind, count, p0, p1, dst, a, b, phase;
 };
@@ -191,28 +174,52 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
     uint64_t total = 0;
     const std::vector<uint32_t>& P = out.pool;
     auto span_ok = [&](uint32_t off, uint64_t n) { return off <= P.size() && n <= P.size() - off; };
+    // the words [off, off + n) as cells a lane reads; in a sparse record 0xffffffff is no entry, and `other`, the array it is paired with
+    // (DOT), must have none there either.  -> what is wrong, or nullptr
+    auto readable = [&](uint32_t off, uint64_t n, bool sparse, const uint32_t* other) -> const char* {
+        for (uint64_t i = 0; i < n; i++) {
+            const uint32_t x = P[off + i];
+            if (sparse && x == NONE) {
+                if (other && other[i] != NONE) return "a product with one operand";
+                continue;
+            }
+            if (x >= cells) return "cell index out of range";
+            if (!written.get(x)) return "a cell is read before an earlier record has written it";
+        }
+        return nullptr;
+    };
+    // the words at a or b by their role; lim: what an index stays below
+    auto operand = [&](Role role, uint32_t off, uint64_t n, uint32_t lim, bool sparse, const uint32_t* other) -> const char* {
+        if (role == CELLS) return readable(off, n, sparse, other);
+        if (role == INDICES || role == DIGITS)
+            for (uint64_t i = 0; i < n; i++)
+                if (P[off + i] >= lim && !(role == DIGITS && P[off + i] == NONE)) return role == DIGITS ? "bad decomposition" : "table index out of range";
+        return nullptr;
+    };
     int col_phase[MAX_ADVICE];
     for (uint32_t c = 0; c < MAX_ADVICE; c++) col_phase[c] = -1;
     uint32_t last_phase = 0;
     for (size_t ri = 0; ri < out.recs.size(); ri++) {
         const Rec& r = out.recs[ri];
-        if (r.kind >= KINDS_TOP || r.kind == KINDS_LIMIT || r.kind == KINDS_END || r.kind == N_KINDS || r.kind == UNASSIGNED) return at_rec(ri, r.kind, "unknown kind");
+        if (!known(r.kind)) return at_rec(ri, r.kind, "unknown kind");
         if (r.count == 0 && r.kind != COMPLEMENT) return at_rec(ri, r.kind, "empty");     // (nothing missing: a complement that writes no cell)
         if (r.phase >= n_phases) return at_rec(ri, r.kind, "phase out of range");
         if (r.phase < last_phase) return at_rec(ri, r.kind, "phases decrease");
         last_phase = r.phase;
         if ((r.kind == INPUT || r.kind == MATMUL) && r.phase != 0) return at_rec(ri, r.kind, "input and matmul records belong to phase 0");
-        uint64_t n_dst = r.count, n_a = r.count, n_b = 0;
-        bool a_cells = false, b_cells = false;
-        uint32_t a_lim = 0;
+        // the kind's own parameters, and the words it has: n_dst at dst, n_a at a, n_b at b, lim for its indices, n_extra further cells a lane reads
+        const KindInfo& K = KINDS[r.kind];
+        const uint64_t n_dst = dst_words(r.kind, r.count, r.p1);
+        uint64_t n_a = r.count, n_b = 0, n_extra = 0;
+        uint32_t lim = 0, extra = 0;
         switch (r.kind) {
-        case COPY: case INVZ: a_cells = true; break;
-        case ADD: case SUB: case MUL: a_cells = b_cells = true; n_b = r.count; break;
-        case CONST: a_lim = n_con; break;
-        case INPUT: a_lim = n_in; break;
-        case PARAM: a_lim = n_par; break;
-        case HINT: {
-            a_cells = true; n_b = r.count;
+        case COPY: case INVZ: break;
+        case ADD: case SUB: case MUL: n_b = r.count; break;
+        case CONST: lim = n_con; break;
+        case INPUT: lim = n_in; break;
+        case PARAM: lim = n_par; break;
+        case HINT: {                                     // p0 = base, p1 = legs; b: the digit of each element, below p1
+            n_b = r.count; lim = r.p1;
             uint64_t bound = 1;
             if (r.p0 < 2 || r.p1 == 0) return at_rec(ri, r.kind, "bad decomposition");
             for (uint32_t t = 0; t < r.p1; t++) {
@@ -221,132 +228,89 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
             }
             break;
         }
-        case RCIDX: a_cells = true; if (r.p1 == 0) return at_rec(ri, r.kind, "zero table column size"); break;
-        case DIVC: a_cells = true; if (r.p0 == 0) return at_rec(ri, r.kind, "zero divisor"); break;
-        case TABLE: case TBLIDX: a_cells = true; if (r.p0 >= n_tab) return at_rec(ri, r.kind, "lookup table index out of range"); break;
-        case MATMUL: {                                   // p0 = kd, p1 = n, count = m * n: a = m * kd, b = kd * n input indices
+        case RCIDX: if (r.p1 == 0) return at_rec(ri, r.kind, "zero table column size"); break;
+        case DIVC: if (r.p0 == 0) return at_rec(ri, r.kind, "zero divisor"); break;
+        case TABLE: case TBLIDX: if (r.p0 >= n_tab) return at_rec(ri, r.kind, "lookup table index out of range"); break;
+        case MATMUL:                                     // p0 = kd, p1 = n, count = m * n: a = m * kd, b = kd * n input indices
             if (r.p0 == 0 || r.p1 == 0 || r.count % r.p1 != 0) return at_rec(ri, r.kind, "bad matmul shape");
-            n_a = (uint64_t)(r.count / r.p1) * r.p0; n_b = (uint64_t)r.p0 * r.p1; a_lim = n_in;
+            n_a = (uint64_t)(r.count / r.p1) * r.p0; n_b = (uint64_t)r.p0 * r.p1; lim = n_in;
             if (!span_ok(r.dst, n_dst) || !span_ok(r.a, n_a) || !span_ok(r.b, n_b)) return at_rec(ri, r.kind, "bad matmul shape");
             break;
-        }
         case RLC:                                        // p0 = challenge, p1 = steps, count = scans
             if (r.p0 >= n_chal) return at_rec(ri, r.kind, "challenge index out of range");
-            if (r.p1 == 0 || (uint64_t)r.count * r.p1 > P.size()) return at_rec(ri, r.kind, "bad rlc shape");
-            n_dst = n_a = (uint64_t)r.count * r.p1; a_cells = true;
+            if (r.p1 == 0 || n_dst > P.size()) return at_rec(ri, r.kind, "bad rlc shape");
+            n_a = n_dst;
             break;
         case SUMACC: case PRODACC:                       // p0 = operands per step, p1 = steps, count = scans
-            if (r.p0 == 0 || r.p1 == 0 || !span_ok(r.dst, (uint64_t)r.count * r.p1) || !span_ok(r.a, (uint64_t)r.count * r.p1 * r.p0)) return at_rec(ri, r.kind, "bad scan shape");
-            n_dst = (uint64_t)r.count * r.p1; n_a = n_dst * r.p0; a_cells = true;
+            if (r.p0 == 0 || r.p1 == 0 || !span_ok(r.dst, n_dst) || !span_ok(r.a, n_dst * r.p0)) return at_rec(ri, r.kind, "bad scan shape");
+            n_a = n_dst * r.p0;
             break;
-        case GATHER: {                                   // p0 = pool offset of the table's cell list, p1 = its length
-            a_cells = true;
+        case GATHER:                                     // p0 = pool offset of the table's cell list, p1 = its length: cells a lane reads
             if (r.p1 == 0) return at_rec(ri, r.kind, "empty gather table");
             if (!span_ok(r.p0, r.p1)) return at_rec(ri, r.kind, "gather table runs past the pool");
-            for (uint32_t i = 0; i < r.p1; i++) {        // every cell of the table is one a lane can read
-                const uint32_t x = P[r.p0 + i];
-                if (x >= cells) return at_rec(ri, r.kind, "cell index out of range");
-                if (!written.get(x)) return at_rec(ri, r.kind, "a cell is read before an earlier record has written it");
-            }
+            extra = r.p0; n_extra = r.p1;
             break;
-        }
-        case CLAMP: a_cells = true; if ((int32_t)r.p0 > (int32_t)r.p1) return at_rec(ri, r.kind, "bad clamp bounds"); break;
+        case CLAMP: if ((int32_t)r.p0 > (int32_t)r.p1) return at_rec(ri, r.kind, "bad clamp bounds"); break;
         case SORT: case ARGSORT:                         // p0 = segment length, p1 = mode, count = segments * p0
             if (r.p0 == 0 || r.count % r.p0 != 0 || r.p1 > 1 || r.count > MAX_SORT_COUNT) return at_rec(ri, r.kind, "bad sort shape");
-            a_cells = true;
             break;
         case RECIP: {                                    // S = p0 | p1 << 32, b = the constant a zero input takes
-            a_cells = true;
             const uint64_t S = (uint64_t)r.p0 | ((uint64_t)r.p1 << 32);
             if (S == 0 || S >= ((uint64_t)1 << 62)) return at_rec(ri, r.kind, "reciprocal scale outside [1, 2^62)");
             if (r.b >= n_con) return at_rec(ri, r.kind, "zero-inverse index past the constants");
             break;
         }
         case ISQRT:
-            a_cells = true;
             if (r.p0 == 0) return at_rec(ri, r.kind, "zero square-root scale");
             if (r.p1 != 0) return at_rec(ri, r.kind, "a square-root record with a second parameter");
             break;
         case ARGEXT:                                     // p0 = segment length, p1 = mode, count = segments = destination cells
-            if (r.p0 == 0 || r.p1 > 1 || (uint64_t)r.count * r.p0 > MAX_SORT_COUNT || !span_ok(r.dst, r.count) || !span_ok(r.a, (uint64_t)r.count * r.p0))
-                return at_rec(ri, r.kind, "bad arg-extremum shape");
-            n_a = (uint64_t)r.count * r.p0; a_cells = true;
+            n_a = (uint64_t)r.count * r.p0;
+            if (r.p0 == 0 || r.p1 > 1 || n_a > MAX_SORT_COUNT || !span_ok(r.dst, n_dst) || !span_ok(r.a, n_a)) return at_rec(ri, r.kind, "bad arg-extremum shape");
             break;
         case SCATTER: {                                  // p0 = elements, p1 = multiplier, b: extent, index cells, source cells, offsets
-            if (r.p0 == 0 || r.p1 == 0 || r.count > MAX_SORT_COUNT || !span_ok(r.dst, r.count) || !span_ok(r.a, r.count) || !span_ok(r.b, 1 + 3ull * r.p0))
-                return at_rec(ri, r.kind, "bad scatter shape");
+            n_b = 1 + 3ull * r.p0;
+            if (r.p0 == 0 || r.p1 == 0 || r.count > MAX_SORT_COUNT || !span_ok(r.dst, n_dst) || !span_ok(r.a, n_a) || !span_ok(r.b, n_b)) return at_rec(ri, r.kind, "bad scatter shape");
             const uint32_t extent = P[r.b];
             if (extent == 0) return at_rec(ri, r.kind, "bad scatter shape");
             for (uint32_t j = 0; j < r.p0; j++)          // every target of an index inside [0, extent) is a destination: no overflow, both factors are 32-bit
                 if ((uint64_t)P[r.b + 1 + 2ull * r.p0 + j] + (uint64_t)(extent - 1) * r.p1 >= r.count) return at_rec(ri, r.kind, "bad scatter shape");
-            for (uint64_t j = 0; j < 2ull * r.p0; j++) {   // the index and source cells: ones a lane can read
-                const uint32_t x = P[r.b + 1 + j];
-                if (x >= cells) return at_rec(ri, r.kind, "cell index out of range");
-                if (!written.get(x)) return at_rec(ri, r.kind, "a cell is read before an earlier record has written it");
-            }
-            a_cells = true;
+            extra = r.b + 1; n_extra = 2ull * r.p0;      // the index and source cells: ones a lane reads
             break;
         }
         case COMPLEMENT:                                 // p0 = n, p1 = sources, count = n - sources
-            if (r.p1 > r.p0 || r.count != r.p0 - r.p1 || r.p0 > MAX_SORT_COUNT || !span_ok(r.dst, r.count) || !span_ok(r.a, r.p1)) return at_rec(ri, r.kind, "bad complement shape");
-            n_a = r.p1; a_cells = true;
+            n_a = r.p1;
+            if (r.p1 > r.p0 || r.count != r.p0 - r.p1 || r.p0 > MAX_SORT_COUNT || !span_ok(r.dst, n_dst) || !span_ok(r.a, n_a)) return at_rec(ri, r.kind, "bad complement shape");
             break;
-        case ONEHOT: a_cells = true; n_b = r.count; if (r.p0 == 0) return at_rec(ri, r.kind, "zero one-hot classes"); break;
-        case DOT:
-            if (r.p0 == 0 || r.p1 == 0 || (uint64_t)r.count * r.p1 > P.size() || (uint64_t)r.count * r.p1 * r.p0 > P.size()) return at_rec(ri, r.kind, "bad dot shape");
-            n_dst = (uint64_t)r.count * r.p1; n_a = n_b = n_dst * r.p0; a_cells = b_cells = true;
+        case ONEHOT: n_b = r.count; if (r.p0 == 0) return at_rec(ri, r.kind, "zero one-hot classes"); break;     // b: the position of each element
+        case DOT:                                        // p0 = products per step, p1 = steps, count = dot products
+            if (r.p0 == 0 || r.p1 == 0 || n_dst > P.size() || n_dst * r.p0 > P.size()) return at_rec(ri, r.kind, "bad dot shape");
+            n_a = n_b = n_dst * r.p0;
             break;
         }
-        if (!span_ok(r.dst, n_dst) || !span_ok(r.a, n_a) || (r.kind != RECIP && r.kind != SCATTER && !span_ok(r.b, n_b)))     // (RECIP: b is no pool offset; SCATTER: checked above)
-            return at_rec(ri, r.kind, "an index array runs past the pool");
-        const bool sparse = r.kind == DOT || r.kind == SUMACC || r.kind == PRODACC;     // 0xffffffff = no entry
-        for (uint64_t i = 0; i < n_a; i++) {
-            const uint32_t x = P[r.a + i];
-            if (sparse && x == NONE) {
-                if (r.kind == DOT && P[r.b + i] != NONE) return at_rec(ri, r.kind, "a product with one operand");
-                continue;
-            }
-            if (a_cells) {
-                if (x >= cells) return at_rec(ri, r.kind, "cell index out of range");
-                if (!written.get(x)) return at_rec(ri, r.kind, "a cell is read before an earlier record has written it");
-            } else if (x >= a_lim) return at_rec(ri, r.kind, "table index out of range");
-        }
-        for (uint64_t i = 0; i < n_b; i++) {
-            const uint32_t x = P[r.b + i];
-            if (r.kind == HINT) {
-                if (x != NONE && x >= r.p1) return at_rec(ri, r.kind, "bad decomposition");
-                continue;
-            }
-            if (r.kind == ONEHOT) continue;              // positions: plain words
-            if (sparse && x == NONE) {
-                if (P[r.a + i] != NONE) return at_rec(ri, r.kind, "a product with one operand");
-                continue;
-            }
-            if (r.kind == MATMUL) {
-                if (x >= a_lim) return at_rec(ri, r.kind, "table index out of range");
-                continue;
-            }
-            if (b_cells) {
-                if (x >= cells) return at_rec(ri, r.kind, "cell index out of range");
-                if (!written.get(x)) return at_rec(ri, r.kind, "a cell is read before an earlier record has written it");
-            }
-        }
+        // what holds for every kind: the spans inside the pool, every source a cell written earlier or an index below its limit
+        const char* bad = readable(extra, n_extra, false, nullptr);
+        if (bad) return at_rec(ri, r.kind, bad);
+        if (!span_ok(r.dst, n_dst) || !span_ok(r.a, n_a) || (K.b != NOT_POOL && !span_ok(r.b, n_b))) return at_rec(ri, r.kind, "an index array runs past the pool");
+        const bool paired = K.sparse && n_b;             // DOT: a product has both operands or none
+        if ((bad = operand(K.a, r.a, n_a, lim, K.sparse, paired ? &P[r.b] : nullptr))) return at_rec(ri, r.kind, bad);
+        if ((bad = operand(K.b, r.b, n_b, lim, K.sparse, paired ? &P[r.a] : nullptr))) return at_rec(ri, r.kind, bad);
         // destinations after every source of the record: a record never reads what it writes
         for (uint64_t i = 0; i < n_dst; i++) {
             const uint32_t x = P[r.dst + i];
-            if (sparse && x == NONE) continue;
+            if (K.sparse && x == NONE) continue;
             if (x >= cells) return at_rec(ri, r.kind, "cell index out of range");
         }
         for (uint64_t i = 0; i < n_dst; i++) {
             const uint32_t x = P[r.dst + i];
-            if (sparse && x == NONE) continue;
+            if (K.sparse && x == NONE) continue;
             if (written.get(x)) return at_rec(ri, r.kind, "a cell is written twice");
             written.set(x);
             total++;
         }
         for (uint64_t i = 0; i < n_dst; i++) {
             const uint32_t x = P[r.dst + i];
-            if (sparse && x == NONE) continue;
+            if (K.sparse && x == NONE) continue;
             int& cp = col_phase[x >> k];
             if (cp >= 0 && cp != (int)r.phase) return at_rec(ri, r.kind, "a column is written in two phases");
             cp = (int)r.phase;

@@ -49,91 +49,86 @@ The plan is a flat little-endian blob (`WitnessPlan.to_bytes`):
     tables   n_tables  x 4 u32        lo (int32), n (entries), col_size, offset into the values      } both sections are empty in a plan
     values   n_table_values x int64   f(lo + i) of a static lookup table, as a signed integer        } without lookups: the MLP blobs
 
-A record of an element-wise kind has `count` destination cells pool[dst + i], produced from pool[a + i] (and pool[b + i]):
+THE RECORD KINDS, by number; `KINDS` below is the same list as a table (name, run-time failure, span shape) and csrc/witness_plan.hpp holds
+its twin.  Kinds 16, 23, 26 and 28 are unassigned and refused as unknown, as is everything from KINDS_TOP = 32 on.  Unless an entry says
+otherwise a record is element-wise: `count` destination cells pool[dst + i], produced from pool[a + i] (and pool[b + i]); b unused is zero;
+s is the signed value of the source cell.  A run-time failure is a lane's: reported as "<words> (<kind> record r, element e)", here by
+`run_plan_host` and on the device through the status words; the lane writes nothing.
 
-    COPY a = source cell | CONST a = constant index | INPUT a = input index | PARAM a = parameter index | ADD, SUB, MUL a, b = source cells
-    HINT   a = source cell, b = 0xffffffff: the sign of the signed value; else the digit (|x| // p0^b) % p0; p0 = base, p1 = legs, and
-           |x| >= p0^p1 is the decomposition-range failure
-    RCIDX  a = source cell: |x - p0| // p1 (p0 = the range's lower end as int32, p1 = the table column size); |x| >= 2^62 -- more than a lane
-           holds in 64 bits, never a sign or a digit -- is reported like a decomposition-range failure, here and on the device
-    INVZ   a = source cell: 1 / x, or 0 for x = 0
-    DIVC   a = source cell, p0 = d (u32, >= 1), p1 = 0: with s the signed value of the cell, sgn(s) * ((|s| + d // 2) // d) -- s / d rounded half
-           away from zero, the claimed quotient of `div` (ezkl_layout.round_div); |s| >= 2^52 is the run-time failure "rebase dividend outside
-           the exact-division range", reported like the decomposition-range failure
-    GATHER a = the cell holding the index, p0 = the pool offset of the table's cell list, p1 = its length n >= 1: with s the signed value of
-           the index cell, the value of cell pool[p0 + s].  s < 0, s >= n or |s| >= 2^62 is the run-time failure "gather index outside the table",
-           reported like the decomposition-range failure; the lane tests s before it reads pool[p0 + s]
-    CLAMP  a = source cell, p0 = lo, p1 = hi (int32, lo <= hi): min(max(s, lo), hi); a value beyond 62 bits clamps by its sign; never fails
-    DOT    count dot products of p1 steps of p0 products each, step-major: step s of dot d writes the running sum to pool[dst + s * count + d]
-           (0xffffffff: no such step) after adding the products of pool[a + (s * p0 + j) * count + d] and pool[b + ...] (0xffffffff: none --
-           the duplicated running sum at the top of a new column is a step without products)
-    (kind 16 is unassigned: a plan that uses it is refused as an unknown kind; the four kinds below are 17 .. 20)
-    SUMACC / PRODACC   count scans of p1 steps with p0 operands each, step-major as DOT is: step s of scan d folds the cells
-           pool[a + (s * p0 + j) * count + d], j < p0 (0xffffffff: no operand -- the duplicated row at the top of a new column), into the running
-           value (0 at the start of a sum, 1 of a product) and writes it to pool[dst + s * count + d] (0xffffffff: the scan has no such step: a
-           ragged record); b is unused and zero   (BaseRegion._accumulate, layouts.rs:2472-2621)
-    TABLE  a = source cell, p0 = table index: with s the signed value of the cell, values[offset + (s - lo)] as a field element (a negative
-           value as integer_rep_to_felt maps it)
-    TBLIDX a = source cell, p0 = table index: (s - lo) // col_size, the table column that holds s
-           both: s < lo, s > lo + n - 1 or |s| >= 2^62 is the lookup-range failure ("lookup input outside the table range"), reported like the
-           decomposition-range failure
-
-    SORT / ARGSORT (21 / 22)   count destination cells pool[dst + e] in segments of p0 = n elements (n >= 1, count % n == 0, count <= 2^28), p1 =
-           mode (0: position ascending among equal values, 1: descending), a = the source cells, segment-major and dense, b = 0.  The order of
-           a segment is by (signed value, position) -- a total order.  SORT: destination s * n + i gets the i-th smallest signed value of the
-           cells pool[a + s * n .. + n) as integer_rep_to_felt maps it; ARGSORT: the position, in [0, n), of that element in its segment
-           (BaseRegion.sort_ascending, layouts.rs:1158-1275 with the claimed indices of `shuffles`, :1624-1760).  A source with |s| >= 2^62 is
-           the run-time failure "sort key beyond 62 bits", reported like the decomposition-range failure with element = its place in a; on
-           the device its segment writes none of its cells
-
-    (kind 23 is unassigned as 16 is; the two kinds below are 24 and 25)
-    RECIP  a = source cell, b = the index in the constants section of `zero_inverse` (ONE word for the record, not a pool offset), p0 / p1 =
-           the low / high word of S = input_scale * output_scale, 1 <= S < 2^62.  With x the signed value of the cell: x = 0 -> that
-           constant; x > 0 -> ceil((2S - x) / (2x)); x < 0 -> -floor((2S + |x|) / (2|x|)): the smallest integer minimiser of |y * x - S|
-           (ezkl_layout.recip_claim).  |x| >= 2^62 is the run-time failure "reciprocal operand beyond 62 bits", reported like the
-           decomposition-range failure
-    ISQRT  a = source cell, b = 0, p0 = the input scale >= 1, p1 = 0.  With T = x * p0: T <= 0 -> 0, else r = isqrt(T), r + (T - r * r > r):
-           the integer nearest to sqrt(T) (ezkl_layout.sqrt_claim).  |x| >= 2^62 or T >= 2^62 is the run-time failure "square-root operand
-           outside the exact range", reported like the decomposition-range failure
-
-    (kind 26 is unassigned as 16 and 23 are; the kind below is 27)
-    ARGEXT count segments of p0 = n >= 1 source cells and as many destination cells pool[dst + s], p1 = mode (0: argmax, 1: argmin), a = the
-           count * n source cells, segment-major and dense, b = 0; count * n <= 2^28.  Destination s gets the SMALLEST position j in [0, n)
-           whose signed value is the greatest (mode 0) or the least (mode 1) of the cells pool[a + s * n .. + n): the claimed index of
-           `argmax` / `argmin` (BaseRegion._arg_extremum, layouts.rs:5225-5293), the one claim the gates accept.  A source with |s| >= 2^62 is
-           the run-time failure "arg-extremum key beyond 62 bits", reported like the decomposition-range failure with element = its place in
-           a; on the device its segment's cell is not written.  ARGEXT_CHUNK is the number of sources one workgroup reduces
-
-    (kind 28 is unassigned as 16, 23 and 26 are; the three kinds below are 29 .. 31 and KINDS_TOP follows them)
-    SCATTER (29)   ONE tensor: count = n destination cells pool[dst + i], a = the n base cells, p0 = m >= 1 elements, p1 = the multiplier of
-           the scattered dimension >= 1, b = the pool offset of 1 + 3m words: the extent of that dimension, m index cells, m source cells, m
-           constant offsets (plain u32, not cells).  With s_j the signed value of index cell j its target is t_j = s_j * p1 + off_j;
-           destination i gets the value of source cell j for the GREATEST j with t_j == i, else the value of base cell i: the claimed output
-           of `scatter_elements` (BaseRegion._scattered, layouts.rs:2313-2379, `tensor::ops::scatter`: the later element wins).  s_j < 0,
-           s_j >= extent or |s_j| >= 2^62 is the run-time failure "scatter index outside the tensor", reported like the decomposition-range
-           failure with element = j, every such j counted; the record then writes none of its cells.  p0, p1 or the extent zero, count >
-           2^28, an array past the pool or an offset with off_j + (extent - 1) * p1 >= count: "bad scatter shape".  SCATTER_TILE is the
-           number of destinations one workgroup resolves in LDS
-    COMPLEMENT (30)   p0 = n: the set {0 .. n - 1}, p1 = m <= n source cells at a, count = n - m destination cells, b = 0.  Destination i
-           gets the i-th smallest v in [0, n) that is the signed value of no source cell: the claimed output of `get_missing_set_elements`
-           over the positions (BaseRegion._missing, layouts.rs:2213-2286).  A source outside [0, n) or beyond 62 bits removes nothing; the
-           kind never fails.  p1 > p0, count != p0 - p1, p0 > 2^28 or an array past the pool: "bad complement shape"
-    ONEHOT (31)   element-wise: a = the index cell of element e, b = the pool offset of the per-element positions (u32), p0 = num_classes
-           >= 1 ("zero one-hot classes"), p1 = 0: 1 if the signed value equals the position, else 0 (BaseRegion._one_hot,
-           layouts.rs:1398-1442).  s < 0, s >= p0 or |s| >= 2^62 is the run-time failure "one-hot index outside the classes", reported like
-           the decomposition-range failure; the lane writes nothing
+     0 COPY    a = source cell
+     1 CONST   a = constant index
+     2 INPUT   a = input index
+     3 PARAM   a = parameter index
+   4-6 ADD, SUB, MUL   a, b = source cells
+     7 HINT    a = source cell, b = 0xffffffff: the sign of s; else the digit (|s| // p0^b) % p0; p0 = base >= 2, p1 = legs >= 1, p0^p1 < 2^62 and
+               every digit below p1 ("bad decomposition").  |s| >= p0^p1 fails: "value exceeds the decomposition range"
+     8 RCIDX   a = source cell: |s - p0| // p1 (p0 = the range's lower end as int32, p1 = the table column size >= 1).  |s| >= 2^62 -- more than a
+               lane holds in 64 bits, never a sign or a digit -- fails with the decomposition-range words
+     9 INVZ    a = source cell: 1 / x, or 0 for x = 0
+    10 DOT     count dot products of p1 steps of p0 products each, step-major: step t of dot d writes the running sum to pool[dst + t * count + d]
+               (0xffffffff: no such step) after adding the products of pool[a + (t * p0 + j) * count + d] and pool[b + ...] (0xffffffff in both:
+               none -- the duplicated running sum at the top of a new column is a step without products)
+    11 TABLE   a = source cell, p0 = table index: values[offset + (s - lo)] as a field element (a negative value as integer_rep_to_felt maps it)
+    12 TBLIDX  a = source cell, p0 = table index: (s - lo) // col_size, the table column that holds s.  Both: s < lo, s > lo + n - 1 or
+               |s| >= 2^62 fails: "lookup input outside the table range"
+    13 MATMUL  count = m * n outputs, p0 = kd, p1 = n: pool[dst + i * n + j] = sum_t in[pool[a + i * kd + t]] * in[pool[b + t * n + j]] over the
+               INTEGERS, then integer_rep_to_felt -- the product the prover witnesses (EinsumMatmulCircuit.matmul); a: m * kd, b: kd * n input
+               indices; phase 0.  An operand with |v| >= 2^31 (the sum would not fit 128 bits) fails: "einsum operand outside the exact-product
+               range", element = the operand's place in a, or m * kd + its place in b; the count is of operand reads
+    14 RLC     count scans of p1 steps with challenge p0 (< n_challenges), step-major and dense: out[0] = c * v[0], out[t] = out[t - 1] * c + c * v[t]
+               with v[t] = the cell pool[a + t * count + d], out[t] -> pool[dst + t * count + d]   (RLCConfig::assign_rlc at block width 1)
+    15 DIVC    a = source cell, p0 = d >= 1 ("zero divisor"), p1 = 0: sgn(s) * ((|s| + d // 2) // d) -- s / d rounded half away from zero, the
+               claimed quotient of `div` (ezkl_layout.round_div).  |s| >= 2^52 fails: "rebase dividend outside the exact-division range"
+ 17, 18 SUMACC, PRODACC   count scans of p1 steps with p0 operands each, step-major as DOT is: step t of scan d folds the cells
+               pool[a + (t * p0 + j) * count + d], j < p0 (0xffffffff: no operand -- the duplicated row at the top of a new column), into the running
+               value (0 at the start of a sum, 1 of a product) and writes it to pool[dst + t * count + d] (0xffffffff: the scan has no such step: a
+               ragged record).  p0 or p1 zero, or an array past the pool: "bad scan shape"   (BaseRegion._accumulate, layouts.rs:2472-2621)
+    19 GATHER  a = the cell holding the index, p0 = the pool offset of the table's cell list, p1 = its length n >= 1 ("empty gather table", "gather
+               table runs past the pool"); every cell of the list is one a lane can read.  The value of cell pool[p0 + s].  s < 0, s >= n or
+               |s| >= 2^62 fails: "gather index outside the table"; the lane tests s before it reads pool[p0 + s]
+    20 CLAMP   a = source cell, p0 = lo, p1 = hi (int32, lo <= hi, else "bad clamp bounds"): min(max(s, lo), hi); a value beyond 62 bits clamps by
+               its sign; never fails
+ 21, 22 SORT, ARGSORT   count destination cells pool[dst + e] in segments of p0 = n elements (n >= 1, count % n == 0, count <= 2^28), p1 = mode
+               (0: position ascending among equal values, 1: descending; anything else of these: "bad sort shape"), a = the source cells,
+               segment-major and dense.  The order of a segment is by (signed value, position) -- a total order.  SORT: destination g * n + i gets
+               the i-th smallest signed value of the cells pool[a + g * n .. + n) as integer_rep_to_felt maps it; ARGSORT: the position, in
+               [0, n), of that element in its segment (BaseRegion.sort_ascending, layouts.rs:1158-1275 with the claimed indices of `shuffles`,
+               :1624-1760).  A source with |s| >= 2^62 fails: "sort key beyond 62 bits", element = its place in a; on the device its segment
+               writes none of its cells.  SORT_TILE is the number of keys one workgroup sorts in LDS
+    24 RECIP   a = source cell, b = the index in the constants section of `zero_inverse` (ONE word for the record, not a pool offset: "zero-inverse
+               index past the constants"), p0 / p1 = the low / high word of S = input_scale * output_scale, 1 <= S < 2^62 ("reciprocal scale
+               outside [1, 2^62)").  s = 0 -> that constant; s > 0 -> ceil((2S - s) / (2s)); s < 0 -> -floor((2S + |s|) / (2|s|)): the smallest
+               integer minimiser of |y * s - S| (ezkl_layout.recip_claim).  |s| >= 2^62 fails: "reciprocal operand beyond 62 bits"
+    25 ISQRT   a = source cell, p0 = the input scale >= 1 ("zero square-root scale"), p1 = 0 ("a square-root record with a second parameter").
+               With T = s * p0: T <= 0 -> 0, else r = isqrt(T), r + (T - r * r > r): the integer nearest to sqrt(T) (ezkl_layout.sqrt_claim).
+               |s| >= 2^62 or T >= 2^62 fails: "square-root operand outside the exact range"
+    27 ARGEXT  count segments of p0 = n >= 1 source cells and as many destination cells pool[dst + g], p1 = mode (0: argmax, 1: argmin), a = the
+               count * n <= 2^28 source cells, segment-major and dense (else "bad arg-extremum shape").  Destination g gets the SMALLEST position
+               j in [0, n) whose signed value is the greatest (mode 0) or the least (mode 1) of the cells pool[a + g * n .. + n): the claimed
+               index of `argmax` / `argmin` (BaseRegion._arg_extremum, layouts.rs:5225-5293), the one claim the gates accept.  A source with
+               |s| >= 2^62 fails: "arg-extremum key beyond 62 bits", element = its place in a; on the device its segment's cell is not written.
+               ARGEXT_CHUNK is the number of sources one workgroup reduces
+    29 SCATTER ONE tensor: count = n destination cells pool[dst + i], a = the n base cells, p0 = m >= 1 elements, p1 = the multiplier of the
+               scattered dimension >= 1, b = the pool offset of 1 + 3m words: the extent of that dimension, m index cells, m source cells, m
+               constant offsets (plain u32, not cells).  With s_j the signed value of index cell j its target is t_j = s_j * p1 + off_j;
+               destination i gets the value of source cell j for the GREATEST j with t_j == i, else the value of base cell i: the claimed output
+               of `scatter_elements` (BaseRegion._scattered, layouts.rs:2313-2379, `tensor::ops::scatter`: the later element wins).  p0, p1 or the
+               extent zero, count > 2^28, an array past the pool or an offset with off_j + (extent - 1) * p1 >= count: "bad scatter shape" -- so
+               every target of an index inside [0, extent) is a destination.  s_j < 0, s_j >= extent or |s_j| >= 2^62 fails: "scatter index
+               outside the tensor", element = j, every such j counted; the record then writes none of its cells.  SCATTER_TILE is the number of
+               destinations one workgroup resolves in LDS
+    30 COMPLEMENT   p0 = n: the set {0 .. n - 1}, p1 = m <= n source cells at a, count = n - m destination cells (zero is legal: the record writes
+               nothing).  Destination i gets the i-th smallest v in [0, n) that is the signed value of no source cell: the claimed output of
+               `get_missing_set_elements` over the positions (BaseRegion._missing, layouts.rs:2213-2286).  A source outside [0, n) or beyond 62
+               bits removes nothing; never fails.  p1 > p0, count != p0 - p1, p0 > 2^28 or an array past the pool: "bad complement shape"
+    31 ONEHOT  a = the index cell of element e, b = the pool offset of the per-element positions (plain u32), p0 = num_classes >= 1 ("zero
+               one-hot classes"), p1 = 0: 1 if s equals the position, else 0 (BaseRegion._one_hot, layouts.rs:1398-1442).  s < 0, s >= p0 or
+               |s| >= 2^62 fails: "one-hot index outside the classes"
 
 PHASES.  A circuit with second-phase advice (the Freivalds einsum) has columns that depend on challenges squeezed after the first-phase
 commitments: its plan has n_phases = 2, and every record carries the phase whose run replays it.  Phases are non-decreasing along the
 record list; a column belongs to the phase of the records that write it (never to two; a column no record writes: phase 0); INPUT and
 MATMUL records belong to phase 0, with which the inputs are uploaded.  A later phase reads the cells of an earlier one where they are.
-    MATMUL count = m * n outputs, p0 = kd, p1 = n: pool[dst + i * n + j] = sum_t in[pool[a + i * kd + t]] * in[pool[b + t * n + j]] over the
-           INTEGERS, then integer_rep_to_felt -- the product the prover witnesses (EinsumMatmulCircuit.matmul); a: m * kd, b: kd * n input
-           indices.  Every operand must satisfy |v| < 2^31 (the sum then fits 128 bits): one outside is the run-time failure "einsum operand
-           outside the exact-product range", reported like the decomposition-range failure with element = the operand's place in a, or m * kd +
-           its place in b
-    RLC    count scans of p1 steps with challenge p0, step-major and dense: out[0] = c * v[0], out[t] = out[t - 1] * c + c * v[t] with
-           v[t] = the cell pool[a + t * count + d], out[t] -> pool[dst + t * count + d]   (RLCConfig::assign_rlc at block width 1)
 
 COUPLING WITH ezkl_layout.py.  The recorder reuses BaseRegion's value expressions too, by operator overloading on the symbols below, and
 recognises them AS THEY ARE SPELT there.  Whoever rewrites one of these lines of BaseRegion must extend the symbol classes with it (the
@@ -167,6 +162,7 @@ equality tests of tests/test_witness_plan_cpu.py fail loudly -- an assert or a P
 Every cell is written at most once and only reads cells of earlier records; `validate` checks that (the C library runs the same check
 on upload).  `run_plan_host` interprets the blob with Python integers: the executable specification of the device kernels."""
 import bisect
+import collections
 import hashlib
 import struct
 
@@ -178,20 +174,10 @@ R = EL.R
 MAGIC, VERSION = 0x50575A45, 1                  # "EZWP"
 NONE = 0xFFFFFFFF
 COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC = range(16)
-UNASSIGNED = 16                                    # the kind after DIVC names nothing and never will: both validators refuse it as unknown
-SUMACC, PRODACC, GATHER, CLAMP = range(17, 21)
-SORT, ARGSORT = 21, 22
-UNASSIGNED_2 = 23                                  # the kind after ARGSORT names nothing either: N_KINDS of csrc/witness_plan.hpp, the end of its name table
-RECIP, ISQRT = 24, 25
-UNASSIGNED_3 = 26                                  # the kind after ISQRT names nothing either: KINDS_END of csrc/witness_plan.hpp
-ARGEXT = 27
-UNASSIGNED_4 = 28                                  # the kind after ARGEXT names nothing either: KINDS_LIMIT of csrc/witness_plan.hpp
+SUMACC, PRODACC, GATHER, CLAMP, SORT, ARGSORT = range(17, 23)
+RECIP, ISQRT, ARGEXT = 24, 25, 27
 SCATTER, COMPLEMENT, ONEHOT = 29, 30, 31
 KINDS_TOP = 32                                     # the first kind past them all
-KIND_NAMES = ["copy", "const", "input", "param", "add", "sub", "mult", "decompose", "range_check", "equals_zero", "dot", "nonlinearity", "nonlinearity_index", "matmul", "rlc",
-              "div", "?", "sum", "prod", "gather", "clamp"]
-_LATER_KIND_NAMES = {SORT: "sort", ARGSORT: "argsort", RECIP: "recip", ISQRT: "sqrt", ARGEXT: "argext", SCATTER: "scatter", COMPLEMENT: "complement",
-                     ONEHOT: "one_hot"}         # KIND_NAMES is the list of the kinds up to CLAMP, as tests pin it: later kinds are named here
 SORT_TILE, MAX_SORT_COUNT = 2048, 1 << 28                       # csrc/witness_plan.hpp: the keys one workgroup sorts in LDS; the most cells of a sort record
 ARGEXT_CHUNK = 4096                                             # csrc/witness_plan.hpp: the sources one workgroup of an arg-extremum reduces
 SCATTER_TILE = 4096                                             # csrc/witness_plan.hpp: the destinations one workgroup of a scatter / a complement resolves in LDS
@@ -207,14 +193,40 @@ ARGEXT_ERROR = EL.ARGEXT_ERROR
 SCATTER_ERROR, ONEHOT_ERROR = EL.SCATTER_ERROR, EL.ONEHOT_ERROR
 MAX_PHASES, MAX_CHALLENGES = 3, 64
 
+# The table of record kinds, the same as KINDS of csrc/witness_plan.hpp (tests/test_witness_plan_table.py): the name a message gives the kind,
+# the words of its run-time failure (None: a lane of this kind never fails), what that failure counts, whether the record has count * p1
+# destination words (a scan) or count, whether 0xffffffff in dst, a or b is "no entry", and what the words at a and at b are: cells a lane
+# reads, indices below a limit the kind's case names (DIGITS: 0xffffffff too, the sign), plain words (none where the kind does not use the
+# array), or no pool offset at all.
+CELLS, INDICES, DIGITS, WORDS, NOT_POOL = "cells", "indices", "digits", "words", "not a pool offset"
+Kind = collections.namedtuple("Kind", "name failure unit scan sparse a b", defaults=(None, "cells", False, False, CELLS, WORDS))
+_ASSIGNED = {
+    COPY: Kind("copy"), CONST: Kind("const", a=INDICES), INPUT: Kind("input", a=INDICES), PARAM: Kind("param", a=INDICES),
+    ADD: Kind("add", b=CELLS), SUB: Kind("sub", b=CELLS), MUL: Kind("mult", b=CELLS),
+    HINT: Kind("decompose", RANGE_ERROR, b=DIGITS), RCIDX: Kind("range_check", RANGE_ERROR), INVZ: Kind("equals_zero"),
+    DOT: Kind("dot", scan=True, sparse=True, b=CELLS), TABLE: Kind("nonlinearity", LOOKUP_ERROR), TBLIDX: Kind("nonlinearity_index", LOOKUP_ERROR),
+    MATMUL: Kind("matmul", OPERAND_ERROR, "operand reads", a=INDICES, b=INDICES), RLC: Kind("rlc", scan=True), DIVC: Kind("div", DIV_ERROR),
+    SUMACC: Kind("sum", scan=True, sparse=True), PRODACC: Kind("prod", scan=True, sparse=True), GATHER: Kind("gather", GATHER_ERROR), CLAMP: Kind("clamp"),
+    SORT: Kind("sort", SORT_ERROR), ARGSORT: Kind("argsort", SORT_ERROR), RECIP: Kind("recip", RECIP_ERROR, b=NOT_POOL), ISQRT: Kind("sqrt", SQRT_ERROR),
+    ARGEXT: Kind("argext", ARGEXT_ERROR), SCATTER: Kind("scatter", SCATTER_ERROR), COMPLEMENT: Kind("complement"), ONEHOT: Kind("one_hot", ONEHOT_ERROR),
+}
+KINDS = [_ASSIGNED.get(kind, Kind("?", a=WORDS)) for kind in range(KINDS_TOP)]
+UNASSIGNED_KINDS = tuple(kind for kind in range(KINDS_TOP) if kind not in _ASSIGNED)      # (16, 23, 26, 28): they name nothing and never will; refused as unknown
+KIND_NAMES = [K.name for K in KINDS]               # "?" in the four holes
+
 
 class PlanError(ValueError):
     pass
 
 
 def kind_name(kind):
-    """the name a message gives a record kind: KIND_NAMES up to CLAMP, "sort" / "argsort" after it, "?" for anything else"""
-    return KIND_NAMES[kind] if 0 <= kind < len(KIND_NAMES) else _LATER_KIND_NAMES.get(kind, "?")
+    """the name a message gives a record kind; "?" for a number that names nothing"""
+    return KIND_NAMES[kind] if 0 <= kind < KINDS_TOP else "?"
+
+
+def dst_words(kind, count, p1):
+    """how many destination words a record has: every step of every scan, else one per element"""
+    return count * p1 if KINDS[kind].scan else count
 
 
 # ---- symbolic values: what a Val's .v holds during the recording pass -------------------------------------------------------------------
@@ -1441,10 +1453,16 @@ class _Written:
         self.flags[self._at(x)[0]] = True
 
 
+def _refuse(ri, kind, words):
+    """a record refused; kind None: the messages that do not name the kind"""
+    return PlanError("witness plan: record %d%s: %s" % (ri, "" if kind is None else " (%s)" % KIND_NAMES[kind], words))
+
+
 def validate(plan):
-    """the check ezkl_hip_witness_plan_upload makes before anything reaches the device, mirrored line by line: geometry, every cell index below
+    """the check ezkl_hip_witness_plan_upload makes before anything reaches the device, mirrored: geometry, every cell index below
     n_advice * 2^k, every table index in range, every lookup table inside the table values, every cell written at most once and read only
-    after an EARLIER record wrote it, the phases non-decreasing and below n_phases, every column written in one phase only"""
+    after an EARLIER record wrote it, the phases non-decreasing and below n_phases, every column written in one phase only.  A kind's case
+    checks its own parameters and says which words it has; what holds for every kind is checked once, after the cases"""
     if not 1 <= plan.k <= 28 or not 0 < plan.n_advice <= 64 or (plan.n_advice << plan.k) > 1 << 32:
         raise PlanError("witness plan: bad geometry")
     cells = plan.n_advice << plan.k
@@ -1460,138 +1478,121 @@ def validate(plan):
         if off > len(plan.table_values) or n > len(plan.table_values) - off:
             raise PlanError("witness plan: table %d: runs past the table values" % ti)
     written = _Written(cells, plan.pool)
-    total = 0
+    total, words = 0, len(plan.pool)
+    fits = lambda off, n: off <= words and n <= words - off
     col_phase, last_phase = [None] * plan.n_advice, 0
     for ri, (kind, count, p0, p1, dst, a, b, phase) in enumerate(plan.records.tolist()):
-        if kind >= KINDS_TOP or kind in (UNASSIGNED, UNASSIGNED_2, UNASSIGNED_3, UNASSIGNED_4):
+        if kind >= KINDS_TOP or kind in UNASSIGNED_KINDS:
             raise PlanError("witness plan: record %d: unknown kind %d" % (ri, kind))
         if count == 0 and kind != COMPLEMENT:             # (nothing missing: a complement that writes no cell)
             raise PlanError("witness plan: record %d is empty" % ri)
         if phase >= plan.n_phases:
-            raise PlanError("witness plan: record %d (%s): phase out of range" % (ri, kind_name(kind)))
+            raise _refuse(ri, kind, "phase out of range")
         if phase < last_phase:
-            raise PlanError("witness plan: record %d (%s): phases decrease" % (ri, kind_name(kind)))
+            raise _refuse(ri, kind, "phases decrease")
         last_phase = phase
         if kind in (INPUT, MATMUL) and phase != 0:
-            raise PlanError("witness plan: record %d (%s): input and matmul records belong to phase 0" % (ri, KIND_NAMES[kind]))
-        if kind == MATMUL:
-            kd, nn = p0, p1
-            if kd == 0 or nn == 0 or count % nn != 0 or any(off > len(plan.pool) or n > len(plan.pool) - off for off, n in
-                                                             ((dst, count), (a, count // nn * kd), (b, kd * nn))):
-                raise PlanError("witness plan: record %d (%s): bad matmul shape" % (ri, KIND_NAMES[kind]))
-            d = _span(plan, dst, count, "dst", ri)
-            if (_span(plan, a, count // nn * kd, "a", ri) >= plan.n_inputs).any() or (_span(plan, b, kd * nn, "b", ri) >= plan.n_inputs).any():
-                raise PlanError("witness plan: record %d (%s): table index out of range" % (ri, KIND_NAMES[kind]))
-            srcs = np.zeros(0, np.uint32)
-        elif kind == RLC:
+            raise _refuse(ri, kind, "input and matmul records belong to phase 0")
+        # the kind's own parameters, and the words it has: n_dst at dst, n_a at a, n_b at b, lim for its indices, `extra` further cells a lane reads
+        K, n_dst = KINDS[kind], dst_words(kind, count, p1)
+        n_a, n_b, lim, extra = count, 0, 0, None
+        if kind in (ADD, SUB, MUL, ONEHOT):               # (ONEHOT: the position each element stands for, plain words)
+            n_b = count
+            if kind == ONEHOT and p0 == 0:
+                raise _refuse(ri, kind, "zero one-hot classes")
+        elif kind in (CONST, INPUT, PARAM):
+            lim = {CONST: len(plan.consts), INPUT: plan.n_inputs, PARAM: len(plan.params)}[kind]
+        elif kind == HINT:                                # p0 = base, p1 = legs; b: the digit of each element, below p1
+            n_b, lim = count, p1
+            if p0 < 2 or p1 == 0 or p0 ** p1 >= 1 << 62:
+                raise _refuse(ri, None, "bad decomposition")
+        elif kind == RCIDX and p1 == 0:
+            raise _refuse(ri, None, "zero table column size")
+        elif kind == DIVC and p0 == 0:
+            raise _refuse(ri, None, "zero divisor")
+        elif kind in (TABLE, TBLIDX) and p0 >= len(plan.tables):
+            raise _refuse(ri, kind, "lookup table index out of range")
+        elif kind == MATMUL:                              # p0 = kd, p1 = n, count = m * n: a = m * kd, b = kd * n input indices
+            if p0 == 0 or p1 == 0 or count % p1 != 0 or not (fits(dst, count) and fits(a, count // p1 * p0) and fits(b, p0 * p1)):
+                raise _refuse(ri, kind, "bad matmul shape")
+            n_a, n_b, lim = count // p1 * p0, p0 * p1, plan.n_inputs
+        elif kind == RLC:                                 # p0 = challenge, p1 = steps, count = scans
             if p0 >= plan.n_challenges:
-                raise PlanError("witness plan: record %d (%s): challenge index out of range" % (ri, KIND_NAMES[kind]))
-            if p1 == 0 or count * p1 > len(plan.pool):
-                raise PlanError("witness plan: record %d (%s): bad rlc shape" % (ri, KIND_NAMES[kind]))
-            d = _span(plan, dst, count * p1, "dst", ri)
-            srcs = _span(plan, a, count * p1, "a", ri)
-        elif kind in (SUMACC, PRODACC):
-            w, ns = p0, p1
-            if w == 0 or ns == 0 or any(off > len(plan.pool) or n > len(plan.pool) - off for off, n in ((dst, count * ns), (a, count * ns * w))):
-                raise PlanError("witness plan: record %d (%s): bad scan shape" % (ri, KIND_NAMES[kind]))
-            d = _span(plan, dst, count * ns, "dst", ri)
-            srcs = _span(plan, a, count * ns * w, "a", ri)
-            srcs = srcs[srcs != NONE]
-            d = d[d != NONE]
-        elif kind in (SORT, ARGSORT):
+                raise _refuse(ri, kind, "challenge index out of range")
+            if p1 == 0 or n_dst > words:
+                raise _refuse(ri, kind, "bad rlc shape")
+            n_a = n_dst
+        elif kind in (SUMACC, PRODACC):                   # p0 = operands per step, p1 = steps, count = scans
+            n_a = n_dst * p0
+            if p0 == 0 or p1 == 0 or not (fits(dst, n_dst) and fits(a, n_a)):
+                raise _refuse(ri, kind, "bad scan shape")
+        elif kind == GATHER:                              # p0 = pool offset of the table's cell list, p1 = its length: cells a lane reads
+            if p1 == 0:
+                raise _refuse(ri, kind, "empty gather table")
+            if not fits(p0, p1):
+                raise _refuse(ri, kind, "gather table runs past the pool")
+            extra = plan.pool[p0:p0 + p1]
+        elif kind == CLAMP and _i32(p0) > _i32(p1):
+            raise _refuse(ri, kind, "bad clamp bounds")
+        elif kind in (SORT, ARGSORT):                     # p0 = segment length, p1 = mode, count = segments * p0
             if p0 == 0 or count % p0 != 0 or p1 > 1 or count > MAX_SORT_COUNT:
-                raise PlanError("witness plan: record %d (%s): bad sort shape" % (ri, kind_name(kind)))
-            d = _span(plan, dst, count, "dst", ri)
-            srcs = _span(plan, a, count, "a", ri)
+                raise _refuse(ri, kind, "bad sort shape")
+        elif kind == RECIP:                               # S = p0 | p1 << 32; b: the constant a zero input takes
+            if not 1 <= (p0 | p1 << 32) < 1 << 62:
+                raise _refuse(ri, kind, "reciprocal scale outside [1, 2^62)")
+            if b >= len(plan.consts):
+                raise _refuse(ri, kind, "zero-inverse index past the constants")
+        elif kind == ISQRT:
+            if p0 == 0:
+                raise _refuse(ri, kind, "zero square-root scale")
+            if p1 != 0:
+                raise _refuse(ri, kind, "a square-root record with a second parameter")
         elif kind == ARGEXT:                              # p0 = segment length, p1 = mode, count = segments = destination cells
-            if (p0 == 0 or p1 > 1 or count * p0 > MAX_SORT_COUNT or dst > len(plan.pool) or count > len(plan.pool) - dst
-                    or a > len(plan.pool) or count * p0 > len(plan.pool) - a):
-                raise PlanError("witness plan: record %d (%s): bad arg-extremum shape" % (ri, kind_name(kind)))
-            d = _span(plan, dst, count, "dst", ri)
-            srcs = _span(plan, a, count * p0, "a", ri)
+            n_a = count * p0
+            if p0 == 0 or p1 > 1 or n_a > MAX_SORT_COUNT or not (fits(dst, count) and fits(a, n_a)):
+                raise _refuse(ri, kind, "bad arg-extremum shape")
         elif kind == SCATTER:                             # p0 = elements, p1 = multiplier, b: extent, index cells, source cells, offsets
-            words = len(plan.pool)
-            ok = (p0 >= 1 and p1 >= 1 and count <= MAX_SORT_COUNT and dst <= words and count <= words - dst and a <= words and count <= words - a
-                  and b <= words and 1 + 3 * p0 <= words - b)
+            n_b = 1 + 3 * p0
+            ok = p0 >= 1 and p1 >= 1 and count <= MAX_SORT_COUNT and fits(dst, count) and fits(a, count) and fits(b, n_b)
             if ok:
                 extent = int(plan.pool[b])
                 ok = extent >= 1 and int(plan.pool[b + 1 + 2 * p0:b + 1 + 3 * p0].max()) + (extent - 1) * p1 < count
             if not ok:
-                raise PlanError("witness plan: record %d (%s): bad scatter shape" % (ri, kind_name(kind)))
-            d = _span(plan, dst, count, "dst", ri)
-            srcs = np.concatenate([_span(plan, a, count, "a", ri), plan.pool[b + 1:b + 1 + 2 * p0]])
+                raise _refuse(ri, kind, "bad scatter shape")
+            extra = plan.pool[b + 1:b + 1 + 2 * p0]       # the index and source cells: ones a lane reads
         elif kind == COMPLEMENT:                          # p0 = n, p1 = sources, count = n - sources
-            words = len(plan.pool)
-            if p1 > p0 or count != p0 - p1 or p0 > MAX_SORT_COUNT or dst > words or count > words - dst or a > words or p1 > words - a:
-                raise PlanError("witness plan: record %d (%s): bad complement shape" % (ri, kind_name(kind)))
-            d = _span(plan, dst, count, "dst", ri)
-            srcs = _span(plan, a, p1, "a", ri)
-        elif kind == DOT:
-            w, ns = p0, p1
-            if w == 0 or ns == 0 or count * ns * w > len(plan.pool):
-                raise PlanError("witness plan: record %d: bad dot shape" % ri)
-            d = _span(plan, dst, count * ns, "dst", ri)
-            xa, xb = _span(plan, a, count * ns * w, "a", ri), _span(plan, b, count * ns * w, "b", ri)
-            if ((xa == NONE) != (xb == NONE)).any():
-                raise PlanError("witness plan: record %d (dot): a product with one operand" % ri)
-            srcs = np.concatenate([xa, xb])
-            srcs = srcs[srcs != NONE]
-            d = d[d != NONE]
-        else:
-            d = _span(plan, dst, count, "dst", ri)
-            x = _span(plan, a, count, "a", ri)
-            srcs = np.zeros(0, np.uint32)
-            if kind in (COPY, ADD, SUB, MUL, HINT, RCIDX, INVZ, TABLE, TBLIDX, DIVC, GATHER, CLAMP, RECIP, ISQRT, ONEHOT):
-                srcs = x
-            else:
-                lim = {CONST: len(plan.consts), INPUT: plan.n_inputs, PARAM: len(plan.params)}[kind]
-                if (x >= lim).any():
-                    raise PlanError("witness plan: record %d (%s): table index out of range" % (ri, KIND_NAMES[kind]))
-            if kind in (ADD, SUB, MUL):
-                srcs = np.concatenate([srcs, _span(plan, b, count, "b", ri)])
-            if kind == HINT:
-                e = _span(plan, b, count, "b", ri)
-                if p0 < 2 or p1 == 0 or p0 ** p1 >= 1 << 62 or ((e != NONE) & (e >= p1)).any():
-                    raise PlanError("witness plan: record %d: bad decomposition" % ri)
-            if kind == RCIDX and p1 == 0:
-                raise PlanError("witness plan: record %d: zero table column size" % ri)
-            if kind == DIVC and p0 == 0:
-                raise PlanError("witness plan: record %d: zero divisor" % ri)
-            if kind == GATHER:                            # every cell of the table is one a lane can read
-                if p1 == 0:
-                    raise PlanError("witness plan: record %d (%s): empty gather table" % (ri, KIND_NAMES[kind]))
-                if p0 > len(plan.pool) or p1 > len(plan.pool) - p0:
-                    raise PlanError("witness plan: record %d (%s): gather table runs past the pool" % (ri, KIND_NAMES[kind]))
-                srcs = np.concatenate([srcs, plan.pool[p0:p0 + p1]])
-            if kind == CLAMP and _i32(p0) > _i32(p1):
-                raise PlanError("witness plan: record %d (%s): bad clamp bounds" % (ri, KIND_NAMES[kind]))
-            if kind == RECIP:                             # S = p0 | p1 << 32; b: the constant a zero input takes
-                if not 1 <= (p0 | p1 << 32) < 1 << 62:
-                    raise PlanError("witness plan: record %d (%s): reciprocal scale outside [1, 2^62)" % (ri, kind_name(kind)))
-                if b >= len(plan.consts):
-                    raise PlanError("witness plan: record %d (%s): zero-inverse index past the constants" % (ri, kind_name(kind)))
-            if kind == ISQRT:
-                if p0 == 0:
-                    raise PlanError("witness plan: record %d (%s): zero square-root scale" % (ri, kind_name(kind)))
-                if p1 != 0:
-                    raise PlanError("witness plan: record %d (%s): a square-root record with a second parameter" % (ri, kind_name(kind)))
-            if kind == ONEHOT:                            # b: the position each element stands for, plain words
-                _span(plan, b, count, "b", ri)
-                if p0 == 0:
-                    raise PlanError("witness plan: record %d (%s): zero one-hot classes" % (ri, kind_name(kind)))
-            if kind in (TABLE, TBLIDX) and p0 >= len(plan.tables):
-                raise PlanError("witness plan: record %d (%s): lookup table index out of range" % (ri, KIND_NAMES[kind]))
+            n_a = p1
+            if p1 > p0 or count != p0 - p1 or p0 > MAX_SORT_COUNT or not (fits(dst, count) and fits(a, p1)):
+                raise _refuse(ri, kind, "bad complement shape")
+        elif kind == DOT:                                 # p0 = products per step, p1 = steps, count = dot products
+            n_a = n_b = n_dst * p0
+            if p0 == 0 or p1 == 0 or n_a > words:
+                raise _refuse(ri, None, "bad dot shape")
+        # what holds for every kind
+        d, xa = _span(plan, dst, n_dst, "dst", ri), _span(plan, a, n_a, "a", ri)
+        xb = _span(plan, b, n_b, "b", ri) if n_b else xa[:0]
+        if K.sparse and n_b and ((xa == NONE) != (xb == NONE)).any():
+            raise _refuse(ri, kind, "a product with one operand")
+        for role, x in ((K.a, xa), (K.b, xb)):
+            if role == INDICES and (x >= lim).any():
+                raise _refuse(ri, kind, "table index out of range")
+            if role == DIGITS and ((x != NONE) & (x >= lim)).any():
+                raise _refuse(ri, None, "bad decomposition")
+        srcs = [x for role, x in ((K.a, xa), (K.b, xb)) if role == CELLS] + ([extra] if extra is not None else [])
+        srcs = srcs[0] if len(srcs) == 1 else np.concatenate(srcs) if srcs else xa[:0]
+        if K.sparse:                                      # 0xffffffff: no entry
+            srcs, d = srcs[srcs != NONE], d[d != NONE]
         if (d >= cells).any() or (srcs >= cells).any():
-            raise PlanError("witness plan: record %d (%s): cell index out of range" % (ri, kind_name(kind)))
+            raise _refuse(ri, kind, "cell index out of range")
         if not written.get(srcs).all():
-            raise PlanError("witness plan: record %d (%s): a cell is read before an earlier record has written it" % (ri, kind_name(kind)))
+            raise _refuse(ri, kind, "a cell is read before an earlier record has written it")
         if written.get(d).any() or len(np.unique(d)) != len(d):
-            raise PlanError("witness plan: record %d (%s): a cell is written twice" % (ri, kind_name(kind)))
+            raise _refuse(ri, kind, "a cell is written twice")
         written.set(d)
         total += len(d)
         for c in np.unique(d >> plan.k).tolist():
             if col_phase[c] is not None and col_phase[c] != phase:
-                raise PlanError("witness plan: record %d (%s): a column is written in two phases" % (ri, kind_name(kind)))
+                raise _refuse(ri, kind, "a column is written in two phases")
             col_phase[c] = phase
     if total != plan.n_cells:
         raise PlanError("witness plan: %d cells written, its header says %d" % (total, plan.n_cells))
@@ -1599,13 +1600,16 @@ def validate(plan):
         raise PlanError("witness plan: an output cell is never written")
 
 
+def _written_cells(plan, kind, count, p1, dst):
+    d = plan.pool[dst:dst + dst_words(kind, count, p1)]
+    return d[d != NONE] >> plan.k
+
+
 def column_phases(plan):
     """the phase each advice column belongs to: that of the records that write it (`validate` refuses two), 0 for a column no record writes"""
     out = [0] * plan.n_advice
     for kind, count, p0, p1, dst, a, b, phase in plan.records.tolist():
-        n = count * p1 if kind in (DOT, RLC, SUMACC, PRODACC) else count
-        d = plan.pool[dst:dst + n]
-        for c in np.unique(d[d != NONE] >> plan.k).tolist():
+        for c in np.unique(_written_cells(plan, kind, count, p1, dst)).tolist():
             out[c] = phase
     return out
 
@@ -1614,9 +1618,13 @@ def written_columns(plan):
     """the advice columns some record writes a cell of (every other column is all zeros after its phase has run)"""
     out = set()
     for kind, count, p0, p1, dst, a, b, phase in plan.records.tolist():
-        d = plan.pool[dst:dst + (count * p1 if kind in (DOT, RLC, SUMACC, PRODACC) else count)]
-        out.update((d[d != NONE] >> plan.k).tolist())
+        out.update(_written_cells(plan, kind, count, p1, dst).tolist())
     return out
+
+
+def _lane_failure(kind, ri, element):
+    """the run-time failure of a lane, worded as the device words it (csrc/witness.hip)"""
+    return AssertionError("%s (%s record %d, element %d)" % (KINDS[kind].failure, KIND_NAMES[kind], ri, element))
 
 
 def run_plan_host(plan, x, challenges=None, phase=None):
@@ -1644,7 +1652,7 @@ def run_plan_host(plan, x, challenges=None, phase=None):
             ia, ib = P[a:a + m * kd], P[b:b + kd * nn]
             for e, i in enumerate(ia + ib):                # every operand a lane reads, the smallest failing element first
                 if abs(xs[i]) >= 1 << 31:
-                    raise AssertionError("%s (%s record %d, element %d)" % (OPERAND_ERROR, KIND_NAMES[kind], ri, e))
+                    raise _lane_failure(kind, ri, e)
             for i in range(m):
                 for j in range(nn):
                     cells[P[dst + i * nn + j]] = sum(xs[ia[i * kd + t]] * xs[ib[t * nn + j]] for t in range(kd)) % R
@@ -1689,7 +1697,7 @@ def run_plan_host(plan, x, challenges=None, phase=None):
             vals = [EL.signed(cells[c]) for c in P[a:a + count * p0]]
             for e, sv in enumerate(vals):                  # every source a lane reads, the smallest failing element first
                 if abs(sv) >= 1 << 62:
-                    raise AssertionError("%s (%s record %d, element %d)" % (ARGEXT_ERROR, kind_name(kind), ri, e))
+                    raise _lane_failure(kind, ri, e)
             for g in range(count):
                 seg = vals[g * p0:(g + 1) * p0]
                 cells[P[dst + g]] = seg.index(min(seg) if p1 else max(seg))     # the first position that holds the extremum
@@ -1699,7 +1707,7 @@ def run_plan_host(plan, x, challenges=None, phase=None):
             idx = [EL.signed(cells[c]) for c in P[b + 1:b + 1 + m]]
             for j, sv in enumerate(idx):                   # every index a lane reads, the smallest failing element first
                 if sv < 0 or sv >= extent or abs(sv) >= 1 << 62:
-                    raise AssertionError("%s (%s record %d, element %d)" % (SCATTER_ERROR, kind_name(kind), ri, j))
+                    raise _lane_failure(kind, ri, j)
             out = [cells[c] for c in P[a:a + count]]
             for j, sv in enumerate(idx):
                 out[sv * p1 + P[b + 1 + 2 * m + j]] = cells[P[b + 1 + m + j]]
@@ -1716,7 +1724,7 @@ def run_plan_host(plan, x, challenges=None, phase=None):
             vals = [EL.signed(cells[c]) for c in P[a:a + count]]
             for e, sv in enumerate(vals):                  # every source a lane reads, the smallest failing element first
                 if abs(sv) >= 1 << 62:
-                    raise AssertionError("%s (%s record %d, element %d)" % (SORT_ERROR, kind_name(kind), ri, e))
+                    raise _lane_failure(kind, ri, e)
             for g in range(0, count, p0):
                 seg = vals[g:g + p0]
                 for i, j in enumerate(sorted(range(p0), key=lambda j: (seg[j], -j if p1 else j))):
@@ -1737,44 +1745,44 @@ def run_plan_host(plan, x, challenges=None, phase=None):
                 t_lo, t_n, t_col, t_off = plan.tables[p0]
                 s = EL.signed(cells[ia])
                 if s < t_lo or s > t_lo + t_n - 1 or abs(s) >= 1 << 62:
-                    raise AssertionError("%s (%s record %d, element %d)" % (LOOKUP_ERROR, KIND_NAMES[kind], ri, i))
+                    raise _lane_failure(kind, ri, i)
                 v = int(plan.table_values[t_off + s - t_lo]) % R if kind == TABLE else (s - t_lo) // t_col
             elif kind == DIVC:
                 s = EL.signed(cells[ia])
                 if abs(s) >= 1 << 52:
-                    raise AssertionError("%s (%s record %d, element %d)" % (DIV_ERROR, KIND_NAMES[kind], ri, i))
+                    raise _lane_failure(kind, ri, i)
                 v = EL.round_div(s, p0) % R
             elif kind == GATHER:                          # the index is tested before it is used
                 s = EL.signed(cells[ia])
                 if s < 0 or s >= p1 or abs(s) >= 1 << 62:
-                    raise AssertionError("%s (%s record %d, element %d)" % (GATHER_ERROR, KIND_NAMES[kind], ri, i))
+                    raise _lane_failure(kind, ri, i)
                 v = cells[P[p0 + s]]
             elif kind == CLAMP:                           # beyond 62 bits: by its sign, as the lane does
                 v = min(max(EL.signed(cells[ia]), lo), _i32(p1)) % R
             elif kind == RECIP:                           # the claim rule is the layout's, in exact integers
                 s = EL.signed(cells[ia])
                 if abs(s) >= 1 << 62:
-                    raise AssertionError("%s (%s record %d, element %d)" % (RECIP_ERROR, kind_name(kind), ri, i))
+                    raise _lane_failure(kind, ri, i)
                 v = consts[b] if s == 0 else EL.recip_claim(s, p0 | p1 << 32, 0) % R
             elif kind == ISQRT:
                 s = EL.signed(cells[ia])
                 if abs(s) >= 1 << 62 or s * p0 >= 1 << 62:
-                    raise AssertionError("%s (%s record %d, element %d)" % (SQRT_ERROR, kind_name(kind), ri, i))
+                    raise _lane_failure(kind, ri, i)
                 v = EL.sqrt_claim(s, p0)
             elif kind == ONEHOT:
                 s = EL.signed(cells[ia])
                 if s < 0 or s >= p0 or abs(s) >= 1 << 62:
-                    raise AssertionError("%s (%s record %d, element %d)" % (ONEHOT_ERROR, kind_name(kind), ri, i))
+                    raise _lane_failure(kind, ri, i)
                 v = int(s == P[b + i])
             elif kind == RCIDX:
                 s = EL.signed(cells[ia])
                 if abs(s) >= 1 << 62:                 # what a lane holds in 64 bits; the layout only range-checks signs and digits
-                    raise AssertionError("%s (%s record %d, element %d)" % (RANGE_ERROR, KIND_NAMES[kind], ri, i))
+                    raise _lane_failure(kind, ri, i)
                 v = abs(s - lo) // p1
             else:
                 s, e = EL.signed(cells[ia]), P[b + i]
                 if abs(s) >= p0 ** p1:
-                    raise AssertionError("%s (%s record %d, element %d)" % (RANGE_ERROR, KIND_NAMES[kind], ri, i))
+                    raise _lane_failure(kind, ri, i)
                 v = ((s > 0) - (s < 0)) % R if e == NONE else (abs(s) // p0 ** e) % p0
             cells[P[dst + i]] = v
     done = phase is None or phase == plan.n_phases - 1

@@ -1,49 +1,10 @@
-// The witness-plan parser (ezkl_amd/csrc/witness_plan.hpp) on blobs the Python side wrote: plans with SCATTER, COMPLEMENT and ONEHOT records it
-// must take, and plans with one defect each that it must refuse with the words the Python validator used.  A plain program: built with
-// -fsanitize=address,undefined by tests/test_witness_plan_scatter_cpp.py, so every index the parser forms from a blob's words is checked.
-//
-//   test_witness_plan_scatter <dir>     <dir>/manifest.txt: one line per blob, "<file> <ok|bad> <the message expected, to the end of the line>"
-//
-// Every good blob is also parsed cut short at every section boundary of its header and a few places past it, with each record's kind set
-// to the four unassigned ones (16, 23 = N_KINDS, 26 = KINDS_END, 28 = KINDS_LIMIT), to the end after the last kind and to 0xffffffff --
-// refused by name -- and with every word of every record of a new kind, and every pool word of a SCATTER record's parameter array, set to a
-// list of edge values: whatever the parser then answers, it must not read past the buffer, and a plan it takes must satisfy what the kernels
-// index with -- at least one element, a multiplier and an extent of at least 1, every target of an index inside the extent a destination, at
-// most 2^28 cells, every base, index, source and destination a cell inside the pool's span; a complement of n - m cells over m <= n <= 2^28
-// sources; at least one one-hot class.
-#include <stdio.h>
-#include <fstream>
-#include <iterator>
-#include <sstream>
-#include <string>
-#include <vector>
-
-#include "witness_plan.hpp"
-
-using namespace ezkl::wplan;
-
-static int failures = 0;
-#define CHECK(cond, ...)                      \
-    do {                                      \
-        if (!(cond)) {                        \
-            failures++;                       \
-            fprintf(stderr, "FAILED %s:%d: %s: ", __FILE__, __LINE__, #cond); \
-            fprintf(stderr, __VA_ARGS__);     \
-            fprintf(stderr, "\n");            \
-        }                                     \
-    } while (0)
-
-static std::vector<uint8_t> slurp(const std::string& path) {
-    std::ifstream f(path, std::ios::binary);
-    return std::vector<uint8_t>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-
-// the blob in a heap block of exactly its size: a read one byte past it is an AddressSanitizer report
-static bool parse_exact(const std::vector<uint8_t>& blob, size_t len, Plan& plan, std::string& why) {
-    std::vector<uint8_t> exact(blob.begin(), blob.begin() + len);
-    exact.shrink_to_fit();
-    return parse(len ? exact.data() : nullptr, len, plan, why);
-}
+// The witness-plan parser on blobs the Python side wrote (tests/test_witness_plan_scatter_cpp.py): plans with SCATTER, COMPLEMENT and ONEHOT
+// records it must take, and plans with one defect each that it must refuse.  wplan_harness.hpp says what every blob goes through; here every
+// word of every record of the three kinds, and every pool word of a SCATTER record's parameter array, is also set to a list of edge values:
+// whatever the parser then answers, a plan it takes must satisfy what the kernels index with -- at least one element, a multiplier and an
+// extent of at least 1, every target of an index inside the extent a destination, at most 2^28 cells, every base, index, source and
+// destination a cell inside the pool's span; a complement of n - m cells over m <= n <= 2^28 sources; at least one one-hot class.
+#include "wplan_harness.hpp"
 
 static bool is_new(uint32_t kind) { return kind == SCATTER || kind == COMPLEMENT || kind == ONEHOT; }
 
@@ -82,94 +43,31 @@ static unsigned check_indexed(const Plan& plan, const char* file) {
 }
 
 int main(int argc, char** argv) {
-    if (argc != 2) {
-        fprintf(stderr, "usage: %s <dir>\n", argv[0]);
-        return 2;
-    }
-    static_assert(UNASSIGNED == 16 && N_KINDS == 23 && RECIP == 24 && ISQRT == 25 && KINDS_END == 26 && ARGEXT == 27 && KINDS_LIMIT == 28 && SCATTER == 29 && COMPLEMENT == 30 &&
-                      ONEHOT == 31 && KINDS_TOP == 32,
+    static_assert(DIVC == 15 && ARGSORT == 22 && RECIP == 24 && ISQRT == 25 && ARGEXT == 27 && SCATTER == 29 && COMPLEMENT == 30 && ONEHOT == 31 && KINDS_TOP == 32,
                   "16, 23, 26 and 28 stay unassigned; the kinds are appended after them");
-    static_assert(VERSION == 1 && SORT_TILE == 2048 && ARGEXT_CHUNK == 4096 && SCATTER_TILE == 4096 && sizeof(KIND_NAMES) / sizeof(KIND_NAMES[0]) == 23, "the pinned constants");
-    CHECK(std::string(kind_name(SCATTER)) == "scatter" && std::string(kind_name(COMPLEMENT)) == "complement" && std::string(kind_name(ONEHOT)) == "one_hot" &&
-              std::string(kind_name(ARGEXT)) == "argext" && std::string(kind_name(COPY)) == "copy" && std::string(kind_name(UNASSIGNED)) == "?" &&
-              std::string(kind_name(N_KINDS)) == "?" && std::string(kind_name(KINDS_END)) == "?" && std::string(kind_name(KINDS_LIMIT)) == "?" &&
-              std::string(kind_name(KINDS_TOP)) == "?" && std::string(kind_name(0xFFFFFFFFu)) == "?",
-          "kind names");
-    const std::string dir = argv[1];
-    std::ifstream manifest(dir + "/manifest.txt");
-    std::string line;
-    unsigned n_ok = 0, n_bad = 0, n_claims = 0, n_tampered = 0, n_taken = 0;
-    while (std::getline(manifest, line)) {
-        std::istringstream is(line);
-        std::string file, verdict, want;
-        is >> file >> verdict;
-        std::getline(is, want);
-        if (!want.empty() && want[0] == ' ') want.erase(0, 1);
-        const std::vector<uint8_t> blob = slurp(dir + "/" + file);
-        CHECK(!blob.empty(), "%s is empty or missing", file.c_str());
-        if (blob.empty()) continue;
-        Plan plan;
-        std::string why;
-        const bool ok = parse_exact(blob, blob.size(), plan, why);
-        if (verdict == "ok") {
-            n_ok++;
-            CHECK(ok, "%s refused: %s", file.c_str(), why.c_str());
-            if (!ok) continue;
-            uint64_t cells = 0;
-            for (const Rec& r : plan.recs) {
-                const bool scan = r.kind == DOT || r.kind == RLC || r.kind == SUMACC || r.kind == PRODACC;
-                for (uint64_t i = 0; i < (scan ? (uint64_t)r.count * r.p1 : r.count); i++) cells += plan.pool[r.dst + i] != NONE;
-            }
-            n_claims += check_indexed(plan, file.c_str());
-            CHECK(cells == plan.n_cells, "%s: %llu destinations, the header says %u", file.c_str(), (unsigned long long)cells, plan.n_cells);
-            const size_t recs_at = 112 + 8 * plan.params.size() + plan.consts.size(), outs_at = recs_at + 32 * plan.recs.size(), pool_at = outs_at + 4 * plan.outputs.size();
-            for (size_t cut : {(size_t)0, (size_t)1, (size_t)79, (size_t)111, (size_t)112, recs_at, recs_at + 31, outs_at, pool_at, pool_at + 4, blob.size() / 2, blob.size() - 4,
-                               blob.size() - 1}) {
-                Plan p2;
-                CHECK(!parse_exact(blob, cut < blob.size() ? cut : blob.size() - 1, p2, why), "%s cut to %zu bytes was taken", file.c_str(), cut);
-            }
-            const uint32_t words = (uint32_t)plan.pool.size();
-            auto tamper = [&](size_t at, uint32_t v, const char* what, size_t ri, int field) {      // one word of the blob replaced: taken -> checked, refused -> by name
-                std::vector<uint8_t> b2 = blob;
-                memcpy(b2.data() + at, &v, 4);
-                Plan p2;
-                n_tampered++;
-                if (parse_exact(b2, b2.size(), p2, why)) {
-                    n_taken++;
-                    check_indexed(p2, file.c_str());
-                } else
-                    CHECK(why.rfind("witness plan: ", 0) == 0, "%s record %zu %s %d = %u: \"%s\"", file.c_str(), ri, what, field, v, why.c_str());
-            };
-            for (size_t ri = 0; ri < plan.recs.size(); ri++) {
-                for (const uint32_t kind : {(uint32_t)UNASSIGNED, (uint32_t)N_KINDS, (uint32_t)KINDS_END, (uint32_t)KINDS_LIMIT, (uint32_t)KINDS_TOP, 0xFFFFFFFFu}) {     // refused by name
-                    std::vector<uint8_t> b2 = blob;
-                    memcpy(b2.data() + recs_at + 32 * ri, &kind, 4);
-                    Plan p2;
-                    CHECK(!parse_exact(b2, b2.size(), p2, why) && why.find("(?): unknown kind") != std::string::npos, "%s record %zu: %s", file.c_str(), ri, why.c_str());
-                }
-                const Rec& r = plan.recs[ri];
-                if (!is_new(r.kind) || plan.pool.size() > 4096) continue;            // (the large plans: parsed, cut and renamed only)
-                for (int field = 1; field < 8; field++)              // count, p0, p1, dst, a, b, phase: every word of the record at its edges
-                    for (const uint32_t v : {0u, 1u, 2u, 3u, 5u, 6u, 7u, 64u, 4096u, 4097u, 1u << 28, (1u << 28) + 1, 0x55555555u, 0x55555556u, 0x7FFFFFFFu, 0x80000000u, 0xFFFFFFFEu,
-                                             0xFFFFFFFFu, words - 1, words, words + 1, r.count, r.p0})
-                        tamper(recs_at + 32 * ri + 4 * field, v, "field", ri, field);
-                if (r.kind != SCATTER) continue;
-                for (uint32_t w = 0; w < 1 + 3 * r.p0; w++)           // the extent, the index cells, the source cells, the offsets
-                    for (const uint32_t v : {0u, 1u, r.count - 1, r.count, r.count + 1, 0x7FFFFFFFu, 0x80000000u, 0xFFFFFFFFu, (uint32_t)((uint64_t)plan.n_advice << plan.k)})
-                        tamper(pool_at + 4 * (r.b + w), v, "pool word", ri, (int)w);
-            }
-        } else {
-            n_bad++;
-            CHECK(!ok, "%s was taken, expected: %s", file.c_str(), want.c_str());
-            CHECK(why == want, "%s: \"%s\", expected \"%s\"", file.c_str(), why.c_str(), want.c_str());
+    static_assert(VERSION == 1 && SORT_TILE == 2048 && ARGEXT_CHUNK == 4096 && SCATTER_TILE == 4096, "the pinned constants");
+    check_kind_names();
+    CHECK(!known(16) && !known(23) && !known(26) && !known(28) && !known(KINDS_TOP), "the unassigned kinds");
+    unsigned n_claims = 0;
+    run_manifest(argc, argv, [&](const Good& g) {
+        const Plan& plan = g.plan;
+        n_claims += check_indexed(plan, g.file.c_str());
+        const uint32_t words = (uint32_t)plan.pool.size();
+        auto on_taken = [&](const Plan& p2) { check_indexed(p2, g.file.c_str()); };
+        for (size_t ri = 0; ri < plan.recs.size(); ri++) {
+            const Rec& r = plan.recs[ri];
+            if (!is_new(r.kind) || plan.pool.size() > 4096) continue;            // (the large plans: parsed, cut and renamed only)
+            tamper_words(g.blob, g.recs_at, ri,
+                         {0u, 1u, 2u, 3u, 5u, 6u, 7u, 64u, 4096u, 4097u, 1u << 28, (1u << 28) + 1, 0x55555555u, 0x55555556u, 0x7FFFFFFFu, 0x80000000u, 0xFFFFFFFEu, 0xFFFFFFFFu, words - 1, words,
+                          words + 1, r.count, r.p0},
+                         on_taken);
+            if (r.kind != SCATTER) continue;
+            for (uint32_t w = 0; w < 1 + 3 * r.p0; w++)           // the extent, the index cells, the source cells, the offsets
+                for (const uint32_t v : {0u, 1u, r.count - 1, r.count, r.count + 1, 0x7FFFFFFFu, 0x80000000u, 0xFFFFFFFFu, (uint32_t)((uint64_t)plan.n_advice << plan.k)})
+                    tamper(g.blob, g.pool_at + 4 * (r.b + w), v, on_taken);
         }
-    }
+    });
     CHECK(n_ok >= 8 && n_bad >= 30 && n_claims >= 20 && n_tampered >= 1000 && n_taken >= 8 && n_taken < n_tampered,
           "the manifest is thin: %u good, %u bad, %u records of the new kinds, %u tampered words of which %u taken", n_ok, n_bad, n_claims, n_tampered, n_taken);
-    if (failures) {
-        fprintf(stderr, "%d checks failed\n", failures);
-        return 1;
-    }
-    printf("%u good and %u bad blobs, %u tampered words: all checks passed\n", n_ok, n_bad, n_tampered);
-    return 0;
+    return finish("words");
 }

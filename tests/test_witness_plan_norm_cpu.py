@@ -45,7 +45,7 @@ def test_the_host_interpreter_equals_the_closed_form(parser, name):
 def test_the_cases_plant_what_they_claim():
     from ezkl_amd import ezkl_layout as EL, witness_plan as WP
     assert (WP.RECIP, WP.ISQRT, WP.VERSION) == (24, 25, 1) and (WP.RECIP_ERROR, WP.SQRT_ERROR) == (EL.RECIP_ERROR, EL.SQRT_ERROR)
-    assert [WP.kind_name(kd) for kd in (WP.ARGSORT, 23, WP.RECIP, WP.ISQRT, 26, WP.UNASSIGNED)] == ["argsort", "?", "recip", "sqrt", "?", "?"]
+    assert [WP.kind_name(kd) for kd in (WP.ARGSORT, 23, WP.RECIP, WP.ISQRT, 26, 16)] == ["argsort", "?", "recip", "sqrt", "?", "?"]
     assert T.COUNTS == [1, 63, 64, 65, 255, 256, 257] and T.RECIP_SCALES == [1, 1 << 21, (1 << 62) - 1] and T.SQRT_SCALES == [1, 128, (1 << 31) - 1]
     assert [T.recip_expected(x, 1) for x in (1, 2, 3, -1, -2, -3)] == [1, 0, 0, -1, -1, 0], "the ties +-2S: towards zero above, away from it below"
     assert [T.sqrt_expected(t) for t in (1, 2, 3, 6, 7, (1 << 62) - 1)] == [1, 1, 2, 2, 3, 1 << 31]

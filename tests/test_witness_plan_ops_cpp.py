@@ -2,42 +2,13 @@
 UndefinedBehaviorSanitizer: tests/cpp/test_witness_plan_ops.cpp reads the blobs written here -- synthetic plans of the new kinds it must
 take, and every plan of witness_synth_ops.bad_plans() with the message the Python validator gave for it -- and says what it asserts.  No
 device, no library loaded into the interpreter, no preload."""
-import os
-import subprocess
-
-import pytest
-
 import witness_synth_ops as O
+import wplan_cpp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "test_witness_plan_ops.cpp")
-_FLAGS = ["-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "ezkl_amd", "csrc"), SRC]
 GOOD = ["sum-ragged-33-17-16-5-1-w3", "prod-partial-operandless-ragged", "sum-scans9-steps33-w3", "prod-special-values", "gather-lanes257-table300",
         "gather-outside-table1-lanes65", "clamp-bounds-and-edges"]
 
 
-def _run(cmd, **kw):
-    r = subprocess.run(cmd, capture_output=True, text=True, **kw)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
-    return r
-
-
 def test_the_parser_additions_under_the_sanitizers(tmp_path):
-    from ezkl_amd import witness_plan as WP
-    lines = []
-    for i, plan in enumerate([O.small_plan().plan] + [O.CASES[name](1).plan for name in GOOD]):
-        (tmp_path / ("good_%d.bin" % i)).write_bytes(plan.validate().to_bytes())
-        lines.append("good_%d.bin ok" % i)
-    for i, (words, rec, plan) in enumerate(O.bad_plans()):
-        with pytest.raises(WP.PlanError, match=words) as e:
-            WP.validate(plan)
-        (tmp_path / ("bad_%d.bin" % i)).write_bytes(plan.to_bytes())
-        lines.append("bad_%d.bin bad %s" % (i, e.value))
-    (tmp_path / "manifest.txt").write_text("\n".join(lines) + "\n")
-    exe = str(tmp_path / "test_witness_plan_ops")
-    _run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"] + _FLAGS + ["-o", exe])
-    r = _run([exe, str(tmp_path)], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    assert "all checks passed" in r.stdout
-    for mark in ("Sanitizer", "runtime error"):
-        assert mark not in r.stderr, r.stderr[-6000:]
+    plans = [O.small_plan().plan] + [O.CASES[name](1).plan for name in GOOD]
+    wplan_cpp.parser_program(tmp_path, "test_witness_plan_ops", plans, O.bad_plans(), ends_with=False)

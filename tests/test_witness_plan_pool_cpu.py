@@ -43,8 +43,8 @@ def test_the_host_interpreter_equals_the_closed_form(parser, name):
 
 def test_the_cases_plant_what_they_claim():
     from ezkl_amd import ezkl_layout as EL, witness_plan as WP
-    assert (WP.ARGEXT, WP.ARGEXT_CHUNK, WP.VERSION, WP.SORT_TILE, len(WP.KIND_NAMES)) == (27, 4096, 1, 2048, 21) and WP.ARGEXT_ERROR == EL.ARGEXT_ERROR
-    assert [WP.kind_name(kd) for kd in (WP.ISQRT, 26, WP.ARGEXT, 28, 23, WP.UNASSIGNED)] == ["sqrt", "?", "argext", "?", "?", "?"]
+    assert (WP.ARGEXT, WP.ARGEXT_CHUNK, WP.VERSION, WP.SORT_TILE) == (27, 4096, 1, 2048) and WP.ARGEXT_ERROR == EL.ARGEXT_ERROR
+    assert [WP.kind_name(kd) for kd in (WP.ISQRT, 26, WP.ARGEXT, 28, 23, 16)] == ["sqrt", "?", "argext", "?", "?", "?"]
     assert T.LENGTHS == [1, 2, 3, 31, 32, 33, 63, 64, 65, 255, 256, 257, 4095, 4096, 4097, 8193] and T.MANY == [(300, 5), (7, 64), (9, 100), (130, 1)]
     assert T.closed_form([2, 15, 2], 0) == 1 and T.closed_form([1, 1, 0], 0) == 0 and T.closed_form([3, -1, 5, -1], 1) == 1
     for mode in (0, 1):
