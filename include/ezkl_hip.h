@@ -471,7 +471,10 @@ int ezkl_hip_batch_invert_dev(void* a_dev, size_t n, void* stream);
 
 /* ---- quotient numerator: replaces plonk::evaluation::Evaluator::evaluate_h's row sweep
  *      (GraphEvaluator::evaluate; icicle "gate_eval" program on the GPU build) ---- */
-/* instruction = 8 x u32: [op, target, s0.kind, s0.idx, s0.rot, s1.kind, s1.idx, s1.rot] */
+/* instruction = 8 x u32: [op, target, s0.kind, s0.idx, s0.rot, s1.kind, s1.idx, s1.rot] (a unary op has s0 only).  An intermediate index
+ * may be rewritten any number of times, also by an instruction that reads it; a HORNER_STEP on a target no instruction has written is
+ * its term s0; a read of an intermediate that is not written at that point is EZKL_ERR_INVALID; the result is the last instruction's
+ * target (tests/evalh_forms.py). */
 enum { EZKL_OP_ADD = 0, EZKL_OP_SUB, EZKL_OP_MUL, EZKL_OP_SQUARE, EZKL_OP_DOUBLE, EZKL_OP_NEGATE,
        EZKL_OP_STORE, EZKL_OP_HORNER_STEP /* target = target*s1 + s0 */ };
 enum { EZKL_SRC_CONST = 0, EZKL_SRC_INTERMEDIATE, EZKL_SRC_COLUMN, EZKL_SRC_CHALLENGE, EZKL_SRC_PREVIOUS };

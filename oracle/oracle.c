@@ -469,7 +469,9 @@ void oracle_eval_program(const oracle_program *p, fe *out) {
             for (uint32_t ii = 0; ii < p->n_instr; ii++) {
                 const uint32_t *I = p->code + 8 * (size_t)ii;
                 fe s[2];
-                for (int q = 0; q < 2; q++) {
+                /* a unary instruction has one operand: its second triple is not part of the program and is not read */
+                const int n_src = (I[0] == OP_SQUARE || I[0] == OP_DOUBLE || I[0] == OP_NEGATE || I[0] == OP_STORE) ? 1 : 2;
+                for (int q = 0; q < n_src; q++) {
                     uint32_t kind = I[2 + 3 * q], idx = I[3 + 3 * q], rot = I[4 + 3 * q];
                     switch (kind) {
                     case SRC_CONST: s[q] = p->constants[idx]; break;

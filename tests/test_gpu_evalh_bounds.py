@@ -11,6 +11,7 @@ import pytest
 
 from conftest import ROOT
 import evalh_programs as EP
+from evalh_forms import _draw, _ints, _words
 from oracle import binding as ob
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -19,31 +20,6 @@ import evalh29_model as E  # noqa: E402
 pytestmark = pytest.mark.gpu
 P = E.P
 MODES = [("jit", "2"), ("jit", "1"), ("jit", "0"), ("interp", "2")]
-
-
-def _words(ints):
-    return np.frombuffer(b"".join(int(x).to_bytes(32, "little") for x in ints), np.uint64).reshape(-1, 4).copy()
-
-
-def _ints(a):
-    b = np.ascontiguousarray(a, np.uint64).tobytes()
-    return [int.from_bytes(b[32 * i:32 * i + 32], "little") for i in range(len(b) // 32)]
-
-
-def _draw(rng, n):
-    """n words, each drawn from: p - 1, 0, 1, p - 2, (p -+ 1) / 2, uniform over [2^253, p), uniform over all of [0, p)"""
-    special = [P - 1, 0, 1, P - 2, (P - 1) // 2, (P + 1) // 2]
-    kind = rng.integers(0, 8, n)
-    out = []
-    for i in range(n):
-        k = int(kind[i])
-        if k < 6:
-            out.append(special[k])
-        else:
-            lo = (1 << 253) if k == 6 else 0
-            w = int.from_bytes(rng.bytes(32), "little") % (P - lo) + lo      # bias < 2^-250
-            out.append(w)
-    return out
 
 
 def _datasets(rng, ne, ncols, nchal):
