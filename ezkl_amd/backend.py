@@ -153,6 +153,16 @@ class _Bases:
         _l.check(_l.load().ezkl_hip_bases_download(self.h, _p(out)), "ezkl_hip_bases_download")
         return out
 
+    def check(self, first=0, n=None):
+        """is every record in [first, first + n) a point of G1, as halo2's raw-bytes reader decides it (ezkl_hip_bases_check)?  ->
+        dict(bad: how many are not, first_bad: the smallest such index in the set or None, reason: 1 x >= q / 2 y >= q / 3 off the curve
+        (0: none), identities: all-zero records, which are valid).  Reads the resident records; builds no window table."""
+        n = self.n - first if n is None else n
+        out = np.zeros(4, np.uint64)
+        _l.check(_l.load().ezkl_hip_bases_check(self.h, C.c_size_t(first), C.c_size_t(n), _p(out)), "ezkl_hip_bases_check")
+        bad = int(out[0])
+        return dict(bad=bad, first_bad=int(out[1]) if bad else None, reason=int(out[2]), identities=int(out[3]))
+
     def prepare(self):
         """start the window-table precompute now, without waiting (ezkl_hip_bases_prepare)"""
         _l.check(_l.load().ezkl_hip_bases_prepare(self.h), "ezkl_hip_bases_prepare")
@@ -314,6 +324,13 @@ class ParamsKZG:
         self.k, self.n = k, 1 << k
         self._g = _Bases(g)
         self._gl = _Bases(g_lagrange)
+
+    @classmethod
+    def from_bases(cls, k, g, g_lagrange):
+        """around two base sets that are resident already (and are this object's to free from here on)"""
+        self = cls.__new__(cls)
+        self.k, self.n, self._g, self._gl = k, 1 << k, g, g_lagrange
+        return self
 
     @classmethod
     def read(cls, buf):
@@ -620,6 +637,96 @@ def gen_srs(k, s):
     vec_scale(den.ptr, _to_mont((pow(s, n, _R) - 1) * pow(n, -1, _R) % _R), den.ptr, n)
     gl = _Bases.from_scalars(G, den.ptr, n)
     return g, gl
+
+
+POINT_REASONS = {1: "x coordinate not below the field modulus", 2: "y coordinate not below the field modulus", 3: "point not on the curve"}
+
+
+def srs_check_key(seed=None):
+    """the 32-byte ChaCha20 key check_srs draws its scalars under: OS entropy, or derived from `seed` (an int) so that a run can be replayed"""
+    import hashlib
+    import os
+    if seed is None:
+        return os.urandom(32)
+    return hashlib.sha256(b"ezkl_amd.check_srs" + int(seed).to_bytes(32, "little", signed=True)).digest()
+
+
+def srs_power_combination(g, key):
+    """(A, B) = (sum r_i g[i], sum r_i g[i + 1]) over i < n - 1 for the n - 1 scalars of ChaCha20 stream 0 under `key`: the same resident
+    scalars in two MSMs on the one handle, at base offsets 0 and 1.  A one-point set has no adjacent pair: both are the identity."""
+    m = g.n - 1
+    if m == 0:
+        return np.zeros(8, np.uint64), np.zeros(8, np.uint64)
+    r = DeviceBuffer(32 * m)
+    try:
+        chacha20_fr(key, 0, r.ptr, m)
+        return msm_g1_dev(g, r.ptr, m, 0), msm_g1_dev(g, r.ptr, m, 1)
+    finally:
+        r.free()
+
+
+def check_srs(srs, seed=None, structure=True):
+    """Is a parsed SRS file (codecs.read_srs) what a prover may use?  -> dict(k, key, points=dict(g=.., g_lagrange=..), powers, lagrange,
+    g2, ok, reason): `points` holds Bases.check of either set and always runs; powers / lagrange / g2 are True / False, or None where the
+    check did not run; reason is None or says in words what is wrong; key is the ChaCha20 key the scalars came from (srs_check_key(seed)).
+    structure=True adds, once every point is valid:
+      identities  an identity anywhere in either set fails ("degenerate set"): the point check accepts it, as halo2's reader does, but no
+                  power of a usable secret and no L_i(s) of one is zero;
+      powers      e(A, s_g2) == e(B, g2) for (A, B) = srs_power_combination: g[i + 1] = s g[i] for every i and the s of s_g2, or the
+                  pairing passes with probability 1 / r.  g2 / s_g2 are first held to be canonical points of order r of the twist;
+      lagrange    commit_lagrange(v) == commit(iNTT v) byte for byte for a uniform v (stream 1): g_lagrange is the Lagrange basis of g.
+    Both sets are uploaded for the duration of the call and freed on every path."""
+    from . import native as _nv                            # (native imports plonk, which imports this module)
+    k = int(srs["k"])
+    n = 1 << k
+    key = srs_check_key(seed)
+    rep = dict(k=k, key=key, points={}, powers=None, lagrange=None, g2=None, ok=False, reason=None)
+    sets, v = {}, None
+    try:
+        for name in ("g", "g_lagrange"):
+            sets[name] = _Bases(np.ascontiguousarray(srs[name]))
+            if sets[name].n != n:
+                raise ValueError("check_srs: %s has %d points, k = %d" % (name, sets[name].n, k))
+            rep["points"][name] = sets[name].check()
+        for name in ("g", "g_lagrange"):
+            p = rep["points"][name]
+            if p["bad"]:
+                rep["reason"] = "%s[%d]: %s" % (name, p["first_bad"], POINT_REASONS[p["reason"]])
+                return rep
+        if not structure:
+            rep["ok"] = True
+            return rep
+        ids = sum(rep["points"][name]["identities"] for name in ("g", "g_lagrange"))
+        if ids:
+            rep["reason"] = "degenerate set: %d identities" % ids
+            return rep
+        a, b = srs_power_combination(sets["g"], key)
+        try:
+            rep["powers"] = _nv.srs_pairing_check(a, b, srs["g2"], srs["s_g2"])
+            rep["g2"] = True
+        except _nv.SrsOperandError as e:
+            rep["g2"] = False
+            rep["reason"] = str(e)
+            return rep
+        v = DeviceBuffer(32 * n)
+        chacha20_fr(key, 1, v.ptr, n)
+        left = msm_g1_dev(sets["g_lagrange"], v.ptr, n)
+        w = pow(EvaluationDomain.ROOT, 1 << (28 - k), _R)
+        if k:                                                  # (the one-point transform is the identity)
+            ntt_dev(v.ptr, k, _to_mont(pow(w, -1, _R)), inverse=True)
+        rep["lagrange"] = bool((left == msm_g1_dev(sets["g"], v.ptr, n)).all())
+        if not rep["powers"]:
+            rep["reason"] = "g: not consecutive powers of one secret"
+        elif not rep["lagrange"]:
+            rep["reason"] = "g_lagrange is not the Lagrange basis of g"
+        else:
+            rep["ok"] = True
+        return rep
+    finally:
+        if v is not None:
+            v.free()
+        for b in sets.values():
+            b.free()
 
 
 _Q = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47

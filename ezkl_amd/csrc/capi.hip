@@ -591,6 +591,13 @@ int ezkl_hip_bases_download(ezkl_bases_t h, void* out_host) {
     EZ_HIP(copy_sync(c, out_host, b->pts, b->n * 64, hipMemcpyDeviceToHost));
     return EZKL_OK;
 }
+int ezkl_hip_bases_check(ezkl_bases_t h, size_t first, size_t n, uint64_t out[4]) {
+    if (!h || !out) return EZKL_ERR_INVALID;
+    Bases* b = reinterpret_cast<Bases*>(h);
+    if (first > b->n || n > b->n - first) return EZKL_ERR_INVALID;
+    EZ_CTX(c);
+    return g1_check(c, c->stream, b->pts, first, n, out);     // the 64-byte records alone: no window table is built or read
+}
 int ezkl_hip_bases_from_scalars(const void* base_point, const void* scalars_dev, size_t n, ezkl_bases_t* out) {
     if (!base_point || !scalars_dev || !out || n == 0) return EZKL_ERR_INVALID;
     EZ_CTX(c);

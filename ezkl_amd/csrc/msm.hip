@@ -37,8 +37,10 @@
 #include "curve.hpp"
 #include "curve29.hpp"
 #include "host64.hpp"
+#include "srs_check.hpp"  // the point predicate of g1_check_kernel
 #include "msm_plan.hpp"   // constants, WinPlan / pick_plan, ReduceGeom and the launch plan (host-only arithmetic)
 #include <string.h>
+#include <algorithm>
 
 namespace ezkl {
 
@@ -1655,6 +1657,76 @@ int g1_mul_fixed(Ctx* c, hipStream_t st, const void* base_host, const fe_t* scal
     memcpy(&b, base_host, 64);
     hipLaunchKernelGGL(g1_mul_fixed_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, b, scalars, n, (g1a_t*)out_dev);
     EZ_HIP(hipGetLastError());
+    return EZKL_OK;
+}
+
+// ---- is every record of a resident base set a point of G1?  (srs_check.hpp: halo2's RawBytes reader refuses a non-canonical coordinate
+//      and a point off the curve; an SRS file is the one large input this library takes from outside) ----
+// One lane per point, a grid-stride loop over [first, first + n) of the set with the next record's loads issued before this one's three
+// products.  acc[0] += bad points, acc[1] = min over bad points of (index << 2 | reason), acc[2] += identities: two sums and a minimum, so
+// the answer does not depend on the order the waves arrive in.  Counts are wave ballots (lane 0 of a wave is in every trip any of its
+// lanes is in, so its copy is complete); a wave touches memory only if it has something to report, with vector atomics.  Any bytes are
+// legal input: the predicate branches on them and never indexes by them.
+__global__ __launch_bounds__(256) void g1_check_kernel(const g1a_t* pts, size_t first, size_t n, unsigned long long* acc) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long key = ~0ull;
+    uint32_t n_bad = 0, n_id = 0;
+    g1a_t next;
+    if (i < n) next = ld_g1a(pts + first + i);
+    while (i < n) {
+        const g1a_t p = next;
+        if (i + stride < n) next = ld_g1a(pts + first + i + stride);
+        uint32_t w[16];
+#pragma unroll
+        for (int j = 0; j < 8; j++) { w[j] = p.x.v[j]; w[8 + j] = p.y.v[j]; }
+        bool id;
+        const uint32_t reason = srs::point_reason<Fq>(w, &id);
+        n_bad += (uint32_t)__popcll(__ballot(reason != 0));
+        n_id += (uint32_t)__popcll(__ballot(id));
+        if (reason) {
+            const unsigned long long k = ((unsigned long long)(first + i) << 2) | reason;
+            key = k < key ? k : key;
+        }
+        i += stride;
+    }
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+        const unsigned long long o = __shfl_xor(key, off);
+        key = o < key ? o : key;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (n_bad) {
+            atomicAdd(acc, (unsigned long long)n_bad);
+            atomicMin(acc + 1, key);
+        }
+        if (n_id) atomicAdd(acc + 2, (unsigned long long)n_id);
+    }
+}
+// out: {bad points, smallest bad index in the set or UINT64_MAX, its reason, identities}.  The caller has checked the range against the set.
+int g1_check(Ctx* c, hipStream_t st, const void* pts_dev, size_t first, size_t n, uint64_t out[4]) {
+    out[0] = 0; out[1] = UINT64_MAX; out[2] = 0; out[3] = 0;
+    if (n == 0) return EZKL_OK;
+    unsigned long long* acc = nullptr;
+    int rc = arena_reserve(c->aux, 32, st, (void**)&acc);
+    if (rc) return rc;
+    hipEvent_t e0, e1;
+    if ((rc = ev_pair(c, "bases_check", &e0, &e1))) return rc;
+    EZ_HIP(hipMemsetAsync(acc, 0, 32, st));
+    EZ_HIP(hipMemsetAsync(acc + 1, 0xff, 8, st));
+    // one workgroup per CU at the most: 2^16 lanes on 256 CUs, each with its next record in flight
+    const unsigned blocks = std::min<size_t>(cdiv(n, 256), (size_t)std::max(c->num_cus, 1));
+    EZ_HIP(hipEventRecord(e0, st));
+    hipLaunchKernelGGL(g1_check_kernel, dim3(blocks), dim3(256), 0, st, (const g1a_t*)pts_dev, first, n, acc);
+    EZ_HIP(hipGetLastError());
+    EZ_HIP(hipEventRecord(e1, st));
+    unsigned long long host[3] = {0, 0, 0};
+    EZ_HIP(hipMemcpyAsync(host, acc, sizeof host, hipMemcpyDeviceToHost, st));
+    if ((rc = arena_done(c->aux, st))) return rc;
+    EZ_HIP(hipStreamSynchronize(st));
+    out[0] = host[0];
+    out[3] = host[2];
+    if (host[1] != ~0ull) { out[1] = host[1] >> 2; out[2] = host[1] & 3; }
     return EZKL_OK;
 }
 

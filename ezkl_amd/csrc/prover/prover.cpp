@@ -26,6 +26,7 @@
 #include "keyfile.hpp"
 #include "verify.hpp"
 #include "../witness_plan.hpp"
+#include "../srs_check.hpp"
 
 namespace ezkl_prover {
 using ezkl_hip::check;
@@ -2554,6 +2555,46 @@ int ezkl_prover_g2_mul_generator(const void* scalar, void* out128) {
         std::memcpy(sv.data(), scalar, 32);
         if (cmp(sv, FR.p) >= 0) throw Error(EZKL_ERR_INVALID, "non-canonical scalar");
         bn::g2_to_bytes(bn::g2_mul(bn::g2_generator(), Fe{sv}.canonical()), (uint8_t*)out128);
+    });
+}
+// e(a, s_g2) == e(b, g2) for points of an SRS file: with a = sum r_i g[i] and b = sum r_i g[i + 1] over random r_i this says that g is a
+// sequence of consecutive powers of the secret s_g2 carries (backend.check_srs).  Operands are refused, not computed with, unless they are
+// what the pairing assumes: G1 points by the file reader's predicate (srs_check.hpp), G2 points canonical, on the twist, not the identity
+// and of order r -- the twist's cofactor is not 1, so being on it does not put a point in G2.
+static bn::G2 srs_g2_operand(const void* bytes, const char* name) {
+    U256 l[4];
+    std::memcpy(l, bytes, 128);
+    for (const U256& c : l)
+        if (cmp(c, FQ.p) >= 0) throw Error(EZKL_ERR_INVALID, std::string(name) + ": coordinate not below the field modulus");
+    const bn::G2 p = bn::g2_from_bytes((const uint8_t*)bytes);
+    if (p.inf) throw Error(EZKL_ERR_INVALID, std::string(name) + " is the identity");
+    if (!bn::g2_on_curve(p)) throw Error(EZKL_ERR_INVALID, std::string(name) + ": point not on the twist");
+    if (!bn::g2_mul(p, FR.p).inf) throw Error(EZKL_ERR_INVALID, std::string(name) + ": point not of order r");
+    return p;
+}
+static bn::P1 srs_g1_operand(const void* bytes, const char* name) {
+    uint32_t w[16];
+    std::memcpy(w, bytes, 64);
+    bool identity;
+    static const char* const why[] = {"", "x not below the field modulus", "y not below the field modulus", "point not on the curve"};
+    const uint32_t reason = ezkl::srs::point_reason<ezkl::srs::FqPortable>(w, &identity);
+    if (reason) throw Error(EZKL_ERR_INVALID, std::string(name) + ": " + why[reason]);
+    G1 g;
+    std::memcpy(g.x.data(), bytes, 32);
+    std::memcpy(g.y.data(), (const uint8_t*)bytes + 32, 32);
+    return bn::p1_from(g);
+}
+int ezkl_prover_srs_pairing_check(const void* a_g1, const void* b_g1, const void* g2, const void* s_g2, int* ok) {
+    if (!a_g1 || !b_g1 || !g2 || !s_g2 || !ok) return EZKL_ERR_INVALID;
+    *ok = 0;
+    return guarded([&] {
+        const bn::P1 a = srs_g1_operand(a_g1, "a"), b = srs_g1_operand(b_g1, "b");
+        const bn::G2 q = srs_g2_operand(g2, "g2"), sq = srs_g2_operand(s_g2, "s_g2");
+        if (a.inf && b.inf) {                   // the k = 0 file: one point, no adjacent pair to relate
+            *ok = 1;
+            return;
+        }
+        *ok = bn::pairing_check({{a, sq}, {bn::p1_neg(b), q}}) ? 1 : 0;
     });
 }
 int ezkl_prover_keccak256(const void* data, size_t len, void* out32) {

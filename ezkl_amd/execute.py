@@ -164,19 +164,76 @@ def gen_srs(srs_path, logrows, secret=None):
     return len(data)
 
 
+class SrsError(ValueError):
+    """an SRS file that must not be used: .report is what backend.check_srs (or the loaders' point check, in the same shape) found"""
+
+    def __init__(self, msg, report):
+        super().__init__(msg)
+        self.report = report
+
+
+SRS_CHECK_POLICIES = ("points", "full", "off")
+
+
+def _srs_policy():
+    """EZKL_SRS_CHECK: what the loaders check before a point set of an SRS file is used.  "points" (the default): every point that will be
+    used is a point of G1 (Bases.check); "full": also the structure of the whole file (backend.check_srs); "off": nothing."""
+    policy = os.environ.get("EZKL_SRS_CHECK", "points")
+    if policy not in SRS_CHECK_POLICIES:
+        raise ValueError("EZKL_SRS_CHECK must be one of points, full, off; got %r" % policy)
+    return policy
+
+
+def check_srs(srs_path, structure=True, seed=None):
+    """The whole SRS file, whatever circuit it will later serve: every point of both sets on the device, and with structure=True that g is
+    a sequence of powers of the secret s_g2 carries (a random combination and one pairing), that g_lagrange is the Lagrange basis of g
+    and that neither set holds an identity (backend.check_srs).  Returns the report; a file that fails raises SrsError, which carries
+    it, with a message such as "g_lagrange[513]: point not on the curve"."""
+    report = B.check_srs(codecs.read_srs(open(srs_path, "rb").read()), seed=seed, structure=structure)
+    if not report["ok"]:
+        raise SrsError(report["reason"], report)
+    return report
+
+
 def _read_srs(srs_path, logrows):
-    """the SRS file, parsed; one smaller than the circuit is refused"""
+    """the SRS file, parsed; one smaller than the circuit is refused.  Under EZKL_SRS_CHECK=full the whole file is held to
+    backend.check_srs here, before any of it is used."""
+    policy = _srs_policy()
     srs = codecs.read_srs(open(srs_path, "rb").read())
     if srs["k"] < logrows:
         raise ValueError("SRS too small: k=%d < logrows=%d" % (srs["k"], logrows))
+    if policy == "full":
+        report = B.check_srs(srs)
+        if not report["ok"]:
+            raise SrsError(report["reason"], report)
     return srs
+
+
+def _srs_bases(points, name):
+    """THE way a point set of an SRS file becomes a resident base set in this module: uploaded, and unless EZKL_SRS_CHECK=off every point
+    of it -- exactly the points that will be used -- checked on the device before anything else touches the handle.  A bad point raises
+    SrsError naming the set, the index and the reason; nothing stays resident then."""
+    policy = _srs_policy()
+    b = B.Bases(np.ascontiguousarray(points))
+    if policy == "off":
+        return b
+    try:
+        found = b.check()
+    except BaseException:
+        b.free()
+        raise
+    if found["bad"]:
+        b.free()
+        why = "%s[%d]: %s" % (name, found["first_bad"], B.POINT_REASONS[found["reason"]])
+        raise SrsError(why, dict(k=None, key=None, points={name: found}, powers=None, lagrange=None, g2=None, ok=False, reason=why))
+    return b
 
 
 def _downsized(srs, logrows):
     """`params.downsize(logrows)` of an SRS larger than the circuit -> the two resident base sets (g, g_lagrange): the coefficient basis
     is truncated, the Lagrange basis of the smaller domain is rebuilt on the device by an inverse NTT over G1 (ezkl_hip_bases_downsize =
     halo2's g_to_lagrange)"""
-    big = B.Bases(np.ascontiguousarray(srs["g"][:1 << logrows]))
+    big = _srs_bases(srs["g"][:1 << logrows], "g")
     try:
         return big.downsize(logrows)
     finally:
@@ -202,7 +259,7 @@ def setup(compiled_circuit, srs_path, vk_path, pk_path, sample_input=None):
     srs = load_params_prover(srs_path, circuit.k)
     x = sample_input if sample_input is not None else [0] * circuit.n_inputs
     cs, fixed, copies, reg = circuit.keygen_inputs(x)          # synthesis without witness values: selectors + copy constraints
-    bg = B.Bases(srs["g"])
+    bg = _srs_bases(srs["g"], "g")
     try:
         pk = NV.NativeProvingKey(NV.NativeCircuit(cs), bg, EL.cols_to_mont(fixed, B), copies)
         pk.set_selectors(reg.selector_rows())
@@ -323,7 +380,13 @@ def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None
         if vk_path is not None and have_srs:
             blinding = 5                 # vk.cs().blinding_factors() of this gate family: no advice column is queried at more than 3 rotations
             srs = load_params_prover(srs_path, ra["logrows"])
-            params = B.ParamsKZG(ra["logrows"], srs["g"], srs["g_lagrange"])
+            bg = _srs_bases(srs["g"], "g")
+            try:
+                bgl = _srs_bases(srs["g_lagrange"], "g_lagrange")
+            except BaseException:
+                bg.free()
+                raise
+            params = B.ParamsKZG.from_bases(ra["logrows"], bg, bgl)
             try:
                 def commit(vals):
                     msg = np.stack([np.frombuffer(((v % EL.R) * (1 << 256) % EL.R).to_bytes(32, "little"), np.uint64) for v in vals])
@@ -461,8 +524,8 @@ class Prover:
             if srs["k"] > k:                                     # load_params_prover's downsize, its two resident sets kept
                 self.bg, self.bgl = _downsized(srs, k)
             else:
-                self.bg = B.Bases(srs["g"])
-                self.bgl = B.Bases(srs["g_lagrange"])
+                self.bg = _srs_bases(srs["g"], "g")
+                self.bgl = _srs_bases(srs["g_lagrange"], "g_lagrange")
             del srs
             self.bg.prepare(); self.bgl.prepare()                # the window tables build while the key is read
             t = stage("srs_to_device", t)
@@ -606,7 +669,7 @@ def verify(proof_path, compiled_circuit, vk_path=None, srs_path=None, recommit=F
     if os.path.getsize(vk_path) <= len(vk_bytes):                               # a vk-only file has no polynomials to commit again
         raise ValueError("recommit=True needs the PROVING key file (its polynomials are committed again under this SRS); %s is a verifying key" % vk_path)
     srs = codecs.read_srs(open(srs_path, "rb").read())
-    bg = B.Bases(srs["g"])
+    bg = _srs_bases(srs["g"], "g")
     try:
         pk = NV.NativeProvingKey.from_file(NV.NativeCircuit(cs_), vk_path, recommit=bg)
         return NV.verify_proof(pk, srs["g2"], srs["s_g2"], pr["proof"], pr["instances"])

@@ -16,7 +16,7 @@ _lib = None
 SYMBOLS = ["ezkl_prover_cs_parse", "ezkl_prover_cs_free", "ezkl_prover_cs_info", "ezkl_prover_cs_set_shard", "ezkl_prover_cs_set_shard_comm", "ezkl_prover_cs_set_shard_full_bases", "ezkl_prover_cs_set_advice_by_pointer", "ezkl_prover_cs_set_sweep_gather",
            "ezkl_prover_cs_sharded_sweeps", "ezkl_prover_cs_set_shard_exchange", "ezkl_prover_cs_shard_stats", "ezkl_prover_group_create", "ezkl_prover_group_size", "ezkl_prover_group_free",
            "ezkl_prover_group_load_srs", "ezkl_prover_group_keygen", "ezkl_prover_group_pk", "ezkl_prover_group_pk_read_file", "ezkl_prover_pk_residency", "ezkl_prover_group_create_proof", "ezkl_prover_keygen", "ezkl_prover_pk_free", "ezkl_prover_pk_sweep_stats", "ezkl_prover_pk_write", "ezkl_prover_pk_read", "ezkl_prover_pk_read_file", "ezkl_prover_pk_recommit", "ezkl_prover_pk_set_selectors", "ezkl_prover_pk_set_transcript_repr", "ezkl_prover_vk",
-           "ezkl_prover_create_proof", "ezkl_prover_create_proof_fmt", "ezkl_prover_mock", "ezkl_prover_verify_proof", "ezkl_prover_verify_proof_vk", "ezkl_prover_g2_mul_generator", "ezkl_prover_keccak256", "ezkl_prover_last_error", "ezkl_prover_witness_plan_check"]
+           "ezkl_prover_create_proof", "ezkl_prover_create_proof_fmt", "ezkl_prover_mock", "ezkl_prover_verify_proof", "ezkl_prover_verify_proof_vk", "ezkl_prover_g2_mul_generator", "ezkl_prover_srs_pairing_check", "ezkl_prover_keccak256", "ezkl_prover_last_error", "ezkl_prover_witness_plan_check"]
 ADVICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p))
 RNG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_size_t)
 FOLD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32)
@@ -360,6 +360,24 @@ def verify_proof(pk, g2, s_g2, proof, instances=()):
     proof = bytes(proof)
     _check(load().ezkl_prover_verify_proof(pk.h, bytes(g2), bytes(s_g2), proof, C.c_size_t(len(proof)), _ptr_array(inst), lens, C.byref(ok)),
            "ezkl_prover_verify_proof")
+    return bool(ok.value)
+
+
+class SrsOperandError(ValueError):
+    """ezkl_prover_srs_pairing_check refused an operand (EZKL_ERR_INVALID): the message says which and why"""
+
+
+def srs_pairing_check(a, b, g2, s_g2):
+    """e(a, s_g2) == e(b, g2) on the host (ezkl_prover_srs_pairing_check): a, b 64-byte G1 points (bytes or 8 x u64), g2 / s_g2 the
+    128-byte tail elements of the SRS file.  An operand that is not a point of its group raises SrsOperandError."""
+    a, b, g2, s_g2 = (x.tobytes() if isinstance(x, np.ndarray) else bytes(x) for x in (a, b, g2, s_g2))
+    if (len(a), len(b), len(g2), len(s_g2)) != (64, 64, 128, 128):
+        raise ValueError("srs_pairing_check: G1 points are 64 bytes, G2 points 128")
+    ok = C.c_int(0)
+    rc = load().ezkl_prover_srs_pairing_check(a, b, g2, s_g2, C.byref(ok))
+    if rc == -3:
+        raise SrsOperandError(load().ezkl_prover_last_error().decode())
+    _check(rc, "ezkl_prover_srs_pairing_check")
     return bool(ok.value)
 
 

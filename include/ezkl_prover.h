@@ -239,6 +239,14 @@ int ezkl_prover_verify_proof_vk(ezkl_cs_t cs, const void* vk_buf, size_t vk_len,
                                 const void* const* instances, const uint32_t* instance_lens, int* accepted);
 /* [s] G2 for a Montgomery Fr scalar s: the `s_g2` of a test SRS (gen_srs, src/pfsys/srs.rs:13-16); s = 1 gives the generator g2. */
 int ezkl_prover_g2_mul_generator(const void* scalar, void* out128);
+/* The pairing half of the SRS file check (backend.check_srs): *ok = 1 iff e(a, s_g2) == e(b, g2).  a_g1 / b_g1: 64-byte affine G1 points,
+ * g2 / s_g2: the 128-byte G2 elements that end the file, all in the file's Montgomery byte layout.  With a = sum r_i g[i] and
+ * b = sum r_i g[i + 1] for random r_i it holds, except with probability 1 / r, only if every g[i + 1] is s g[i] for the s of s_g2.
+ * EZKL_ERR_INVALID (the reason in ezkl_prover_last_error) for an operand the pairing must not be fed: a G1 point the file reader's
+ * predicate refuses (csrc/srs_check.hpp), a G2 point with a coordinate not below q, off the twist, the identity, or not of order r ([r]P
+ * computed: the twist has a cofactor, so on-curve is not in-group).  a and b both the identity: ok without a pairing (the k = 0 file has
+ * no adjacent pair).  Host only: no device. */
+int ezkl_prover_srs_pairing_check(const void* a_g1, const void* b_g1, const void* g2, const void* s_g2, int* ok);
 /* keccak256 of a byte string (exposed so the transcript can be tested against the Python restatement without a GPU) */
 int ezkl_prover_keccak256(const void* data, size_t len, void* out32);
 /* the host-side validation ezkl_hip_witness_plan_upload runs on a witness-plan blob (ezkl_hip.h; csrc/witness_plan.hpp), without a device
