@@ -148,6 +148,17 @@ class _Bases:
             out.append(b)
         return tuple(out)
 
+    def mul_scalars(self, scalars_ptr, first=0, n=None):
+        """a new resident set of n points, out[i] = scalars[i] * self[first + i], for n resident Montgomery scalars: the per-row product
+        of an SRS update (ezkl_hip_bases_mul_scalars).  Reads the resident records; builds no window table; self is unchanged."""
+        n = self.n - first if n is None else n
+        h = _vp()
+        _l.check(_l.load().ezkl_hip_bases_mul_scalars(self.h, _vp(scalars_ptr), C.c_size_t(first), C.c_size_t(n), C.byref(h)),
+                 "ezkl_hip_bases_mul_scalars")
+        b = type(self).__new__(type(self))
+        b.n, b.h = n, h
+        return b
+
     def download(self):
         out = np.empty((self.n, 8), np.uint64)
         _l.check(_l.load().ezkl_hip_bases_download(self.h, _p(out)), "ezkl_hip_bases_download")
@@ -727,6 +738,119 @@ def check_srs(srs, seed=None, structure=True):
             v.free()
         for b in sets.values():
             b.free()
+
+
+def update_srs(srs, t, stages=None, g=None):
+    """One step of an updatable SRS: multiply a fresh secret t into a parsed file (codecs.read_srs) whose own secret s nobody here knows
+    -> (new_srs, proof).  All on the device:
+      g'[i] = t^i g[i]                  t^i by vec_fill + an exclusive product scan, as gen_srs makes s^i; the per-row product is
+                                        Bases.mul_scalars (ezkl_hip_bases_mul_scalars)
+      g_lagrange'                       rebuilt from g' by the inverse NTT over G1 (Bases.downsize at the file's own k)
+      g2' = g2,  s_g2' = [t] s_g2       ezkl_hip_msm_g2 with n = 1
+    new_srs has the keys of read_srs; proof = dict(t_g2=[t] g2 as the 128 bytes of the file's G2 layout), what verify_srs_update links
+    the two files by.  t is an integer in [1, r) and is in neither return value.  Not detected here: a t with (s t)^n = 1 puts the new
+    secret inside the domain and the Lagrange basis comes out degenerate (one point and n - 1 identities); that cannot be seen without
+    s, and the structural check of verify_srs_update (or check_srs) reports it as the degenerate set it is.
+    stages: a dict to fill with wall seconds per stage, the device drained after each (tools/srs_update_bench.py); None: no extra waits.
+    g: srs["g"] as a base set that is resident already (a loader's, checked under its policy); it is read and stays the caller's."""
+    import time
+    if not isinstance(t, (int, np.integer)) or isinstance(t, bool) or not 1 <= int(t) < _R:
+        raise ValueError("update_srs: the secret must be an integer in [1, r)")
+    t, k = int(t), int(srs["k"])
+    n = 1 << k
+    clock = [time.perf_counter()]
+
+    def lap(name):
+        if stages is not None:
+            synchronize()
+            now = time.perf_counter()
+            stages[name] = now - clock[0]
+            clock[0] = now
+    held, tpow = [], None
+    try:
+        if g is None:
+            g = _Bases(np.ascontiguousarray(srs["g"]))
+            held.append(g)
+        if g.n != n:
+            raise ValueError("update_srs: g has %d points, k = %d" % (g.n, k))
+        lap("upload")
+        tpow = DeviceBuffer(32 * n)
+        vec_fill(tpow.ptr, _to_mont(t), n)
+        prefix_scan("mul", tpow.ptr, tpow.ptr, n, exclusive=True)             # t^i
+        lap("powers")
+        g1 = g.mul_scalars(tpow.ptr)
+        held.append(g1)
+        lap("mul_scalars")
+        same, gl1 = g1.downsize(k)
+        held += [same, gl1]
+        lap("lagrange")
+        tm = _to_mont(t)[None]
+        g2 = np.frombuffer(bytes(srs["g2"]), np.uint64)[None]
+        s_g2 = np.frombuffer(bytes(srs["s_g2"]), np.uint64)[None]
+        new_s_g2, t_g2 = msm_g2(s_g2, tm), msm_g2(g2, tm)
+        lap("g2")
+        new = dict(k=k, g=g1.download(), g_lagrange=gl1.download(), g2=bytes(srs["g2"]), s_g2=new_s_g2.tobytes())
+        lap("download")
+        return new, dict(t_g2=t_g2.tobytes())
+    finally:
+        if tpow is not None:
+            tpow.free()
+        for b in held:
+            b.free()
+
+
+def verify_srs_update(old, new, proof, seed=None):
+    """Is `new` the file `old` updated by the t behind proof["t_g2"] (update_srs)?  Both are parsed files (codecs.read_srs).  -> dict(k,
+    old, new, t_g2, link, ok, reason): old / new are the reports of check_srs (None where it did not run), t_g2 / link True / False /
+    None, reason None or words that begin with the step that failed.  In order:
+      1  k: both files have the same k (decided on the host, before any library is loaded); g2: the same g2; g[0]: g'[0] == g[0];
+      2  old: / new: check_srs with structure=True of either file -- every point, g = powers of the secret of s_g2, g_lagrange its
+         Lagrange basis, no identity;
+      3  t_g2: a canonical point of the twist, of order r, not the identity (what ezkl_prover_srs_pairing_check demands of s_g2);
+      4  link: e(g[1], t_g2) == e(g'[1], g2), i.e. g'[1] = t g[1].
+    With s, s' the secrets that step 2 proves either file to have, step 4 gives s' = t s; step 2 then gives g'[i] = (t s)^i G and
+    s_g2' = t s g2 for every i.  NOT proven: that whoever made `new` knew t (there is no proof of knowledge: t_g2 may have been put
+    together from other parties' points), nor that they discarded it.  A k = 0 file has no g[1] and is refused at step 4."""
+    rep = dict(k=None, old=None, new=None, t_g2=None, link=None, ok=False, reason=None)
+    ko, kn = int(old["k"]), int(new["k"])
+    if ko != kn:
+        rep["reason"] = "k: the old file has k = %d, the new one k = %d" % (ko, kn)
+        return rep
+    rep["k"] = ko
+    if bytes(old["g2"]) != bytes(new["g2"]):
+        rep["reason"] = "g2: the two files differ in g2"
+        return rep
+    if np.asarray(old["g"][0]).tobytes() != np.asarray(new["g"][0]).tobytes():
+        rep["reason"] = "g[0]: the new file's first point is not the old file's"
+        return rep
+    for name, srs in (("old", old), ("new", new)):
+        rep[name] = check_srs(srs, seed=seed)
+        if not rep[name]["ok"]:
+            rep["reason"] = "%s: %s" % (name, rep[name]["reason"])
+            return rep
+    if ko == 0:
+        rep["reason"] = "link: a one-point file has no g[1] to link the secrets by"
+        return rep
+    from . import native as _nv
+    t_g2 = proof["t_g2"]
+    t_g2 = t_g2.tobytes() if isinstance(t_g2, np.ndarray) else bytes(t_g2)
+    if len(t_g2) != 128:
+        rep["t_g2"] = False
+        rep["reason"] = "t_g2: %d bytes, a G2 point of the file is 128" % len(t_g2)
+        return rep
+    try:
+        rep["link"] = _nv.srs_pairing_check(old["g"][1], new["g"][1], old["g2"], t_g2)
+        rep["t_g2"] = True
+    except _nv.SrsOperandError as e:                           # both files passed check_srs: g[1], g'[1] and g2 are points of their groups
+        rep["t_g2"] = False
+        why = str(e)
+        rep["reason"] = "t_g2" + why[len("s_g2"):] if why.startswith("s_g2") else why
+        return rep
+    if not rep["link"]:
+        rep["reason"] = "link: e(g[1], t_g2) != e(g'[1], g2): the new file is not the old one updated by the secret of t_g2"
+    else:
+        rep["ok"] = True
+    return rep
 
 
 _Q = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47

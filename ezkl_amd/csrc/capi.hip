@@ -613,6 +613,30 @@ int ezkl_hip_bases_from_scalars(const void* base_point, const void* scalars_dev,
     *out = reinterpret_cast<ezkl_bases_t>(b);
     return EZKL_OK;
 }
+// out[i] = scalars[i] * in[first + i] (g1_mul_rows in msm.hip): a new set of n points from the records of `in`, never its window tables
+int ezkl_hip_bases_mul_scalars(ezkl_bases_t in, const void* scalars_dev, size_t first, size_t n, ezkl_bases_t* out) {
+    if (!in || !scalars_dev || !out || n == 0) return EZKL_ERR_INVALID;       // (a base set is never empty: ezkl_hip_bases_upload)
+    Bases* src = reinterpret_cast<Bases*>(in);
+    if (first > src->n || n > src->n - first) return EZKL_ERR_INVALID;
+    EZ_CTX(c);
+    Bases* b = new Bases();
+    b->n = n;
+    int rc = EZKL_OK;
+    hipError_t e = hipMalloc(&b->pts, n * 64);
+    if (e != hipSuccess) rc = set_hip_error(e, "ezkl_hip_bases_mul_scalars", __FILE__, __LINE__);
+    if (!rc) rc = g1_mul_rows(c, c->stream, (const char*)src->pts + first * 64, (const fe_t*)scalars_dev, n, b->pts);
+    if (!rc) {
+        e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = set_hip_error(e, "g1_mul_rows", __FILE__, __LINE__);
+    }
+    if (rc) {
+        if (b->pts) (void)hipFree(b->pts);
+        delete b;
+        return rc;
+    }
+    *out = reinterpret_cast<ezkl_bases_t>(b);
+    return EZKL_OK;
+}
 // ParamsKZG::downsize (see g1_to_lagrange in msm.hip): out_g = the first 2^new_k points of g (a device copy), out_g_lagrange = the
 // Lagrange basis of the 2^new_k-point domain = the inverse NTT over G1 of those points
 static fe_t domain_omega(uint32_t k, bool inverse);

@@ -176,6 +176,7 @@ int ubench(Ctx* c, const char* which, double* out);
 void msm_table_drop(const Bases* b);
 int msm_table_prepare(Ctx* c, const Bases* b);
 int g1_mul_fixed(Ctx* c, hipStream_t st, const void* base_host, const fe_t* scalars, size_t n, void* out_dev);
+int g1_mul_rows(Ctx* c, hipStream_t st, const void* pts_dev, const fe_t* scalars, size_t n, void* out_dev);
 int g1_check(Ctx* c, hipStream_t st, const void* pts_dev, size_t first, size_t n, uint64_t out[4]);
 int gen_bases(Ctx* c, hipStream_t st, uint64_t seed, size_t first, size_t n, void* out_dev);
 int g1_to_lagrange(Ctx* c, hipStream_t st, const void* g_dev, uint32_t log_n, fe_t* tw_mont, const fe_t& ninv_mont, void* out_dev);

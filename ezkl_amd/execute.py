@@ -229,6 +229,55 @@ def _srs_bases(points, name):
     return b
 
 
+def _update_secret(secret):
+    """the t of update_srs: None draws 64 bytes of OS entropy, reduced mod r and redrawn if 0; an explicit one must be an integer in [1, r)"""
+    if secret is None:
+        while True:
+            t = int.from_bytes(os.urandom(64), "little") % EL.R
+            if t:
+                return t
+    if isinstance(secret, bool) or not isinstance(secret, (int, np.integer)):
+        raise ValueError("update_srs: the secret must be an integer in [1, r), got %s" % type(secret).__name__)
+    if not 1 <= int(secret) < EL.R:
+        raise ValueError("update_srs: the secret must be an integer in [1, r)")
+    return int(secret)
+
+
+def update_srs(srs_in, srs_out, secret=None):
+    """One step of an updatable SRS: multiply a fresh secret t into the file srs_in -- g'[i] = t^i g[i], g_lagrange' rebuilt from g',
+    s_g2' = [t] s_g2, all on the device (backend.update_srs) -- and write the result to srs_out in the same layout.  Whoever made srs_in
+    knows its secret s; the new file's secret is s t, which nobody knows once one updater has discarded their t.  secret=None draws t
+    from OS entropy; an explicit one must be an integer in [1, r) and is refused (ValueError) before any device work otherwise.  The
+    input is read as every loader reads an SRS file: EZKL_SRS_CHECK applies to it.  -> dict(k, t_g2: [t] g2 as hex, what
+    verify_srs_update needs next to the two files, sha256_in, sha256_out).  t itself is not returned and not written anywhere."""
+    import hashlib
+    t = _update_secret(secret)
+    srs = _read_srs(srs_in, 0)
+    g = _srs_bases(srs["g"], "g")                             # the points the update multiplies, held to the loaders' policy
+    try:
+        new, proof = B.update_srs(srs, t, g=g)
+    finally:
+        g.free()
+    data = codecs.write_srs(new)
+    open(srs_out, "wb").write(data)
+    return dict(k=new["k"], t_g2=proof["t_g2"].hex(), sha256_in=hashlib.sha256(open(srs_in, "rb").read()).hexdigest(),
+                sha256_out=hashlib.sha256(data).hexdigest())
+
+
+def verify_srs_update(old_path, new_path, t_g2):
+    """Is the file new_path the file old_path updated by the secret behind t_g2 (the hex string, or the 128 bytes, update_srs returned)?
+    Both files whole: same k and g2, both pass the structural check of check_srs, t_g2 is a point of G2, and e(g[1], t_g2) ==
+    e(g'[1], g2) (backend.verify_srs_update).  Returns the report; a failure raises SrsError, which carries it, with a message that
+    begins with the step that failed.  It does not prove that the updater knew or discarded their secret."""
+    if isinstance(t_g2, str):
+        t_g2 = bytes.fromhex(t_g2)
+    old, new = (codecs.read_srs(open(p, "rb").read()) for p in (old_path, new_path))
+    report = B.verify_srs_update(old, new, dict(t_g2=t_g2))
+    if not report["ok"]:
+        raise SrsError(report["reason"], report)
+    return report
+
+
 def _downsized(srs, logrows):
     """`params.downsize(logrows)` of an SRS larger than the circuit -> the two resident base sets (g, g_lagrange): the coefficient basis
     is truncated, the Lagrange basis of the smaller domain is rebuilt on the device by an inverse NTT over G1 (ezkl_hip_bases_downsize =

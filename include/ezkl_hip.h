@@ -171,6 +171,15 @@ int ezkl_hip_bases_check(ezkl_bases_t h, size_t first, size_t n, uint64_t out[4]
  * generation for tests (gen_srs -> ParamsKZG::setup, /root/reference/src/pfsys/srs.rs:14-16): g[i] = s^i G,
  * g_lagrange[i] = L_i(s) G */
 int ezkl_hip_bases_from_scalars(const void* base_point, const void* scalars_dev, size_t n, ezkl_bases_t* out_handle);
+/* per-row product: a NEW resident set of n points, out[i] = scalars[i] * in[first + i], for n resident Montgomery scalars laid out as
+ * ezkl_hip_bases_from_scalars takes them (n x 32 B).  The step of an SRS update, g'[i] = t^i g[i] (backend.update_srs).
+ * Output records are canonical affine; the identity -- an identity input, a zero scalar -- is the all-zero record.  first + n beyond the
+ * set: EZKL_ERR_INVALID.  n = 0: EZKL_ERR_INVALID as well, since a base-set handle cannot be empty (ezkl_hip_bases_upload refuses
+ * n = 0 too).  Reads the records the handle holds, never the window tables (and builds none); `in` is unchanged and nothing is kept
+ * across calls.  One kernel, one lane per point, the double-and-add of ezkl_hip_bases_from_scalars with the point in vector registers,
+ * 43.6 ms for 2^20 points on an MI355X, level with that call at the same n;
+ * HIP events around it: ezkl_hip_last_kernel_ms("bases_mul_scalars") (and "bases_from_scalars" for the call above). */
+int ezkl_hip_bases_mul_scalars(ezkl_bases_t in, const void* scalars_dev, size_t first, size_t n, ezkl_bases_t* out_handle);
 /* ParamsKZG::downsize(new_k) -- halo2; called by load_params_prover (/root/reference/src/execute.rs:1739-1750) whenever the SRS file is
  * larger than the circuit, the normal case with a shared kzg22.srs: `g` (at least 2^new_k points of the coefficient basis s^i G) ->
  * out_g = its first 2^new_k points (may be NULL), out_g_lagrange = the Lagrange basis of the 2^new_k-point domain, L_i(s) G, computed as
