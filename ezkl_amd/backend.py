@@ -179,6 +179,30 @@ class _Bases:
         _l.check(_l.load().ezkl_hip_bases_prepare(self.h), "ezkl_hip_bases_prepare")
         return self
 
+    def has_table(self):
+        """does the handle have a window table, built or being built (ezkl_hip_bases_has_table)?"""
+        return bool(_l.load().ezkl_hip_bases_has_table(self.h))
+
+    def msm(self, scalars_ptr, first=0, n=None, stream=None):
+        """sum_i scalars[i] * self[first + i] over n resident Montgomery scalars, fixed-base: builds the window tables at first use"""
+        return msm_g1_dev(self, scalars_ptr, self._count(first, n), first, stream)
+
+    def msm_once(self, scalars, first=0, n=None, stream=None):
+        """the same point WITHOUT window tables (ezkl_hip_msm_g1_once_dev): none is read, built or kept -- for a set that serves a few MSMs
+        and is freed.  `scalars`: a device pointer (or a DeviceBuffer) of n resident Montgomery scalars."""
+        n = self._count(first, n)
+        out = np.zeros(8, np.uint64)
+        _l.check(_l.load().ezkl_hip_msm_g1_once_dev(self.h, C.c_size_t(first), _vp(getattr(scalars, "ptr", scalars)), C.c_size_t(n), _p(out),
+                                                     _stream_ptr(stream)), "ezkl_hip_msm_g1_once_dev")
+        return out
+
+    def _count(self, first, n):
+        first = int(first)
+        n = self.n - first if n is None else int(n)
+        if first < 0 or n < 0 or first + n > self.n:
+            raise ValueError("records [%d, %d) of a set of %d points" % (first, first + n, self.n))
+        return n
+
     def free(self):
         if self.h:
             _l.load().ezkl_hip_bases_free(self.h)
@@ -186,6 +210,25 @@ class _Bases:
 
 
 Bases = _Bases
+
+# Below this many points a set that is used once still builds its tables (0: the table-free path wins at every measured size, 2^16 and 2^20:
+# profiles/r15_msm_once.json, DESIGN.md §4.1 "MSM without window tables").  check_srs, execute.gen_witness and pk_recommit read it.
+MSM_ONCE_MIN_POINTS = 0
+
+
+def msm_used_once(bases, scalars_ptr, n, offset=0):
+    """an MSM on a set that will serve a few MSMs and be freed: table-free from MSM_ONCE_MIN_POINTS points on"""
+    if n and n >= MSM_ONCE_MIN_POINTS:
+        return bases.msm_once(scalars_ptr, offset, n)
+    return msm_g1_dev(bases, scalars_ptr, n, offset)
+
+
+def msm_points(points_dev, scalars_dev, n, stream=None):
+    """sum_i scalars[i] * points[i] over n resident 64-byte affine Montgomery records that are no base set (ezkl_hip_msm_g1_points_dev)"""
+    out = np.zeros(8, np.uint64)
+    _l.check(_l.load().ezkl_hip_msm_g1_points_dev(_vp(getattr(points_dev, "ptr", points_dev)), _vp(getattr(scalars_dev, "ptr", scalars_dev)),
+                                                   C.c_size_t(int(n)), _p(out), _stream_ptr(stream)), "ezkl_hip_msm_g1_points_dev")
+    return out
 
 
 def msm_g1_dev(bases, scalars_ptr, n, offset=0, stream=None):
@@ -386,11 +429,12 @@ class ParamsKZG:
         self._gl.free()
 
 
-def polycommit_commit(message, num_unusable_rows, params):
+def polycommit_commit(message, num_unusable_rows, params, once=False):
     """PolyCommitChip::commit (/root/reference/src/circuit/modules/polycommit.rs:46-81): pad the message into
     ceil-ish(len / (2^k - u)) Lagrange-basis columns (num_poly = len / n + 1 as the reference computes it), leave
     the u unusable rows at Blind::default().0 (= Fr::ONE in halo2, passed here as `blind`), commit each column with
-    commit_lagrange and return the normalised affine points.  The batch goes through the pipelined MSM path."""
+    commit_lagrange and return the normalised affine points.  The batch goes through the pipelined MSM path; once=True: `params` was
+    loaded for these few columns alone (execute.gen_witness), and each is committed without window tables (msm_used_once)."""
     message = _fe(message)
     n_rows = 1 << params.k
     n = n_rows - num_unusable_rows
@@ -400,6 +444,14 @@ def polycommit_commit(message, num_unusable_rows, params):
     for i in range(message.shape[0]):
         polys[i // n, i % n] = message[i]
     out = np.zeros((num_poly, 8), np.uint64)
+    if once:
+        for j in range(num_poly):
+            col = DeviceBuffer.from_numpy(polys[j])
+            try:
+                out[j] = msm_used_once(params._gl, col.ptr, n_rows)
+            finally:
+                col.free()
+        return out
     arr = (C.c_void_p * num_poly)(*[polys[j].ctypes.data for j in range(num_poly)])
     _l.check(_l.load().ezkl_hip_msm_g1_batch(params._gl.h, arr, C.c_size_t(num_poly), C.c_size_t(n_rows), _p(out)),
              "ezkl_hip_msm_g1_batch")
@@ -664,14 +716,15 @@ def srs_check_key(seed=None):
 
 def srs_power_combination(g, key):
     """(A, B) = (sum r_i g[i], sum r_i g[i + 1]) over i < n - 1 for the n - 1 scalars of ChaCha20 stream 0 under `key`: the same resident
-    scalars in two MSMs on the one handle, at base offsets 0 and 1.  A one-point set has no adjacent pair: both are the identity."""
+    scalars in two MSMs on the one handle, at base offsets 0 and 1, without window tables (msm_used_once: the callers, check_srs and
+    verify_srs_update, free the set after these and one more MSM).  A one-point set has no adjacent pair: both are the identity."""
     m = g.n - 1
     if m == 0:
         return np.zeros(8, np.uint64), np.zeros(8, np.uint64)
     r = DeviceBuffer(32 * m)
     try:
         chacha20_fr(key, 0, r.ptr, m)
-        return msm_g1_dev(g, r.ptr, m, 0), msm_g1_dev(g, r.ptr, m, 1)
+        return msm_used_once(g, r.ptr, m, 0), msm_used_once(g, r.ptr, m, 1)
     finally:
         r.free()
 
@@ -721,11 +774,11 @@ def check_srs(srs, seed=None, structure=True):
             return rep
         v = DeviceBuffer(32 * n)
         chacha20_fr(key, 1, v.ptr, n)
-        left = msm_g1_dev(sets["g_lagrange"], v.ptr, n)
+        left = msm_used_once(sets["g_lagrange"], v.ptr, n)
         w = pow(EvaluationDomain.ROOT, 1 << (28 - k), _R)
         if k:                                                  # (the one-point transform is the identity)
             ntt_dev(v.ptr, k, _to_mont(pow(w, -1, _R)), inverse=True)
-        rep["lagrange"] = bool((left == msm_g1_dev(sets["g"], v.ptr, n)).all())
+        rep["lagrange"] = bool((left == msm_used_once(sets["g"], v.ptr, n)).all())
         if not rep["powers"]:
             rep["reason"] = "g: not consecutive powers of one secret"
         elif not rep["lagrange"]:

@@ -706,6 +706,23 @@ int ezkl_hip_msm_g1_dev(ezkl_bases_t h, size_t base_offset, const void* scalars_
     EZ_CTX(c);
     return msm_run(c, pick_stream(c, stream), b, base_offset, (const fe_t*)scalars_dev, n, out);
 }
+// the MSM without window tables (msm_once_run in msm.hip): over a range of a base set's records, or over any resident points
+int ezkl_hip_msm_g1_points_dev(const void* points_dev, const void* scalars_dev, size_t n, void* out, void* stream) {
+    if (!points_dev || !scalars_dev || !out || n == 0 || ((uintptr_t)points_dev & 15)) return EZKL_ERR_INVALID;
+    EZ_CTX(c);
+    return msm_once_run(c, pick_stream(c, stream), points_dev, (const fe_t*)scalars_dev, n, out);
+}
+int ezkl_hip_msm_g1_once_dev(ezkl_bases_t h, size_t base_offset, const void* scalars_dev, size_t n, void* out, void* stream) {
+    if (!h || !out || !scalars_dev || n == 0) return EZKL_ERR_INVALID;
+    Bases* b = reinterpret_cast<Bases*>(h);
+    if (base_offset > b->n || n > b->n - base_offset) return EZKL_ERR_INVALID;
+    return ezkl_hip_msm_g1_points_dev((const char*)b->pts + base_offset * 64, scalars_dev, n, out, stream);
+}
+int ezkl_hip_bases_has_table(ezkl_bases_t h) {
+    if (!h) return 0;
+    EZ_CTX(c);
+    return msm_table_exists(reinterpret_cast<Bases*>(h)) ? 1 : 0;
+}
 // one MSM in two halves (msm_call_start / msm_call_finish): the launches are queued behind the library stream's work so far and the call
 // returns; finish waits for them and writes the point.  In between the caller may issue any other call, batches and upload phases included
 // (the MSM runs on a call slot of its own).  `token` is the slot (0 .. 3).

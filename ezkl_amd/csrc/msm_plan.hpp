@@ -201,4 +201,68 @@ inline MsmPlan msm_plan(size_t n, WinPlan wp, size_t count, int num_cus, int acc
     return p;
 }
 
+// ---- an MSM WITHOUT window tables (msm.hip: msm_once_run) ------------------------------------------------------------------------
+// sum_i s_i P_i = sum_w 2^offset(w) * S_w with S_w = sum_i d_{w,i} P_i: every window is an MSM of its own over the raw points -- the chain
+// above with the points as a one-level "table", the pairs of ONE window, n pairs instead of n * W -- and the windows are the members of fused
+// groups (gridDim.z), because they read the same scalar column.  The host combines the S_w (msm_once_finish).
+// Cost model in point additions: every window has a bucket set of its own, so W * (n + 4 * 2^(cmax-1)), plus what a SEQUENCE OF LAUNCHES
+// costs when W outgrows one fused group: 14 launches and their latency-bound tails, measured at 0.3-0.5 ms (2^14 points: 0.80 ms as 12 + 12
+// windows, 0.49 ms as 16; 2^16: 1.09 ms as 11 + 11, 0.58 ms as 16 -- DESIGN.md §4.1), which is 2^22 additions at the ~7 per ns the path
+// sustains at 2^20 points.  So in practice a plan is 12 .. 16 windows in ONE sequence, and narrower windows than pick_plan's: 2^20 points:
+// W = 16 (14 x 16 + 2 x 15 bits) where the table path has 13 windows of 20 / 19 bits.
+static constexpr size_t MSM_ONCE_CHAIN_COST = (size_t)1 << 22;        // one sequence of launches, in point additions
+static constexpr uint32_t MSM_ONCE_MAX_W = 127;                       // most windows of a plan (two bits each): the landing buffer has a block for each
+static constexpr size_t MSM_ONCE_SCRATCH_CAP =(size_t)4 << 30;       // the slabs of one fused group stay below this (fewer windows per group beyond it)
+inline WinPlan pick_plan_once(size_t n) {
+    WinPlan best{0, 0, 0};
+    double best_cost = 0;
+    for (uint32_t W = 12; W <= MSM_ONCE_MAX_W; W++) {     // 254 bits in windows of at most 23 (msm_recode's bit buffer): at least 12 of them
+        WinPlan p{W, 254 / W, 254 % W};
+        if (p.cmax() > 23) continue;
+        const double groups = (double)((W + MSM_MAX_GROUP - 1) / MSM_MAX_GROUP);
+        const double cost = (double)W * ((double)n + 4.0 * (double)((size_t)1 << (p.cmax() - 1))) + groups * (double)MSM_ONCE_CHAIN_COST;
+        if (!best.W || cost < best_cost) { best = p; best_cost = cost; }
+    }
+    return best;
+}
+// the launch plan of a table-free MSM:
+//   wp             the W windows the scalars are recoded into (pick_plan_once)
+//   chain          ONE window's chain: msm_plan for n pairs (a plan of one window as wide as wp's widest), `group` slabs bstride apart;
+//                  the lanes are sized for the pairs of the whole group, which share the device
+//   group, ngroups windows per sequence of launches (<= MSM_MAX_GROUP; fewer when their slabs would outgrow MSM_ONCE_SCRATCH_CAP) and
+//                  sequences: sequence g serves the windows [g * group, min(W, (g + 1) * group)) and reuses the slabs
+//   o_points       the points in the accumulate kernel's form (R' = 2^261), n x 64 bytes, shared by all windows;  o_slabs: the first slab
+//   bytes          the whole scratch
+struct MsmOncePlan {
+    WinPlan wp;
+    MsmPlan chain;
+    size_t group, ngroups, o_points, o_slabs, bytes;
+};
+inline MsmOncePlan msm_plan_once(size_t n, int num_cus, int acc_blocks_per_cu, const MsmTuning& tu) {
+    MsmOncePlan q{};
+    q.wp = pick_plan_once(n);
+    const WinPlan one{1, q.wp.cmax(), 0};                 // bits = cmax - 1, npairs = n: a narrower window of wp uses the low half of the buckets
+    size_t group = q.wp.W < MSM_MAX_GROUP ? q.wp.W : MSM_MAX_GROUP;
+    for (;;) {
+        q.ngroups = (q.wp.W + group - 1) / group;
+        q.group = group = (q.wp.W + q.ngroups - 1) / q.ngroups;   // balanced: 13 windows under the cap go as 5 + 5 + 3, not 6 + 6 + 1
+        MsmTuning t = tu;
+        if (!t.L_override) {                              // msm_plan's lane rule, for the group's pairs
+            const size_t resident = (size_t)acc_blocks_per_cu * 256 * num_cus, total = n * group;
+            const size_t load = n >> (one.cmax() - 1), per_lane = load * 9 / 10 > 40 ? load * 9 / 10 : 40;
+            size_t rounds = total / (resident * per_lane);
+            if (rounds < 1) rounds = 1;
+            const size_t L = (total + resident * rounds - 1) / (resident * rounds);
+            t.L_override = (uint32_t)(L < 8 ? 8 : L);
+        }
+        q.chain = msm_plan(n, one, group, num_cus, acc_blocks_per_cu, t);
+        if (group == 1 || group * q.chain.slab_bytes <= MSM_ONCE_SCRATCH_CAP) break;
+        group--;                                          // (the lanes, and with them a slab, depend on the group: sized again)
+    }
+    q.o_points = 0;
+    q.o_slabs = (n * 64 + 255) & ~(size_t)255;
+    q.bytes = q.o_slabs + group * q.chain.slab_bytes;
+    return q;
+}
+
 }  // namespace ezkl

@@ -1074,9 +1074,26 @@ static std::unique_ptr<ProvingKey> pk_read_file(ConstraintSystem& cs, const char
 
 // commitments of the fixed / permutation polynomials under another SRS (a key file made with the public SRS, proved here under a
 // test SRS): the resident polynomials are committed again and the digest follows
+// A base set WITHOUT window tables -- `verify` with recommit uploads g for these commitments and frees it -- stays without them: up to
+// this many columns are committed table-free (ezkl_hip_msm_g1_once_dev: 2.4 ms each at 2^20 points, 0.6 ms at 2^16, against a table build
+// of 55 / 6 ms and then 1.25 / 0.4 ms each -- DESIGN.md §4.1 -- so the build pays for itself from ~45 / ~25 columns on; batches of fused
+// fixed-base MSMs bring that down, hence the margin).  A set whose tables exist or are being built (execute.Prover prepares its own g
+// before it reads the key, and proves on it afterwards) uses them.
+static constexpr size_t PK_RECOMMIT_ONCE_MAX_COLUMNS = 16;
 static void pk_recommit(ProvingKey& pk, ezkl_bases_t g) {
     ConstraintSystem& cs = *pk.vk.cs;
     Backend be(cs.k, cs.n, g, nullptr, cs.shard);
+    if (!cs.shard.on() && !ezkl_hip_bases_has_table(g) && pk.fixed_polys.size() + pk.sigma_polys.size() <= PK_RECOMMIT_ONCE_MAX_COLUMNS) {
+        auto once = [&](const std::vector<Col>& hs) {
+            std::vector<G1> out(hs.size());
+            for (size_t i = 0; i < hs.size(); i++) check(ezkl_hip_msm_g1_once_dev(g, 0, hs[i]->ptr(), cs.n, &out[i], nullptr), "ezkl_hip_msm_g1_once_dev");
+            return out;
+        };
+        pk.vk.fixed_commitments = once(pk.fixed_polys);
+        pk.vk.sigma_commitments = once(pk.sigma_polys);
+        pk.vk.digest = vk_digest(pk.vk);
+        return;
+    }
     pk.vk.fixed_commitments = be.commit(pk.fixed_polys);
     pk.vk.sigma_commitments = be.commit(pk.sigma_polys);
     pk.vk.digest = vk_digest(pk.vk);

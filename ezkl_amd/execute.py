@@ -439,7 +439,7 @@ def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None
             try:
                 def commit(vals):
                     msg = np.stack([np.frombuffer(((v % EL.R) * (1 << 256) % EL.R).to_bytes(32, "little"), np.uint64) for v in vals])
-                    pts = B.polycommit_commit(msg, blinding + 1, params)
+                    pts = B.polycommit_commit(msg, blinding + 1, params, once=True)    # the SRS is loaded for these one to three columns
                     out = []
                     for p in pts:
                         xi, yi = (int.from_bytes(p[4 * h:4 * h + 4].tobytes(), "little") * pow(1 << 256, -1, B._Q) % B._Q for h in (0, 1))

@@ -199,6 +199,21 @@ int ezkl_hip_msm_g1(ezkl_bases_t h, const void* scalars, size_t n, void* out_aff
  * The result is written to host memory and the call returns after the stream has drained. */
 int ezkl_hip_msm_g1_dev(ezkl_bases_t h, size_t base_offset, const void* scalars_dev, size_t n,
                         void* out_affine, void* stream);
+/* sum_i scalars[i] * bases[base_offset + i] WITHOUT window tables: none is read, none is built, none is kept -- for a base set that is
+ * uploaded, used for a few MSMs and freed (an SRS under check, a one-shot commit), where the ~55 ms table build of 2^20 points would
+ * outweigh the MSMs.  Every window of the signed-digit recoding is summed by the chain of the fixed-base path over the raw records (W
+ * window sums as fused groups of one sequence of launches, combined on the host: msm.hip, msm_once_run; DESIGN.md §4.1 "MSM without
+ * window tables" has the cost and the measured times).  Results and errors as ezkl_hip_msm_g1_dev: canonical affine, (0,0) for the
+ * identity, returns after the stream has drained; n = 0 and a range that runs past the set are EZKL_ERR_INVALID.  A handle that HAS a
+ * table may be used here as well: the table is ignored.  Scratch is kept between calls (grown on demand, no allocation in steady state).
+ * HIP events around the device work: ezkl_hip_last_kernel_ms("msm_once").  Not for a proving session: on prepared tables an MSM of 2^20
+ * points takes 1.2 ms where this call takes 2.2 (0.6 against 1.5 on witness-like scalars). */
+int ezkl_hip_msm_g1_once_dev(ezkl_bases_t h, size_t base_offset, const void* scalars_dev, size_t n, void* out_affine, void* stream);
+/* the same over n points that are no base set: points_dev = n x 64 B affine Montgomery records, (0,0) = identity, resident (16-byte
+ * aligned; read, never written) -- a verifier's commitments, a random combination of proof points */
+int ezkl_hip_msm_g1_points_dev(const void* points_dev, const void* scalars_dev, size_t n, void* out_affine, void* stream);
+/* 1 if the handle has a window table (built or being built: a fixed-base MSM or ezkl_hip_bases_prepare has run on it), else 0 */
+int ezkl_hip_bases_has_table(ezkl_bases_t h);
 /* batch of `batch` scalar vectors against the same bases (one commit per advice column) */
 int ezkl_hip_msm_g1_batch(ezkl_bases_t h, const void* const* scalars, size_t batch, size_t n, void* out_affine);
 /* One MSM in two halves: start queues it behind what the library stream has been asked to do so far (the scalar column may still be in
