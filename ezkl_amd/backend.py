@@ -1200,6 +1200,10 @@ class WitnessPlan:
         self.n_phases, self.n_challenges = int(ph[0]), int(ph[1])
         self.column_phase = [int(v) for v in col_phase]   # the phase each advice column belongs to
         self.last = None                             # counters of the last run
+        # the records of kind 11 (a static lookup's outputs): header of 20 words and the parameter hash, the parameters, the constants, then 8 words a record
+        head = np.frombuffer(blob, "<u4", 20)
+        kinds = np.frombuffer(blob, "<u4", 8 * int(head[4]), 112 + 8 * int(head[6]) + 32 * int(head[7]))[0::8]
+        self.n_lookup_records, self.last_stats_ms = int((kinds == 11).sum()), None
 
     def alloc_columns(self):
         return [DeviceBuffer(32 << self.k) for _ in range(self.n_advice)]
@@ -1242,6 +1246,23 @@ class WitnessPlan:
         self.last["device_ms"] = last_kernel_ms("witness")
         done = phase is None or phase == self.n_phases - 1
         return cols, [_from_mont_int(outs[i]) for i in range(self.n_outputs)] if done else []
+
+    def lookup_stats(self, columns, stream=None):
+        """(min_lookup_inputs, max_lookup_inputs) of the witness in `columns` -- the columns a `run` of this plan that raised nothing has
+        just written: the least and the greatest signed input of its static lookups, folded with 0 (ezkl_hip_witness_lookup_stats_dev;
+        witness_plan.lookup_stats_host is its specification).  self.last_stats_ms: the kernel's HIP-event time, None when the plan has no
+        static lookup and nothing was launched.  Raises WitnessError when a source is beyond 62 bits."""
+        if len(columns) != self.n_advice or any(c.nbytes < (32 << self.k) for c in columns):
+            raise ValueError("the plan reads %d columns of %d bytes" % (self.n_advice, 32 << self.k))
+        ptrs = (_vp * self.n_advice)(*[c.ptr for c in columns])
+        out = (C.c_int64 * 2)()
+        L = _l.load()
+        rc = L.ezkl_hip_witness_lookup_stats_dev(self.h, ptrs, out, _stream_ptr(stream))
+        if rc == -3:
+            raise WitnessError(L.ezkl_hip_witness_last_error().decode() or "ezkl_hip_witness_lookup_stats_dev: invalid argument")
+        _l.check(rc, "ezkl_hip_witness_lookup_stats_dev")
+        self.last_stats_ms = last_kernel_ms("witness_lookup_stats") if self.n_lookup_records else None
+        return int(out[0]), int(out[1])
 
     def advice_fn(self, inputs, columns):
         """the per-phase witness callback of native.create_proof(..., device_columns=range(n_advice)): (phase, challenges) -> {column:

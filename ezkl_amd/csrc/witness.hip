@@ -66,7 +66,7 @@
 // one (|s| >= 2^52: "rebase dividend outside the exact-division range"): the lane counts itself in status[0] and keeps the SMALLEST
 // (record, element) in status[1] -- vector atomics in plain C++, as the mock prover's kernels in vecops.hip -- and the host call
 // returns EZKL_ERR_INVALID naming the op.  Nothing traps.
-// The only device memory written is the destination columns, the plan's own scratch (inputs, outputs, sort keys, arg-extremum slots, scatter winners or complement flags) and the status words; the plan's
+// The only device memory written is the destination columns, the plan's own scratch (inputs, outputs, sort keys, arg-extremum slots, scatter winners or complement flags, the three words of the lookup statistics) and the status words; the plan's
 // index pool, parameters, constants and lookup-table values are read-only after upload.
 #include "common.hpp"
 #include "witness_plan.hpp"
@@ -437,6 +437,50 @@ __global__ __launch_bounds__(64) void wit_rlc_kernel(WitCols cols, uint32_t k, c
 __global__ __launch_bounds__(64) void wit_gather_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ cells, uint32_t n, fe_t* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) st_fe(out + i, ld_fe(wit_cell(cols, k, cells[i])));
+}
+
+// ezkl_hip_witness_lookup_stats_dev: the least and the greatest signed input of every static lookup of a replayed plan, folded with 0 --
+// what BaseRegion.nonlinearity keeps on the host as min_lookup_inputs / max_lookup_inputs (the reference's src/circuit/ops/region.rs:548-559).
+// recs: (pool offset of the source cells, count) of every TABLE record; one lane per element, the grid striding over each record in
+// turn; the extrema are reduced across the wave in registers and leave it through one signed 64-bit atomicMin and one atomicMax on
+// out[0] / out[1], which the host call has set to 0; a source beyond 62 bits is counted in out[2] instead and the call refuses the result.
+// Every index read here was checked on upload: a TABLE record's sources are cells below n_advice * 2^k.
+struct StatRec {
+    uint32_t a, count;
+};
+constexpr uint32_t STATS_THREADS = 256, STATS_MAX_BLOCKS = 256;             // at most a workgroup per CU: past 2^16 elements the lanes stride
+__global__ __launch_bounds__(STATS_THREADS) void wit_lookup_stats_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ pool, const StatRec* __restrict__ recs,
+                                                                         uint32_t n_recs, long long* __restrict__ out) {
+    const uint64_t first = (uint64_t)blockIdx.x * STATS_THREADS + threadIdx.x, stride = (uint64_t)gridDim.x * STATS_THREADS;
+    int64_t lo = 0, hi = 0;
+    uint32_t bad = 0;
+    for (uint32_t r = 0; r < n_recs; r++) {
+        const StatRec rec = recs[r];
+        const uint32_t* __restrict__ a = pool + rec.a;
+        for (uint64_t i = first; i < rec.count; i += stride) {
+            bool neg, fits;
+            uint64_t mag;
+            wit_signed(ld_fe(wit_cell(cols, k, a[i])), neg, mag, fits);
+            const int64_t s = neg ? -(int64_t)mag : (int64_t)mag;          // |s| < 2^62 where it fits
+            bad += fits ? 0u : 1u;
+            lo = fits && s < lo ? s : lo;
+            hi = fits && s > hi ? s : hi;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+        const uint32_t l0 = (uint32_t)__shfl_xor((int)(uint32_t)lo, off), l1 = (uint32_t)__shfl_xor((int)(uint32_t)((uint64_t)lo >> 32), off);
+        const uint32_t h0 = (uint32_t)__shfl_xor((int)(uint32_t)hi, off), h1 = (uint32_t)__shfl_xor((int)(uint32_t)((uint64_t)hi >> 32), off);
+        const int64_t ylo = (int64_t)((uint64_t)l0 | ((uint64_t)l1 << 32)), yhi = (int64_t)((uint64_t)h0 | ((uint64_t)h1 << 32));
+        lo = ylo < lo ? ylo : lo;
+        hi = yhi > hi ? yhi : hi;
+        bad += (uint32_t)__shfl_xor((int)bad, off);
+    }
+    if ((threadIdx.x & 63) == 0) {                                          // one atomic of each per wave, none where the wave changes nothing
+        if (lo < 0) atomicMin(&out[0], (long long)lo);
+        if (hi > 0) atomicMax(&out[1], (long long)hi);
+        if (bad) atomicAdd(reinterpret_cast<unsigned long long*>(&out[2]), (unsigned long long)bad);
+    }
 }
 
 // ezkl_hip_witness_tile_dev: rows [t * U, (t + 1) * U) of dst[pair] get rows [0, U) of src[pair].  One lane per destination cell, a
@@ -931,6 +975,10 @@ struct DevPlan {
     SortKey* sort_keys = nullptr;   // the padded keys of the largest sort record with segments above SORT_TILE, or the chunk slots of the
                                     // largest arg-extremum record with segments above ARGEXT_CHUNK, or the winner words / the flags and counts of the
                                     // largest scatter / complement record above SCATTER_TILE, whichever is more (one slot when there is none)
+    StatRec* stat_recs = nullptr;   // (source offset, count) of every TABLE record, in all phases: what ezkl_hip_witness_lookup_stats_dev strides over
+    uint32_t n_stat_recs = 0;
+    uint64_t stat_elems = 0;
+    long long* stats = nullptr;     // its result words: least, greatest, sources beyond 62 bits; set per call
     Ctx* ctx = nullptr;
     // a plan with phases: the last phase that ran to its end since the last phase 0 with no earlier phase started again since, and the
     // columns it ran on
@@ -947,7 +995,7 @@ size_t wit_scratch_bytes(const Rec& r) {
 }
 
 void plan_release(DevPlan* p) {
-    for (void* q : {(void*)p->pool, (void*)p->outputs, (void*)p->params, (void*)p->consts, (void*)p->table_values, (void*)p->inputs, (void*)p->outs, (void*)p->status, (void*)p->sort_keys})
+    for (void* q : {(void*)p->pool, (void*)p->outputs, (void*)p->params, (void*)p->consts, (void*)p->table_values, (void*)p->inputs, (void*)p->outs, (void*)p->status, (void*)p->sort_keys, (void*)p->stat_recs, (void*)p->stats})
         if (q) (void)ezkl_hip_free(q);
     delete p;
 }
@@ -1076,12 +1124,20 @@ int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out
     }
     size_t sort_bytes = 0;                                        // the records run one after another on the stream: they share the scratch
     for (const Rec& r : h.recs) sort_bytes = std::max(sort_bytes, wit_scratch_bytes(r));
+    std::vector<StatRec> stat_recs;
+    for (const Rec& r : h.recs)
+        if (r.kind == TABLE) {
+            stat_recs.push_back(StatRec{r.a, r.count});
+            p->stat_elems += r.count;
+        }
+    p->n_stat_recs = (uint32_t)stat_recs.size();
     struct Up { void** dev; const void* src; size_t bytes; };
     const Up ups[] = {{(void**)&p->pool, h.pool.data(), h.pool.size() * 4},       {(void**)&p->outputs, h.outputs.data(), h.outputs.size() * 4},
                       {(void**)&p->params, h.params.data(), h.params.size() * 8}, {(void**)&p->consts, consts.data(), consts.size() * 32},
                       {(void**)&p->inputs, nullptr, (size_t)h.n_inputs * 8},      {(void**)&p->outs, nullptr, h.outputs.size() * 32},
                       {(void**)&p->status, nullptr, 32},                          {(void**)&p->table_values, h.table_values.data(), h.table_values.size() * 8},
-                      {(void**)&p->sort_keys, nullptr, sort_bytes}};
+                      {(void**)&p->sort_keys, nullptr, sort_bytes},               {(void**)&p->stat_recs, stat_recs.data(), stat_recs.size() * sizeof(StatRec)},
+                      {(void**)&p->stats, nullptr, 32}};
     int rc = EZKL_OK;
     for (const Up& u : ups) {
         if ((rc = ezkl_hip_malloc(u.dev, u.bytes ? u.bytes : 1))) break;
@@ -1256,6 +1312,44 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
     p->done_phase = (int)phase;
     if (first) memcpy(p->done_cols, advice_cols_dev, h.n_advice * sizeof(void*));
     t_wit_error.clear();
+    return EZKL_OK;
+}
+
+int ezkl_hip_witness_lookup_stats_dev(ezkl_wplan_t plan, void* const* advice_cols_dev, int64_t out_min_max[2], void* stream) {
+    if (!plan || !advice_cols_dev || !out_min_max) return EZKL_ERR_INVALID;
+    out_min_max[0] = out_min_max[1] = 0;
+    t_wit_error.clear();
+    DevPlan* p = reinterpret_cast<DevPlan*>(plan);
+    const Plan& h = p->host;
+    WitCols cols;
+    for (uint32_t j = 0; j < MAX_ADVICE; j++) cols.p[j] = nullptr;
+    for (uint32_t j = 0; j < h.n_advice; j++) {
+        if (!advice_cols_dev[j]) return EZKL_ERR_INVALID;
+        cols.p[j] = static_cast<fe_t*>(advice_cols_dev[j]);
+    }
+    if (p->n_stat_recs == 0) return EZKL_OK;                       // no static lookup: (0, 0), nothing launched
+    EZ_CTX(c);
+    if (c != p->ctx) return EZKL_ERR_INVALID;
+    hipStream_t st = pick_stream(c, stream);
+    hipEvent_t e0, e1;
+    int rc = ev_pair(c, "witness_lookup_stats", &e0, &e1);
+    if (rc) return rc;
+    const uint64_t blocks = (p->stat_elems + STATS_THREADS - 1) / STATS_THREADS;
+    EZ_HIP(hipEventRecord(e0, st));
+    EZ_HIP(hipMemsetAsync(p->stats, 0, 32, st));
+    hipLaunchKernelGGL(wit_lookup_stats_kernel, dim3((uint32_t)(blocks < STATS_MAX_BLOCKS ? blocks : STATS_MAX_BLOCKS)), dim3(STATS_THREADS), 0, st, cols, h.k,
+                       (const uint32_t*)p->pool, (const StatRec*)p->stat_recs, p->n_stat_recs, p->stats);
+    EZ_HIP(hipGetLastError());
+    EZ_HIP(hipEventRecord(e1, st));
+    long long got[4] = {0, 0, 0, 0};
+    EZ_HIP(hipMemcpyAsync(got, p->stats, 32, hipMemcpyDeviceToHost, st));
+    EZ_HIP(hipStreamSynchronize(st));
+    if (got[2]) {
+        t_wit_error = "witness: " + std::to_string(got[2]) + " lookup inputs beyond 62 bits: the columns are not those of a replay that passed";
+        return EZKL_ERR_INVALID;
+    }
+    out_min_max[0] = got[0];
+    out_min_max[1] = got[1];
     return EZKL_OK;
 }
 

@@ -18,7 +18,18 @@ description of the same family ({"model": "mlp", "run_args": {...}, "weights": [
 "rebase": [d per layer] every Gemm is wrapped in the RebaseScale division ezkl puts around it at non-zero scales (layouts.rs:219-267 `div`):
 the input is then quantized at run_args.input_scale and the outputs are reported at input_scale + sum(param_scale - log2 d), or at
 "output_scale" where a divisor is no power of two.
+Three more families are read as JSON descriptions, chosen by "model" through the table FAMILIES (`describe` writes one from a circuit):
+    {"model": "conv", "run_args": {...}, "image", "kernel", "out_channels", "stride", "classes", "lookup_range": [lo, hi], "denom", ["capacity"],
+     "kernels": [oc][K][K], "conv_bias": [oc], "fc_w": [classes][oc * slides^2], "fc_b": [classes]}                  -> ezkl_layout.ConvMnistCircuit
+    {"model": "pool_classifier", "run_args": {...}, "image", "kernel", "out_channels", "stride", "pool_size", "pool_stride", "classes",
+     "pool": "max" | "sum", "capacity", and the same four arrays}                                                     -> PoolClassifierCircuit
+    {"model": "norm", "run_args": {...}, "rows", "length", "input_scale", "output_scale", "eps", "layer_norm", "lookup_range", "capacity"}   -> NormCircuit
+with run_args = logrows, num_inner_cols, decomp_base, decomp_legs and optionally input_scale / output_scale (the witness file's scales,
+default 0); private input, private parameters and public output only -- any other visibility is refused by name, a malformed field by a
+ValueError that names it.  setup, gen_witness, mock, prove, verify and Prover treat them as they treat the MLP.  The einsum and the
+transformer surrogate (two-phase plans) and the SortTopk / SumProd / ScatterGather circuits have no description: "unsupported compiled circuit".
 Errors surface as exceptions with the reference's wording where it has one."""
+import collections
 import json
 import os
 
@@ -40,39 +51,43 @@ def _read_compiled(path, any_visibility=False):
     raw = open(path, "rb").read()
     if raw[:1] == b"{":
         j = json.loads(raw)
-        if j.get("model") != "mlp":
+        family = FAMILIES.get(j.get("model")) if isinstance(j.get("model"), str) else None
+        if family is None:                                                           # (the einsum and the surrogate among them: two-phase plans have no file-level loader)
             raise ValueError("unsupported compiled circuit: %r" % j.get("model"))
-        ra, weights = j["run_args"], j["weights"]
-        scale = ra.get("input_scale", 0) if not weights else 0                      # a Gemm-free graph keeps its input scale (ezkl's default: 7)
-        in_scale = out_scale = scale
-        rebase = j.get("rebase")
-        if rebase is not None:                                                       # every Gemm wrapped in a RebaseScale: the scales are the run args'
-            rebase = [int(d) for d in rebase]
-            if len(rebase) != len(weights) or any(not 1 <= d < 1 << 32 for d in rebase):
-                raise ValueError("compiled circuit: \"rebase\" takes one divisor in [1, 2^32) per layer")
-            in_scale = ra.get("input_scale", 0)
-            if "output_scale" in j:
-                out_scale = int(j["output_scale"])
-            elif all(d & (d - 1) == 0 for d in rebase) and "param_scale" in ra:       # a layer adds the parameter scale, its rebase takes log2 d off
-                out_scale = in_scale + sum(ra["param_scale"] - (d.bit_length() - 1) for d in rebase)
-            else:
-                raise ValueError("compiled circuit: \"output_scale\" is required where a rebase divisor is not a power of two (or run_args has no param_scale)")
-        return dict(weights=weights, biases=j["biases"], relu_last=j.get("relu_last", True), relu_first=j.get("relu_first", False), rebase=rebase,
-                    n_inputs=j.get("n_inputs", len(weights[0][0]) if weights else None), run_args=ra, settings=None,
-                    total_assignments=j.get("total_assignments"), in_scale=in_scale, out_scale=out_scale, datum_type="F32", input_decomp=True,
-                    visibility=dict(input=ra.get("input_visibility", "Private"), params=ra.get("param_visibility", "Private"),
-                                    output=ra.get("output_visibility", "Public"))), j
+        return dict(family.describe(j), family=j["model"]), j
     c = codecs.read_compiled_circuit(raw)
     weights, biases, relu_last, relu_first, n_inputs = _mlp_of_graph(c["model"], any_visibility)
     st, in_op = c["settings"], c["model"]["nodes"][c["model"]["inputs"][0]]["opkind"]
     return dict(weights=weights, biases=biases, relu_last=relu_last, relu_first=relu_first, rebase=None, n_inputs=n_inputs, run_args=st["run_args"], settings=st,
                 total_assignments=st["total_assignments"], in_scale=st["model_input_scales"][0], out_scale=st["model_output_scales"][0],
-                datum_type=in_op.get("datum_type", "F32"), input_decomp=in_op.get("decomp", True), visibility=c["model"]["visibility"]), c
+                datum_type=in_op.get("datum_type", "F32"), input_decomp=in_op.get("decomp", True), visibility=c["model"]["visibility"], family="mlp"), c
 
 
-def _load_circuit(path):
-    """the compiled circuit (_read_compiled) as an MlpCircuit -> (circuit, the parsed file)"""
-    d, parsed = _read_compiled(path)
+def _describe_mlp(j):
+    """{"model": "mlp", ...} as plain data (the module's text has the fields)"""
+    ra, weights = j["run_args"], j["weights"]
+    scale = ra.get("input_scale", 0) if not weights else 0                      # a Gemm-free graph keeps its input scale (ezkl's default: 7)
+    in_scale = out_scale = scale
+    rebase = j.get("rebase")
+    if rebase is not None:                                                       # every Gemm wrapped in a RebaseScale: the scales are the run args'
+        rebase = [int(d) for d in rebase]
+        if len(rebase) != len(weights) or any(not 1 <= d < 1 << 32 for d in rebase):
+            raise ValueError("compiled circuit: \"rebase\" takes one divisor in [1, 2^32) per layer")
+        in_scale = ra.get("input_scale", 0)
+        if "output_scale" in j:
+            out_scale = int(j["output_scale"])
+        elif all(d & (d - 1) == 0 for d in rebase) and "param_scale" in ra:       # a layer adds the parameter scale, its rebase takes log2 d off
+            out_scale = in_scale + sum(ra["param_scale"] - (d.bit_length() - 1) for d in rebase)
+        else:
+            raise ValueError("compiled circuit: \"output_scale\" is required where a rebase divisor is not a power of two (or run_args has no param_scale)")
+    return dict(weights=weights, biases=j["biases"], relu_last=j.get("relu_last", True), relu_first=j.get("relu_first", False), rebase=rebase,
+                n_inputs=j.get("n_inputs", len(weights[0][0]) if weights else None), run_args=ra, settings=None,
+                total_assignments=j.get("total_assignments"), in_scale=in_scale, out_scale=out_scale, datum_type="F32", input_decomp=True,
+                visibility=dict(input=ra.get("input_visibility", "Private"), params=ra.get("param_visibility", "Private"),
+                                output=ra.get("output_visibility", "Public")))
+
+
+def _build_mlp(d):
     st, ra = d["settings"], d["run_args"]
     if st is not None:
         want = [(-1, 1), (0, ra["decomp_base"] - 1)]
@@ -81,7 +96,212 @@ def _load_circuit(path):
             raise ValueError("unsupported compiled circuit: its settings ask for arguments outside the MLP family")
     return EL.MlpCircuit(ra["logrows"], ra["num_inner_cols"], d["weights"], d["biases"], ra["decomp_base"], ra["decomp_legs"],
                          total_assignments=d["total_assignments"], relu_last=d["relu_last"], n_inputs=d["n_inputs"], relu_first=d["relu_first"],
-                         rebase=d["rebase"]), parsed
+                         rebase=d["rebase"])
+
+
+_REQUIRED = object()
+_PARAMETER_ARRAYS = ("kernels", "conv_bias", "fc_w", "fc_b")
+
+
+def _int_field(j, name, least=None, default=_REQUIRED, prefix=""):
+    """the integer field `name` of a JSON description, at least `least`; a missing, non-integer or smaller one is a ValueError naming it"""
+    v = j.get(name, default)
+    if v is _REQUIRED:
+        raise ValueError("compiled circuit: \"%s%s\" is missing" % (prefix, name))
+    if isinstance(v, bool) or not isinstance(v, int) or (least is not None and v < least):
+        raise ValueError("compiled circuit: \"%s%s\" must be an integer%s" % (prefix, name, "" if least is None else " >= %d" % least))
+    return v
+
+
+def _range_field(j, name):
+    v = j.get(name)
+    if not isinstance(v, (list, tuple)) or len(v) != 2 or any(isinstance(x, bool) or not isinstance(x, int) for x in v) or v[0] > v[1]:
+        raise ValueError("compiled circuit: \"%s\" must be [lo, hi], two integers with lo <= hi" % name)
+    return (v[0], v[1])
+
+
+def _describe_layout(j, fields, n_inputs):
+    """what the conv, pool_classifier and norm descriptions share: run_args (logrows, num_inner_cols, decomp_base, decomp_legs; input_scale
+    and output_scale are the witness file's scales, default 0), private input, private parameters and a public output -- any other
+    visibility is refused by name --, and the family's own fields, each read by its reader; n_inputs(fields): the length of the input vector.
+    -> plain data; "fields": the circuit's arguments"""
+    ra = j.get("run_args")
+    if not isinstance(ra, dict):
+        raise ValueError("compiled circuit: \"run_args\" must be an object")
+    for what, key, want in (("input", "input_visibility", "Private"), ("params", "param_visibility", "Private"), ("output", "output_visibility", "Public")):
+        v = ra.get(key, want)
+        if v != want:
+            named = v if isinstance(v, str) else next(iter(v), "?") if isinstance(v, dict) else repr(v)
+            raise ValueError("unsupported visibility: %s is %s (the %s family takes a private input, private parameters and a public output)"
+                             % (what, named, j["model"]))
+    run = {name: _int_field(ra, name, least, prefix="run_args.") for name, least in (("logrows", 1), ("num_inner_cols", 1), ("decomp_base", 2), ("decomp_legs", 1))}
+    in_scale, out_scale = (_int_field(ra, name, default=0, prefix="run_args.") for name in ("input_scale", "output_scale"))
+    f = {name: read(j, name) for name, read in fields}
+    return dict(run_args=dict(ra, **run), settings=None, in_scale=in_scale, out_scale=out_scale, datum_type="F32", n_inputs=n_inputs(f),
+                visibility=dict(input="Private", params="Private", output="Public"), fields=f)
+
+
+def _parameter_field(j, name):
+    if name not in j:
+        raise ValueError("compiled circuit: \"%s\" is missing" % name)
+    return j[name]                                                               # its shape and entries: the circuit's constructor (ValueError naming the array)
+
+
+def _optional(read):
+    return lambda j, name: read(j, name) if j.get(name) is not None else None
+
+
+def _choice_field(*choices):
+    def read(j, name):
+        if j.get(name) not in choices:
+            raise ValueError("compiled circuit: \"%s\" must be one of %s" % (name, ", ".join("\"%s\"" % c for c in choices)))
+        return j[name]
+    return read
+
+
+def _eps_field(j, name):
+    v = j.get(name)
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not v > 0:
+        raise ValueError("compiled circuit: \"%s\" must be a positive number" % name)
+    return float(v)
+
+
+def _bool_field(j, name):
+    if not isinstance(j.get(name), bool):
+        raise ValueError("compiled circuit: \"%s\" must be true or false" % name)
+    return j[name]
+
+
+_positive = lambda j, name: _int_field(j, name, 1)
+_PARAMETERS = [(name, _parameter_field) for name in _PARAMETER_ARRAYS]
+_CONV_FIELDS = [(name, _positive) for name in ("image", "kernel", "out_channels", "stride", "classes", "denom")] + \
+               [("lookup_range", _range_field), ("capacity", _optional(_positive))] + _PARAMETERS
+_POOL_FIELDS = [(name, _positive) for name in ("image", "kernel", "out_channels", "stride", "pool_size", "pool_stride", "classes", "capacity")] + \
+               [("pool", _choice_field("max", "sum"))] + _PARAMETERS
+_NORM_FIELDS = [(name, _positive) for name in ("rows", "length", "input_scale", "output_scale", "capacity")] + \
+               [("eps", _eps_field), ("layer_norm", _bool_field), ("lookup_range", _range_field)]
+
+
+def _configured(model, make):
+    """the circuit, or a ValueError: what the configuration itself refuses (a geometry that does not fit, a kernel larger than its image)
+    is refused as a field is"""
+    try:
+        return make()
+    except (AssertionError, ZeroDivisionError, IndexError) as e:
+        raise ValueError("compiled circuit: the \"%s\" description cannot be configured: %s" % (model, e or type(e).__name__)) from None
+
+
+def _build_conv(d):
+    ra, f = d["run_args"], d["fields"]
+    if f["kernel"] > f["image"]:
+        raise ValueError("compiled circuit: \"kernel\" is larger than \"image\"")
+    return _configured("conv", lambda: EL.ConvMnistCircuit(
+        ra["logrows"], f["image"], f["kernel"], f["out_channels"], f["stride"], f["classes"], f["lookup_range"], f["denom"], ra["decomp_base"],
+        ra["decomp_legs"], num_inner_cols=ra["num_inner_cols"], capacity=f["capacity"], **{name: f[name] for name in _PARAMETER_ARRAYS}))
+
+
+def _build_pool(d):
+    ra, f = d["run_args"], d["fields"]
+    if f["kernel"] > f["image"]:
+        raise ValueError("compiled circuit: \"kernel\" is larger than \"image\"")
+    if f["pool_size"] > (f["image"] - f["kernel"]) // f["stride"] + 1:
+        raise ValueError("compiled circuit: \"pool_size\" is larger than the convolution's output")
+    return _configured("pool_classifier", lambda: EL.PoolClassifierCircuit(
+        ra["logrows"], ra["num_inner_cols"], f["capacity"], f["image"], f["kernel"], f["out_channels"], f["stride"], f["pool_size"], f["pool_stride"],
+        f["classes"], f["pool"], ra["decomp_base"], ra["decomp_legs"], **{name: f[name] for name in _PARAMETER_ARRAYS}))
+
+
+def _build_norm(d):
+    ra, f = d["run_args"], d["fields"]
+    return _configured("norm", lambda: EL.NormCircuit(
+        ra["logrows"], ra["num_inner_cols"], f["capacity"], f["rows"], f["length"], f["input_scale"], f["output_scale"], f["eps"], f["layer_norm"],
+        ra["decomp_base"], ra["decomp_legs"], f["lookup_range"]))
+
+
+def _forward_layout(d, x):
+    """gen_witness on the host for a circuit that states its `layout`: its own synthesis, the outputs it ties to the instance column and
+    the statistics the layout kept.  What the layout asserts of a witness (a lookup input outside its table, a value beyond the
+    decomposition range) is a ValueError with the layout's words."""
+    circuit = FAMILIES[d["family"]].build(d)
+    try:
+        reg = circuit.synthesize(x, witness=True)
+    except AssertionError as e:
+        raise ValueError(str(e) or "the layout refused the input") from None
+    return [EL.signed(v) for v in circuit.outputs], (reg.min_lookup_inputs, reg.max_lookup_inputs), _max_range_size(circuit)
+
+
+def _max_range_size(circuit):
+    """the largest hi - lo of the circuit's range checks (GraphWitness max_range_size)"""
+    return max((hi - lo for lo, hi in circuit.gc.settings.required_range_checks), default=0)
+
+
+def _forward_mlp(d, x):
+    """gen_witness on the host for the MLP family: the integer arithmetic of its ops in Python lists, with the range checks the layout
+    would make.  -> (outputs, (0, 0): no lookups, max_range_size)"""
+    weights, biases, relu_last, relu_first = d["weights"], d["biases"], d["relu_last"], d["relu_first"]
+    base, legs = d["run_args"]["decomp_base"], d["run_args"]["decomp_legs"]
+    limit = base ** legs
+    ranged = False
+    def decomposed(vals, where):
+        nonlocal ranged
+        ranged = True
+        for v in vals:
+            if abs(v) >= limit:
+                raise ValueError("%s: %d exceeds the decomposition range (-%d^%d, %d^%d)" % (where, v, base, legs, base, legs))
+    if d["input_decomp"]:
+        decomposed(x, "input")
+    if relu_first:
+        decomposed(x, "LeakyReLU input")
+        x = [v if v > 0 else 0 for v in x]
+    rebase = d["rebase"] or [1] * len(weights)
+    for li, (W, bvec) in enumerate(zip(weights, biases)):
+        x = [sum(a * w for a, w in zip(x, row)) for row in W]
+        if rebase[li] != 1:                              # RebaseScale around the Gemm: `div` claims the rounded quotient and decomposes it
+            if any(abs(v) >= 1 << 52 for v in x):
+                raise ValueError("layer %d: %s" % (li, EL.DIV_ERROR))
+            x = [EL.round_div(v, rebase[li]) for v in x]
+            decomposed(x + [rebase[li]], "rebase quotient of layer %d" % li)        # (the divisor: d - |remainder| is decomposed too)
+        x = [v + bvec[o] for o, v in enumerate(x)]
+        if li + 1 < len(weights) or relu_last:
+            decomposed(x, "LeakyReLU input of layer %d" % li)
+            x = [v if v > 0 else 0 for v in x]
+    decomposed(x, "output")                              # `output` range-checks the outputs and the instance cells (layouts.rs:6740-6779)
+    return x, (0, 0), (base - 1) if ranged else 0
+
+
+# THE families a JSON description may name: how its fields are read, how the circuit is built from them, and gen_witness's forward pass on
+# the host.  (The reference's own model.compiled is the MLP family's.)  The einsum and the transformer surrogate -- two-phase plans -- and
+# the SortTopk, SumProd and ScatterGather circuits are not here: naming one is "unsupported compiled circuit".
+Family = collections.namedtuple("Family", "describe build forward")
+FAMILIES = {
+    "mlp": Family(_describe_mlp, _build_mlp, _forward_mlp),
+    "conv": Family(lambda j: _describe_layout(j, _CONV_FIELDS, lambda f: f["image"] ** 2), _build_conv, _forward_layout),
+    "pool_classifier": Family(lambda j: _describe_layout(j, _POOL_FIELDS, lambda f: f["image"] ** 2), _build_pool, _forward_layout),
+    "norm": Family(lambda j: _describe_layout(j, _NORM_FIELDS, lambda f: f["rows"] * f["length"]), _build_norm, _forward_layout),
+}
+
+
+def describe(circuit, input_scale=0, output_scale=0):
+    """the JSON description (a dict) of a ConvMnistCircuit, a PoolClassifierCircuit or a NormCircuit: what `_load_circuit` builds the same
+    circuit from -- same plan_identity, same settings"""
+    ra = dict(logrows=circuit.k, num_inner_cols=circuit.w, decomp_base=circuit.base, decomp_legs=circuit.legs, input_scale=input_scale, output_scale=output_scale)
+    params = lambda: {name: np.asarray(getattr(circuit, name)).tolist() for name in _PARAMETER_ARRAYS}
+    if type(circuit) is EL.ConvMnistCircuit:
+        return dict(model="conv", run_args=ra, image=circuit.image, kernel=circuit.kernel, out_channels=circuit.oc, stride=circuit.stride, classes=circuit.classes,
+                    lookup_range=list(circuit.lookup_range), denom=circuit.denom, capacity=circuit.capacity, **params())
+    if type(circuit) is EL.PoolClassifierCircuit:
+        return dict(model="pool_classifier", run_args=ra, image=circuit.image, kernel=circuit.kernel, out_channels=circuit.oc, stride=circuit.stride,
+                    pool_size=circuit.pool_size, pool_stride=circuit.pool_stride, classes=circuit.classes, pool=circuit.pool, capacity=circuit.capacity, **params())
+    if type(circuit) is EL.NormCircuit:
+        return dict(model="norm", run_args=ra, rows=circuit.rows, length=circuit.length, input_scale=circuit.input_scale, output_scale=circuit.output_scale,
+                    eps=circuit.eps, layer_norm=circuit.layer_norm, lookup_range=list(circuit.lookup_range), capacity=circuit.capacity)
+    raise ValueError("no JSON description for a %s" % type(circuit).__name__)
+
+
+def _load_circuit(path):
+    """the compiled circuit (_read_compiled) as the circuit of its family (FAMILIES) -> (circuit, the parsed file)"""
+    d, parsed = _read_compiled(path)
+    return FAMILIES[d["family"]].build(d), parsed
 
 
 def _mlp_of_graph(model, any_visibility=False):
@@ -363,66 +583,71 @@ def _quantize(v, scale, datum_type):
     return _rust_round(mult * x)
 
 
-def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None):
+def _forward_device(d, x, mode, pk_path):
+    """gen_witness's forward pass on the device, for every family: the circuit's witness plan -- the `.wplan` next to pk_path where one is
+    given and is this circuit's, else a fresh recording -- uploaded and replayed, the outputs read back, the lookup statistics by
+    ezkl_hip_witness_lookup_stats_dev over the replayed cells.  -> (outputs, (min, max), max_range_size), or None when mode is "auto" and
+    the device path is not to be taken (_open_plan, or an input that does not fit int64); mode "device" raises instead.  A witness the
+    device refuses raises backend.WitnessError, a ValueError with the layout's words."""
+    if not _fits_plan(x, mode):
+        return None
+    circuit = FAMILIES[d["family"]].build(d)
+    dev = _open_plan(circuit, pk_path, mode)
+    if dev is None:
+        return None
+    cols = None
+    try:
+        cols, outs = dev.run(x)
+        stats = dev.lookup_stats(cols)
+    finally:
+        for c in cols or []:
+            c.free()
+        dev.free()
+    return [EL.signed(v) for v in outs], stats, _max_range_size(circuit)
+
+
+def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None, synthesis="host", pk_path=None):
     """`ezkl gen-witness` (/root/reference/src/execute.rs:577-660 -> GraphCircuit::forward, src/graph/mod.rs:1734-1849; Python binding
     src/bindings/python.rs:914-941): the compiled circuit + the input data (GraphData JSON: a path, a JSON string or a dict with
     "input_data") -> the GraphWitness, written to `output` as the reference's witness.json and returned as a dict.
 
     * inputs are quantized as load_graph_input does (datum-type round trip, times 2^scale, half away from zero);
-    * the forward pass is the integer arithmetic of the op family this package lays out (_mlp_of_graph: Einsum "mk,nk->mn", Add,
-      LeakyReLU slope 0 at scale 0; a JSON description with "rebase" divides every Gemm's output by its layer's divisor, rounded half away
-      from zero as the circuit's `div` claims it -- ezkl_layout.round_div -- and reports the outputs at the rebased scale) with the range checks the layout would make: a value outside (-base^legs, base^legs) where the
-      circuit decomposes it is the reference's decomposition error, here a ValueError; max_range_size = decomp_base - 1;
-    * KZGCommit visibility of the input / parameters / output ("polycommit"): PolyCommitChip::commit on the GPU (backend.polycommit_commit:
+    * synthesis="host" (the default): the forward pass of the circuit's family (FAMILIES).  The MLP family's is the integer arithmetic of
+      its ops (_mlp_of_graph: Einsum "mk,nk->mn", Add, LeakyReLU slope 0 at scale 0; a JSON description with "rebase" divides every Gemm's
+      output by its layer's divisor, rounded half away from zero as the circuit's `div` claims it -- ezkl_layout.round_div -- and reports the
+      outputs at the rebased scale) with the range checks the layout would make: a value outside (-base^legs, base^legs) where the
+      circuit decomposes it is the reference's decomposition error, here a ValueError; max_range_size = decomp_base - 1.  The conv,
+      pool_classifier and norm families run their circuit's own `synthesize`: the outputs are what it ties to the instance column,
+      min_lookup_inputs / max_lookup_inputs what BaseRegion.nonlinearity kept of the signed inputs to every static lookup (both from 0, as
+      region.rs:548-559 / graph/mod.rs:166-167), max_range_size the largest hi - lo of the circuit's range checks; a lookup input outside
+      its table is a ValueError;
+    * synthesis="device": the circuit's witness plan replayed on the GPU (the `.wplan` setup wrote next to pk_path, where pk_path is given,
+      else a fresh recording), the statistics by the lookup-statistics kernel; raises where that cannot be done.  "auto": the device when
+      the GPU gate is open and a device is there, else the host -- the rules of `prove`.  The witness.json bytes are the same either way;
+    * KZGCommit visibility of the input / parameters / output ("polycommit", the MLP family only): PolyCommitChip::commit on the GPU (backend.polycommit_commit:
       one commit_lagrange MSM per column of 2^k - (blinding factors + 1) values) -- needs srs_path, and like the reference a vk to know the
       blinding factors (here: any file at vk_path; the count is read off the constraint system);  without an SRS the processed value stays
-      None, as in the reference ("SRS for poly commit does not exist (will be ignored)").  Hashed (Poseidon) visibility is refused.
-    The statistics fields are what the reference's dummy layout reports for this family: no lookups (0, 0), max_range_size."""
+      None, as in the reference ("SRS for poly commit does not exist (will be ignored)").  Hashed (Poseidon) visibility is refused."""
+    if synthesis not in ("auto", "host", "device"):
+        raise ValueError("synthesis must be \"auto\", \"host\" or \"device\"")
     d, _ = _read_compiled(compiled_circuit, any_visibility=True)
-    weights, biases, relu_last, relu_first, n_inputs = d["weights"], d["biases"], d["relu_last"], d["relu_first"], d["n_inputs"]
     ra, vis, in_scale, out_scale = d["run_args"], d["visibility"], d["in_scale"], d["out_scale"]
-    datum_type, input_decomp = d["datum_type"], d["input_decomp"]
     for what, v in vis.items():
         if isinstance(v, dict):
             raise ValueError("unsupported visibility: %s is Hashed (Poseidon modules are outside this package's scope)" % what)
-    base, legs = ra["decomp_base"], ra["decomp_legs"]
     if isinstance(data, (bytes, str)) and os.path.exists(data):
         data = open(data).read()
     if isinstance(data, (bytes, str)):
         data = json.loads(data)
     cols = data["input_data"]
-    if len(cols) != 1 or len(cols[0]) != n_inputs:
+    if len(cols) != 1 or len(cols[0]) != d["n_inputs"]:
         raise ValueError("input data does not match the circuit's input shape")
-    x = [_quantize(v, in_scale, datum_type) for v in cols[0]]
+    x = [_quantize(v, in_scale, d["datum_type"]) for v in cols[0]]
     x = [EL.signed(v % EL.R) for v in x]
-    limit = base ** legs
-    ranged = False
-    def decomposed(vals, where):
-        nonlocal ranged
-        ranged = True
-        for v in vals:
-            if abs(v) >= limit:
-                raise ValueError("%s: %d exceeds the decomposition range (-%d^%d, %d^%d)" % (where, v, base, legs, base, legs))
     inputs = list(x)
-    if input_decomp:
-        decomposed(x, "input")
-    if relu_first:
-        decomposed(x, "LeakyReLU input")
-        x = [v if v > 0 else 0 for v in x]
-    rebase = d["rebase"] or [1] * len(weights)
-    for li, (W, bvec) in enumerate(zip(weights, biases)):
-        x = [sum(a * w for a, w in zip(x, row)) for row in W]
-        if rebase[li] != 1:                              # RebaseScale around the Gemm: `div` claims the rounded quotient and decomposes it
-            if any(abs(v) >= 1 << 52 for v in x):
-                raise ValueError("layer %d: %s" % (li, EL.DIV_ERROR))
-            x = [EL.round_div(v, rebase[li]) for v in x]
-            decomposed(x + [rebase[li]], "rebase quotient of layer %d" % li)        # (the divisor: d - |remainder| is decomposed too)
-        x = [v + bvec[o] for o, v in enumerate(x)]
-        if li + 1 < len(weights) or relu_last:
-            decomposed(x, "LeakyReLU input of layer %d" % li)
-            x = [v if v > 0 else 0 for v in x]
-    outputs = x
-    decomposed(outputs, "output")                        # `output` range-checks the outputs and the instance cells (layouts.rs:6740-6779)
+    made = _forward_device(d, x, synthesis, pk_path) if synthesis != "host" else None
+    outputs, (min_lookup, max_lookup), max_range_size = made if made is not None else FAMILIES[d["family"]].forward(d, x)
+    weights, biases = d.get("weights"), d.get("biases")                         # (what a KZGCommit of the parameters commits to: the MLP family's)
     processed = dict(input=None, params=None, output=None)
     if any(v == "KZGCommit" for v in vis.values()):
         have_srs = srs_path is not None and os.path.exists(srs_path)
@@ -455,15 +680,18 @@ def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None
                 if v == "KZGCommit": processed[what] = {"poseidon_hash": None, "polycommit": None}
     text = codecs.write_witness_json([[v % EL.R for v in inputs]], [[v % EL.R for v in outputs]], [in_scale], [out_scale],
                                      processed_inputs=processed["input"], processed_params=processed["params"], processed_outputs=processed["output"],
-                                     max_lookup_inputs=0, min_lookup_inputs=0, max_range_size=(base - 1) if ranged else 0)
+                                     max_lookup_inputs=max_lookup, min_lookup_inputs=min_lookup, max_range_size=max_range_size)
     if output is not None:
         open(output, "w").write(text)
     return json.loads(text)
 
 
 def _plan_for(circuit, pk_path):
-    """the witness plan setup wrote next to the key, if it is THIS circuit's (geometry and parameter hash); otherwise a fresh recording"""
+    """the witness plan setup wrote next to the key, if it is THIS circuit's (geometry and parameter hash); otherwise -- or without a key
+    path -- a fresh recording"""
     try:
+        if pk_path is None:
+            raise OSError("no key path")
         blob = open(pk_path + ".wplan", "rb").read()
         h = WP.peek(blob)
         if (h["k"], h["n_advice"], h["n_inputs"], h["param_hash"]) == (circuit.k, len(circuit.gc.cs.advice), circuit.n_inputs, WP.params_hash(circuit)):

@@ -413,6 +413,9 @@ class BaseRegion(Region):
         self.decomp = None                             # RegionCtx's (base, legs), region.rs `base()` / `legs()`: set by the circuit's layout
         self.shuffle_index = 0                         # region.shuffle_index(): the constant that keeps the sorts of a region apart in the argument
         self.dynamic_lookup_index = 0                  # region.dynamic_lookup_index(): the same for the `select`s of a region
+        # region.rs:548-559 `update_max_min_lookup_inputs`: the running extrema of the signed inputs to every static lookup, both from 0
+        # (graph/mod.rs:166-167) -- a witness file's min_lookup_inputs / max_lookup_inputs
+        self.min_lookup_inputs = self.max_lookup_inputs = 0
 
     def cell_of(self, var, linear):
         x, y, z = var.cartesian_coord(linear)
@@ -691,6 +694,7 @@ class BaseRegion(Region):
         signed = lambda v: v if v < R // 2 else v - R
         for v in w:
             assert table.range[0] <= signed(v.v) <= table.range[1], "lookup input %d outside the table range" % signed(v.v)
+        self.lookup_inputs_seen([signed(v.v) for v in w])
         out = self.assign(self.output, [Val(table.f(signed(v.v)) % R) for v in w])
         self.assign(self.inputs[1], [Val((signed(v.v) - table.range[0]) // table.col_size) for v in w])
         for t in range(len(w)):
@@ -698,6 +702,11 @@ class BaseRegion(Region):
             self.enable(self.base.static_selectors[(name, x, y)], z)
         self.increment(len(w))
         return out
+
+    def lookup_inputs_seen(self, signed_inputs):
+        """the statistics of `nonlinearity` (a recording region, whose values are symbols, keeps none)"""
+        self.min_lookup_inputs = min(self.min_lookup_inputs, *signed_inputs)
+        self.max_lookup_inputs = max(self.max_lookup_inputs, *signed_inputs)
 
     def _lookup_any(self, table_sel, input_sels, table_rows, picks, constrained=False):
         """the two sides of a lookup_any argument of BaseConfig::_configure_any (chip.rs:619-833): `table_rows` (3-tuples) go to the three
@@ -1303,6 +1312,25 @@ class MlpCircuit(LayoutCircuit):
         return reg
 
 
+def _given_parameters(circuit, **arrays):
+    """the parameter arrays a caller hands a circuit in place of its seeded ones (None: keep the seeded one): int64 integers in the shape
+    the seeded array has; anything else is a ValueError that names the array"""
+    for name, given in arrays.items():
+        if given is None:
+            continue
+        want = getattr(circuit, name).shape
+        try:
+            a = np.array(given, dtype=object)
+        except ValueError:
+            a = None
+        if a is None or a.shape != want:
+            raise ValueError("%s: the circuit takes an array of shape %s" % (name, list(want)))
+        flat = a.reshape(-1).tolist()
+        if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -(1 << 63) <= int(v) < 1 << 63 for v in flat):
+            raise ValueError("%s: every entry is an integer that fits int64" % name)
+        setattr(circuit, name, np.array([int(v) for v in flat], np.int64).reshape(want))
+
+
 class ConvMnistConfig(EC.GraphConfig):
     """the Config of /root/reference/examples/conv2d_mnist/main.rs:148-186, in its order: three one-column advice VarTensors (input,
     params, output), the constant columns, BaseConfig over them, range checks (-1, 1) and (0, base - 1) (RegionCtx's decomposition:
@@ -1335,19 +1363,28 @@ class ConvMnistCircuit(LayoutCircuit):
     matter to the prover, the data is synthetic."""
 
     def __init__(self, logrows=17, image=28, kernel=5, out_channels=4, stride=2, classes=10, lookup_range=(-32768, 32768), denom=32,
-                 decomp_base=1024, decomp_legs=2, seed=0, num_inner_cols=1, capacity=None):
+                 decomp_base=1024, decomp_legs=2, seed=0, num_inner_cols=1, capacity=None, kernels=None, conv_bias=None, fc_w=None, fc_b=None):
+        """kernels [oc][K][K], conv_bias [oc], fc_w [classes][oc * slides^2], fc_b [classes]: the parameters as integers (a shape that
+        does not fit is a ValueError naming the array); an array that is absent keeps its seeded synthetic values"""
         self.k, self.w = logrows, num_inner_cols
         self.image, self.kernel, self.oc, self.stride, self.classes = image, kernel, out_channels, stride, classes
         self.slides = (image - kernel) // stride + 1
         self.n_inputs = image * image
         self.length = out_channels * self.slides * self.slides
         self.base, self.legs, self.denom = decomp_base, decomp_legs, denom
+        self.lookup_range, self.seed, self.capacity = tuple(lookup_range), seed, capacity
         rng = np.random.default_rng(seed)
         self.kernels = rng.integers(-20, 21, (out_channels, kernel, kernel))               # round(32 * trained float), main.rs:346-358
         self.conv_bias = np.zeros(out_channels, np.int64)                                 # main.rs:366-367
         self.fc_w = rng.integers(-12, 13, (classes, self.length))
         self.fc_b = rng.integers(-40, 41, classes)
+        _given_parameters(self, kernels=kernels, conv_bias=conv_bias, fc_w=fc_w, fc_b=fc_b)
         self.gc = ConvMnistConfig(logrows, self.length, lookup_range, denom, decomp_base, num_inner_cols, capacity)
+
+    def fresh(self):
+        """the same circuit, its parameters as they are now, with an untouched constraint system (compress_selectors rewrites a system in place)"""
+        return ConvMnistCircuit(self.k, self.image, self.kernel, self.oc, self.stride, self.classes, self.lookup_range, self.denom, self.base, self.legs,
+                                self.seed, self.w, self.capacity, self.kernels, self.conv_bias, self.fc_w, self.fc_b)
 
     def model(self, img):
         """the integer forward pass the circuit proves"""
@@ -1505,6 +1542,7 @@ class NormCircuit(LayoutCircuit):
     def __init__(self, logrows, num_inner_cols, capacity, rows, length, input_scale=8, output_scale=64, eps=1.0 / 128, layer_norm=False,
                  decomp_base=128, decomp_legs=2, lookup_range=(-255, 0)):
         self.k, self.w, self.rows, self.length, self.n_inputs = logrows, num_inner_cols, int(rows), int(length), int(rows) * int(length)
+        self.capacity = capacity
         self.input_scale, self.output_scale, self.eps, self.layer_norm = int(input_scale), int(output_scale), float(eps), bool(layer_norm)
         self.base, self.legs, self.lookup_range = decomp_base, decomp_legs, tuple(lookup_range)
         assert self.input_scale >= 1 and self.output_scale >= 1 and abs(zero_recip(self.output_scale, self.eps)) < decomp_base ** decomp_legs
@@ -1536,6 +1574,11 @@ class NormCircuit(LayoutCircuit):
                  self.lookup_range[0], self.lookup_range[1], self.gc.advices[0].num_blocks()]
         return np.asarray(shape, np.int64).tobytes() + np.float64(self.eps).tobytes()
 
+    def fresh(self):
+        """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
+        return NormCircuit(self.k, self.w, self.capacity, self.rows, self.length, self.input_scale, self.output_scale, self.eps, self.layer_norm,
+                           self.base, self.legs, self.lookup_range)
+
     def synthesize(self, x, witness=True):
         assert len(x) == self.n_inputs
         reg = BaseRegion(self.gc, witness)
@@ -1554,7 +1597,9 @@ class PoolClassifierCircuit(LayoutCircuit):
     are seeded synthetic integers, as ConvMnistCircuit's are."""
 
     def __init__(self, logrows, num_inner_cols, capacity, image=8, kernel=3, out_channels=2, stride=1, pool_size=2, pool_stride=2, classes=4,
-                 pool="max", decomp_base=128, decomp_legs=3, seed=0):
+                 pool="max", decomp_base=128, decomp_legs=3, seed=0, kernels=None, conv_bias=None, fc_w=None, fc_b=None):
+        """kernels [oc][K][K], conv_bias [oc], fc_w [classes][oc * pooled^2], fc_b [classes]: the parameters as integers (a shape that
+        does not fit is a ValueError naming the array); an array that is absent keeps its seeded synthetic values"""
         assert pool in ("max", "sum"), pool
         self.k, self.w, self.capacity = logrows, num_inner_cols, capacity
         self.image, self.kernel, self.oc, self.stride, self.classes = image, kernel, out_channels, stride, classes
@@ -1569,6 +1614,7 @@ class PoolClassifierCircuit(LayoutCircuit):
         self.conv_bias = rng.integers(-8, 9, out_channels)
         self.fc_w = rng.integers(-4, 5, (classes, self.length))
         self.fc_b = rng.integers(-16, 17, classes)
+        _given_parameters(self, kernels=kernels, conv_bias=conv_bias, fc_w=fc_w, fc_b=fc_b)
         windows = self.length if pool == "max" and pool_size > 1 else 0        # one sort per window; a `max` of one element sorts nothing
         sort_rows = windows * pool_size * pool_size + (classes if classes > 1 else 0)
         self.settings = EC.GraphSettings(logrows, num_inner_cols, capacity, total_const_size=16, required_range_checks=[(-1, 1), (0, decomp_base - 1), (0, 1)],
@@ -1625,7 +1671,7 @@ class PoolClassifierCircuit(LayoutCircuit):
     def fresh(self):
         """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
         return PoolClassifierCircuit(self.k, self.w, self.capacity, self.image, self.kernel, self.oc, self.stride, self.pool_size, self.pool_stride,
-                                     self.classes, self.pool, self.base, self.legs, self.seed)
+                                     self.classes, self.pool, self.base, self.legs, self.seed, self.kernels, self.conv_bias, self.fc_w, self.fc_b)
 
     def synthesize(self, img, witness=True):
         reg = BaseRegion(self.gc, witness)

@@ -156,7 +156,9 @@ equality tests of tests/test_witness_plan_cpu.py fail loudly -- an assert or a P
     equals_zero               `pow(v, -1, R) if v else 0`   (the truth value of a cell symbol is True: INVZ covers both branches)
     div (round_div)           `mag = abs(s)`, `assert mag < 1 << 52` (recorded as the run-time check), `((s > 0) - (s < 0)) * ((mag + d // 2) // d)`
     nonlinearity              `assert table.range[0] <= signed(v) <= table.range[1]` (recorded as the run-time check), `table.f(signed(v)) % R`,
-                              `(signed(v) - table.range[0]) // table.col_size` -- LookupRecordingRegion only; `table` is its stand-in there
+                              `(signed(v) - table.range[0]) // table.col_size` -- LookupRecordingRegion only; `table` is its stand-in there;
+                              `lookup_inputs_seen` (the running extrema of a witness file) is overridden to nothing: `lookup_stats_host` and
+                              the device compute them from the replayed cells
     Val.__init__ and the ops  `... % R` on any symbol is the symbol
 
 Every cell is written at most once and only reads cells of earlier records; `validate` checks that (the C library runs the same check
@@ -679,6 +681,9 @@ class RecordingRegion(EL.BaseRegion):
         self._dot = None
 
     def copy(self, a, b):                          # copy constraints belong to keygen, not to the witness
+        pass
+
+    def lookup_inputs_seen(self, signed_inputs):   # symbols have no extrema: the statistics of a replay are lookup_stats_host's
         pass
 
     def _const(self, v):
@@ -1620,6 +1625,30 @@ def written_columns(plan):
     for kind, count, p0, p1, dst, a, b, phase in plan.records.tolist():
         out.update(_written_cells(plan, kind, count, p1, dst).tolist())
     return out
+
+
+STATS_ERROR = "lookup input beyond 62 bits"
+
+
+def lookup_stats_host(plan, columns):
+    """(min_lookup_inputs, max_lookup_inputs) of a replayed plan, in Python integers: the executable specification of
+    ezkl_hip_witness_lookup_stats_dev.  Over every TABLE record, in all phases, the least and the greatest signed value of the source
+    cells pool[a + i], both folded with 0 -- what BaseRegion.nonlinearity keeps as it lays the same circuit out.  columns: the advice
+    columns as canonical integers (run_plan_host's).  A source whose magnitude needs 62 bits or more is refused (ValueError), never
+    folded in: no column of a replay that passed holds one there."""
+    n = 1 << plan.k
+    lo = hi = 0
+    P = plan.pool.tolist()
+    for kind, count, p0, p1, dst, a, b, phase in plan.records.tolist():
+        if kind != TABLE:
+            continue
+        for i in range(count):
+            c = P[a + i]
+            s = EL.signed(int(columns[c >> plan.k][c & (n - 1)]) % R)
+            if abs(s) >= 1 << 62:
+                raise ValueError(STATS_ERROR)
+            lo, hi = min(lo, s), max(hi, s)
+    return lo, hi
 
 
 def _lane_failure(kind, ri, element):

@@ -385,8 +385,17 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *   One launch on `stream` (NULL: the library stream), not waited for; HIP events around it: ezkl_hip_last_kernel_ms("witness_tile").  Nothing
  *   is launched and the call returns EZKL_ERR_INVALID when U = 0 or T = 0, U * T > 2^k, a column index >= n_advice (<= 64), a column appears twice
  *   as dst, a column that is some pair's src is another pair's dst with dst != src (its rows [0, U) would be written while they are read), or
- *   two of the columns named share a buffer. */
+ *   two of the columns named share a buffer.
+ * lookup_stats: the statistics a witness file carries of a circuit with static lookups (GraphWitness min_lookup_inputs / max_lookup_inputs,
+ *   which the reference's layout keeps in region.rs:548-559): over the source cells of every nonlinearity (11) record of the plan, in all
+ *   phases, the least and the greatest signed value, both folded with 0 -- a plan without such a record answers (0, 0) and launches
+ *   nothing.  advice_cols_dev: the n_advice columns of a run that returned EZKL_OK (every source is then canonical and inside its table; the
+ *   columns of a refused run are not to be passed).  A source whose magnitude needs 62 bits or more makes the call return EZKL_ERR_INVALID
+ *   (ezkl_hip_witness_last_error counts them) with out_min_max = (0, 0) rather than a wrong extremum.  One launch: a lane per element,
+ *   striding over the records; one 64-bit atomicMin and one atomicMax per wave on two result words the plan owns, set to 0 by every call.
+ *   The call waits for its result; HIP events around the launch: ezkl_hip_last_kernel_ms("witness_lookup_stats"). */
 typedef struct ezkl_wplan_s* ezkl_wplan_t;
+typedef ezkl_wplan_t ezkl_witness_plan_t;
 int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out_plan);
 int ezkl_hip_witness_plan_free(ezkl_wplan_t plan);
 int ezkl_hip_witness_plan_info(ezkl_wplan_t plan, uint32_t out[8]);
@@ -397,6 +406,7 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
 int ezkl_hip_witness_plan_phases(ezkl_wplan_t plan, uint32_t out[2], uint8_t* column_phase);
 int ezkl_hip_witness_tile_dev(void* const* advice_cols_dev, uint32_t n_advice, uint32_t k, uint32_t unit_rows, uint32_t tiles, const uint32_t* dst_cols,
                               const uint32_t* src_cols, uint32_t n_pairs, void* stream);
+int ezkl_hip_witness_lookup_stats_dev(ezkl_witness_plan_t plan, void* const* advice_cols_dev, int64_t out_min_max[2], void* stream);
 const char* ezkl_hip_witness_last_error(void);   /* the calling thread's last refusal (upload) or range failure (run); "" after a success */
 /* A commit batch fed as its columns become final: begin; push (one column / several: fused into groups as the one-call batch does) any
  * number of times; finish returns the points in push order and closes the batch (also after an error).  A push returns once the MSMs
