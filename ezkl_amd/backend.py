@@ -1178,6 +1178,14 @@ def witness_tile(columns, k, unit_rows, tiles, pairs, stream=None):
     _l.check(rc, "ezkl_hip_witness_tile_dev")
 
 
+def witness_wide_dots(reset=False):
+    """how many DOT records this process has replayed on the wide kernel (ezkl_hip_witness_wide_dots: one step of at least
+    witness_plan.DOT_WIDE_MIN products, the claimed product of an einsum); reset: back to zero after the reading"""
+    out = C.c_uint64(0)
+    _l.check(_l.load().ezkl_hip_witness_wide_dots(C.byref(out), C.c_int(1 if reset else 0)), "ezkl_hip_witness_wide_dots")
+    return int(out.value)
+
+
 class WitnessPlan:
     """a witness plan (witness_plan.WitnessPlan bytes) resident on the device: `run` synthesizes the advice columns of one proof
     into DeviceBuffers (ezkl_hip_witness_run_dev) -- the columns native.create_proof takes as they are.  A plan with phases

@@ -22,6 +22,12 @@
 //    see wit_rlc_kernel.  The contraction "j,j->" is a dot record with w = 1; everything else is a copy.  An operand of a matmul
 //    outside |v| < 2^31 is reported as the range failures below are ("einsum operand outside the exact-product range").
 //
+//  * the general einsum (ezkl_layout.EinsumCircuit: any two-operand equation of the Freivalds chip, over cells the circuit computed).  The
+//    product the prover claims is a dot record of ONE step of K products per output element, over the operands' cells: such a record
+//    (p1 == 1, p0 >= DOT_WIDE_MIN) runs on wit_dot_wide_kernel, every lane of a wave multiplying, the partial sums met by wave shuffles; the
+//    lanes to a dot are chosen on the host (dot_wide_lanes).  The cells are wit_dot_kernel's bit for bit; ezkl_hip_witness_wide_dots counts
+//    the launches.  The second-phase pairwise product is a mult record, the einsum's sum / prod are sum / prod records.
+//
 //  * the surrogate's ops.  sum / prod records (BaseRegion._accumulate, layouts.rs:2472-2621: the running sum or product of w cells per
 //    row): the chunked scan of the dot records with one operand per entry and addition or the Montgomery product as the monoid, see
 //    wit_acc_kernel.  gather records (row `index` of a dynamic table, the structure of `select`, layouts.rs:1483-1581): an element-wise
@@ -70,6 +76,7 @@
 // index pool, parameters, constants and lookup-table values are read-only after upload.
 #include "common.hpp"
 #include "witness_plan.hpp"
+#include <atomic>
 
 namespace ezkl {
 namespace {
@@ -279,6 +286,47 @@ __global__ __launch_bounds__(64) void wit_dot_kernel(WitCols cols, uint32_t k, c
             wrote++;
         }
     wit_count(wrote, status);
+}
+
+// A DOT record of one step (n_steps == 1) with many products: the claimed product of an einsum, dot d = sum_j a[j * n_dots + d] * b[...], j < w,
+// written to dst[d].  wit_dot_kernel would cut the ONE step into 16 chunks and leave 15 lanes of 16 idle; here every lane multiplies.  A wave
+// holds 64 / G dots, G lanes to a dot (G a power of two the host chooses, dot_wide_lanes): lane l works on dot l % (64 / G) and takes the
+// products j = l / (64 / G), + G, + 2G, ... -- so the 64 / G lanes with the same j read consecutive index words (the arrays are j-major, dense
+// along d), for G = 1 a whole wave does.  Two running sums per lane keep two Montgomery products in flight.  The partial sums of a dot sit
+// 64 / G lanes apart and are added by a butterfly of wave shuffles; the lane with j = 0 writes.  Field addition is exact and Fr::add answers
+// the canonical word, so the cell is wit_dot_kernel's bit for bit whatever the order of the additions.
+EZ_D fe_t wit_shfl_xor(const fe_t& v, uint32_t mask) {
+    fe_t r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.v[i] = __shfl_xor(v.v[i], (int)mask, 64);
+    return r;
+}
+EZ_D fe_t wit_product(const WitCols& cols, uint32_t k, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, size_t at, fe_t acc) {
+    const uint32_t ia = a[at];
+    if (ia != NONE) acc = Fr::add(acc, Fr::mul(ld_fe(wit_cell(cols, k, ia)), ld_fe(wit_cell(cols, k, b[at]))));
+    return acc;
+}
+__global__ __launch_bounds__(64) void wit_dot_wide_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const uint32_t* __restrict__ a,
+                                                          const uint32_t* __restrict__ b, uint32_t n_dots, uint32_t w, uint32_t lanes,
+                                                          unsigned long long* status) {
+    const uint32_t per_wave = 64 / lanes, l = threadIdx.x & 63;
+    const size_t d = (size_t)blockIdx.x * per_wave + l % per_wave;
+    const uint32_t g = l / per_wave;
+    const uint32_t cell = d < n_dots ? dst[d] : NONE;            // the same for every lane of a dot; no destination: no products either
+    fe_t s0 = Fr::zero(), s1 = Fr::zero();
+    if (cell != NONE) {
+        uint32_t j = g;
+        for (; j + lanes < w; j += 2 * lanes) {
+            s0 = wit_product(cols, k, a, b, (size_t)j * n_dots + d, s0);
+            s1 = wit_product(cols, k, a, b, (size_t)(j + lanes) * n_dots + d, s1);
+        }
+        if (j < w) s0 = wit_product(cols, k, a, b, (size_t)j * n_dots + d, s0);
+    }
+    fe_t sum = Fr::add(s0, s1);
+    for (uint32_t off = per_wave; off < 64; off <<= 1) sum = Fr::add(sum, wit_shfl_xor(sum, off));     // every lane of the wave takes part
+    const bool write = cell != NONE && g == 0;
+    if (write) st_fe(wit_cell(cols, k, cell), sum);
+    wit_count(write ? 1u : 0u, status);
 }
 
 // The running sum (SUMACC) or product (PRODACC) of w cells per row: wit_dot_kernel with one operand per entry and the fold as the monoid.
@@ -986,6 +1034,7 @@ struct DevPlan {
     void* done_cols[MAX_ADVICE] = {nullptr};
 };
 thread_local std::string t_wit_error;
+std::atomic<uint64_t> g_wide_dots{0};                             // DOT records launched on wit_dot_wide_kernel (ezkl_hip_witness_wide_dots)
 // the bytes of sort_keys a record's launchers go through
 size_t wit_scratch_bytes(const Rec& r) {
     if (r.kind == SORT || r.kind == ARGSORT)                      // segments * P * 16 B of a sort that leaves LDS
@@ -1101,6 +1150,12 @@ using namespace ezkl;
 extern "C" {
 
 const char* ezkl_hip_witness_last_error(void) { return t_wit_error.c_str(); }
+
+int ezkl_hip_witness_wide_dots(uint64_t* launches, int reset) {
+    if (!launches) return EZKL_ERR_INVALID;
+    *launches = reset ? g_wide_dots.exchange(0) : g_wide_dots.load();
+    return EZKL_OK;
+}
 
 int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out) {
     if (!out) return EZKL_ERR_INVALID;
@@ -1277,7 +1332,14 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
                                p->status);
             break;
         case DOT:
-            hipLaunchKernelGGL(wit_dot_kernel, dim3(cdiv((size_t)r.count * DOT_LANES, 64)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, p->pool + r.b, r.count, r.p0, r.p1,
+            if (r.p1 == 1 && r.p0 >= DOT_WIDE_MIN) {                 // one long step: every lane multiplies
+                const uint32_t lanes = dot_wide_lanes(r.count, r.p0);
+                hipLaunchKernelGGL(wit_dot_wide_kernel, dim3(cdiv((size_t)r.count, 64 / lanes)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, p->pool + r.b,
+                                   r.count, r.p0, lanes, p->status);
+                g_wide_dots.fetch_add(1, std::memory_order_relaxed);
+                break;
+            }
+            hipLaunchKernelGGL(wit_dot_kernel,dim3(cdiv((size_t)r.count * DOT_LANES, 64)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, p->pool + r.b, r.count, r.p0, r.p1,
                                p->status);
             break;
         default:                                                   // (`parse` refuses every kind this loop does not name)

@@ -27,6 +27,16 @@ namespace wplan {
 
 constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64, MAX_PHASES = 3, MAX_CHALLENGES = 64, SORT_TILE = 2048,
                    MAX_SORT_COUNT = 1u << 28, ARGEXT_CHUNK = 4096, SCATTER_TILE = 4096;
+// A DOT record of ONE step (p1 == 1) with p0 >= DOT_WIDE_MIN products -- the claimed product of an einsum -- runs on wit_dot_wide_kernel;
+// every other DOT record on wit_dot_kernel.  DOT_WIDE_FILL: the lanes that fill the device (256 compute units x 4 SIMDs x 2 waves of 64).
+constexpr uint32_t DOT_WIDE_MIN = 16, DOT_WIDE_FILL = 1u << 17;
+// how many lanes of a wave share one dot of the wide kernel: a power of two, at most 64 and at most p0; one when `count` dots alone fill
+// the device, more when there are few long dots
+inline uint32_t dot_wide_lanes(uint32_t count, uint32_t p0) {
+    uint32_t g = 1;
+    while (g < 64 && 2 * g <= p0 && (uint64_t)count * g < DOT_WIDE_FILL) g *= 2;
+    return g;
+}
 // kinds 16, 23, 26 and 28 are unassigned and refused; KINDS_TOP is the first kind past them all
 enum Kind : uint32_t { COPY, CONST, INPUT, PARAM, ADD, SUB, MUL, HINT, RCIDX, INVZ, DOT, TABLE, TBLIDX, MATMUL, RLC, DIVC, SUMACC = 17, PRODACC, GATHER, CLAMP, SORT, ARGSORT,
                        RECIP = 24, ISQRT, ARGEXT = 27, SCATTER = 29, COMPLEMENT, ONEHOT, KINDS_TOP };

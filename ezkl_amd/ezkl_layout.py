@@ -326,6 +326,274 @@ class EinsumMatmulCircuit:
         return fn
 
 
+EINSUM_OPERANDS_ERROR = "the einsum layout takes two operands"
+EINSUM_BASE_OPS_ERROR = "an einsum the reference lays out with base ops, not with Freivalds' argument"
+EINSUM_REPEAT_ERROR = "an einsum operand with a repeated axis"
+EINSUM_OVERFLOW_ERROR = "column overflow (duplication) is not laid out here"
+EINSUM_WIDTH_ERROR = "one inner column, as in the reference bench"
+EINSUM_SHAPE_ERROR = "an einsum operand of another size than its axes give"
+
+
+class _HostEinsumOps:
+    """the running values `EinsumCircuit.sequence` asks for, on integers: cur = 0 answers zeros for whatever a challenge enters (those
+    cells are not written in the first phase)"""
+
+    def __init__(self, challenges):
+        self.challenges, self.cur = challenges, 0 if challenges is None else 1
+
+    def rlc(self, vals, ci):
+        if self.cur == 0:
+            return [Val(0)] * len(vals)
+        c, acc, run = self.challenges[ci], 0, []
+        for v in vals:
+            acc = (acc * c + c * v.v) % R
+            run.append(Val(acc))
+        return run
+
+    def dot(self, xs, ys):
+        acc, run = 0, []
+        for x, y in zip(xs, ys):
+            acc = (acc + x.v * y.v) % R
+            run.append(Val(acc))
+        return run
+
+    def sum(self, xs):
+        acc, run = 0, []
+        for x in xs:
+            acc = (acc + x.v) % R
+            run.append(Val(acc))
+        return run
+
+    def prod(self, xs):
+        acc, run = 1, []
+        for x in xs:
+            acc = acc * x.v % R
+            run.append(Val(acc))
+        return run
+
+    def mul(self, xs, ys):
+        return [Val(x.v * y.v) for x, y in zip(xs, ys)]
+
+
+class EinsumCircuit(EinsumMatmulCircuit):
+    """`Einsums::assign_einsum` (/root/reference/src/circuit/ops/chip/einsum/mod.rs:105-300) for any two-operand equation the reference
+    lays out with Freivalds' argument, at block width 1 in one block: the plan is einsum_plan's (reduction_planner.rs, analysis.rs), the
+    output is squashed by `assign_output` (:302-348), the operands by the plan's reductions -- an RLC (RLCConfig::assign_rlc :785-866), a
+    pairwise product (`assign_pairwise_mult` :351-376, einsum/layouts.rs:16-93 `pairwise`) or a contraction (`assign_input_contraction`
+    :378-420: `sum` layouts.rs:95-163 of one tensor, `dot` :233-315 of two) --, the scalars that remain go through `prod` (:165-231) and
+    the result is copy-constrained to the squashed output.  dims: axis -> extent for every axis of an operand; an operand is its entries
+    row-major in the order of its own expression.  With standalone columns (this constructor) max_num_output_axes and the capacity come
+    from the analysis; `over` lays the same sequence over the Freivalds columns of a GraphConfig.  Three or more operands (`multi_dot`),
+    the base-op strategy and a column that overflows into a second block are refused by name."""
+
+    def __init__(self, k, equation, dims, num_inner_cols=1):
+        self._plan(k, equation, dims, num_inner_cols)
+        cs = self.cs = ConstraintSystem()
+        self.base = type("Cfg", (), {})()
+        self.einsums = EC.Einsums(cs, self.reduction_length, self.analysis.num_output_axes, num_inner_cols, k)
+        self.const_cols = EC.VarTensor.constant_cols(cs, k, 2)
+        cs.chunk_lookups()
+        assert all(v.num_blocks() == 1 for v in self.einsums.inputs + self.einsums.outputs), EINSUM_OVERFLOW_ERROR
+        self.standalone = True
+
+    def _plan(self, k, equation, dims, num_inner_cols):
+        """everything that is refused, before a column exists"""
+        from . import einsum_plan as EP
+        inputs_eq, _ = equation.split("->")
+        exprs = inputs_eq.split(",")
+        if len(exprs) != 2:
+            raise ValueError(EINSUM_OPERANDS_ERROR)
+        if any(len(set(e)) != len(e) for e in exprs):
+            raise ValueError(EINSUM_REPEAT_ERROR)
+        if num_inner_cols != 1:
+            raise ValueError(EINSUM_WIDTH_ERROR)
+        self.k, self.w, self.equation = k, num_inner_cols, equation
+        self.dims = {c: int(dims[c]) for e in exprs for c in e}
+        self.analysis = EP.einsum_analysis(equation, self.dims)
+        if self.analysis.strategy != EP.FREIVALDS:
+            raise ValueError(EINSUM_BASE_OPS_ERROR)
+        self.reductions = EP.einsum_reductions(self.analysis.equation)
+        self.reduction_length = self.analysis.reduction_length
+        self.exprs = self.analysis.equation.split("->")[0].split(",")              # without the trivial axes; the entries stay in place
+        self.sizes = [math.prod(self.dims[c] for c in e) for e in self.exprs]
+        self.out_shape = [self.dims[c] for c in self.analysis.output_indices]
+
+    @property
+    def n_inputs(self):
+        """the entries of the first operand, then of the second, row-major: the input vector of a witness plan"""
+        return sum(self.sizes)
+
+    @classmethod
+    def over(cls, gc, equation, dims):
+        """the same layout over the Freivalds columns of an existing GraphConfig (BaseConfig::configure_einsums), written into the
+        caller's region next to its other ops (BaseRegion.einsum)"""
+        self = cls.__new__(cls)
+        self._plan(gc.settings.logrows, equation, dims, gc.settings.num_inner_cols)
+        self.cs, self.einsums, self.const_cols = gc.cs, gc.base.einsums, gc.const_cols
+        assert len(self.einsums.rlc) >= self.analysis.num_output_axes, "the configuration has fewer RLC gates than the einsum has output axes"
+        assert all(v.num_blocks() == 1 and v.num_inner_cols == 1 for v in self.einsums.inputs + self.einsums.outputs), EINSUM_OVERFLOW_ERROR
+        return self
+
+    # ---- the pieces of assign_einsum -------------------------------------------------------------------------------
+    def _live(self, var, cur):
+        return cur == 1 or not any(var is v for v in (self.einsums.inputs[2], self.einsums.inputs[3], self.einsums.outputs[1]))
+
+    def _vars(self, phases):
+        """ContractionConfig::get_input_vars / get_output_var (mod.rs:463-481) -> (InputPhases, input VarTensors, output VarTensor)"""
+        E = self.einsums
+        ph = {(0,): EC.FIRST_PHASE, (1,): EC.SECOND_PHASE, (0, 0): EC.BOTH_FIRST, (0, 1): EC.MIXED, (1, 0): EC.MIXED, (1, 1): EC.BOTH_SECOND}[tuple(phases)]
+        ins = {EC.FIRST_PHASE: [E.inputs[0]], EC.SECOND_PHASE: [E.inputs[2]], EC.BOTH_FIRST: [E.inputs[0], E.inputs[1]],
+               EC.MIXED: [E.inputs[0], E.inputs[2]], EC.BOTH_SECOND: [E.inputs[2], E.inputs[3]]}[ph]
+        return ph, ins, E.outputs[0] if ph in (EC.FIRST_PHASE, EC.BOTH_FIRST) else E.outputs[1]
+
+    def _rlc_placed(self, region, gate_idx, vals, rlc, rlc_len, phase, cur):
+        """`_rlc`, answering the placed inputs beside the results"""
+        g = self.einsums.rlc[gate_idx]
+        in_var, out_var = [self.einsums.inputs[0], self.einsums.inputs[2]][phase], self.einsums.outputs[1]
+        results, placed = [], []
+        for s in range(0, len(vals), rlc_len):
+            chunk = self._assign(region, in_var, vals[s:s + rlc_len], live=(phase == 0 or cur == 1))
+            outs = self._assign(region, out_var, rlc(chunk, gate_idx), live=(cur == 1))
+            init_s, acc_s = g["selectors"][(phase, 0)]
+            region.enable(init_s, region.coord)
+            for t in range(1, len(chunk)):
+                region.enable(acc_s, region.coord + t)
+            results.append(outs[-1])
+            placed += chunk
+            region.coord += len(chunk)
+        return results, placed
+
+    def _accumulated(self, region, ins, running, ops_kind, phases, cur):
+        """einsum/layouts.rs `sum` (:95-163), `prod` (:165-231) and `dot` (:233-315) at block width 1: the tensors into the input
+        VarTensors of their phases, the running value beside them, the INIT selector on the first row and the accumulating one after"""
+        init_op, op = ops_kind
+        ph, in_vars, out_var = self._vars(phases)
+        placed = [self._assign(region, var, vals, live=self._live(var, cur)) for var, vals in zip(in_vars, ins)]
+        outs = self._assign(region, out_var, running(*placed), live=self._live(out_var, cur))
+        sel = self.einsums.contraction_selectors
+        region.enable(sel[((init_op, ph), 0, 0)], region.coord)
+        for t in range(1, len(outs)):
+            region.enable(sel[((op, ph), 0, 0)], region.coord + t)
+        region.coord += len(outs)
+        return outs[-1]
+
+    def _pairwise_mult(self, region, ins, ops, phases, cur):
+        """einsum/layouts.rs:16-93 `pairwise` with BaseOp::Mult: one MULT row per element"""
+        ph, in_vars, out_var = self._vars(phases)
+        placed = [self._assign(region, var, vals, live=self._live(var, cur)) for var, vals in zip(in_vars, ins)]
+        outs = self._assign(region, out_var, ops.mul(*placed), live=self._live(out_var, cur))
+        for t in range(len(outs)):
+            region.enable(self.einsums.contraction_selectors[((EC.MULT, ph), 0, 0)], region.coord + t)
+        region.coord += len(outs)
+        return outs
+
+    def sequence(self, region, operands, O, ops, cur):
+        """assign_einsum, stated once: `synthesize` runs it on integers, the witness-plan recorder (witness_plan.py) on symbols.
+        operands: the two operands as flat row-major lists of Vals; O: the Vals of the product, row-major over the output axes; ops:
+        rlc(vals, challenge index), dot(xs, ys), sum(xs), prod(xs) -- the running values over assigned Vals -- and mul(xs, ys); cur: the
+        phase being synthesized (0: first-phase columns, selectors, copies; 1: everything).  Returns the product as the Vals
+        `assign_output`'s first RLC placed in the first-phase input column."""
+        from . import einsum_plan as EP
+        E, dims = self.einsums, self.dims
+        assert [len(t) for t in operands] == self.sizes and len(O) == math.prod(self.out_shape), EINSUM_SHAPE_ERROR
+        # assign_output (:302-348): the axes in reverse, phase 0 for the first RLC and phase 1 after it, then the squashed scalar
+        inter, product, n_axes = list(O), None, len(self.out_shape)
+        for idx in range(n_axes):
+            inter, placed = self._rlc_placed(region, n_axes - 1 - idx, inter, ops.rlc, self.out_shape[n_axes - 1 - idx], 1 if idx else 0, cur)
+            product = placed if product is None else product
+        out_var = E.outputs[1 if n_axes else 0]
+        squashed_out = self._assign(region, out_var, inter, live=self._live(out_var, cur))[0]
+        region.coord += 1
+        # the input reductions (:168-283)
+        tensors = [(e, list(t)) for e, t in zip(self.exprs, operands)]
+        reduced_phase = 0
+        for red in self.reductions:
+            in_exprs, out_expr = red.expression.split("->")
+            in_exprs = in_exprs.split(",")
+            inputs = [tensors[i] for i in EP.reduction_inputs(red)]
+            flat = [[] for _ in inputs]
+            for at in np.ndindex(*[dims[c] for c in out_expr]):                   # one running value per index tuple of the remaining axes
+                fixed = dict(zip(out_expr, at))
+                for t, (expr, vals) in enumerate(inputs):
+                    ranges = [[fixed[c]] if c in fixed else range(dims[c]) for c in expr]
+                    strides = self._strides([dims[c] for c in expr])
+                    flat[t] += [vals[sum(i * s for i, s in zip(pos, strides))] for pos in self._product(ranges)]
+            if isinstance(red, EP.RLC):
+                result, _ = self._rlc_placed(region, red.challenge_index, flat[0], ops.rlc, dims[red.axis], red.input_phase, cur)
+            elif red.axis is None:                                                # assign_pairwise_mult (:351-376)
+                phases = list(red.input_phases)
+                if phases[0] > phases[1]:
+                    flat, phases = flat[::-1], phases[::-1]
+                result = self._pairwise_mult(region, flat, ops, phases, cur)
+            else:                                                                 # assign_input_contraction (:378-420)
+                length, result = dims[red.axis], []
+                for s in range(0, len(flat[0]), length):
+                    chunk = [f[s:s + length] for f in flat]
+                    if len(chunk) == 1:
+                        result.append(chunk[0][0] if length == 1 else
+                                      self._accumulated(region, chunk, ops.sum, (EC.SUMINIT, EC.SUM), red.input_phases, cur))
+                    else:
+                        phases = list(red.input_phases)
+                        if phases[0] > phases[1]:
+                            chunk, phases = chunk[::-1], phases[::-1]
+                        result.append(self._accumulated(region, chunk, ops.dot, (EC.DOTINIT, EC.DOT), phases, cur))
+            tensors.append((out_expr, result))
+            reduced_phase = EP.reduction_output_phase(red)
+        # the scalars that remain, through `prod`; the result is the squashed output
+        scalars = [vals[0] for _, vals in tensors if len(vals) == 1]
+        squashed_in = self._accumulated(region, [scalars], ops.prod, (EC.CUMPRODINIT, EC.CUMPROD), [reduced_phase], cur)
+        region.copy(squashed_in.cell, squashed_out.cell)
+        return product
+
+    @staticmethod
+    def _strides(shape):
+        out, s = [], 1
+        for d in reversed(shape):
+            out.append(s)
+            s *= d
+        return out[::-1]
+
+    @staticmethod
+    def _product(ranges):
+        out = [()]
+        for r in ranges:
+            out = [p + (i,) for p in out for i in r]
+        return out
+
+    # ---- on integers ------------------------------------------------------------------------------------------------
+    def einsum(self, a, b):
+        """the product the prover witnesses: the exact contraction over the integers, flat and row-major over the output axes"""
+        shapes = [[self.dims[c] for c in e] for e in self.exprs]
+        a, b = (np.array([int(v) for v in np.asarray(x, dtype=object).reshape(-1)], dtype=object).reshape(s) for x, s in zip((a, b), shapes))
+        out = np.einsum(self.analysis.equation, a, b)
+        return [int(v) for v in np.asarray(out, dtype=object).reshape(-1)]
+
+    def host_ops(self, a, b, challenges=None):
+        """what `sequence` takes besides the operands when it runs on integers: (the product's Vals, the running values, the phase)"""
+        ops = _HostEinsumOps(challenges)
+        return [Val(v) for v in self.einsum(a, b)], ops, ops.cur
+
+    def synthesize(self, a, b, challenges=None, region=None):
+        """a, b: the operands as integer arrays (values mod r, or signed).  challenges=None: first phase (first-phase columns, selectors,
+        copies); else the challenges, one per output axis: everything.  Returns the Region (a fresh one unless the caller hands its own)."""
+        if region is None:
+            region = Region(self.cs, self.k)
+        flat = lambda x: [Val(int(v)) for v in np.asarray(x, dtype=object).reshape(-1)]
+        self.sequence(region, [flat(a), flat(b)], *self.host_ops(a, b, challenges))
+        return region
+
+    def plan_identity(self):
+        dims = ",".join("%s=%d" % (c, self.dims[c]) for c in sorted(self.dims))
+        return ("%s:k=%d:%s:%s" % (type(self).__name__, self.k, self.equation, dims)).encode()
+
+    def advice_fn(self, a, b, n_advice):
+        n, nc = 1 << self.k, self.analysis.num_output_axes
+        def fn(phase, challenges):
+            region = self.synthesize(a, b, None if phase == 0 else tuple(challenges[:nc]))
+            return {c.index: region.advice.get(c.index, [0] * n) for c in self.cs.advice if c.phase == phase}
+        return fn
+
+
 def ints_to_mont(colv):
     """list of n canonical ints -> (n, 4) u64 Montgomery array (plain Python: small columns / tests)"""
     if isinstance(colv, np.ndarray):
@@ -1170,7 +1438,14 @@ class BaseRegion(Region):
 
     def einsum(self, ein, A, B, challenges=None):
         """assign_einsum of an EinsumMatmulCircuit laid over this region's configuration (EinsumMatmulCircuit.over), in this region, at
-        the einsum coordinate: A, B are len x len Vals"""
+        the einsum coordinate: A, B are len x len Vals.  Of an EinsumCircuit (EinsumCircuit.over): A, B are the operands as flat
+        row-major lists of Vals, which may hold a cell already (`_assign` copy-constrains it), and the product comes back as Vals that
+        carry the cell the claim landed in -- the first-phase RLC input column, at the rows of `assign_output`'s first RLC -- so that
+        a later op that places the product is tied to it.  (The reference returns bare values here, layouts.rs:879: a deliberate
+        superset of its copy constraints.)"""
+        if isinstance(ein, EinsumCircuit):
+            a, b = ([signed(v.v) for v in M] for M in (A, B))
+            return ein.sequence(self, [list(A), list(B)], *ein.host_ops(a, b, challenges))
         ints = lambda M: np.array([[signed(v.v) for v in row] for row in M], np.int64)
         ein.sequence(self, A, B, *ein.host_ops(ints(A), ints(B), challenges))
 
@@ -2064,6 +2339,131 @@ class _DeviceSurrogateWitness:
             c.free()
         self.columns = []
         self.plan.free()
+
+
+class AttentionHeadCircuit(LayoutCircuit):
+    """One attention head over `n` tokens, every matmul a Freivalds einsum over the circuit's own configuration (layouts.rs:826 `einsum`,
+    BaseRegion.einsum) -- the path the matmuls of a transformer graph take to the prover.  X (n x e) is the private model input, Wq, Wk,
+    Wv (e x d) are parameters: Q, K, V = einsum("ie,ed->id"); S = einsum("id,jd->ij", Q, K), `div` by `score_div`, `softmax_axes` over the
+    rows (the pieces of NormCircuit: max by sort, the exp table, sum, the claimed reciprocal, MULT -- outputs at input_scale *
+    output_scale); O = einsum("ij,jd->id", P, V), `div` by input_scale * output_scale, range-checked and tied to the instance column.
+    From the second einsum on the operands are cells the circuit computed.  The op sequence is stated once (`layout`).  The defaults keep
+    the scores inside the exp table for entries of X in [-4, 4] and of the weights in [-2, 2] (`default_inputs`, the seeded weights);
+    another input that leaves it is refused by the layout's own assertion."""
+
+    def __init__(self, logrows, n, e, d, capacity, num_inner_cols=1, input_scale=8, output_scale=64, eps=1.0 / 128, score_div=None,
+                 decomp_base=128, decomp_legs=2, lookup_range=(-255, 0), seed=1):
+        from . import einsum_plan as EP
+        self.k, self.w, self.n, self.e, self.d, self.capacity = logrows, num_inner_cols, int(n), int(e), int(d), capacity
+        self.n_inputs = self.n * self.e
+        self.input_scale, self.output_scale, self.eps = int(input_scale), int(output_scale), float(eps)
+        self.score_div = int(score_div) if score_div is not None else max(1, math.ceil(self.e * math.sqrt(self.d)))
+        self.out_div = self.input_scale * self.output_scale
+        self.base, self.legs, self.lookup_range, self.seed = decomp_base, decomp_legs, tuple(lookup_range), seed
+        assert abs(zero_recip(self.output_scale, self.eps)) < decomp_base ** decomp_legs
+        scale = self.input_scale
+        self.exp = lambda x: int(math.floor(scale * math.exp(x / scale) + 0.5))         # LookupOp::Exp { scale, base: e } (ops.rs `exp`)
+        self.equations = [("ie,ed->id", dict(i=self.n, e=self.e, d=self.d))] * 3 + [("id,jd->ij", dict(i=self.n, j=self.n, d=self.d)),
+                                                                                   ("ij,jd->id", dict(i=self.n, j=self.n, d=self.d))]
+        analyses = [EP.einsum_analysis(eq, dims) for eq, dims in self.equations]
+        self.settings = EC.GraphSettings(logrows, num_inner_cols, capacity, total_const_size=16,
+                                         required_range_checks=[(-1, 1), (0, decomp_base - 1), (0, 1)], required_lookups=[("exp", self.exp)],
+                                         lookup_range=self.lookup_range, model_instance_shapes=[[self.n, self.d]],
+                                         total_shuffle_col_size=self.n * self.n, num_shuffles=1,
+                                         einsum_reduction_length=sum(a.reduction_length for a in analyses), einsum_max_output_axes=2)
+        self.gc = EC.GraphConfig(self.settings)
+        self.eins = [EinsumCircuit.over(self.gc, eq, dims) for eq, dims in self.equations]
+        rng = np.random.default_rng(seed)
+        self.Wq, self.Wk, self.Wv = (rng.integers(-2, 3, (self.e, self.d)) for _ in range(3))
+        self.x = rng.integers(-4, 5, (self.n, self.e))
+
+    def default_inputs(self):
+        return [int(v) for v in self.x.reshape(-1)]
+
+    def layout(self, reg, inputs, param, challenges=None):
+        """inputs: X row-major as `n_inputs` Vals; param(v) -> the Val of a circuit parameter (asked for in the order Wq, Wk, Wv, row-major);
+        challenges: None lays the first phase (as the witness-plan recorder does, on symbols), else the two challenges: everything"""
+        reg.decomp = (self.base, self.legs)
+        n, d = self.n, self.d
+        x = reg.assign(reg.inputs[0], inputs)                                        # placed once: the three projections read the same cells
+        reg.increment(len(x))
+        Wq, Wk, Wv = ([param(int(v)) for v in W.reshape(-1)] for W in (self.Wq, self.Wk, self.Wv))
+        Q, K, V = (reg.einsum(ein, x, W, challenges) for ein, W in zip(self.eins[:3], (Wq, Wk, Wv)))
+        S = reg.div(reg.einsum(self.eins[3], Q, K, challenges), self.score_div)
+        P_ = reg.softmax_axes([S[i * n:(i + 1) * n] for i in range(n)], self.input_scale, self.output_scale, self.eps)
+        O = reg.div(reg.einsum(self.eins[4], [v for row in P_ for v in row], V, challenges), self.out_div)
+        return reg.output_equals_instance(O, self.gc.instance, 0, self.base, self.legs)
+
+    def plan_identity(self):
+        shape = [self.k, self.w, self.n, self.e, self.d, self.input_scale, self.output_scale, self.score_div, self.base, self.legs,
+                 self.lookup_range[0], self.lookup_range[1], self.gc.advices[0].num_blocks()]
+        return b"".join(np.asarray(a, np.int64).tobytes() for a in (shape, self.Wq, self.Wk, self.Wv)) + np.float64(self.eps).tobytes()
+
+    def fresh(self):
+        """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
+        return AttentionHeadCircuit(self.k, self.n, self.e, self.d, self.capacity, self.w, self.input_scale, self.output_scale, self.eps,
+                                    self.score_div, self.base, self.legs, self.lookup_range, self.seed)
+
+    def synthesize(self, x, witness=True, challenges=None):
+        assert len(x) == self.n_inputs
+        reg = BaseRegion(self.gc, witness)
+        outs = self.layout(reg, [Val(int(v) % R) for v in x], Val, challenges)
+        reg.finish(self.gc.const_cols)
+        self.outputs = [v.v for v in outs]
+        return reg
+
+    def build(self, gpu=None, synthesis="host", as_ints=False, inputs=None):
+        """-> dict(cs, fixed, copies, advice (callable(phase, challenges) -> {column: Montgomery array}), instances): the inputs of keygen
+        and create_proof, as TransformerSurrogateCircuit.build gives them, without tiling.  as_ints: the advice callback returns lists of
+        canonical ints (the MockProver's input).  inputs: X row-major (default: the seeded matrix).  synthesis: "host" -- the layout in
+        Python, once per phase -- or "device" (needs gpu = ezkl_amd.backend): both phases replayed on the device from the circuit's
+        witness plan; `advice` then returns {column: DeviceBuffer} of one resident set of columns, `device_columns` names them,
+        `witness` holds what to free, and the instance vector is read from the plan's output cells."""
+        if synthesis not in ("host", "device"):
+            raise ValueError("synthesis is \"host\" or \"device\", not %r" % (synthesis,))
+        if synthesis == "device" and (gpu is None or as_ints):
+            raise ValueError("synthesis=\"device\" needs a gpu backend and returns device columns")
+        inputs = self.default_inputs() if inputs is None else [int(v) for v in inputs]
+        cs0, n = self.gc.cs, 1 << self.k
+        cs, fixed, copies, reg = self.keygen_inputs(inputs, with_witness=True)
+        instances = [list(self.outputs)]
+        def columns_of(region, phase):
+            idx = [c.index for c in cs0.advice if c.phase == phase]
+            cols = [region.advice.get(i) or [0] * n for i in idx]
+            return dict(zip(idx, cols if as_ints else cols_to_mont(cols, gpu)))
+        cache = {}
+        def advice(phase, challenges):
+            key = (int(phase), tuple(challenges))
+            if key not in cache:
+                cache[key] = columns_of(reg if phase == 0 else self.synthesize(inputs, True, tuple(challenges[:2])), int(phase))
+            return cache[key]
+        out = dict(cs=cs, fixed=fixed, copies=copies, advice=advice, instances=instances)
+        if synthesis == "device":
+            out["witness"] = dev = _DeviceAttentionWitness(self, gpu, inputs)
+            out.update(advice=dev.advice, device_columns=list(range(len(cs0.advice))))
+            try:
+                dev.advice(0, [])
+                out["instances"] = [dev.read_outputs()]
+            except Exception:
+                dev.free()
+                raise
+        return out
+
+
+class _DeviceAttentionWitness(_DeviceSurrogateWitness):
+    """the attention head's witness made on the device: phase p replays phase p of the circuit's plan into one resident set of columns.
+    phase_ms[p] = the device milliseconds of the last call."""
+
+    def __init__(self, circuit, gpu, inputs):
+        super().__init__(circuit, gpu, inputs, 0, 1, {})
+
+    def advice(self, phase, challenges):
+        phase = int(phase)
+        _, outs = self.plan.run(self.inputs, columns=self.columns, phase=phase, challenges=list(challenges))
+        self.phase_ms[phase] = self.plan.last["device_ms"]
+        if phase == self.plan.n_phases - 1:
+            self.outputs = outs
+        return {c: self.columns[c] for c in range(self.plan.n_advice) if self.plan.column_phase[c] == phase}
 
 
 def limbs_to_mont(cols, gpu=None):

@@ -1,5 +1,6 @@
-"""Witness plans: the layout of an MlpCircuit, a ConvMnistCircuit, an EinsumMatmulCircuit, a SumProdLayoutCircuit, a SortTopkCircuit, a
-NormCircuit, a PoolClassifierCircuit, a ScatterGatherCircuit or the TransformerSurrogateCircuit's unit recorded ONCE, replayed for every proof.
+"""Witness plans: the layout of an MlpCircuit, a ConvMnistCircuit, an EinsumMatmulCircuit, an EinsumCircuit, a SumProdLayoutCircuit, a
+SortTopkCircuit, a NormCircuit, a PoolClassifierCircuit, a ScatterGatherCircuit, an AttentionHeadCircuit or the TransformerSurrogateCircuit's
+unit recorded ONCE, replayed for every proof.
 
 Which advice cell holds which value depends only on the circuit (BaseRegion places cells from the linear coordinate, the duplicated rows
 of `dot` from the block geometry; constants and the circuit's parameters are the same for every input), so `record_plan` runs one
@@ -35,6 +36,9 @@ The MLP recorder keeps refusing them by name.  The TransformerSurrogateCircuit l
 (`BaseRegion.einsum`): it is recorded on a PhasedLookupRecordingRegion -- the lookup region with the einsum region's `put_cell`, matmul
 record, running values and phase bookkeeping -- into a TWO-phase plan of the unit's rows; the tiling is the device's
 (ezkl_hip_witness_tile_dev).
+An EinsumCircuit -- any two-operand equation of the Freivalds chip -- standing alone or laid over an AttentionHeadCircuit's configuration
+is recorded from its own `sequence` too (EinsumRecordingRegion.lay_einsum): its operands may be cells the circuit computed, and the product
+the prover claims is ONE DOT record of one step over those cells, emitted after them although the layout writes it before them.
 
 The plan is a flat little-endian blob (`WitnessPlan.to_bytes`):
 
@@ -68,6 +72,8 @@ s is the signed value of the source cell.  A run-time failure is a lane's: repor
     10 DOT     count dot products of p1 steps of p0 products each, step-major: step t of dot d writes the running sum to pool[dst + t * count + d]
                (0xffffffff: no such step) after adding the products of pool[a + (t * p0 + j) * count + d] and pool[b + ...] (0xffffffff in both:
                none -- the duplicated running sum at the top of a new column is a step without products)
+               An einsum's claimed product is such a record with p1 = 1 and p0 = the contracted index tuples, 2 * p0 * count <= 2^28 pool words;
+               from p0 = DOT_WIDE_MIN on the device runs a one-step record on a kernel of its own (dot_wide_lanes lanes to a dot): same cells
     11 TABLE   a = source cell, p0 = table index: values[offset + (s - lo)] as a field element (a negative value as integer_rep_to_felt maps it)
     12 TBLIDX  a = source cell, p0 = table index: (s - lo) // col_size, the table column that holds s.  Both: s < lo, s > lo + n - 1 or
                |s| >= 2^62 fails: "lookup input outside the table range"
@@ -183,6 +189,18 @@ KINDS_TOP = 32                                     # the first kind past them al
 SORT_TILE, MAX_SORT_COUNT = 2048, 1 << 28                       # csrc/witness_plan.hpp: the keys one workgroup sorts in LDS; the most cells of a sort record
 ARGEXT_CHUNK = 4096                                             # csrc/witness_plan.hpp: the sources one workgroup of an arg-extremum reduces
 SCATTER_TILE = 4096                                             # csrc/witness_plan.hpp: the destinations one workgroup of a scatter / a complement resolves in LDS
+DOT_WIDE_MIN, DOT_WIDE_FILL = 16, 1 << 17                       # csrc/witness_plan.hpp: a DOT record of one step with this many products runs on the wide kernel; the lanes that fill the device
+MAX_CLAIM_WORDS = 1 << 28                                       # the most pool words (2 * K * |O|) of an einsum's claim
+CLAIM_ERROR = "an einsum claim of more than 2^28 pool words"
+
+
+def dot_wide_lanes(count, p0):
+    """csrc/witness_plan.hpp dot_wide_lanes: how many lanes of a wave share one dot of the wide kernel -- a power of two, at most 64 and at
+    most p0; one when `count` dots alone fill the device, more when there are few long dots"""
+    g = 1
+    while g < 64 and 2 * g <= p0 and count * g < DOT_WIDE_FILL:
+        g *= 2
+    return g
 _HEADER = struct.Struct("<20I32s")
 RANGE_ERROR = "value exceeds the decomposition range"
 LOOKUP_ERROR = "lookup input outside the table range"
@@ -1094,14 +1112,59 @@ class _MatOut(_Sym):
     def __init__(self, rec, at): self.rec, self.at = rec, at
 
 
+class _Placed(_Sym):
+    """a value whose cell is fixed before the layout reaches it -- an element of an einsum's claimed product, whose DOT record is emitted
+    ahead of the layout -- : `put_cell` only checks that the layout places it there"""
+
+    def __init__(self, dst): self.dst = dst
+
+
+class _Tag(_Sym):
+    """what a layout pass that only asks WHERE things land carries as a value (`_Probe`)"""
+
+    def __init__(self, key=None): self.key = key
+
+
+class _Probe(EL.Region):
+    """a Region that records, for every tagged value, the first cell the layout places it in: no cells, selectors or copies"""
+
+    def __init__(self, cs, k, coord):
+        super().__init__(cs, k)
+        self.coord, self.where = coord, {}
+
+    def copy(self, a, b): pass
+    def enable(self, selector, row): pass
+    def constant(self, const_cols, value): return None
+
+    def put_cell(self, col, row, v):
+        if isinstance(v, _Tag) and v.key is not None:
+            self.where.setdefault(v.key, (col, row))
+        return v
+
+    tagged = staticmethod(lambda xs, *_: [EL.Val(_Tag()) for _ in xs])
+    rlc = dot = sum = prod = mul = tagged
+
+
 class _Run:
-    """the running values of one RLC scan or one dot, pending until the layout has placed every step"""
+    """the running values of one RLC scan, one dot or one running sum / product, pending until the layout has placed every step"""
 
     def __init__(self, kind, p0, src): self.kind, self.p0, self.src, self.dst, self.left = kind, p0, src, [None] * len(src), len(src)
 
 
 class _Step(_Sym):
     def __init__(self, run, t): self.run, self.t = run, t
+
+
+class _EinsumOps:
+    """what EinsumCircuit.sequence asks of its `ops`, answered by an EinsumRecordingRegion's symbols (by the class's own methods: on a
+    PhasedLookupRecordingRegion `dot` and `sum` are the model's ops)"""
+
+    def __init__(self, reg): self.reg = reg
+    def rlc(self, vals, ci): return EinsumRecordingRegion.rlc(self.reg, vals, ci)
+    def dot(self, xs, ys): return EinsumRecordingRegion.dot(self.reg, xs, ys)
+    def sum(self, xs): return EinsumRecordingRegion.acc(self.reg, SUMACC, xs)
+    def prod(self, xs): return EinsumRecordingRegion.acc(self.reg, PRODACC, xs)
+    def mul(self, xs, ys): return EinsumRecordingRegion.mul(self.reg, xs, ys)
 
 
 class EinsumRecordingRegion(EL.Region):
@@ -1117,6 +1180,7 @@ class EinsumRecordingRegion(EL.Region):
         self.out = _Records(earliest=True)
         self.consts, self.n_ops = [], 0
         self.phase_of = {}                         # cell -> the phase that writes it
+        self.preplaced = {}                        # cell -> the operand symbol an einsum's claim had placed there ahead of the layout
 
     def copy(self, a, b):                          # copy constraints and selectors belong to keygen, not to the witness
         pass
@@ -1144,12 +1208,86 @@ class EinsumRecordingRegion(EL.Region):
         run = _Run(DOT, 1, list(zip(self._cells(xs), self._cells(ys))))
         return [EL.Val(_Step(run, t)) for t in range(len(xs))]
 
+    def acc(self, kind, xs):
+        """the running values of the einsum's `sum` (SUMACC) or `prod` (PRODACC): one scan of one operand per step"""
+        run = _Run(kind, 1, self._cells(xs))
+        return [EL.Val(_Step(run, t)) for t in range(len(xs))]
+
+    def mul(self, xs, ys):
+        return [EL.Val(_Bin(MUL, x.v, y.v)) for x, y in zip(xs, ys)]
+
+    def lay_einsum(self, ein, operands):
+        """an EinsumCircuit's `sequence` over symbols.  The prover's claim -- the product -- is ONE DOT record in phase 0: count = |O| dots
+        of one step (p1 = 1) of p0 = K products, K the index tuples of the axes that are not in the output (an operand without such an
+        axis repeats its cell); pool cost 2 * K * |O| words.  It reads CELLS: the cell an operand element already holds, else the
+        first-phase einsum cell its own input reduction places it in.  The layout writes the claim BEFORE those cells, and a record
+        reads only cells of earlier records: so the einsum is laid out once on a `_Probe` to learn where the operands and the product
+        land, the operand cells are placed ahead of the layout, the claim is emitted, and the layout then finds both where it puts
+        them.  Returns the product as Vals that carry the claimed cells."""
+        import itertools, math
+        self.n_ops += 1
+        an, dims = ein.analysis, ein.dims
+        contracted = sorted(set("".join(ein.exprs)) - set(an.output_indices))
+        K, n_out = math.prod(dims[c] for c in contracted), math.prod(ein.out_shape)
+        if 2 * K * n_out > MAX_CLAIM_WORDS:
+            raise PlanError(CLAIM_ERROR)
+        probe = _Probe(self.cs, self.k, self.coord)
+        ein.sequence(probe, [[EL.Val(_Tag(("operand", t, e))) for e in range(len(vals))] for t, vals in enumerate(operands)],
+                     [EL.Val(_Tag(("product", at))) for at in range(n_out)], probe, 1)
+        cells = []
+        for t, vals in enumerate(operands):
+            mine = []
+            for e, val in enumerate(vals):
+                if isinstance(val.v, _Cell):                       # a cell the circuit computed: read where it is
+                    mine.append(val.v.idx)
+                    continue
+                col, row = probe.where[("operand", t, e)]
+                if self.cs.advice[col.index].phase != 0:
+                    raise PlanError("an einsum operand that starts outside the first phase")
+                mine.append(self.put_cell(col, row, val.v).idx)
+                self.preplaced[mine[-1]] = val.v
+            cells.append(mine)
+        strides = [dict(zip(e, ein._strides([dims[c] for c in e]))) for e in ein.exprs]
+        ri = self.out._new((DOT, K, 0, 0))
+        product = []
+        for at, out_pos in enumerate(itertools.product(*[range(n) for n in ein.out_shape])):
+            pos = dict(zip(an.output_indices, out_pos))
+            pairs = []
+            for inner in itertools.product(*[range(dims[c]) for c in contracted]):
+                pos.update(zip(contracted, inner))
+                pairs.append(tuple(cells[t][sum(pos[c] * strides[t][c] for c in ein.exprs[t])] for t in (0, 1)))
+            col, row = probe.where[("product", at)]
+            dst = (col.index << self.k) + row
+            for c in (c for ab in pairs for c in ab):
+                if c not in self.out.rec_of:
+                    raise PlanError("advice cell %d is read before it is written" % c)
+            self.out.recs[ri]["dots"].append([(dst, pairs)])
+            self.out._claim(dst, ri)
+            if self.cs.advice[col.index].phase != 0 or dst in self.phase_of:
+                raise PlanError("an einsum's claim outside a free first-phase cell")
+            self.phase_of[dst] = 0
+            product.append(EL.Val(_Placed(dst)))
+        return ein.sequence(self, operands, product, _EinsumOps(self), 1)
+
     def put_cell(self, col, row, v):
         dst = (col.index << self.k) + row
         out = self.out
+        if isinstance(v, _Placed):
+            if v.dst != dst:
+                raise PlanError("a claimed product element is placed in another cell than its claim names")
+            return _Cell(dst)
+        if dst in self.preplaced and self.preplaced[dst] is v:
+            del self.preplaced[dst]
+            return _Cell(dst)
         if isinstance(v, _Input):
             phase = 0
             out.emit(INPUT, dst, v.idx)
+        elif isinstance(v, _Param):
+            phase = 0
+            out.emit(PARAM, dst, v.idx)
+        elif isinstance(v, _Bin):
+            phase = max(self.phase_of[v.a], self.phase_of[v.b])
+            out.emit(v.kind, dst, v.a, v.b, reads=(v.a, v.b), phase=phase)
         elif isinstance(v, _MatOut):
             phase = 0
             out.matmul_dst(v.rec, v.at, dst)
@@ -1163,11 +1301,14 @@ class EinsumRecordingRegion(EL.Region):
             run.dst[v.t] = dst
             run.left -= 1
             if run.left == len(run.src) - 1:       # the phase of the whole run: worked out once, at its first step
-                run.phase = max([1 if run.kind == RLC else 0] + [self.phase_of[c] for c in (run.src if run.kind == RLC else [c for ab in run.src for c in ab])])
+                run.phase = max([1 if run.kind == RLC else 0] + [self.phase_of[c] for c in (run.src if run.kind != DOT else [c for ab in run.src for c in ab])])
             phase = run.phase
             if run.kind == RLC:
                 if not run.left:
                     out.emit_scan(run.p0, run.src, run.dst, phase)
+            elif run.kind in (SUMACC, PRODACC):
+                if not run.left:
+                    out.emit_acc(run.kind, run.p0, [(d, [c]) for d, c in zip(run.dst, run.src)], phase)
             else:
                 if not run.left:
                     out.emit_dot(run.p0, [(d, [ab]) for d, ab in zip(run.dst, run.src)], phase)
@@ -1195,6 +1336,8 @@ class PhasedLookupRecordingRegion(LookupRecordingRegion, EinsumRecordingRegion):
         return placed
 
     def einsum(self, ein, A, B, challenges=None):
+        if isinstance(ein, EL.EinsumCircuit):
+            return [EL.Val(v.v, ("adv", v.v.idx >> self.k, v.v.idx & ((1 << self.k) - 1))) for v in self.lay_einsum(ein, [list(A), list(B)])]
         L = ein.len
         flat = [v.v for M in (A, B) for row in M for v in row]
         if not all(isinstance(v, _Input) for v in flat):
@@ -1219,12 +1362,27 @@ def _record_einsum(circuit):
                                       n_phases=1 + max(c.phase for c in circuit.cs.advice))
 
 
+def _record_general_einsum(circuit):
+    """a standalone EinsumCircuit: its own `sequence` over symbols (EinsumRecordingRegion.lay_einsum) -- the inputs are the first operand,
+    then the second, row-major; the product is one DOT record over their cells"""
+    if (len(circuit.cs.advice) << circuit.k) > 1 << 32:
+        raise PlanError("cells are numbered in 32 bits")
+    reg = EinsumRecordingRegion(circuit)
+    at = [0, circuit.sizes[0]]
+    reg.lay_einsum(circuit, [[EL.Val(_Input(at[t] + e)) for e in range(circuit.sizes[t])] for t in (0, 1)])
+    return WitnessPlan._from_recorder(circuit, reg, [], [], n_challenges=len(circuit.cs.challenges),
+                                      n_phases=1 + max(c.phase for c in circuit.cs.advice))
+
+
 def params_hash(circuit):
     """what a plan depends on besides the layout code: the circuit's `plan_identity()` bytes -- its shape options and its parameters -- and
     its static lookup tables.  (The domain prefix is keyed on the circuit: none for an MlpCircuit, whose hashes stay what they were.)"""
     h = hashlib.sha256()
     if type(circuit) is EL.EinsumMatmulCircuit:
         h.update(b"phased:" + circuit.plan_identity())
+        return h.digest()
+    if type(circuit) is EL.EinsumCircuit:
+        h.update(b"einsum:" + circuit.plan_identity())
         return h.digest()
     if type(circuit) is not EL.MlpCircuit:
         h.update(("layout:%s:" % type(circuit).__name__).encode())
@@ -1245,11 +1403,13 @@ def record_plan(circuit):
     refused by name."""
     if type(circuit) is EL.EinsumMatmulCircuit and getattr(circuit, "standalone", False):
         return _record_einsum(circuit)
+    if type(circuit) is EL.EinsumCircuit and getattr(circuit, "standalone", False):
+        return _record_general_einsum(circuit)
     if not (callable(getattr(circuit, "layout", None)) and callable(getattr(circuit, "plan_identity", None))):
         raise PlanError("witness plans cover MlpCircuit and circuits that state their `layout`, not %s" % type(circuit).__name__)
     if getattr(circuit, "gc", None) is None:
         raise PlanError("witness plans are recorded from a configured circuit: this %s has no configuration" % type(circuit).__name__)
-    phased = type(circuit) is EL.TransformerSurrogateCircuit      # its einsum is laid over its own configuration: a two-phase plan
+    phased = type(circuit) in (EL.TransformerSurrogateCircuit, EL.AttentionHeadCircuit)      # einsums laid over its own configuration: a two-phase plan
     if any(c.phase != 0 for c in circuit.gc.cs.advice) and not phased:
         raise PlanError("witness plans do not cover second-phase advice")
     reg = RecordingRegion(circuit.gc) if type(circuit) is EL.MlpCircuit else (PhasedLookupRecordingRegion if phased else LookupRecordingRegion)(circuit.gc)

@@ -408,6 +408,10 @@ int ezkl_hip_witness_tile_dev(void* const* advice_cols_dev, uint32_t n_advice, u
                               const uint32_t* src_cols, uint32_t n_pairs, void* stream);
 int ezkl_hip_witness_lookup_stats_dev(ezkl_witness_plan_t plan, void* const* advice_cols_dev, int64_t out_min_max[2], void* stream);
 const char* ezkl_hip_witness_last_error(void);   /* the calling thread's last refusal (upload) or range failure (run); "" after a success */
+/* Which kernel replayed the DOT records: *launches = how many of them, in this process so far, went to the wide kernel -- a record of ONE step
+ * (p1 == 1) with p0 >= 16 products, the claimed product of an einsum, every lane of a wave multiplying -- instead of the chunked scan every
+ * other DOT record runs on.  reset != 0 sets the count back to zero after reading it.  The cells do not depend on the kernel. */
+int ezkl_hip_witness_wide_dots(uint64_t* launches, int reset);
 /* A commit batch fed as its columns become final: begin; push (one column / several: fused into groups as the one-call batch does) any
  * number of times; finish returns the points in push order and closes the batch (also after an error).  A push returns once the MSMs
  * are QUEUED: they start behind everything queued on the library stream so far (an event, no host synchronisation), on the MSM slot
