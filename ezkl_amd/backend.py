@@ -1301,6 +1301,38 @@ def ubench(which):
     return float(out.value)
 
 
+def field_probe_names():
+    """{name: (operands, words per operand row, words per result row)} of ezkl_hip_field_probe_dev (host only, no device needed)"""
+    n = C.c_size_t(0)
+    _l.check(_l.load().ezkl_hip_field_probe_names(None, C.c_size_t(0), C.byref(n)), "ezkl_hip_field_probe_names")
+    buf = C.create_string_buffer(n.value + 1)
+    _l.check(_l.load().ezkl_hip_field_probe_names(buf, C.c_size_t(n.value + 1), C.byref(n)), "ezkl_hip_field_probe_names")
+    out = {}
+    for line in buf.value.decode().splitlines():
+        name, arity, w_in, w_out = line.split()
+        out[name] = (int(arity), int(w_in), int(w_out))
+    return out
+
+
+def field_probe(name, operands):
+    """test hook: one field primitive on the device.  operands: uint32 arrays (n, words per row); returns the (n, words) uint32 result"""
+    arity, w_in, w_out = field_probe_names()[name]
+    ops = [np.ascontiguousarray(o, dtype=np.uint32) for o in operands]
+    if len(ops) != arity or any(o.ndim != 2 or o.shape != (ops[0].shape[0], w_in) for o in ops):
+        raise ValueError("%s takes %d operands of shape (n, %d)" % (name, arity, w_in))
+    n = ops[0].shape[0]
+    bufs = [DeviceBuffer.from_numpy(o) for o in ops]
+    out = DeviceBuffer(max(1, n) * w_out * 4)
+    arr = (C.c_void_p * 4)(*([b.ptr for b in bufs] + [None] * (4 - arity)))
+    try:
+        _l.check(_l.load().ezkl_hip_field_probe_dev(name.encode(), arr, _vp(out.ptr), C.c_size_t(n), _vp(None)), "ezkl_hip_field_probe_dev")
+        return out.to_numpy(np.uint32)[:n * w_out].reshape(n, w_out)
+    finally:
+        out.free()
+        for b in bufs:
+            b.free()
+
+
 # ---------------------------------------------------------------------------------------------------
 # A13 helpers composed from the kernels above (SURVEY.md §8(a) A13; [UPSTREAM] halo2 permutation::prover::commit
 # and mv_lookup::prover::commit_grand_sum).  Everything stays resident; blinding rows / RNG stay with the caller.

@@ -1253,5 +1253,18 @@ int ezkl_hip_ubench(const char* which, double* out) {
     EZ_CTX(c);
     return ubench(c, which, out);
 }
+int ezkl_hip_field_probe_dev(const char* name, const void* const ops_dev[4], void* out_dev, size_t n, void* stream) {
+    if (!name || !ops_dev || !out_dev) return EZKL_ERR_INVALID;
+    EZ_CTX(c);
+    hipStream_t st = pick_stream(c, stream);
+    const uint32_t* ops[4];
+    for (int k = 0; k < 4; k++) ops[k] = (const uint32_t*)ops_dev[k];
+    int rc = field_probe(c, st, name, ops, (uint32_t*)out_dev, n);
+    return rc ? rc : finish(c, st, stream);
+}
+int ezkl_hip_field_probe_names(char* out, size_t cap, size_t* len) {
+    if (!len) return EZKL_ERR_INVALID;
+    return field_probe_names(out, cap, len);       // host-only: no device needed
+}
 
 }  // extern "C"

@@ -173,6 +173,8 @@ int eval_prepare(Ctx* c, const ezkl_program_t* p);
 int eval_schedule_only(const ezkl_program_t* p, uint32_t* out_code);
 void eval_jit_stats(uint64_t* compiled, uint64_t* from_disk, uint64_t* hits);
 int ubench(Ctx* c, const char* which, double* out);
+int field_probe(Ctx* c, hipStream_t st, const char* name, const uint32_t* const ops[4], uint32_t* out, size_t n);
+int field_probe_names(char* out, size_t cap, size_t* len);
 int msm_once_run(Ctx* c, hipStream_t st, const void* points_dev, const fe_t* scalars, size_t n, void* out_host);
 bool msm_table_exists(const Bases* b);
 void msm_table_drop(const Bases* b);

@@ -644,6 +644,18 @@ int ezkl_hip_kernel_ms_stats(const char* which, double* sum_ms, uint64_t* count,
  * "copy" (HBM float4 copy bytes/s); result in *out (per second) */
 int ezkl_hip_ubench(const char* which, double* out);
 
+/* ---- test hooks ---- */
+/* ONE field primitive of csrc/field.hpp or csrc/field29.hpp applied to n rows of operands that are on the device (csrc/fieldprobe.hip):
+ * the tests compare every word with big-integer arithmetic at the operands where a carry, a borrow or a conditional subtraction can go
+ * wrong.  `name` is "<field>.<primitive>" with field fr / fq (rows of 8 uint32 words) or fr29 / fq29 (rows of 9), e.g. "fr.mul_lazy",
+ * "fq29.cond_sub2"; an unknown name is EZKL_ERR_INVALID.  Operand j of row i is the row i of ops_dev[j] (up to 4 operands, unused ones
+ * may be NULL), the result is row i of out_dev.  "<field>.live_<product>" probes write the product, then 6 further rows of operand 0
+ * (rows i+1 .. i+6 mod n) that were held in registers across the product, then 64 words 0x9e3779b9 * (j + 1) held in scalar registers. */
+int ezkl_hip_field_probe_dev(const char* name, const void* const ops_dev[4], void* out_dev, size_t n, void* stream);
+/* every name the probe knows, one per line: "<name> <operands> <words per operand row> <words per result row>".  Host only.  *len is the
+ * length of the whole list; at most cap - 1 characters and a 0 are written to out (out may be NULL to ask for the length). */
+int ezkl_hip_field_probe_names(char* out, size_t cap, size_t* len);
+
 #ifdef __cplusplus
 }
 #endif

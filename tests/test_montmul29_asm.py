@@ -135,3 +135,20 @@ def test_two_product_form_overflows_when_the_bound_is_broken():
     except Overflow:
         return
     raise AssertionError("expected a 64-bit column overflow")
+
+
+def test_square_bound_is_loose_2():
+    """Field29::sqr takes normalized and loose(2) values, not loose(3): the column bound 9 A^2 + 9 < 64 (units of 2^58) of the product
+    holds for the dedicated squaring too.  All limbs at the class maximum: loose(2) squares exactly, loose(3) overflows a column."""
+    for name, mod in (("mont_sqr29_fq", FQ), ("mont_sqr29_fr", FR)):
+        lines = asm_of(name)
+        rinv = pow(1 << 261, -1, mod)
+        for top in (0, 1 << 26):
+            a = [2 * (1 << 29) - 1] * 8 + [top]
+            r = run(lines, {"a": a})
+            assert value(r) % mod == value(a) ** 2 * rinv % mod and all(x <= M29 for x in r[:8])
+            try:
+                run(lines, {"a": [3 * (1 << 29) - 1] * 8 + [top]})
+            except Overflow:
+                continue
+            raise AssertionError("%s: expected a 64-bit column overflow at loose(3) limbs" % name)
