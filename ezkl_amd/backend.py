@@ -1210,8 +1210,10 @@ class WitnessPlan:
         self.last = None                             # counters of the last run
         # the records of kind 11 (a static lookup's outputs): header of 20 words and the parameter hash, the parameters, the constants, then 8 words a record
         head = np.frombuffer(blob, "<u4", 20)
-        kinds = np.frombuffer(blob, "<u4", 8 * int(head[4]), 112 + 8 * int(head[6]) + 32 * int(head[7]))[0::8]
-        self.n_lookup_records, self.last_stats_ms = int((kinds == 11).sum()), None
+        recs = np.frombuffer(blob, "<u4", 8 * int(head[4]), 112 + 8 * int(head[6]) + 32 * int(head[7])).reshape(-1, 8)
+        kinds = recs[:, 0]
+        self.n_lookup_records, self.last_stats_ms, self.last_outputs_ms = int((kinds == 11).sum()), None, None
+        self.lookup_phases = sorted(set(int(p) for p in recs[kinds == 11, 7]))      # the phases that hold such a record
 
     def alloc_columns(self):
         return [DeviceBuffer(32 << self.k) for _ in range(self.n_advice)]
@@ -1271,6 +1273,23 @@ class WitnessPlan:
         _l.check(rc, "ezkl_hip_witness_lookup_stats_dev")
         self.last_stats_ms = last_kernel_ms("witness_lookup_stats") if self.n_lookup_records else None
         return int(out[0]), int(out[1])
+
+    def outputs(self, columns, stream=None):
+        """the plan's outputs as ints, gathered from `columns` once phase 0 has run to its end on them (ezkl_hip_witness_outputs_dev:
+        one launch, one copy, one wait) -- `run` hands them back with the LAST phase only, the instance column is needed before the first
+        commitment.  self.last_outputs_ms: the gather's HIP-event time, None for a plan without outputs.  Raises ValueError with the
+        library's reason, nothing launched, before phase 0 has succeeded or on other columns than it ran on."""
+        if len(columns) != self.n_advice or any(c.nbytes < (32 << self.k) for c in columns):
+            raise ValueError("the plan reads %d columns of %d bytes" % (self.n_advice, 32 << self.k))
+        ptrs = (_vp * self.n_advice)(*[c.ptr for c in columns])
+        outs = np.zeros((max(1, self.n_outputs), 4), np.uint64)
+        L = _l.load()
+        rc = L.ezkl_hip_witness_outputs_dev(self.h, ptrs, _p(outs), _stream_ptr(stream))
+        if rc == -3:
+            raise ValueError(L.ezkl_hip_witness_last_error().decode() or "ezkl_hip_witness_outputs_dev: invalid argument")
+        _l.check(rc, "ezkl_hip_witness_outputs_dev")
+        self.last_outputs_ms = last_kernel_ms("witness_outputs") if self.n_outputs else None
+        return [_from_mont_int(outs[i]) for i in range(self.n_outputs)]
 
     def advice_fn(self, inputs, columns):
         """the per-phase witness callback of native.create_proof(..., device_columns=range(n_advice)): (phase, challenges) -> {column:

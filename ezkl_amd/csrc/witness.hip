@@ -1415,6 +1415,42 @@ int ezkl_hip_witness_lookup_stats_dev(ezkl_wplan_t plan, void* const* advice_col
     return EZKL_OK;
 }
 
+int ezkl_hip_witness_outputs_dev(ezkl_wplan_t plan, void* const* advice_cols_dev, void* outputs_host, void* stream) {
+    if (!plan || !advice_cols_dev) return EZKL_ERR_INVALID;
+    t_wit_error.clear();
+    DevPlan* p = reinterpret_cast<DevPlan*>(plan);
+    const Plan& h = p->host;
+    auto refuse = [&](const std::string& why) { t_wit_error = "witness: " + why; return EZKL_ERR_INVALID; };
+    if (!h.outputs.empty() && !outputs_host) return EZKL_ERR_INVALID;
+    // the cells are read where a finished phase left them: phase 0 must have run to its end on exactly these columns, and no output
+    // may sit in a column that a phase not yet finished zero-fills and writes
+    if (p->done_phase < 0) return refuse("the outputs before phase 0 has run to its end");
+    WitCols cols;
+    for (uint32_t j = 0; j < MAX_ADVICE; j++) cols.p[j] = nullptr;
+    for (uint32_t j = 0; j < h.n_advice; j++) {
+        if (!advice_cols_dev[j]) return EZKL_ERR_INVALID;
+        if (advice_cols_dev[j] != p->done_cols[j]) return refuse("the outputs on other columns than the ones phase 0 ran on");
+        cols.p[j] = static_cast<fe_t*>(advice_cols_dev[j]);
+    }
+    for (const uint32_t cell : h.outputs)                          // (cell < n_advice * 2^k: checked on upload)
+        if ((int)h.col_phase[cell >> h.k] > p->done_phase)
+            return refuse("an output cell belongs to phase " + std::to_string(h.col_phase[cell >> h.k]) + ", which has not run to its end");
+    if (h.outputs.empty()) return EZKL_OK;
+    EZ_CTX(c);
+    if (c != p->ctx) return EZKL_ERR_INVALID;
+    hipStream_t st = pick_stream(c, stream);
+    hipEvent_t e0, e1;
+    int rc = ev_pair(c, "witness_outputs", &e0, &e1);
+    if (rc) return rc;
+    EZ_HIP(hipEventRecord(e0, st));
+    hipLaunchKernelGGL(wit_gather_kernel, dim3(cdiv(h.outputs.size(), 64)), dim3(64), 0, st, cols, h.k, p->outputs, (uint32_t)h.outputs.size(), p->outs);
+    EZ_HIP(hipGetLastError());
+    EZ_HIP(hipEventRecord(e1, st));
+    EZ_HIP(hipMemcpyAsync(outputs_host, p->outs, h.outputs.size() * 32, hipMemcpyDeviceToHost, st));
+    EZ_HIP(hipStreamSynchronize(st));
+    return EZKL_OK;
+}
+
 int ezkl_hip_witness_tile_dev(void* const* advice_cols_dev, uint32_t n_advice, uint32_t k, uint32_t unit_rows, uint32_t tiles, const uint32_t* dst_cols,
                               const uint32_t* src_cols, uint32_t n_pairs, void* stream) {
     if (!advice_cols_dev || n_advice == 0 || n_advice > MAX_ADVICE || k < 1 || k > 28 || (n_pairs && (!dst_cols || !src_cols))) return EZKL_ERR_INVALID;

@@ -26,8 +26,22 @@ Three more families are read as JSON descriptions, chosen by "model" through the
     {"model": "norm", "run_args": {...}, "rows", "length", "input_scale", "output_scale", "eps", "layer_norm", "lookup_range", "capacity"}   -> NormCircuit
 with run_args = logrows, num_inner_cols, decomp_base, decomp_legs and optionally input_scale / output_scale (the witness file's scales,
 default 0); private input, private parameters and public output only -- any other visibility is refused by name, a malformed field by a
-ValueError that names it.  setup, gen_witness, mock, prove, verify and Prover treat them as they treat the MLP.  The einsum and the
-transformer surrogate (two-phase plans) and the SortTopk / SumProd / ScatterGather circuits have no description: "unsupported compiled circuit".
+ValueError that names it.  setup, gen_witness, mock, prove, verify and Prover treat them as they treat the MLP.
+Two families have SECOND-PHASE advice -- their matmuls are Freivalds einsums over the circuit's own configuration, two challenges -- and
+live in the table PHASED_FAMILIES:
+    {"model": "mlp_batch", "run_args": {logrows, num_inner_cols, decomp_base, decomp_legs[, input_scale, param_scale]}, "batch": m, "weights", "biases",
+     ["rebase", "output_scale", "relu_last", "relu_first", "capacity"]}      -> ezkl_layout.BatchMlpCircuit: the MLP description on m >= 2 input rows (ezkl's batch_size;
+                                                                                the scales and the rebase divisors follow the MLP description's rules)
+    {"model": "attention", "run_args": {...}, "n", "e", "d", "capacity", "input_scale", "output_scale", "eps", "score_div", "lookup_range", "Wq", "Wk", "Wv"}
+                                                                             -> AttentionHeadCircuit
+A circuit is phased when its constraint system has advice beyond phase 0 (_phased), and every entry point then takes one path for
+both: setup writes a two-phase witness plan next to the key; gen_witness runs the layout's first phase, or replays phase 0 of the plan
+and gathers the outputs (ezkl_hip_witness_outputs_dev) -- the outputs and every static lookup live in phase 0; mock, prove and Prover
+hand native.mock / native.create_proof a callable advice(phase, challenges), which on the device keeps the phase-0 columns as they
+are and replays phase p > 0 with the prover's challenges into the session's one resident column set; verify is host only, as ever.
+Both take num_inner_cols = 1: the einsum layout places one entry a row.
+The standalone einsum and the transformer surrogate, the SortTopk / SumProd / ScatterGather circuits and sharded / group proving have
+no description: "unsupported compiled circuit".
 Errors surface as exceptions with the reference's wording where it has one."""
 import collections
 import json
@@ -51,8 +65,8 @@ def _read_compiled(path, any_visibility=False):
     raw = open(path, "rb").read()
     if raw[:1] == b"{":
         j = json.loads(raw)
-        family = FAMILIES.get(j.get("model")) if isinstance(j.get("model"), str) else None
-        if family is None:                                                           # (the einsum and the surrogate among them: two-phase plans have no file-level loader)
+        family = _family(j.get("model"))
+        if family is None:                                                           # (the standalone einsum and the surrogate among them)
             raise ValueError("unsupported compiled circuit: %r" % j.get("model"))
         return dict(family.describe(j), family=j["model"]), j
     c = codecs.read_compiled_circuit(raw)
@@ -120,11 +134,10 @@ def _range_field(j, name):
     return (v[0], v[1])
 
 
-def _describe_layout(j, fields, n_inputs):
-    """what the conv, pool_classifier and norm descriptions share: run_args (logrows, num_inner_cols, decomp_base, decomp_legs; input_scale
-    and output_scale are the witness file's scales, default 0), private input, private parameters and a public output -- any other
-    visibility is refused by name --, and the family's own fields, each read by its reader; n_inputs(fields): the length of the input vector.
-    -> plain data; "fields": the circuit's arguments"""
+def _run_args(j):
+    """the run_args of a JSON description that states its layout: logrows, num_inner_cols, decomp_base and decomp_legs as checked
+    integers over the object as it stands; private input, private parameters and a public output -- any other visibility is refused by
+    name"""
     ra = j.get("run_args")
     if not isinstance(ra, dict):
         raise ValueError("compiled circuit: \"run_args\" must be an object")
@@ -135,9 +148,18 @@ def _describe_layout(j, fields, n_inputs):
             raise ValueError("unsupported visibility: %s is %s (the %s family takes a private input, private parameters and a public output)"
                              % (what, named, j["model"]))
     run = {name: _int_field(ra, name, least, prefix="run_args.") for name, least in (("logrows", 1), ("num_inner_cols", 1), ("decomp_base", 2), ("decomp_legs", 1))}
+    return dict(ra, **run)
+
+
+def _describe_layout(j, fields, n_inputs):
+    """what the conv, pool_classifier and norm descriptions share: run_args (logrows, num_inner_cols, decomp_base, decomp_legs; input_scale
+    and output_scale are the witness file's scales, default 0), private input, private parameters and a public output -- any other
+    visibility is refused by name --, and the family's own fields, each read by its reader; n_inputs(fields): the length of the input vector.
+    -> plain data; "fields": the circuit's arguments"""
+    ra = _run_args(j)
     in_scale, out_scale = (_int_field(ra, name, default=0, prefix="run_args.") for name in ("input_scale", "output_scale"))
     f = {name: read(j, name) for name, read in fields}
-    return dict(run_args=dict(ra, **run), settings=None, in_scale=in_scale, out_scale=out_scale, datum_type="F32", n_inputs=n_inputs(f),
+    return dict(run_args=ra, settings=None, in_scale=in_scale, out_scale=out_scale, datum_type="F32", n_inputs=n_inputs(f),
                 visibility=dict(input="Private", params="Private", output="Public"), fields=f)
 
 
@@ -218,11 +240,75 @@ def _build_norm(d):
         ra["decomp_base"], ra["decomp_legs"], f["lookup_range"]))
 
 
+_ATTENTION_WEIGHTS = ("Wq", "Wk", "Wv")
+_ATTENTION_FIELDS = [(name, _positive) for name in ("n", "e", "d", "capacity", "input_scale", "output_scale", "score_div")] + \
+                    [("eps", _eps_field), ("lookup_range", _range_field)] + [(name, _parameter_field) for name in _ATTENTION_WEIGHTS]
+
+
+def _one_inner_column(d, model):
+    """the einsum layout's own rule, named as a field: a wider block folds num_inner_cols entries a row in its RLC gate, which neither
+    ezkl_layout.EinsumCircuit lays out nor a witness plan's RLC record states"""
+    if d["run_args"]["num_inner_cols"] != 1:
+        raise ValueError("compiled circuit: \"run_args.num_inner_cols\" must be 1 in the \"%s\" family: %s" % (model, EL.EINSUM_WIDTH_ERROR))
+
+
+def _build_attention(d):
+    ra, f = d["run_args"], d["fields"]
+    _one_inner_column(d, "attention")
+    return _configured("attention", lambda: EL.AttentionHeadCircuit(
+        ra["logrows"], f["n"], f["e"], f["d"], f["capacity"], ra["num_inner_cols"], f["input_scale"], f["output_scale"], f["eps"], f["score_div"],
+        ra["decomp_base"], ra["decomp_legs"], f["lookup_range"], **{name: f[name] for name in _ATTENTION_WEIGHTS}))
+
+
+def _integer_rows(j, name, depth):
+    """the field `name`: a non-empty list, nested `depth` deep, of int64 integers (rows of one level may differ in length: the circuit's
+    constructor holds the shapes together); anything else is a ValueError naming the field"""
+    def ok(v, depth):
+        if depth == 0:
+            return not isinstance(v, bool) and isinstance(v, int) and -(1 << 63) <= v < 1 << 63
+        return isinstance(v, list) and len(v) > 0 and all(ok(x, depth - 1) for x in v)
+    if name not in j:
+        raise ValueError("compiled circuit: \"%s\" is missing" % name)
+    if not ok(j[name], depth):
+        raise ValueError("compiled circuit: \"%s\" must be a non-empty list, nested %d deep, of integers that fit int64" % (name, depth))
+    return j[name]
+
+
+def _describe_mlp_batch(j):
+    """{"model": "mlp_batch", ...} as plain data: the MLP description's fields, read by _describe_mlp -- its rules for the scales and
+    the rebase divisors hold --, on a batch of "batch" input rows"""
+    ra = _run_args(j)
+    m = _int_field(j, "batch", 1)
+    weights, biases = _integer_rows(j, "weights", 3), _integer_rows(j, "biases", 2)
+    if len(biases) != len(weights):
+        raise ValueError("compiled circuit: \"biases\" takes one vector per matrix of \"weights\"")
+    for name in ("relu_last", "relu_first"):
+        if name in j:
+            _bool_field(j, name)
+    for name in ("input_scale", "param_scale"):
+        if name in ra:
+            _int_field(ra, name, prefix="run_args.")
+    if "rebase" in j and j["rebase"] is not None and (not isinstance(j["rebase"], list) or any(isinstance(v, bool) or not isinstance(v, int) for v in j["rebase"])):
+        raise ValueError("compiled circuit: \"rebase\" takes one divisor in [1, 2^32) per layer")
+    if "output_scale" in j:
+        _int_field(j, "output_scale")
+    d = _describe_mlp(dict(j, run_args=ra))
+    return dict(d, batch=m, n_inputs=m * len(weights[0][0]), capacity=_optional(_positive)(j, "capacity"))
+
+
+def _build_mlp_batch(d):
+    ra = d["run_args"]
+    _one_inner_column(d, "mlp_batch")
+    return _configured("mlp_batch", lambda: EL.BatchMlpCircuit(
+        ra["logrows"], ra["num_inner_cols"], d["batch"], d["weights"], d["biases"], ra["decomp_base"], ra["decomp_legs"], capacity=d["capacity"],
+        relu_last=d["relu_last"], relu_first=d["relu_first"], rebase=d["rebase"]))
+
+
 def _forward_layout(d, x):
     """gen_witness on the host for a circuit that states its `layout`: its own synthesis, the outputs it ties to the instance column and
     the statistics the layout kept.  What the layout asserts of a witness (a lookup input outside its table, a value beyond the
     decomposition range) is a ValueError with the layout's words."""
-    circuit = FAMILIES[d["family"]].build(d)
+    circuit = _family(d["family"]).build(d)
     try:
         reg = circuit.synthesize(x, witness=True)
     except AssertionError as e:
@@ -270,8 +356,8 @@ def _forward_mlp(d, x):
 
 
 # THE families a JSON description may name: how its fields are read, how the circuit is built from them, and gen_witness's forward pass on
-# the host.  (The reference's own model.compiled is the MLP family's.)  The einsum and the transformer surrogate -- two-phase plans -- and
-# the SortTopk, SumProd and ScatterGather circuits are not here: naming one is "unsupported compiled circuit".
+# the host.  (The reference's own model.compiled is the MLP family's.)  The standalone einsum, the transformer surrogate and the SortTopk,
+# SumProd and ScatterGather circuits are in neither table: naming one is "unsupported compiled circuit".
 Family = collections.namedtuple("Family", "describe build forward")
 FAMILIES = {
     "mlp": Family(_describe_mlp, _build_mlp, _forward_mlp),
@@ -279,11 +365,23 @@ FAMILIES = {
     "pool_classifier": Family(lambda j: _describe_layout(j, _POOL_FIELDS, lambda f: f["image"] ** 2), _build_pool, _forward_layout),
     "norm": Family(lambda j: _describe_layout(j, _NORM_FIELDS, lambda f: f["rows"] * f["length"]), _build_norm, _forward_layout),
 }
+# the families whose circuits lay Freivalds einsums over their own configuration -- second-phase advice, two-phase plans (_phased) --,
+# read, built and run as the ones above are (`_family` looks a name up in both tables); the host forward pass is the layout's first phase
+PHASED_FAMILIES = {
+    "mlp_batch": Family(_describe_mlp_batch, _build_mlp_batch, _forward_layout),
+    "attention": Family(lambda j: _describe_layout(j, _ATTENTION_FIELDS, lambda f: f["n"] * f["e"]), _build_attention, _forward_layout),
+}
+
+
+def _family(name):
+    """the Family a description's "model" names, or None"""
+    return (FAMILIES.get(name) or PHASED_FAMILIES.get(name)) if isinstance(name, str) else None
 
 
 def describe(circuit, input_scale=0, output_scale=0):
-    """the JSON description (a dict) of a ConvMnistCircuit, a PoolClassifierCircuit or a NormCircuit: what `_load_circuit` builds the same
-    circuit from -- same plan_identity, same settings"""
+    """the JSON description (a dict) of a ConvMnistCircuit, a PoolClassifierCircuit, a NormCircuit, an AttentionHeadCircuit or a
+    BatchMlpCircuit: what `_load_circuit` builds the same circuit from -- same plan_identity, same settings.  (A BatchMlpCircuit that
+    rescales nothing is at scale 0, as the MLP description is: input_scale and output_scale go with its rebase divisors.)"""
     ra = dict(logrows=circuit.k, num_inner_cols=circuit.w, decomp_base=circuit.base, decomp_legs=circuit.legs, input_scale=input_scale, output_scale=output_scale)
     params = lambda: {name: np.asarray(getattr(circuit, name)).tolist() for name in _PARAMETER_ARRAYS}
     if type(circuit) is EL.ConvMnistCircuit:
@@ -295,13 +393,22 @@ def describe(circuit, input_scale=0, output_scale=0):
     if type(circuit) is EL.NormCircuit:
         return dict(model="norm", run_args=ra, rows=circuit.rows, length=circuit.length, input_scale=circuit.input_scale, output_scale=circuit.output_scale,
                     eps=circuit.eps, layer_norm=circuit.layer_norm, lookup_range=list(circuit.lookup_range), capacity=circuit.capacity)
+    if type(circuit) is EL.AttentionHeadCircuit:
+        return dict(model="attention", run_args=ra, n=circuit.n, e=circuit.e, d=circuit.d, capacity=circuit.capacity, input_scale=circuit.input_scale,
+                    output_scale=circuit.output_scale, eps=circuit.eps, score_div=circuit.score_div, lookup_range=list(circuit.lookup_range),
+                    **{name: np.asarray(getattr(circuit, name)).tolist() for name in _ATTENTION_WEIGHTS})
+    if type(circuit) is EL.BatchMlpCircuit:                                       # _describe_mlp's rules: the scales go with the rebase divisors
+        ra = {name: v for name, v in ra.items() if name != "output_scale"}
+        scaled = dict(rebase=list(circuit.rebase), output_scale=output_scale) if any(d != 1 for d in circuit.rebase) else {}
+        return dict(model="mlp_batch", run_args=ra, batch=circuit.m, weights=circuit.weights, biases=circuit.biases, relu_last=circuit.relu_last,
+                    relu_first=circuit.relu_first, capacity=circuit.capacity, **scaled)
     raise ValueError("no JSON description for a %s" % type(circuit).__name__)
 
 
 def _load_circuit(path):
     """the compiled circuit (_read_compiled) as the circuit of its family (FAMILIES) -> (circuit, the parsed file)"""
     d, parsed = _read_compiled(path)
-    return FAMILIES[d["family"]].build(d), parsed
+    return _family(d["family"]).build(d), parsed
 
 
 def _mlp_of_graph(model, any_visibility=False):
@@ -583,21 +690,65 @@ def _quantize(v, scale, datum_type):
     return _rust_round(mult * x)
 
 
+def _phased(circuit):
+    """whether the circuit's constraint system has advice beyond phase 0 (Freivalds einsums over its own configuration): its witness is
+    made phase by phase, between the prover's commit stages, with the challenges squeezed so far"""
+    return any(c.phase != 0 for c in circuit.gc.cs.advice)
+
+
+def _first_phase(plan, x, columns=None):
+    """what comes before the first commitment, on the device: phase 0 of the plan and the outputs, which live in it -> (columns,
+    outputs).  A one-phase plan: its one-call run.  A plan with phases gathers its outputs with its LAST phase only, so they are taken
+    by backend.WitnessPlan.outputs -- one more launch and one copy.  A witness the device refuses raises backend.WitnessError."""
+    if plan.n_phases == 1:
+        return plan.run(x, columns=columns)
+    cols, _ = plan.run(x, columns=columns, phase=0)
+    try:
+        return cols, plan.outputs(cols)
+    except BaseException:
+        if columns is None:
+            for c in cols:
+                c.free()
+        raise
+
+
+def _host_advice(circuit, x, region=None):
+    """the advice(phase, challenges) callable of native.create_proof and native.mock over the HOST layout of a phased circuit: phase 0 is
+    `region` (the first-phase synthesis the caller already has, else made here), phase p > 0 the layout laid again with the challenges
+    squeezed so far.  -> (the callable, columns: {column index: list of ints}, filled as the phases are asked for)"""
+    cs0, n = circuit.gc.cs, 1 << circuit.k
+    first, columns = [region], {}
+    def advice(phase, challenges):
+        if phase == 0:
+            first[0] = reg = first[0] if first[0] is not None else circuit.synthesize(x, True)
+        else:
+            reg = circuit.synthesize(x, True, tuple(challenges[:len(cs0.challenges)]))
+        idx = [c.index for c in cs0.advice if c.phase == phase]
+        cols = [reg.advice.get(i) or [0] * n for i in idx]
+        columns.update(zip(idx, cols))
+        return dict(zip(idx, EL.cols_to_mont(cols, B)))
+    return advice, columns
+
+
 def _forward_device(d, x, mode, pk_path):
     """gen_witness's forward pass on the device, for every family: the circuit's witness plan -- the `.wplan` next to pk_path where one is
     given and is this circuit's, else a fresh recording -- uploaded and replayed, the outputs read back, the lookup statistics by
-    ezkl_hip_witness_lookup_stats_dev over the replayed cells.  -> (outputs, (min, max), max_range_size), or None when mode is "auto" and
+    ezkl_hip_witness_lookup_stats_dev over the replayed cells.  Of a plan with phases only phase 0 is replayed (_first_phase): the
+    outputs and every static lookup live in it, and a plan that has a nonlinearity record in a later phase is refused before the replay.  -> (outputs, (min, max), max_range_size), or None when mode is "auto" and
     the device path is not to be taken (_open_plan, or an input that does not fit int64); mode "device" raises instead.  A witness the
     device refuses raises backend.WitnessError, a ValueError with the layout's words."""
     if not _fits_plan(x, mode):
         return None
-    circuit = FAMILIES[d["family"]].build(d)
+    circuit = _family(d["family"]).build(d)
     dev = _open_plan(circuit, pk_path, mode)
     if dev is None:
         return None
     cols = None
     try:
-        cols, outs = dev.run(x)
+        late = [p for p in dev.lookup_phases if p > 0]
+        if late:                                         # the statistics kernel reads the sources of every such record, in all phases
+            raise ValueError("gen_witness: the plan has a nonlinearity record in phase %d; only phase 0 is replayed for a witness file" % late[0])
+        cols, outs = _first_phase(dev, x)
         stats = dev.lookup_stats(cols)
     finally:
         for c in cols or []:
@@ -646,7 +797,7 @@ def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None
     x = [EL.signed(v % EL.R) for v in x]
     inputs = list(x)
     made = _forward_device(d, x, synthesis, pk_path) if synthesis != "host" else None
-    outputs, (min_lookup, max_lookup), max_range_size = made if made is not None else FAMILIES[d["family"]].forward(d, x)
+    outputs, (min_lookup, max_lookup), max_range_size = made if made is not None else _family(d["family"]).forward(d, x)
     weights, biases = d.get("weights"), d.get("biases")                         # (what a KZGCommit of the parameters commits to: the MLP family's)
     processed = dict(input=None, params=None, output=None)
     if any(v == "KZGCommit" for v in vis.values()):
@@ -853,7 +1004,9 @@ class Prover:
         """one proof of this session's circuit: GraphWitness file -> proof bytes (written as proof.json to proof_path when one is given).
         seed, check_mode and what report receives are `prove`'s below; report["stages"] adds the wall seconds of each stage of this call
         (witness_read, synthesis, [host_columns,] create_proof, [proof_write]) and report["create_proof_breakdown"] the prover's own
-        split of create_proof."""
+        split of create_proof.  A circuit with second-phase advice (_phased) is proved through a callable: "synthesis" is then its first
+        phase and the outputs, the later phases run inside create_proof -- on the device by the plan's replay with the prover's
+        challenges, report["phase_ms"] = {phase: device milliseconds}; with synthesis="host" by the layout laid again."""
         import time
         if not self._open:
             raise RuntimeError("this Prover is closed")
@@ -868,10 +1021,24 @@ class Prover:
         w, x = _witness if _witness is not None else _read_witness(circuit, witness_path, self.synthesis)      # (`prove` has read it already)
         stage("witness_read")
         on_device = self.plan is not None and _fits_plan(x, self.synthesis)                 # "auto": wider inputs take the host layout
+        phased, advice, resident = _phased(circuit), None, ()
         if on_device:
-            _, outs = self.plan.run(x, columns=self._cols)                      # into the session's columns, whatever they held
+            _, outs = _first_phase(self.plan, x, columns=self._cols)            # into the session's columns, whatever they held
             adv, inst = self._cols, [outs]
             how = dict(self.plan.last, path="device")
+            if phased:                                                          # the columns of phase 0 as they are; phase p > 0 replayed with the prover's challenges
+                plan, cols, phase_ms = self.plan, self._cols, {0: self.plan.last["device_ms"]}
+                how["phase_ms"] = phase_ms
+                def advice(phase, challenges):
+                    if phase > 0:
+                        plan.run(x, columns=cols, phase=phase, challenges=list(challenges))
+                        phase_ms[phase] = plan.last["device_ms"]
+                    return {c: cols[c] for c in range(plan.n_advice) if plan.column_phase[c] == phase}
+                resident = range(plan.n_advice)
+        elif phased:
+            reg = circuit.synthesize(x, True)                                   # the first phase: the outputs live in it
+            inst, how = [list(circuit.outputs)], dict(path="host")
+            advice, _ = _host_advice(circuit, x, reg)
         else:
             adv, inst = circuit.witness(x)                                      # GraphCircuit::synthesize
             how = dict(path="host")
@@ -882,12 +1049,12 @@ class Prover:
             report["stages"] = stages
         if w["outputs"] and inst != w["outputs"]:
             raise ValueError("the witness file's outputs do not match the circuit's outputs")
-        if not on_device:
+        if not on_device and not phased:
             adv = EL.cols_to_mont(adv, B)
             stage("host_columns")
         tm = {}
-        proof = NV.create_proof(self.pk, self.bg, self.bgl, adv, seed=seed, instances=inst, check_mode=check_mode, g2=self.g2, s_g2=self.s_g2,
-                                timings=tm)
+        proof = NV.create_proof(self.pk, self.bg, self.bgl, advice if phased else adv, seed=seed, instances=inst, check_mode=check_mode, g2=self.g2,
+                                s_g2=self.s_g2, timings=tm, device_columns=resident)
         stage("create_proof")
         if report is not None:
             report["create_proof_breakdown"] = tm
@@ -1021,15 +1188,24 @@ def mock(witness_path, compiled_circuit):
     """`ezkl mock` (/root/reference/src/execute.rs:1280-1305: MockProver::run(logrows, &circuit, public_inputs).verify()) on the GPU: the
     witness is laid out by the synthesis `prove` uses and every gate, lookup and copy constraint is checked row by row
     (native.mock -> ezkl_prover_mock).  No SRS, no keys.  The public inputs are the witness file's outputs (prepare_public_inputs), so a
-    wrong output is a failing copy into the instance column.  Returns "" when every constraint holds; raises MockError otherwise, its message
+    wrong output is a failing copy into the instance column.  A circuit with second-phase advice is laid out once per phase, at the challenges
+    the mock prover draws (_host_advice).  Returns "" when every constraint holds; raises MockError otherwise, its message
     naming the first failures (gate / row, lookup / input / row, the two cells of a copy)."""
     w = codecs.read_witness_json(open(witness_path).read())
     circuit, j = _load_circuit(compiled_circuit)
     w, x = _read_witness(circuit, witness_path, "host", w)
-    adv, inst = circuit.witness(x)                                              # GraphCircuit::synthesize
-    public = [list(c) for c in w["outputs"]] if w["outputs"] else inst
+    if _phased(circuit):                                                        # one layout pass per phase, at the challenges the mock prover draws
+        advice, by_index = _host_advice(circuit, x)
+        advice(0, [])                                                           # the first phase, kept for the mock prover's call: the outputs live in it
+        adv, inst = None, [list(circuit.outputs)]
+    else:
+        adv, inst = circuit.witness(x)                                          # GraphCircuit::synthesize
     cs, fixed, copies, _ = _fresh_keygen_inputs(circuit)
-    records, totals = NV.mock(cs, EL.cols_to_mont(fixed, B), copies, EL.cols_to_mont(adv, B), instances=public, seed=1, cap=MOCK_CAP)
+    public = [list(c) for c in w["outputs"]] if w["outputs"] else inst
+    records, totals = NV.mock(cs, EL.cols_to_mont(fixed, B), copies, advice if adv is None else EL.cols_to_mont(adv, B), instances=public, seed=1,
+                              cap=MOCK_CAP)
+    if adv is None:
+        adv = [by_index.get(c) or [0] * cs.n for c in range(cs.n_advice)]
     if not any(totals):
         return ""
     cols = {"adv": adv, "fix": fixed, "inst": [list(c) + [0] * (cs.n - len(c)) for c in public]}

@@ -1502,6 +1502,11 @@ class LayoutCircuit:
         return adv, [self.outputs]
 
 
+def _decomposition_cells(m, w, legs):
+    """the cells `decompose` places for m values: hints, the two range checks, the recomposing dots, MULT by the sign, the equality"""
+    return m * (legs + 1) + m + m * legs + m * (-(-legs // w) * w) + 2 * m
+
+
 class MlpCircuit(LayoutCircuit):
     """`layers` x (Gemm + bias + ReLU) on one input vector, the op sequence of the reference's fixture model
     (tests/assets/network.onnx: Gemm 3 -> 4 + ReLU) and of examples/onnx/large_mlp/gen.py:6-43 (9 x Linear(100, 100) + ReLU; with
@@ -1535,7 +1540,7 @@ class MlpCircuit(LayoutCircuit):
 
     def _count_cells(self):
         w, lg = self.w, self.legs
-        def dec(m): return m * (lg + 1) + m + m * lg + m * (-(-lg // w) * w) + 2 * m
+        def dec(m): return _decomposition_cells(m, w, lg)
         def al(c): return -(-c // w) * w
         c = dec(self.n_inputs)
         if self.relu_first:
@@ -2302,7 +2307,6 @@ class _DeviceSurrogateWitness:
         from . import witness_plan as WP
         self.gpu, self.inputs, self.U, self.T, self.k = gpu, list(inputs), U, T, circuit.k
         host_plan = WP.record_plan(circuit)
-        self.out_cells = [int(c) for c in host_plan.outputs]
         self.plan = gpu.WitnessPlan(host_plan.to_bytes())
         self.columns = self.plan.alloc_columns()
         # the columns the plan writes are tiled onto themselves and, those of block 0, into their blocks; the run of a phase zero-fills every
@@ -2329,10 +2333,9 @@ class _DeviceSurrogateWitness:
         self.inputs = [int(v) for v in inputs]
 
     def read_outputs(self):
-        """the circuit's outputs as canonical ints, read where phase 0 wrote them (the plan gathers them with its last phase)"""
-        M_inv = pow(1 << 256, -1, R)
-        words = [self.columns[c >> self.k].words(c & ((1 << self.k) - 1)) for c in self.out_cells]
-        return [int.from_bytes(w.tobytes(), "little") * M_inv % R for w in words]
+        """the circuit's outputs as canonical ints, gathered where phase 0 wrote them: one launch and one copy
+        (backend.WitnessPlan.outputs; `run` hands them back with the plan's last phase only)"""
+        return self.plan.outputs(self.columns)
 
     def free(self):
         for c in self.columns:
@@ -2341,68 +2344,11 @@ class _DeviceSurrogateWitness:
         self.plan.free()
 
 
-class AttentionHeadCircuit(LayoutCircuit):
-    """One attention head over `n` tokens, every matmul a Freivalds einsum over the circuit's own configuration (layouts.rs:826 `einsum`,
-    BaseRegion.einsum) -- the path the matmuls of a transformer graph take to the prover.  X (n x e) is the private model input, Wq, Wk,
-    Wv (e x d) are parameters: Q, K, V = einsum("ie,ed->id"); S = einsum("id,jd->ij", Q, K), `div` by `score_div`, `softmax_axes` over the
-    rows (the pieces of NormCircuit: max by sort, the exp table, sum, the claimed reciprocal, MULT -- outputs at input_scale *
-    output_scale); O = einsum("ij,jd->id", P, V), `div` by input_scale * output_scale, range-checked and tied to the instance column.
-    From the second einsum on the operands are cells the circuit computed.  The op sequence is stated once (`layout`).  The defaults keep
-    the scores inside the exp table for entries of X in [-4, 4] and of the weights in [-2, 2] (`default_inputs`, the seeded weights);
-    another input that leaves it is refused by the layout's own assertion."""
-
-    def __init__(self, logrows, n, e, d, capacity, num_inner_cols=1, input_scale=8, output_scale=64, eps=1.0 / 128, score_div=None,
-                 decomp_base=128, decomp_legs=2, lookup_range=(-255, 0), seed=1):
-        from . import einsum_plan as EP
-        self.k, self.w, self.n, self.e, self.d, self.capacity = logrows, num_inner_cols, int(n), int(e), int(d), capacity
-        self.n_inputs = self.n * self.e
-        self.input_scale, self.output_scale, self.eps = int(input_scale), int(output_scale), float(eps)
-        self.score_div = int(score_div) if score_div is not None else max(1, math.ceil(self.e * math.sqrt(self.d)))
-        self.out_div = self.input_scale * self.output_scale
-        self.base, self.legs, self.lookup_range, self.seed = decomp_base, decomp_legs, tuple(lookup_range), seed
-        assert abs(zero_recip(self.output_scale, self.eps)) < decomp_base ** decomp_legs
-        scale = self.input_scale
-        self.exp = lambda x: int(math.floor(scale * math.exp(x / scale) + 0.5))         # LookupOp::Exp { scale, base: e } (ops.rs `exp`)
-        self.equations = [("ie,ed->id", dict(i=self.n, e=self.e, d=self.d))] * 3 + [("id,jd->ij", dict(i=self.n, j=self.n, d=self.d)),
-                                                                                   ("ij,jd->id", dict(i=self.n, j=self.n, d=self.d))]
-        analyses = [EP.einsum_analysis(eq, dims) for eq, dims in self.equations]
-        self.settings = EC.GraphSettings(logrows, num_inner_cols, capacity, total_const_size=16,
-                                         required_range_checks=[(-1, 1), (0, decomp_base - 1), (0, 1)], required_lookups=[("exp", self.exp)],
-                                         lookup_range=self.lookup_range, model_instance_shapes=[[self.n, self.d]],
-                                         total_shuffle_col_size=self.n * self.n, num_shuffles=1,
-                                         einsum_reduction_length=sum(a.reduction_length for a in analyses), einsum_max_output_axes=2)
-        self.gc = EC.GraphConfig(self.settings)
-        self.eins = [EinsumCircuit.over(self.gc, eq, dims) for eq, dims in self.equations]
-        rng = np.random.default_rng(seed)
-        self.Wq, self.Wk, self.Wv = (rng.integers(-2, 3, (self.e, self.d)) for _ in range(3))
-        self.x = rng.integers(-4, 5, (self.n, self.e))
-
-    def default_inputs(self):
-        return [int(v) for v in self.x.reshape(-1)]
-
-    def layout(self, reg, inputs, param, challenges=None):
-        """inputs: X row-major as `n_inputs` Vals; param(v) -> the Val of a circuit parameter (asked for in the order Wq, Wk, Wv, row-major);
-        challenges: None lays the first phase (as the witness-plan recorder does, on symbols), else the two challenges: everything"""
-        reg.decomp = (self.base, self.legs)
-        n, d = self.n, self.d
-        x = reg.assign(reg.inputs[0], inputs)                                        # placed once: the three projections read the same cells
-        reg.increment(len(x))
-        Wq, Wk, Wv = ([param(int(v)) for v in W.reshape(-1)] for W in (self.Wq, self.Wk, self.Wv))
-        Q, K, V = (reg.einsum(ein, x, W, challenges) for ein, W in zip(self.eins[:3], (Wq, Wk, Wv)))
-        S = reg.div(reg.einsum(self.eins[3], Q, K, challenges), self.score_div)
-        P_ = reg.softmax_axes([S[i * n:(i + 1) * n] for i in range(n)], self.input_scale, self.output_scale, self.eps)
-        O = reg.div(reg.einsum(self.eins[4], [v for row in P_ for v in row], V, challenges), self.out_div)
-        return reg.output_equals_instance(O, self.gc.instance, 0, self.base, self.legs)
-
-    def plan_identity(self):
-        shape = [self.k, self.w, self.n, self.e, self.d, self.input_scale, self.output_scale, self.score_div, self.base, self.legs,
-                 self.lookup_range[0], self.lookup_range[1], self.gc.advices[0].num_blocks()]
-        return b"".join(np.asarray(a, np.int64).tobytes() for a in (shape, self.Wq, self.Wk, self.Wv)) + np.float64(self.eps).tobytes()
-
-    def fresh(self):
-        """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
-        return AttentionHeadCircuit(self.k, self.n, self.e, self.d, self.capacity, self.w, self.input_scale, self.output_scale, self.eps,
-                                    self.score_div, self.base, self.legs, self.lookup_range, self.seed)
+class PhasedLayoutCircuit(LayoutCircuit):
+    """what the circuits share that lay Freivalds einsums over their own configuration (`BaseRegion.einsum`) and so have second-phase
+    advice: `layout(reg, inputs, param, challenges=None) -> outputs` states the op sequence, `synthesize` runs it for one phase or for
+    both, `build` gives keygen's and create_proof's inputs with a per-phase advice callable, on the host or from the witness plan.
+    Subclasses give `layout`, `n_inputs`, `default_inputs()`, `plan_identity()` and `fresh()`."""
 
     def synthesize(self, x, witness=True, challenges=None):
         assert len(x) == self.n_inputs
@@ -2448,6 +2394,172 @@ class AttentionHeadCircuit(LayoutCircuit):
                 dev.free()
                 raise
         return out
+
+
+class AttentionHeadCircuit(PhasedLayoutCircuit):
+    """One attention head over `n` tokens, every matmul a Freivalds einsum over the circuit's own configuration (layouts.rs:826 `einsum`,
+    BaseRegion.einsum) -- the path the matmuls of a transformer graph take to the prover.  X (n x e) is the private model input, Wq, Wk,
+    Wv (e x d) are parameters: Q, K, V = einsum("ie,ed->id"); S = einsum("id,jd->ij", Q, K), `div` by `score_div`, `softmax_axes` over the
+    rows (the pieces of NormCircuit: max by sort, the exp table, sum, the claimed reciprocal, MULT -- outputs at input_scale *
+    output_scale); O = einsum("ij,jd->id", P, V), `div` by input_scale * output_scale, range-checked and tied to the instance column.
+    From the second einsum on the operands are cells the circuit computed.  The op sequence is stated once (`layout`).  The defaults keep
+    the scores inside the exp table for entries of X in [-4, 4] and of the weights in [-2, 2] (`default_inputs`, the seeded weights);
+    another input that leaves it is refused by the layout's own assertion."""
+
+    def __init__(self, logrows, n, e, d, capacity, num_inner_cols=1, input_scale=8, output_scale=64, eps=1.0 / 128, score_div=None,
+                 decomp_base=128, decomp_legs=2, lookup_range=(-255, 0), seed=1, Wq=None, Wk=None, Wv=None):
+        """Wq, Wk, Wv: e x d integer matrices in place of the seeded ones (None: keep the seeded one)"""
+        from . import einsum_plan as EP
+        self.k, self.w, self.n, self.e, self.d, self.capacity = logrows, num_inner_cols, int(n), int(e), int(d), capacity
+        self.n_inputs = self.n * self.e
+        self.input_scale, self.output_scale, self.eps = int(input_scale), int(output_scale), float(eps)
+        self.score_div = int(score_div) if score_div is not None else max(1, math.ceil(self.e * math.sqrt(self.d)))
+        self.out_div = self.input_scale * self.output_scale
+        self.base, self.legs, self.lookup_range, self.seed = decomp_base, decomp_legs, tuple(lookup_range), seed
+        assert abs(zero_recip(self.output_scale, self.eps)) < decomp_base ** decomp_legs
+        scale = self.input_scale
+        self.exp = lambda x: int(math.floor(scale * math.exp(x / scale) + 0.5))         # LookupOp::Exp { scale, base: e } (ops.rs `exp`)
+        self.equations = [("ie,ed->id", dict(i=self.n, e=self.e, d=self.d))] * 3 + [("id,jd->ij", dict(i=self.n, j=self.n, d=self.d)),
+                                                                                   ("ij,jd->id", dict(i=self.n, j=self.n, d=self.d))]
+        analyses = [EP.einsum_analysis(eq, dims) for eq, dims in self.equations]
+        self.settings = EC.GraphSettings(logrows, num_inner_cols, capacity, total_const_size=16,
+                                         required_range_checks=[(-1, 1), (0, decomp_base - 1), (0, 1)], required_lookups=[("exp", self.exp)],
+                                         lookup_range=self.lookup_range, model_instance_shapes=[[self.n, self.d]],
+                                         total_shuffle_col_size=self.n * self.n, num_shuffles=1,
+                                         einsum_reduction_length=sum(a.reduction_length for a in analyses), einsum_max_output_axes=2)
+        self.gc = EC.GraphConfig(self.settings)
+        self.eins = [EinsumCircuit.over(self.gc, eq, dims) for eq, dims in self.equations]
+        rng = np.random.default_rng(seed)
+        self.Wq, self.Wk, self.Wv = (rng.integers(-2, 3, (self.e, self.d)) for _ in range(3))
+        self.x = rng.integers(-4, 5, (self.n, self.e))
+        _given_parameters(self, Wq=Wq, Wk=Wk, Wv=Wv)
+
+    def default_inputs(self):
+        return [int(v) for v in self.x.reshape(-1)]
+
+    def layout(self, reg, inputs, param, challenges=None):
+        """inputs: X row-major as `n_inputs` Vals; param(v) -> the Val of a circuit parameter (asked for in the order Wq, Wk, Wv, row-major);
+        challenges: None lays the first phase (as the witness-plan recorder does, on symbols), else the two challenges: everything"""
+        reg.decomp = (self.base, self.legs)
+        n, d = self.n, self.d
+        x = reg.assign(reg.inputs[0], inputs)                                        # placed once: the three projections read the same cells
+        reg.increment(len(x))
+        Wq, Wk, Wv = ([param(int(v)) for v in W.reshape(-1)] for W in (self.Wq, self.Wk, self.Wv))
+        Q, K, V = (reg.einsum(ein, x, W, challenges) for ein, W in zip(self.eins[:3], (Wq, Wk, Wv)))
+        S = reg.div(reg.einsum(self.eins[3], Q, K, challenges), self.score_div)
+        P_ = reg.softmax_axes([S[i * n:(i + 1) * n] for i in range(n)], self.input_scale, self.output_scale, self.eps)
+        O = reg.div(reg.einsum(self.eins[4], [v for row in P_ for v in row], V, challenges), self.out_div)
+        return reg.output_equals_instance(O, self.gc.instance, 0, self.base, self.legs)
+
+    def plan_identity(self):
+        shape = [self.k, self.w, self.n, self.e, self.d, self.input_scale, self.output_scale, self.score_div, self.base, self.legs,
+                 self.lookup_range[0], self.lookup_range[1], self.gc.advices[0].num_blocks()]
+        return b"".join(np.asarray(a, np.int64).tobytes() for a in (shape, self.Wq, self.Wk, self.Wv)) + np.float64(self.eps).tobytes()
+
+    def fresh(self):
+        """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
+        return AttentionHeadCircuit(self.k, self.n, self.e, self.d, self.capacity, self.w, self.input_scale, self.output_scale, self.eps,
+                                    self.score_div, self.base, self.legs, self.lookup_range, self.seed, self.Wq, self.Wk, self.Wv)
+
+
+class BatchMlpCircuit(PhasedLayoutCircuit):
+    """MlpCircuit's op sequence on a BATCH: an m x k input matrix, m >= 2 rows through the same `layers` x (Gemm + bias + ReLU) in one
+    proof -- ezkl's batch_size, and examples/onnx/large_mlp as the reference states it (9 x Linear(100, 100) + ReLU on a 10 x 100 batch).
+    With m > 1 the Gemm "mk,nk->mn" has two non-common indices and the reference's analysis (einsum/analysis.rs:170-198) sends it to
+    Freivalds' argument: every layer's product is an einsum over the circuit's own configuration (`BaseRegion.einsum`), second-phase
+    advice and two challenges.  Private input and parameters, public output; the m * k inputs, row-major, and the m * n outputs are
+    range-checked by decomposition.  The bias [1, n] is added to every row: layouts.rs `pairwise` (:2917) broadcasts both operands to
+    [m, n] with `expand` (:3038, which repeats the VALUES -- a private parameter has no cell to share) and assigns all m * n entries of
+    each, so the bias takes m * n cells of the second input column beside the m * n quotients, one ADD row per element, and the m
+    copies of a bias entry are tied to nothing, as the entries of a private weight matrix are.
+    A Gemm the analysis lays out with base ops -- m = 1, a layer with n = 1, or k = 1, where the sanitised equation has no common
+    index -- is refused by name (ValueError): batch 1 is MlpCircuit's.  So is num_inner_cols != 1, the einsum layout's own rule: the RLC
+    gate of a wider block folds num_inner_cols entries a row, which the witness plan's RLC record does not state."""
+
+    def __init__(self, logrows, num_inner_cols, batch, weights, biases, decomp_base, decomp_legs, capacity=None, relu_last=True, relu_first=False,
+                 rebase=None):
+        """weights: per layer n x k integers; biases: per layer n; rebase: one divisor in [1, 2^32) per layer (MlpCircuit's), or None;
+        capacity: the cells of a model column set (GraphSettings.total_assignments; None: counted)"""
+        from . import einsum_plan as EP
+        self.k, self.w, self.m = logrows, num_inner_cols, int(batch)
+        self.weights = [[[int(v) for v in row] for row in W] for W in weights]
+        self.biases = [[int(v) for v in b] for b in biases]
+        self.base, self.legs, self.relu_last, self.relu_first = decomp_base, decomp_legs, bool(relu_last), bool(relu_first)
+        self.rebase = [1] * len(self.weights) if rebase is None else [int(d) for d in rebase]
+        if len(self.rebase) != len(self.weights) or any(not 1 <= d < 1 << 32 for d in self.rebase):
+            raise ValueError("BatchMlpCircuit: rebase takes one divisor in [1, 2^32) per layer")
+        if not self.weights:
+            raise ValueError("BatchMlpCircuit: no layer (a Gemm-free graph is MlpCircuit's)")
+        width = len(self.weights[0][0]) if self.weights[0] else 0
+        self.equations = []
+        for i, (W, b) in enumerate(zip(self.weights, self.biases)):
+            if not W or any(len(row) != width for row in W) or len(b) != len(W) or width == 0:
+                raise ValueError("BatchMlpCircuit: layer %d takes an n x %d weight matrix and n biases" % (i, width))
+            dims = dict(m=self.m, k=width, n=len(W))
+            if self.m < 1 or EP.einsum_analysis("mk,nk->mn", dims).strategy != EP.FREIVALDS:
+                raise ValueError("BatchMlpCircuit: the Gemm of layer %d (m = %d, k = %d, n = %d) is %s%s"
+                                 % (i, self.m, width, len(W), EINSUM_BASE_OPS_ERROR, " (batch 1 is MlpCircuit's)" if self.m == 1 else ""))
+            self.equations.append(("mk,nk->mn", dims))
+            width = len(W)
+        if len(self.biases) != len(self.weights):
+            raise ValueError("BatchMlpCircuit: one bias vector per weight matrix")
+        if num_inner_cols != 1:
+            raise ValueError("BatchMlpCircuit: num_inner_cols = %d: %s" % (num_inner_cols, EINSUM_WIDTH_ERROR))
+        self.n_in, self.n_out = len(self.weights[0][0]), len(self.weights[-1])
+        self.n_inputs = self.m * self.n_in
+        self.capacity = int(capacity) if capacity is not None else self._count_cells()
+        analyses = [EP.einsum_analysis(eq, dims) for eq, dims in self.equations]
+        self.settings = EC.GraphSettings(logrows, num_inner_cols, self.capacity, total_const_size=16,
+                                         required_range_checks=[(-1, 1), (0, decomp_base - 1)], model_instance_shapes=[[self.m, self.n_out]],
+                                         einsum_reduction_length=sum(a.reduction_length for a in analyses), einsum_max_output_axes=2)
+        self.gc = EC.GraphConfig(self.settings)
+        self.eins = [EinsumCircuit.over(self.gc, eq, dims) for eq, dims in self.equations]
+
+    def _count_cells(self):
+        """an upper bound of the cells the layout places in a model column set (MlpCircuit._count_cells's terms, per batch element)"""
+        dec = lambda c: _decomposition_cells(c, self.w, self.legs)
+        c = dec(self.n_inputs)
+        if self.relu_first:
+            c += dec(self.n_inputs) + 6 * self.n_inputs
+        for i, W in enumerate(self.weights):
+            mn = self.m * len(W)
+            if self.rebase[i] != 1:
+                c += 3 * (dec(mn) + self.w) + 16 * mn
+            c += mn
+            if i + 1 < len(self.weights) or self.relu_last:
+                c += dec(mn) + 6 * mn
+        return c + 2 * dec(self.m * self.n_out) + self.m * self.n_out + 64
+
+    def default_inputs(self):
+        return [(7 * i + 3) % 11 - 5 for i in range(self.n_inputs)]
+
+    def layout(self, reg, inputs, param, challenges=None):
+        """inputs: the m x k matrix row-major as `n_inputs` Vals; param(v) -> the Val of a circuit parameter (asked for per layer: the
+        weight matrix row-major, then the biases); challenges: None lays the first phase (as the witness-plan recorder does, on
+        symbols), else the two challenges: everything"""
+        reg.decomp = (self.base, self.legs)
+        _, vals = reg.decompose(inputs, self.base, self.legs)                   # input range check
+        if self.relu_first:
+            vals = reg.relu(vals, self.base, self.legs)
+        for i, (W, b, ein) in enumerate(zip(self.weights, self.biases, self.eins)):
+            outs = reg.einsum(ein, vals, [param(wv) for row in W for wv in row], challenges)      # the Gemm: a Freivalds einsum
+            outs = reg.div(outs, self.rebase[i])                                   # RebaseScale around the Einsum node
+            bias = [param(bv) for bv in b]
+            vals = reg.pairwise(outs, bias * self.m, EC.ADD)                       # [1, n] broadcast over the m rows: m * n cells
+            if i + 1 < len(self.weights) or self.relu_last:
+                vals = reg.relu(vals, self.base, self.legs)
+        return reg.output_equals_instance(vals, self.gc.instance, 0, self.base, self.legs)
+
+    def plan_identity(self):
+        shape = [self.k, self.w, self.m, self.base, self.legs, int(self.relu_last), int(self.relu_first), len(self.weights),
+                 self.gc.advices[0].num_blocks()]
+        per_layer = [a for W, b in zip(self.weights, self.biases) for a in ([len(W), len(W[0])], W, b)]
+        return b"".join(np.asarray(a, np.int64).tobytes() for a in [shape] + per_layer + [self.rebase])
+
+    def fresh(self):
+        """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
+        return BatchMlpCircuit(self.k, self.w, self.m, self.weights, self.biases, self.base, self.legs, self.capacity, self.relu_last,
+                               self.relu_first, self.rebase)
 
 
 class _DeviceAttentionWitness(_DeviceSurrogateWitness):

@@ -15,7 +15,7 @@ SYMBOLS = [
     "ezkl_hip_coset_ntt_batch", "ezkl_hip_coset_ntt_dev", "ezkl_hip_coeff_to_cosets_dev", "ezkl_hip_coeff_to_cosets_range_dev", "ezkl_hip_cosets_transpose_dev", "ezkl_hip_vec_op_dev", "ezkl_hip_vec_scale_dev", "ezkl_hip_permutation_sigma_dev", "ezkl_hip_vec_fill_dev", "ezkl_hip_host_malloc", "ezkl_hip_host_free", "ezkl_hip_upload_commit_batch", "ezkl_hip_upload_begin", "ezkl_hip_upload_begin_fmt", "ezkl_hip_upload_wait", "ezkl_hip_upload_commit", "ezkl_hip_upload_end", "ezkl_hip_msm_batch_begin", "ezkl_hip_msm_batch_push_dev", "ezkl_hip_msm_batch_push_many_dev", "ezkl_hip_msm_batch_finish", "ezkl_hip_eval_poly_batch_dev", "ezkl_hip_lincomb_dev", "ezkl_hip_kate_division_dev", "ezkl_hip_chacha20_fr_dev",
     "ezkl_hip_divide_by_vanishing_dev", "ezkl_hip_prefix_scan_dev", "ezkl_hip_eval_poly_dev", "ezkl_hip_lookup_multiplicity_dev", "ezkl_hip_lookup_multiplicity_acc_dev", "ezkl_hip_lookup_multiplicity_batch_dev", "ezkl_hip_batch_invert_dev", "ezkl_hip_eval_h_dev", "ezkl_hip_eval_h_check", "ezkl_hip_eval_h_source", "ezkl_hip_eval_h_schedule", "ezkl_hip_eval_h_prepare", "ezkl_hip_eval_h_jit_stats", "ezkl_hip_eval_check_dev", "ezkl_hip_eval_check_source", "ezkl_hip_lookup_missing_rows_dev", "ezkl_hip_copy_check_dev", "ezkl_hip_set_async", "ezkl_hip_stream_wait_library",
     "ezkl_hip_last_kernel_ms", "ezkl_hip_kernel_ms_stats", "ezkl_hip_ubench", "ezkl_hip_field_probe_dev", "ezkl_hip_field_probe_names",
-    "ezkl_hip_witness_plan_upload", "ezkl_hip_witness_plan_free", "ezkl_hip_witness_plan_info", "ezkl_hip_witness_run_dev", "ezkl_hip_witness_run_phase_dev", "ezkl_hip_witness_plan_phases", "ezkl_hip_witness_tile_dev", "ezkl_hip_witness_lookup_stats_dev", "ezkl_hip_witness_last_error", "ezkl_hip_witness_wide_dots",
+    "ezkl_hip_witness_plan_upload", "ezkl_hip_witness_plan_free", "ezkl_hip_witness_plan_info", "ezkl_hip_witness_run_dev", "ezkl_hip_witness_run_phase_dev", "ezkl_hip_witness_plan_phases", "ezkl_hip_witness_tile_dev", "ezkl_hip_witness_lookup_stats_dev", "ezkl_hip_witness_outputs_dev", "ezkl_hip_witness_last_error", "ezkl_hip_witness_wide_dots",
     "ezkl_hip_comm_available", "ezkl_hip_comm_unique_id", "ezkl_hip_comm_init", "ezkl_hip_comm_info", "ezkl_hip_comm_destroy", "ezkl_hip_comm_allgather_dev",
     "ezkl_hip_comm_fold_points", "ezkl_hip_comm_broadcast_host", "ezkl_hip_comm_alltoall_dev", "ezkl_hip_comm_allgather_host", "ezkl_hip_comm_alltoallv_dev", "ezkl_hip_comm_stats", "ezkl_hip_comm_selftest",
 ]

@@ -1409,7 +1409,7 @@ def record_plan(circuit):
         raise PlanError("witness plans cover MlpCircuit and circuits that state their `layout`, not %s" % type(circuit).__name__)
     if getattr(circuit, "gc", None) is None:
         raise PlanError("witness plans are recorded from a configured circuit: this %s has no configuration" % type(circuit).__name__)
-    phased = type(circuit) in (EL.TransformerSurrogateCircuit, EL.AttentionHeadCircuit)      # einsums laid over its own configuration: a two-phase plan
+    phased = type(circuit) in (EL.TransformerSurrogateCircuit, EL.AttentionHeadCircuit, EL.BatchMlpCircuit)      # einsums laid over its own configuration: a two-phase plan
     if any(c.phase != 0 for c in circuit.gc.cs.advice) and not phased:
         raise PlanError("witness plans do not cover second-phase advice")
     reg = RecordingRegion(circuit.gc) if type(circuit) is EL.MlpCircuit else (PhasedLookupRecordingRegion if phased else LookupRecordingRegion)(circuit.gc)

@@ -393,7 +393,13 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *   columns of a refused run are not to be passed).  A source whose magnitude needs 62 bits or more makes the call return EZKL_ERR_INVALID
  *   (ezkl_hip_witness_last_error counts them) with out_min_max = (0, 0) rather than a wrong extremum.  One launch: a lane per element,
  *   striding over the records; one 64-bit atomicMin and one atomicMax per wave on two result words the plan owns, set to 0 by every call.
- *   The call waits for its result; HIP events around the launch: ezkl_hip_last_kernel_ms("witness_lookup_stats"). */
+ *   The call waits for its result; HIP events around the launch: ezkl_hip_last_kernel_ms("witness_lookup_stats").
+ * outputs: the plan's output cells before its last phase -- run_phase gathers them with the LAST phase only, and the instance column is
+ *   needed before the first commitment.  advice_cols_dev: the n_advice column pointers phase 0 last ran to its end on; outputs_host
+ *   receives n_outputs x 32 bytes, Montgomery words, as run's does.  One gather launch, one copy, one wait; HIP events around the launch:
+ *   ezkl_hip_last_kernel_ms("witness_outputs").  Before phase 0 has succeeded, on other column pointers than it ran on, or with an
+ *   output cell in a column of a phase that has not run to its end, the call returns EZKL_ERR_INVALID, ezkl_hip_witness_last_error says
+ *   which, and nothing is launched.  A plan without outputs: EZKL_OK, nothing launched. */
 typedef struct ezkl_wplan_s* ezkl_wplan_t;
 typedef ezkl_wplan_t ezkl_witness_plan_t;
 int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out_plan);
@@ -407,6 +413,7 @@ int ezkl_hip_witness_plan_phases(ezkl_wplan_t plan, uint32_t out[2], uint8_t* co
 int ezkl_hip_witness_tile_dev(void* const* advice_cols_dev, uint32_t n_advice, uint32_t k, uint32_t unit_rows, uint32_t tiles, const uint32_t* dst_cols,
                               const uint32_t* src_cols, uint32_t n_pairs, void* stream);
 int ezkl_hip_witness_lookup_stats_dev(ezkl_witness_plan_t plan, void* const* advice_cols_dev, int64_t out_min_max[2], void* stream);
+int ezkl_hip_witness_outputs_dev(ezkl_witness_plan_t plan, void* const* advice_cols_dev, void* outputs_host, void* stream);
 const char* ezkl_hip_witness_last_error(void);   /* the calling thread's last refusal (upload) or range failure (run); "" after a success */
 /* Which kernel replayed the DOT records: *launches = how many of them, in this process so far, went to the wide kernel -- a record of ONE step
  * (p1 == 1) with p0 >= 16 products, the claimed product of an einsum, every lane of a wave multiplying -- instead of the chunked scan every
