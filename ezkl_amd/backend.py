@@ -458,6 +458,29 @@ def polycommit_commit(message, num_unusable_rows, params, once=False):
     return out
 
 
+def polycommit_commit_dev(columns, length, num_unusable_rows, params):
+    """PolyCommitChip::commit of a message that is RESIDENT already, laid out as a circuit's module columns hold it (VarTensor::assign
+    from row 0, n = 2^k - num_unusable_rows values a column, every other usable row zero: what a witness plan's replay leaves): the
+    unusable rows of each of the length // n + 1 columns are filled with Blind::default() = 1 in place (vec_fill) and the column is committed
+    against g_lagrange without window tables (msm_once).  columns: DeviceBuffers of 2^k Montgomery words, at least length // n + 1 of
+    them.  -> (length // n + 1, 8) affine points, the same as polycommit_commit gives for the message."""
+    n_rows = 1 << params.k
+    u = int(num_unusable_rows)
+    if not 0 < u < n_rows:
+        raise ValueError("%d unusable rows of %d" % (u, n_rows))
+    n = n_rows - u
+    num_poly = int(length) // n + 1
+    if length < 0 or num_poly > len(columns):
+        raise ValueError("a message of %d values takes %d columns of %d, got %d" % (length, num_poly, n, len(columns)))
+    if any(c.nbytes < 32 * n_rows for c in columns[:num_poly]):
+        raise ValueError("a column holds %d words of 32 bytes" % n_rows)
+    out = np.zeros((num_poly, 8), np.uint64)
+    for j in range(num_poly):
+        vec_fill(columns[j].ptr + 32 * n, _to_mont(1), u)
+        out[j] = params._gl.msm_once(columns[j], 0, n_rows)
+    return out
+
+
 def msm_g2(points, scalars):
     """sum_i scalars[i] * points[i] over G2: points (n, 16) u64 affine (x.c0, x.c1, y.c0, y.c1 Montgomery Fq, the SRS file's layout),
     scalars (n, 4) Montgomery Fr -> (16,) u64 affine (ezkl_hip_msm_g2)"""

@@ -7,13 +7,21 @@
     prove(witness, compiled_circuit, pk_path, proof_path, srs_path, check_mode)  execute.rs:1575-1627 -> create_proof_circuit (mod.rs:404-489)
     mock(witness, compiled_circuit)                                              execute.rs:1280-1305 -> MockProver::run(..).verify()
     verify(proof_path, compiled_circuit, pk_path, srs_path)                      execute.rs:1651-1722 -> verify_proof_circuit (mod.rs:557-590)
+    swap_proof_commitments(proof_path, witness_path)                             execute.rs:1629-1650 -> pfsys::swap_proof_commitments (mod.rs:492-554)
 
 File formats are the reference's: kzg*.srs / pk.key / vk.key in halo2 raw bytes, witness.json (GraphWitness), proof.json (Snark) and
 `model.compiled` -- the bincode of ezkl's GraphCircuit (node graph + GraphSettings), read by codecs.read_compiled_circuit: on the
 reference's fixture `prove` runs from the reference's artefact files alone (tests/test_execute.py).  What a compiled circuit may
-CONTAIN here is the op family ezkl_layout.MlpCircuit lays out (Input -> Gemm as Einsum "mk,nk->mn" + bias + LeakyReLU slope 0, private
-parameters, public output): ezkl's general layout lives in 6.8k lines of Rust (out of scope) and any other graph
-is refused by name.  On the fixture model that layout reproduces the reference's pk.key bit for bit (tests/test_ezkl_circuit.py).  A JSON
+CONTAIN here is the op family ezkl_layout.MlpCircuit lays out (Input -> Gemm as Einsum "mk,nk->mn" + bias + LeakyReLU slope 0): ezkl's
+general layout lives in 6.8k lines of Rust (out of scope) and any other graph is refused by name.
+VISIBILITY, the MLP family in both its forms (run_args.input_visibility / param_visibility / output_visibility of a description, the
+model's own of a model.compiled): the input Private, Public or KZGCommit; the parameters Private, Fixed or KZGCommit; the output Public or
+KZGCommit -- 18 triples, Private / Private / Public being the default and what it always was, byte for byte.  A Public input shares the
+instance column with the output (input first); Fixed parameters are constants of the key; a KZGCommit tensor is laid into unblinded advice
+columns that come first in the system, so its commitment -- which gen_witness writes into witness.json as processed_*.polycommit -- is
+one of the first points of every proof (swap_proof_commitments; ezkl_layout.MlpCircuit has the layout).  Anything Hashed, a Fixed input or
+output and a Private output are refused by name by every entry point.  A description that asked for another triple used to be laid out
+with the default one, silently; it now gets the circuit it asks for.  On the fixture model that layout reproduces the reference's pk.key bit for bit (tests/test_ezkl_circuit.py).  A JSON
 description of the same family ({"model": "mlp", "run_args": {...}, "weights": [...], "biases": [...]}) is accepted as well; with
 "rebase": [d per layer] every Gemm is wrapped in the RebaseScale division ezkl puts around it at non-zero scales (layouts.rs:219-267 `div`):
 the input is then quantized at run_args.input_scale and the outputs are reported at input_scale + sum(param_scale - log2 d), or at
@@ -25,8 +33,8 @@ Three more families are read as JSON descriptions, chosen by "model" through the
      "pool": "max" | "sum", "capacity", and the same four arrays}                                                     -> PoolClassifierCircuit
     {"model": "norm", "run_args": {...}, "rows", "length", "input_scale", "output_scale", "eps", "layer_norm", "lookup_range", "capacity"}   -> NormCircuit
 with run_args = logrows, num_inner_cols, decomp_base, decomp_legs and optionally input_scale / output_scale (the witness file's scales,
-default 0); private input, private parameters and public output only -- any other visibility is refused by name, a malformed field by a
-ValueError that names it.  setup, gen_witness, mock, prove, verify and Prover treat them as they treat the MLP.
+default 0); private input, private parameters and public output only in THESE families -- any other visibility is refused by name, a
+malformed field by a ValueError that names it.  setup, gen_witness, mock, prove, verify and Prover treat them as they treat the MLP.
 Two families have SECOND-PHASE advice -- their matmuls are Freivalds einsums over the circuit's own configuration, two challenges -- and
 live in the table PHASED_FAMILIES:
     {"model": "mlp_batch", "run_args": {logrows, num_inner_cols, decomp_base, decomp_legs[, input_scale, param_scale]}, "batch": m, "weights", "biases",
@@ -58,6 +66,9 @@ class CheckMode:
     SAFE, UNSAFE = "SAFE", "UNSAFE"
 
 
+POLYCOMMIT_BLINDING = 5                  # vk.cs().blinding_factors() of this gate family: no advice column is queried at more than 3 rotations
+
+
 def _read_compiled(path, any_visibility=False):
     """the reference's own `model.compiled` (bincode of GraphCircuit, codecs.read_compiled_circuit) or this package's JSON description
     -> (what it says of the op family, as plain data; the parsed file).  settings: the file's GraphSettings (the JSON description has
@@ -70,11 +81,17 @@ def _read_compiled(path, any_visibility=False):
             raise ValueError("unsupported compiled circuit: %r" % j.get("model"))
         return dict(family.describe(j), family=j["model"]), j
     c = codecs.read_compiled_circuit(raw)
+    return _describe_compiled(c, any_visibility), c
+
+
+def _describe_compiled(c, any_visibility=False):
+    """a parsed `model.compiled` (codecs.read_compiled_circuit: "model", the node graph with its visibilities, and "settings") as the
+    plain data of the MLP family"""
     weights, biases, relu_last, relu_first, n_inputs = _mlp_of_graph(c["model"], any_visibility)
     st, in_op = c["settings"], c["model"]["nodes"][c["model"]["inputs"][0]]["opkind"]
     return dict(weights=weights, biases=biases, relu_last=relu_last, relu_first=relu_first, rebase=None, n_inputs=n_inputs, run_args=st["run_args"], settings=st,
                 total_assignments=st["total_assignments"], in_scale=st["model_input_scales"][0], out_scale=st["model_output_scales"][0],
-                datum_type=in_op.get("datum_type", "F32"), input_decomp=in_op.get("decomp", True), visibility=c["model"]["visibility"], family="mlp"), c
+                datum_type=in_op.get("datum_type", "F32"), input_decomp=in_op.get("decomp", True), visibility=c["model"]["visibility"], family="mlp")
 
 
 def _describe_mlp(j):
@@ -108,9 +125,21 @@ def _build_mlp(d):
         if [tuple(x) for x in st["required_range_checks"]] != want or st["required_lookups"] or st["num_dynamic_lookups"] or st["num_shuffles"] \
                 or st["einsum_params"]["equations"]:
             raise ValueError("unsupported compiled circuit: its settings ask for arguments outside the MLP family")
-    return EL.MlpCircuit(ra["logrows"], ra["num_inner_cols"], d["weights"], d["biases"], ra["decomp_base"], ra["decomp_legs"],
-                         total_assignments=d["total_assignments"], relu_last=d["relu_last"], n_inputs=d["n_inputs"], relu_first=d["relu_first"],
-                         rebase=d["rebase"])
+    vis = EL.visibility_triple(d["visibility"])                                  # (anything outside the family's triples: refused by name)
+    # the constant cells of a compiled file with Fixed parameters are the file's count; a description's are counted by a dummy pass
+    consts = st["total_const_size"] if st is not None and vis[1] == "Fixed" else None
+    circuit = EL.MlpCircuit(ra["logrows"], ra["num_inner_cols"], d["weights"], d["biases"], ra["decomp_base"], ra["decomp_legs"],
+                            total_assignments=d["total_assignments"], relu_last=d["relu_last"], n_inputs=d["n_inputs"], relu_first=d["relu_first"],
+                            rebase=d["rebase"], visibility=vis, total_const_size=consts)
+    if st is not None and [int(v) for v in st["module_sizes"]["polycommit"]] != circuit.settings.polycommit_sizes:
+        raise ValueError("unsupported compiled circuit: its module sizes %s are not those of its visibilities %s"
+                         % (list(st["module_sizes"]["polycommit"]), circuit.settings.polycommit_sizes))
+    # a module column holds 2^k - 6 values because the system had 5 blinding factors when it was configured; gen_witness commits at that
+    # split too.  A finished system with another count would put the unusable rows elsewhere: refused, never committed at the wrong split
+    if circuit.gc.polycommit and circuit.gc.cs.blinding_factors() != POLYCOMMIT_BLINDING:
+        raise ValueError("unsupported compiled circuit: %d blinding factors where the KZG-committed columns were sized for %d"
+                         % (circuit.gc.cs.blinding_factors(), POLYCOMMIT_BLINDING))
+    return circuit
 
 
 _REQUIRED = object()
@@ -413,15 +442,16 @@ def _load_circuit(path):
 
 def _mlp_of_graph(model, any_visibility=False):
     """the op family ezkl_layout.MlpCircuit lays out, read off ezkl's node graph: Input -> (Einsum "mk,nk->mn" with a constant [n, k]
-    -> Add of a constant [1, n] -> LeakyReLU slope 0)*, private input and parameters at scale 0, public output.  A LeakyReLU slope 0 may
+    -> Add of a constant [1, n] -> LeakyReLU slope 0)*, at scale 0, with one of the family's visibility triples (ezkl_layout.VISIBILITIES).  A LeakyReLU slope 0 may
     sit straight on the input, and the layer list may be EMPTY: Input -> LeakyReLU -> output is examples/onnx/1l_relu (BASELINE
     configs[0]; with no Gemm nothing is rescaled, so that graph may carry any ONE scale -- ezkl's default input scale is 7).
-    any_visibility (the forward pass of gen_witness, which lays nothing out): the visibilities are the caller's business.
+    any_visibility (gen_witness, which names a refused visibility itself): the visibilities are the caller's business.
     -> (weights, biases, relu_last, relu_first, n_inputs)"""
     nodes, vis = model["nodes"], model["visibility"]
-    if len(model["inputs"]) != 1 or len(model["outputs"]) != 1 or \
-            (not any_visibility and (vis["input"], vis["params"], vis["output"]) != ("Private", "Private", "Public")):
+    if len(model["inputs"]) != 1 or len(model["outputs"]) != 1:
         raise ValueError("unsupported compiled circuit: visibility / arity")
+    if not any_visibility:
+        EL.visibility_triple(vis)                                                   # a triple outside the family's is refused by name
     def const(idx, dims_ok):
         op = nodes[idx]["opkind"]
         if op["kind"] != "Constant" or not dims_ok(op["quantized_values"]["dims"]):
@@ -730,11 +760,22 @@ def _host_advice(circuit, x, region=None):
     return advice, columns
 
 
-def _forward_device(d, x, mode, pk_path):
+def _module_result(points):
+    """the ModuleForwardResult of one committed tensor as witness.json holds it, from PolyCommitChip::commit's affine Montgomery points"""
+    out = []
+    for p in points:
+        xi, yi = (int.from_bytes(p[4 * h:4 * h + 4].tobytes(), "little") * pow(1 << 256, -1, B._Q) % B._Q for h in (0, 1))
+        out.append({"x": codecs.felt_to_hex_le(xi), "y": codecs.felt_to_hex_le(yi)})
+    return {"poseidon_hash": None, "polycommit": [out]}
+
+
+def _forward_device(d, x, mode, pk_path, kzg=None):
     """gen_witness's forward pass on the device, for every family: the circuit's witness plan -- the `.wplan` next to pk_path where one is
     given and is this circuit's, else a fresh recording -- uploaded and replayed, the outputs read back, the lookup statistics by
     ezkl_hip_witness_lookup_stats_dev over the replayed cells.  Of a plan with phases only phase 0 is replayed (_first_phase): the
-    outputs and every static lookup live in it, and a plan that has a nonlinearity record in a later phase is refused before the replay.  -> (outputs, (min, max), max_range_size), or None when mode is "auto" and
+    outputs and every static lookup live in it, and a plan that has a nonlinearity record in a later phase is refused before the replay.  kzg (a resident backend.ParamsKZG, or None): the commitments of the circuit's KZG-committed tensors are then taken from the
+    replayed module columns themselves (backend.polycommit_commit_dev: the tail rows filled with one, one table-free MSM over g_lagrange a
+    column; the message never comes back to the host).  -> (outputs, (min, max), max_range_size, {tensor: points} or None), or None when mode is "auto" and
     the device path is not to be taken (_open_plan, or an input that does not fit int64); mode "device" raises instead.  A witness the
     device refuses raises backend.WitnessError, a ValueError with the layout's words."""
     if not _fits_plan(x, mode):
@@ -750,11 +791,15 @@ def _forward_device(d, x, mode, pk_path):
             raise ValueError("gen_witness: the plan has a nonlinearity record in phase %d; only phase 0 is replayed for a witness file" % late[0])
         cols, outs = _first_phase(dev, x)
         stats = dev.lookup_stats(cols)
+        points = None
+        if kzg is not None and callable(getattr(circuit, "committed", None)):          # last: it overwrites the unusable rows of those columns
+            points = {what: B.polycommit_commit_dev([cols[blk[0].index] for blk in var.inner], length, POLYCOMMIT_BLINDING + 1, kzg)
+                      for what, var, length in circuit.committed()}
     finally:
         for c in cols or []:
             c.free()
         dev.free()
-    return [EL.signed(v) for v in outs], stats, _max_range_size(circuit)
+    return [EL.signed(v) for v in outs], stats, _max_range_size(circuit), points
 
 
 def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None, synthesis="host", pk_path=None):
@@ -778,7 +823,14 @@ def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None
     * KZGCommit visibility of the input / parameters / output ("polycommit", the MLP family only): PolyCommitChip::commit on the GPU (backend.polycommit_commit:
       one commit_lagrange MSM per column of 2^k - (blinding factors + 1) values) -- needs srs_path, and like the reference a vk to know the
       blinding factors (here: any file at vk_path; the count is read off the constraint system);  without an SRS the processed value stays
-      None, as in the reference ("SRS for poly commit does not exist (will be ignored)").  Hashed (Poseidon) visibility is refused."""
+      None, as in the reference ("SRS for poly commit does not exist (will be ignored)").  On the host path the message is the tensor
+      as Python integers (the parameters in the order the circuit's module holds them: per layer the weight rows, then the bias --
+      MlpCircuit.flat_params); on the device path it is the replayed module column itself (_forward_device).  Either way a tensor of
+      `len` values gets len // n + 1 commitments, n = 2^k - 6, as the reference computes it: when len is a multiple of n the last one is the
+      commitment to an EMPTY column (zeros and the six ones) -- which the circuit has too, VarTensor.new_advice leaves room for a
+      duplicated row that a module never writes.  (For other lengths the circuit can have one column MORE than the file has
+      commitments, e.g. len = n - 1: the reference's swap-proof-commitments then misplaces every later tensor's points; so does ours.)
+      Hashed (Poseidon) visibility, a Fixed input or output and a Private output are refused by name."""
     if synthesis not in ("auto", "host", "device"):
         raise ValueError("synthesis must be \"auto\", \"host\" or \"device\"")
     d, _ = _read_compiled(compiled_circuit, any_visibility=True)
@@ -786,6 +838,8 @@ def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None
     for what, v in vis.items():
         if isinstance(v, dict):
             raise ValueError("unsupported visibility: %s is Hashed (Poseidon modules are outside this package's scope)" % what)
+    if d["family"] == "mlp":
+        EL.visibility_triple(vis)
     if isinstance(data, (bytes, str)) and os.path.exists(data):
         data = open(data).read()
     if isinstance(data, (bytes, str)):
@@ -796,39 +850,39 @@ def gen_witness(compiled_circuit, data, output=None, vk_path=None, srs_path=None
     x = [_quantize(v, in_scale, d["datum_type"]) for v in cols[0]]
     x = [EL.signed(v % EL.R) for v in x]
     inputs = list(x)
-    made = _forward_device(d, x, synthesis, pk_path) if synthesis != "host" else None
-    outputs, (min_lookup, max_lookup), max_range_size = made if made is not None else _family(d["family"]).forward(d, x)
-    weights, biases = d.get("weights"), d.get("biases")                         # (what a KZGCommit of the parameters commits to: the MLP family's)
     processed = dict(input=None, params=None, output=None)
-    if any(v == "KZGCommit" for v in vis.values()):
-        have_srs = srs_path is not None and os.path.exists(srs_path)
-        if vk_path is not None and have_srs:
-            blinding = 5                 # vk.cs().blinding_factors() of this gate family: no advice column is queried at more than 3 rotations
-            srs = load_params_prover(srs_path, ra["logrows"])
-            bg = _srs_bases(srs["g"], "g")
-            try:
-                bgl = _srs_bases(srs["g_lagrange"], "g_lagrange")
-            except BaseException:
-                bg.free()
-                raise
-            params = B.ParamsKZG.from_bases(ra["logrows"], bg, bgl)
-            try:
-                def commit(vals):
-                    msg = np.stack([np.frombuffer(((v % EL.R) * (1 << 256) % EL.R).to_bytes(32, "little"), np.uint64) for v in vals])
-                    pts = B.polycommit_commit(msg, blinding + 1, params, once=True)    # the SRS is loaded for these one to three columns
-                    out = []
-                    for p in pts:
-                        xi, yi = (int.from_bytes(p[4 * h:4 * h + 4].tobytes(), "little") * pow(1 << 256, -1, B._Q) % B._Q for h in (0, 1))
-                        out.append({"x": codecs.felt_to_hex_le(xi), "y": codecs.felt_to_hex_le(yi)})
-                    return {"poseidon_hash": None, "polycommit": [out]}
-                if vis["input"] == "KZGCommit": processed["input"] = commit(inputs)
-                if vis["params"] == "KZGCommit": processed["params"] = commit([w for W in weights for row in W for w in row] + [b for bv in biases for b in bv])
-                if vis["output"] == "KZGCommit": processed["output"] = commit(outputs)
-            finally:
-                params.free()
+    committed = [what for what in ("input", "params", "output") if vis[what] == "KZGCommit"]
+    kzg = None
+    if committed and vk_path is not None and srs_path is not None and os.path.exists(srs_path):
+        srs = load_params_prover(srs_path, ra["logrows"])
+        bg = _srs_bases(srs["g"], "g")
+        try:
+            bgl = _srs_bases(srs["g_lagrange"], "g_lagrange")
+        except BaseException:
+            bg.free()
+            raise
+        kzg = B.ParamsKZG.from_bases(ra["logrows"], bg, bgl)
+    try:
+        made = _forward_device(d, x, synthesis, pk_path, kzg) if synthesis != "host" else None
+        if made is not None:
+            outputs, (min_lookup, max_lookup), max_range_size, points = made
         else:
-            for what, v in vis.items():                      # the reference: a module result without its commitments
-                if v == "KZGCommit": processed[what] = {"poseidon_hash": None, "polycommit": None}
+            (outputs, (min_lookup, max_lookup), max_range_size), points = _family(d["family"]).forward(d, x), None
+        if kzg is not None and points is None:               # the host path: PolyCommitChip::commit of the message as integers
+            weights, biases = d.get("weights"), d.get("biases")                     # (what a KZGCommit of the parameters commits to: the MLP family's)
+            messages = dict(input=inputs, output=outputs, params=[v for W, bv in zip(weights, biases) for v in [w for row in W for w in row] + list(bv)])
+            def commit(vals):
+                msg = np.stack([np.frombuffer(((v % EL.R) * (1 << 256) % EL.R).to_bytes(32, "little"), np.uint64) for v in vals])
+                return B.polycommit_commit(msg, POLYCOMMIT_BLINDING + 1, kzg, once=True)    # the SRS is loaded for these one to three columns
+            points = {what: commit(messages[what]) for what in committed if messages[what]}
+        for what in committed:
+            if kzg is None:                                  # the reference: a module result without its commitments
+                processed[what] = {"poseidon_hash": None, "polycommit": None}
+            elif what in points:
+                processed[what] = _module_result(points[what])
+    finally:
+        if kzg is not None:
+            kzg.free()
     text = codecs.write_witness_json([[v % EL.R for v in inputs]], [[v % EL.R for v in outputs]], [in_scale], [out_scale],
                                      processed_inputs=processed["input"], processed_params=processed["params"], processed_outputs=processed["output"],
                                      max_lookup_inputs=max_lookup, min_lookup_inputs=min_lookup, max_range_size=max_range_size)
@@ -908,7 +962,7 @@ def _device_witness(circuit, pk_path, x, mode):
         return None
     try:
         cols, outs = dev.run(x)
-        return cols, [outs], dev.last
+        return cols, circuit.instances(x, outs), dev.last
     finally:
         dev.free()
 
@@ -1024,7 +1078,7 @@ class Prover:
         phased, advice, resident = _phased(circuit), None, ()
         if on_device:
             _, outs = _first_phase(self.plan, x, columns=self._cols)            # into the session's columns, whatever they held
-            adv, inst = self._cols, [outs]
+            adv, inst = self._cols, circuit.instances(x, outs)
             how = dict(self.plan.last, path="device")
             if phased:                                                          # the columns of phase 0 as they are; phase p > 0 replayed with the prover's challenges
                 plan, cols, phase_ms = self.plan, self._cols, {0: self.plan.last["device_ms"]}
@@ -1047,7 +1101,7 @@ class Prover:
             report.clear()
             report.update(how)
             report["stages"] = stages
-        if w["outputs"] and inst != w["outputs"]:
+        if w["outputs"] and [list(outs if on_device else circuit.outputs)] != w["outputs"]:
             raise ValueError("the witness file's outputs do not match the circuit's outputs")
         if not on_device and not phased:
             adv = EL.cols_to_mont(adv, B)
@@ -1119,6 +1173,36 @@ def verify(proof_path, compiled_circuit, vk_path=None, srs_path=None, recommit=F
         return NV.verify_proof(pk, srs["g2"], srs["s_g2"], pr["proof"], pr["instances"])
     finally:
         bg.free()
+
+
+def witness_commitments(witness):
+    """GraphWitness::get_polycommitments: the KZG commitments of a witness file (a path, or the parsed JSON) as (x, y) integers, in the
+    order input, params, output -- the order of the module columns, which are the first advice columns of the circuit"""
+    w = json.load(open(witness)) if isinstance(witness, (str, bytes, os.PathLike)) else witness
+    return [(codecs.felt_from_hex_le(p["x"]), codecs.felt_from_hex_le(p["y"]))
+            for key in ("processed_inputs", "processed_params", "processed_outputs")
+            for group in ((w.get(key) or {}).get("polycommit") or []) for p in group]
+
+
+def swap_proof_commitments(proof_path, witness_path):
+    """`ezkl swap-proof-commitments` (src/execute.rs:1629-1650 of the reference -> pfsys::swap_proof_commitments, src/pfsys/mod.rs:492-554):
+    the witness file's KZG commitments, in the order input, params, output, written as the EVM transcript writes points (32 bytes
+    big-endian x, then y) over the FIRST bytes of the proof -- the commitments to the module columns are the first points of a proof --,
+    the hex form refreshed, the file saved in place.  A proof made from that witness is left as it is; one made from another input or
+    other parameters no longer verifies.  A witness without commitments changes nothing, and the result says so.
+    -> dict(commitments: how many were written, changed: whether the proof bytes differ now, proof: the bytes, note)"""
+    points = witness_commitments(witness_path)
+    j = json.loads(open(proof_path).read())
+    old = codecs.read_proof_json(json.dumps(j))["proof"]
+    head = b"".join(c.to_bytes(32, "big") for p in points for c in p)
+    if len(head) > len(old):
+        raise ValueError("the witness holds %d commitments, the proof only %d bytes" % (len(points), len(old)))
+    new = head + old[len(head):]
+    j["proof"], j["hex_proof"] = list(new), "0x" + new.hex()                     # create_hex_proof
+    open(proof_path, "w").write(json.dumps(j, separators=(",", ":")))
+    note = "no commitments found in witness: the proof is unchanged" if not points else \
+           ("swap proof has created a different proof" if new != old else "the proof already carried these commitments")
+    return dict(commitments=len(points), changed=new != old, proof=new, note=note)
 
 
 def _key_system(circuit, key):
@@ -1201,7 +1285,7 @@ def mock(witness_path, compiled_circuit):
     else:
         adv, inst = circuit.witness(x)                                          # GraphCircuit::synthesize
     cs, fixed, copies, _ = _fresh_keygen_inputs(circuit)
-    public = [list(c) for c in w["outputs"]] if w["outputs"] else inst
+    public = circuit.instances(x, w["outputs"][0]) if w["outputs"] else inst     # prepare_public_inputs: from the witness file
     records, totals = NV.mock(cs, EL.cols_to_mont(fixed, B), copies, advice if adv is None else EL.cols_to_mont(adv, B), instances=public, seed=1,
                               cap=MOCK_CAP)
     if adv is None:

@@ -443,7 +443,7 @@ class GraphSettings:
 
     def __init__(self, logrows, num_inner_cols, total_assignments, total_const_size=0, required_range_checks=(), required_lookups=(),
                  lookup_range=(0, 0), model_instance_shapes=(), total_dynamic_col_size=0, num_dynamic_lookups=0, total_shuffle_col_size=0,
-                 num_shuffles=0, einsum_reduction_length=0, einsum_max_output_axes=0):
+                 num_shuffles=0, einsum_reduction_length=0, einsum_max_output_axes=0, polycommit_sizes=(), always_instance=False):
         self.logrows, self.num_inner_cols, self.total_assignments, self.total_const_size = logrows, num_inner_cols, total_assignments, total_const_size
         self.required_range_checks = [tuple(r) for r in required_range_checks]
         self.required_lookups = list(required_lookups)          # [(name, f)]
@@ -452,6 +452,10 @@ class GraphSettings:
         self.total_dynamic_col_size, self.num_dynamic_lookups = total_dynamic_col_size, num_dynamic_lookups
         self.total_shuffle_col_size, self.num_shuffles = total_shuffle_col_size, num_shuffles
         self.einsum_reduction_length, self.einsum_max_output_axes = einsum_reduction_length, einsum_max_output_axes
+        # module_sizes.polycommit: the length of every KZG-committed tensor, in the order input, params, output; always_instance: the
+        # instance column is made whatever the shapes are (instantiate_instance, vars.rs:423-441: a circuit without a public tensor has
+        # one of length 0)
+        self.polycommit_sizes, self.always_instance = [int(v) for v in polycommit_sizes], bool(always_instance)
 
     @classmethod
     def from_json(cls, j):
@@ -461,7 +465,8 @@ class GraphSettings:
         assert not ep.get("total_einsum_col_size", 0), "einsum parameters: pass einsum_reduction_length / einsum_max_output_axes explicitly"
         return cls(ra["logrows"], ra["num_inner_cols"], j["total_assignments"], j["total_const_size"], j["required_range_checks"], (),
                    ra.get("lookup_range", (0, 0)), j.get("model_instance_shapes", ()), j.get("total_dynamic_col_size", 0),
-                   j.get("num_dynamic_lookups", 0), j.get("total_shuffle_col_size", 0), j.get("num_shuffles", 0))
+                   j.get("num_dynamic_lookups", 0), j.get("total_shuffle_col_size", 0), j.get("num_shuffles", 0),
+                   polycommit_sizes=(j.get("module_sizes") or {}).get("polycommit", ()))
 
     def requires_dynamic_lookup(self): return self.num_dynamic_lookups > 0
     def requires_shuffle(self): return self.num_shuffles > 0
@@ -469,12 +474,16 @@ class GraphSettings:
 
 
 class GraphConfig:
-    """GraphCircuit::configure_with_params (src/graph/mod.rs:1945-2004): ModelVars::new -> instance column -> Model::configure"""
+    """GraphCircuit::configure_with_params (src/graph/mod.rs:1945-2004): ModuleConfigs::from_visibility (one PolyCommitConfig per
+    committed tensor, src/graph/modules.rs:36-52: the FIRST advice columns of the system, unblinded) -> ModelVars::new -> instance
+    column -> Model::configure"""
 
     def __init__(self, settings):
         s = self.settings = settings
         cs = self.cs = ConstraintSystem()
         k, w = s.logrows, s.num_inner_cols
+        # PolyCommitChip::configure (src/circuit/modules/polycommit.rs:104-107); the column length is the blinding factors' of this moment
+        self.polycommit = [VarTensor.new_unblinded_advice(cs, k, 1, size) for size in s.polycommit_sizes]
         # ModelVars::new
         self.advices = [VarTensor.new_advice(cs, k, w, s.total_assignments) for _ in range(3)]
         if s.requires_dynamic_lookup() or s.requires_shuffle():
@@ -483,7 +492,7 @@ class GraphConfig:
         self.const_cols = VarTensor.constant_cols(cs, k, s.total_const_size)
         # instantiate_instance: one instance column for all public tensors
         self.instance = None
-        if s.model_instance_shapes:
+        if s.model_instance_shapes or s.always_instance:
             self.instance = cs.instance_column()
             cs.enable_equality(self.instance)
         # Model::configure

@@ -1501,25 +1501,71 @@ class LayoutCircuit:
         adv = [reg.advice.get(c.index) or [0] * n for c in self.gc.cs.advice]
         return adv, [self.outputs]
 
+    def instances(self, x, outputs=None):
+        """the instance columns of a witness: the public output (None: that of the last synthesis)"""
+        return [list(self.outputs if outputs is None else outputs)]
+
 
 def _decomposition_cells(m, w, legs):
     """the cells `decompose` places for m values: hints, the two range checks, the recomposing dots, MULT by the sign, the equality"""
     return m * (legs + 1) + m + m * legs + m * (-(-legs // w) * w) + 2 * m
 
 
+DEFAULT_VISIBILITY = ("Private", "Private", "Public")
+VISIBILITIES = (("Private", "Public", "KZGCommit"), ("Private", "Fixed", "KZGCommit"), ("Public", "KZGCommit"))     # input, params, output
+
+
+def visibility_triple(vis):
+    """(input, params, output) of an MlpCircuit, checked: None is the default triple; a dict with those keys or a sequence of three.
+    Refused by name, as a ValueError: anything Hashed (a dict, as ezkl's Visibility::Hashed deserialises), a Fixed input or output, a
+    Private output, and whatever else is outside VISIBILITIES."""
+    if vis is None:
+        return DEFAULT_VISIBILITY
+    if isinstance(vis, dict):
+        vis = (vis.get("input", "Private"), vis.get("params", "Private"), vis.get("output", "Public"))
+    vis = tuple(vis)
+    if len(vis) != 3:
+        raise ValueError("a visibility triple is (input, params, output)")
+    for what, v, accepted in zip(("input", "params", "output"), vis, VISIBILITIES):
+        if isinstance(v, dict) or v == "Hashed":
+            raise ValueError("unsupported visibility: %s is Hashed (Poseidon modules are outside this package's scope)" % what)
+        if v not in accepted:
+            raise ValueError("unsupported visibility: %s is %s (the mlp family takes an input that is %s, parameters that are %s and an output that is %s)"
+                             % ((what, v if isinstance(v, str) else repr(v)) + tuple(", ".join(a[:-1]) + " or " + a[-1] for a in VISIBILITIES)))
+    return vis
+
+
 class MlpCircuit(LayoutCircuit):
     """`layers` x (Gemm + bias + ReLU) on one input vector, the op sequence of the reference's fixture model
     (tests/assets/network.onnx: Gemm 3 -> 4 + ReLU) and of examples/onnx/large_mlp/gen.py:6-43 (9 x Linear(100, 100) + ReLU; with
-    batch 1 the einsum "mk,nk->mn" has one non-common index and is laid out with base ops, einsum/analysis.rs:165-184), private
-    input and parameters, public output, inputs / outputs range-checked by decomposition (src/graph/model.rs:1132-1258)."""
+    batch 1 the einsum "mk,nk->mn" has one non-common index and is laid out with base ops, einsum/analysis.rs:165-184), inputs /
+    outputs range-checked by decomposition (src/graph/model.rs:1132-1258).  By default private input and parameters and a public
+    output; `visibility` = (input, params, output) chooses among VISIBILITIES, as GraphCircuit::synthesize does (src/graph/mod.rs:2010-2200):
+
+      KZGCommit   the tensor is assigned, from row 0 and without duplication, to unblinded advice columns of its own that come BEFORE the
+                  model's (GraphConfig.polycommit, in the order input, params, output; all parameters are ONE tensor, in the order `layout`
+                  asks for them: per layer the weight rows, then the bias -- `flat_params`); the model reads those cells in place of the raw
+                  values (an input / a parameter: copy constraints from the module's cells; the outputs: copy constraints to the model's
+                  cells, and no `output` op).  The commitment to such a column is what PolyCommitChip::commit computes outside the
+                  circuit, and the first points of a proof.
+                  (The reference hands a constant that ONE node uses to the model as a bare value, src/graph/model.rs:1323-1330, which
+                  leaves it untied to the module; here every parameter is read from the module's cell.)
+      Public      input: the single instance column holds the input first, the output after it; the model's first use of the input
+                  assigns it from the instance (assign_advice_from_instance), the output comparison moves to offset n_inputs
+      Fixed       params: every parameter is a ValType::Constant -- placed through the region's constant cache (one fixed cell per
+                  distinct value, shared with the layout's own constants; BaseRegion.put / finish), so the parameters are part of the key
+
+    `instances(x)` is the instance column of a witness (prepare_public_inputs, src/graph/mod.rs:1411-1446)."""
 
     def __init__(self, logrows, num_inner_cols, weights, biases, decomp_base, decomp_legs, total_assignments=None, relu_last=True,
-                 n_inputs=None, relu_first=False, rebase=None):
+                 n_inputs=None, relu_first=False, rebase=None, visibility=None, total_const_size=None):
         """rebase: one positive integer per layer, the denominator of the RebaseScale that wraps the layer's Einsum node (node.rs:143-205:
         `div` of the Gemm's output, before the bias is added; 1 = the layer is not rescaled), or None for none.
         relu_first / n_inputs: a LeakyReLU (slope 0) straight on the input, before any Gemm -- with no layers at all that is
         examples/onnx/1l_relu (gen.py: nn.ReLU on a vector of 3), BASELINE configs[0]'s model; n_inputs is needed when there is no weight
-        matrix to read the input length from"""
+        matrix to read the input length from.
+        total_const_size: the settings' count of constant cells (None: 4 as ever; with Fixed parameters what a dummy pass would count:
+        one cell per distinct value among the parameters and the layout's own constants, `_own_constants`)"""
         self.k, self.w = logrows, num_inner_cols
         self.weights = [[[int(v) for v in row] for row in W] for W in weights]
         self.biases = [[int(v) for v in b] for b in biases]
@@ -1530,13 +1576,46 @@ class MlpCircuit(LayoutCircuit):
         self.n_inputs = int(n_inputs) if n_inputs is not None else (len(self.weights[0][0]) if self.weights else None)
         if self.n_inputs is None or (self.weights and len(self.weights[0][0]) != self.n_inputs):
             raise ValueError("MlpCircuit: the input length is unknown or does not match the first weight matrix")
+        self.visibility = visibility_triple(visibility)
         if total_assignments is None:                  # the dummy layout pass of gen-settings: count the cells
             total_assignments = self._count_cells()
-        n_out = len(self.weights[-1]) if self.weights else self.n_inputs
+        self.n_outputs = len(self.weights[-1]) if self.weights else self.n_inputs
+        self.n_params = sum(len(W) * len(W[0]) + len(b) for W, b in zip(self.weights, self.biases))
+        if total_const_size is None and self.visibility[1] == "Fixed":      # one constant cell per distinct value
+            total_const_size = len(set(self._own_constants()) | {v % R for v in self.flat_params()})
+        self._configure(total_assignments, 4 if total_const_size is None else int(total_const_size))
+
+    def _own_constants(self):
+        """the constants the layout itself places, whatever the parameters are -- zeros (the padding of a dot whose length is no multiple of
+        the width, the equalities of equals_zero), ones, the powers of the decomposition base, what `div` needs of its divisor --, read off
+        a dummy pass over a MINIATURE of this circuit: same options, same divisors, zero parameters that are Private, every dimension d
+        beyond two rows cut to w + d % w (a constant's value never depends on a length, only a dot's padding on its residue).  Costs
+        nothing next to a pass over the circuit itself, which every `verify` of a description with Fixed parameters would pay otherwise"""
+        w = self.w
+        cut = lambda d: d if d <= 2 * w else w + d % w
+        dims = [cut(self.n_inputs)] + [cut(len(W)) for W in self.weights]
+        mini = MlpCircuit(self.k, w, [[[0] * dims[i]] * dims[i + 1] for i in range(len(self.weights))], [[0] * d for d in dims[1:]], self.base, self.legs,
+                          relu_last=self.relu_last, n_inputs=dims[0], relu_first=self.relu_first, rebase=self.rebase,
+                          visibility=(self.visibility[0], "Private", self.visibility[2]))
+        reg = BaseRegion(mini.gc, False)
+        mini.layout(reg, [Val(0)] * dims[0], Val)
+        return [v for v, _ in reg.const_order]
+
+    def _configure(self, total_assignments, total_const_size):
+        vin, vpar, vout = self.visibility
+        # module_sizes.polycommit (src/graph/mod.rs:1344-1356, modules.rs:171-205): input, ALL parameters as one tensor, output; a tensor of
+        # length 0 has no module
+        sizes = [n for v, n in zip(self.visibility, (self.n_inputs, self.n_params, self.n_outputs)) if v == "KZGCommit" and n > 0]
+        shapes = ([[1, self.n_inputs]] if vin == "Public" else []) + ([[1, self.n_outputs]] if vout == "Public" else [])
         # max_rows uses blinding factors = 5 (no gate queries 3+ rotations of a column)
-        self.settings = EC.GraphSettings(logrows, num_inner_cols, total_assignments, total_const_size=4,
-                                         required_range_checks=[(-1, 1), (0, decomp_base - 1)], model_instance_shapes=[[1, n_out]])
+        self.settings = EC.GraphSettings(self.k, self.w, total_assignments, total_const_size=total_const_size,
+                                         required_range_checks=[(-1, 1), (0, self.base - 1)], model_instance_shapes=shapes,
+                                         polycommit_sizes=sizes, always_instance=True)
         self.gc = EC.GraphConfig(self.settings)
+
+    def flat_params(self):
+        """every parameter in the order `layout` asks for them: what a KZGCommit of the parameters commits to"""
+        return [v for W, b in zip(self.weights, self.biases) for v in [wv for row in W for wv in row] + list(b)]
 
     def _count_cells(self):
         w, lg = self.w, self.legs
@@ -1555,11 +1634,35 @@ class MlpCircuit(LayoutCircuit):
         m = len(self.weights[-1]) if self.weights else self.n_inputs
         return c + 2 * dec(m) + m + 64
 
+    def _modules(self):
+        """the PolyCommit column set of the input, the parameters and the output (None: the tensor is not committed)"""
+        it = iter(self.gc.polycommit)
+        return [next(it) if v == "KZGCommit" and n > 0 else None
+                for v, n in zip(self.visibility, (self.n_inputs, self.n_params, self.n_outputs))]
+
+    def committed(self):
+        """[(tensor name, its module's VarTensor, its length)] of the KZG-committed tensors, in the order of their columns"""
+        lengths = (self.n_inputs, self.n_params, self.n_outputs)
+        return [(what, var, n) for what, var, n in zip(("input", "params", "output"), self._modules(), lengths) if var is not None]
+
     def layout(self, reg, inputs, param):
         """the op sequence, stated once: `synthesize` runs it on a BaseRegion with the input's values, witness_plan.record_plan on a
         recording region with symbols.  inputs: the input vector as Vals; param(v) -> the Val of a circuit parameter (they are asked for
-        in a fixed order: per layer, each weight row, then the biases)"""
+        in a fixed order: per layer, each weight row, then the biases).  Around the model, in the order of GraphCircuit::synthesize:
+        the input's module, the parameters' module, the model, the output's module (PolyCommitChip::layout: VarTensor::assign from row 0)."""
         reg.decomp = (self.base, self.legs)
+        vin, vpar, vout = self.visibility
+        m_in, m_par, m_out = self._modules()
+        inst = self.gc.instance
+        if m_in is not None:
+            inputs = reg.assign(m_in, inputs, 0)
+        elif vin == "Public":                          # the model's first use of a ValTensor::Instance: assign_advice_from_instance, without advancing
+            inputs = reg.assign(reg.inputs[0], [Val(v.v, ("inst", inst.index, t)) for t, v in enumerate(inputs)])
+        if m_par is not None:                          # one module for all parameters; the model reads its cells (replace_consts)
+            committed = iter(reg.assign(m_par, [param(v) for v in self.flat_params()], 0))
+            param = lambda v: next(committed)
+        elif vpar == "Fixed":
+            param = lambda v: Val(int(v), const=True)
         _, vals = reg.decompose(inputs, self.base, self.legs)                   # input range check
         if self.relu_first:
             vals = reg.relu(vals, self.base, self.legs)
@@ -1569,7 +1672,10 @@ class MlpCircuit(LayoutCircuit):
             vals = reg.pairwise(outs, [param(bv) for bv in b], EC.ADD)
             if i + 1 < len(self.weights) or self.relu_last:
                 vals = reg.relu(vals, self.base, self.legs)
-        reg.output_equals_instance(vals, self.gc.instance, 0, self.base, self.legs)
+        if vout == "Public":
+            reg.output_equals_instance(vals, inst, self.n_inputs if vin == "Public" else 0, self.base, self.legs)
+        elif m_out is not None:                        # copy_advice of every output into the module's column: no `output` op
+            reg.assign(m_out, vals, 0)
         return vals                                                              # the values the final equality is made on
 
     def plan_identity(self):
@@ -1577,19 +1683,35 @@ class MlpCircuit(LayoutCircuit):
         shape = [self.k, self.w, self.base, self.legs, int(self.relu_last), int(self.relu_first), self.n_inputs, len(self.weights)]
         per_layer = [a for W, b in zip(self.weights, self.biases) for a in ([len(W), len(W[0]), len(b)], W, b)]
         rebase = [self.rebase] if any(d != 1 for d in self.rebase) else []      # (a circuit that rescales nothing keeps its hash)
-        return b"".join(np.asarray(a, np.int64).tobytes() for a in [shape] + per_layer + rebase)
+        ident = b"".join(np.asarray(a, np.int64).tobytes() for a in [shape] + per_layer + rebase)
+        if self.visibility != DEFAULT_VISIBILITY:      # (the default triple keeps its hash)
+            ident += ("visibility:%s/%s/%s" % self.visibility).encode()
+        return ident
 
     def fresh(self):
         """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
         return MlpCircuit(self.k, self.w, self.weights, self.biases, self.base, self.legs, total_assignments=self.settings.total_assignments,
-                          relu_last=self.relu_last, n_inputs=self.n_inputs, relu_first=self.relu_first, rebase=self.rebase)
+                          relu_last=self.relu_last, n_inputs=self.n_inputs, relu_first=self.relu_first, rebase=self.rebase,
+                          visibility=self.visibility, total_const_size=self.settings.total_const_size)
 
     def synthesize(self, x, witness=True):
         reg = BaseRegion(self.gc, witness)
         outs = self.layout(reg, [Val(int(v)) for v in x], Val)
         reg.finish(self.gc.const_cols)
         self.outputs = [v.v for v in outs]
+        self.public = self.instances(x)[0]
         return reg
+
+    def instances(self, x, outputs=None):
+        """the instance column of a witness (prepare_public_inputs): the input where it is public, then the output where it is;
+        outputs: None = those of the last synthesis"""
+        outputs = self.outputs if outputs is None else outputs
+        return [([int(v) % R for v in x] if self.visibility[0] == "Public" else []) +
+                ([int(v) % R for v in outputs] if self.visibility[2] == "Public" else [])]
+
+    def witness_of(self, reg):
+        n = 1 << self.k
+        return [reg.advice.get(c.index) or [0] * n for c in self.gc.cs.advice], [self.public]
 
 
 def _given_parameters(circuit, **arrays):

@@ -1376,7 +1376,10 @@ def _record_general_einsum(circuit):
 
 def params_hash(circuit):
     """what a plan depends on besides the layout code: the circuit's `plan_identity()` bytes -- its shape options and its parameters -- and
-    its static lookup tables.  (The domain prefix is keyed on the circuit: none for an MlpCircuit, whose hashes stay what they were.)"""
+    its static lookup tables.  (The domain prefix is keyed on the circuit: none for an MlpCircuit, whose hashes stay what they were.)
+    An MlpCircuit's identity takes its visibility triple in unless it is the default one: the module columns of a KZG-committed tensor, the
+    instance-fed cells of a public input and the constants of Fixed parameters are INPUT / PARAM / CONST / COPY records of another plan,
+    and a `.wplan` written for another triple next to a key is recorded again, not replayed."""
     h = hashlib.sha256()
     if type(circuit) is EL.EinsumMatmulCircuit:
         h.update(b"phased:" + circuit.plan_identity())
