@@ -144,6 +144,7 @@ def _build_mlp(d):
 
 _REQUIRED = object()
 _PARAMETER_ARRAYS = ("kernels", "conv_bias", "fc_w", "fc_b")
+_CIRCUIT_RUN_ARGS = ("logrows", "num_inner_cols", "decomp_base", "decomp_legs")      # the run_args that are constructor arguments of a circuit
 
 
 def _int_field(j, name, least=None, default=_REQUIRED, prefix=""):
@@ -242,31 +243,26 @@ def _configured(model, make):
         raise ValueError("compiled circuit: the \"%s\" description cannot be configured: %s" % (model, e or type(e).__name__)) from None
 
 
-def _build_conv(d):
-    ra, f = d["run_args"], d["fields"]
-    if f["kernel"] > f["image"]:
-        raise ValueError("compiled circuit: \"kernel\" is larger than \"image\"")
-    return _configured("conv", lambda: EL.ConvMnistCircuit(
-        ra["logrows"], f["image"], f["kernel"], f["out_channels"], f["stride"], f["classes"], f["lookup_range"], f["denom"], ra["decomp_base"],
-        ra["decomp_legs"], num_inner_cols=ra["num_inner_cols"], capacity=f["capacity"], **{name: f[name] for name in _PARAMETER_ARRAYS}))
+def _build_layout(d):
+    """the circuit of a description that states its layout: the family's cross-field checks, then its class over the validated fields --
+    the family's own ("fields") and the four of run_args that configure a circuit, by the constructor's parameter names"""
+    family = _family(d["family"])
+    family.check(d)
+    args = dict(d["fields"], **{name: d["run_args"][name] for name in _CIRCUIT_RUN_ARGS})
+    return _configured(d["family"], lambda: family.circuit(**args))
 
 
-def _build_pool(d):
-    ra, f = d["run_args"], d["fields"]
+def _conv_fits(d):
+    f = d["fields"]
     if f["kernel"] > f["image"]:
         raise ValueError("compiled circuit: \"kernel\" is larger than \"image\"")
+
+
+def _pool_fits(d):
+    f = d["fields"]
+    _conv_fits(d)
     if f["pool_size"] > (f["image"] - f["kernel"]) // f["stride"] + 1:
         raise ValueError("compiled circuit: \"pool_size\" is larger than the convolution's output")
-    return _configured("pool_classifier", lambda: EL.PoolClassifierCircuit(
-        ra["logrows"], ra["num_inner_cols"], f["capacity"], f["image"], f["kernel"], f["out_channels"], f["stride"], f["pool_size"], f["pool_stride"],
-        f["classes"], f["pool"], ra["decomp_base"], ra["decomp_legs"], **{name: f[name] for name in _PARAMETER_ARRAYS}))
-
-
-def _build_norm(d):
-    ra, f = d["run_args"], d["fields"]
-    return _configured("norm", lambda: EL.NormCircuit(
-        ra["logrows"], ra["num_inner_cols"], f["capacity"], f["rows"], f["length"], f["input_scale"], f["output_scale"], f["eps"], f["layer_norm"],
-        ra["decomp_base"], ra["decomp_legs"], f["lookup_range"]))
 
 
 _ATTENTION_WEIGHTS = ("Wq", "Wk", "Wv")
@@ -274,19 +270,11 @@ _ATTENTION_FIELDS = [(name, _positive) for name in ("n", "e", "d", "capacity", "
                     [("eps", _eps_field), ("lookup_range", _range_field)] + [(name, _parameter_field) for name in _ATTENTION_WEIGHTS]
 
 
-def _one_inner_column(d, model):
+def _one_inner_column(d):
     """the einsum layout's own rule, named as a field: a wider block folds num_inner_cols entries a row in its RLC gate, which neither
     ezkl_layout.EinsumCircuit lays out nor a witness plan's RLC record states"""
     if d["run_args"]["num_inner_cols"] != 1:
-        raise ValueError("compiled circuit: \"run_args.num_inner_cols\" must be 1 in the \"%s\" family: %s" % (model, EL.EINSUM_WIDTH_ERROR))
-
-
-def _build_attention(d):
-    ra, f = d["run_args"], d["fields"]
-    _one_inner_column(d, "attention")
-    return _configured("attention", lambda: EL.AttentionHeadCircuit(
-        ra["logrows"], f["n"], f["e"], f["d"], f["capacity"], ra["num_inner_cols"], f["input_scale"], f["output_scale"], f["eps"], f["score_div"],
-        ra["decomp_base"], ra["decomp_legs"], f["lookup_range"], **{name: f[name] for name in _ATTENTION_WEIGHTS}))
+        raise ValueError("compiled circuit: \"run_args.num_inner_cols\" must be 1 in the \"%s\" family: %s" % (d["family"], EL.EINSUM_WIDTH_ERROR))
 
 
 def _integer_rows(j, name, depth):
@@ -322,15 +310,17 @@ def _describe_mlp_batch(j):
     if "output_scale" in j:
         _int_field(j, "output_scale")
     d = _describe_mlp(dict(j, run_args=ra))
-    return dict(d, batch=m, n_inputs=m * len(weights[0][0]), capacity=_optional(_positive)(j, "capacity"))
+    fields = dict({name: d[name] for name in ("weights", "biases", "relu_last", "relu_first", "rebase")}, batch=m, capacity=_optional(_positive)(j, "capacity"))
+    return dict(d, n_inputs=m * len(weights[0][0]), fields=fields)
 
 
-def _build_mlp_batch(d):
-    ra = d["run_args"]
-    _one_inner_column(d, "mlp_batch")
-    return _configured("mlp_batch", lambda: EL.BatchMlpCircuit(
-        ra["logrows"], ra["num_inner_cols"], d["batch"], d["weights"], d["biases"], ra["decomp_base"], ra["decomp_legs"], capacity=d["capacity"],
-        relu_last=d["relu_last"], relu_first=d["relu_first"], rebase=d["rebase"]))
+def _mlp_batch_scales(run_args, fields, output_scale):
+    """what a written "mlp_batch" description says of its scales, by _describe_mlp's rules: they go with the rebase divisors -- a circuit
+    that rescales nothing states neither divisors nor an output scale --, and run_args has no output_scale"""
+    del run_args["output_scale"]
+    rebase = fields.pop("rebase")
+    if any(d != 1 for d in rebase):
+        fields.update(rebase=list(rebase), output_scale=output_scale)
 
 
 def _forward_layout(d, x):
@@ -387,19 +377,25 @@ def _forward_mlp(d, x):
 # THE families a JSON description may name: how its fields are read, how the circuit is built from them, and gen_witness's forward pass on
 # the host.  (The reference's own model.compiled is the MLP family's.)  The standalone einsum, the transformer surrogate and the SortTopk,
 # SumProd and ScatterGather circuits are in neither table: naming one is "unsupported compiled circuit".
-Family = collections.namedtuple("Family", "describe build forward")
+# A family that states its layout also names its circuit class -- built from the validated fields by the constructor's parameter names
+# (_build_layout, after the family's cross-field `check`) and written back from the class's `config()` (describe; `scales` adjusts what
+# is written of the scales) --; the MLP family reads the reference's files too and has a builder and no writer of its own.
+Family = collections.namedtuple("Family", "describe build forward circuit check scales", defaults=(None,) + (lambda *args: None,) * 2)
 FAMILIES = {
     "mlp": Family(_describe_mlp, _build_mlp, _forward_mlp),
-    "conv": Family(lambda j: _describe_layout(j, _CONV_FIELDS, lambda f: f["image"] ** 2), _build_conv, _forward_layout),
-    "pool_classifier": Family(lambda j: _describe_layout(j, _POOL_FIELDS, lambda f: f["image"] ** 2), _build_pool, _forward_layout),
-    "norm": Family(lambda j: _describe_layout(j, _NORM_FIELDS, lambda f: f["rows"] * f["length"]), _build_norm, _forward_layout),
+    "conv": Family(lambda j: _describe_layout(j, _CONV_FIELDS, lambda f: f["image"] ** 2), _build_layout, _forward_layout, EL.ConvMnistCircuit, _conv_fits),
+    "pool_classifier": Family(lambda j: _describe_layout(j, _POOL_FIELDS, lambda f: f["image"] ** 2), _build_layout, _forward_layout,
+                              EL.PoolClassifierCircuit, _pool_fits),
+    "norm": Family(lambda j: _describe_layout(j, _NORM_FIELDS, lambda f: f["rows"] * f["length"]), _build_layout, _forward_layout, EL.NormCircuit),
 }
 # the families whose circuits lay Freivalds einsums over their own configuration -- second-phase advice, two-phase plans (_phased) --,
 # read, built and run as the ones above are (`_family` looks a name up in both tables); the host forward pass is the layout's first phase
 PHASED_FAMILIES = {
-    "mlp_batch": Family(_describe_mlp_batch, _build_mlp_batch, _forward_layout),
-    "attention": Family(lambda j: _describe_layout(j, _ATTENTION_FIELDS, lambda f: f["n"] * f["e"]), _build_attention, _forward_layout),
+    "mlp_batch": Family(_describe_mlp_batch, _build_layout, _forward_layout, EL.BatchMlpCircuit, _one_inner_column, _mlp_batch_scales),
+    "attention": Family(lambda j: _describe_layout(j, _ATTENTION_FIELDS, lambda f: f["n"] * f["e"]), _build_layout, _forward_layout,
+                        EL.AttentionHeadCircuit, _one_inner_column),
 }
+_DESCRIBED = {family.circuit: name for name, family in {**FAMILIES, **PHASED_FAMILIES}.items() if family.circuit is not None}
 
 
 def _family(name):
@@ -409,29 +405,17 @@ def _family(name):
 
 def describe(circuit, input_scale=0, output_scale=0):
     """the JSON description (a dict) of a ConvMnistCircuit, a PoolClassifierCircuit, a NormCircuit, an AttentionHeadCircuit or a
-    BatchMlpCircuit: what `_load_circuit` builds the same circuit from -- same plan_identity, same settings.  (A BatchMlpCircuit that
-    rescales nothing is at scale 0, as the MLP description is: input_scale and output_scale go with its rebase divisors.)"""
-    ra = dict(logrows=circuit.k, num_inner_cols=circuit.w, decomp_base=circuit.base, decomp_legs=circuit.legs, input_scale=input_scale, output_scale=output_scale)
-    params = lambda: {name: np.asarray(getattr(circuit, name)).tolist() for name in _PARAMETER_ARRAYS}
-    if type(circuit) is EL.ConvMnistCircuit:
-        return dict(model="conv", run_args=ra, image=circuit.image, kernel=circuit.kernel, out_channels=circuit.oc, stride=circuit.stride, classes=circuit.classes,
-                    lookup_range=list(circuit.lookup_range), denom=circuit.denom, capacity=circuit.capacity, **params())
-    if type(circuit) is EL.PoolClassifierCircuit:
-        return dict(model="pool_classifier", run_args=ra, image=circuit.image, kernel=circuit.kernel, out_channels=circuit.oc, stride=circuit.stride,
-                    pool_size=circuit.pool_size, pool_stride=circuit.pool_stride, classes=circuit.classes, pool=circuit.pool, capacity=circuit.capacity, **params())
-    if type(circuit) is EL.NormCircuit:
-        return dict(model="norm", run_args=ra, rows=circuit.rows, length=circuit.length, input_scale=circuit.input_scale, output_scale=circuit.output_scale,
-                    eps=circuit.eps, layer_norm=circuit.layer_norm, lookup_range=list(circuit.lookup_range), capacity=circuit.capacity)
-    if type(circuit) is EL.AttentionHeadCircuit:
-        return dict(model="attention", run_args=ra, n=circuit.n, e=circuit.e, d=circuit.d, capacity=circuit.capacity, input_scale=circuit.input_scale,
-                    output_scale=circuit.output_scale, eps=circuit.eps, score_div=circuit.score_div, lookup_range=list(circuit.lookup_range),
-                    **{name: np.asarray(getattr(circuit, name)).tolist() for name in _ATTENTION_WEIGHTS})
-    if type(circuit) is EL.BatchMlpCircuit:                                       # _describe_mlp's rules: the scales go with the rebase divisors
-        ra = {name: v for name, v in ra.items() if name != "output_scale"}
-        scaled = dict(rebase=list(circuit.rebase), output_scale=output_scale) if any(d != 1 for d in circuit.rebase) else {}
-        return dict(model="mlp_batch", run_args=ra, batch=circuit.m, weights=circuit.weights, biases=circuit.biases, relu_last=circuit.relu_last,
-                    relu_first=circuit.relu_first, capacity=circuit.capacity, **scaled)
-    raise ValueError("no JSON description for a %s" % type(circuit).__name__)
+    BatchMlpCircuit: what `_load_circuit` builds the same circuit from -- same plan_identity, same settings.  It is the circuit's
+    `config()`: run_args holds the fields of _CIRCUIT_RUN_ARGS and the two scales, every other field stands under its own name, arrays as
+    lists; the seed is left out, the parameter arrays it seeded are all there.  (A BatchMlpCircuit that rescales nothing is at scale 0,
+    as the MLP description is: input_scale and output_scale go with its rebase divisors.)"""
+    name = _DESCRIBED.get(type(circuit))
+    if name is None:
+        raise ValueError("no JSON description for a %s" % type(circuit).__name__)
+    fields = {key: np.asarray(v).tolist() if isinstance(v, (np.ndarray, tuple)) else v for key, v in circuit.config().items() if key != "seed"}
+    run_args = dict({key: fields.pop(key) for key in _CIRCUIT_RUN_ARGS}, input_scale=input_scale, output_scale=output_scale)
+    _family(name).scales(run_args, fields, output_scale)
+    return dict(model=name, run_args=run_args, **fields)
 
 
 def _load_circuit(path):
@@ -745,18 +729,13 @@ def _first_phase(plan, x, columns=None):
 def _host_advice(circuit, x, region=None):
     """the advice(phase, challenges) callable of native.create_proof and native.mock over the HOST layout of a phased circuit: phase 0 is
     `region` (the first-phase synthesis the caller already has, else made here), phase p > 0 the layout laid again with the challenges
-    squeezed so far.  -> (the callable, columns: {column index: list of ints}, filled as the phases are asked for)"""
-    cs0, n = circuit.gc.cs, 1 << circuit.k
-    first, columns = [region], {}
+    squeezed so far (ezkl_layout.host_phase_columns).  -> (the callable, columns: {column index: list of ints}, filled as the phases
+    are asked for)"""
+    per_phase, columns = EL.host_phase_columns(circuit, x, region), {}
     def advice(phase, challenges):
-        if phase == 0:
-            first[0] = reg = first[0] if first[0] is not None else circuit.synthesize(x, True)
-        else:
-            reg = circuit.synthesize(x, True, tuple(challenges[:len(cs0.challenges)]))
-        idx = [c.index for c in cs0.advice if c.phase == phase]
-        cols = [reg.advice.get(i) or [0] * n for i in idx]
-        columns.update(zip(idx, cols))
-        return dict(zip(idx, EL.cols_to_mont(cols, B)))
+        cols = per_phase(phase, challenges)
+        columns.update(cols)
+        return dict(zip(cols, EL.cols_to_mont(list(cols.values()), B)))
     return advice, columns
 
 

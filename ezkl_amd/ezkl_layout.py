@@ -156,6 +156,7 @@ class Val:
 
 class EinsumMatmulCircuit:
     """benches/accum_einsum_matmul.rs MyCircuit for "ij,jk->ik" with square len x len inputs"""
+    plan_domain, plan_tables = b"phased:", False       # (what witness_plan asks of a class: see LayoutCircuit)
 
     def __init__(self, k, length, num_inner_cols=1):
         self.k, self.len, self.w = k, length, num_inner_cols
@@ -385,6 +386,7 @@ class EinsumCircuit(EinsumMatmulCircuit):
     row-major in the order of its own expression.  With standalone columns (this constructor) max_num_output_axes and the capacity come
     from the analysis; `over` lays the same sequence over the Freivalds columns of a GraphConfig.  Three or more operands (`multi_dot`),
     the base-op strategy and a column that overflows into a second block are refused by name."""
+    plan_domain = b"einsum:"
 
     def __init__(self, k, equation, dims, num_inner_cols=1):
         self._plan(k, equation, dims, num_inner_cols)
@@ -1246,6 +1248,25 @@ class BaseRegion(Region):
                     self.flush()
         return self.div(out, kernel[0] * kernel[1]) if normalized else out
 
+    def conv(self, kernels, image, bias, channels, side, kernel, stride):
+        """layouts.rs:4499-4661 of ONE input channel, a square `side` x `side` image and `channels` square filters, all row-major: kernels
+        and image are assigned once, side by side (every patch / filter slice below is a copy of those cells); then per output, in the
+        order (channel, row, column), one `dot` of the patch with the filter and the channel's bias added.  bias(o) -> the Val of channel
+        o's bias, asked for at every output position -> the outputs, row-major"""
+        K, slides = kernel, (side - kernel) // stride + 1
+        ker = self.assign(self.inputs[0], kernels)
+        im = self.assign(self.inputs[1], image)
+        self.increment(max(len(ker), len(im)))
+        out = []
+        for o in range(channels):
+            for i in range(slides):
+                for j in range(slides):
+                    patch = [im[(i * stride + a) * side + j * stride + b] for a in range(K) for b in range(K)]
+                    res = self.pairwise([self.dot(patch, ker[o * K * K:(o + 1) * K * K])], [bias(o)], EC.ADD)
+                    self.flush()
+                    out.append(res[0])
+        return out
+
     # ---- the indexed family: gather, scatter, one-hot ---------------------------------------------------------------------------------
     def select_elements(self, vals, indices):
         """layouts.rs:1363-1396 `select` for many picks in ONE dynamic lookup (:1483-1581): table side (the position as a constant, vals_j,
@@ -1468,8 +1489,31 @@ class BaseRegion(Region):
 
 
 class LayoutCircuit:
-    """what every circuit built on BaseRegion shares: the keygen pass (selector activations, fixed columns, copy constraints)
-    and the witness pass; subclasses give `synthesize(x, witness) -> region` and set self.outputs"""
+    """what every circuit built on BaseRegion shares: the synthesis pass over its `layout(reg, inputs, param[, challenges]) -> outputs`,
+    the keygen pass (selector activations, fixed columns, copy constraints) and the witness pass.  Subclasses give `layout`, `n_inputs`,
+    `plan_identity()` and `config()`: the constructor's keyword arguments, read off the attributes as they are now -- the ONE statement
+    of a family's fields, which `fresh()` and execute.describe go through.
+    What witness_plan asks of a circuit's class: plan_domain, the prefix of its params_hash (None: b"layout:<ClassName>:"; the empty one
+    marks the MLP family, whose hashes and blobs stay what they were before plans held lookups); plan_tables, whether the static lookup
+    tables are hashed in; lays_einsums, whether it lays Freivalds einsums over its own configuration (second-phase advice, a plan with
+    phases)."""
+    plan_domain, plan_tables, lays_einsums = None, True, False
+
+    def synthesize(self, x, witness=True, challenges=None):
+        """one pass of `layout` over a BaseRegion with the values of x (any shape, row-major) -> the region; sets self.outputs.
+        challenges: given to a layout with phases (None lays its first phase only)"""
+        x = np.asarray(x, dtype=object).reshape(-1).tolist()
+        assert len(x) == self.n_inputs
+        reg = BaseRegion(self.gc, witness)
+        outs = self.layout(reg, [Val(int(v)) for v in x], lambda v: Val(int(v)), *(() if challenges is None else (challenges,)))
+        reg.finish(self.gc.const_cols)
+        self.outputs = [v.v for v in outs]
+        return reg
+
+    def fresh(self):
+        """the same circuit, its fields and parameters as they are now, with an untouched constraint system (compress_selectors
+        rewrites a system in place)"""
+        return type(self)(**self.config())
 
     def keygen_inputs(self, x, with_witness=False):
         """-> (plonk.ConstraintSystem, fixed columns (lists of ints), copies over cs.perm positions, region); with_witness: ONE synthesis
@@ -1556,6 +1600,7 @@ class MlpCircuit(LayoutCircuit):
                   distinct value, shared with the layout's own constants; BaseRegion.put / finish), so the parameters are part of the key
 
     `instances(x)` is the instance column of a witness (prepare_public_inputs, src/graph/mod.rs:1411-1446)."""
+    plan_domain = b""
 
     def __init__(self, logrows, num_inner_cols, weights, biases, decomp_base, decomp_legs, total_assignments=None, relu_last=True,
                  n_inputs=None, relu_first=False, rebase=None, visibility=None, total_const_size=None):
@@ -1688,17 +1733,13 @@ class MlpCircuit(LayoutCircuit):
             ident += ("visibility:%s/%s/%s" % self.visibility).encode()
         return ident
 
-    def fresh(self):
-        """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
-        return MlpCircuit(self.k, self.w, self.weights, self.biases, self.base, self.legs, total_assignments=self.settings.total_assignments,
-                          relu_last=self.relu_last, n_inputs=self.n_inputs, relu_first=self.relu_first, rebase=self.rebase,
-                          visibility=self.visibility, total_const_size=self.settings.total_const_size)
+    def config(self):
+        return dict(logrows=self.k, num_inner_cols=self.w, weights=self.weights, biases=self.biases, decomp_base=self.base, decomp_legs=self.legs,
+                    total_assignments=self.settings.total_assignments, relu_last=self.relu_last, n_inputs=self.n_inputs,
+                    relu_first=self.relu_first, rebase=self.rebase, visibility=self.visibility, total_const_size=self.settings.total_const_size)
 
     def synthesize(self, x, witness=True):
-        reg = BaseRegion(self.gc, witness)
-        outs = self.layout(reg, [Val(int(v)) for v in x], Val)
-        reg.finish(self.gc.const_cols)
-        self.outputs = [v.v for v in outs]
+        reg = super().synthesize(x, witness)
         self.public = self.instances(x)[0]
         return reg
 
@@ -1783,10 +1824,10 @@ class ConvMnistCircuit(LayoutCircuit):
         _given_parameters(self, kernels=kernels, conv_bias=conv_bias, fc_w=fc_w, fc_b=fc_b)
         self.gc = ConvMnistConfig(logrows, self.length, lookup_range, denom, decomp_base, num_inner_cols, capacity)
 
-    def fresh(self):
-        """the same circuit, its parameters as they are now, with an untouched constraint system (compress_selectors rewrites a system in place)"""
-        return ConvMnistCircuit(self.k, self.image, self.kernel, self.oc, self.stride, self.classes, self.lookup_range, self.denom, self.base, self.legs,
-                                self.seed, self.w, self.capacity, self.kernels, self.conv_bias, self.fc_w, self.fc_b)
+    def config(self):
+        return dict(logrows=self.k, image=self.image, kernel=self.kernel, out_channels=self.oc, stride=self.stride, classes=self.classes,
+                    lookup_range=self.lookup_range, denom=self.denom, decomp_base=self.base, decomp_legs=self.legs, seed=self.seed,
+                    num_inner_cols=self.w, capacity=self.capacity, kernels=self.kernels, conv_bias=self.conv_bias, fc_w=self.fc_w, fc_b=self.fc_b)
 
     def model(self, img):
         """the integer forward pass the circuit proves"""
@@ -1801,21 +1842,7 @@ class ConvMnistCircuit(LayoutCircuit):
         """the op sequence, stated once: `synthesize` runs it on a BaseRegion with the image's values, witness_plan.record_plan on a
         recording region with symbols.  inputs: the image, row-major, as Vals; param(v) -> the Val of a circuit parameter (they are
         asked for in a fixed order: kernels, then per output its conv bias, the linear layer's rows, its biases)"""
-        s, K, st = self.slides, self.kernel, self.stride
-        # conv: kernel and image are assigned once, side by side; every patch / filter slice below is a copy of those cells
-        ker = reg.assign(reg.inputs[0], [param(v) for v in self.kernels.reshape(-1)])
-        im = reg.assign(reg.inputs[1], inputs)
-        reg.increment(max(len(ker), len(im)))
-        ker = [ker[o * K * K:(o + 1) * K * K] for o in range(self.oc)]
-        vals = []
-        for o in range(self.oc):
-            for i in range(s):
-                for j in range(s):
-                    patch = [im[(i * st + a) * self.image + j * st + b] for a in range(K) for b in range(K)]
-                    res = reg.dot(patch, ker[o])
-                    res = reg.pairwise([res], [param(self.conv_bias[o])], EC.ADD)
-                    reg.flush()
-                    vals.append(res[0])
+        vals = reg.conv([param(v) for v in self.kernels.reshape(-1)], inputs, lambda o: param(self.conv_bias[o]), self.oc, self.image, self.kernel, self.stride)
         vals = reg.relu(vals, self.base, self.legs)
         vals = reg.nonlinearity(vals, "div_%d" % self.denom)
         outs = [reg.dot([param(v) for v in row], vals) for row in self.fc_w]
@@ -1829,23 +1856,18 @@ class ConvMnistCircuit(LayoutCircuit):
                  self.gc.advices[0].num_blocks()]
         return b"".join(np.asarray(a, np.int64).tobytes() for a in (shape, self.kernels, self.conv_bias, self.fc_w, self.fc_b))
 
-    def synthesize(self, img, witness=True):
-        reg = BaseRegion(self.gc, witness)
-        img = np.asarray(img, np.int64).reshape(self.image, self.image)
-        outs = self.layout(reg, [Val(int(v) % R) for v in img.reshape(-1)], lambda v: Val(int(v) % R))
-        reg.finish(self.gc.const_cols)
-        self.outputs = [v.v for v in outs]
-        return reg
-
 
 class SumProdCircuit(LayoutCircuit):
     """the accumulated SUM / CUMPROD gates of BaseConfig (chip.rs:343-359, base.rs) on a private vector: instance = [sum(x), prod(x),
     sum of the pairwise products x_i * x_{i+1}] -- used by the tests that drive the gates the MLP / conv circuits never switch on"""
 
     def __init__(self, logrows, num_inner_cols, capacity):
-        self.k, self.w = logrows, num_inner_cols
+        self.k, self.w, self.capacity = logrows, num_inner_cols, capacity
         self.settings = EC.GraphSettings(logrows, num_inner_cols, capacity, total_const_size=4, required_range_checks=[], model_instance_shapes=[[1, 3]])
         self.gc = EC.GraphConfig(self.settings)
+
+    def config(self):
+        return dict(logrows=self.k, num_inner_cols=self.w, capacity=self.capacity)
 
     def synthesize(self, x, witness=True):
         reg = BaseRegion(self.gc, witness)
@@ -1865,10 +1887,14 @@ class SumProdCircuit(LayoutCircuit):
 class SumProdLayoutCircuit(SumProdCircuit):
     """SumProdCircuit with its op sequence stated once (`layout`), so that witness_plan.record_plan can run it on symbols: the same
     cells, values, selectors and copies as its parent's `synthesize`.  length: the number of inputs."""
+    synthesize = LayoutCircuit.synthesize              # (not the parent's: that one states the ops a second time)
 
     def __init__(self, logrows, num_inner_cols, capacity, length):
         super().__init__(logrows, num_inner_cols, capacity)
         self.n_inputs = int(length)
+
+    def config(self):
+        return dict(super().config(), length=self.n_inputs)
 
     def layout(self, reg, inputs, param):
         vals = reg.assign(reg.inputs[0], inputs)
@@ -1884,14 +1910,6 @@ class SumProdLayoutCircuit(SumProdCircuit):
     def plan_identity(self):
         return np.asarray([self.k, self.w, self.n_inputs, self.gc.advices[0].num_blocks()], np.int64).tobytes()
 
-    def synthesize(self, x, witness=True):
-        assert len(x) == self.n_inputs
-        reg = BaseRegion(self.gc, witness)
-        outs = self.layout(reg, [Val(int(v) % R) for v in x], Val)
-        reg.finish(self.gc.const_cols)
-        self.outputs = [v.v for v in outs]
-        return reg
-
 
 class SortTopkCircuit(LayoutCircuit):
     """a top-k and a full sort of one private vector (layouts.rs `topk_axes` / `_sort_ascending`): instance = the k_top largest (or
@@ -1901,7 +1919,7 @@ class SortTopkCircuit(LayoutCircuit):
 
     def __init__(self, logrows, num_inner_cols, capacity, length, k_top, largest=True, mode="unsorted", decomp_base=16, decomp_legs=2):
         assert mode in SORT_MODES and 1 <= k_top <= length
-        self.k, self.w, self.n_inputs = logrows, num_inner_cols, int(length)
+        self.k, self.w, self.capacity, self.n_inputs = logrows, num_inner_cols, capacity, int(length)
         self.k_top, self.largest, self.mode, self.base, self.legs = int(k_top), bool(largest), mode, decomp_base, decomp_legs
         checks = [(-1, 1), (0, decomp_base - 1)] + ([(0, 1)] if mode != "unsorted" else [])
         self.settings = EC.GraphSettings(logrows, num_inner_cols, capacity, total_const_size=4, required_range_checks=checks,
@@ -1923,13 +1941,9 @@ class SortTopkCircuit(LayoutCircuit):
         shape = [self.k, self.w, self.n_inputs, self.k_top, int(self.largest), SORT_MODES.index(self.mode), self.base, self.legs, self.gc.advices[0].num_blocks()]
         return np.asarray(shape, np.int64).tobytes()
 
-    def synthesize(self, x, witness=True):
-        assert len(x) == self.n_inputs
-        reg = BaseRegion(self.gc, witness)
-        outs = self.layout(reg, [Val(int(v) % R) for v in x], Val)
-        reg.finish(self.gc.const_cols)
-        self.outputs = [v.v for v in outs]
-        return reg
+    def config(self):
+        return dict(logrows=self.k, num_inner_cols=self.w, capacity=self.capacity, length=self.n_inputs, k_top=self.k_top, largest=self.largest,
+                    mode=self.mode, decomp_base=self.base, decomp_legs=self.legs)
 
 
 class NormCircuit(LayoutCircuit):
@@ -1976,18 +1990,10 @@ class NormCircuit(LayoutCircuit):
                  self.lookup_range[0], self.lookup_range[1], self.gc.advices[0].num_blocks()]
         return np.asarray(shape, np.int64).tobytes() + np.float64(self.eps).tobytes()
 
-    def fresh(self):
-        """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
-        return NormCircuit(self.k, self.w, self.capacity, self.rows, self.length, self.input_scale, self.output_scale, self.eps, self.layer_norm,
-                           self.base, self.legs, self.lookup_range)
-
-    def synthesize(self, x, witness=True):
-        assert len(x) == self.n_inputs
-        reg = BaseRegion(self.gc, witness)
-        outs = self.layout(reg, [Val(int(v) % R) for v in x], Val)
-        reg.finish(self.gc.const_cols)
-        self.outputs = [v.v for v in outs]
-        return reg
+    def config(self):
+        return dict(logrows=self.k, num_inner_cols=self.w, rows=self.rows, length=self.length, input_scale=self.input_scale,
+                    output_scale=self.output_scale, eps=self.eps, layer_norm=self.layer_norm, decomp_base=self.base, decomp_legs=self.legs,
+                    lookup_range=self.lookup_range, capacity=self.capacity)
 
 
 class PoolClassifierCircuit(LayoutCircuit):
@@ -2042,20 +2048,8 @@ class PoolClassifierCircuit(LayoutCircuit):
         """inputs: the image, row-major, as Vals; param(v) -> the Val of a circuit parameter (asked for in a fixed order: kernels, then per
         output its conv bias, the linear layer's rows, its biases)"""
         reg.decomp = (self.base, self.legs)
-        s, K, st = self.slides, self.kernel, self.stride
-        ker = reg.assign(reg.inputs[0], [param(v) for v in self.kernels.reshape(-1)])
-        im = reg.assign(reg.inputs[1], inputs)
-        reg.increment(max(len(ker), len(im)))
-        ker = [ker[o * K * K:(o + 1) * K * K] for o in range(self.oc)]
-        vals = []
-        for o in range(self.oc):
-            for i in range(s):
-                for j in range(s):
-                    patch = [im[(i * st + a) * self.image + j * st + b] for a in range(K) for b in range(K)]
-                    res = reg.dot(patch, ker[o])
-                    res = reg.pairwise([res], [param(self.conv_bias[o])], EC.ADD)
-                    reg.flush()
-                    vals.append(res[0])
+        s = self.slides
+        vals = reg.conv([param(v) for v in self.kernels.reshape(-1)], inputs, lambda o: param(self.conv_bias[o]), self.oc, self.image, self.kernel, self.stride)
         vals = reg.relu(vals, self.base, self.legs)
         geometry = (self.oc, s, s, ((0, 0), (0, 0)), (self.pool_stride,) * 2, (self.pool_size,) * 2)
         vals = reg.max_pool(vals, *geometry) if self.pool == "max" else reg.sumpool(vals, *geometry, True)
@@ -2070,19 +2064,11 @@ class PoolClassifierCircuit(LayoutCircuit):
                  int(self.pool == "max"), self.base, self.legs, self.gc.advices[0].num_blocks()]
         return b"".join(np.asarray(a, np.int64).tobytes() for a in (shape, self.kernels, self.conv_bias, self.fc_w, self.fc_b))
 
-    def fresh(self):
-        """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
-        return PoolClassifierCircuit(self.k, self.w, self.capacity, self.image, self.kernel, self.oc, self.stride, self.pool_size, self.pool_stride,
-                                     self.classes, self.pool, self.base, self.legs, self.seed, self.kernels, self.conv_bias, self.fc_w, self.fc_b)
-
-    def synthesize(self, img, witness=True):
-        reg = BaseRegion(self.gc, witness)
-        img = np.asarray(img, np.int64).reshape(-1)
-        assert len(img) == self.n_inputs
-        outs = self.layout(reg, [Val(int(v) % R) for v in img], lambda v: Val(int(v) % R))
-        reg.finish(self.gc.const_cols)
-        self.outputs = [v.v for v in outs]
-        return reg
+    def config(self):
+        return dict(logrows=self.k, num_inner_cols=self.w, image=self.image, kernel=self.kernel, out_channels=self.oc, stride=self.stride,
+                    pool_size=self.pool_size, pool_stride=self.pool_stride, classes=self.classes, pool=self.pool, decomp_base=self.base,
+                    decomp_legs=self.legs, seed=self.seed, capacity=self.capacity, kernels=self.kernels, conv_bias=self.conv_bias, fc_w=self.fc_w,
+                    fc_b=self.fc_b)
 
 
 class ScatterGatherCircuit(LayoutCircuit):
@@ -2132,18 +2118,9 @@ class ScatterGatherCircuit(LayoutCircuit):
         shape = [self.k, self.w, self.rows, self.cols, self.m, self.picks, self.base, self.legs, self.gc.advices[0].num_blocks()]
         return np.asarray(shape, np.int64).tobytes()
 
-    def fresh(self):
-        """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
-        return ScatterGatherCircuit(self.k, self.w, self.capacity, self.rows, self.cols, self.m, self.picks, self.base, self.legs)
-
-    def synthesize(self, x, witness=True):
-        x = np.asarray(x, np.int64).reshape(-1)
-        assert len(x) == self.n_inputs
-        reg = BaseRegion(self.gc, witness)
-        outs = self.layout(reg, [Val(int(v) % R) for v in x], Val)
-        reg.finish(self.gc.const_cols)
-        self.outputs = [v.v for v in outs]
-        return reg
+    def config(self):
+        return dict(logrows=self.k, num_inner_cols=self.w, capacity=self.capacity, rows=self.rows, cols=self.cols, m=self.m, picks=self.picks,
+                    decomp_base=self.base, decomp_legs=self.legs)
 
 
 class _CopyArray:
@@ -2175,6 +2152,7 @@ class TransformerSurrogateCircuit:
     move with their tile, the lookup arguments are multiset statements over all rows), so the circuit is FULL (every tile is a valid
     witness of the same statement) without minutes of Python per cell and without a laid-out circuit in the repository.  Only the first
     tile's outputs are tied to the instance column."""
+    lays_einsums = True                                # (what witness_plan asks of a class: see LayoutCircuit)
 
     def __init__(self, logrows, blocks=4, num_inner_cols=1, d=16, einsum_len=16, decomp_base=16384, decomp_legs=2, lookup_max=None, seed=1):
         import math
@@ -2280,10 +2258,7 @@ class TransformerSurrogateCircuit:
         witness plan; `advice` then returns {column: DeviceBuffer} of one resident set of columns, `device_columns` names them for
         native.create_proof(..., device_columns=...), `witness` holds what to free (`free()`), and the instance vector comes from the
         plan's outputs."""
-        if synthesis not in ("host", "device"):
-            raise ValueError("synthesis is \"host\" or \"device\", not %r" % (synthesis,))
-        if synthesis == "device" and (gpu is None or as_ints):
-            raise ValueError("synthesis=\"device\" needs a gpu backend and returns device columns")
+        _check_synthesis(synthesis, gpu, as_ints)
         gc, cs0, n = self.gc, self.gc.cs, 1 << self.k
         inputs = self.default_inputs() if inputs is None else [int(v) for v in inputs]
         reg = BaseRegion(gc, True)
@@ -2408,42 +2383,64 @@ class TransformerSurrogateCircuit:
                     unit_rows=U, tiles=T, blocks=B, cells_used=int(reg.linear) * T * B)
         self.outputs = [v.v for v in h]
         out = dict(cs=cs, fixed=fixed, copies=copies, advice=advice, instances=[self.outputs], info=info)
-        if synthesis == "device":
-            out["witness"] = dev = _DeviceSurrogateWitness(self, gpu, inputs, U, T, colmap)
-            out.update(advice=dev.advice, device_columns=list(range(len(cs0.advice))))
-            try:
-                dev.advice(0, [])                                              # (a failing lane raises here, as the host layout's assertion does above)
-                out["instances"] = [dev.read_outputs()]
-            except Exception:
-                dev.free()
-                raise
+        if synthesis == "device":                                              # (a failing lane raises here, as the host layout's assertion does above)
+            _attach_device_witness(out, _DeviceSurrogateWitness(self, gpu, inputs, U, T, colmap))
         return out
 
 
-class _DeviceSurrogateWitness:
-    """the surrogate's witness made on the device: phase p replays phase p of the circuit's plan into rows [0, U) of the block-0 and
-    shared columns of one resident set, then tiles the columns of that phase (backend.witness_tile) -- U rows repeated T times down
-    each column and into the columns of the other blocks.  phase_ms[p] = (run, tile) device milliseconds of the last call."""
+def _check_synthesis(synthesis, gpu, as_ints):
+    """the `synthesis` argument of a `build`, refused by name where it is unknown or cannot be served"""
+    if synthesis not in ("host", "device"):
+        raise ValueError("synthesis is \"host\" or \"device\", not %r" % (synthesis,))
+    if synthesis == "device" and (gpu is None or as_ints):
+        raise ValueError("synthesis=\"device\" needs a gpu backend and returns device columns")
 
-    def __init__(self, circuit, gpu, inputs, U, T, colmap):
+
+def _attach_device_witness(out, dev):
+    """a `build` result served from the device: `advice` replays the plan, `device_columns` names the resident columns, `witness` holds what
+    to free, and the instance vector is read where phase 0 wrote it.  A witness the device refuses frees everything and raises."""
+    out.update(witness=dev, advice=dev.advice, device_columns=list(range(dev.plan.n_advice)))
+    try:
+        dev.advice(0, [])
+        out["instances"] = [dev.read_outputs()]
+    except Exception:
+        dev.free()
+        raise
+
+
+def host_phase_columns(circuit, x, first=None):
+    """the advice columns of a circuit with phases from its HOST layout, phase by phase: those of phase 0 come from `first` (the first-phase
+    region the caller already has; None: laid when first asked for), those of a phase p > 0 from the layout laid again with the
+    challenges squeezed so far.  -> columns(phase, challenges) -> {column index: list of ints}"""
+    cs0, n, regs = circuit.gc.cs, 1 << circuit.k, [first]
+    def columns(phase, challenges):
+        if phase == 0:
+            reg = regs[0] = regs[0] if regs[0] is not None else circuit.synthesize(x, True)
+        else:
+            reg = circuit.synthesize(x, True, tuple(challenges[:len(cs0.challenges)]))
+        return {c.index: reg.advice.get(c.index) or [0] * n for c in cs0.advice if c.phase == phase}
+    return columns
+
+
+class _DeviceWitness:
+    """a circuit's witness made on the device: phase p replays phase p of the circuit's plan into one resident set of columns.
+    phase_ms[p] = the device milliseconds of the last call."""
+
+    def __init__(self, circuit, gpu, inputs, host_plan=None):
         from . import witness_plan as WP
-        self.gpu, self.inputs, self.U, self.T, self.k = gpu, list(inputs), U, T, circuit.k
-        host_plan = WP.record_plan(circuit)
-        self.plan = gpu.WitnessPlan(host_plan.to_bytes())
+        self.gpu, self.inputs, self.k = gpu, list(inputs), circuit.k
+        self.plan = gpu.WitnessPlan((host_plan or WP.record_plan(circuit)).to_bytes())
         self.columns = self.plan.alloc_columns()
-        # the columns the plan writes are tiled onto themselves and, those of block 0, into their blocks; the run of a phase zero-fills every
-        # column of that phase first, the columns of blocks > 0 and the ones no record writes (phase 0) among them
-        written, phase_of = sorted(WP.written_columns(host_plan)), self.plan.column_phase
-        assert all(len(colmap.get(c, [c])) == 1 or colmap[c][0] == c for c in written), "the plan writes block-0 and shared columns only"
-        self.pairs = {p: [(cb, c) for c in written if phase_of[c] == p for cb in colmap.get(c, [c])] for p in range(self.plan.n_phases)}
         self.outputs, self.phase_ms = None, {}
+
+    def _ran(self, phase, run_ms):
+        """what follows the replay of a phase -> its phase_ms entry"""
+        return run_ms
 
     def advice(self, phase, challenges):
         phase = int(phase)
         _, outs = self.plan.run(self.inputs, columns=self.columns, phase=phase, challenges=list(challenges))
-        run_ms = self.plan.last["device_ms"]
-        self.gpu.witness_tile(self.columns, self.k, self.U, self.T, self.pairs[phase])
-        self.phase_ms[phase] = (run_ms, self.gpu.last_kernel_ms("witness_tile"))   # (reading the tile's events waits for it: the columns are final)
+        self.phase_ms[phase] = self._ran(phase, self.plan.last["device_ms"])
         if phase == self.plan.n_phases - 1:
             self.outputs = outs
         return {c: self.columns[c] for c in range(self.plan.n_advice) if self.plan.column_phase[c] == phase}
@@ -2466,19 +2463,33 @@ class _DeviceSurrogateWitness:
         self.plan.free()
 
 
+class _DeviceSurrogateWitness(_DeviceWitness):
+    """the surrogate's witness made on the device: the replay of a phase fills rows [0, U) of the block-0 and shared columns; the columns
+    of that phase are then tiled (backend.witness_tile) -- U rows repeated T times down each column and into the columns of the other
+    blocks.  phase_ms[p] = (run, tile) device milliseconds of the last call."""
+
+    def __init__(self, circuit, gpu, inputs, U, T, colmap):
+        from . import witness_plan as WP
+        host_plan = WP.record_plan(circuit)
+        super().__init__(circuit, gpu, inputs, host_plan)
+        self.U, self.T = U, T
+        # the columns the plan writes are tiled onto themselves and, those of block 0, into their blocks; the run of a phase zero-fills every
+        # column of that phase first, the columns of blocks > 0 and the ones no record writes (phase 0) among them
+        written, phase_of = sorted(WP.written_columns(host_plan)), self.plan.column_phase
+        assert all(len(colmap.get(c, [c])) == 1 or colmap[c][0] == c for c in written), "the plan writes block-0 and shared columns only"
+        self.pairs = {p: [(cb, c) for c in written if phase_of[c] == p for cb in colmap.get(c, [c])] for p in range(self.plan.n_phases)}
+
+    def _ran(self, phase, run_ms):
+        self.gpu.witness_tile(self.columns, self.k, self.U, self.T, self.pairs[phase])
+        return run_ms, self.gpu.last_kernel_ms("witness_tile")                    # (reading the tile's events waits for it: the columns are final)
+
+
 class PhasedLayoutCircuit(LayoutCircuit):
     """what the circuits share that lay Freivalds einsums over their own configuration (`BaseRegion.einsum`) and so have second-phase
-    advice: `layout(reg, inputs, param, challenges=None) -> outputs` states the op sequence, `synthesize` runs it for one phase or for
-    both, `build` gives keygen's and create_proof's inputs with a per-phase advice callable, on the host or from the witness plan.
-    Subclasses give `layout`, `n_inputs`, `default_inputs()`, `plan_identity()` and `fresh()`."""
-
-    def synthesize(self, x, witness=True, challenges=None):
-        assert len(x) == self.n_inputs
-        reg = BaseRegion(self.gc, witness)
-        outs = self.layout(reg, [Val(int(v) % R) for v in x], Val, challenges)
-        reg.finish(self.gc.const_cols)
-        self.outputs = [v.v for v in outs]
-        return reg
+    advice: `layout(reg, inputs, param, challenges=None) -> outputs` states the op sequence (`synthesize` runs it for one phase or for
+    both), `build` gives keygen's and create_proof's inputs with a per-phase advice callable, on the host or from the witness plan.
+    Subclasses give `layout`, `n_inputs`, `default_inputs()`, `plan_identity()` and `config()`."""
+    lays_einsums = True
 
     def build(self, gpu=None, synthesis="host", as_ints=False, inputs=None):
         """-> dict(cs, fixed, copies, advice (callable(phase, challenges) -> {column: Montgomery array}), instances): the inputs of keygen
@@ -2487,34 +2498,20 @@ class PhasedLayoutCircuit(LayoutCircuit):
         Python, once per phase -- or "device" (needs gpu = ezkl_amd.backend): both phases replayed on the device from the circuit's
         witness plan; `advice` then returns {column: DeviceBuffer} of one resident set of columns, `device_columns` names them,
         `witness` holds what to free, and the instance vector is read from the plan's output cells."""
-        if synthesis not in ("host", "device"):
-            raise ValueError("synthesis is \"host\" or \"device\", not %r" % (synthesis,))
-        if synthesis == "device" and (gpu is None or as_ints):
-            raise ValueError("synthesis=\"device\" needs a gpu backend and returns device columns")
+        _check_synthesis(synthesis, gpu, as_ints)
         inputs = self.default_inputs() if inputs is None else [int(v) for v in inputs]
-        cs0, n = self.gc.cs, 1 << self.k
         cs, fixed, copies, reg = self.keygen_inputs(inputs, with_witness=True)
         instances = [list(self.outputs)]
-        def columns_of(region, phase):
-            idx = [c.index for c in cs0.advice if c.phase == phase]
-            cols = [region.advice.get(i) or [0] * n for i in idx]
-            return dict(zip(idx, cols if as_ints else cols_to_mont(cols, gpu)))
-        cache = {}
+        columns, cache = host_phase_columns(self, inputs, reg), {}
         def advice(phase, challenges):
             key = (int(phase), tuple(challenges))
             if key not in cache:
-                cache[key] = columns_of(reg if phase == 0 else self.synthesize(inputs, True, tuple(challenges[:2])), int(phase))
+                cols = columns(int(phase), challenges)
+                cache[key] = cols if as_ints else dict(zip(cols, cols_to_mont(list(cols.values()), gpu)))
             return cache[key]
         out = dict(cs=cs, fixed=fixed, copies=copies, advice=advice, instances=instances)
         if synthesis == "device":
-            out["witness"] = dev = _DeviceAttentionWitness(self, gpu, inputs)
-            out.update(advice=dev.advice, device_columns=list(range(len(cs0.advice))))
-            try:
-                dev.advice(0, [])
-                out["instances"] = [dev.read_outputs()]
-            except Exception:
-                dev.free()
-                raise
+            _attach_device_witness(out, _DeviceWitness(self, gpu, inputs))
         return out
 
 
@@ -2578,10 +2575,10 @@ class AttentionHeadCircuit(PhasedLayoutCircuit):
                  self.lookup_range[0], self.lookup_range[1], self.gc.advices[0].num_blocks()]
         return b"".join(np.asarray(a, np.int64).tobytes() for a in (shape, self.Wq, self.Wk, self.Wv)) + np.float64(self.eps).tobytes()
 
-    def fresh(self):
-        """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
-        return AttentionHeadCircuit(self.k, self.n, self.e, self.d, self.capacity, self.w, self.input_scale, self.output_scale, self.eps,
-                                    self.score_div, self.base, self.legs, self.lookup_range, self.seed, self.Wq, self.Wk, self.Wv)
+    def config(self):
+        return dict(logrows=self.k, n=self.n, e=self.e, d=self.d, capacity=self.capacity, num_inner_cols=self.w, input_scale=self.input_scale,
+                    output_scale=self.output_scale, eps=self.eps, score_div=self.score_div, decomp_base=self.base, decomp_legs=self.legs,
+                    lookup_range=self.lookup_range, seed=self.seed, Wq=self.Wq, Wk=self.Wk, Wv=self.Wv)
 
 
 class BatchMlpCircuit(PhasedLayoutCircuit):
@@ -2678,26 +2675,9 @@ class BatchMlpCircuit(PhasedLayoutCircuit):
         per_layer = [a for W, b in zip(self.weights, self.biases) for a in ([len(W), len(W[0])], W, b)]
         return b"".join(np.asarray(a, np.int64).tobytes() for a in [shape] + per_layer + [self.rebase])
 
-    def fresh(self):
-        """the same circuit with an untouched constraint system (compress_selectors rewrites a system in place)"""
-        return BatchMlpCircuit(self.k, self.w, self.m, self.weights, self.biases, self.base, self.legs, self.capacity, self.relu_last,
-                               self.relu_first, self.rebase)
-
-
-class _DeviceAttentionWitness(_DeviceSurrogateWitness):
-    """the attention head's witness made on the device: phase p replays phase p of the circuit's plan into one resident set of columns.
-    phase_ms[p] = the device milliseconds of the last call."""
-
-    def __init__(self, circuit, gpu, inputs):
-        super().__init__(circuit, gpu, inputs, 0, 1, {})
-
-    def advice(self, phase, challenges):
-        phase = int(phase)
-        _, outs = self.plan.run(self.inputs, columns=self.columns, phase=phase, challenges=list(challenges))
-        self.phase_ms[phase] = self.plan.last["device_ms"]
-        if phase == self.plan.n_phases - 1:
-            self.outputs = outs
-        return {c: self.columns[c] for c in range(self.plan.n_advice) if self.plan.column_phase[c] == phase}
+    def config(self):
+        return dict(logrows=self.k, num_inner_cols=self.w, batch=self.m, weights=self.weights, biases=self.biases, decomp_base=self.base,
+                    decomp_legs=self.legs, relu_last=self.relu_last, relu_first=self.relu_first, capacity=self.capacity, rebase=self.rebase)
 
 
 def limbs_to_mont(cols, gpu=None):

@@ -1376,46 +1376,47 @@ def _record_general_einsum(circuit):
 
 def params_hash(circuit):
     """what a plan depends on besides the layout code: the circuit's `plan_identity()` bytes -- its shape options and its parameters -- and
-    its static lookup tables.  (The domain prefix is keyed on the circuit: none for an MlpCircuit, whose hashes stay what they were.)
+    its static lookup tables, where its class has them hashed in (`plan_tables`).  The domain prefix is the class's `plan_domain`, by
+    default b"layout:<ClassName>:" (none for an MlpCircuit, whose hashes stay what they were).
     An MlpCircuit's identity takes its visibility triple in unless it is the default one: the module columns of a KZG-committed tensor, the
     instance-fed cells of a public input and the constants of Fixed parameters are INPUT / PARAM / CONST / COPY records of another plan,
     and a `.wplan` written for another triple next to a key is recorded again, not replayed."""
-    h = hashlib.sha256()
-    if type(circuit) is EL.EinsumMatmulCircuit:
-        h.update(b"phased:" + circuit.plan_identity())
-        return h.digest()
-    if type(circuit) is EL.EinsumCircuit:
-        h.update(b"einsum:" + circuit.plan_identity())
-        return h.digest()
-    if type(circuit) is not EL.MlpCircuit:
-        h.update(("layout:%s:" % type(circuit).__name__).encode())
-    h.update(circuit.plan_identity())
-    for name, table in sorted(circuit.gc.base.static_tables.items()):
+    h = hashlib.sha256(_plan_domain(circuit) + circuit.plan_identity())
+    for name, table in sorted(circuit.gc.base.static_tables.items()) if getattr(circuit, "plan_tables", True) else ():
         h.update(name.encode() + struct.pack("<3q", table.range[0], table.range[1], table.col_size))
         h.update(_table_values(table).tobytes())
     return h.digest()
+
+
+def _plan_domain(circuit):
+    domain = getattr(circuit, "plan_domain", None)
+    return ("layout:%s:" % type(circuit).__name__).encode() if domain is None else domain
+
+
+_STANDALONE_RECORDERS = {b"phased:": _record_einsum, b"einsum:": _record_general_einsum}
 
 
 def record_plan(circuit):
     """one witness-free layout pass -> WitnessPlan, with the input vector and the parameters as symbols.  A circuit built on BaseRegion
     states its op sequence itself -- `layout(reg, inputs, param) -> outputs`, which its own `synthesize` runs too, with `n_inputs` and
     `plan_identity()` (MlpCircuit, ConvMnistCircuit) -- and is recorded from that; the parameters enter the blob in the order `layout` asks
-    for them.  Only the recording region is chosen here: an MlpCircuit keeps RecordingRegion (latest-fit grouping, `nonlinearity` refused
-    by name: its blobs stay what they were), any other such circuit gets a LookupRecordingRegion.  An EinsumMatmulCircuit with columns of
-    its own (not one laid over another circuit's) is recorded from its `sequence` into a two-phase plan.  Every other circuit class is
-    refused by name."""
-    if type(circuit) is EL.EinsumMatmulCircuit and getattr(circuit, "standalone", False):
-        return _record_einsum(circuit)
-    if type(circuit) is EL.EinsumCircuit and getattr(circuit, "standalone", False):
-        return _record_general_einsum(circuit)
+    for them.  Only the recording region is chosen here, by what the circuit's class declares (ezkl_layout.LayoutCircuit): the one without a
+    domain prefix, MlpCircuit, keeps RecordingRegion (latest-fit grouping, `nonlinearity` refused by name: its blobs stay what they
+    were); one that declares `lays_einsums` -- second-phase advice of its own; such columns without the declaration are refused -- gets
+    a PhasedLookupRecordingRegion and a plan with phases; any other a LookupRecordingRegion.  An EinsumMatmulCircuit or EinsumCircuit
+    with columns of its own (not one laid over another circuit's) is recorded from its `sequence` into a two-phase plan.  Every other
+    circuit class is refused by name."""
+    standalone = _STANDALONE_RECORDERS.get(_plan_domain(circuit))
+    if standalone is not None and getattr(circuit, "standalone", False):
+        return standalone(circuit)
     if not (callable(getattr(circuit, "layout", None)) and callable(getattr(circuit, "plan_identity", None))):
         raise PlanError("witness plans cover MlpCircuit and circuits that state their `layout`, not %s" % type(circuit).__name__)
     if getattr(circuit, "gc", None) is None:
         raise PlanError("witness plans are recorded from a configured circuit: this %s has no configuration" % type(circuit).__name__)
-    phased = type(circuit) in (EL.TransformerSurrogateCircuit, EL.AttentionHeadCircuit, EL.BatchMlpCircuit)      # einsums laid over its own configuration: a two-phase plan
-    if any(c.phase != 0 for c in circuit.gc.cs.advice) and not phased:
+    phased = any(c.phase != 0 for c in circuit.gc.cs.advice)                    # einsums laid over its own configuration: a two-phase plan
+    if phased and not getattr(circuit, "lays_einsums", False):
         raise PlanError("witness plans do not cover second-phase advice")
-    reg = RecordingRegion(circuit.gc) if type(circuit) is EL.MlpCircuit else (PhasedLookupRecordingRegion if phased else LookupRecordingRegion)(circuit.gc)
+    reg = (RecordingRegion if _plan_domain(circuit) == b"" else PhasedLookupRecordingRegion if phased else LookupRecordingRegion)(circuit.gc)
     if (len(circuit.gc.cs.advice) << circuit.k) > 1 << 32:
         raise PlanError("cells are numbered in 32 bits")
     params = []
