@@ -107,6 +107,19 @@ class PinnedArray:
             self._p = None
 
 
+# why ezkl_hip_bases_decompress refuses an encoding (csrc/g1_encoding.hpp; 1 and 3 are POINT_REASONS' numbers)
+COMPRESSED_REASONS = {1: "x coordinate not below the field modulus", 3: "no point with this x (x^3 + 3 is not a square)",
+                      4: "malformed flags (identity flag with a non-zero x or the sign bit)"}
+
+
+class CompressedPointError(ValueError):
+    """a compressed point that is no point: .index in its set, .reason (COMPRESSED_REASONS)"""
+
+    def __init__(self, name, index, reason):
+        super().__init__("%s[%d]: %s" % (name, index, COMPRESSED_REASONS[reason]))
+        self.name, self.index, self.reason = name, index, reason
+
+
 class _Bases:
     def __init__(self, pts):
         pts = _fe(pts, 8)
@@ -158,6 +171,35 @@ class _Bases:
         b = type(self).__new__(type(self))
         b.n, b.h = n, h
         return b
+
+    @classmethod
+    def from_compressed(cls, data, name="points"):
+        """n x 32 bytes of compressed points (halo2's processed format; codecs.G1_SIGN_BIT / G1_IDENTITY_BIT) -> a resident set, every
+        point decompressed on the device (ezkl_hip_bases_decompress: y = (x^3 + 3)^((q + 1) / 4), accepted if y^2 == x^3 + 3 -- so a set
+        made here has passed the curve check of Bases.check already).  `data`: bytes or an array of n x 32 bytes, or a DeviceBuffer that
+        holds them.  A refused encoding raises CompressedPointError (index, reason; "<name>[<index>]: <why>") and leaves nothing resident."""
+        h, bad, why = _vp(), C.c_uint64(0), C.c_int(0)
+        if isinstance(data, DeviceBuffer):
+            n = data.nbytes // 32
+            rc = _l.load().ezkl_hip_bases_decompress_dev(_vp(data.ptr), C.c_size_t(n), C.byref(h), C.byref(bad), C.byref(why))
+        else:
+            a = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data).view(np.uint8).reshape(-1)
+            if a.size % 32:
+                raise ValueError("compressed points are 32 bytes each, got %d bytes" % a.size)
+            n = a.size // 32
+            rc = _l.load().ezkl_hip_bases_decompress(_p(a), C.c_size_t(n), C.byref(h), C.byref(bad), C.byref(why))
+        _l.check(rc, "ezkl_hip_bases_decompress")
+        if why.value:
+            raise CompressedPointError(name, int(bad.value), int(why.value))
+        self = cls.__new__(cls)
+        self.n, self.h = n, h
+        return self
+
+    def compressed(self):
+        """the set as n x 32 bytes of compressed points (ezkl_hip_bases_compress), the inverse of from_compressed"""
+        out = np.empty(self.n * 32, np.uint8)
+        _l.check(_l.load().ezkl_hip_bases_compress(self.h, _p(out)), "ezkl_hip_bases_compress")
+        return out.tobytes()
 
     def download(self):
         out = np.empty((self.n, 8), np.uint64)
@@ -771,10 +813,20 @@ def check_srs(srs, seed=None, structure=True):
     sets, v = {}, None
     try:
         for name in ("g", "g_lagrange"):
-            sets[name] = _Bases(np.ascontiguousarray(srs[name]))
+            pts = np.ascontiguousarray(srs[name])
+            if pts.dtype == np.uint8:                      # a processed file's compressed points: decompressing them IS the point check
+                try:
+                    sets[name] = _Bases.from_compressed(pts, name)
+                except CompressedPointError as e:           # (bad: at least this one; the kernel reports the lowest index)
+                    rep["points"][name] = dict(bad=1, first_bad=e.index, reason=e.reason, identities=0)
+                    rep["reason"] = str(e)
+                    return rep
+                rep["points"][name] = dict(bad=0, first_bad=None, reason=0, identities=int((pts[:, 31] >> 7).sum()))
+            else:
+                sets[name] = _Bases(pts)
+                rep["points"][name] = sets[name].check()
             if sets[name].n != n:
                 raise ValueError("check_srs: %s has %d points, k = %d" % (name, sets[name].n, k))
-            rep["points"][name] = sets[name].check()
         for name in ("g", "g_lagrange"):
             p = rep["points"][name]
             if p["bad"]:

@@ -27,9 +27,25 @@ from . import backend as _b
 
 
 # ------------------------------------------------------------------ SRS
+# The compressed point encoding of halo2's SerdeFormat::Processed (halo2curves 0.7.0), restated from csrc/g1_encoding.hpp -- the device's
+# table: a point is its x as a canonical little-endian integer, bit 254 = the parity of the canonical y, bit 255 = the identity flag (x and
+# the sign bit zero then).  G2 likewise over Fq2: x.c0 then x.c1, 32 bytes each, the two flags in the last byte, the parity that of y.c0.
+G1_SIGN_BIT, G1_IDENTITY_BIT = 254, 255
+_Q = _b._Q
+_RINV = pow(1 << 256, -1, _Q)
+
+
 def read_srs(buf):
+    """a raw-bytes file -> g / g_lagrange as (n, 8) uint64 records; a processed file (_srs_len_processed: the only other length taken) ->
+    g / g_lagrange as (n, 32) uint8 compressed points, which the loaders decompress on the device (backend.Bases.from_compressed).  g2 and
+    s_g2 are the 128 raw bytes either way (a processed file's two are decompressed here, in Python integers)."""
     k = struct.unpack_from("<I", buf, 0)[0]
     n = 1 << k
+    if k < 32 and len(buf) == _srs_len_processed(k):
+        g = np.frombuffer(buf, np.uint8, 32 * n, 4).reshape(n, 32)
+        gl = np.frombuffer(buf, np.uint8, 32 * n, 4 + 32 * n).reshape(n, 32)
+        off = 4 + 64 * n
+        return dict(k=k, g=g, g_lagrange=gl, g2=g2_decompress(buf[off:off + 64]), s_g2=g2_decompress(buf[off + 64:off + 128]))
     if len(buf) != _srs_len(k):
         raise ValueError("SRS length %d does not match k=%d" % (len(buf), k))
     g = np.frombuffer(buf, np.uint64, 8 * n, 4).reshape(n, 8)
@@ -42,14 +58,27 @@ def _srs_len(k):
     return 4 + 128 * (1 << k) + 256
 
 
+def _srs_len_processed(k):
+    return 4 + 64 * (1 << k) + 128
+
+
+def srs_is_processed(srs):
+    """does a parsed file (read_srs) hold compressed point sets?"""
+    return srs["g"].dtype == np.uint8
+
+
 def read_srs_g2(path):
-    """(g2, s_g2) of an SRS FILE without reading its G1 sets: the header for k, the length check of read_srs, the last 256 bytes -- all
+    """(g2, s_g2) of an SRS FILE without reading its G1 sets: the header for k, the length check of read_srs, the tail -- all
     a verifier needs of a file that is 128 MB at k = 20"""
     import os
     with open(path, "rb") as f:
         head = f.read(4)
         size = f.seek(0, os.SEEK_END)
         k = struct.unpack("<I", head)[0] if len(head) == 4 else 32
+        if k < 32 and size == _srs_len_processed(k):
+            f.seek(size - 128)
+            tail = f.read(128)
+            return g2_decompress(tail[:64]), g2_decompress(tail[64:])
         if k >= 32 or size != _srs_len(k):
             raise ValueError("SRS length %d does not match k=%d" % (size, k))
         f.seek(size - 256)
@@ -58,10 +87,76 @@ def read_srs_g2(path):
 
 
 def write_srs(srs):
+    """the file of a parsed SRS, in the layout its point sets are in: (n, 8) uint64 records -> raw bytes, (n, 32) uint8 compressed points
+    -> processed (g2 / s_g2, 128 raw bytes in the dict, are compressed here)"""
     n = 1 << srs["k"]
+    if srs_is_processed(srs):
+        g, gl = np.ascontiguousarray(srs["g"], np.uint8), np.ascontiguousarray(srs["g_lagrange"], np.uint8)
+        assert g.shape == (n, 32) and gl.shape == (n, 32)
+        return struct.pack("<I", srs["k"]) + g.tobytes() + gl.tobytes() + g2_compress(srs["g2"]) + g2_compress(srs["s_g2"])
     g, gl = np.ascontiguousarray(srs["g"], np.uint64), np.ascontiguousarray(srs["g_lagrange"], np.uint64)
     assert g.shape == (n, 8) and gl.shape == (n, 8)
     return struct.pack("<I", srs["k"]) + g.tobytes() + gl.tobytes() + srs["g2"] + srs["s_g2"]
+
+
+# Fq2 = Fq[u] / (u^2 + 1) as pairs (c0, c1) of Python integers: what the two G2 points of a processed file need, and no more
+def _fq_sqrt(a):
+    y = pow(a, (_Q + 1) // 4, _Q)
+    return y if y * y % _Q == a % _Q else None
+
+
+def fq2_sqrt(a):
+    """a square root of a = (a0, a1) in Fq2, or None: with s^2 = a0^2 + a1^2 (the norm), x0^2 = (a0 +- s) / 2 and x1 = a1 / (2 x0)"""
+    a0, a1 = a[0] % _Q, a[1] % _Q
+    if a1 == 0:
+        y = _fq_sqrt(a0)
+        if y is not None:
+            return (y, 0)
+        return (0, _fq_sqrt(-a0 % _Q))                      # -a0 is a square when a0 is not: (y u)^2 = -y^2
+    s = _fq_sqrt((a0 * a0 + a1 * a1) % _Q)
+    if s is None:
+        return None
+    half = pow(2, -1, _Q)
+    x0 = _fq_sqrt((a0 + s) * half % _Q)
+    if x0 is None:
+        x0 = _fq_sqrt((a0 - s) * half % _Q)
+    if not x0:
+        return None
+    x1 = a1 * pow(2 * x0, -1, _Q) % _Q
+    ok = ((x0 * x0 - x1 * x1) % _Q, 2 * x0 * x1 % _Q) == (a0, a1)
+    return (x0, x1) if ok else None
+
+
+_G2_B = tuple(c * pow(82, -1, _Q) % _Q for c in (27, -3))       # 3 / (9 + u) = 3 (9 - u) / 82
+
+
+def g2_decompress(b):
+    """64 bytes -> the 128 raw bytes of the file's G2 layout (x.c0, x.c1, y.c0, y.c1 in Montgomery form); ValueError if it is no point"""
+    v = int.from_bytes(b[32:64], "little")
+    sign, ident = (v >> (G1_SIGN_BIT)) & 1, v >> G1_IDENTITY_BIT
+    x0, x1 = int.from_bytes(b[:32], "little"), v & ((1 << G1_SIGN_BIT) - 1)
+    if ident:
+        if x0 or x1 or sign:
+            raise ValueError("compressed G2 point: malformed flags")
+        return bytes(128)
+    if x0 >= _Q or x1 >= _Q:
+        raise ValueError("compressed G2 point: coordinate not below the field modulus")
+    xx = ((x0 * x0 - x1 * x1) % _Q, 2 * x0 * x1 % _Q)
+    t = ((xx[0] * x0 - xx[1] * x1 + _G2_B[0]) % _Q, (xx[0] * x1 + xx[1] * x0 + _G2_B[1]) % _Q)
+    y = fq2_sqrt(t)
+    if y is None:
+        raise ValueError("compressed G2 point: no point with this x")
+    if (y[0] & 1) != sign:
+        y = (-y[0] % _Q, -y[1] % _Q)
+    return b"".join(((c << 256) % _Q).to_bytes(32, "little") for c in (x0, x1, y[0], y[1]))
+
+
+def g2_compress(raw):
+    """the inverse of g2_decompress"""
+    x0, x1, y0, _ = (int.from_bytes(raw[i:i + 32], "little") * _RINV % _Q for i in range(0, 128, 32))
+    if bytes(raw) == bytes(128):
+        return bytes(63) + bytes([1 << (G1_IDENTITY_BIT - 248)])
+    return x0.to_bytes(32, "little") + (x1 | ((y0 & 1) << G1_SIGN_BIT)).to_bytes(32, "little")
 
 
 def downsize_srs(srs, k):

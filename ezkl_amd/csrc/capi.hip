@@ -598,6 +598,75 @@ int ezkl_hip_bases_check(ezkl_bases_t h, size_t first, size_t n, uint64_t out[4]
     EZ_CTX(c);
     return g1_check(c, c->stream, b->pts, first, n, out);     // the 64-byte records alone: no window table is built or read
 }
+// ---- compressed points (g1_compress.hip): 32 bytes per point in, a resident base set out, and back ----
+static int bases_from_compressed(Ctx* c, const void* compressed_dev, size_t n, ezkl_bases_t* out, uint64_t* bad_index, int* reason) {
+    Bases* b = new Bases();
+    b->n = n;
+    int rc = EZKL_OK;
+    hipError_t e = hipMalloc(&b->pts, n * 64);
+    if (e != hipSuccess) rc = set_hip_error(e, "ezkl_hip_bases_decompress", __FILE__, __LINE__);
+    if (!rc) rc = g1_decompress(c, c->stream, compressed_dev, n, b->pts, -1, bad_index, reason);
+    if (rc || *reason) {                           // a refused encoding: no handle, and *out as the caller left it
+        if (b->pts) (void)hipFree(b->pts);
+        delete b;
+        return rc;
+    }
+    *out = reinterpret_cast<ezkl_bases_t>(b);
+    return EZKL_OK;
+}
+int ezkl_hip_bases_decompress_dev(const void* compressed_dev, size_t n, ezkl_bases_t* out, uint64_t* bad_index, int* reason) {
+    if (!compressed_dev || !out || !bad_index || !reason || n == 0 || ((uintptr_t)compressed_dev & 15)) return EZKL_ERR_INVALID;
+    EZ_CTX(c);
+    return bases_from_compressed(c, compressed_dev, n, out, bad_index, reason);
+}
+// the host-pointer form: the encodings go up through the pinned staging ring, 4 MiB at a time, into a block of the column pool
+int ezkl_hip_bases_decompress(const void* compressed_host, size_t n, ezkl_bases_t* out, uint64_t* bad_index, int* reason) {
+    if (!compressed_host || !out || !bad_index || !reason || n == 0) return EZKL_ERR_INVALID;
+    EZ_CTX(c);
+    void* dev = nullptr;
+    int rc = ezkl_hip_malloc(&dev, n * 32);
+    if (rc) return rc;
+    const size_t chunk = (size_t)4 << 20;
+    for (size_t off = 0; off < n * 32 && !rc; off += chunk) {
+        const size_t m = std::min(chunk, n * 32 - off);
+        void* stg = nullptr;
+        hipError_t e;
+        if (uint8_t* H = staging_acquire(c, m, &stg)) {
+            memcpy(H, (const uint8_t*)compressed_host + off, m);
+            e = hipMemcpyAsync((uint8_t*)dev + off, H, m, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) rc = staging_release(stg, c->stream);
+        } else {
+            e = copy_sync(c, (uint8_t*)dev + off, (const uint8_t*)compressed_host + off, m, hipMemcpyHostToDevice);
+        }
+        if (e != hipSuccess) rc = set_hip_error(e, "ezkl_hip_bases_decompress", __FILE__, __LINE__);
+    }
+    if (!rc) rc = bases_from_compressed(c, dev, n, out, bad_index, reason);        // synchronises the stream: the pool block is idle after it
+    else (void)hipStreamSynchronize(c->stream);
+    (void)ezkl_hip_free(dev);
+    return rc;
+}
+int ezkl_hip_bases_compress(ezkl_bases_t h, void* out_host) {
+    if (!h || !out_host) return EZKL_ERR_INVALID;
+    EZ_CTX(c);
+    Bases* b = reinterpret_cast<Bases*>(h);
+    void* dev = nullptr;
+    int rc = ezkl_hip_malloc(&dev, b->n * 32);
+    if (rc) return rc;
+    rc = g1_compress(c, c->stream, b->pts, b->n, dev);
+    if (!rc) {
+        hipError_t e = copy_sync(c, out_host, dev, b->n * 32, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = set_hip_error(e, "ezkl_hip_bases_compress", __FILE__, __LINE__);
+    } else (void)hipStreamSynchronize(c->stream);
+    (void)ezkl_hip_free(dev);
+    return rc;
+}
+// for tools/srs_compress_bench.py alone: n encodings -> n records in the caller's buffer, by one of the table forms of g1_compress.hip
+// (form < 0: the library's own); the kernel's time is ezkl_hip_last_kernel_ms("g1_decompress")
+int ezkl_hip_g1_decompress_form_dev(const void* compressed_dev, size_t n, int form, void* out_pts_dev, uint64_t* bad_index, int* reason) {
+    if (!compressed_dev || !out_pts_dev || !bad_index || !reason || ((uintptr_t)compressed_dev & 15)) return EZKL_ERR_INVALID;
+    EZ_CTX(c);
+    return g1_decompress(c, c->stream, compressed_dev, n, out_pts_dev, form, bad_index, reason);
+}
 int ezkl_hip_bases_from_scalars(const void* base_point, const void* scalars_dev, size_t n, ezkl_bases_t* out) {
     if (!base_point || !scalars_dev || !out || n == 0) return EZKL_ERR_INVALID;
     EZ_CTX(c);

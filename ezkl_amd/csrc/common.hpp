@@ -182,6 +182,8 @@ int msm_table_prepare(Ctx* c, const Bases* b);
 int g1_mul_fixed(Ctx* c, hipStream_t st, const void* base_host, const fe_t* scalars, size_t n, void* out_dev);
 int g1_mul_rows(Ctx* c, hipStream_t st, const void* pts_dev, const fe_t* scalars, size_t n, void* out_dev);
 int g1_check(Ctx* c, hipStream_t st, const void* pts_dev, size_t first, size_t n, uint64_t out[4]);
+int g1_decompress(Ctx* c, hipStream_t st, const void* in_dev, size_t n, void* out_dev, int form, uint64_t* bad_index, int* reason);
+int g1_compress(Ctx* c, hipStream_t st, const void* pts_dev, size_t n, void* out_dev);
 int gen_bases(Ctx* c, hipStream_t st, uint64_t seed, size_t first, size_t n, void* out_dev);
 int g1_to_lagrange(Ctx* c, hipStream_t st, const void* g_dev, uint32_t log_n, fe_t* tw_mont, const fe_t& ninv_mont, void* out_dev);
 void g1_add_affine_host(const void* a, const void* b, void* out);

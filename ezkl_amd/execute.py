@@ -555,7 +555,14 @@ def _srs_bases(points, name):
     of it -- exactly the points that will be used -- checked on the device before anything else touches the handle.  A bad point raises
     SrsError naming the set, the index and the reason; nothing stays resident then."""
     policy = _srs_policy()
-    b = B.Bases(np.ascontiguousarray(points))
+    points = np.ascontiguousarray(points)
+    if points.dtype == np.uint8:                              # a processed file's compressed points: the square root's y^2 == x^3 + 3 is the
+        try:                                                  # point check, under every policy, and it is not run a second time
+            return B.Bases.from_compressed(points, name)
+        except B.CompressedPointError as e:
+            found = dict(bad=1, first_bad=e.index, reason=e.reason, identities=0)
+            raise SrsError(str(e), dict(k=None, key=None, points={name: found}, powers=None, lagrange=None, g2=None, ok=False, reason=str(e)))
+    b = B.Bases(points)
     if policy == "off":
         return b
     try:
@@ -586,7 +593,7 @@ def _update_secret(secret):
 
 def update_srs(srs_in, srs_out, secret=None):
     """One step of an updatable SRS: multiply a fresh secret t into the file srs_in -- g'[i] = t^i g[i], g_lagrange' rebuilt from g',
-    s_g2' = [t] s_g2, all on the device (backend.update_srs) -- and write the result to srs_out in the same layout.  Whoever made srs_in
+    s_g2' = [t] s_g2, all on the device (backend.update_srs) -- and write the result to srs_out in raw bytes (srs_in may be a processed file).  Whoever made srs_in
     knows its secret s; the new file's secret is s t, which nobody knows once one updater has discarded their t.  secret=None draws t
     from OS entropy; an explicit one must be an integer in [1, r) and is refused (ValueError) before any device work otherwise.  The
     input is read as every loader reads an SRS file: EZKL_SRS_CHECK applies to it.  -> dict(k, t_g2: [t] g2 as hex, what
@@ -612,11 +619,58 @@ def verify_srs_update(old_path, new_path, t_g2):
     begins with the step that failed.  It does not prove that the updater knew or discarded their secret."""
     if isinstance(t_g2, str):
         t_g2 = bytes.fromhex(t_g2)
-    old, new = (codecs.read_srs(open(p, "rb").read()) for p in (old_path, new_path))
+    old, new = (_raw_srs(codecs.read_srs(open(p, "rb").read())) for p in (old_path, new_path))
     report = B.verify_srs_update(old, new, dict(t_g2=t_g2))
     if not report["ok"]:
         raise SrsError(report["reason"], report)
     return report
+
+
+def _raw_srs(srs):
+    """a parsed SRS with its point sets as raw records: a processed file's are decompressed on the device and read back (a refused encoding
+    raises SrsError); a raw file's dict is returned as it is"""
+    if not codecs.srs_is_processed(srs):
+        return srs
+    out = dict(srs)
+    for name in ("g", "g_lagrange"):
+        b = _srs_bases(srs[name], name)
+        try:
+            out[name] = b.download()
+        finally:
+            b.free()
+    return out
+
+
+def _convert_srs(src, dst, compress):
+    import hashlib
+    buf = open(src, "rb").read()
+    srs = codecs.read_srs(buf)
+    if codecs.srs_is_processed(srs) == compress:
+        raise ValueError("%s is %s already" % (src, "a processed file" if compress else "a raw-bytes file"))
+    out = dict(srs)
+    for name in ("g", "g_lagrange"):
+        b = _srs_bases(srs[name], name)                       # the input is read as every loader reads it: EZKL_SRS_CHECK applies
+        try:
+            out[name] = np.frombuffer(b.compressed(), np.uint8).reshape(-1, 32) if compress else b.download()
+        finally:
+            b.free()
+    data = codecs.write_srs(out)
+    open(dst, "wb").write(data)
+    return dict(k=srs["k"], sha256_in=hashlib.sha256(buf).hexdigest(), sha256_out=hashlib.sha256(data).hexdigest())
+
+
+def compress_srs(src, dst):
+    """a raw-bytes SRS file -> the same SRS in halo2's processed layout (SerdeFormat::Processed: 32 bytes per G1 point, x and the parity of
+    y; half the size), both point sets compressed on the device (Bases.compressed), g2 / s_g2 on the host.  Every loader of this module
+    takes the result where it takes the raw file.  -> dict(k, sha256_in, sha256_out).  Byte parity with a file halo2 wrote is NOT verified
+    (DESIGN.md "Compressed points")."""
+    return _convert_srs(src, dst, True)
+
+
+def decompress_srs(src, dst):
+    """a processed SRS file -> raw bytes: one square root per point on the device (Bases.from_compressed); a point that is none raises
+    SrsError naming the set and the index.  -> dict(k, sha256_in, sha256_out)"""
+    return _convert_srs(src, dst, False)
 
 
 def _downsized(srs, logrows):

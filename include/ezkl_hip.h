@@ -167,6 +167,24 @@ int ezkl_hip_bases_download(ezkl_bases_t h, void* out_host /* n x 64 B */);
  * that point, out[3] = identities.  first + n beyond the set: EZKL_ERR_INVALID; n = 0 writes {0, UINT64_MAX, 0, 0}.  Reads the records the
  * handle holds, never the window tables (and builds none); one kernel, 47 us for 2^20 points on an MI355X. */
 int ezkl_hip_bases_check(ezkl_bases_t h, size_t first, size_t n, uint64_t out[4]);
+/* Compressed points: halo2's SerdeFormat::Processed, 32 bytes per G1 point -- x as a canonical little-endian integer, bit 254 (0x40 of byte
+ * 31) the parity of the canonical y, bit 255 (0x80 of byte 31) the identity flag; csrc/g1_encoding.hpp is the one table of it.
+ *   ezkl_hip_bases_decompress_dev   n encodings resident at a 16-byte aligned device pointer -> a NEW base set: per point one square root in
+ *                                   Fq, y = (x^3 + 3)^((q + 1) / 4), accepted if y^2 == x^3 + 3 (g1_decompress_kernel, csrc/g1_compress.hip:
+ *                                   a generated addition chain of 251 squarings + 54 products, one point per lane).  A set that came through
+ *                                   it needs no ezkl_hip_bases_check: the comparison is the curve equation.
+ *   ezkl_hip_bases_decompress       the same from a host pointer, staged through the pinned ring into a block of the column pool
+ *   ezkl_hip_bases_compress         the inverse: the n records of a set -> n x 32 B at out_host
+ * *bad_index = the smallest refused index or UINT64_MAX, *reason = 0 or why that one was refused: 1 = x >= q, 3 = x^3 + 3 is not a square
+ * (no point has this x), 4 = malformed flags (the identity flag with a non-zero x or with the sign bit).  When an encoding is refused the
+ * call still returns EZKL_OK, makes no handle and leaves *out_handle as it was.  n = 0: EZKL_ERR_INVALID (a base set is never empty).
+ * HIP events around the kernels: ezkl_hip_last_kernel_ms("g1_decompress") / ("g1_compress"). */
+int ezkl_hip_bases_decompress_dev(const void* compressed_dev, size_t n, ezkl_bases_t* out_handle, uint64_t* bad_index, int* reason);
+int ezkl_hip_bases_decompress(const void* compressed_host, size_t n, ezkl_bases_t* out_handle, uint64_t* bad_index, int* reason);
+int ezkl_hip_bases_compress(ezkl_bases_t h, void* out_host /* n x 32 B */);
+/* measurement only (tools/srs_compress_bench.py): the decompression kernel with one of its window-table forms -- 0 registers, 1 LDS,
+ * 2 no table (binary chain), 3 / 4 = 0 / 1 with the runs of squarings as loops; < 0 the library's own -- into the caller's n x 64 B */
+int ezkl_hip_g1_decompress_form_dev(const void* compressed_dev, size_t n, int form, void* out_pts_dev, uint64_t* bad_index, int* reason);
 /* base set bases[i] = scalars[i] * P for one point P (64 B affine, host) and n resident Montgomery scalars: SRS
  * generation for tests (gen_srs -> ParamsKZG::setup, /root/reference/src/pfsys/srs.rs:14-16): g[i] = s^i G,
  * g_lagrange[i] = L_i(s) G */
