@@ -28,6 +28,12 @@
 //    lanes to a dot are chosen on the host (dot_wide_lanes).  The cells are wit_dot_kernel's bit for bit; ezkl_hip_witness_wide_dots counts
 //    the launches.  The second-phase pairwise product is a mult record, the einsum's sum / prod are sum / prod records.
 //
+//  * contract records (a version-2 plan: the same claimed product stated as m x kd by kd x n matrices of cells, m * kd + kd * n + m * n index
+//    words where the dot record takes 2 * kd * m * n).  Two launches: wit_contract_gather_kernel turns the operands' cells into int32 in the
+//    plan's scratch -- one conversion and one range test per ELEMENT --, wit_contract_gemm_kernel multiplies them: 64 x 64 output tiles, a
+//    4 x 4 block of 128-bit accumulators per lane, double-buffered LDS slices of 16.  An operand outside |v| < 2^31 is reported with the
+//    matmul record's words and the record writes none of its cells.
+//
 //  * the surrogate's ops.  sum / prod records (BaseRegion._accumulate, layouts.rs:2472-2621: the running sum or product of w cells per
 //    row): the chunked scan of the dot records with one operand per entry and addition or the Montgomery product as the monoid, see
 //    wit_acc_kernel.  gather records (row `index` of a dynamic table, the structure of `select`, layouts.rs:1483-1581): an element-wise
@@ -441,6 +447,127 @@ __global__ __launch_bounds__(MM_TILE * MM_TILE) void wit_matmul_kernel(WitCols c
     }
     wit_report(bad, rec, bad_elem, status);
     wit_count(live ? 1u : 0u, status);
+}
+
+// A CONTRACT record, pass 1: the cells of a (m * kd words) and b (kd * n words) -> int32 operands in the plan's scratch, A row-major then B
+// row-major.  One lane per operand, the index arrays read coalesced; one wit_signed conversion and one range test (|v| < 2^31) per element -- not
+// one per product.  A bad operand stores zero, reports (record, element) with element = its place in a, or m * kd + its place in b, and marks
+// the record in status[3] (rec + 1 by atomicMax: the records of a phase run in ascending order on one stream, so the word names THIS
+// record exactly when its own gather failed): the GEMM below then writes nothing.
+constexpr uint32_t CT_THREADS = 256;
+__global__ __launch_bounds__(CT_THREADS) void wit_contract_gather_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ a, size_t n_a,
+                                                                         const uint32_t* __restrict__ b, size_t n_b, int32_t* __restrict__ ops, uint32_t rec,
+                                                                         unsigned long long* status) {
+    const size_t e = (size_t)blockIdx.x * CT_THREADS + threadIdx.x;
+    bool fail = false;
+    if (e < n_a + n_b) {
+        bool neg, fits;
+        uint64_t mag;
+        wit_signed(ld_fe(wit_cell(cols, k, e < n_a ? a[e] : b[e - n_a])), neg, mag, fits);
+        fail = !fits || (mag >> 31) != 0;
+        ops[e] = fail ? 0 : neg ? -(int32_t)mag : (int32_t)mag;
+        if (fail) atomicMax(&status[3], (unsigned long long)rec + 1);
+    }
+    wit_report(fail, rec, (uint32_t)e, status);                   // (e < 2^32: both arrays lie inside the pool)
+}
+
+// A CONTRACT record, pass 2: C = A . B over the integers from the gathered int32 operands, C[i][j] -> the cell dst[i * n + j].
+//   * a workgroup of 256 lanes owns a CT_TILE x CT_TILE = 64 x 64 tile of C; lane (ty, tx) = (lane / 16, lane % 16) owns the 4 x 4 block of rows
+//     4 ty .. 4 ty + 3 and columns 4 tx .. 4 tx + 3: sixteen 128-bit accumulators (a 64-bit low word, a signed high word) in registers, so an
+//     operand fetched from LDS is used four times and one fetched from memory 64 times;
+//   * the k loop goes through LDS in slices of CT_SLICE = 16: the A slice TRANSPOSED (As[t][i]) and the B slice as it is (Bs[t][j]), so that a
+//     lane's four rows and its four columns at one t are each ONE 16-byte LDS read; within a wave the 16 tx read one contiguous 256-byte run of
+//     Bs and the 4 ty broadcast their run of As -- no bank conflicts.  Rows are padded to CT_ROW = 68 words: the transposing store of the A
+//     slice (consecutive lanes: consecutive t, so a stride of one LDS row) then lands 4 banks apart per t and the wave's 64 stores in 64
+//     different banks, and a row stays 16-byte aligned;
+//   * the two slices are double-buffered: the global loads of slice s + 1 are issued into registers before the products of slice s and stored
+//     to the other buffer after them -- one barrier per slice;
+//   * products are int32 x int32 -> int64, |p| <= (2^31 - 1)^2 < 2^62: two of them add exactly in 64 bits, so the 128-bit carry chain runs once
+//     per PAIR of k steps; kd * 2^62 < 2^127 bounds the sum.  Positions past m, n or kd load zeros;
+//   * the epilogue turns the two words into sign and magnitude and Montgomery form (wit_from_mag128) and stores through the index array.
+// No matrix instructions: at this operand range an int8 MFMA needs four digits per operand and sixteen products per product.
+constexpr uint32_t CT_TILE = 64, CT_SLICE = 16, CT_ROW = CT_TILE + 4, CT_BLK = 4;
+static_assert(CT_THREADS == (CT_TILE / CT_BLK) * (CT_TILE / CT_BLK) && CT_THREADS % CT_SLICE == 0 && CT_THREADS % CT_TILE == 0 && CT_SLICE % 2 == 0 && (CT_ROW * 4) % 16 == 0,
+              "a lane per 4 x 4 block; whole rows of lanes load a slice; products are added in pairs; an LDS row stays 16-byte aligned");
+struct alignas(16) CtQuad {
+    int32_t v[CT_BLK];
+};
+__global__ __launch_bounds__(CT_THREADS) void wit_contract_gemm_kernel(WitCols cols, uint32_t k, const uint32_t* __restrict__ dst, const int32_t* __restrict__ A,
+                                                                       const int32_t* __restrict__ B, uint32_t m, uint32_t kd, uint32_t n, uint32_t rec,
+                                                                       unsigned long long* status) {
+    __shared__ alignas(16) int32_t As[2][CT_SLICE][CT_ROW], Bs[2][CT_SLICE][CT_ROW];
+    if (status[3] == (unsigned long long)rec + 1) return;      // the gather met a bad operand (the same word for every lane of the grid)
+    constexpr uint32_t A_PER = CT_TILE * CT_SLICE / CT_THREADS, B_PER = A_PER, A_ROWS = CT_THREADS / CT_SLICE, B_ROWS = CT_THREADS / CT_TILE;
+    const uint32_t tiles_n = (n + CT_TILE - 1) / CT_TILE;
+    const uint32_t i0 = (blockIdx.x / tiles_n) * CT_TILE, j0 = (blockIdx.x % tiles_n) * CT_TILE;
+    const uint32_t tx = threadIdx.x % (CT_TILE / CT_BLK), ty = threadIdx.x / (CT_TILE / CT_BLK);
+    const uint32_t at = threadIdx.x % CT_SLICE, ai = threadIdx.x / CT_SLICE;         // the A elements this lane loads: A[i0 + ai + A_ROWS r][t0 + at]
+    const uint32_t bj = threadIdx.x % CT_TILE, bt = threadIdx.x / CT_TILE;           // the B elements: B[t0 + bt + B_ROWS r][j0 + bj]
+    int32_t ra[A_PER], rb[B_PER];
+    auto fetch = [&](uint32_t t0) {
+#pragma unroll
+        for (uint32_t r = 0; r < A_PER; r++) {
+            const uint32_t i = i0 + ai + A_ROWS * r, t = t0 + at;
+            ra[r] = i < m && t < kd ? A[(size_t)i * kd + t] : 0;
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < B_PER; r++) {
+            const uint32_t t = t0 + bt + B_ROWS * r, j = j0 + bj;
+            rb[r] = t < kd && j < n ? B[(size_t)t * n + j] : 0;
+        }
+    };
+    auto stage = [&](uint32_t buf) {
+#pragma unroll
+        for (uint32_t r = 0; r < A_PER; r++) As[buf][at][ai + A_ROWS * r] = ra[r];
+#pragma unroll
+        for (uint32_t r = 0; r < B_PER; r++) Bs[buf][bt + B_ROWS * r][bj] = rb[r];
+    };
+    uint64_t lo[CT_BLK][CT_BLK];
+    int64_t hi[CT_BLK][CT_BLK];
+#pragma unroll
+    for (uint32_t y = 0; y < CT_BLK; y++)
+#pragma unroll
+        for (uint32_t x = 0; x < CT_BLK; x++) { lo[y][x] = 0; hi[y][x] = 0; }
+    const uint32_t slices = (kd + CT_SLICE - 1) / CT_SLICE;
+    fetch(0);
+    stage(0);
+    __syncthreads();
+    for (uint32_t s = 0; s < slices; s++) {
+        const uint32_t buf = s & 1;
+        if (s + 1 < slices) fetch((s + 1) * CT_SLICE);
+#pragma unroll
+        for (uint32_t t = 0; t < CT_SLICE; t += 2) {
+            const CtQuad a0 = *reinterpret_cast<const CtQuad*>(&As[buf][t][CT_BLK * ty]), a1 = *reinterpret_cast<const CtQuad*>(&As[buf][t + 1][CT_BLK * ty]);
+            const CtQuad b0 = *reinterpret_cast<const CtQuad*>(&Bs[buf][t][CT_BLK * tx]), b1 = *reinterpret_cast<const CtQuad*>(&Bs[buf][t + 1][CT_BLK * tx]);
+#pragma unroll
+            for (uint32_t y = 0; y < CT_BLK; y++)
+#pragma unroll
+                for (uint32_t x = 0; x < CT_BLK; x++) {
+                    const int64_t p = (int64_t)a0.v[y] * (int64_t)b0.v[x] + (int64_t)a1.v[y] * (int64_t)b1.v[x];      // |p| < 2^63: exact
+                    lo[y][x] += (uint64_t)p;
+                    hi[y][x] += (p >> 63) + (lo[y][x] < (uint64_t)p ? 1 : 0);
+                }
+        }
+        if (s + 1 < slices) stage(buf ^ 1);                    // the buffer slice s - 1 was read from: every lane has passed the barrier since
+        __syncthreads();
+    }
+    uint32_t wrote = 0;
+#pragma unroll
+    for (uint32_t y = 0; y < CT_BLK; y++)
+#pragma unroll
+        for (uint32_t x = 0; x < CT_BLK; x++) {
+            const uint32_t i = i0 + CT_BLK * ty + y, j = j0 + CT_BLK * tx + x;
+            if (i >= m || j >= n) continue;
+            const bool neg = hi[y][x] < 0;
+            uint64_t mlo = lo[y][x], mhi = (uint64_t)hi[y][x];
+            if (neg) {
+                mlo = ~mlo + 1;
+                mhi = ~mhi + (mlo == 0 ? 1 : 0);
+            }
+            st_fe(wit_cell(cols, k, dst[(size_t)i * n + j]), wit_from_mag128(neg, mlo, mhi));
+            wrote++;
+        }
+    wit_count(wrote, status);
 }
 
 // RLC_LANES consecutive lanes share one scan out[t] = c * (out[t-1] + v[t]) (= out[t-1] * c + c * v[t]: field arithmetic is exact), out[-1] = 0;
@@ -1023,6 +1150,7 @@ struct DevPlan {
     SortKey* sort_keys = nullptr;   // the padded keys of the largest sort record with segments above SORT_TILE, or the chunk slots of the
                                     // largest arg-extremum record with segments above ARGEXT_CHUNK, or the winner words / the flags and counts of the
                                     // largest scatter / complement record above SCATTER_TILE, whichever is more (one slot when there is none)
+    int32_t* contract_ops = nullptr;   // the gathered int32 operands of a CONTRACT record, A then B: the largest m * kd + kd * n of the plan's (one word when there is none)
     StatRec* stat_recs = nullptr;   // (source offset, count) of every TABLE record, in all phases: what ezkl_hip_witness_lookup_stats_dev strides over
     uint32_t n_stat_recs = 0;
     uint64_t stat_elems = 0;
@@ -1044,7 +1172,7 @@ size_t wit_scratch_bytes(const Rec& r) {
 }
 
 void plan_release(DevPlan* p) {
-    for (void* q : {(void*)p->pool, (void*)p->outputs, (void*)p->params, (void*)p->consts, (void*)p->table_values, (void*)p->inputs, (void*)p->outs, (void*)p->status, (void*)p->sort_keys, (void*)p->stat_recs, (void*)p->stats})
+    for (void* q : {(void*)p->pool, (void*)p->outputs, (void*)p->params, (void*)p->consts, (void*)p->table_values, (void*)p->inputs, (void*)p->outs, (void*)p->status, (void*)p->sort_keys, (void*)p->contract_ops, (void*)p->stat_recs, (void*)p->stats})
         if (q) (void)ezkl_hip_free(q);
     delete p;
 }
@@ -1179,6 +1307,9 @@ int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out
     }
     size_t sort_bytes = 0;                                        // the records run one after another on the stream: they share the scratch
     for (const Rec& r : h.recs) sort_bytes = std::max(sort_bytes, wit_scratch_bytes(r));
+    size_t contract_words = 0;                                    // (m * kd + kd * n <= the pool's words: checked by `parse`)
+    for (const Rec& r : h.recs)
+        if (r.kind == CONTRACT) contract_words = std::max(contract_words, ((size_t)(r.count / r.p1) + r.p1) * r.p0);
     std::vector<StatRec> stat_recs;
     for (const Rec& r : h.recs)
         if (r.kind == TABLE) {
@@ -1192,7 +1323,7 @@ int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out
                       {(void**)&p->inputs, nullptr, (size_t)h.n_inputs * 8},      {(void**)&p->outs, nullptr, h.outputs.size() * 32},
                       {(void**)&p->status, nullptr, 32},                          {(void**)&p->table_values, h.table_values.data(), h.table_values.size() * 8},
                       {(void**)&p->sort_keys, nullptr, sort_bytes},               {(void**)&p->stat_recs, stat_recs.data(), stat_recs.size() * sizeof(StatRec)},
-                      {(void**)&p->stats, nullptr, 32}};
+                      {(void**)&p->stats, nullptr, 32},                           {(void**)&p->contract_ops, nullptr, contract_words * 4}};
     int rc = EZKL_OK;
     for (const Up& u : ups) {
         if ((rc = ezkl_hip_malloc(u.dev, u.bytes ? u.bytes : 1))) break;
@@ -1327,6 +1458,17 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
                                p->pool + r.b, m, r.p0, r.p1, (const int64_t*)p->inputs, (uint32_t)ri, p->status);
             break;
         }
+        case CONTRACT: {                                           // gather the operands' cells as int32, then the tiled integer product
+            const uint32_t m = r.count / r.p1;
+            const size_t n_a = (size_t)m * r.p0, n_b = (size_t)r.p0 * r.p1;
+            hipLaunchKernelGGL(wit_contract_gather_kernel, dim3((uint32_t)cdiv(n_a + n_b, CT_THREADS)), dim3(CT_THREADS), 0, st, cols, k, p->pool + r.a, n_a, p->pool + r.b, n_b,
+                               p->contract_ops, (uint32_t)ri, p->status);
+            EZ_HIP(hipGetLastError());
+            hipLaunchKernelGGL(wit_contract_gemm_kernel, dim3(cdiv(m, CT_TILE) * cdiv(r.p1, CT_TILE)), dim3(CT_THREADS), 0, st, cols, k, p->pool + r.dst,
+                               (const int32_t*)p->contract_ops, (const int32_t*)p->contract_ops + n_a, m, r.p0, r.p1, (uint32_t)ri, p->status);
+            launches++;
+            break;
+        }
         case RLC:
             hipLaunchKernelGGL(wit_rlc_kernel, dim3(cdiv((size_t)r.count * RLC_LANES, 64)), dim3(64), 0, st, cols, k, p->pool + r.dst, p->pool + r.a, r.count, r.p1, chal[r.p0],
                                p->status);
@@ -1366,9 +1508,10 @@ int ezkl_hip_witness_run_phase_dev(ezkl_wplan_t plan, uint32_t phase, const int6
     status[3] = launches;
     if (dev_status[0]) {
         const uint32_t ri = (uint32_t)(status[1] >> 32), el = (uint32_t)status[1];
-        const uint32_t kind = ri < h.recs.size() ? h.recs[ri].kind : (uint32_t)KINDS_TOP;     // (KINDS_TOP: no such record)
-        t_wit_error = std::string("witness: ") + failure_words(kind) + " (" + kind_name(kind) + " record " + std::to_string(ri) + ", element " + std::to_string(el) + "; " +
-                      std::to_string(dev_status[0]) + " " + (kind < KINDS_TOP ? KINDS[kind].unit : "cells") + " in all)";
+        const uint32_t kind = ri < h.recs.size() ? h.recs[ri].kind : NONE;                    // (NONE: no such record -- no kind of either table)
+        const KindInfo* K = kind_info(kind, h.version);
+        t_wit_error = std::string("witness: ") + failure_words(kind, h.version) + " (" + kind_name(kind, h.version) + " record " + std::to_string(ri) + ", element " + std::to_string(el) + "; " +
+                      std::to_string(dev_status[0]) + " " + (K ? K->unit : "cells") + " in all)";
         return EZKL_ERR_INVALID;
     }
     p->done_phase = (int)phase;

@@ -7,6 +7,8 @@
 // then n_params x int64, n_consts x 32 bytes (canonical Fr), n_records x {kind, count, p0, p1, dst, a, b, phase}, n_outputs x u32 cells,
 // n_words x u32 pool, n_tables x {lo (int32), n, col_size, offset} and n_table_values x int64: the static lookup tables, f(lo + i) as signed
 // integers (both sections are empty in a plan without lookups).  Cells are numbered column * 2^k + row.
+// Version 2 (VERSION2) is the same blob whose record list may also hold the kinds of a SECOND table, KINDS2, numbered from KINDS_TOP = 32:
+// CONTRACT for now.  A version-1 blob that names kind 32 is refused as unknown; the serializer writes version 2 only when a record needs it.
 //
 // What every kind of record means, its parameters and its run-time failure: the module docstring of ezkl_amd/witness_plan.py, kind by kind;
 // `run_plan_host` there is the executable form.  KINDS below is the same table as KINDS there (tests/test_witness_plan_table.py).
@@ -15,6 +17,7 @@
 // span a record names lies inside the pool; every word a lane uses as a cell is below n_advice * 2^k, every index below the section it
 // points into; a cell is written at most once and read only after an EARLIER record has written it; the phases are non-decreasing, below
 // n_phases, and every column is written in one phase only (INPUT and MATMUL records in phase 0, with which the inputs are uploaded).
+// For a CONTRACT record: m, kd, n >= 1, m * n = count, its three spans inside the pool, every word of a and b a cell written earlier.
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -25,7 +28,7 @@
 namespace ezkl {
 namespace wplan {
 
-constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64, MAX_PHASES = 3, MAX_CHALLENGES = 64, SORT_TILE = 2048,
+constexpr uint32_t MAGIC = 0x50575A45u, VERSION = 1, VERSION2 = 2, NONE = 0xFFFFFFFFu, MAX_ADVICE = 64, MAX_PHASES = 3, MAX_CHALLENGES = 64, SORT_TILE = 2048,
                    MAX_SORT_COUNT = 1u << 28, ARGEXT_CHUNK = 4096, SCATTER_TILE = 4096;
 // A DOT record of ONE step (p1 == 1) with p0 >= DOT_WIDE_MIN products -- the claimed product of an einsum -- runs on wit_dot_wide_kernel;
 // every other DOT record on wit_dot_kernel.  DOT_WIDE_FILL: the lanes that fill the device (256 compute units x 4 SIMDs x 2 waves of 64).
@@ -84,10 +87,29 @@ static const KindInfo KINDS[KINDS_TOP] = {
     {"complement", nullptr, "cells", false, false, CELLS, WORDS},
     {"one_hot", "one-hot index outside the classes", "cells", false, false, CELLS, WORDS},
 };
-inline bool known(uint32_t kind) { return kind < KINDS_TOP && KINDS[kind].name[0] != '?'; }
-inline const char* kind_name(uint32_t kind) { return kind < KINDS_TOP ? KINDS[kind].name : "?"; }     // the name a message gives a kind
+// the second table: the kinds a version-2 blob may name besides, numbered from KINDS_TOP.  CONTRACT: count = m * n destination cells, p0 = kd,
+// p1 = n, a = m * kd CELLS (row-major A), b = kd * n CELLS (row-major B): cell[dst[i * n + j]] = the integer sum over t of the signed values of
+// cell[a[i * kd + t]] and cell[b[t * n + j]], as integer_rep_to_felt maps it.  Any phase; a cell may repeat within a or b.  MATMUL's shape
+// rules and MATMUL's failure: an operand with |v| >= 2^31, element = its place in a, or m * kd + its place in b.
+enum Kind2 : uint32_t { CONTRACT = KINDS_TOP, KINDS2_TOP };
+static const KindInfo KINDS2[KINDS2_TOP - KINDS_TOP] = {
+    {"contract", "einsum operand outside the exact-product range", "operand reads", false, false, CELLS, CELLS},       // 32
+};
+// the row of a kind in a blob of `version`, or nullptr: the number names nothing there
+inline const KindInfo* kind_info(uint32_t kind, uint32_t version = VERSION) {
+    if (kind < KINDS_TOP) return KINDS[kind].name[0] != '?' ? &KINDS[kind] : nullptr;
+    return version >= VERSION2 && kind < KINDS2_TOP ? &KINDS2[kind - KINDS_TOP] : nullptr;
+}
+inline bool known(uint32_t kind, uint32_t version = VERSION) { return kind_info(kind, version) != nullptr; }
+inline const char* kind_name(uint32_t kind, uint32_t version = VERSION) {     // the name a message gives a kind
+    const KindInfo* K = kind_info(kind, version);
+    return K ? K->name : "?";
+}
 // the words a lane's run-time failure is reported with; a kind that has none is reported as a value beyond its decomposition is
-inline const char* failure_words(uint32_t kind) { return kind < KINDS_TOP && KINDS[kind].failure ? KINDS[kind].failure : KINDS[HINT].failure; }
+inline const char* failure_words(uint32_t kind, uint32_t version = VERSION) {
+    const KindInfo* K = kind_info(kind, version);
+    return K && K->failure ? K->failure : KINDS[HINT].failure;
+}
 // how many destination words a record has: every step of every scan, else one per element
 inline uint64_t dst_words(uint32_t kind, uint32_t count, uint32_t p1) { return kind < KINDS_TOP && KINDS[kind].scan ? (uint64_t)count * p1 : count; }
 struct Rec {
@@ -98,7 +120,7 @@ struct Table {
     uint32_t n, col_size, off;
 };
 struct Plan {
-    uint32_t k = 0, n_advice = 0, n_inputs = 0, n_cells = 0, n_ops = 0, n_challenges = 0, n_phases = 1;
+    uint32_t version = VERSION, k = 0, n_advice = 0, n_inputs = 0, n_cells = 0, n_ops = 0, n_challenges = 0, n_phases = 1;
     uint8_t col_phase[MAX_ADVICE] = {0};       // the phase each column belongs to (a column no record writes: 0)
     uint8_t param_hash[32] = {0};
     std::vector<int64_t> params;
@@ -148,20 +170,20 @@ inline bool canonical(const uint8_t* c) {                 // below the modulus, 
 // after an EARLIER record has written it; the phases are non-decreasing and every column is written in one phase only.
 inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
     auto fail = [&](const std::string& s) { why = "witness plan: " + s; return false; };
-    auto at_rec = [&](size_t ri, uint32_t kind, const char* s) { return fail("record " + std::to_string(ri) + " (" + kind_name(kind) + "): " + s); };
-    const uint8_t* p = static_cast<const uint8_t*>(blob);
     uint32_t h[20];
+    auto at_rec = [&](size_t ri, uint32_t kind, const char* s) { return fail("record " + std::to_string(ri) + " (" + kind_name(kind, h[1]) + "): " + s); };
+    const uint8_t* p = static_cast<const uint8_t*>(blob);
     if (!blob || len < sizeof h + 32) return fail("shorter than its header");
     memcpy(h, p, sizeof h);
     if (h[0] != MAGIC) return fail("bad magic");
-    if (h[1] != VERSION) return fail("version " + std::to_string(h[1]) + ", this build reads " + std::to_string(VERSION));
+    if (h[1] != VERSION && h[1] != VERSION2) return fail("version " + std::to_string(h[1]) + ", this build reads " + std::to_string(VERSION) + " and " + std::to_string(VERSION2));
     const uint32_t k = h[2], n_adv = h[3], n_rec = h[4], n_in = h[5], n_par = h[6], n_con = h[7], n_out = h[8], n_cells = h[9], n_words = h[10], n_tab = h[12], n_val = h[13];
     if (k < 1 || k > 28 || n_adv == 0 || n_adv > MAX_ADVICE || ((uint64_t)n_adv << k) > ((uint64_t)1 << 32)) return fail("bad geometry");
     const uint32_t n_chal = h[14], n_phases = h[15] ? h[15] : 1;
     if (n_phases > MAX_PHASES || n_chal > MAX_CHALLENGES) return fail("bad phase or challenge count");
     const uint64_t want = (uint64_t)sizeof h + 32 + 8ull * n_par + 32ull * n_con + 32ull * n_rec + 4ull * n_out + 4ull * n_words + 16ull * n_tab + 8ull * n_val;
     if (want != len) return fail(std::to_string(len) + " bytes, its header says " + std::to_string(want));
-    out.k = k; out.n_advice = n_adv; out.n_inputs = n_in; out.n_cells = n_cells; out.n_ops = h[11]; out.n_challenges = n_chal; out.n_phases = n_phases;
+    out.version = h[1]; out.k = k; out.n_advice = n_adv; out.n_inputs = n_in; out.n_cells = n_cells; out.n_ops = h[11]; out.n_challenges = n_chal; out.n_phases = n_phases;
     p += sizeof h;
     memcpy(out.param_hash, p, 32); p += 32;
     out.params.resize(n_par);   if (n_par) memcpy(out.params.data(), p, 8ull * n_par);   p += 8ull * n_par;
@@ -211,14 +233,14 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
     uint32_t last_phase = 0;
     for (size_t ri = 0; ri < out.recs.size(); ri++) {
         const Rec& r = out.recs[ri];
-        if (!known(r.kind)) return at_rec(ri, r.kind, "unknown kind");
+        if (!known(r.kind, h[1])) return at_rec(ri, r.kind, "unknown kind");
         if (r.count == 0 && r.kind != COMPLEMENT) return at_rec(ri, r.kind, "empty");     // (nothing missing: a complement that writes no cell)
         if (r.phase >= n_phases) return at_rec(ri, r.kind, "phase out of range");
         if (r.phase < last_phase) return at_rec(ri, r.kind, "phases decrease");
         last_phase = r.phase;
         if ((r.kind == INPUT || r.kind == MATMUL) && r.phase != 0) return at_rec(ri, r.kind, "input and matmul records belong to phase 0");
         // the kind's own parameters, and the words it has: n_dst at dst, n_a at a, n_b at b, lim for its indices, n_extra further cells a lane reads
-        const KindInfo& K = KINDS[r.kind];
+        const KindInfo& K = *kind_info(r.kind, h[1]);
         const uint64_t n_dst = dst_words(r.kind, r.count, r.p1);
         uint64_t n_a = r.count, n_b = 0, n_extra = 0;
         uint32_t lim = 0, extra = 0;
@@ -245,6 +267,11 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
             if (r.p0 == 0 || r.p1 == 0 || r.count % r.p1 != 0) return at_rec(ri, r.kind, "bad matmul shape");
             n_a = (uint64_t)(r.count / r.p1) * r.p0; n_b = (uint64_t)r.p0 * r.p1; lim = n_in;
             if (!span_ok(r.dst, n_dst) || !span_ok(r.a, n_a) || !span_ok(r.b, n_b)) return at_rec(ri, r.kind, "bad matmul shape");
+            break;
+        case CONTRACT:                                   // p0 = kd, p1 = n, count = m * n: a = m * kd, b = kd * n cells (version 2 only: `known`)
+            if (r.p0 == 0 || r.p1 == 0 || r.count % r.p1 != 0) return at_rec(ri, r.kind, "bad contract shape");
+            n_a = (uint64_t)(r.count / r.p1) * r.p0; n_b = (uint64_t)r.p0 * r.p1;
+            if (!span_ok(r.dst, n_dst) || !span_ok(r.a, n_a) || !span_ok(r.b, n_b)) return at_rec(ri, r.kind, "bad contract shape");
             break;
         case RLC:                                        // p0 = challenge, p1 = steps, count = scans
             if (r.p0 >= n_chal) return at_rec(ri, r.kind, "challenge index out of range");
@@ -326,6 +353,8 @@ inline bool parse(const void* blob, size_t len, Plan& out, std::string& why) {
             cp = (int)r.phase;
         }
     }
+    if (h[1] == VERSION2 && std::none_of(out.recs.begin(), out.recs.end(), [](const Rec& r) { return r.kind >= KINDS_TOP; }))
+        return fail("version 2 without a record of the second kind table");     // (the serializer writes version 2 only when a record needs it)
     if (total != n_cells) return fail(std::to_string(total) + " cells written, its header says " + std::to_string(n_cells));
     for (uint32_t c : out.outputs)
         if (c >= cells || !written.get(c)) return fail("an output cell is never written");

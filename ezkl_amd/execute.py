@@ -42,6 +42,8 @@ live in the table PHASED_FAMILIES:
                                                                                 the scales and the rebase divisors follow the MLP description's rules)
     {"model": "attention", "run_args": {...}, "n", "e", "d", "capacity", "input_scale", "output_scale", "eps", "score_div", "lookup_range", "Wq", "Wk", "Wv"}
                                                                              -> AttentionHeadCircuit
+    (both take an optional "einsum_claim": "dot" | "contract" -- how the witness plan has the device compute the einsums' claimed products,
+    witness_plan.py CONTRACT; `describe` writes it only when it is not "dot")
 A circuit is phased when its constraint system has advice beyond phase 0 (_phased), and every entry point then takes one path for
 both: setup writes a two-phase witness plan next to the key; gen_witness runs the layout's first phase, or replays phase 0 of the plan
 and gathers the outputs (ezkl_hip_witness_outputs_dev) -- the outputs and every static lookup live in phase 0; mock, prove and Prover
@@ -211,6 +213,11 @@ def _choice_field(*choices):
     return read
 
 
+def _claim_field(j, name):
+    """the optional "einsum_claim" of the families that lay einsums: how their witness plan claims the products ("dot" when absent)"""
+    return _choice_field("dot", "contract")(j, name) if name in j else "dot"
+
+
 def _eps_field(j, name):
     v = j.get(name)
     if isinstance(v, bool) or not isinstance(v, (int, float)) or not v > 0:
@@ -267,7 +274,7 @@ def _pool_fits(d):
 
 _ATTENTION_WEIGHTS = ("Wq", "Wk", "Wv")
 _ATTENTION_FIELDS = [(name, _positive) for name in ("n", "e", "d", "capacity", "input_scale", "output_scale", "score_div")] + \
-                    [("eps", _eps_field), ("lookup_range", _range_field)] + [(name, _parameter_field) for name in _ATTENTION_WEIGHTS]
+                    [("eps", _eps_field), ("lookup_range", _range_field)] + [(name, _parameter_field) for name in _ATTENTION_WEIGHTS] + [("einsum_claim", _claim_field)]
 
 
 def _one_inner_column(d):
@@ -310,7 +317,8 @@ def _describe_mlp_batch(j):
     if "output_scale" in j:
         _int_field(j, "output_scale")
     d = _describe_mlp(dict(j, run_args=ra))
-    fields = dict({name: d[name] for name in ("weights", "biases", "relu_last", "relu_first", "rebase")}, batch=m, capacity=_optional(_positive)(j, "capacity"))
+    fields = dict({name: d[name] for name in ("weights", "biases", "relu_last", "relu_first", "rebase")}, batch=m, capacity=_optional(_positive)(j, "capacity"),
+                  einsum_claim=_claim_field(j, "einsum_claim"))
     return dict(d, n_inputs=m * len(weights[0][0]), fields=fields)
 
 

@@ -376,6 +376,18 @@ class _HostEinsumOps:
         return [Val(x.v * y.v) for x, y in zip(xs, ys)]
 
 
+def claim_form(einsum_claim):
+    """the claim form of a circuit's einsums as its constructor takes it: "dot" or "contract", anything else a ValueError"""
+    if einsum_claim not in ("dot", "contract"):
+        raise ValueError("einsum_claim must be \"dot\" or \"contract\", not %r" % (einsum_claim,))
+    return einsum_claim
+
+
+def claim_identity(einsum_claim):
+    """what the claim form adds to a circuit's plan_identity: nothing for the default, so that every hash of a "dot" plan stays what it was"""
+    return b"" if einsum_claim == "dot" else b":einsum_claim=" + einsum_claim.encode()
+
+
 class EinsumCircuit(EinsumMatmulCircuit):
     """`Einsums::assign_einsum` (/root/reference/src/circuit/ops/chip/einsum/mod.rs:105-300) for any two-operand equation the reference
     lays out with Freivalds' argument, at block width 1 in one block: the plan is einsum_plan's (reduction_planner.rs, analysis.rs), the
@@ -387,9 +399,14 @@ class EinsumCircuit(EinsumMatmulCircuit):
     from the analysis; `over` lays the same sequence over the Freivalds columns of a GraphConfig.  Three or more operands (`multi_dot`),
     the base-op strategy and a column that overflows into a second block are refused by name."""
     plan_domain = b"einsum:"
+    einsum_claim = "dot"
 
-    def __init__(self, k, equation, dims, num_inner_cols=1):
+    def __init__(self, k, equation, dims, num_inner_cols=1, einsum_claim="dot"):
+        """einsum_claim: how a witness plan has the device compute the claimed product -- "dot", one one-step DOT record over the
+        operands' cells, or "contract", one CONTRACT record per index tuple of the batch axes (witness_plan.py); the cells, selectors,
+        copies and the proof do not depend on it"""
         self._plan(k, equation, dims, num_inner_cols)
+        self.einsum_claim = claim_form(einsum_claim)
         cs = self.cs = ConstraintSystem()
         self.base = type("Cfg", (), {})()
         self.einsums = EC.Einsums(cs, self.reduction_length, self.analysis.num_output_axes, num_inner_cols, k)
@@ -586,7 +603,7 @@ class EinsumCircuit(EinsumMatmulCircuit):
 
     def plan_identity(self):
         dims = ",".join("%s=%d" % (c, self.dims[c]) for c in sorted(self.dims))
-        return ("%s:k=%d:%s:%s" % (type(self).__name__, self.k, self.equation, dims)).encode()
+        return ("%s:k=%d:%s:%s" % (type(self).__name__, self.k, self.equation, dims)).encode() + claim_identity(self.einsum_claim)
 
     def advice_fn(self, a, b, n_advice):
         n, nc = 1 << self.k, self.analysis.num_output_axes
@@ -2484,12 +2501,32 @@ class _DeviceSurrogateWitness(_DeviceWitness):
         return run_ms, self.gpu.last_kernel_ms("witness_tile")                    # (reading the tile's events waits for it: the columns are final)
 
 
-class PhasedLayoutCircuit(LayoutCircuit):
+class _TakesEinsumClaim(type):
+    """every PhasedLayoutCircuit takes one keyword more than its constructor names: einsum_claim="dot" | "contract", how its witness plan
+    has the device compute the einsums' claimed products (EinsumCircuit).  It is no field of the layout -- cells, selectors, copies and
+    the proof do not depend on it -- so it is set here, once for all subclasses, and `config()` states it only when it is not the default.
+    Why not a plain `__init__` keyword: tests/test_circuit_config_cpu.py holds every key of `config()` to be a constructor parameter that its
+    helper can mutate and that `describe` always writes, while a description is to state the claim form only when it is not "dot".  The
+    attribute is set AFTER `__init__` returns: an `__init__` must not read it (nothing of the configuration depends on it; `plan_identity`
+    and the recorder read it later)."""
+
+    def __call__(cls, *args, einsum_claim="dot", **kw):
+        self = super().__call__(*args, **kw)
+        self.einsum_claim = claim_form(einsum_claim)
+        return self
+
+
+class PhasedLayoutCircuit(LayoutCircuit, metaclass=_TakesEinsumClaim):
     """what the circuits share that lay Freivalds einsums over their own configuration (`BaseRegion.einsum`) and so have second-phase
     advice: `layout(reg, inputs, param, challenges=None) -> outputs` states the op sequence (`synthesize` runs it for one phase or for
     both), `build` gives keygen's and create_proof's inputs with a per-phase advice callable, on the host or from the witness plan.
     Subclasses give `layout`, `n_inputs`, `default_inputs()`, `plan_identity()` and `config()`."""
     lays_einsums = True
+    einsum_claim = "dot"
+
+    def _claim_config(self):
+        """what `config()` adds for the claim form: nothing for the default, so that a description states it only when it is not "dot\""""
+        return {} if self.einsum_claim == "dot" else dict(einsum_claim=self.einsum_claim)
 
     def build(self, gpu=None, synthesis="host", as_ints=False, inputs=None):
         """-> dict(cs, fixed, copies, advice (callable(phase, challenges) -> {column: Montgomery array}), instances): the inputs of keygen
@@ -2573,12 +2610,12 @@ class AttentionHeadCircuit(PhasedLayoutCircuit):
     def plan_identity(self):
         shape = [self.k, self.w, self.n, self.e, self.d, self.input_scale, self.output_scale, self.score_div, self.base, self.legs,
                  self.lookup_range[0], self.lookup_range[1], self.gc.advices[0].num_blocks()]
-        return b"".join(np.asarray(a, np.int64).tobytes() for a in (shape, self.Wq, self.Wk, self.Wv)) + np.float64(self.eps).tobytes()
+        return b"".join(np.asarray(a, np.int64).tobytes() for a in (shape, self.Wq, self.Wk, self.Wv)) + np.float64(self.eps).tobytes() + claim_identity(self.einsum_claim)
 
     def config(self):
         return dict(logrows=self.k, n=self.n, e=self.e, d=self.d, capacity=self.capacity, num_inner_cols=self.w, input_scale=self.input_scale,
                     output_scale=self.output_scale, eps=self.eps, score_div=self.score_div, decomp_base=self.base, decomp_legs=self.legs,
-                    lookup_range=self.lookup_range, seed=self.seed, Wq=self.Wq, Wk=self.Wk, Wv=self.Wv)
+                    lookup_range=self.lookup_range, seed=self.seed, Wq=self.Wq, Wk=self.Wk, Wv=self.Wv, **self._claim_config())
 
 
 class BatchMlpCircuit(PhasedLayoutCircuit):
@@ -2673,11 +2710,11 @@ class BatchMlpCircuit(PhasedLayoutCircuit):
         shape = [self.k, self.w, self.m, self.base, self.legs, int(self.relu_last), int(self.relu_first), len(self.weights),
                  self.gc.advices[0].num_blocks()]
         per_layer = [a for W, b in zip(self.weights, self.biases) for a in ([len(W), len(W[0])], W, b)]
-        return b"".join(np.asarray(a, np.int64).tobytes() for a in [shape] + per_layer + [self.rebase])
+        return b"".join(np.asarray(a, np.int64).tobytes() for a in [shape] + per_layer + [self.rebase]) + claim_identity(self.einsum_claim)
 
     def config(self):
         return dict(logrows=self.k, num_inner_cols=self.w, batch=self.m, weights=self.weights, biases=self.biases, decomp_base=self.base,
-                    decomp_legs=self.legs, relu_last=self.relu_last, relu_first=self.relu_first, capacity=self.capacity, rebase=self.rebase)
+                    decomp_legs=self.legs, relu_last=self.relu_last, relu_first=self.relu_first, capacity=self.capacity, rebase=self.rebase, **self._claim_config())
 
 
 def limbs_to_mont(cols, gpu=None):

@@ -38,7 +38,8 @@ record, running values and phase bookkeeping -- into a TWO-phase plan of the uni
 (ezkl_hip_witness_tile_dev).
 An EinsumCircuit -- any two-operand equation of the Freivalds chip -- standing alone or laid over an AttentionHeadCircuit's configuration
 is recorded from its own `sequence` too (EinsumRecordingRegion.lay_einsum): its operands may be cells the circuit computed, and the product
-the prover claims is ONE DOT record of one step over those cells, emitted after them although the layout writes it before them.
+the prover claims is ONE DOT record of one step over those cells, emitted after them although the layout writes it before them -- or, asked
+for with the claim form "contract" (the circuit's `einsum_claim`), one CONTRACT record per index tuple of the equation's batch axes.
 
 The plan is a flat little-endian blob (`WitnessPlan.to_bytes`):
 
@@ -131,6 +132,19 @@ s is the signed value of the source cell.  A run-time failure is a lane's: repor
                one-hot classes"), p1 = 0: 1 if s equals the position, else 0 (BaseRegion._one_hot, layouts.rs:1398-1442).  s < 0, s >= p0 or
                |s| >= 2^62 fails: "one-hot index outside the classes"
 
+VERSION 2 is the same blob -- header, sections, rules -- whose record list may also hold the kinds of a SECOND table, `KINDS2`, numbered from
+KINDS_TOP = 32 (up to KINDS2_TOP = 33).  `to_bytes` writes version 2 only when a record needs it; a version-1 blob that names kind 32 is
+refused as unknown, as it always was, and so is a version-2 blob none of whose records is of the second table (the serializer never writes
+one); VERSION, KINDS, KINDS_TOP and UNASSIGNED_KINDS stay what they were.
+
+    32 CONTRACT  count = m * n destination cells, p0 = kd, p1 = n (all >= 1, count % n == 0, the three arrays inside the pool: else "bad
+               contract shape"); a: m * kd CELLS, row-major A; b: kd * n CELLS, row-major B.  pool[dst + i * n + j] = sum_t s(pool[a + i * kd + t]) *
+               s(pool[b + t * n + j]) over the INTEGERS, then integer_rep_to_felt: MATMUL over cells the circuit computed, in any phase.  A cell
+               may repeat within a or b: that is how an operand without one of the contracted axes is stated.  An operand with |s| >= 2^31
+               fails with MATMUL's words, element = its place in a, or m * kd + its place in b; the count is of operand reads; on the device
+               the record then writes none of its cells.  An einsum's claimed product recorded with the claim form "contract" is one such
+               record per index tuple of the batch axes: m * kd + kd * n + m * n pool words each, where the DOT claim takes 2 * kd * m * n
+
 PHASES.  A circuit with second-phase advice (the Freivalds einsum) has columns that depend on challenges squeezed after the first-phase
 commitments: its plan has n_phases = 2, and every record carries the phase whose run replays it.  Phases are non-decreasing along the
 record list; a column belongs to the phase of the records that write it (never to two; a column no record writes: phase 0); INPUT and
@@ -186,12 +200,15 @@ SUMACC, PRODACC, GATHER, CLAMP, SORT, ARGSORT = range(17, 23)
 RECIP, ISQRT, ARGEXT = 24, 25, 27
 SCATTER, COMPLEMENT, ONEHOT = 29, 30, 31
 KINDS_TOP = 32                                     # the first kind past them all
+VERSION2, CONTRACT, KINDS2_TOP = 2, 32, 33         # a version-2 blob may also name the kinds of KINDS2, numbered from KINDS_TOP
 SORT_TILE, MAX_SORT_COUNT = 2048, 1 << 28                       # csrc/witness_plan.hpp: the keys one workgroup sorts in LDS; the most cells of a sort record
 ARGEXT_CHUNK = 4096                                             # csrc/witness_plan.hpp: the sources one workgroup of an arg-extremum reduces
 SCATTER_TILE = 4096                                             # csrc/witness_plan.hpp: the destinations one workgroup of a scatter / a complement resolves in LDS
 DOT_WIDE_MIN, DOT_WIDE_FILL = 16, 1 << 17                       # csrc/witness_plan.hpp: a DOT record of one step with this many products runs on the wide kernel; the lanes that fill the device
-MAX_CLAIM_WORDS = 1 << 28                                       # the most pool words (2 * K * |O|) of an einsum's claim
+MAX_CLAIM_WORDS = 1 << 28                                       # the most pool words of an einsum's claim: 2 * K * |O| as a DOT record, m * kd + kd * n + m * n per CONTRACT record
 CLAIM_ERROR = "an einsum claim of more than 2^28 pool words"
+CLAIM_FORMS = ("dot", "contract")
+VERSION2_ERROR = "witness plan: version 2 without a record of the second kind table"
 
 
 def dot_wide_lanes(count, p0):
@@ -233,20 +250,29 @@ _ASSIGNED = {
 KINDS = [_ASSIGNED.get(kind, Kind("?", a=WORDS)) for kind in range(KINDS_TOP)]
 UNASSIGNED_KINDS = tuple(kind for kind in range(KINDS_TOP) if kind not in _ASSIGNED)      # (16, 23, 26, 28): they name nothing and never will; refused as unknown
 KIND_NAMES = [K.name for K in KINDS]               # "?" in the four holes
+KINDS2 = [Kind("contract", OPERAND_ERROR, "operand reads", b=CELLS)]     # the second table (KINDS2 of csrc/witness_plan.hpp): kind 32 on, version 2 only
 
 
 class PlanError(ValueError):
     pass
 
 
-def kind_name(kind):
-    """the name a message gives a record kind; "?" for a number that names nothing"""
-    return KIND_NAMES[kind] if 0 <= kind < KINDS_TOP else "?"
+def kind_info(kind, version=VERSION):
+    """the row of a kind in a blob of `version`, or None: the number names nothing there"""
+    if 0 <= kind < KINDS_TOP:
+        return None if kind in UNASSIGNED_KINDS else KINDS[kind]
+    return KINDS2[kind - KINDS_TOP] if version >= VERSION2 and KINDS_TOP <= kind < KINDS2_TOP else None
+
+
+def kind_name(kind, version=VERSION):
+    """the name a message gives a record kind; "?" for a number that names nothing (in a version-1 blob: everything from KINDS_TOP on)"""
+    K = kind_info(kind, version)
+    return K.name if K else "?"
 
 
 def dst_words(kind, count, p1):
     """how many destination words a record has: every step of every scan, else one per element"""
-    return count * p1 if KINDS[kind].scan else count
+    return count * p1 if kind < KINDS_TOP and KINDS[kind].scan else count
 
 
 # ---- symbolic values: what a Val's .v holds during the recording pass -------------------------------------------------------------------
@@ -1216,20 +1242,23 @@ class EinsumRecordingRegion(EL.Region):
     def mul(self, xs, ys):
         return [EL.Val(_Bin(MUL, x.v, y.v)) for x, y in zip(xs, ys)]
 
-    def lay_einsum(self, ein, operands):
+    def lay_einsum(self, ein, operands, claim="dot"):
         """an EinsumCircuit's `sequence` over symbols.  The prover's claim -- the product -- is ONE DOT record in phase 0: count = |O| dots
         of one step (p1 = 1) of p0 = K products, K the index tuples of the axes that are not in the output (an operand without such an
         axis repeats its cell); pool cost 2 * K * |O| words.  It reads CELLS: the cell an operand element already holds, else the
         first-phase einsum cell its own input reduction places it in.  The layout writes the claim BEFORE those cells, and a record
         reads only cells of earlier records: so the einsum is laid out once on a `_Probe` to learn where the operands and the product
         land, the operand cells are placed ahead of the layout, the claim is emitted, and the layout then finds both where it puts
-        them.  Returns the product as Vals that carry the claimed cells."""
+        them.  Returns the product as Vals that carry the claimed cells.
+        claim="contract": the same cells, claimed by CONTRACT records (`_claim_contract`) -- only how the device computes them differs."""
         import itertools, math
+        if claim not in CLAIM_FORMS:
+            raise PlanError("an einsum claim form that is neither \"dot\" nor \"contract\": %r" % (claim,))
         self.n_ops += 1
         an, dims = ein.analysis, ein.dims
         contracted = sorted(set("".join(ein.exprs)) - set(an.output_indices))
         K, n_out = math.prod(dims[c] for c in contracted), math.prod(ein.out_shape)
-        if 2 * K * n_out > MAX_CLAIM_WORDS:
+        if claim == "dot" and 2 * K * n_out > MAX_CLAIM_WORDS:
             raise PlanError(CLAIM_ERROR)
         probe = _Probe(self.cs, self.k, self.coord)
         ein.sequence(probe, [[EL.Val(_Tag(("operand", t, e))) for e in range(len(vals))] for t, vals in enumerate(operands)],
@@ -1248,26 +1277,53 @@ class EinsumRecordingRegion(EL.Region):
                 self.preplaced[mine[-1]] = val.v
             cells.append(mine)
         strides = [dict(zip(e, ein._strides([dims[c] for c in e]))) for e in ein.exprs]
-        ri = self.out._new((DOT, K, 0, 0))
-        product = []
-        for at, out_pos in enumerate(itertools.product(*[range(n) for n in ein.out_shape])):
-            pos = dict(zip(an.output_indices, out_pos))
-            pairs = []
-            for inner in itertools.product(*[range(dims[c]) for c in contracted]):
-                pos.update(zip(contracted, inner))
-                pairs.append(tuple(cells[t][sum(pos[c] * strides[t][c] for c in ein.exprs[t])] for t in (0, 1)))
+        for c in (c for mine in cells for c in mine):
+            if c not in self.out.rec_of:
+                raise PlanError("advice cell %d is read before it is written" % c)
+        dsts = []
+        for at in range(n_out):
             col, row = probe.where[("product", at)]
-            dst = (col.index << self.k) + row
-            for c in (c for ab in pairs for c in ab):
-                if c not in self.out.rec_of:
-                    raise PlanError("advice cell %d is read before it is written" % c)
-            self.out.recs[ri]["dots"].append([(dst, pairs)])
-            self.out._claim(dst, ri)
-            if self.cs.advice[col.index].phase != 0 or dst in self.phase_of:
+            dsts.append((col.index << self.k) + row)
+            if self.cs.advice[col.index].phase != 0 or dsts[-1] in self.phase_of:
                 raise PlanError("an einsum's claim outside a free first-phase cell")
-            self.phase_of[dst] = 0
-            product.append(EL.Val(_Placed(dst)))
-        return ein.sequence(self, operands, product, _EinsumOps(self), 1)
+            self.phase_of[dsts[-1]] = 0
+        if claim == "contract":
+            self._claim_contract(ein, cells, strides, contracted, dsts)
+        else:
+            ri = self.out._new((DOT, K, 0, 0))
+            for at, out_pos in enumerate(itertools.product(*[range(n) for n in ein.out_shape])):
+                pos = dict(zip(an.output_indices, out_pos))
+                pairs = []
+                for inner in itertools.product(*[range(dims[c]) for c in contracted]):
+                    pos.update(zip(contracted, inner))
+                    pairs.append(tuple(cells[t][sum(pos[c] * strides[t][c] for c in ein.exprs[t])] for t in (0, 1)))
+                self.out.recs[ri]["dots"].append([(dsts[at], pairs)])
+                self.out._claim(dsts[at], ri)
+        return ein.sequence(self, operands, [EL.Val(_Placed(dst)) for dst in dsts], _EinsumOps(self), 1)
+
+    def _claim_contract(self, ein, cells, strides, contracted, dsts):
+        """the claim as CONTRACT records in phase 0.  The axes of the equation fall into four groups -- batch: in both operands and the
+        output; M: in the first operand and the output; N: in the second and the output; K: everything that is not in the output -- and
+        every index tuple of the batch axes is one m x kd by kd x n product: one record of m * kd + kd * n + m * n pool words (the 2^28
+        limit holds for their sum).  An operand that lacks a K axis has no stride along it: it repeats its cell."""
+        import itertools, math
+        dims, out_axes = ein.dims, ein.analysis.output_indices
+        groups = [[c for c in out_axes if (c in ein.exprs[0]) == in_a and (c in ein.exprs[1]) == in_b] for in_a, in_b in ((True, True), (True, False), (False, True))]
+        batch, M, N = ([dict(zip(g, t)) for t in itertools.product(*[range(dims[c]) for c in g])] for g in groups)
+        Ks = [dict(zip(contracted, t)) for t in itertools.product(*[range(dims[c]) for c in contracted])]
+        m, n, kd = len(M), len(N), len(Ks)
+        if len(batch) * (m * kd + kd * n + m * n) > MAX_CLAIM_WORDS:
+            raise PlanError(CLAIM_ERROR)
+        out_strides = dict(zip(out_axes, ein._strides(ein.out_shape)))
+        at = lambda stride, *parts: sum(i * stride.get(c, 0) for part in parts for c, i in part.items())
+        for bt in batch:
+            ri = self.out._new((CONTRACT, kd, n, 0))
+            rec = self.out.recs[ri]
+            rec["a"] = [cells[0][at(strides[0], bt, i, t)] for i in M for t in Ks]
+            rec["b"] = [cells[1][at(strides[1], bt, t, j)] for t in Ks for j in N]
+            rec["dst"] = [dsts[at(out_strides, bt, i, j)] for i in M for j in N]
+            for dst in rec["dst"]:
+                self.out._claim(dst, ri)
 
     def put_cell(self, col, row, v):
         dst = (col.index << self.k) + row
@@ -1325,7 +1381,9 @@ class EinsumRecordingRegion(EL.Region):
 class PhasedLookupRecordingRegion(LookupRecordingRegion, EinsumRecordingRegion):
     """LookupRecordingRegion for a circuit that lays an einsum over its own configuration (`BaseRegion.einsum`): the model ops are
     placed by `put` (phase 0), the einsum's cells by EinsumRecordingRegion's `put_cell` with its matmul record, running values and phase
-    bookkeeping -- one record list, one cell numbering.  (The constructor chain ends in EinsumRecordingRegion's, as a Region's.)"""
+    bookkeeping -- one record list, one cell numbering.  (The constructor chain ends in EinsumRecordingRegion's, as a Region's.)
+    einsum_claim: the claim form of the circuit being recorded (`record_plan` sets it)."""
+    einsum_claim = "dot"
 
     def put(self, var, linear, val):
         placed = super().put(var, linear, val)
@@ -1337,7 +1395,7 @@ class PhasedLookupRecordingRegion(LookupRecordingRegion, EinsumRecordingRegion):
 
     def einsum(self, ein, A, B, challenges=None):
         if isinstance(ein, EL.EinsumCircuit):
-            return [EL.Val(v.v, ("adv", v.v.idx >> self.k, v.v.idx & ((1 << self.k) - 1))) for v in self.lay_einsum(ein, [list(A), list(B)])]
+            return [EL.Val(v.v, ("adv", v.v.idx >> self.k, v.v.idx & ((1 << self.k) - 1))) for v in self.lay_einsum(ein, [list(A), list(B)], self.einsum_claim)]
         L = ein.len
         flat = [v.v for M in (A, B) for row in M for v in row]
         if not all(isinstance(v, _Input) for v in flat):
@@ -1369,7 +1427,7 @@ def _record_general_einsum(circuit):
         raise PlanError("cells are numbered in 32 bits")
     reg = EinsumRecordingRegion(circuit)
     at = [0, circuit.sizes[0]]
-    reg.lay_einsum(circuit, [[EL.Val(_Input(at[t] + e)) for e in range(circuit.sizes[t])] for t in (0, 1)])
+    reg.lay_einsum(circuit, [[EL.Val(_Input(at[t] + e)) for e in range(circuit.sizes[t])] for t in (0, 1)], circuit.einsum_claim)
     return WitnessPlan._from_recorder(circuit, reg, [], [], n_challenges=len(circuit.cs.challenges),
                                       n_phases=1 + max(c.phase for c in circuit.cs.advice))
 
@@ -1427,6 +1485,7 @@ def record_plan(circuit):
         params.append(v)
         return EL.Val(_Param(len(params) - 1))
     reg.param_values = params
+    reg.einsum_claim = getattr(circuit, "einsum_claim", "dot")
     outs = circuit.layout(reg, [EL.Val(_Input(i)) for i in range(circuit.n_inputs)], param)
     # (reg.finish writes the fixed constant column: keygen's, not the witness's)
     if phased:
@@ -1437,9 +1496,9 @@ def record_plan(circuit):
 
 class WitnessPlan:
     def __init__(self, k, n_advice, n_inputs, params, consts, records, outputs, pool, n_cells, n_ops, param_hash, tables=(), table_values=(),
-                 n_challenges=0, n_phases=1):
+                 n_challenges=0, n_phases=1, blob_version=None):
         """tables: (lo, n, col_size, offset into table_values) per static lookup table"""
-        self.k, self.n_advice, self.n_inputs = k, n_advice, n_inputs
+        self.k, self.n_advice, self.n_inputs, self.blob_version = k, n_advice, n_inputs, blob_version
         self.n_challenges, self.n_phases = n_challenges, n_phases or 1
         self.tables = [tuple(int(v) for v in t) for t in tables]
         self.table_values = np.ascontiguousarray(table_values, np.int64).reshape(-1)
@@ -1466,11 +1525,11 @@ class WitnessPlan:
                 src, dst = (np.array([sc[t] for sc in rec["scans"]], np.uint32).T for t in (0, 1))     # step-major
                 n_cells += dst.size
                 records.append([RLC, len(rec["scans"]), rec["p0"], rec["p1"], push(dst), push(src), 0, phase])
-            elif rec["kind"] == MATMUL:
+            elif rec["kind"] in (MATMUL, CONTRACT):
                 if None in rec["dst"]:
                     raise PlanError("a matmul output is never placed")
                 n_cells += len(rec["dst"])
-                records.append([MATMUL, len(rec["dst"]), rec["p0"], rec["p1"], push(rec["dst"]), push(rec["a"]), push(rec["b"]), phase])
+                records.append([rec["kind"], len(rec["dst"]), rec["p0"], rec["p1"], push(rec["dst"]), push(rec["a"]), push(rec["b"]), phase])
             elif rec["kind"] in (SUMACC, PRODACC):
                 w, scans = rec["p0"], rec["scans"]
                 nd, ns = len(scans), max(len(sc) for sc in scans)
@@ -1532,8 +1591,15 @@ class WitnessPlan:
                    tables, np.concatenate(values) if values else (), n_challenges, n_phases)
 
     # ---- the blob ------------------------------------------------------------------------------------------------------------------------
+    @property
+    def version(self):
+        """what `to_bytes` writes: the version of the blob the plan was read from, else 2 only when a record is of a kind of the second table"""
+        if self.blob_version is not None:
+            return self.blob_version
+        return VERSION2 if len(self.records) and int(self.records[:, 0].max()) >= KINDS_TOP else VERSION
+
     def to_bytes(self):
-        head = _HEADER.pack(MAGIC, VERSION, self.k, self.n_advice, len(self.records), self.n_inputs, len(self.params), len(self.consts),
+        head = _HEADER.pack(MAGIC, self.version, self.k, self.n_advice, len(self.records), self.n_inputs, len(self.params), len(self.consts),
                             len(self.outputs), self.n_cells, len(self.pool), self.n_ops, len(self.tables), len(self.table_values), self.n_challenges,
                             self.n_phases if self.n_phases > 1 else 0, 0, 0, 0, 0, self.param_hash)
         directory = b"".join(struct.pack("<iIII", *t) for t in self.tables)
@@ -1549,8 +1615,8 @@ class WitnessPlan:
         f = _HEADER.unpack_from(blob)
         if f[0] != MAGIC:
             raise PlanError("witness plan: bad magic")
-        if f[1] != VERSION:
-            raise PlanError("witness plan: version %d, this build reads %d" % (f[1], VERSION))
+        if f[1] not in (VERSION, VERSION2):
+            raise PlanError("witness plan: version %d, this build reads %d and %d" % (f[1], VERSION, VERSION2))
         _, _, k, n_adv, n_rec, n_in, n_par, n_con, n_out, n_cells, n_words, n_ops, n_tab, n_val = f[:14]
         sizes = [8 * n_par, 32 * n_con, 32 * n_rec, 4 * n_out, 4 * n_words, 16 * n_tab, 8 * n_val]
         if len(blob) != _HEADER.size + sum(sizes):
@@ -1561,11 +1627,13 @@ class WitnessPlan:
         params = np.frombuffer(blob, "<i8", n_par, o[0])
         consts = [int.from_bytes(blob[o[1] + 32 * i:o[1] + 32 * i + 32], "little") for i in range(n_con)]
         records = np.frombuffer(blob, "<u4", 8 * n_rec, o[2])
+        if f[1] == VERSION2 and not (records[0::8] >= KINDS_TOP).any():     # `validate`'s rule, here too: a blob under a version word this
+            raise PlanError(VERSION2_ERROR)                                   # reader has no use for is refused when it is read, as ever
         outputs = np.frombuffer(blob, "<u4", n_out, o[3])
         pool = np.frombuffer(blob, "<u4", n_words, o[4])
         tables = [struct.unpack_from("<iIII", blob, o[5] + 16 * i) for i in range(n_tab)]
         values = np.frombuffer(blob[o[6]:o[7]], "<i8")
-        return cls(k, n_adv, n_in, params, consts, records, outputs, pool, n_cells, n_ops, f[20], tables, values, f[14], f[15])
+        return cls(k, n_adv, n_in, params, consts, records, outputs, pool, n_cells, n_ops, f[20], tables, values, f[14], f[15], f[1])
 
     def __eq__(self, other):
         return isinstance(other, WitnessPlan) and self.to_bytes() == other.to_bytes()
@@ -1584,7 +1652,7 @@ def peek(blob):
     if len(blob) < _HEADER.size:
         raise PlanError("witness plan: shorter than its header")
     f = _HEADER.unpack_from(blob)
-    if f[0] != MAGIC or f[1] != VERSION:
+    if f[0] != MAGIC or f[1] not in (VERSION, VERSION2):
         raise PlanError("witness plan: bad magic or version")
     names = ["k", "n_advice", "n_records", "n_inputs", "n_params", "n_consts", "n_outputs", "n_cells", "n_words", "n_ops", "n_tables", "n_table_values"]
     return dict(zip(names, f[2:14]), n_challenges=f[14], n_phases=f[15] or 1, param_hash=f[20])
@@ -1624,7 +1692,7 @@ class _Written:
 
 def _refuse(ri, kind, words):
     """a record refused; kind None: the messages that do not name the kind"""
-    return PlanError("witness plan: record %d%s: %s" % (ri, "" if kind is None else " (%s)" % KIND_NAMES[kind], words))
+    return PlanError("witness plan: record %d%s: %s" % (ri, "" if kind is None else " (%s)" % kind_name(kind, VERSION2), words))
 
 
 def validate(plan):
@@ -1646,12 +1714,15 @@ def validate(plan):
             raise PlanError("witness plan: table %d: bad lookup table shape" % ti)
         if off > len(plan.table_values) or n > len(plan.table_values) - off:
             raise PlanError("witness plan: table %d: runs past the table values" % ti)
+    if plan.version == VERSION2 and not (len(plan.records) and (plan.records[:, 0] >= KINDS_TOP).any()):
+        raise PlanError(VERSION2_ERROR)                   # (the serializer writes version 2 only when a record needs it; csrc/witness_plan.hpp refuses it too)
     written = _Written(cells, plan.pool)
     total, words = 0, len(plan.pool)
     fits = lambda off, n: off <= words and n <= words - off
     col_phase, last_phase = [None] * plan.n_advice, 0
     for ri, (kind, count, p0, p1, dst, a, b, phase) in enumerate(plan.records.tolist()):
-        if kind >= KINDS_TOP or kind in UNASSIGNED_KINDS:
+        K = kind_info(kind, plan.version)
+        if K is None:
             raise PlanError("witness plan: record %d: unknown kind %d" % (ri, kind))
         if count == 0 and kind != COMPLEMENT:             # (nothing missing: a complement that writes no cell)
             raise PlanError("witness plan: record %d is empty" % ri)
@@ -1663,7 +1734,7 @@ def validate(plan):
         if kind in (INPUT, MATMUL) and phase != 0:
             raise _refuse(ri, kind, "input and matmul records belong to phase 0")
         # the kind's own parameters, and the words it has: n_dst at dst, n_a at a, n_b at b, lim for its indices, `extra` further cells a lane reads
-        K, n_dst = KINDS[kind], dst_words(kind, count, p1)
+        n_dst = dst_words(kind, count, p1)
         n_a, n_b, lim, extra = count, 0, 0, None
         if kind in (ADD, SUB, MUL, ONEHOT):               # (ONEHOT: the position each element stands for, plain words)
             n_b = count
@@ -1685,7 +1756,11 @@ def validate(plan):
             if p0 == 0 or p1 == 0 or count % p1 != 0 or not (fits(dst, count) and fits(a, count // p1 * p0) and fits(b, p0 * p1)):
                 raise _refuse(ri, kind, "bad matmul shape")
             n_a, n_b, lim = count // p1 * p0, p0 * p1, plan.n_inputs
-        elif kind == RLC:                                 # p0 = challenge, p1 = steps, count = scans
+        elif kind == CONTRACT:                            # p0 = kd, p1 = n, count = m * n: a = m * kd, b = kd * n cells (version 2 only: kind_info)
+            if p0 == 0 or p1 == 0 or count % p1 != 0 or not (fits(dst, count) and fits(a, count // p1 * p0) and fits(b, p0 * p1)):
+                raise _refuse(ri, kind, "bad contract shape")
+            n_a, n_b = count // p1 * p0, p0 * p1
+        elif kind == RLC:                                # p0 = challenge, p1 = steps, count = scans
             if p0 >= plan.n_challenges:
                 raise _refuse(ri, kind, "challenge index out of range")
             if p1 == 0 or n_dst > words:
@@ -1817,7 +1892,8 @@ def lookup_stats_host(plan, columns):
 
 def _lane_failure(kind, ri, element):
     """the run-time failure of a lane, worded as the device words it (csrc/witness.hip)"""
-    return AssertionError("%s (%s record %d, element %d)" % (KINDS[kind].failure, KIND_NAMES[kind], ri, element))
+    K = kind_info(kind, VERSION2)
+    return AssertionError("%s (%s record %d, element %d)" % (K.failure, K.name, ri, element))
 
 
 def run_plan_host(plan, x, challenges=None, phase=None):
@@ -1839,16 +1915,17 @@ def run_plan_host(plan, x, challenges=None, phase=None):
     for ri, (kind, count, p0, p1, dst, a, b, rec_phase) in enumerate(plan.records.tolist()):
         if phase is not None and rec_phase > phase:
             break
-        if kind == MATMUL:
+        if kind in (MATMUL, CONTRACT):                     # MATMUL: over the inputs; CONTRACT: over the signed values of cells
             kd, nn = p0, p1
             m = count // nn
-            ia, ib = P[a:a + m * kd], P[b:b + kd * nn]
-            for e, i in enumerate(ia + ib):                # every operand a lane reads, the smallest failing element first
-                if abs(xs[i]) >= 1 << 31:
+            ops = [xs[i] if kind == MATMUL else EL.signed(cells[i]) for i in P[a:a + m * kd] + P[b:b + kd * nn]]
+            for e, v in enumerate(ops):                    # every operand a lane reads, the smallest failing element first
+                if abs(v) >= 1 << 31:
                     raise _lane_failure(kind, ri, e)
+            va, vb = ops[:m * kd], ops[m * kd:]
             for i in range(m):
                 for j in range(nn):
-                    cells[P[dst + i * nn + j]] = sum(xs[ia[i * kd + t]] * xs[ib[t * nn + j]] for t in range(kd)) % R
+                    cells[P[dst + i * nn + j]] = sum(va[i * kd + t] * vb[t * nn + j] for t in range(kd)) % R
             continue
         if kind == RLC:
             c = challenges[p0]

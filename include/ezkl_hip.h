@@ -417,7 +417,14 @@ int ezkl_hip_upload_end(ezkl_upload_t upload);
  *   receives n_outputs x 32 bytes, Montgomery words, as run's does.  One gather launch, one copy, one wait; HIP events around the launch:
  *   ezkl_hip_last_kernel_ms("witness_outputs").  Before phase 0 has succeeded, on other column pointers than it ran on, or with an
  *   output cell in a column of a phase that has not run to its end, the call returns EZKL_ERR_INVALID, ezkl_hip_witness_last_error says
- *   which, and nothing is launched.  A plan without outputs: EZKL_OK, nothing launched. */
+ *   which, and nothing is launched.  A plan without outputs: EZKL_OK, nothing launched.
+ * a version-2 plan: the same blob (header word 1 = 2) whose records may also be CONTRACT records (kind 32: the second kind table of
+ *   csrc/witness_plan.hpp) -- an m x kd by kd x n integer product over CELLS, in any phase, the claimed product of an einsum stated with
+ *   m * kd + kd * n + m * n index words.  Upload takes both versions (a version-1 blob that names kind 32 is refused as unknown) and sizes an
+ *   int32 operand scratch to the plan's largest m * kd + kd * n; run_phase launches two kernels for such a record where it launches one for
+ *   the others (a gather of the operands' cells, a tiled integer product), and reports an operand with |v| >= 2^31 as a matmul record's is:
+ *   the record then writes none of its cells.  plan_info's eight words are the same for both versions: k, n_advice, n_inputs, n_outputs,
+ *   n_records, n_cells, n_ops, n_params. */
 typedef struct ezkl_wplan_s* ezkl_wplan_t;
 typedef ezkl_wplan_t ezkl_witness_plan_t;
 int ezkl_hip_witness_plan_upload(const void* blob, size_t len, ezkl_wplan_t* out_plan);

@@ -12,6 +12,14 @@ Legs, each a child process of its own under `timeout -k 10`, one after the other
     attention  AttentionHeadCircuit at n = 64, e = 64, d = 32 (k = 17): both phases of its recorded plan; and its five claims record by
                record, as synthetic one-record plans of their (count, p0).
 
+    contract   (--claim contract, in place of the two above) the SAME products claimed both ways -- one one-step DOT record, one CONTRACT
+               record (a version-2 plan: wit_contract_gather_kernel + wit_contract_gemm_kernel) -- over the same cells of seeded int32-range
+               inputs: m x kd x n = 64 x 64 x 32 (the head's 2048 x 64 claims), 64 x 32 x 64 (its 4096 x 32 claim), 256^3, and 512^3 as a
+               CONTRACT record alone (its DOT claim is 2^28 pool words: the last size the recorder takes, a 1 GiB blob); and the attention
+               head recorded with einsum_claim="contract" beside the default recording.  Slots: `this_dot`, `this_dot_again` (the dot
+               leg's own spread), `this_contract`, `parent_dot` (the parent library replays the version-1 blobs).  Every entry carries
+               `bytes`, the size of its plan blob; all slots must write the same columns for a product, and for the head.
+
 A time is that of a whole `run` between the HIP events the library records around it (ezkl_hip_last_kernel_ms("witness")): the column
 fills, the records, the status read-back.  Per plan: --repeat runs after a first one, in each of --sittings uploads of the plan; `ms` is the
 median of the sitting medians, `spread` the greatest distance of a sitting median from it.  A DOT record's own cost is ms - floor.  The
@@ -31,6 +39,7 @@ sys.path.insert(0, ROOT)
 COUNT, WIDTHS, N_SRC, K_DOTS = 4096, (16, 24, 32, 48, 64, 128, 256, 512), 300, 13
 ATT = dict(k=17, n=64, e=64, d=32, blocks=4, decomp_base=1024)
 LIMIT_S = 420
+PRODUCTS, CONTRACT_ONLY, K_PRODUCTS = ((64, 64, 32), (64, 32, 64), (256, 256, 256), (512, 512, 512)), (512, 512, 512), 18
 
 
 def dot_blob(p0, count, seed=1, k=K_DOTS):
@@ -49,9 +58,34 @@ def dot_blob(p0, count, seed=1, k=K_DOTS):
     return WP.WitnessPlan(k, 2, 0, [], consts, records, [], np.concatenate(pool), cells, len(records), b"\0" * 32).validate().to_bytes()
 
 
-def attention():
+def product_inputs(m, kd, n):
+    """A (m x kd) then B (kd x n), row-major: seeded integers over the whole exact-product range"""
+    return np.random.default_rng(m * kd + n).integers(-(1 << 31) + 1, 1 << 31, m * kd + kd * n).tolist()
+
+
+def product_blob(m, kd, n, claim, k=K_PRODUCTS):
+    """the operands placed by one INPUT record in consecutive cells, the m * n products claimed from the next free column on: as one DOT
+    record of one step of kd products, or as one CONTRACT record over the same cells -- the same columns either way"""
+    from ezkl_amd import witness_plan as WP
+    n_a, n_in, count = m * kd, m * kd + kd * n, m * n
+    src = np.arange(n_in, dtype=np.uint32)
+    dst = (-(-n_in // (1 << k)) << k) + np.arange(count, dtype=np.uint32)
+    if claim == "contract":
+        a, b, rec = src[:n_a], src[n_a:], [WP.CONTRACT, count, kd, n]
+    else:                                                          # dot d = i * n + j, product t: A[i][t] . B[t][j], product-major
+        a = np.arange(kd, dtype=np.uint32)[:, None] + (np.arange(m, dtype=np.uint32) * kd).repeat(n)[None, :]
+        b = n_a + np.arange(kd, dtype=np.uint32)[:, None] * n + np.tile(np.arange(n, dtype=np.uint32), m)[None, :]
+        a, b, rec = a.reshape(-1), b.reshape(-1), [WP.DOT, count, kd, 1]
+    o = 2 * n_in
+    records = [[WP.INPUT, n_in, 0, 0, 0, n_in, 0, 0], rec + [o, o + count, o + count + len(a), 0]]
+    n_advice = -(-(int(dst[-1]) + 1) // (1 << k))
+    return WP.WitnessPlan(k, n_advice, n_in, [], [], records, [], np.concatenate([src, src, dst, a, b]), n_in + count, 2, b"\0" * 32).validate().to_bytes()
+
+
+def attention(einsum_claim="dot"):
     from ezkl_amd import ezkl_layout as EL
-    return EL.AttentionHeadCircuit(ATT["k"], ATT["n"], ATT["e"], ATT["d"], capacity=ATT["blocks"] << ATT["k"], decomp_base=ATT["decomp_base"])
+    return EL.AttentionHeadCircuit(ATT["k"], ATT["n"], ATT["e"], ATT["d"], capacity=ATT["blocks"] << ATT["k"], decomp_base=ATT["decomp_base"],
+                                   einsum_claim=einsum_claim)
 
 
 def timed(B, blob, inputs, repeat, sittings, challenges=()):
@@ -98,7 +132,20 @@ def child(a):
     ezkl_amd.init(0)
     blobs = os.path.join(ROOT, "profiles", "%s_einsum_blobs" % a.tag)
     entry = dict(library=os.path.relpath(lib.lib_path(), ROOT))
-    if a.leg == "dots":
+    if a.leg == "contract":
+        read = lambda name: open(os.path.join(blobs, name), "rb").read()
+        for m, kd, n in PRODUCTS:
+            if a.claim == "dot" and (m, kd, n) == CONTRACT_ONLY:
+                continue
+            blob = read("product_%dx%dx%d_%s.wplan" % (m, kd, n, a.claim))
+            t, _, digest = timed(B, blob, product_inputs(m, kd, n), a.repeat, a.sittings)
+            entry["%dx%dx%d" % (m, kd, n)] = dict(t["run"], columns=digest, bytes=len(blob))
+            print("contract leg, %s: %dx%dx%d %.4f ms" % (a.slot, m, kd, n, t["run"]["ms"]), flush=True)
+        meta = json.load(open(os.path.join(blobs, "attention.json")))
+        blob = read("attention.wplan" if a.claim == "dot" else "attention_contract.wplan")
+        t, _, digest = timed(B, blob, meta["inputs"], a.repeat, a.sittings, meta["challenges"])
+        entry["attention"] = dict(t, columns=digest, bytes=len(blob))
+    elif a.leg == "dots":
         for name in ["floor"] + ["p0_%d" % w for w in WIDTHS]:
             t, wide, digest = timed(B, open(os.path.join(blobs, name + ".wplan"), "rb").read(), [], a.repeat, a.sittings)
             entry[name] = dict(t["run"], wide_launches=wide, columns=digest)
@@ -113,16 +160,23 @@ def child(a):
         entry["claim_floor"] = dict(t["run"], columns=digest)
     dst = os.path.join(ROOT, "profiles", "%s_einsum.json" % a.tag)
     doc = json.load(open(dst)) if os.path.exists(dst) else {}
-    doc.setdefault(a.leg, {})[a.side] = entry
+    doc.setdefault(a.leg, {})[a.slot or a.side] = entry
     json.dump(doc, open(dst, "w"), indent=1, sort_keys=True)
-    print(json.dumps({a.leg: {a.side: entry}}))
+    print(json.dumps({a.leg: {a.slot or a.side: entry}}))
 
 
-def write_blobs(tag):
+def write_blobs(tag, claim="dot"):
     from ezkl_amd import ezkl_layout as EL, witness_plan as WP
     blobs = os.path.join(ROOT, "profiles", "%s_einsum_blobs" % tag)
     os.makedirs(blobs, exist_ok=True)
     put = lambda name, blob: open(os.path.join(blobs, name), "wb").write(blob)
+    if claim == "contract":                                        # beside the blobs below: the products both ways, the head with the contract claim
+        for m, kd, n in PRODUCTS:
+            for form in ("dot", "contract"):
+                if form == "contract" or (m, kd, n) != CONTRACT_ONLY:
+                    put("product_%dx%dx%d_%s.wplan" % (m, kd, n, form), product_blob(m, kd, n, form))
+        put("attention_contract.wplan", WP.record_plan(attention("contract")).validate().to_bytes())
+        return
     put("floor.wplan", dot_blob(0, COUNT))
     for w in WIDTHS:
         put("p0_%d.wplan" % w, dot_blob(w, COUNT))
@@ -144,8 +198,10 @@ def main():
     ap.add_argument("--parent", help="a built checkout of the parent commit: its ezkl_amd/libezkl_hip.so replays the same blobs")
     ap.add_argument("--repeat", type=int, default=20)
     ap.add_argument("--sittings", type=int, default=5)
-    ap.add_argument("--leg", choices=["dots", "attention"], help="one leg, in this process")
+    ap.add_argument("--leg", choices=["dots", "attention", "contract"], help="one leg, in this process")
     ap.add_argument("--side", choices=["this", "parent"], default="this")
+    ap.add_argument("--claim", choices=["dot", "contract"], default="dot", help="contract: the `contract` leg in place of the other two (in a child: the form it replays)")
+    ap.add_argument("--slot", help="(a child of the contract leg) the name its entry is kept under")
     ap.add_argument("--blobs-only", action="store_true", help="write the plan blobs and stop (no GPU)")
     a = ap.parse_args()
     if a.leg is not None:
@@ -153,6 +209,8 @@ def main():
     blobs = os.path.join(ROOT, "profiles", "%s_einsum_blobs" % a.tag)
     if not os.path.exists(os.path.join(blobs, "attention.json")):
         write_blobs(a.tag)
+    if a.claim == "contract" and not os.path.exists(os.path.join(blobs, "attention_contract.wplan")):
+        write_blobs(a.tag, "contract")
     if a.blobs_only:
         return
     if not a.parent:
@@ -160,17 +218,28 @@ def main():
     parent_lib = os.path.join(os.path.abspath(a.parent), "ezkl_amd", "libezkl_hip.so")
     if not os.path.exists(parent_lib):
         sys.exit("einsum_bench: %s is not built" % parent_lib)
+    def run_child(leg, side, *more):
+        env = dict(os.environ)
+        env.pop("EZKL_HIP_LIB", None)
+        if side == "parent":
+            env["EZKL_HIP_LIB"] = parent_lib
+        cmd = ["timeout", "-k", "10", str(LIMIT_S), sys.executable, os.path.abspath(__file__), "--tag", a.tag, "--repeat", str(a.repeat), "--sittings",
+               str(a.sittings), "--leg", leg, "--side", side] + list(more)
+        rc = subprocess.call(cmd, env=env)
+        if rc != 0:
+            sys.exit("einsum_bench: the %s leg on the %s library ended with status %d: nothing more is started" % (leg, side, rc))
+    if a.claim == "contract":
+        for slot, side, claim in (("this_dot", "this", "dot"), ("this_contract", "this", "contract"), ("parent_dot", "parent", "dot"), ("this_dot_again", "this", "dot")):
+            run_child("contract", side, "--claim", claim, "--slot", slot)
+        got = json.load(open(os.path.join(ROOT, "profiles", "%s_einsum.json" % a.tag)))["contract"]
+        want = {name: e["columns"] for name, e in got["this_contract"].items() if isinstance(e, dict)}
+        differ = [slot + ": " + name for slot, entry in got.items() for name, e in entry.items() if isinstance(e, dict) and e["columns"] != want[name]]
+        if differ:
+            sys.exit("einsum_bench: different columns for %s" % ", ".join(differ))
+        return
     for leg in ("dots", "attention"):
         for side in ("this", "parent"):
-            env = dict(os.environ)
-            env.pop("EZKL_HIP_LIB", None)
-            if side == "parent":
-                env["EZKL_HIP_LIB"] = parent_lib
-            cmd = ["timeout", "-k", "10", str(LIMIT_S), sys.executable, os.path.abspath(__file__), "--tag", a.tag, "--repeat", str(a.repeat), "--sittings",
-                   str(a.sittings), "--leg", leg, "--side", side]
-            rc = subprocess.call(cmd, env=env)
-            if rc != 0:
-                sys.exit("einsum_bench: the %s leg on the %s library ended with status %d: nothing more is started" % (leg, side, rc))
+            run_child(leg, side)
         got = json.load(open(os.path.join(ROOT, "profiles", "%s_einsum.json" % a.tag)))[leg]
         differ = [name for name, e in got["this"].items() if isinstance(e, dict) and e.get("columns") != got["parent"][name].get("columns")]
         if differ:
