@@ -584,10 +584,21 @@ def vec_fill(out_ptr, value, n, stream=None):
     _l.check(_l.load().ezkl_hip_vec_fill_dev(_vp(out_ptr), _p(_fe(value)), C.c_size_t(n), _stream_ptr(stream)), "ezkl_hip_vec_fill_dev")
 
 
-def coset_ntt_dev(in_ptr, out_ptr, k, ext_k, inverse=False, in_len=None, batch=1, stream=None):
-    """coeff_to_extended (inverse=False: 2^k coefficients in, 2^ext_k evaluations out) / extended_to_coeff on resident columns"""
-    nin = (1 << ext_k) if inverse else (1 << k)
-    _l.check(_l.load().ezkl_hip_coset_ntt_dev(_vp(in_ptr), _vp(out_ptr), C.c_size_t(batch), C.c_size_t(nin), C.c_size_t(1 << ext_k),
+def ntt_plan_info(log_n, max_radix=0):
+    """the pass plan of a 2^log_n transform (ezkl_hip_ntt_plan_info; no device needed): max_radix 0 = what this process read from
+    EZKL_NTT_MAXR.  Per pass: log2 radix, log2 tile, workgroup size"""
+    out = (C.c_uint32 * 16)()
+    _l.check(_l.load().ezkl_hip_ntt_plan_info(C.c_uint32(log_n), C.c_uint32(max_radix), out), "ezkl_hip_ntt_plan_info")
+    npass = out[0]
+    return dict(npass=npass, log_radix=list(out[1:1 + npass]), log_tile=list(out[5:5 + npass]), threads=list(out[9:9 + npass]), max_radix=out[13])
+
+
+def coset_ntt_dev(in_ptr, out_ptr, k, ext_k, inverse=False, batch=1, in_stride=None, out_stride=None, stream=None):
+    """coeff_to_extended (inverse=False: 2^k coefficients in, 2^ext_k evaluations out) / extended_to_coeff on resident columns;
+    in_stride / out_stride: elements between the columns of a batch (default: the columns lie one after the other)"""
+    nin = ((1 << ext_k) if inverse else (1 << k)) if in_stride is None else in_stride
+    nout = (1 << ext_k) if out_stride is None else out_stride
+    _l.check(_l.load().ezkl_hip_coset_ntt_dev(_vp(in_ptr), _vp(out_ptr), C.c_size_t(batch), C.c_size_t(nin), C.c_size_t(nout),
                                                C.c_uint32(k), C.c_uint32(ext_k), C.c_int(1 if inverse else 0), _stream_ptr(stream)),
              "ezkl_hip_coset_ntt_dev")
 

@@ -1024,6 +1024,8 @@ int ezkl_hip_ntt(void* data, uint32_t log_n, const void* omega, int inverse) {
     return rc;
 }
 
+int ezkl_hip_ntt_plan_info(uint32_t log_n, uint32_t max_radix, uint32_t* out16) { return ntt_plan_info(log_n, max_radix, out16); }
+
 static fe_t domain_omega(uint32_t k, bool inverse) {
     fe_t w = fr_const(FrConst::ROOT);
     for (uint32_t i = k; i < 28; i++) w = Fr::sqr(w);

@@ -378,13 +378,12 @@ static uint32_t ntt_max_radix() {
     }();
     return v;
 }
-static void plan_radices(uint32_t log_n, NttPlan* p) {
+static void plan_radices(uint32_t log_n, uint32_t maxr, NttPlan* p) {
     if (log_n <= NTT_LOG_SINGLE) {
         p->npass = 1;
         p->log_radix[0] = log_n;
         return;
     }
-    const uint32_t maxr = ntt_max_radix();
     int np = (int)((log_n + maxr - 1) / maxr);
     if (np < 2) np = 2;
     if (np > 4) np = 4;
@@ -396,10 +395,35 @@ static void plan_radices(uint32_t log_n, NttPlan* p) {
 // (radix 2^11 -- EZKL_NTT_MAXR=11, a 2^22 transform in TWO passes -- keeps the 72 KiB tile of the single-pass transforms: ONE column per tile,
 //  32-byte row segments; measured in round 6, profiles/r06j_ntt_maxr.log)
 static uint32_t pass_log_tile(uint32_t log_r) { return log_r >= 11 ? log_r : (log_r + 2 > NTT_LOG_TILE ? log_r + 2 : NTT_LOG_TILE); }
+// tile of one pass of a plan: a single-pass transform is its own tile, and no tile is smaller than the pass's radix
+static uint32_t plan_log_tile(uint32_t log_n, uint32_t npass, uint32_t log_r) {
+    const uint32_t log_tile = npass == 1 ? log_n : pass_log_tile(log_r);
+    return log_tile < log_r ? log_r : log_tile;
+}
+// workgroup size of a pass = the instance of ntt_pass_kernel that runs it
+static uint32_t pass_threads(uint32_t npass, uint32_t log_tile) { return npass > 1 && log_tile == 12 ? 1024u : (npass > 1 && log_tile == 11 ? 512u : 256u); }
 static void launch_pass(const PassArgs& a, uint32_t tiles, unsigned blocks_y, size_t lds, hipStream_t st) {
-    if (a.npass > 1 && a.log_tile == 12) hipLaunchKernelGGL(ntt_pass_kernel<1024>, dim3(tiles, blocks_y), dim3(1024), lds, st, a);
-    else if (a.npass > 1 && a.log_tile == 11) hipLaunchKernelGGL(ntt_pass_kernel<512>, dim3(tiles, blocks_y), dim3(512), lds, st, a);
+    const uint32_t threads = pass_threads(a.npass, a.log_tile);
+    if (threads == 1024) hipLaunchKernelGGL(ntt_pass_kernel<1024>, dim3(tiles, blocks_y), dim3(1024), lds, st, a);
+    else if (threads == 512) hipLaunchKernelGGL(ntt_pass_kernel<512>, dim3(tiles, blocks_y), dim3(512), lds, st, a);
     else hipLaunchKernelGGL(ntt_pass_kernel<256>, dim3(tiles, blocks_y), dim3(256), lds, st, a);
+}
+// the plan of a 2^log_n transform as the launches above take it, without a device (ezkl_hip_ntt_plan_info): out16 = npass, log_radix[4],
+// log_tile[4], workgroup size[4], the max radix in force, two zero words.  max_radix 0: what this process read from EZKL_NTT_MAXR
+int ntt_plan_info(uint32_t log_n, uint32_t max_radix, uint32_t* out16) {
+    if (!out16 || log_n > 28 || (max_radix != 0 && (max_radix < 6 || max_radix > 11))) return EZKL_ERR_INVALID;
+    const uint32_t maxr = max_radix ? max_radix : ntt_max_radix();
+    NttPlan p;
+    plan_radices(log_n, maxr, &p);
+    memset(out16, 0, 16 * sizeof(uint32_t));
+    out16[0] = (uint32_t)p.npass;
+    for (int i = 0; i < p.npass; i++) {
+        out16[1 + i] = p.log_radix[i];
+        out16[5 + i] = plan_log_tile(log_n, (uint32_t)p.npass, p.log_radix[i]);
+        out16[9 + i] = pass_threads((uint32_t)p.npass, out16[5 + i]);
+    }
+    out16[13] = maxr;
+    return EZKL_OK;
 }
 static int ntt_kernel_attrs() {
     bool& attr_set = ntt_state().attrs_set;               // function attributes are per device
@@ -419,7 +443,7 @@ static int plan_get(Ctx* c, hipStream_t st, uint32_t log_n, const fe_t& omega, N
     if (it != g_plans.end()) { *out = it->second; return EZKL_OK; }
     NttPlan* p = new NttPlan();
     p->log_n = log_n;
-    plan_radices(log_n, p);
+    plan_radices(log_n, ntt_max_radix(), p);
     // host: omega^(2^b), n^-1
     std::vector<fe_t> pow2(log_n ? log_n : 1);
     fe_t w = omega;
@@ -513,8 +537,7 @@ static int ntt_run_chunk(Ctx* c, hipStream_t st, const fe_t* in, fe_t* out, uint
         a.log_r = p->log_radix[i];
         a.lds_stages = ntt_lds_stages(a.log_r);
         a.log_m = log_m;
-        a.log_tile = p->npass == 1 ? log_n : pass_log_tile(a.log_r);
-        if (a.log_tile < a.log_r) a.log_tile = a.log_r;
+        a.log_tile = plan_log_tile(log_n, (uint32_t)p->npass, a.log_r);
         a.first = first;
         a.last = last;
         a.in_log_len = first ? in_log_len : log_n;
@@ -615,8 +638,7 @@ static int coset_cm_chunk(Ctx* c, hipStream_t st, const fe_t* in, fe_t* out, uin
         a.log_r = p->log_radix[i];
         a.lds_stages = ntt_lds_stages(a.log_r);
         a.log_m = log_m;
-        a.log_tile = p->npass == 1 ? log_n : pass_log_tile(a.log_r);
-        if (a.log_tile < a.log_r) a.log_tile = a.log_r;
+        a.log_tile = plan_log_tile(log_n, (uint32_t)p->npass, a.log_r);
         a.first = first;
         a.last = last;
         a.in_log_len = log_n;

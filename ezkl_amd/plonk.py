@@ -219,7 +219,7 @@ class GpuBackend:
         _b.coset_ntt_dev(h.ptr, o.ptr, self.k, ext_k, inverse=False)
         return o
     def extended_to_coeff(self, h, ext_k):
-        _b.coset_ntt_dev(h.ptr, h.ptr, self.k, ext_k, inverse=True, in_len=1 << ext_k)
+        _b.coset_ntt_dev(h.ptr, h.ptr, self.k, ext_k, inverse=True)
         return h
     def divide_by_vanishing(self, h, ext_k): _b.divide_by_vanishing_dev(h.ptr, self.k, ext_k)
     def eval_program(self, prog, cols, challenges, out): prog.evaluate_h([c.ptr for c in cols], [to_mont(c) for c in challenges], out.ptr)

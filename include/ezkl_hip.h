@@ -466,6 +466,10 @@ int ezkl_hip_ntt(void* data, uint32_t log_n, const void* omega, int inverse);
 /* device-resident batch: `batch` columns of 2^log_n elements, column b at data_dev + b*stride_elems*32 */
 int ezkl_hip_ntt_dev(void* data_dev, uint32_t log_n, const void* omega, int inverse,
                      size_t batch, size_t stride_elems, void* stream);
+/* the pass plan of a 2^log_n transform, from the functions the launches use; needs no device.  out16: number of passes, four
+ * log2 radices, four log2 tile sizes, four workgroup sizes (unused passes 0), the max radix in force, two zero words.
+ * max_radix 0: the value this process read from EZKL_NTT_MAXR; otherwise 6..11.  log_n <= 28. */
+int ezkl_hip_ntt_plan_info(uint32_t log_n, uint32_t max_radix, uint32_t* out16);
 /* coeff_to_extended (inverse = 0): in[b] has 2^log_n coefficients, out[b] gets 2^log_n_ext evaluations on
  * the zeta-coset.  extended_to_coeff (inverse = 1): in[b] has 2^log_n_ext evaluations, out[b] receives
  * 2^log_n_ext coefficients (caller truncates).  Host pointers.  in == out allowed when sizes match. */

@@ -229,6 +229,14 @@ def plan_radices(log_n, maxr=8):
     return [base + (1 if i < extra else 0) for i in range(np_)]
 
 
+def plan_log_tile(log_n, npass, log_r):
+    """ntt.hip plan_log_tile / pass_log_tile: a single-pass transform is its own tile; a pass of a longer plan takes at least 1024 elements
+    and 4 columns, except radix 2^11, which keeps ONE column per tile"""
+    if npass == 1:
+        return log_n
+    return log_r if log_r >= 11 else max(log_r + 2, NTT_LOG_TILE)
+
+
 def inter_table(log_n, log_m, log_r, w_n, twist=1, log_e=0, b=0, w_ext=None):
     """the inter-pass twiddles of a pass (ntt_twiddle_kernel mode 1; ntt_coset_table_kernel mode 1 for the twisted first pass): entry
     k1 S + i2 = w_M^(i2 k1) [* c_b^i2 for coset b], in the 2^261 domain"""
@@ -249,8 +257,7 @@ def run_pass(src, n_out, log_n, radices, i, table, tw_inter, unit1, in_log_len=N
     log_r, npass = radices[i], len(radices)
     first, last = i == 0, i + 1 == len(radices)
     log_m = log_n - sum(radices[:i])
-    log_tile = log_n if npass == 1 else max(log_r + 2, NTT_LOG_TILE)
-    log_tile = max(log_tile, log_r)
+    log_tile = max(plan_log_tile(log_n, npass, log_r), log_r)
     logC = log_tile - log_r
     C, R, TILE = 1 << logC, 1 << log_r, 1 << log_tile
     log_s = log_m - log_r
