@@ -534,6 +534,25 @@ def msm_g2(points, scalars):
     return out
 
 
+# csrc/msm_plan.hpp, held equal to it by tests/test_msm_g2_cpu.py: the n from which ezkl_hip_msm_g2 takes the bucket chain, and the scalars
+# of one tile of the chain's sort front end
+MSM_G2_CROSSOVER = 16
+MSM_G2_SORT_TILE = 1024
+
+
+def msm_g2_points(points, scalars, n=None, stream=None):
+    """sum_i scalars[i] * points[i] over G2 on resident data: points a DeviceBuffer of n 128-byte affine records (the SRS tail's layout),
+    scalars a DeviceBuffer of n Montgomery Fr -> (16,) u64 affine (ezkl_hip_msm_g2_points_dev; n defaults to what `scalars` holds)"""
+    if n is None:
+        n = scalars.nbytes // 32
+        if points.nbytes // 128 != n:
+            raise ValueError("one scalar per point")
+    out = np.zeros(16, np.uint64)
+    _l.check(_l.load().ezkl_hip_msm_g2_points_dev(_vp(getattr(points, "ptr", points)), _vp(getattr(scalars, "ptr", scalars)), C.c_size_t(int(n)),
+                                                   _p(out), _stream_ptr(stream)), "ezkl_hip_msm_g2_points_dev")
+    return out
+
+
 def g1_add_affine(a, b):
     a, b = _fe(a, 8), _fe(b, 8)
     out = np.zeros(8, np.uint64)

@@ -757,6 +757,11 @@ int ezkl_hip_msm_g2(const void* points_affine, const void* scalars, size_t n, vo
     EZ_CTX(c);
     return g2_msm(c, c->stream, points_affine, scalars, n, out_affine);
 }
+int ezkl_hip_msm_g2_points_dev(const void* points_dev, const void* scalars_dev, size_t n, void* out, void* stream) {
+    if (!points_dev || !scalars_dev || !out || n == 0 || ((uintptr_t)points_dev & 15)) return EZKL_ERR_INVALID;
+    EZ_CTX(c);
+    return g2_msm_points_run(c, pick_stream(c, stream), points_dev, (const fe_t*)scalars_dev, n, out);
+}
 size_t ezkl_hip_bases_len(ezkl_bases_t h) { return h ? reinterpret_cast<Bases*>(h)->n : 0; }
 
 int ezkl_hip_msm_g1_dev(ezkl_bases_t h, size_t base_offset, const void* scalars_dev, size_t n, void* out, void* stream) {

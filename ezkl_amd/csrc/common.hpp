@@ -189,5 +189,11 @@ int gen_bases(Ctx* c, hipStream_t st, uint64_t seed, size_t first, size_t n, voi
 int g1_to_lagrange(Ctx* c, hipStream_t st, const void* g_dev, uint32_t log_n, fe_t* tw_mont, const fe_t& ninv_mont, void* out_dev);
 void g1_add_affine_host(const void* a, const void* b, void* out);
 int g2_msm(Ctx* c, hipStream_t st, const void* pts_host, const void* scalars_host, size_t n, void* out_host);
+int g2_msm_points_run(Ctx* c, hipStream_t st, const void* pts_dev, const fe_t* scalars_dev, size_t n, void* out_host);
+struct WinPlan;
+struct MsmPlan;
+struct MsmG2Plan;
+void msm_once_sort_enqueue(hipStream_t st, const fe_t* scalars, size_t n, const WinPlan& wp, const MsmPlan& p, uint32_t w0, unsigned Z, uint8_t* S);
+int msm_g2_prepare(Ctx* c, size_t n, MsmG2Plan* plan, uint8_t** scratch);
 
 }  // namespace ezkl

@@ -1,13 +1,22 @@
 // g2.hip -- BN254 G2 (the sextic twist y^2 = x^3 + 3 / (9 + u) over Fq2 = Fq[u] / (u^2 + 1)) on the device.
 //
-// The north star names "multi-scalar multiplication over BN254 G1/G2".  On the reference's prove path G2 is DATA: the two points g2 and
-// s_g2 of the SRS file (/root/reference/src/pfsys/srs.rs:14-16: gen_srs -> ParamsKZG::setup computes s_g2 = [s] g2 once), consumed by the
-// verifier's pairing; no G2 MSM runs in `prove`.  This file is therefore a plain, correct G2 group law and a small MSM -- one
-// double-and-add per (point, scalar) pair, a strided partial sum per thread, one LDS tree -- for SRS generation and for callers that hold G2
-// commitments; it shares nothing with the G1 Pippenger pipeline and is not a hot path (n is 1 for every use the reference has).
+// On the prove path G2 is DATA (the two points g2 and s_g2 of the SRS file, consumed by the verifier's pairing); G2 sums are for SRS
+// generation and update, and for callers that hold G2 points on the device (an SRS tail, G2 commitments of another protocol, the G2 powers of
+// a powers-of-tau file).  Two paths:
+//   * g2_msm_points_run: a signed-digit BUCKET chain over resident points and scalars.  The table-free G1 chain's sort front end
+//     (msm_once_sort_enqueue, msm.hip) turns the scalars into per-window lists of (bucket, index) pairs; the kernels here are where the
+//     group law lives: accumulate (one lane per bucket + a workgroup per long run), reduce (segments of buckets, then one workgroup per
+//     window) and a tail that folds the windows and normalises on the device.  ~30 Fq products per (point, window) pair.  DESIGN.md §4.1
+//     "G2 MSM"; the plan is msm_plan_g2 (msm_plan.hpp).
+//   * g2_msm_partial_kernel / g2_msm_reduce_kernel: one double-and-add per (point, scalar) pair, ~4 000 Fq products each, a strided partial
+//     sum per thread, one LDS tree.  ezkl_hip_msm_g2 (host pointers) keeps it below MSM_G2_CROSSOVER points -- n = 1 in gen_srs / update_srs.
+// Field layer: field.hpp (radix 2^32, Fq::mul), not field29.hpp: the records arrive in the R = 2^256 Montgomery form of the SRS file and are
+// consumed as they are (no conversion pass), an XYZZ accumulator over Fq2 is 64 VGPRs instead of 72, and every kernel here is bound by the
+// latency of dependent products in few waves, not by the product throughput the radix-2^29 form was built for.
 // Layout: a G2 affine point is the 128 bytes of the SRS file -- x.c0, x.c1, y.c0, y.c1, each a 32-byte little-endian Montgomery Fq --
 // (0, 0) = identity.
 #include "common.hpp"
+#include "msm_plan.hpp"
 #include <string.h>
 
 namespace ezkl {
@@ -131,8 +140,270 @@ __global__ __launch_bounds__(64) void g2_msm_reduce_kernel(const g2j_t* partial,
     if (threadIdx.x == 0) *out = g2_to_affine(sh[0]);
 }
 
+// ---- the bucket chain --------------------------------------------------------------------------------------------------------------
+// XYZZ (extended Jacobian): x = X / ZZ, y = Y / ZZZ, ZZ^3 = ZZZ^2; identity: ZZ = 0 whatever the rest holds.  8 Fq values, 256 bytes.
+struct g2x_t {
+    fq2_t x, y, zz, zzz;
+};
+static_assert(sizeof(g2x_t) == MSM_G2_POINT_BYTES, "msm_plan_g2 lays the scratch out in points of this size");
+EZ_D g2x_t g2x_identity() { return g2x_t{f2_zero(), f2_zero(), f2_zero(), f2_zero()}; }
+EZ_D bool g2x_is_id(const g2x_t& p) { return f2_is_zero(p.zz); }
+EZ_D fq2_t ld_f2(const fq2_t* p) { return fq2_t{ld_fe(&p->a), ld_fe(&p->b)}; }
+EZ_D void st_f2(fq2_t* p, const fq2_t& v) { st_fe(&p->a, v.a); st_fe(&p->b, v.b); }
+EZ_D g2x_t ld_g2x(const g2x_t* p) { return g2x_t{ld_f2(&p->x), ld_f2(&p->y), ld_f2(&p->zz), ld_f2(&p->zzz)}; }
+EZ_D void st_g2x(g2x_t* p, const g2x_t& v) { st_f2(&p->x, v.x); st_f2(&p->y, v.y); st_f2(&p->zz, v.zz); st_f2(&p->zzz, v.zzz); }
+// the tail of a doubling, shared by the affine and the XYZZ form: U = 2Y, V = U^2, W = U V, S = X V, M = 3 X^2 (a = 0)
+EZ_D g2x_t g2x_double_core(const fq2_t& X, const fq2_t& Y, fq2_t& V, fq2_t& W) {
+    const fq2_t U = f2_dbl(Y);
+    V = f2_sqr(U);
+    W = f2_mul(U, V);
+    const fq2_t S = f2_mul(X, V), X2 = f2_sqr(X), M = f2_add(f2_dbl(X2), X2);
+    g2x_t r;
+    r.x = f2_sub(f2_sqr(M), f2_dbl(S));
+    r.y = f2_sub(f2_mul(M, f2_sub(S, r.x)), f2_mul(W, Y));
+    return r;
+}
+EZ_D g2x_t g2x_double_affine(const fq2_t& x, const fq2_t& y) {         // mdbl-2008-s-1; y = 0 gives ZZ = 0, the identity, as it must
+    fq2_t V, W;
+    g2x_t r = g2x_double_core(x, y, V, W);
+    r.zz = V; r.zzz = W;
+    return r;
+}
+EZ_D g2x_t g2x_double(const g2x_t& p) {                                // dbl-2008-s-1; the identity stays the identity (ZZ3 = V * 0)
+    fq2_t V, W;
+    g2x_t r = g2x_double_core(p.x, p.y, V, W);
+    r.zz = f2_mul(V, p.zz); r.zzz = f2_mul(W, p.zzz);
+    return r;
+}
+// the common tail of both additions: P = U2 - U1 != 0, R = S2 - S1; the caller multiplies ZZ, ZZZ by PP, PPP
+EZ_D g2x_t g2x_add_core(const fq2_t& U1, const fq2_t& S1, const fq2_t& P, const fq2_t& R, fq2_t& PP, fq2_t& PPP) {
+    PP = f2_sqr(P);
+    PPP = f2_mul(P, PP);
+    const fq2_t Q = f2_mul(U1, PP);
+    g2x_t r;
+    r.x = f2_sub(f2_sub(f2_sqr(R), PPP), f2_dbl(Q));
+    r.y = f2_sub(f2_mul(R, f2_sub(Q, r.x)), f2_mul(S1, PPP));
+    return r;
+}
+// madd-2008-s with every edge: the identity record (0, 0), an identity accumulator, P + P (a doubling) and P + (-P) (the identity).
+// neg: add -q.  8 M + 2 S over Fq2 = 28 Fq products on the common path.
+EZ_D g2x_t g2x_add_mixed(const g2x_t& p, const g2a_t& q, bool neg) {
+    if (f2_is_zero(q.x) && f2_is_zero(q.y)) return p;
+    const fq2_t qy = neg ? f2_neg(q.y) : q.y;
+    if (g2x_is_id(p)) return g2x_t{q.x, qy, f2_one(), f2_one()};
+    const fq2_t P = f2_sub(f2_mul(q.x, p.zz), p.x), R = f2_sub(f2_mul(qy, p.zzz), p.y);
+    if (f2_is_zero(P)) return f2_is_zero(R) ? g2x_double_affine(q.x, qy) : g2x_identity();
+    fq2_t PP, PPP;
+    g2x_t r = g2x_add_core(p.x, p.y, P, R, PP, PPP);
+    r.zz = f2_mul(p.zz, PP); r.zzz = f2_mul(p.zzz, PPP);
+    return r;
+}
+// add-2008-s with the same edges: 12 M + 2 S over Fq2 = 40 Fq products
+EZ_D g2x_t g2x_add(const g2x_t& p, const g2x_t& q) {
+    if (g2x_is_id(p)) return q;
+    if (g2x_is_id(q)) return p;
+    const fq2_t U1 = f2_mul(p.x, q.zz), S1 = f2_mul(p.y, q.zzz);
+    const fq2_t P = f2_sub(f2_mul(q.x, p.zz), U1), R = f2_sub(f2_mul(q.y, p.zzz), S1);
+    if (f2_is_zero(P)) return f2_is_zero(R) ? g2x_double(p) : g2x_identity();
+    fq2_t PP, PPP;
+    g2x_t r = g2x_add_core(U1, S1, P, R, PP, PPP);
+    r.zz = f2_mul(f2_mul(p.zz, q.zz), PP); r.zzz = f2_mul(f2_mul(p.zzz, q.zzz), PPP);
+    return r;
+}
+// k * p for a small k (a lane's or a segment's first weight: below 2^10), from the top bit; k = 0: the identity
+EZ_D g2x_t g2x_mul_small(const g2x_t& p, uint32_t k) {
+    g2x_t acc = g2x_identity();
+#pragma unroll 1
+    for (int b = 31 - __clz(k | 1u); b >= 0; b--) {
+        acc = g2x_double(acc);
+        if ((k >> b) & 1u) acc = g2x_add(acc, p);
+    }
+    return acc;
+}
+// sh[0] = sum of sh[0 .. T) (T a power of two, one entry per thread), every thread of the workgroup calls it
+EZ_D void g2x_lds_tree(g2x_t* sh, uint32_t T) {
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t s = T >> 1; s > 0; s >>= 1) {
+        if (threadIdx.x < s) sh[threadIdx.x] = g2x_add(sh[threadIdx.x], sh[threadIdx.x + s]);
+        __syncthreads();
+    }
+}
+template <class T> EZ_D T* g2_shift(T* p, size_t bytes) { return reinterpret_cast<T*>(reinterpret_cast<char*>(p) + bytes); }
+template <class T> EZ_D const T* g2_shift(const T* p, size_t bytes) { return reinterpret_cast<const T*>(reinterpret_cast<const char*>(p) + bytes); }
+
+// A pair of the sorted lists: the point's index and the sign of its digit.  The 128-byte record is eight 16-byte global loads.
+EZ_D g2a_t g2_fetch(const g2a_t* pts, uint32_t v) { return ld_g2a(pts + (v & 0x7fffffffu)); }
+// accumulate: member blockIdx.z of the group is one window; LANE = BUCKET.  A lane walks its bucket's run of the sorted payloads
+// [offsets[b], offsets[b + 1]) with the next payload and the next record loaded one addition ahead (the eight loads are in flight
+// under the ~28 dependent products of the addition that precedes their use).  Whole runs per lane: with at most 2^10 buckets per window and
+// up to 16 windows in a launch, the lanes of a launch are fewer than the device holds at one wave per SIMD, so a balanced split of the pairs
+// (the G1 kernel's lanes and fix-ups) would buy nothing here.  What breaks lane = bucket is skew, and a run longer than long_run is not walked:
+// the lane queues its bucket for g2_accumulate_long_kernel.  One-wave workgroups spread the few waves over the CUs.
+__global__ __launch_bounds__(64) void g2_accumulate_kernel(const g2a_t* pts, const uint32_t* offsets, const uint32_t* vals, uint32_t* long_list,
+                                                           uint32_t* long_count, size_t bstride, uint32_t nb, uint32_t long_run, g2x_t* buckets) {
+    const size_t bo = (size_t)blockIdx.z * bstride;
+    offsets = g2_shift(offsets, bo); vals = g2_shift(vals, bo); long_list = g2_shift(long_list, bo); long_count = g2_shift(long_count, bo);
+    buckets += (size_t)blockIdx.z * nb;
+    const uint32_t b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= nb) return;
+    const uint32_t beg = offsets[b], end = offsets[b + 1];
+    if (end - beg > long_run) {
+        long_list[atomicAdd(long_count, 1u)] = b;
+        return;
+    }
+    g2x_t acc = g2x_identity();
+    if (beg < end) {
+        uint32_t v = vals[beg];
+        g2a_t nxt = g2_fetch(pts, v);
+#pragma unroll 1
+        for (uint32_t k = beg; k < end; k++) {
+            const g2a_t cur = nxt;
+            const bool neg = (v >> 31) != 0;
+            if (k + 1 < end) {
+                v = vals[k + 1];
+                nxt = g2_fetch(pts, v);
+            }
+            acc = g2x_add_mixed(acc, cur, neg);
+        }
+    }
+    st_g2x(buckets + b, acc);
+}
+// the long runs (a column of equal scalars puts all n pairs of a window into one bucket): a workgroup per queued bucket, every thread a
+// strided share of the run, the MSM_G2_LONG_THREADS partial sums folded by a tree through LDS (32 KiB)
+__global__ __launch_bounds__(MSM_G2_LONG_THREADS) void g2_accumulate_long_kernel(const g2a_t* pts, const uint32_t* offsets, const uint32_t* vals,
+                                                                                 const uint32_t* long_list, const uint32_t* long_count, size_t bstride,
+                                                                                 uint32_t nb, g2x_t* buckets) {
+    __shared__ g2x_t sh[MSM_G2_LONG_THREADS];
+    const size_t bo = (size_t)blockIdx.z * bstride;
+    offsets = g2_shift(offsets, bo); vals = g2_shift(vals, bo); long_list = g2_shift(long_list, bo); long_count = g2_shift(long_count, bo);
+    buckets += (size_t)blockIdx.z * nb;
+    const uint32_t count = *long_count < nb ? *long_count : nb;
+#pragma unroll 1
+    for (uint32_t h = blockIdx.x; h < count; h += gridDim.x) {
+        const uint32_t b = long_list[h], beg = offsets[b], end = offsets[b + 1];
+        g2x_t acc = g2x_identity();
+        uint32_t k = beg + threadIdx.x;
+        if (k < end) {
+            uint32_t v = vals[k];
+            g2a_t nxt = g2_fetch(pts, v);
+#pragma unroll 1
+            for (; k < end; k += MSM_G2_LONG_THREADS) {
+                const g2a_t cur = nxt;
+                const bool neg = (v >> 31) != 0;
+                if (k + MSM_G2_LONG_THREADS < end) {
+                    v = vals[k + MSM_G2_LONG_THREADS];
+                    nxt = g2_fetch(pts, v);
+                }
+                acc = g2x_add_mixed(acc, cur, neg);
+            }
+        }
+        sh[threadIdx.x] = acc;
+        g2x_lds_tree(sh, MSM_G2_LONG_THREADS);
+        if (threadIdx.x == 0) st_g2x(buckets + b, sh[0]);
+        __syncthreads();
+    }
+}
+// reduce, first launch: sum_b (b + 1) * B_b over one SEGMENT of MSM_G2_SEG buckets per workgroup (one wave), as (C, T): C the weighted sum
+// with the segment's first bucket at weight 1, T the plain sum.  Lane l scans its MSM_G2_LANE_K consecutive buckets from the top with a
+// running suffix sum (run += B; U += run: two additions per bucket, U = sum_j (j + 1) B_j), lifts U by its own first weight
+// (U + (l K) * run, a double-and-add of at most 8 bits) and the 64 lane results of both kinds are folded by trees through LDS (32 KiB).
+__global__ __launch_bounds__(64) void g2_reduce_seg_kernel(const g2x_t* buckets, uint32_t nb, uint32_t nseg, g2x_t* seg) {
+    __shared__ g2x_t shC[64], shT[64];
+    buckets += (size_t)blockIdx.z * nb;
+    seg += ((size_t)blockIdx.z * nseg + blockIdx.x) * 2;
+    const uint32_t l = threadIdx.x, base = blockIdx.x * MSM_G2_SEG + l * MSM_G2_LANE_K;
+    g2x_t run = g2x_identity(), U = g2x_identity();
+#pragma unroll 1
+    for (uint32_t j = MSM_G2_LANE_K; j-- > 0;) {
+        if (base + j < nb) run = g2x_add(run, ld_g2x(buckets + base + j));
+        U = g2x_add(U, run);
+    }
+    shC[l] = g2x_add(U, g2x_mul_small(run, l * MSM_G2_LANE_K));
+    shT[l] = run;
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t s = 32; s > 0; s >>= 1) {
+        if (l < s) {
+            shC[l] = g2x_add(shC[l], shC[l + s]);
+            shT[l] = g2x_add(shT[l], shT[l + s]);
+        }
+        __syncthreads();
+    }
+    if (l == 0) { st_g2x(seg, shC[0]); st_g2x(seg + 1, shT[0]); }
+}
+// reduce, second launch: a workgroup per window combines the segments, S_w = sum_s C_s + (s * MSM_G2_SEG) * T_s
+__global__ __launch_bounds__(64) void g2_reduce_win_kernel(const g2x_t* seg, uint32_t nseg, g2x_t* win) {
+    __shared__ g2x_t sh[64];
+    seg += (size_t)blockIdx.z * nseg * 2;
+    g2x_t acc = g2x_identity();
+#pragma unroll 1
+    for (uint32_t s = threadIdx.x; s < nseg; s += 64) {
+        acc = g2x_add(acc, ld_g2x(seg + 2 * s));
+        acc = g2x_add(acc, g2x_mul_small(ld_g2x(seg + 2 * s + 1), s * MSM_G2_SEG));
+    }
+    sh[threadIdx.x] = acc;
+    g2x_lds_tree(sh, 64);
+    if (threadIdx.x == 0) st_g2x(win + blockIdx.z, sh[0]);
+}
+// tail: acc = S_{W-1}, then acc = 2^width(w) * acc + S_w for w = W-2 .. 0, and the canonical affine form (one f2_inv) -- 254 dependent
+// doublings, so one lane, in Jacobian coordinates (a doubling is 16 Fq products there against 24 in XYZZ).  (X, Y, ZZ, ZZZ) is the
+// Jacobian point (X ZZ, Y ZZZ, ZZ): Z^2 = ZZ^2 and Z^3 = ZZ^3 = ZZZ^2.
+__global__ __launch_bounds__(64) void g2_tail_kernel(const g2x_t* win, WinPlan wp, g2a_t* out) {
+    if (threadIdx.x) return;
+    g2j_t acc = g2_identity();
+#pragma unroll 1
+    for (uint32_t w = wp.W; w-- > 0;) {
+        if (w + 1 < wp.W) {
+#pragma unroll 1
+            for (uint32_t k = 0; k < wp.width(w); k++) acc = g2_double(acc);
+        }
+        const g2x_t s = ld_g2x(win + w);
+        if (!g2x_is_id(s)) acc = g2_add(acc, g2j_t{f2_mul(s.x, s.zz), f2_mul(s.y, s.zzz), s.zz});
+    }
+    const g2a_t r = g2_to_affine(acc);
+    st_f2(&out->x, r.x); st_f2(&out->y, r.y);
+}
+
+// points: n resident 128-byte affine records, scalars: n resident Montgomery Fr; out_host: 128 bytes; returns after `st` has drained
+int g2_msm_points_run(Ctx* c, hipStream_t st, const void* pts_dev, const fe_t* scalars_dev, size_t n, void* out_host) {
+    if (n == 0) return EZKL_ERR_INVALID;
+    if (n >= ((size_t)1 << 31)) return EZKL_ERR_UNSUPPORTED;      // a payload is 31 bits of index and the sign
+    MsmG2Plan q;
+    uint8_t* base = nullptr;
+    int rc = msm_g2_prepare(c, n, &q, &base);
+    if (rc) return rc;
+    const MsmPlan& p = q.chain;
+    if (p.LB != 0 || p.nb != q.nb) return EZKL_ERR_UNSUPPORTED;   // the reduce kernels weigh position b as bucket b (msm_plan_g2)
+    const g2a_t* pts = (const g2a_t*)pts_dev;
+    uint8_t* S = base + q.o_slabs;
+    g2x_t *bkt = (g2x_t*)(base + q.o_bkt), *seg = (g2x_t*)(base + q.o_seg), *win = (g2x_t*)(base + q.o_win);
+    g2a_t* d_out = (g2a_t*)(base + q.o_out);
+    const uint32_t *offs = (const uint32_t*)(S + p.o.offs), *vals = (const uint32_t*)(S + p.o.vals);
+    uint32_t *long_list = (uint32_t*)(S + p.o.heavy), *long_count = (uint32_t*)(S + p.o.hcnt);     // zeroed by the front end's first kernel
+    hipEvent_t m0 = nullptr, m1 = nullptr;
+    if ((rc = ev_pair(c, "msm_g2", &m0, &m1))) return rc;
+    EZ_HIP(hipEventRecord(m0, st));
+    for (size_t g = 0; g < q.ngroups; g++) {                      // one sequence of launches per group of windows; the groups reuse the slabs
+        const uint32_t w0 = (uint32_t)(g * q.group);
+        const unsigned Z = (unsigned)(q.wp.W - w0 < q.group ? q.wp.W - w0 : q.group);
+        msm_once_sort_enqueue(st, scalars_dev, n, q.wp, p, w0, Z, S);
+        hipLaunchKernelGGL(g2_accumulate_kernel, dim3(cdiv(q.nb, 64), 1, Z), dim3(64), 0, st, pts, offs, vals, long_list, long_count, p.bstride, q.nb,
+                           q.long_run, bkt);
+        hipLaunchKernelGGL(g2_accumulate_long_kernel, dim3(q.long_blocks, 1, Z), dim3(MSM_G2_LONG_THREADS), 0, st, pts, offs, vals,
+                           (const uint32_t*)long_list, (const uint32_t*)long_count, p.bstride, q.nb, bkt);
+        hipLaunchKernelGGL(g2_reduce_seg_kernel, dim3(q.nseg, 1, Z), dim3(64), 0, st, (const g2x_t*)bkt, q.nb, q.nseg, seg);
+        hipLaunchKernelGGL(g2_reduce_win_kernel, dim3(1, 1, Z), dim3(64), 0, st, (const g2x_t*)seg, q.nseg, win + w0);
+    }
+    hipLaunchKernelGGL(g2_tail_kernel, dim3(1), dim3(64), 0, st, (const g2x_t*)win, q.wp, d_out);
+    EZ_HIP(hipGetLastError());
+    EZ_HIP(hipEventRecord(m1, st));
+    EZ_HIP(hipMemcpyAsync(out_host, d_out, sizeof(g2a_t), hipMemcpyDeviceToHost, st));
+    EZ_HIP(hipStreamSynchronize(st));
+    return EZKL_OK;
+}
+
 int g2_msm(Ctx* c, hipStream_t st, const void* pts_host, const void* scalars_host, size_t n, void* out_host) {
-    (void)c;
     if (n == 0) { memset(out_host, 0, 128); return EZKL_OK; }
     g2a_t *d_pts = nullptr, *d_out = nullptr;
     fe_t* d_sc = nullptr;
@@ -145,12 +416,14 @@ int g2_msm(Ctx* c, hipStream_t st, const void* pts_host, const void* scalars_hos
     if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(g2a_t));
     if (e == hipSuccess) e = hipMemcpyAsync(d_pts, pts_host, n * sizeof(g2a_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_sc, scalars_host, n * sizeof(fe_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
+    if (e == hipSuccess && n >= MSM_G2_CROSSOVER) {          // the bucket chain on the uploaded copies
+        rc = g2_msm_points_run(c, st, d_pts, d_sc, n, out_host);
+    } else if (e == hipSuccess) {
         hipLaunchKernelGGL(g2_msm_partial_kernel, dim3(cdiv(T, 64)), dim3(64), 0, st, (const g2a_t*)d_pts, (const fe_t*)d_sc, n, d_part, T);
         hipLaunchKernelGGL(g2_msm_reduce_kernel, dim3(1), dim3(64), 0, st, (const g2j_t*)d_part, T, d_out);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_host, d_out, sizeof(g2a_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && n < MSM_G2_CROSSOVER) e = hipMemcpyAsync(out_host, d_out, sizeof(g2a_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) rc = set_hip_error(e, "g2_msm", __FILE__, __LINE__);
     if (d_pts) (void)hipFree(d_pts);

@@ -145,6 +145,7 @@ struct MsmState {
     MsmSlot slots[MSM_MAX_SLOTS];
     MsmSlot call_slots[MSM_CALL_SLOTS];
     MsmSlot once_slot;                // the MSM without window tables (msm_once_run): its scratch holds the converted points and a group's slabs
+    MsmSlot g2_slot;                  // the G2 MSM (g2.hip): scratch only
     bool call_claimed[MSM_CALL_SLOTS] = {false, false, false, false};
     bool call_finishing[MSM_CALL_SLOTS] = {false, false, false, false};   // a finish is running outside the lock: a second finish of the token is refused
     std::thread::id call_owner[MSM_CALL_SLOTS];
@@ -1175,6 +1176,43 @@ int msm_run(Ctx* c, hipStream_t st, const Bases* b, size_t base_offset, const fe
     return rc;
 }
 
+// The sort front end of the table-free chain, alone: windows w0 .. w0 + Z - 1 of one scalar column into per-window lists of (bucket, index)
+// pairs -- offsets[0 .. nb] and the sorted payloads (index | sign << 31) in the Z slabs at S, laid out by p.  What consumes the lists knows
+// what a point is: msm_once_run below (G1) and g2_msm_points_run (g2.hip).  The caller checks hipGetLastError.
+void msm_once_sort_enqueue(hipStream_t st, const fe_t* scalars, size_t n, const WinPlan& wp, const MsmPlan& p, uint32_t w0, unsigned Z, uint8_t* S) {
+    const uint32_t LB = p.LB, NP = p.NP, NQ = p.NQ;
+    const size_t per_block = p.per_block, bstride = p.bstride;
+    MsmCols kcols;                                            // every member reads the one column
+    for (size_t j = 0; j < MSM_MAX_GROUP; j++) kcols.col[j] = scalars;
+    auto u32 = [&](size_t o) { return (uint32_t*)(S + o); };
+    uint2* entries = (uint2*)(S + p.o.ent);
+    uint32_t *vals = u32(p.o.vals), *offs = u32(p.o.offs), *pcnt = u32(p.o.pcnt), *pbase = u32(p.o.pbase), *wghist = u32(p.o.wghist), *hcnt = u32(p.o.hcnt);
+    uint32_t *bflag = u32(p.o.bflag), *blist = u32(p.o.blist), *btot = u32(p.o.btot), *boff = u32(p.o.boff);
+    uint32_t* bcnt = hcnt + 2;
+    g1x29_t* bkt = (g1x29_t*)(S + p.o.bkt);
+    hipLaunchKernelGGL(msm_hist_once_kernel, dim3(p.sgrid, 1, Z), dim3(256), 0, st, kcols, n, per_block, wp, LB, NP, wghist, hcnt,
+                       (uint32_t)(p.zero_bytes / 4), bstride, w0);
+    hipLaunchKernelGGL(msm_hist_scan_kernel, dim3(cdiv(NQ, MSM_SCAN_COLS), 1, Z), dim3(1024), 0, st, wghist, p.sgrid, NQ, pcnt, bstride);
+    hipLaunchKernelGGL(msm_part_scan_kernel, dim3(1, 1, Z), dim3(1024), 0, st, pcnt, NQ, pbase, bflag, blist, bcnt, bstride);
+    hipLaunchKernelGGL(msm_partition_once_kernel, dim3(p.pgrid, 1, Z), dim3((unsigned)per_block), p.part_lds, st, kcols, n, per_block,
+                       (uint32_t)p.sgrid, wp, LB, NP, (size_t)0, (size_t)0, pbase, wghist, pcnt, entries, vals, bstride, w0);     // payload = index
+    hipLaunchKernelGGL(msm_binsort_kernel, dim3(NP + MSM_BIG_BLOCKS * MSM_BIG_ROWS, 1, Z), dim3(512), MSM_BINSORT_STAGE * 4, st, entries, pbase, LB, NP, bflag,
+                       offs, vals, bkt, blist, bcnt, btot, boff, bstride);
+    hipLaunchKernelGGL(msm_bigsort_scatter_kernel, dim3(MSM_BIG_BLOCKS, MSM_BIG_ROWS, Z), dim3(512), 0, st, entries, pbase, LB, blist, bcnt, btot, boff, offs,
+                       vals, bkt, bstride);
+}
+// what the G2 chain takes from this module: its plan (sized by the same device facts as the G1 chains) and scratch that stays between calls
+int msm_g2_prepare(Ctx* c, size_t n, MsmG2Plan* plan, uint8_t** scratch) {
+    int rc = EZKL_OK;
+    int& acc_blocks_per_cu = msm_state().acc_blocks_per_cu;
+    if ((rc = msm_device_init(acc_blocks_per_cu))) return rc;
+    *plan = msm_plan_g2(n, c->num_cus, acc_blocks_per_cu, msm_tuning());
+    MsmSlot& sl = msm_state().g2_slot;
+    if ((rc = slot_prepare(sl, plan->bytes, 0))) return rc;
+    *scratch = sl.scratch;
+    return EZKL_OK;
+}
+
 // ---- an MSM WITHOUT window tables: for points that are used once (an SRS under check, a verifier's commitments) -------------------------
 // sum_i s_i P_i = sum_w 2^offset(w) * S_w,  S_w = sum_i d_{w,i} P_i  (d: msm_recode's signed digits).  Every S_w is the chain above run over
 // the raw points: they stand in as a one-level table (converted once per call to the accumulate kernel's form), the hist and partition passes
@@ -1208,23 +1246,18 @@ int msm_once_run(Ctx* c, hipStream_t st, const void* points_dev, const fe_t* sca
     const MsmPlan& p = q.chain;
     const WinPlan wp = q.wp;
     const ReduceGeom rg = p.rg;
-    const uint32_t nb = p.nb, LB = p.LB, NP = p.NP, NQ = p.NQ, nlanes = p.nlanes, lmin = tu.lmin, span_heavy = tu.span_heavy;
-    const size_t per_block = p.per_block, bstride = p.bstride;
+    const uint32_t nb = p.nb, nlanes = p.nlanes, lmin = tu.lmin, span_heavy = tu.span_heavy;
+    const size_t bstride = p.bstride;
     constexpr uint32_t coop = 7;                              // as in msm_enqueue
     MsmSlot& sl = msm_state().once_slot;
     if (sl.busy) return EZKL_ERR_INVALID;
     if ((rc = slot_prepare(sl, q.bytes, MSM_ONCE_MAX_W))) return rc;     // the landing buffer: a record block per window of ANY plan (585 KB, once)
     g1a_t* pts = (g1a_t*)(sl.scratch + q.o_points);
     uint8_t* S = sl.scratch + q.o_slabs;
-    MsmCols kcols;                                            // every member reads the one column
-    for (size_t j = 0; j < MSM_MAX_GROUP; j++) kcols.col[j] = scalars;
     auto u32 = [&](size_t o) { return (uint32_t*)(S + o); };
     auto pt = [&](size_t o) { return (g1x29_t*)(S + o); };
-    uint2* entries = (uint2*)(S + p.o.ent);
-    uint32_t *vals = u32(p.o.vals), *offs = u32(p.o.offs), *pcnt = u32(p.o.pcnt), *pbase = u32(p.o.pbase), *wghist = u32(p.o.wghist);
+    uint32_t *vals = u32(p.o.vals), *offs = u32(p.o.offs);
     uint32_t *heavy = u32(p.o.heavy), *hcnt = u32(p.o.hcnt), *chunks = u32(p.o.chunks), *lfirst = u32(p.o.lfirst);
-    uint32_t *bflag = u32(p.o.bflag), *blist = u32(p.o.blist), *btot = u32(p.o.btot), *boff = u32(p.o.boff);
-    uint32_t* bcnt = hcnt + 2;
     g1x29_t *bkt = pt(p.o.bkt), *head = pt(p.o.head), *tail = pt(p.o.tail), *planes = pt(p.o.planes);
     g1x29_t *partA = pt(p.o.partA), *partT = pt(p.o.partT), *SA = pt(p.o.SA), *TT = pt(p.o.T);
     hipEvent_t m0 = nullptr, m1 = nullptr;
@@ -1235,16 +1268,7 @@ int msm_once_run(Ctx* c, hipStream_t st, const void* points_dev, const fe_t* sca
         const uint32_t w0 = (uint32_t)(g * q.group);
         const unsigned Z = (unsigned)(wp.W - w0 < q.group ? wp.W - w0 : q.group);
         g1x29_t* landing = (g1x29_t*)sl.pinned_dev + (size_t)w0 * 32;      // window w's planes land in record block w
-        hipLaunchKernelGGL(msm_hist_once_kernel, dim3(p.sgrid, 1, Z), dim3(256), 0, st, kcols, n, per_block, wp, LB, NP, wghist, hcnt,
-                           (uint32_t)(p.zero_bytes / 4), bstride, w0);
-        hipLaunchKernelGGL(msm_hist_scan_kernel, dim3(cdiv(NQ, MSM_SCAN_COLS), 1, Z), dim3(1024), 0, st, wghist, p.sgrid, NQ, pcnt, bstride);
-        hipLaunchKernelGGL(msm_part_scan_kernel, dim3(1, 1, Z), dim3(1024), 0, st, pcnt, NQ, pbase, bflag, blist, bcnt, bstride);
-        hipLaunchKernelGGL(msm_partition_once_kernel, dim3(p.pgrid, 1, Z), dim3((unsigned)per_block), p.part_lds, st, kcols, n, per_block,
-                           (uint32_t)p.sgrid, wp, LB, NP, (size_t)0, (size_t)0, pbase, wghist, pcnt, entries, vals, bstride, w0);     // payload = index
-        hipLaunchKernelGGL(msm_binsort_kernel, dim3(NP + MSM_BIG_BLOCKS * MSM_BIG_ROWS, 1, Z), dim3(512), MSM_BINSORT_STAGE * 4, st, entries, pbase, LB, NP, bflag,
-                           offs, vals, bkt, blist, bcnt, btot, boff, bstride);
-        hipLaunchKernelGGL(msm_bigsort_scatter_kernel, dim3(MSM_BIG_BLOCKS, MSM_BIG_ROWS, Z), dim3(512), 0, st, entries, pbase, LB, blist, bcnt, btot, boff, offs,
-                           vals, bkt, bstride);
+        msm_once_sort_enqueue(st, scalars, n, wp, p, w0, Z, S);
         hipLaunchKernelGGL(msm_accumulate_kernel, dim3(cdiv(nlanes, 256), 1, Z), dim3(256), 0, st, pts, offs, vals, nb, nlanes, bkt, head, tail, lfirst, lmin, bstride);
         if (nlanes > 1)
             hipLaunchKernelGGL(msm_fixup_boundary_tree_kernel, dim3(cdiv(nlanes - 1, 256), 1, Z), dim3(256), 0, st, offs, nb, nlanes, lfirst, head, tail, bkt,

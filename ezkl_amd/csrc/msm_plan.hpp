@@ -265,4 +265,72 @@ inline MsmOncePlan msm_plan_once(size_t n, int num_cus, int acc_blocks_per_cu, c
     return q;
 }
 
+// ---- the G2 MSM (g2.hip: g2_msm_points_run) --------------------------------------------------------------------------------------
+// The table-free chain's sort front end (hist, scans, partition, bin sort: one window per member of a fused group) feeds G2 kernels of
+// their own: accumulate (one lane per bucket, long runs by a workgroup), reduce (segments of MSM_G2_SEG buckets, then one workgroup per
+// window) and a tail that folds the windows and normalises.  An addition over Fq2 costs ~3.5 G1 additions and n is small (an SRS tail,
+// a handful of commitments), so the windows are NARROWER than pick_plan_once's: at most 11 bits, i.e. at most 2^10 buckets per window.
+// That keeps the front end in its one-level form (PB = bits, LB = 0: a bucket's position IS the bucket, weight = position + 1), which
+// the G2 reduce relies on.  Cost model in G2 additions: W * (n + 4 * buckets) + one MSM_G2_CHAIN_COST per sequence of launches.  The
+// constant is an estimate (a sequence of six short launches against ~1 us per latency-bound addition of a lone wave), not a measurement.
+static constexpr uint32_t MSM_G2_MIN_W = 24, MSM_G2_MAX_W = 64;      // 254 bits in windows of 11 .. 4 bits
+static constexpr size_t MSM_G2_CHAIN_COST = (size_t)1 << 14;
+static constexpr size_t MSM_G2_POINT_BYTES = 256;                    // sizeof(g2x_t): XYZZ over Fq2, 8 x 32 bytes (radix 2^32)
+static constexpr uint32_t MSM_G2_LANE_K = 4;                         // consecutive buckets per lane of the segment reduce
+static constexpr uint32_t MSM_G2_SEG = 64 * MSM_G2_LANE_K;           // buckets per segment = per workgroup (one wave) of the segment reduce
+static constexpr uint32_t MSM_G2_LONG_THREADS = 128;                 // lanes that share one long run (32 KiB of LDS for their fold)
+// ezkl_hip_msm_g2 (host pointers): from this n on the bucket chain, below it the double-and-add kernel.  MEASURED (tools/msm_g2_bench.py,
+// profiles/mi355x_msm_g2.json): at every size from 2^4, the smallest measured, to 2^16 the chain's slowest run is below the double-and-add
+// kernel's fastest (7.8 against 14.7 ms at 2^4: the chain's floor is its serial tail, ~254 doublings of one lane, about half the ~254
+// doublings + ~127 additions every lane of the double-and-add kernel runs; 17.7 against 943 ms at 2^16).  Nothing below 2^4 was measured,
+// and the n = 1 of gen_srs / update_srs stays where it was.
+static constexpr size_t MSM_G2_CROSSOVER = 16;
+inline WinPlan pick_plan_g2(size_t n) {
+    WinPlan best{0, 0, 0};
+    double best_cost = 0;
+    for (uint32_t W = MSM_G2_MIN_W; W <= MSM_G2_MAX_W; W++) {
+        WinPlan p{W, 254 / W, 254 % W};
+        const double groups = (double)((W + MSM_MAX_GROUP - 1) / MSM_MAX_GROUP);
+        const double cost = (double)W * ((double)n + 4.0 * (double)((size_t)1 << (p.cmax() - 1))) + groups * (double)MSM_G2_CHAIN_COST;
+        if (!best.W || cost < best_cost) { best = p; best_cost = cost; }
+    }
+    return best;
+}
+// the launch plan of a G2 MSM:
+//   wp             the windows (pick_plan_g2);  chain: ONE window's sort front end, msm_plan for n pairs (its point regions are G1-sized and
+//                  only the empty-bucket marks of the bin sort land there), `group` slabs bstride apart
+//   group, ngroups as in MsmOncePlan;  nb: buckets per window;  nseg: segments of MSM_G2_SEG buckets per window
+//   long_run       a bucket with more pairs than this is left to the workgroups of the long-run kernel (long_blocks of them per window)
+//   o_slabs ..     byte offsets in the scratch: the group's slabs, its bucket sums (group x nb points), its segment results (group x nseg x 2),
+//                  the window sums (W points, kept for the tail), the affine result (128 bytes);  bytes: the whole scratch
+struct MsmG2Plan {
+    WinPlan wp;
+    MsmPlan chain;
+    size_t group, ngroups;
+    uint32_t nb, nseg, long_run, long_blocks;
+    size_t o_slabs, o_bkt, o_seg, o_win, o_out, bytes;
+};
+inline MsmG2Plan msm_plan_g2(size_t n, int num_cus, int acc_blocks_per_cu, const MsmTuning& tu) {
+    MsmG2Plan q{};
+    q.wp = pick_plan_g2(n);
+    const WinPlan one{1, q.wp.cmax(), 0};
+    q.ngroups = (q.wp.W + MSM_MAX_GROUP - 1) / MSM_MAX_GROUP;
+    q.group = (q.wp.W + q.ngroups - 1) / q.ngroups;
+    q.chain = msm_plan(n, one, q.group, num_cus, acc_blocks_per_cu, tu);
+    q.nb = q.chain.nb;
+    q.nseg = (q.nb + MSM_G2_SEG - 1) / MSM_G2_SEG;
+    const size_t load = n / q.nb;                          // four times the mean run, and never a run the lanes of the long-run kernel would not fill
+    q.long_run = (uint32_t)(4 * load > 2 * MSM_G2_LONG_THREADS ? 4 * load : 2 * MSM_G2_LONG_THREADS);
+    q.long_blocks = q.nb < (uint32_t)num_cus ? q.nb : (uint32_t)num_cus;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    q.o_slabs = carve(q.group * q.chain.slab_bytes);
+    q.o_bkt = carve(q.group * q.nb * MSM_G2_POINT_BYTES);
+    q.o_seg = carve(q.group * q.nseg * 2 * MSM_G2_POINT_BYTES);
+    q.o_win = carve(q.wp.W * MSM_G2_POINT_BYTES);
+    q.o_out = carve(128);
+    q.bytes = off;
+    return q;
+}
+
 }  // namespace ezkl

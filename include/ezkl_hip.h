@@ -207,9 +207,17 @@ int ezkl_hip_bases_downsize(ezkl_bases_t g, uint32_t new_k, ezkl_bases_t* out_g,
 /* sum_i scalars[i] * points[i] over G2 (the twist over Fq2).  points: n x 128 B affine -- x.c0, x.c1, y.c0, y.c1 as 32-byte little-endian
  * Montgomery Fq, the layout of the g2 / s_g2 tail of an SRS file, (0, 0) = identity; scalars: n x 32 B Montgomery Fr; out: 128 B canonical
  * affine.  Host pointers, borrowed.  On the reference's prove path G2 is data (the verifier's pairing consumes g2 and s_g2); the one G2
- * computation is gen_srs's s_g2 = [s] g2 (/root/reference/src/pfsys/srs.rs:14-16 -> ParamsKZG::setup), i.e. n = 1.  A plain
- * double-and-add per pair with a tree fold: not a Pippenger pipeline, not a hot path. */
+ * computation is gen_srs's s_g2 = [s] g2 (/root/reference/src/pfsys/srs.rs:14-16 -> ParamsKZG::setup), i.e. n = 1.  Below MSM_G2_CROSSOVER
+ * points (csrc/msm_plan.hpp) a plain double-and-add per pair with a tree fold; from there on the points and scalars are uploaded and summed by
+ * the bucket chain of ezkl_hip_msm_g2_points_dev.  The 128 bytes are the same on either side.  n = 0 writes (0, 0). */
 int ezkl_hip_msm_g2(const void* points_affine, const void* scalars, size_t n, void* out_affine);
+/* the same over n RESIDENT points and scalars, by a signed-digit bucket method (csrc/g2.hip, DESIGN.md §4.1 "G2 MSM"): the sort front end
+ * of the table-free G1 chain, then G2 kernels that accumulate the buckets, reduce them per window and fold the windows and normalise on the
+ * device.  points_dev: n x 128 B records in the SRS tail's layout, (0, 0) = identity, 16-byte aligned, read and never written; scalars_dev:
+ * n x 32 B Montgomery Fr; out_affine: HOST memory, 128 B canonical affine, (0, 0) for the identity.  Returns after the stream has drained.
+ * n = 0 and a null pointer are EZKL_ERR_INVALID.  Scratch is kept between calls (grown on demand, no allocation in steady state).  HIP
+ * events around the device work: ezkl_hip_last_kernel_ms("msm_g2"). */
+int ezkl_hip_msm_g2_points_dev(const void* points_dev, const void* scalars_dev, size_t n, void* out_affine, void* stream);
 /* sum_i scalars[i] * bases[offset + i], i < n.  scalars: n x 32 B Montgomery Fr (host pointer, borrowed).
  * out_affine: 64 B, caller-allocated, canonical affine ((0,0) if the sum is the identity). */
 int ezkl_hip_msm_g1(ezkl_bases_t h, const void* scalars, size_t n, void* out_affine);
