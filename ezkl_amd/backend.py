@@ -553,6 +553,19 @@ def msm_g2_points(points, scalars, n=None, stream=None):
     return out
 
 
+# csrc/msm_plan.hpp, held equal to it by tests/test_fixed_base_cpu.py: the comb's window width, and the n from which
+# ezkl_hip_bases_from_scalars takes the comb
+G1_FIXED_C = 10
+G1_FIXED_CROSSOVER = 2
+
+
+def g1_fixed_base(base_point, scalars_ptr, n, out_ptr, stream=None):
+    """out[i] = scalars[i] * base_point by the windowed comb: base_point (8,) u64 affine on the host, scalars_ptr n resident Montgomery Fr,
+    out_ptr n x 64 resident bytes (ezkl_hip_g1_fixed_base_dev)"""
+    _l.check(_l.load().ezkl_hip_g1_fixed_base_dev(_p(_fe(base_point, 8)), _vp(scalars_ptr), C.c_size_t(int(n)), _vp(out_ptr), _stream_ptr(stream)),
+             "ezkl_hip_g1_fixed_base_dev")
+
+
 def g1_add_affine(a, b):
     a, b = _fe(a, 8), _fe(b, 8)
     out = np.zeros(8, np.uint64)

@@ -1,5 +1,6 @@
 // capi.hip -- the extern "C" surface of libezkl_hip.so (include/ezkl_hip.h) and the library context.
 #include "common.hpp"
+#include "msm_plan.hpp"
 #include <string.h>
 #include <atomic>
 #include <algorithm>
@@ -667,13 +668,31 @@ int ezkl_hip_g1_decompress_form_dev(const void* compressed_dev, size_t n, int fo
     EZ_CTX(c);
     return g1_decompress(c, c->stream, compressed_dev, n, out_pts_dev, form, bad_index, reason);
 }
+// the comb (g1_fixed.hip) under the region name of the call it serves, so that "bases_from_scalars" is the kernel time at every n
+static int from_scalars_comb(Ctx* c, const void* base_point, const fe_t* scalars_dev, size_t n, void* out_dev) {
+    hipEvent_t e0, e1;
+    int rc = ev_pair(c, "bases_from_scalars", &e0, &e1);
+    if (rc) return rc;
+    EZ_HIP(hipEventRecord(e0, c->stream));
+    if ((rc = g1_fixed_base(c, c->stream, base_point, scalars_dev, n, out_dev))) return rc;
+    EZ_HIP(hipEventRecord(e1, c->stream));
+    return EZKL_OK;
+}
+int ezkl_hip_g1_fixed_base_dev(const void* base_point, const void* scalars_dev, size_t n, void* out_pts_dev, void* stream) {
+    if (!base_point || !scalars_dev || !out_pts_dev || n == 0 || ((uintptr_t)out_pts_dev & 15) || ((uintptr_t)scalars_dev & 15)) return EZKL_ERR_INVALID;
+    EZ_CTX(c);
+    hipStream_t st = pick_stream(c, stream);
+    int rc = g1_fixed_base(c, st, base_point, (const fe_t*)scalars_dev, n, out_pts_dev);
+    return rc ? rc : finish(c, st, stream);
+}
 int ezkl_hip_bases_from_scalars(const void* base_point, const void* scalars_dev, size_t n, ezkl_bases_t* out) {
     if (!base_point || !scalars_dev || !out || n == 0) return EZKL_ERR_INVALID;
     EZ_CTX(c);
     Bases* b = new Bases();
     b->n = n;
     EZ_HIP(hipMalloc(&b->pts, n * 64));
-    int rc = g1_mul_fixed(c, c->stream, base_point, (const fe_t*)scalars_dev, n, b->pts);
+    int rc = n >= G1_FIXED_CROSSOVER ? from_scalars_comb(c, base_point, (const fe_t*)scalars_dev, n, b->pts)
+                                     : g1_mul_fixed(c, c->stream, base_point, (const fe_t*)scalars_dev, n, b->pts);
     if (!rc) {
         hipError_t e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = set_hip_error(e, "g1_mul_fixed", __FILE__, __LINE__);

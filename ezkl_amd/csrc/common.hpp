@@ -181,6 +181,7 @@ bool msm_table_exists(const Bases* b);
 void msm_table_drop(const Bases* b);
 int msm_table_prepare(Ctx* c, const Bases* b);
 int g1_mul_fixed(Ctx* c, hipStream_t st, const void* base_host, const fe_t* scalars, size_t n, void* out_dev);
+int g1_fixed_base(Ctx* c, hipStream_t st, const void* base_host, const fe_t* scalars, size_t n, void* out_dev);
 int g1_mul_rows(Ctx* c, hipStream_t st, const void* pts_dev, const fe_t* scalars, size_t n, void* out_dev);
 int g1_check(Ctx* c, hipStream_t st, const void* pts_dev, size_t first, size_t n, uint64_t out[4]);
 int g1_decompress(Ctx* c, hipStream_t st, const void* in_dev, size_t n, void* out_dev, int form, uint64_t* bad_index, int* reason);

@@ -285,6 +285,17 @@ static constexpr uint32_t MSM_G2_LONG_THREADS = 128;                 // lanes th
 // doublings + ~127 additions every lane of the double-and-add kernel runs; 17.7 against 943 ms at 2^16).  Nothing below 2^4 was measured,
 // and the n = 1 of gen_srs / update_srs stays where it was.
 static constexpr size_t MSM_G2_CROSSOVER = 16;
+// The fixed-base comb (g1_fixed.hip): window width c and W = ceil(254 / c) windows of a table of W * 2^(c-1) affine records.  MEASURED over
+// c = 6 .. 10 (tools/fixed_base_bench.py on builds of each, one sitting): at 2^20 scalars 7.3, 6.9, 6.2 - 6.4, 6.2 and 5.9 ms,
+// at 2^16 all within 2.39 - 2.50 ms (the table's serial doubling chain, 1.9 ms at every c, is most of it).  c = 10; the runner-up is c = 8.
+static constexpr uint32_t G1_FIXED_C = 10;
+static constexpr uint32_t G1_FIXED_WINDOWS = (254 + G1_FIXED_C - 1) / G1_FIXED_C;
+// ezkl_hip_bases_from_scalars: from this n on the comb, table build included, below it the double-and-add kernel.  MEASURED
+// (profiles/mi355x_fixed_base.json): the comb is the faster one at every power of two that was tried, n = 1 included (2.4 against 2.9 ms:
+// a lone lane's 250 doublings for the table against its ~254 doublings and ~127 additions).  The constant stops at 2, not 1: one product
+// is 0.5 ms slower than it could be, and the double-and-add kernel keeps a size of its own, so that the two kernels stay held to the
+// same bytes on either side of the switch.
+static constexpr size_t G1_FIXED_CROSSOVER = 2;
 inline WinPlan pick_plan_g2(size_t n) {
     WinPlan best{0, 0, 0};
     double best_cost = 0;

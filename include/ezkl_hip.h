@@ -187,15 +187,17 @@ int ezkl_hip_bases_compress(ezkl_bases_t h, void* out_host /* n x 32 B */);
 int ezkl_hip_g1_decompress_form_dev(const void* compressed_dev, size_t n, int form, void* out_pts_dev, uint64_t* bad_index, int* reason);
 /* base set bases[i] = scalars[i] * P for one point P (64 B affine, host) and n resident Montgomery scalars: SRS
  * generation for tests (gen_srs -> ParamsKZG::setup, /root/reference/src/pfsys/srs.rs:14-16): g[i] = s^i G,
- * g_lagrange[i] = L_i(s) G */
+ * g_lagrange[i] = L_i(s) G.  From G1_FIXED_CROSSOVER scalars on (csrc/msm_plan.hpp) by the comb of ezkl_hip_g1_fixed_base_dev, below it
+ * by a double-and-add per lane; the records are the same bytes either way. */
 int ezkl_hip_bases_from_scalars(const void* base_point, const void* scalars_dev, size_t n, ezkl_bases_t* out_handle);
 /* per-row product: a NEW resident set of n points, out[i] = scalars[i] * in[first + i], for n resident Montgomery scalars laid out as
  * ezkl_hip_bases_from_scalars takes them (n x 32 B).  The step of an SRS update, g'[i] = t^i g[i] (backend.update_srs).
  * Output records are canonical affine; the identity -- an identity input, a zero scalar -- is the all-zero record.  first + n beyond the
  * set: EZKL_ERR_INVALID.  n = 0: EZKL_ERR_INVALID as well, since a base-set handle cannot be empty (ezkl_hip_bases_upload refuses
  * n = 0 too).  Reads the records the handle holds, never the window tables (and builds none); `in` is unchanged and nothing is kept
- * across calls.  One kernel, one lane per point, the double-and-add of ezkl_hip_bases_from_scalars with the point in vector registers,
- * 43.6 ms for 2^20 points on an MI355X, level with that call at the same n;
+ * across calls.  One kernel, one lane per point, the double-and-add kernel of ezkl_hip_bases_from_scalars with the point in vector
+ * registers, 43.6 ms for 2^20 points on an MI355X, level with THAT kernel at the same n (ezkl_hip_bases_from_scalars itself
+ * takes the comb of ezkl_hip_g1_fixed_base_dev from G1_FIXED_CROSSOVER scalars on and is about seven times faster at that n);
  * HIP events around it: ezkl_hip_last_kernel_ms("bases_mul_scalars") (and "bases_from_scalars" for the call above). */
 int ezkl_hip_bases_mul_scalars(ezkl_bases_t in, const void* scalars_dev, size_t first, size_t n, ezkl_bases_t* out_handle);
 /* ParamsKZG::downsize(new_k) -- halo2; called by load_params_prover (/root/reference/src/execute.rs:1739-1750) whenever the SRS file is
@@ -204,6 +206,15 @@ int ezkl_hip_bases_mul_scalars(ezkl_bases_t in, const void* scalars_dev, size_t 
  * halo2's g_to_lagrange does: an inverse NTT over G1 (omega^-1 butterflies on group elements, scaled by 1 / 2^new_k).  New handles,
  * freed with ezkl_hip_bases_free. */
 int ezkl_hip_bases_downsize(ezkl_bases_t g, uint32_t new_k, ezkl_bases_t* out_g, ezkl_bases_t* out_g_lagrange);
+/* out[i] = scalars[i] * P for ONE point P by a windowed comb (csrc/g1_fixed.hip, DESIGN.md §4.1 "Fixed-base products"): a table of the
+ * signed window multiples d 2^(c w) P is built once per call, each scalar then costs at most ceil(254 / c) mixed additions and no doubling,
+ * and the lanes of a workgroup share one field inversion on the way back to affine.  base_point: 64 B affine Montgomery record in HOST
+ * memory, (0, 0) = the identity; scalars_dev: n x 32 B Montgomery Fr, resident; out_pts_dev: n x 64 B, resident; both 16-byte aligned (or EZKL_ERR_INVALID); written
+ * asynchronously on `stream` (NULL: the library stream).  The records are canonical affine, the identity -- a zero scalar, an identity P --
+ * all zero: the bytes ezkl_hip_bases_from_scalars gives, which takes this path from G1_FIXED_CROSSOVER scalars on (csrc/msm_plan.hpp).
+ * Makes no base-set handle.  n = 0 and a null pointer are EZKL_ERR_INVALID.  The table lives in scratch the library keeps between calls.
+ * HIP events around the table and the comb: ezkl_hip_last_kernel_ms("fixed_base"), around the table alone ("fixed_base_table"). */
+int ezkl_hip_g1_fixed_base_dev(const void* base_point, const void* scalars_dev, size_t n, void* out_pts_dev, void* stream);
 /* sum_i scalars[i] * points[i] over G2 (the twist over Fq2).  points: n x 128 B affine -- x.c0, x.c1, y.c0, y.c1 as 32-byte little-endian
  * Montgomery Fq, the layout of the g2 / s_g2 tail of an SRS file, (0, 0) = identity; scalars: n x 32 B Montgomery Fr; out: 128 B canonical
  * affine.  Host pointers, borrowed.  On the reference's prove path G2 is data (the verifier's pairing consumes g2 and s_g2); the one G2
