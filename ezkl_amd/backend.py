@@ -540,13 +540,50 @@ MSM_G2_CROSSOVER = 16
 MSM_G2_SORT_TILE = 1024
 
 
-def msm_g2_points(points, scalars, n=None, stream=None):
+# why ezkl_hip_g2_check_dev refuses a record (csrc/g2.hip)
+G2_POINT_REASONS = {1: "coordinate not below the field modulus", 2: "point not on the curve", 3: "point not in the subgroup"}
+
+
+class G2PointError(ValueError):
+    """a G2 record that must not be used: .index in its set, .reason (G2_POINT_REASONS' words), .report (g2_check_points)"""
+
+    def __init__(self, name, report):
+        super().__init__("%s[%d]: %s" % (name, report["index"], report["reason"]))
+        self.name, self.index, self.reason, self.report = name, report["index"], report["reason"], report
+
+
+def g2_check_points(points, n=None, stream=None):
+    """is every 128-byte record a point of G2 -- canonical, on the twist, of order r?  points: a DeviceBuffer of resident records (n
+    defaults to all it holds), or an (n, 16) u64 array, uploaded for the call -> dict(bad: how many are not, index: the smallest such index
+    or None, reason: why that one is refused, in G2_POINT_REASONS' words, or None, identities: all-zero records, which are valid)
+    (ezkl_hip_g2_check_dev)"""
+    own = None
+    if not hasattr(points, "ptr") and not isinstance(points, int):           # an int is a device address, as msm_g2_points takes one (n given)
+        own = points = DeviceBuffer.from_numpy(_fe(points, 16))
+    try:
+        n = points.nbytes // 128 if n is None else int(n)
+        out = np.zeros(4, np.uint64)
+        _l.check(_l.load().ezkl_hip_g2_check_dev(_vp(getattr(points, "ptr", points)), C.c_size_t(n), _p(out), _stream_ptr(stream)),
+                 "ezkl_hip_g2_check_dev")
+    finally:
+        if own is not None:
+            own.free()
+    bad = int(out[0])
+    return dict(bad=bad, index=int(out[1]) if bad else None, reason=G2_POINT_REASONS[int(out[2])] if bad else None, identities=int(out[3]))
+
+
+def msm_g2_points(points, scalars, n=None, stream=None, check=False):
     """sum_i scalars[i] * points[i] over G2 on resident data: points a DeviceBuffer of n 128-byte affine records (the SRS tail's layout),
-    scalars a DeviceBuffer of n Montgomery Fr -> (16,) u64 affine (ezkl_hip_msm_g2_points_dev; n defaults to what `scalars` holds)"""
+    scalars a DeviceBuffer of n Montgomery Fr -> (16,) u64 affine (ezkl_hip_msm_g2_points_dev; n defaults to what `scalars` holds).
+    check=True puts the records through g2_check_points first and raises G2PointError ("g2[513]: point not in the subgroup") on a bad one."""
     if n is None:
         n = scalars.nbytes // 32
         if points.nbytes // 128 != n:
             raise ValueError("one scalar per point")
+    if check:
+        found = g2_check_points(points, n, stream)
+        if found["bad"]:
+            raise G2PointError("g2", found)
     out = np.zeros(16, np.uint64)
     _l.check(_l.load().ezkl_hip_msm_g2_points_dev(_vp(getattr(points, "ptr", points)), _vp(getattr(scalars, "ptr", scalars)), C.c_size_t(int(n)),
                                                    _p(out), _stream_ptr(stream)), "ezkl_hip_msm_g2_points_dev")

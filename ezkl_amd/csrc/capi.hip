@@ -781,6 +781,11 @@ int ezkl_hip_msm_g2_points_dev(const void* points_dev, const void* scalars_dev, 
     EZ_CTX(c);
     return g2_msm_points_run(c, pick_stream(c, stream), points_dev, (const fe_t*)scalars_dev, n, out);
 }
+int ezkl_hip_g2_check_dev(const void* points_dev, size_t n, uint64_t out[4], void* stream) {
+    if (!points_dev || !out || n == 0 || ((uintptr_t)points_dev & 15)) return EZKL_ERR_INVALID;
+    EZ_CTX(c);
+    return g2_check(c, pick_stream(c, stream), points_dev, n, out);
+}
 size_t ezkl_hip_bases_len(ezkl_bases_t h) { return h ? reinterpret_cast<Bases*>(h)->n : 0; }
 
 int ezkl_hip_msm_g1_dev(ezkl_bases_t h, size_t base_offset, const void* scalars_dev, size_t n, void* out, void* stream) {

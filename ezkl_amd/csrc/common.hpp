@@ -191,6 +191,7 @@ int g1_to_lagrange(Ctx* c, hipStream_t st, const void* g_dev, uint32_t log_n, fe
 void g1_add_affine_host(const void* a, const void* b, void* out);
 int g2_msm(Ctx* c, hipStream_t st, const void* pts_host, const void* scalars_host, size_t n, void* out_host);
 int g2_msm_points_run(Ctx* c, hipStream_t st, const void* pts_dev, const fe_t* scalars_dev, size_t n, void* out_host);
+int g2_check(Ctx* c, hipStream_t st, const void* pts_dev, size_t n, uint64_t out[4]);
 struct WinPlan;
 struct MsmPlan;
 struct MsmG2Plan;

@@ -403,6 +403,136 @@ int g2_msm_points_run(Ctx* c, hipStream_t st, const void* pts_dev, const fe_t* s
     return EZKL_OK;
 }
 
+// ---- is every record of a resident set a point of G2?  (DESIGN.md §4.1 "G2 set check") ------------------------------------------------
+// The twist's group E'(Fq2) has order r (2q - r): a record can be canonical and on the curve and still have an order other than r, and a
+// sum or a pairing over it means nothing.  Per record, the first that applies:
+//   1  one of the four coordinate words >= q        2  y^2 != x^3 + 3 / xi        3  on the twist, not of order r
+// and the all-zero record is the identity: valid, counted apart (what g2x_add_mixed skips).  The order test is not [r]P: with
+// psi = twist . Frobenius . untwist, psi(x, y) = (conj(x) xi^((q-1)/3), conj(y) xi^((q-1)/2)), and the BN parameter x,
+//     [x + 1]P + psi([x]P) + psi^2([x]P) == psi^3([2x]P)
+// holds exactly for the points of order r (DESIGN.md says why).  ONE 63-bit product A = [x]P; the rest is Horner in psi,
+//     T = psi(A + psi(A - psi(2A))) = psi(A) + psi^2(A) - psi^3(2A),        L = A + P,        valid  <=>  L == -T,
+// three maps, a doubling and three additions, the comparison cross-multiplied (no inversion).  psi acts on XYZZ coordinate by coordinate
+// (conjugation is a field automorphism, so ZZ^3 = ZZZ^2 survives): two constant products, and the two constants come from
+// tools/gen_constants.py like the twist's b.  x is a constant: its signed digits (non-adjacent form, read off 3x and x: 24 non-zero ones
+// against 28 set bits) steer one loop whose branches are uniform, 62 doublings and 23 mixed additions of +-P, the same for every lane.
+struct G2Const {
+    static constexpr uint32_t B0[8] = BN32_FQ2_TWIST_B_C0_INIT, B1[8] = BN32_FQ2_TWIST_B_C1_INIT;
+    static constexpr uint32_t PX0[8] = BN32_FQ2_PSI_X_C0_INIT, PX1[8] = BN32_FQ2_PSI_X_C1_INIT;
+    static constexpr uint32_t PY0[8] = BN32_FQ2_PSI_Y_C0_INIT, PY1[8] = BN32_FQ2_PSI_Y_C1_INIT;
+};
+constexpr uint64_t BN_X = 4965661367192848881ull;
+constexpr uint64_t BN_X_POS = ((3 * BN_X) & ~BN_X) >> 1, BN_X_NEG = (~(3 * BN_X) & BN_X) >> 1;     // digit b of x is +1 / -1 where bit b is set
+static_assert(BN_X < (1ull << 63) / 3 * 2 && BN_X_POS - BN_X_NEG == BN_X && (BN_X_POS >> 62) == 1, "3x fits 64 bits; the top digit is +1 at 2^62");
+enum : uint32_t { G2_OK = 0, G2_NOT_CANONICAL = 1, G2_OFF_CURVE = 2, G2_OFF_SUBGROUP = 3 };
+
+EZ_D fq2_t f2_const(const uint32_t (&c0)[8], const uint32_t (&c1)[8]) { return fq2_t{fr_const(c0), fr_const(c1)}; }
+EZ_D bool f2_eq(const fq2_t& x, const fq2_t& y) { return Fq::eq(x.a, y.a) && Fq::eq(x.b, y.b); }
+EZ_D fq2_t f2_conj(const fq2_t& x) { return fq2_t{x.a, Fq::neg(x.b)}; }
+EZ_D g2x_t g2x_psi(const g2x_t& p) {
+    return g2x_t{f2_mul(f2_conj(p.x), f2_const(G2Const::PX0, G2Const::PX1)), f2_mul(f2_conj(p.y), f2_const(G2Const::PY0, G2Const::PY1)),
+                 f2_conj(p.zz), f2_conj(p.zzz)};
+}
+EZ_D bool fe_ge_q(const fe_t& a) {                                       // a >= q as 256-bit integers: a - q leaves no borrow
+    uint32_t br = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) (void)subb32(a.v[i], FqP::MOD[i], br);
+    return br == 0;
+}
+// p is on the twist and not the identity: is it of order r?
+EZ_D bool g2_has_order_r(const g2a_t& p) {
+    g2x_t A{p.x, p.y, f2_one(), f2_one()};
+#pragma unroll 1
+    for (int b = 61; b >= 0; b--) {
+        A = g2x_double(A);
+        if (((BN_X_POS | BN_X_NEG) >> b) & 1) A = g2x_add_mixed(A, p, (BN_X_NEG >> b) & 1);
+    }
+    g2x_t T = g2x_psi(g2x_double(A));
+    T.y = f2_neg(T.y);
+    T = g2x_psi(g2x_add(A, T));
+    T = g2x_psi(g2x_add(A, T));
+    const g2x_t L = g2x_add_mixed(A, p, false);
+    if (g2x_is_id(L) || g2x_is_id(T)) return g2x_is_id(L) && g2x_is_id(T);
+    return f2_eq(f2_mul(L.x, T.zz), f2_mul(T.x, L.zz)) && f2_eq(f2_mul(L.y, T.zzz), f2_neg(f2_mul(T.y, L.zzz)));
+}
+EZ_D uint32_t g2_point_reason(const g2a_t& p, bool* identity) {
+    *identity = f2_is_zero(p.x) && f2_is_zero(p.y);
+    if (*identity) return G2_OK;
+    if (fe_ge_q(p.x.a) || fe_ge_q(p.x.b) || fe_ge_q(p.y.a) || fe_ge_q(p.y.b)) return G2_NOT_CANONICAL;
+    const fq2_t rhs = f2_add(f2_mul(f2_sqr(p.x), p.x), f2_const(G2Const::B0, G2Const::B1));
+    if (!f2_eq(f2_sqr(p.y), rhs)) return G2_OFF_CURVE;
+    return g2_has_order_r(p) ? G2_OK : G2_OFF_SUBGROUP;
+}
+// One lane per point in XYZZ, G2_CHECK_THREADS lanes a workgroup, at most one workgroup per CU, each lane striding over the set with its
+// next record's eight loads issued before this record's ~2 200 products.  ONE wave per SIMD: the accumulator, the record, the next record
+// and the temporaries of an XYZZ + XYZZ addition over Fq2 take 256 VGPRs and 64 AGPRs and no scratch; held to the 168 registers of three
+// waves per SIMD the compiler moves 892 registers through 1 280 bytes of scratch per lane.  The outputs are g1_check_kernel's:
+// acc[0] += bad points, acc[1] = min over bad points of (index << 2 | reason), acc[2] += identities -- two sums and a minimum, so the answer
+// does not depend on the order the waves arrive in; counts are wave ballots (a lane that has left the loop votes 0), a wave touches memory
+// only if it has something to report, with vector atomics.  Any bytes are legal input: the predicate branches on them, never indexes by them.
+constexpr unsigned G2_CHECK_THREADS = 256;
+__global__ __launch_bounds__(G2_CHECK_THREADS) void g2_check_kernel(const g2a_t* pts, size_t n, unsigned long long* acc) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long key = ~0ull;
+    uint32_t n_bad = 0, n_id = 0;
+    g2a_t next;
+    if (i < n) next = ld_g2a(pts + i);
+    while (i < n) {
+        const g2a_t p = next;
+        if (i + stride < n) next = ld_g2a(pts + i + stride);
+        bool id;
+        const uint32_t reason = g2_point_reason(p, &id);
+        n_bad += reason != 0;
+        n_id += id;
+        if (reason) {
+            const unsigned long long k = ((unsigned long long)i << 2) | reason;
+            key = k < key ? k : key;
+        }
+        i += stride;
+    }
+    // lanes leave the loop at different trips, so the counts are per lane and summed across the wave here
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+        const unsigned long long o = __shfl_xor(key, off);
+        key = o < key ? o : key;
+        n_bad += __shfl_xor(n_bad, off);
+        n_id += __shfl_xor(n_id, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (n_bad) {
+            atomicAdd(acc, (unsigned long long)n_bad);
+            atomicMin(acc + 1, key);
+        }
+        if (n_id) atomicAdd(acc + 2, (unsigned long long)n_id);
+    }
+}
+// out: {bad points, smallest bad index or UINT64_MAX, its reason, identities}; returns after `st` has drained
+int g2_check(Ctx* c, hipStream_t st, const void* pts_dev, size_t n, uint64_t out[4]) {
+    out[0] = 0; out[1] = UINT64_MAX; out[2] = 0; out[3] = 0;
+    if (n == 0) return EZKL_ERR_INVALID;
+    unsigned long long* acc = nullptr;
+    int rc = arena_reserve(c->aux, 32, st, (void**)&acc);
+    if (rc) return rc;
+    hipEvent_t e0, e1;
+    if ((rc = ev_pair(c, "g2_check", &e0, &e1))) return rc;
+    EZ_HIP(hipMemsetAsync(acc, 0, 32, st));
+    EZ_HIP(hipMemsetAsync(acc + 1, 0xff, 8, st));
+    const unsigned blocks = std::min<size_t>(cdiv(n, G2_CHECK_THREADS), (size_t)std::max(c->num_cus, 1));
+    EZ_HIP(hipEventRecord(e0, st));
+    hipLaunchKernelGGL(g2_check_kernel, dim3(blocks), dim3(G2_CHECK_THREADS), 0, st, (const g2a_t*)pts_dev, n, acc);
+    EZ_HIP(hipGetLastError());
+    EZ_HIP(hipEventRecord(e1, st));
+    unsigned long long host[3] = {0, 0, 0};
+    EZ_HIP(hipMemcpyAsync(host, acc, sizeof host, hipMemcpyDeviceToHost, st));
+    if ((rc = arena_done(c->aux, st))) return rc;
+    EZ_HIP(hipStreamSynchronize(st));
+    out[0] = host[0];
+    out[3] = host[2];
+    if (host[1] != ~0ull) { out[1] = host[1] >> 2; out[2] = host[1] & 3; }
+    return EZKL_OK;
+}
+
 int g2_msm(Ctx* c, hipStream_t st, const void* pts_host, const void* scalars_host, size_t n, void* out_host) {
     if (n == 0) { memset(out_host, 0, 128); return EZKL_OK; }
     g2a_t *d_pts = nullptr, *d_out = nullptr;

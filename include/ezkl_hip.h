@@ -229,6 +229,14 @@ int ezkl_hip_msm_g2(const void* points_affine, const void* scalars, size_t n, vo
  * n = 0 and a null pointer are EZKL_ERR_INVALID.  Scratch is kept between calls (grown on demand, no allocation in steady state).  HIP
  * events around the device work: ezkl_hip_last_kernel_ms("msm_g2"). */
 int ezkl_hip_msm_g2_points_dev(const void* points_dev, const void* scalars_dev, size_t n, void* out_affine, void* stream);
+/* Is every one of n RESIDENT 128-byte records (the layout above, 16-byte aligned, read and never written) a point of G2?  Per record, the
+ * first that applies: reason 1 = a coordinate word >= q (not canonical), 2 = y^2 != x^3 + 3 / xi (not on the curve), 3 = on the curve
+ * but not of order r (not in the subgroup: the twist has a cofactor, unlike G1); the all-zero record is the identity, valid and counted
+ * apart.  out[0] = invalid points, out[1] = the smallest invalid index (valid when out[0] > 0, else UINT64_MAX), out[2] = the reason of
+ * that point, out[3] = identities.  One kernel, a lane per point; the order test is one product by the 63-bit BN parameter and three
+ * maps of the endomorphism psi, not a product by r (csrc/g2.hip, DESIGN.md §4.1 "G2 set check").  Returns after the stream has drained.
+ * A null pointer, n = 0 and a misaligned points_dev are EZKL_ERR_INVALID.  HIP events around the kernel: ezkl_hip_last_kernel_ms("g2_check"). */
+int ezkl_hip_g2_check_dev(const void* points_dev, size_t n, uint64_t out[4], void* stream);
 /* sum_i scalars[i] * bases[offset + i], i < n.  scalars: n x 32 B Montgomery Fr (host pointer, borrowed).
  * out_affine: 64 B, caller-allocated, canonical affine ((0,0) if the sum is the identity). */
 int ezkl_hip_msm_g1(ezkl_bases_t h, const void* scalars, size_t n, void* out_affine);
